@@ -5,17 +5,27 @@ initialisation (random weights of the real architecture).
 
     python bench.py --gpus N --steps K --warmup W            (N > 1: starts its own N rank processes, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --full                               (also everything beside the headline: several minutes)
+    python bench.py ... --dump-outputs DIR                   (the timed trainer's last-step outputs as DIR/*.npy)
+
+A plain run measures the headline only: set-up, prewarm, W warm-up steps, K timed steps (eager, and at N = 1 also
+replayed from a captured HIP graph: `value` is the faster, timing.mode names it), the outputs if asked for, the line.
+--full adds the in-run accuracy schedule, `other_configs`, `cpu_baseline`, the side lines and, at N > 1, north_star's
+split and the `comm` block. The timed trainers take exactly W + K steps from a fixed seed (the prewarm runs on a
+throwaway trainer), so that two runs with the same arguments compute the same thing.
 
 One step = sample x ~ N(0, 16^2 I) on the device -> operator forward (5 stencil evaluations of the
 16-headed MLP + FD Hamiltonian) -> EVD loss -> backward -> RMSprop(+cosine LR) -> EMA, all HIP kernels.
 N > 1: samples sharded (dp), every rank draws its own 512 rows (weak scaling, global batch 512 N), one
 all-reduce of the 2L^2+1 moment floats and a bucketed exchange of the flat gradient per step over RCCL (the exchange
 algorithm - all-reduce or reduce-scatter / all-gather, with or without head windows of the backward - is timed briefly
-and the fastest one takes the headline run: `comm.candidates`); the `comm` block carries the exposed wait of every
-collective (events on the compute stream) and the same step with the collectives skipped (`compute_only_ms`); the
-head-sharded split (hp) and configs[2] are timed beside it as side fields of the same JSON line.
-Timing: a declared prewarm (>= 1 s of real steps, whatever the step arguments), W warm-up steps, then several
-blocks of EXACTLY K steps (barrier + synchronize on both sides, max over ranks); `value` is the median block.
+and the fastest one takes the headline run); with --full the `comm` block carries the tuner's table
+(`comm.candidates`), the exposed wait of every collective (events on the compute stream) and the same step with the
+collectives skipped (`compute_only_ms`), and the other sharding and configs[2] are timed beside it as side fields of
+the same JSON line.
+Timing: a declared prewarm (>= 1 s of real steps, whatever the step arguments), W warm-up steps, then one block
+(--repeats: several) of EXACTLY K steps (barrier + synchronize on both sides, max over ranks); `value` is the median
+block.
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -187,12 +197,13 @@ class GraphStepper:
             self.pending = 0
 
 
-def run_timed_graph(tr, steps, warmup, repeats, prewarm_s):
-    """run_timed's protocol with the steps replayed from a HIP graph (single GPU)"""
-    g = GraphStepper(tr)
+def run_timed_graph(tr, steps, warmup, repeats, prewarm_s, stepper=None):
+    """run_timed's protocol with the steps replayed from a HIP graph (single GPU); prewarm_s None: no prewarm;
+    stepper: a GraphStepper of `tr` captured beforehand"""
+    g = stepper or GraphStepper(tr)
     t0 = time.perf_counter()
     n_pre = 0
-    while True:
+    while prewarm_s is not None:
         g.gs.replay(25)
         n_pre += 50
         torch.cuda.synchronize()
@@ -255,11 +266,12 @@ def run_timed(tr, comm, steps, warmup, repeats, prewarm_s, events_every=0):
     """prewarm (>= prewarm_s seconds of real steps: the GPU clock ramp and every lazy allocation are behind us
     whatever --steps/--warmup are), `warmup` untimed steps, then `repeats` blocks of EXACTLY `steps` steps, each
     bracketed by barrier + synchronize on both sides and reduced with MAX over ranks. Returns the per-block
-    seconds, the bracketed kernel durations (ms) and the prewarm actually spent."""
+    seconds, the bracketed kernel durations (ms) and the prewarm actually spent. prewarm_s None: no prewarm (the
+    caller has run one: prewarm())."""
     from neural_svd_amd import hip_ops as H
     t0 = time.perf_counter()
     n_pre = 0
-    while True:
+    while prewarm_s is not None:
         for _ in range(50):
             tr.step()
         n_pre += 50
@@ -293,6 +305,51 @@ def run_timed(tr, comm, steps, warmup, repeats, prewarm_s, events_every=0):
         blocks.append(comm.max_float(el) if comm is not None else el)
     kms = sorted(a.elapsed_time(b) for a, b in ev)
     return blocks, kms, prewarm, n_pre
+
+
+def prewarm(cfg, par, comm, dev, path, seconds, **kw):
+    """>= `seconds` of real steps on a throwaway trainer of the timed configuration: the GPU clock ramp and every
+    first-use cost are behind us, while the timed trainers take a fixed number of steps (warm-up + timed), so that what
+    they compute is the same from run to run. -> (seconds spent, steps)"""
+    t, _, _ = make_trainer(cfg, par, comm, dev, path, **kw)
+    _, _, spent, n = run_timed(t, comm, 0, 0, 0, seconds)
+    del t
+    return spent, n
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each (name, tensor) as out_dir/<name>.npy, float32 (float64 stays float64). An array that would
+    take the total past DUMP_BYTES is written as a fixed, seeded sample of its flattened elements, with their flat
+    indices beside it (<name>_index.npy, float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BYTES
+    for name, t in arrays:
+        a = t.detach().cpu().numpy()
+        if a.dtype != np.float64:
+            a = a.astype(np.float32)
+        left -= 128  # the .npy header
+        if a.nbytes > left:
+            left -= 128
+            n = max(0, min(a.size, left // (a.itemsize + 8)))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+            left -= idx.size * 8
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        left -= a.nbytes
+
+
+def trainer_outputs(tr):
+    """what a caller of the training step receives after its last step: the loss vector {loss, operator term,
+    metric term}, f and Tf of the step's batch, the trainable parameters and their EMA shadow (flattened in state_dict
+    order)"""
+    P = tr.P
+    flat = lambda buf: torch.cat([v.reshape(-1) for v in P.views(buf)])  # noqa: E731
+    return [("loss", tr.loss), ("f", tr.f_g), ("Tf", tr.Tf_g), ("params", flat(P.flat)), ("ema_params", flat(P.ema))]
 
 
 def summarize(blocks, steps, world, batch=None):
@@ -614,7 +671,8 @@ def bench_widened(args, as_dict=False):
     blocks, kms, n_pre = _timed_blocks(step, steps, warmup, repeats, args.prewarm_seconds,
                                        H.profile_next_forward if use_ev else None, comm=comm)
     summ = summarize(blocks, steps, 1 if strong else world)
-    if comm is not None:  # where the sharded step's time goes: the exposed collectives, and the step without them
+    if comm is not None and args.full:
+        # where the sharded step's time goes: the exposed collectives, and the step without them
         fk.probe = parallel.CommProbe(dev)
         for _ in range(50):
             step()
@@ -838,8 +896,18 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=None,
-                    help="timed blocks of --steps steps each (median reported); default: about 6000 timed steps in "
-                         "total, between 3 and 25 blocks")
+                    help="timed blocks of --steps steps each (median reported); default: one block, so --steps is the "
+                         "number of timed steps (the --full side measurements: about 6000 timed steps in total, "
+                         "between 3 and 25 blocks)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the in-run accuracy schedule, other_configs, the CPU "
+                         "baseline, the side lines (bf16x3, other shardings, configs[2]), north_star's split and the "
+                         "comm block at N > 1, the per-step loss-sync mode (several minutes); default: the headline "
+                         "only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed trainer computed in its last step as "
+                         "DIR/<name>.npy (loss, f, Tf, params, ema_params; float32, at most 64 MB); same arguments, "
+                         "same inputs")
     ap.add_argument("--prewarm-seconds", type=float, default=1.0,
                     help="real steps run before --warmup, independent of the step arguments (clock ramp)")
     ap.add_argument("--path", default="auto", choices=["auto", "generic", "fused", "bf16x3"],
@@ -886,7 +954,7 @@ def main():
     ap.add_argument("--accuracy", default="auto", choices=["auto", "on", "off"],
                     help="N = 1, headline workload: run the reference's full 500 000-step schedule and its 10^6-point "
                          "evaluation in this run (about 2.5 minutes) and report rel_eigenvalue_error as measured; auto = "
-                         "on for the headline workload on the default path; off: the committed record is quoted instead")
+                         "on with --full for the headline workload on the default path; off: not measured")
     ap.add_argument("--tune-seconds", type=float, default=240.0,
                     help="N > 1: wall-time cap of the exchange tuner; when it hits, the candidates timed so far decide "
                          "and the table says so")
@@ -902,6 +970,8 @@ def main():
         return self_launch(args, sys.argv[1:])
     _claim_stdout()
     if args.config in ("cfg4", "cfg5"):
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the PDE configurations only (cfg1 / cfg2 / cfg3)")
         return bench_widened(args)
 
     from neural_svd_amd import hip_ops as H
@@ -942,7 +1012,8 @@ def main():
     headline = args.config == "cfg2" and args.laplacian_eps is None and not args.batch_size
     path = {"auto": H.PATH_AUTO, "generic": H.PATH_GENERIC, "fused": H.PATH_FUSED,
             "bf16x3": H.PATH_FUSED_BF16X3}[args.path]
-    repeats = args.repeats or max(3, min(25, round(6000 / max(args.steps, 1))))
+    repeats = args.repeats or 1  # the headline: --steps timed steps
+    side_repeats = args.repeats or max(3, min(25, round(6000 / max(args.steps, 1))))  # tuner and side measurements
     if args.parallelism == "hp" and cfg["L"] < world:
         raise SystemExit(f"hp needs at least one head per rank: L = {cfg['L']} < world size {world}")
 
@@ -980,7 +1051,7 @@ def main():
                 if par_t == "dp" and kw["grad_windows"] is None and nwin == 1:
                     del t
                     continue  # same thing as the explicit 1-window candidate
-                bl, _, _, _ = run_timed(t, comm, args.steps, args.warmup, max(3, repeats // 4), 0.3, 0)
+                bl, _, _, _ = run_timed(t, comm, args.steps, args.warmup, max(3, side_repeats // 4), 0.3, 0)
                 d = summarize(bl, args.steps, world)
                 report[name] = dict(steps_per_s=d["value"], ms_per_step=d["ms_per_step"])
                 if name in pre_timed:
@@ -1003,14 +1074,14 @@ def main():
     par, tr_kw, cand_report, other_sharding, tuned = args.parallelism, {}, None, None, {}
     t_tune0 = time.perf_counter()
     pre_timed, north_star = set(), None
-    if multi and not args.no_extras:
+    if multi and args.full and not args.no_extras:
         # FIRST, whatever wins below: north_star's literal split - samples sharded, ONE all-reduce of the 2L^2+1 moment
         # floats and ONE all-reduce of the flat gradient per step, blocking calls on the compute stream - so that the
         # curve the contract names is on every N > 1 line
         try:
             kw_ns = dict(dp_exchange="allreduce", grad_windows=1, grad_buckets=1, sync=True)
             t, _, _ = make_trainer(cfg, "dp", comm, dev, path, **kw_ns)
-            bl, _, _, _ = run_timed(t, comm, args.steps, args.warmup, max(3, repeats // 4), 0.3, 0)
+            bl, _, _, _ = run_timed(t, comm, args.steps, args.warmup, max(3, side_repeats // 4), 0.3, 0)
             north_star = summarize(bl, args.steps, world, cfg["B"])
             north_star.update(unit="steps/s", parallelism=f"dp{world}", final_loss=float(t.loss[0]),
                               params_finite=bool(torch.isfinite(t.P.flat).all()),
@@ -1053,30 +1124,55 @@ def main():
         par = "dp"
     exchange, sync = tr_kw.get("dp_exchange", "allreduce"), tr_kw.get("sync", False)
     tr, shape, prob = make_trainer(cfg, par, comm, dev, path, **tr_kw)
+    # the same step replayed from a captured HIP graph (N = 1, MFMA path): the learning rate, EMA decay and batch
+    # counter live in a device-resident nsvd_step_state advanced by the step's own kernels (trainer.GraphedSteps). Captured
+    # before anything is timed: the capture may take the first step eagerly (`lead`), which then counts as warm-up, so
+    # that both timed trainers have taken the same number of steps when their timed blocks end
+    trg = gstep = None
+    lead, graph_err = 0, None
+    if not multi and args.graph != "off" and H.path_name(tr.shape, tr.B, path, prob) == "fused_mfma":
+        try:
+            trg, _, _ = make_trainer(cfg, par, None, dev, path, device_schedule=True)
+            gstep = GraphStepper(trg)
+            lead = trg.t
+        except Exception as e:  # noqa: BLE001
+            graph_err = f"{type(e).__name__}: {e}"
+            if args.graph == "on":
+                raise
+            trg = gstep = None
+    warmup = max(args.warmup, lead)
+    prewarm_spent, n_pre = prewarm(cfg, par, comm, dev, path, args.prewarm_seconds, **tr_kw)
 
     use_ev = not args.no_kernel_events
     EV_EVERY = 4  # bracket the dominant kernel on every 4th timed step (two event records cost ~2 us)
-    blocks, kms, prewarm, n_pre = run_timed(tr, comm, args.steps, args.warmup, repeats, args.prewarm_seconds,
-                                            EV_EVERY if use_ev else 0)
+    blocks, kms, _, _ = run_timed(tr, comm, args.steps, warmup, repeats, None, EV_EVERY if use_ev else 0)
     summ = summarize(blocks, args.steps, world, cfg["B"])
     modes = {"eager": dict(summ, note="three launches per step from Python (ctypes), the per-step scalars as launch "
                                       "arguments" + ("; every 4th step carries the two event records of the kernel "
                                                      "bracket" if use_ev else ""))}
-    timing_mode = "eager"
-    graph_err = None
-    if not multi and args.graph != "off" and H.path_name(tr.shape, tr.B, path, prob) == "fused_mfma":
-        # the same step replayed from a captured HIP graph: the learning rate, EMA decay and batch counter live in a
-        # device-resident nsvd_step_state advanced by the step's own kernels (trainer.GraphedSteps)
+    timing_mode, timed_tr = "eager", tr
+    if gstep is not None:
         try:
-            trg, _, _ = make_trainer(cfg, par, None, dev, path, device_schedule=True)
-            bg, n_pre_g = run_timed_graph(trg, args.steps, args.warmup, repeats, args.prewarm_seconds)
+            bg, _ = run_timed_graph(trg, args.steps, warmup - lead, repeats, None, stepper=gstep)
             sg = summarize(bg, args.steps, 1, cfg["B"])
-            modes["hip_graph_replay"] = dict(sg, steps_per_graph=2, prewarm_steps=n_pre_g,
-                                             final_loss=float(trg.loss[0]),
+            modes["hip_graph_replay"] = dict(sg, steps_per_graph=2, final_loss=float(trg.loss[0]),
                                              params_finite=bool(torch.isfinite(trg.P.flat).all()),
                                              note="one hipGraphLaunch per two steps; bit-identical to eager stepping "
                                                   "(tests/test_graph_gpu.py)")
-            # per-step host sync on the loss, as the reference's loop does (loss.item(), operator/__init__.py:74)
+            if sg["value"] > summ["value"]:
+                summ, timing_mode, timed_tr = sg, "hip_graph_replay", trg
+        except Exception as e:  # noqa: BLE001
+            graph_err = f"{type(e).__name__}: {e}"
+            if args.graph == "on":
+                raise
+    if args.dump_outputs:
+        if getattr(timed_tr, "_state_sharded", False):
+            timed_tr.gather_optimizer_state()  # (a collective: every rank)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, trainer_outputs(timed_tr))
+    if args.full and "hip_graph_replay" in modes:
+        # per-step host sync on the loss, as the reference's loop does (loss.item(), operator/__init__.py:74)
+        try:
             for _ in range(20):
                 trg.step()
             torch.cuda.synchronize()
@@ -1091,20 +1187,17 @@ def main():
                 value=round(nsync / el, 3), ms_per_step=round(1e3 * el / nsync, 4), steps=nsync,
                 note="eager steps + float(loss) after each (the reference's per-step host sync); the loss VALUE is "
                      "produced by the step's own kernels in every mode")
-            if sg["value"] > summ["value"]:
-                summ, timing_mode = sg, "hip_graph_replay"
-            del trg
-            torch.cuda.empty_cache()
         except Exception as e:  # noqa: BLE001
             graph_err = f"{type(e).__name__}: {e}"
-            if args.graph == "on":
-                raise
+    del trg, gstep, timed_tr
+    torch.cuda.empty_cache()
     loss = float(tr.loss[0])
     finite = bool(torch.isfinite(tr.P.flat).all())
     fused_step, tr_hp, n_train, trB, trL = tr.fused_step, tr.hp, tr.P.n_trainable, tr.B, tr.shape.L
     path_name = H.path_name(tr.shape, tr.B, path, prob)
     comm_block = None
-    if multi:
+    rccl_ranks = comm.count_ranks() if multi else None
+    if multi and args.full:
         # where the multi-GPU step's time goes: (1) the exposed wait of every collective, from events on the compute
         # stream around each wait (parallel.CommProbe), over PROBE_STEPS further steps of the same trainer; (2) the
         # same step with every collective skipped (compute_only_ms; replicas drift apart, which timing does not mind)
@@ -1119,7 +1212,7 @@ def main():
         nwin = len(tr._windows)
         comm.barrier()
         comm.stub = True
-        bl, _, _, _ = run_timed(tr, comm, args.steps, args.warmup, max(3, repeats // 4), 0.2, 0)
+        bl, _, _, _ = run_timed(tr, comm, args.steps, args.warmup, max(3, side_repeats // 4), 0.2, 0)
         comm.stub = False
         co = summarize(bl, args.steps, world, cfg["B"])
         comm_block = {
@@ -1138,7 +1231,6 @@ def main():
                     "with every collective skipped",
             "candidates": cand_report,
         }
-        rccl_ranks = comm.count_ranks()
     del tr
     torch.cuda.empty_cache()
 
@@ -1164,7 +1256,7 @@ def main():
         for vname, kw in variants:
             try:
                 t, _, _ = make_trainer(cfg_s, par_s, comm, dev, path_s, **kw)
-                bl, _, _, _ = run_timed(t, comm, args.steps, args.warmup, max(3, repeats // 3), 0.3, 0)
+                bl, _, _, _ = run_timed(t, comm, args.steps, args.warmup, max(3, side_repeats // 3), 0.3, 0)
                 d = summarize(bl, args.steps, world, cfg_s["B"])
                 d.update(unit="steps/s", final_loss=float(t.loss[0]),
                          params_finite=bool(torch.isfinite(t.P.flat).all()), global_batch=cfg_s["B"] * world, note=note)
@@ -1187,7 +1279,7 @@ def main():
             best.pop("exchange", None)
         extras[name] = best
 
-    if not args.no_extras and headline and args.path == "auto":
+    if args.full and not args.no_extras and headline and args.path == "auto":
         if world == 1 and args.force_exchange:
             side("sharding_hp", cfg, "hp", path, "heads 'sharded' over a world of one: the all-gather of f, Tf as an "
                                                  "RCCL call with nothing on the wire")
@@ -1290,13 +1382,14 @@ def main():
         "value": value, "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
-        "timing": {"protocol": "prewarm, then --warmup steps, then `blocks` timed blocks of exactly --steps steps "
-                               "(barrier + synchronize on both sides, max over ranks); value = median block",
+        "timing": {"protocol": "prewarm (a throwaway trainer of the same configuration), then --warmup steps, then "
+                               "`blocks` timed blocks of exactly --steps steps (barrier + synchronize on both sides, "
+                               "max over ranks); value = median block",
                    "mode": timing_mode, "modes": modes,
                    "loss_every_step": "the loss value of every step is produced on the device by the step's own "
                                       "kernels (no extra launch, no host sync in the timed region)",
                    "blocks": summ["blocks"], "ms_per_step_min": summ["ms_per_step_min"],
-                   "ms_per_step_max": summ["ms_per_step_max"], "prewarm_s": round(prewarm, 3),
+                   "ms_per_step_max": summ["ms_per_step_max"], "prewarm_s": round(prewarm_spent, 3),
                    "prewarm_steps": n_pre},
         "config": {"workload": "configs[1]: 2D hydrogen, L=16, batch_size=512 per GPU, joint nesting, "
                                "MLP 2048(Fourier m=1024)->128->128->128->1 x16 heads, eps=0.01, RMSprop+cosine+EMA",
@@ -1339,8 +1432,8 @@ def main():
         out["metric"] += " [developer run: exchange sequences forced on in an RCCL world of one]"
     # the other half of BASELINE.json's metric: eigenvalue error after the reference's full schedule, MEASURED in this
     # run (N = 1, headline workload, default path) or absent - nothing on this line is quoted from an earlier run
-    want_acc = headline and not multi and (args.accuracy == "on" or (args.accuracy == "auto" and not args.force_exchange
-                                                                   and args.path == "auto"))
+    want_acc = headline and not multi and (args.accuracy == "on" or (args.accuracy == "auto" and args.full and
+                                                                   not args.force_exchange and args.path == "auto"))
     if want_acc:
         try:
             acc = measure_accuracy(cfg, dev, path, graph=(args.graph != "off" and path_name == "fused_mfma"))
@@ -1363,9 +1456,9 @@ def main():
         out["config"]["layer0"] = ("bf16 MFMA, operands split into 3 bf16 planes, 6 partial products, fp32 "
                                    "accumulate; roofline.frac stays relative to the fp32 MFMA peak")
     out.update(extras)
-    if world == 1 and headline and args.path == "auto" and not args.no_extras and not args.force_exchange:
+    if args.full and world == 1 and headline and args.path == "auto" and not args.no_extras and not args.force_exchange:
         out["other_configs"] = measure_other_configs(args, dev)
-    if world == 1 and not args.no_cpu_baseline and args.config == "cfg2" and not args.force_exchange:
+    if args.full and world == 1 and not args.no_cpu_baseline and args.config == "cfg2" and not args.force_exchange:
         cb = cpu_baseline()
         out["cpu_baseline"] = cb
         out["speedup_vs_cpu_baseline"] = round(value / cb["value"], 1)

@@ -4,7 +4,7 @@ tag=${1:-r05i}
 out=/root/repo/gpurun_out/$tag
 mkdir -p $out
 cd /root/repo
-SECONDS=0; timeout 900 python bench.py --steps 20 --warmup 5 > $out/bench_driver_args.json 2> $out/bench_driver_args.err; echo "bench rc=$?"
+SECONDS=0; timeout 900 python bench.py --steps 20 --warmup 5 --full > $out/bench_driver_args.json 2> $out/bench_driver_args.err; echo "bench rc=$?"
 echo "elapsed ${SECONDS}s"
 python - <<PY
 import json

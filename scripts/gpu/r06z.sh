@@ -23,9 +23,9 @@ TOPN=16 TAILN=2 timeout 300 scripts/gpu/prof_by_grid.sh ${tag}_gen64 /root/repo/
 timeout 300 scripts/gpu/pmc_kernels.sh ${tag}_gen256_pmc "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" /root/repo/scripts/dev/generic_time.py 256 > $out/generic_h256_pmc_sq.txt 2>&1
 timeout 300 scripts/gpu/pmc_kernels.sh ${tag}_gen256_pmc2 "TCC_HIT_sum TCC_MISS_sum" /root/repo/scripts/dev/generic_time.py 256 > $out/generic_h256_pmc_l2.txt 2>&1
 echo "generic evidence done"
-SECONDS=0; timeout 1200 python bench.py --steps 20 --warmup 5 > $out/bench_driver_args.json 2> $out/bench_driver_args.err; echo "bench rc=$? in ${SECONDS}s"
-NSVD_FORCE_DEVICE=0 NSVD_DIST_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --accuracy off > $out/bench_n2_gloo.json 2> $out/bench_n2_gloo.err; echo "bench n2 rc=$?"
-timeout 600 python bench.py --gpus 1 --force-exchange --steps 200 --warmup 20 --accuracy off > $out/bench_rccl_world1.json 2> $out/bench_rccl_world1.err; echo "bench rccl1 rc=$?"
+SECONDS=0; timeout 1200 python bench.py --steps 20 --warmup 5 --full > $out/bench_driver_args.json 2> $out/bench_driver_args.err; echo "bench rc=$? in ${SECONDS}s"
+NSVD_FORCE_DEVICE=0 NSVD_DIST_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline --accuracy off --full > $out/bench_n2_gloo.json 2> $out/bench_n2_gloo.err; echo "bench n2 rc=$?"
+timeout 600 python bench.py --gpus 1 --force-exchange --steps 200 --warmup 20 --accuracy off --full > $out/bench_rccl_world1.json 2> $out/bench_rccl_world1.err; echo "bench rccl1 rc=$?"
 python - <<PY
 import json
 d=json.load(open("$out/bench_driver_args.json"))

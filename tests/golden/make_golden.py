@@ -669,8 +669,41 @@ def golden_ground_truth(out):
         out[f"gt_oscillator_{n}"] = HarmonicOscillator(k=1.0, ndim=2).get_eigvals(n)
 
 
+# the cases of tests/test_checkpoint_interchange.py
+CHECKPOINT_CASES = [dict(neigs=4, mlp_hidden_dims="32,32", fourier_mapping_size=16),
+                    dict(neigs=3, mlp_hidden_dims="128,128,128", fourier_mapping_size=64,
+                         potential_type="harmonic_oscillator", apply_exp_mask=1, exp_mask_init_scale=10.0,
+                         sequential=0)]
+
+
+def golden_checkpoint(out):
+    """what a reference checkpoint holds (examples/operator/__init__.py:139-145): per case the reference method's
+    state_dict keys in order with their shapes and dtypes, the number of its trainable tensors, its optimiser's
+    param_groups, and the values of one state_dict drawn under torch.manual_seed(5)"""
+    import json
+    for i, over in enumerate(CHECKPOINT_CASES):
+        args = make_args(**dict(over))
+        torch.manual_seed(5)
+        ref = get_evd_method(args, "neuralsvd", get_wavefunctions(args))
+        sd = ref.state_dict()
+        opt = get_optimizer(args, ref)
+        meta = dict(keys=list(sd.keys()), shapes=[list(t.shape) for t in sd.values()],
+                    dtypes=[str(t.dtype) for t in sd.values()],
+                    n_trainable=sum(1 for p in ref.parameters() if p.requires_grad),
+                    optimizer=type(opt).__name__, param_groups=opt.state_dict()["param_groups"])
+        out[f"case{i}_meta"] = np.array(json.dumps(meta))
+        for k, t in sd.items():
+            out[f"case{i}_sd.{k}"] = t.detach().numpy().copy()
+
+
 def main():
     torch.set_num_threads(8)
+    if len(sys.argv) > 1 and sys.argv[1] == "checkpoint":
+        o = {}
+        golden_checkpoint(o)
+        np.savez_compressed(os.path.join(HERE, "checkpoint.npz"), **o)
+        print("checkpoint", os.path.getsize(os.path.join(HERE, "checkpoint.npz")) // 1024, "KiB")
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "normalize":
         o = {}
         golden_normalize(o)
@@ -713,6 +746,9 @@ def main():
         np.savez_compressed(os.path.join(HERE, "svd_loss.npz"), **o)
         print("svd_loss", os.path.getsize(os.path.join(HERE, "svd_loss.npz")) // 1024, "KiB")
         return
+    o = {}
+    golden_checkpoint(o)
+    np.savez_compressed(os.path.join(HERE, "checkpoint.npz"), **o)
     o = {}
     golden_cdk_step(o)
     np.savez_compressed(os.path.join(HERE, "cdk_step.npz"), **o)

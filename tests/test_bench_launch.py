@@ -93,7 +93,8 @@ def test_launcher_refuses_more_ranks_than_gpus():
 @pytest.mark.gpu
 @pytest.mark.timeout(1500)
 def test_bench_two_ranks_exactly_as_the_driver_calls_it():
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
+                        "--full"],
                        env=_env(NSVD_FORCE_DEVICE="0", NSVD_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0"),
                        capture_output=True, text=True, timeout=1400)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -157,7 +158,7 @@ def test_launcher_retries_with_the_plain_exchange_when_the_tuned_run_dies():
     starts its ranks as the script it was started as): the launcher must start the ranks again with the plainest
     sequence and still deliver ONE line, marked with what failed"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_bench_failing_rank.py"), "--gpus", "2", "--steps",
-                        "20", "--warmup", "5", "--no-cpu-baseline"],
+                        "20", "--warmup", "5", "--no-cpu-baseline", "--full"],
                        env=_env(NSVD_FORCE_DEVICE="0", NSVD_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0"),
                        capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -226,7 +227,7 @@ def test_bench_widened_rows_on_two_ranks(cfg):
     """`bench.py --config cfg4 | cfg5 --gpus 2`: the kernel-operator step with heads sharded (weak scaling) and the CDK
     step with the towers' hidden width sharded (strong scaling), self-launched, one line with its `comm` block"""
     r = subprocess.run([sys.executable, BENCH, "--config", cfg, "--gpus", "2", "--steps", "10", "--warmup", "2",
-                        "--collective-timeout", "120"],
+                        "--collective-timeout", "120", "--full"],
                        env=_env(NSVD_FORCE_DEVICE="0", NSVD_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0"),
                        capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -238,3 +239,59 @@ def test_bench_widened_rows_on_two_ranks(cfg):
     assert d["config"]["parallelism"] == ("hp2" if cfg == "cfg4" else "tp2")
     c = d["comm"]
     assert c["rccl_ranks"] == 2 and c["compute_only_ms"] > 0 and len(c["exposed_wait_us_per_step"]) == (1 if cfg == "cfg4" else 2)
+
+
+def test_dump_outputs_stays_within_its_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs on the CPU: float32 files (float64 kept), and an array that would take the total past the
+    budget is written as a fixed, seeded sample of its elements with their flat indices beside it"""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_dump", BENCH)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    monkeypatch.setattr(mod, "DUMP_BYTES", 4096)
+    small = torch.arange(6, dtype=torch.float64).reshape(2, 3)
+    big = torch.arange(4096, dtype=torch.float32)
+    for d in ("a", "b"):
+        mod.dump_outputs(str(tmp_path / d), [("small", small), ("int", torch.arange(3)), ("big", big)])
+    a = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    b = {f.name: np.load(f) for f in (tmp_path / "b").iterdir()}
+    assert set(a) == {"small.npy", "big.npy", "big_index.npy", "int.npy"}
+    assert a["small.npy"].dtype == np.float64 and np.array_equal(a["small.npy"], small.numpy())
+    assert a["big.npy"].dtype == np.float32 and a["int.npy"].dtype == np.float32
+    assert np.array_equal(a["big.npy"], a["big_index.npy"].astype(np.float32))  # big[i] == i
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 4096
+    assert all(np.array_equal(a[k], b[k]) for k in a)  # the same sample every time
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_plain_run_is_the_headline_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` measures the headline only (no accuracy schedule, no other_configs, no
+    CPU baseline), times exactly K steps, and with --dump-outputs writes the timed trainer's last-step outputs: the same
+    arguments give the same inputs, hence the same outputs"""
+    import numpy as np
+    outs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "30", "--warmup", "4", "--dump-outputs",
+                            str(tmp_path / run)], env=_env(), capture_output=True, text=True, timeout=400)
+        assert r.returncode == 0, r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 30 and d["warmup"] == 4 and d["timing"]["blocks"] == 1 and d["value"] > 0
+        assert abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-2 * 1e3
+        assert d["cpu_baseline"] is None and "other_configs" not in d and "rel_eigenvalue_error" not in d
+        assert "opt_in_path_bf16x3" not in d and "eager_with_loss_item_every_step" not in d["timing"]["modes"]
+        files = {f.name: np.load(f) for f in (tmp_path / run).iterdir()}
+        assert set(files) == {"loss.npy", "f.npy", "Tf.npy", "params.npy", "ema_params.npy"}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in files.values())
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= 64 << 20
+        assert files["f.npy"].shape == (512, 16) and files["params.npy"].size == d["config"]["params"]
+        outs.append(files)
+    for k in outs[0]:
+        # eager and graph-replayed steps are bit-identical up to the device cosine's last bit: either may be timed
+        np.testing.assert_allclose(outs[0][k], outs[1][k], rtol=1e-5, atol=1e-6, err_msg=k)
