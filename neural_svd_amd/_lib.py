@@ -23,8 +23,7 @@ FEATURES_READY = 0x100
 W_PLANES_READY = 0x200
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-# NSVD_LIB_PATH: diagnostic builds only (e.g. the stamped kernels of scripts/dev/stamps.py)
-LIB_PATH = os.environ.get("NSVD_LIB_PATH") or os.path.join(_PKG_DIR, "libnsvd_hip.so")
+LIB_PATH = os.path.join(_PKG_DIR, "libnsvd_hip.so")
 
 
 class ModelDesc(C.Structure):

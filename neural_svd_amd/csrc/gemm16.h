@@ -62,8 +62,6 @@ struct Args {
     long slice_stride;          // elements of C between split-K slices
     int nwg;
     int f16;  // the operands (and a 16-bit output) are IEEE float16 instead of bfloat16
-    int dbg;  // diagnostic builds only (NSVD_G16_DBG): 1 = no DMA after the prologue, 2 = no fragment reads / MFMAs
-    unsigned long long* stamps;  // diagnostic, or null: cycles of block 0 / wave 0 - prologue, K loop (first half | barrier | second half), epilogue
 };
 
 // the problems of a launch with one shape (the two towers): shape and strides of all nprob entries
@@ -268,9 +266,6 @@ __global__ void __launch_bounds__(512) gemm16_kernel(Args a) {
     //   DMA of step t + 3 into stage t % 3 (just freed)
     //   second half          : MFMAs on (t, 1) | reads of (t + 1, 0)
     // Every MFMA block runs on fragments read half a step earlier; a DMA has two steps to land.
-    const bool stamp = a.stamps && blockIdx.x == 0 && tid == 0;
-    const unsigned long long ts0 = a.stamps ? __builtin_readcyclecounter() : 0ull;
-    unsigned long long th1 = 0, thb = 0, th2 = 0;
     G16_ISSUE(0);
     if (nk > 1) G16_ISSUE(1);
     if (nk > 2) G16_ISSUE(2);
@@ -279,31 +274,20 @@ __global__ void __launch_bounds__(512) gemm16_kernel(Args a) {
     else G16_WAIT_BARRIER(0);
     // the second-dispatched half of the workgroup loses every issue arbitration to its SIMD partner (same program, older
     // wave first): a static priority for waves 4-7 evens that out (MI355X_MICROARCH.md, two waves per SIMD, item 4)
-    if (w >= 4 && !(a.dbg & 16)) __builtin_amdgcn_s_setprio(1);
+    if (w >= 4) __builtin_amdgcn_s_setprio(1);
     Frags f0, f1;
-    if (!(a.dbg & 2)) load_frags(f0, lds, 0);
-    const unsigned long long ts1 = a.stamps ? __builtin_readcyclecounter() : 0ull;
+    load_frags(f0, lds, 0);
     for (int t = 0; t < nk; ++t) {
         const char* st = lds + (t % NST) * ST_BYTES;
         const char* sn = lds + ((t + 1) % NST) * ST_BYTES;
-        const unsigned long long u0 = a.stamps ? __builtin_readcyclecounter() : 0ull;
-        if (!(a.dbg & 2)) {
-            load_frags(f1, st, 1);
-            mma(f0);
-        }
-        const unsigned long long u1 = a.stamps ? __builtin_readcyclecounter() : 0ull;
-        if (t + 2 < nk && !(a.dbg & 1)) G16_WAIT_BARRIER(NDMA);
+        load_frags(f1, st, 1);
+        mma(f0);
+        if (t + 2 < nk) G16_WAIT_BARRIER(NDMA);
         else G16_WAIT_BARRIER(0);
-        const unsigned long long u2 = a.stamps ? __builtin_readcyclecounter() : 0ull;
-        if (t + 3 < nk && !(a.dbg & 1)) G16_ISSUE(t % NST);
-        if (!(a.dbg & 2)) {
-            if (t + 1 < nk) load_frags(f0, sn, 0);
-            mma(f1);
-        }
-        const unsigned long long u3 = a.stamps ? __builtin_readcyclecounter() : 0ull;
-        th1 += u1 - u0; thb += u2 - u1; th2 += u3 - u2;
+        if (t + 3 < nk) G16_ISSUE(t % NST);
+        if (t + 1 < nk) load_frags(f0, sn, 0);
+        mma(f1);
     }
-    const unsigned long long ts2 = a.stamps ? __builtin_readcyclecounter() : 0ull;
 #undef G16_ISSUE
 #undef G16_WAIT_BARRIER
 #undef G16_TR
@@ -325,9 +309,7 @@ __global__ void __launch_bounds__(512) gemm16_kernel(Args a) {
                         c3 = acc[i][j][3] + bv.w;
             ss = fmaf(c0, c0, ss); ss = fmaf(c1, c1, ss); ss = fmaf(c2, c2, ss); ss = fmaf(c3, c3, ss);
             char* dst = lds + (64 * wm + 16 * i + l15) * RS + (64 * wn + 16 * j + 4 * g4) * (O16 ? 2 : 4);
-            if (a.dbg & 4) {
-                asm volatile("" ::"v"(c0), "v"(c1), "v"(c2), "v"(c3));
-            } else if (O16) {
+            if (O16) {
                 *reinterpret_cast<uint2*>(dst) = make_uint2(pack_h<F16>(c0, c1), pack_h<F16>(c2, c3));
             } else {
                 *reinterpret_cast<float4*>(dst) = make_float4(c0, c1, c2, c3);
@@ -335,27 +317,21 @@ __global__ void __launch_bounds__(512) gemm16_kernel(Args a) {
         }
     }
     __syncthreads();
-    if (!(a.dbg & 4)) {
-        constexpr int LPR = O16 ? 16 : 32;        // lanes per row (16 bytes each)
-        constexpr int RPP = 512 / LPR;            // rows per pass of the workgroup
-        const int rr = tid / LPR, cc = tid % LPR;
-        char* cbase = reinterpret_cast<char*>(P.C) + ((long)slice * a.slice_stride + (long)BM * tm * P.ldc + BN * tn) * (O16 ? 2 : 4);
-        for (int r = rr; r < BM; r += RPP) {
-            const uint4 v = *reinterpret_cast<const uint4*>(lds + r * RS + 16 * cc);
-            char* dstp = cbase + (long)r * P.ldc * (O16 ? 2 : 4) + 16 * cc;
-            // write-through (sc1): the rows leave for memory as they are stored instead of sitting dirty in this XCD's L2
-            // until the kernel-end write-back (MI355X_MICROARCH.md, stores of each flavour / row `boundary`): 0.9 us of
-            // the 15.8 at (1024, 8192, 512) bfloat16 out, 1.5 of 23.5 at (512, 8192, 1024) float32 out
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-            const u32x4 vv = {v.x, v.y, v.z, v.w};
-            // (s_nop 1 inside the string: hipcc pads nothing behind an asm store - its next instruction may overwrite the
-            // data registers before the store has read them: intermittent wrong elements, found in round 6)
-            asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dstp), "v"(vv) : "memory");
-        }
-    }
-    if (stamp) {
-        a.stamps[0] = ts1 - ts0; a.stamps[1] = th1 / nk; a.stamps[2] = thb / nk; a.stamps[3] = th2 / nk;
-        a.stamps[4] = __builtin_readcyclecounter() - ts2; a.stamps[5] = (unsigned long long)nk;
+    constexpr int LPR = O16 ? 16 : 32;        // lanes per row (16 bytes each)
+    constexpr int RPP = 512 / LPR;            // rows per pass of the workgroup
+    const int rr = tid / LPR, cc = tid % LPR;
+    char* cbase = reinterpret_cast<char*>(P.C) + ((long)slice * a.slice_stride + (long)BM * tm * P.ldc + BN * tn) * (O16 ? 2 : 4);
+    for (int r = rr; r < BM; r += RPP) {
+        const uint4 v = *reinterpret_cast<const uint4*>(lds + r * RS + 16 * cc);
+        char* dstp = cbase + (long)r * P.ldc * (O16 ? 2 : 4) + 16 * cc;
+        // write-through (sc1): the rows leave for memory as they are stored instead of sitting dirty in this XCD's L2
+        // until the kernel-end write-back (MI355X_MICROARCH.md, stores of each flavour / row `boundary`): 0.9 us of
+        // the 15.8 at (1024, 8192, 512) bfloat16 out, 1.5 of 23.5 at (512, 8192, 1024) float32 out
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4 vv = {v.x, v.y, v.z, v.w};
+        // (s_nop 1 inside the string: hipcc pads nothing behind an asm store - its next instruction may overwrite the
+        // data registers before the store has read them: intermittent wrong elements, found in round 6)
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dstp), "v"(vv) : "memory");
     }
     if (P.sumsq) {  // fixed order: lanes of a wave (butterfly), then the eight waves
         ss = nsvd_wave_sum(ss);
@@ -394,15 +370,10 @@ inline int launch(const Args& a0, bool a_strided, bool b_strided, bool out_bf16,
         nwg += P.tiles_m * P.tiles_n * a.S;
     }
     a.nwg = nwg;
-    {
-        static const char* e = getenv("NSVD_G16_DBG");
-        a.dbg = e ? atoi(e) : 0;
-    }
     const dim3 grid((unsigned)nwg);
-    static const char* form_env = getenv("NSVD_G16_FORM");  // "a": the one-workgroup-per-CU kernel above (A/B measurements)
     // two workgroups per CU (gemm16b.h) where the launch has at least two per CU to give; one per CU otherwise (this kernel:
     // deeper K steps, fragments double-buffered - better alone on its CU)
-    const bool form_b = !(form_env && form_env[0] == 'a') && !a.stamps && nwg >= 512;
+    const bool form_b = nwg >= 512;
 #define G16_LAUNCH_T(AS_, BS_, O_, F_)                                                                             \
     if (form_b) {                                                                                                  \
         const int rcb = launch_b_inst<AS_, BS_, O_, F_>(a, s);                                                     \

@@ -423,9 +423,8 @@ __global__ void __launch_bounds__(256) rowsum_kernel(const float* __restrict__ i
 int nsvd_gemm_generic(const NsvdGemm& g, hipStream_t s, bool* rowsum_done) {
     if (g.M <= 0 || g.N <= 0 || g.K <= 0 || g.batch <= 0) return NSVD_EINVAL;
     if (rowsum_done) *rowsum_done = false;
-    // the vectorised kernel where the launch allows it (NSVD_GEMM_GENERIC3=0: off, for A/B measurements)
-    static const char* e3 = getenv("NSVD_GEMM_GENERIC3");
-    if (!(e3 && e3[0] == '0') && generic3_ok(g)) {
+    // the vectorised kernel where the launch allows it
+    if (generic3_ok(g)) {
         // the largest tile that still gives the chip enough workgroups (NSVD_G3_MINWG, default 1024: four per CU, what
         // the registers and the LDS let reside - measured against 128 / 256 / 512: hidden width 64 0.47 / 0.40 / 0.34 /
         // 0.34 ms per step, hidden width 128 0.65 / 0.62 / 0.53 / 0.47); a launch too small for any of them takes the
@@ -437,9 +436,8 @@ int nsvd_gemm_generic(const NsvdGemm& g, hipStream_t s, bool* rowsum_done) {
         if (g.M > 64 && nwg(128, 128) >= minwg) return launch_generic3<2, 2>(g, s);
         if (g.N >= 256 && nwg(64, 256) >= minwg) return launch_generic3<1, 4>(g, s);
         if (nwg(64, 128) >= minwg) return launch_generic3<1, 2>(g, s);
-        // fewer 64 x 64 tiles than half the CUs and a long contraction: four K groups per workgroup (NSVD_G3_KGROUPS=0: off)
-        const char* ekg = getenv("NSVD_G3_KGROUPS");
-        if (nwg(64, 64) <= 128 && g.K >= 256 && !(ekg && ekg[0] == '0')) return launch_generic3<1, 1, 4>(g, s);
+        // fewer 64 x 64 tiles than half the CUs and a long contraction: four K groups per workgroup
+        if (nwg(64, 64) <= 128 && g.K >= 256) return launch_generic3<1, 1, 4>(g, s);
         return launch_generic3<1, 1>(g, s);
     }
     dim3 grid2(nsvd_cdiv(g.N, T2N), nsvd_cdiv(g.M, T2M), g.batch);

@@ -201,8 +201,6 @@ extern "C" const char* nsvd_path_name(const nsvd_model_desc* desc, int B, int pa
 
 extern "C" int nsvd_step_emits_planes(const nsvd_model_desc* desc, int B, int path) {
     if (validate(desc) != 0 || B <= 0 || path != NSVD_PATH_FUSED_BF16X3) return 0;
-    const char* e = getenv("NSVD_PLANES_FROM_STEP");
-    if (e && atoi(e) == 0) return 0;
     // (the streaming backward never runs the kernel that writes the planes)
     return nsvd_fused_supported(*desc, B, false) && nsvd_fused_wgrad_slices(*desc, B) == 1 &&
                    nsvd_fused_stream_bwd_slices(*desc, B) == 0 ? 1 : 0;
@@ -418,9 +416,7 @@ int backward_evd_impl(const nsvd_model_desc* desc, const nsvd_params* params, co
         st.h = nsvd_make_hyper(opt->lr, opt->alpha, opt->eps, opt->has_ema ? opt->ema_decay : 0.0, 1.0);
         st.state = opt->state;
         if (st.state && ((uintptr_t)st.state & 7) != 0) return NSVD_EINVAL;
-        // (NSVD_PLANES_FROM_STEP=0: measurements of the split launch against the epilogue's emission)
-        static const bool planes_env = [] { const char* e = getenv("NSVD_PLANES_FROM_STEP"); return !e || atoi(e) != 0; }();
-        st.emit_planes = !model_mode && path == NSVD_PATH_FUSED_BF16X3 && planes_env;
+        st.emit_planes = !model_mode && path == NSVD_PATH_FUSED_BF16X3;
     }
     if (ws_bytes < (model_mode ? nsvd_model_workspace_bytes(desc, B) : nsvd_workspace_bytes(desc, B))) return NSVD_EINVAL;
     if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
@@ -490,9 +486,8 @@ int backward_evd_impl(const nsvd_model_desc* desc, const nsvd_params* params, co
         if (desc->has_exp_mask)
             add(params->scales, grads->scales, st.sq.scales, st.ema ? st.ema->scales : nullptr, (size_t)desc->L);
         tab.count = c;
-        static const char* et = getenv("NSVD_OPT_TABLE");  // 0: one launch per tensor (A/B, bit-identical)
-        rc = (et && et[0] == '0') ? NSVD_EUNSUPPORTED : nsvd_rmsprop_table_launch(tab, st.h, s);
-        if (rc != NSVD_EUNSUPPORTED) return rc;
+        rc = nsvd_rmsprop_table_launch(tab, st.h, s);
+        if (rc != NSVD_EUNSUPPORTED) return rc;  // (misaligned pointers: one launch per tensor below)
     }
     for (int i = 0; i < desc->nlayers; ++i) {
         const size_t hin = i == 0 ? (size_t)F : (size_t)desc->dims[i - 1], hout = (size_t)desc->dims[i];

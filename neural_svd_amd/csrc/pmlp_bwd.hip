@@ -373,7 +373,7 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_bwd_chain_kernel(ChainArgs 
 //                        longer workgroups next to the dW_0 tiles.)
 //   C  (4 L):            dW_last[l][n] = sum_b dbase[b] softplus(z_{nh-1}[l][n][b]), db_last, d scales, and
 //                        db_0[l][n] = sum_b dz_0[l][n][b] for the same 32 rows.
-// Timeline at cfg2 (NSVD_WG_STAMPS build, scripts/dev/wgrad_stamps.py), fused optimiser step: the A tiles run
+// Timeline at cfg2 (per-block cycle and wall-clock stamps), fused optimiser step: the A tiles run
 // their K loop in 70-79 K cycles (65.5 K of MFMA issue; 69.7 K with nothing else on the chip) and their
 // epilogue - RMSprop + EMA on the tile, 112 MB through HBM for the whole kernel, the state of half of each tile
 // already in registers (fetched under the last two chunks of the loop) - in 22-26 K, ending at 38-48 us; the B
@@ -440,14 +440,6 @@ __device__ __forceinline__ WgDst wg_dst(const WgradArgs& a, float* g, size_t par
     if (a.S > 1) return WgDst{a.part + (size_t)slice * a.part_stride + part_off, 0};
     return WgDst{g, a.opt};
 }
-
-#ifdef NSVD_WG_STAMPS
-// diagnostic build: per-block (kind, realtime start/end, cycles in prologue / loop / epilogue)
-__device__ unsigned long long g_wg_stamps[1024 * 8];
-#define WG_STAMP(slot, v) if (threadIdx.x == 0) g_wg_stamps[(size_t)blockIdx.x * 8 + (slot)] = (v)
-#else
-#define WG_STAMP(slot, v)
-#endif
 
 // one gradient element: store it and / or take the optimiser step on its parameter
 __device__ __forceinline__ void wg_emit1(const NsvdHyper& h, const WgDst& d, const NsvdOptPtrs& o, size_t off,
@@ -638,12 +630,8 @@ __device__ __forceinline__ void wgrad_tile_A(const WgradArgs& a, const NsvdHyper
     const float* a_base = a.dz[0] + (size_t)l * HID * a.B + (size_t)slice * a.Bs;
     const float* b_base = a.phiTc + (size_t)kf0 * a.B + (size_t)slice * a.Bs;
     const size_t o = ((size_t)l * HID + 64 * wm) * a.F + kf0 + 32 * NJ * wn + li;
-    WG_STAMP(0, 1ull);
-    WG_STAMP(1, wall_clock64());
-    WG_STAMP(2, __builtin_readcyclecounter());
     if (MODE == 0) {
         nsvd_tile128_dma(a_base, b_base, (unsigned)a.B, (unsigned)a.B, a.Bs / BK, lds, acc);
-        WG_STAMP(4, __builtin_readcyclecounter());
         const WgDst dW = wg_dst(a, a.gW[0], a.poW[0], slice);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -659,7 +647,6 @@ __device__ __forceinline__ void wgrad_tile_A(const WgradArgs& a, const NsvdHyper
         pf.P = op.p; pf.S = op.sq; pf.E = op.ema;
         pf.base = b00; pf.ld = ld; pf.hi = hi;
         nsvd_tile128_dma(a_base, b_base, (unsigned)a.B, (unsigned)a.B, a.Bs / BK, lds, acc, pf);
-        WG_STAMP(4, __builtin_readcyclecounter());
         if (NJ == 2) {
             // blocks (0,0), (0,1) have their state; the loads of (1,0), (1,1) go out behind the stores of the former
             float p2[16], s2[16], e2[16], p3[16], s3[16], e3[16];
@@ -677,8 +664,6 @@ __device__ __forceinline__ void wgrad_tile_A(const WgradArgs& a, const NsvdHyper
 #undef WG_PL
         }
     }
-    WG_STAMP(5, __builtin_readcyclecounter());
-    WG_STAMP(6, wall_clock64());
 }
 
 // dW_i quadrant through the shared C = A B^T tile routine (tile_nt.h): both operands are plain (L, 128, B) rows now
@@ -938,18 +923,12 @@ __global__ void __launch_bounds__(256, 2) pmlp_fused_wgrad_kernel(WgradArgs a) {
     }
     bid -= a.nA * a.S;
     if (bid < a.nB * a.S) {
-        WG_STAMP(0, 2ull);
-        WG_STAMP(1, wall_clock64());
         if (a.Bs % NSVD_TNT_KC == 0) wgrad_tile_B64<EMIT>(a, h, smem_wg, bid % a.nB, bid / a.nB);
         else wgrad_tile_B<EMIT>(a, h, As, Bs, bid % a.nB, bid / a.nB);
-        WG_STAMP(6, wall_clock64());
         return;
     }
     bid -= a.nB * a.S;
-    WG_STAMP(0, 3ull);
-    WG_STAMP(1, wall_clock64());
     wgrad_tile_C(a, h, As, bid % (4 * a.L), bid / (4 * a.L));
-    WG_STAMP(6, wall_clock64());
 }
 
 // Split-K second pass: gradient = sum of the S partial slices (in slice order), then stored and / or applied
@@ -1095,8 +1074,7 @@ static int fused_backward_impl(const nsvd_model_desc& dfull, const nsvd_params& 
     int SS = 0;
     if (nh == 2 && F == HID && !next && !win && !state && Lc == dfull.L && l0 == 0 && w.gpart &&
         (df || (evd && (evd->moments || evd->part) && evd->Lg % 4 == 0 && evd->Lg <= 128))) {
-        static const char* e = getenv("NSVD_STREAM_BWD");
-        if (!(e && e[0] == '0')) SS = stream_bwd_slices(d, B);
+        SS = stream_bwd_slices(d, B);
     }
     const PartLayout pl = part_layout(d);
     if (SS) {
@@ -1112,30 +1090,14 @@ static int fused_backward_impl(const nsvd_model_desc& dfull, const nsvd_params& 
             sa.pob[i] = pl.ob[i];
         }
         sa.poscales = pl.oscales;
-        {
-            static const char* e2 = getenv("NSVD_STREAM_DBG");
-            sa.dbg = e2 ? atoi(e2) : 0;
-        }
         static bool attr_set = false;
         if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute((const void*)pmlp_stream_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)SB_LDS_BYTES);
+            hipError_t e = hipFuncSetAttribute((const void*)pmlp_stream_bwd2_kernel,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB2_LDS_BYTES);
             if (e != hipSuccess) return -(int)e;
             attr_set = true;
         }
-        static const char* e3 = getenv("NSVD_STREAM_BWD");
-        if (e3 && e3[0] == '1') {  // the one-group form (pmlp_stream_bwd.h), kept for A/B measurements
-            hipLaunchKernelGGL(pmlp_stream_bwd_kernel, dim3(d.L * SS), dim3(256), SB_LDS_BYTES, s, sa);
-        } else {
-            static bool attr2_set = false;
-            if (!attr2_set) {
-                hipError_t er = hipFuncSetAttribute((const void*)pmlp_stream_bwd2_kernel,
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB2_LDS_BYTES);
-                if (er != hipSuccess) return -(int)er;
-                attr2_set = true;
-            }
-            hipLaunchKernelGGL(pmlp_stream_bwd2_kernel, dim3(d.L * SS), dim3(512), SB2_LDS_BYTES, s, sa);
-        }
+        hipLaunchKernelGGL(pmlp_stream_bwd2_kernel, dim3(d.L * SS), dim3(512), SB2_LDS_BYTES, s, sa);
     } else if ((nh == 2 || nh == 3) && chain_only <= 128)
         hipLaunchKernelGGL(pmlp_fused_bwd_chain_kernel<true>, dim3(chain_grid), dim3(256), 0, s, a);
     else
@@ -1247,17 +1209,6 @@ static int fused_backward_impl(const nsvd_model_desc& dfull, const nsvd_params& 
     NSVD_CHECK_LAUNCH();
     return 0;
 }
-
-// developer diagnostic (not in include/nsvd.h): the streaming backward's per-region cycle counts (NSVD_STREAM_DBG = 4)
-extern "C" int nsvd_debug_stream_stamps(unsigned long long* host) {
-    return -(int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_sb_stamps), 8 * sizeof(unsigned long long));
-}
-
-#ifdef NSVD_WG_STAMPS
-extern "C" int nsvd_debug_wgrad_stamps(unsigned long long* host, size_t n) {
-    return -(int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wg_stamps), n * sizeof(unsigned long long));
-}
-#endif
 
 int nsvd_fused_backward(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
                         int B, const float* df, const nsvd_params& g, void* ws, hipStream_t s) {

@@ -70,7 +70,6 @@ struct FwdArgs {
     // launch the direction group that arrives LAST at a (head, sample block) reads the other groups' raw outputs and forms
     // f, Tf itself (fd_math.h: the arithmetic of fd_epilogue_kernel, same bits) - no epilogue launch (round 6)
     unsigned* tickets;
-    unsigned long long* stamps;  // diagnostic build only (NSVD_FWD_STAMPS): per-workgroup s_memtime stamps
 };
 
 
@@ -82,21 +81,12 @@ __device__ __forceinline__ void nsvd_glds16(const float* gsrc, float* lds_base) 
                                      (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
 }
 
-#ifdef NSVD_FWD_STAMPS
-#define NSVD_STAMP(i)                                                                   \
-    if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime();
-#else
-#define NSVD_STAMP(i)
-#endif
 #include "pmlp_layer0_bf3.h"
 
 // BF3 = 1: layer 0 on the bf16 MFMA with three-way split operands (nsvd_layer0_bf3 above); everything after layer 0 is
 //   the same code (one extra barrier after the K loop: the hidden layers' W tile DMA lands in the stage buffers).
 // PL = 1: plain model evaluation (nsvd_model_forward): the E column tiles of a workgroup are E consecutive 32-sample
 // tiles of the batch (no stencil, no jets), so that a head's weight tiles are fetched once per 32 E samples
-#ifdef NSVD_EO_COUNT
-__device__ unsigned long long g_eo_count[8];
-#endif
 template <int E, int JET, int BF3 = 0, int PL = 0, int KS = 0>
 __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
     static_assert(!PL || (!JET && !BF3 && E <= 4), "plain tiles: native fp32 layer 0, at most four sample tiles");
@@ -149,7 +139,6 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
     const int b0 = __builtin_amdgcn_readfirstlane(sb * (PL ? NC : BS));
     grp = __builtin_amdgcn_readfirstlane(grp);
 
-    NSVD_STAMP(0)
     // accumulators start from the bias (z = b + W a): its 16 loads fly under the first chunk's staging instead
     // of sitting, exposed, between the K loop and the softplus
     f32x16 acc[E];
@@ -321,7 +310,6 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
     NSVD_LOAD_CHUNK(0, 0);
     NSVD_STORE_CHUNK(0, 0);
     __syncthreads();
-    NSVD_STAMP(1)
     NSVD_LOAD_CHUNK(1, 1);  // nch = F / 32 is even and >= 4 (F is a multiple of 128)
     Frag<E> f0, f1;
     {
@@ -396,7 +384,6 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
 #undef NSVD_STS
 
     }
-    NSVD_STAMP(2)
     if constexpr (KS == 1) {  // K-split, first launch: leave this slice's accumulators
 #pragma unroll
         for (int e = 0; e < E; ++e)
@@ -510,9 +497,6 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
                     s0v[jj] = nsvd_softplus(z0);
                 }
                 if (__builtin_expect(big > NSVD_EO_TAYLOR_MAX * NSVD_EO_TAYLOR_MAX, 0)) {
-#ifdef NSVD_EO_COUNT
-                    atomicAdd(&g_eo_count[i], 1ull);
-#endif
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj)
 #pragma unroll
@@ -577,7 +561,6 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
                     for (int r = 0; r < 16; ++r) zs[(size_t)acc_row(r, hi) * a.B + e * BS] = acc[e][r];
             }
         }
-        NSVD_STAMP(3 + 4 * i)
         if (!has_next) {
             // ---------------------------------------------------------- last layer 128 -> 1 (weights in nb)
             float part[E];
@@ -594,7 +577,6 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
             }
             break;
         }
-        NSVD_STAMP(4 + 4 * i)
         if constexpr (BF3) {
             // activations -> bf16 planes in LDS, [plane][column][128 k + 16 B pad] (272-B rows: the ds_read_b128
             // fragment reads of 16 consecutive columns hit 16 distinct 4-bank groups); registers 4g .. 4g+3 of a lane
@@ -629,7 +611,6 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            NSVD_STAMP(5 + 4 * i)
             f32x16 accb;  // stencil mode: the centre tile's second accumulator
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -691,7 +672,6 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[0][r] += accb[r];  // (the even / odd tiles stay apart)
             }
-            NSVD_STAMP(6 + 4 * i)
             continue;
         }
         // raw barriers: __syncthreads() would drain the 16 stores above (vmcnt(0)) before every barrier
@@ -710,7 +690,6 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
         if (zs && !(PL && E > 1)) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        NSVD_STAMP(5 + 4 * i)
 #pragma unroll
         for (int e = 0; e < E; ++e)
 #pragma unroll
@@ -732,12 +711,10 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
             if (q + 2 < 16) NSVD_INTERLEAVE(1 + E, 0x100);
             NSVD_FENCE();
         }
-        NSVD_STAMP(6 + 4 * i)
     }
 
 #undef NSVD_INTERLEAVE
 #undef NSVD_FENCE
-    NSVD_STAMP(12)
     __syncthreads();
     if (E == 3 && !JET && !BF3 && a.split) {
         // split-stencil form: raw outputs of the 128 -> 1 layer, one thread per (point, sample)
@@ -821,7 +798,6 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
             if (a.jac) a.jac[idx] = c * mk;
             if (a.dsc) a.dsc[idx] = a.scales ? c * bv * mk * r / (s_l * s_l) : 0.f;
         }
-        NSVD_STAMP(14)
         return;
     }
     if (JET) {
@@ -845,7 +821,6 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
             if (a.jac) a.jac[idx] = o.jac;
             if (a.dsc) a.dsc[idx] = o.dsc;
         }
-        NSVD_STAMP(14)
         return;
     }
     {
@@ -869,7 +844,6 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
             if (a.jac) a.jac[idx] = o.jac;
             if (a.dsc) a.dsc[idx] = o.dsc;
         }
-        NSVD_STAMP(14)
         return;
     }
 }
@@ -971,9 +945,6 @@ int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsv
     // XCD-aware block mapping: split heads into HX groups and sample blocks into 8/HX groups, minimising the
     // bytes each XCD pulls through its L2: (L/HX) * |W_0 slab| + (nsb/SX) * |phi slab|
     a.xcd_remap = pick_xcd_remap(d.L, B / BS, F);
-#ifdef NSVD_FWD_STAMPS
-    a.stamps = (unsigned long long*)w.dz[0];  // diagnostic build: stamps land in the (then unused) dz_0 scratch
-#endif
     if (bf3) {  // opt-in: layer 0 on the bf16 MFMA with three-way split operands
         W0SplitArgs sa;
         memset(&sa, 0, sizeof(sa));
@@ -1093,8 +1064,7 @@ int nsvd_fused_model_forward(const nsvd_model_desc& d, const nsvd_params& p, con
     // the model shape of the kernel-operator row on enough tiles: the streaming form (pmlp_plain_fwd.h) - weights in
     // registers, two workgroups per CU
     {
-        static const char* e = getenv("NSVD_PLAIN_STREAM");
-        const int tpw = (e && e[0] == '0') ? 0 : plain_stream_tpw(d, B);
+        const int tpw = plain_stream_tpw(d, B);
         if (tpw > 0) {
             PlainFwdArgs pa;
             memset(&pa, 0, sizeof(pa));
@@ -1128,13 +1098,3 @@ int nsvd_fused_model_forward(const nsvd_model_desc& d, const nsvd_params& p, con
     a.xcd_remap = pick_xcd_remap(d.L, B / BS, F);
     return launch_fwd<1, 0, 0, 1>(a, s);
 }
-
-#ifdef NSVD_EO_COUNT
-extern "C" void nsvd_debug_eo_count(unsigned long long* out, int reset) {
-    hipMemcpyFromSymbol(out, HIP_SYMBOL(g_eo_count), 8 * sizeof(unsigned long long));
-    if (reset) {
-        unsigned long long z[8] = {0};
-        hipMemcpyToSymbol(HIP_SYMBOL(g_eo_count), z, sizeof(z));
-    }
-}
-#endif

@@ -184,14 +184,10 @@ typedef float nsvd_f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void nsvd_pin(nsvd_f32x4& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ float4 nsvd_f4(const nsvd_f32x4 v) { return __builtin_bit_cast(float4, v); }
 
-// diagnostic builds only (scripts/dev/build_stamps.sh EXTRA=-DNSVD_BF3_EXP=mask): leave parts of the K loop out to
-// price them - 1: the generation of the next pair's sample planes (VALU + LDS stores), 2: the global requests,
-// 4: the barrier, 8: the sample fragment reads. Results are then wrong; only the stamps are read.
-// Measured on the one-barrier-per-chunk, six-products-everywhere form (cycles per 32-wide chunk, cfg2, 1920 of them
-// MFMA issue): everything in 2740; without 1: 2290; without 2: 2500; without 4: 2460; without 8: 2650; MFMAs alone: 1920.
-#ifndef NSVD_BF3_EXP
-#define NSVD_BF3_EXP 0
-#endif
+// What the parts of the K loop cost, measured by leaving each out on the one-barrier-per-chunk, six-products-everywhere
+// form (cycles per 32-wide chunk, cfg2, 1920 of them MFMA issue): everything in 2740; without the generation of the next
+// pair's sample planes (VALU + LDS stores): 2290; without the global requests: 2500; without the barrier: 2460; without
+// the sample fragment reads: 2650; MFMAs alone: 1920.
 // The K loop walks PAIRS of chunks - the 32 sin features k in [32 q, 32 q + 32) and their 32 cos partners - with ONE
 // barrier per pair.
 // Column tiles: tile 0 = the centre rows (three planes, six partial products); tiles 1 .. E-1 = in stencil mode the
@@ -357,8 +353,7 @@ __device__ __forceinline__ void nsvd_layer0_bf3(const FwdArgs& a, f32x16 (&acc)[
 #pragma unroll
         for (int g = 0; g < 4 * NG; ++g) {
             const int s = g / NG, gk = g % NG, h = s >> 1, ks = s & 1;
-            const bool rd = !(NSVD_BF3_EXP & 8);
-            if (s == 3 && gk == 0 && !(NSVD_BF3_EXP & 4)) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            if (s == 3 && gk == 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             // fragment set: k-step s reads set s & 1; A fragments: register set 2 PQ + h
             if (s & 1) {
                 if (h) mma_group(std::integral_constant<int, 2 * PQ + 1>{}, std::integral_constant<int, 1>{}, ks, gk);
@@ -368,25 +363,23 @@ __device__ __forceinline__ void nsvd_layer0_bf3(const FwdArgs& a, f32x16 (&acc)[
                 else mma_group(std::integral_constant<int, 2 * PQ>{}, std::integral_constant<int, 0>{}, ks, gk);
             }
             bool did_frags = false;
-            if (gk == 0 && rd) {
+            if (gk == 0) {
                 if (s == 0) { frags(std::integral_constant<int, 1>{}, PQ, 1); did_frags = true; }
                 if (s == 1) { frags(std::integral_constant<int, 0>{}, PQ, 2); did_frags = true; }
                 if (s == 2) { frags(std::integral_constant<int, 1>{}, PQ, 3); did_frags = true; }
                 if (s == 3 && ST) { frags(std::integral_constant<int, 0>{}, PQ ^ 1, 0); did_frags = true; }
             }
-            const bool gen = ST && !(NSVD_BF3_EXP & 1) && g < 2 * E;
+            const bool gen = ST && g < 2 * E;
             if (gen) {
                 if (g == 0) gen_rows(std::integral_constant<int, 0>{}, FS, rb);
                 if (g == E) gen_rows(std::integral_constant<int, 1>{}, FS, rb);
                 put_row(Bn + (g / E) * HALFB, g % E, rb[g % E]);
             }
             bool did_loads = false;
-            if (!(NSVD_BF3_EXP & 2)) {
-                // (the feature set of pair q + 1 is free once its rows are generated: pair q + 3 goes there)
-                if (g == 2 * E) { load_f(std::integral_constant<int, FS>{}, q + 3); did_loads = true; }
-                if (s == 2 && gk == 1) { load_w(std::integral_constant<int, 2 * PQ>{}, 2 * q + 4); did_loads = true; }
-                if (g == 4 * NG - 1) { load_w(std::integral_constant<int, 2 * PQ + 1>{}, 2 * q + 5); did_loads = true; }
-            }
+            // (the feature set of pair q + 1 is free once its rows are generated: pair q + 3 goes there)
+            if (g == 2 * E) { load_f(std::integral_constant<int, FS>{}, q + 3); did_loads = true; }
+            if (s == 2 && gk == 1) { load_w(std::integral_constant<int, 2 * PQ>{}, 2 * q + 4); did_loads = true; }
+            if (g == 4 * NG - 1) { load_w(std::integral_constant<int, 2 * PQ + 1>{}, 2 * q + 5); did_loads = true; }
             // inside the group: every MFMA followed by its share of the group's other work (a wave issues in order:
             // VALU placed behind all the MFMAs would start only when the last one has issued)
             const int nm = DELTA ? (gk < 3 ? E : 3) : E;  // MFMAs of this group
@@ -438,7 +431,6 @@ __device__ __forceinline__ void nsvd_layer0_bf3(const FwdArgs& a, f32x16 (&acc)[
     load_f(P0{}, 2);
     __syncthreads();
     frags(P0{}, 0, 0);
-    NSVD_STAMP(1)
     int q = 0;
     for (; q + 2 < npair; q += 2) {  // npair is even (F a multiple of 128); branch-free steady state
         pstep(P0{}, T1{}, q);

@@ -790,8 +790,6 @@ __global__ void __launch_bounds__(BN16_NT) tower_bn16_backward_kernel(Bn16Bwd a)
     }
 }
 
-static unsigned long long* g_tcol_stamps = nullptr;  // diagnostic (nsvd_debug_tcol_stamps), or null
-
 inline bool tower16_shape_ok(int B, int d0, int d1, int d2) {
     return tower_shape_ok(B, d0, d1, d2) && B % 256 == 0 && d1 % 256 == 0 && d2 % 256 == 0;
 }
@@ -816,10 +814,9 @@ inline Tower16 views16(const TowerWs& w) {
 // The wide layer with BatchNorm inside the contraction's epilogue (tower_col.h: no Y1h / dA1h round trip, no strip
 // launches) where its recovery of the normalised value from the stored activation is defined: slope > 0. Otherwise (and
 // with NSVD_TOWER16_FUSED=0, for A/B measurements) the contraction + strip pairs below.
-inline bool tower16_fused(int B, int d0, int d1, int d2, float slope, bool backward = false) {
+inline bool tower16_fused(int B, int d0, int d1, int d2, float slope) {
     const char* e = getenv("NSVD_TOWER16_FUSED");  // (read per call: the tests switch forms inside one process)
     if (e && e[0] == '0') return false;
-    if (e && e[0] == 'b' && !backward) return false;  // (diagnostic: strip forward + whole-column backward)
     return slope >= 1e-3f && nsvd_tcol::shape_ok(B, d1, d0) && nsvd_tcol::shape_ok(B, d1, d2);
 }
 
@@ -886,7 +883,6 @@ int tower16_forward(int nt, const float* const* x, const nsvd_tower_params* cons
         }
         c.nt = nt; c.M = B; c.N = d1; c.K = d0; c.eps = eps; c.momentum = momentum; c.slope = slope;
         c.f16 = (flags & NSVD_TOWER16_F16) ? 1 : 0;
-        c.stamps = g_tcol_stamps;
         nsvd_prof_begin(s);  // bench.py --config cfg5 --amp brackets this launch (nsvd_profile_next_forward)
         rc = nsvd_tcol::launch<false>(c, s);
         nsvd_prof_end(s);
@@ -974,7 +970,7 @@ int tower16_backward(int nt, const float* const* x, const nsvd_tower_params* con
         if (rc) return rc;
     }
     nsvd_g16::Args g;
-    if (tower16_fused(B, d0, d1, d2, slope, true)) {
+    if (tower16_fused(B, d0, d1, d2, slope)) {
         // dY1h = BN1'(lrelu'(dY2h W2h)), dgamma1, dbeta1, db1 in ONE launch (tower_col.h)
         nsvd_tcol::Args c;
         memset(&c, 0, sizeof(c));
@@ -986,7 +982,6 @@ int tower16_backward(int nt, const float* const* x, const nsvd_tower_params* con
         }
         c.nt = nt; c.M = B; c.N = d1; c.K = d2; c.slope = slope;
         c.f16 = (flags & NSVD_TOWER16_F16) ? 1 : 0;
-        c.stamps = g_tcol_stamps;
         rc = nsvd_tcol::launch<true>(c, s);
         if (rc) return rc;
     } else {
@@ -1138,19 +1133,6 @@ extern "C" int nsvd_tower_mixed_supported(int B, int d0, int d1, int d2) { retur
 
 extern "C" int nsvd_tower_mixed_fused(int B, int d0, int d1, int d2, float slope) {
     return tower16_shape_ok(B, d0, d1, d2) && tower16_fused(B, d0, d1, d2, slope) ? 1 : 0;
-}
-
-// developer diagnostic (not in include/nsvd.h): the first call arms the stamps of the whole-column launches (cycles of
-// block 0 / wave 0: prologue, K loop, epilogue, stages), later calls read the last launch's
-extern "C" int nsvd_debug_tcol_stamps(unsigned long long* host) {
-    if (!g_tcol_stamps) {
-        hipError_t e = hipMalloc((void**)&g_tcol_stamps, (4 + 4 * 1024) * sizeof(unsigned long long));
-        if (e != hipSuccess) return -(int)e;
-        return -(int)hipMemset(g_tcol_stamps, 0, (4 + 4 * 1024) * sizeof(unsigned long long));
-    }
-    hipError_t e = hipMemcpy(host, g_tcol_stamps, (4 + 4 * 1024) * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return -(int)e;
-    return -(int)hipMemset(g_tcol_stamps + 4, 0, 4 * 1024 * sizeof(unsigned long long));  // (the end stamps are atomic maxima)
 }
 
 // both towers of a mixed-precision CDK step through every launch together (cdk_step.hip); flags: the gemm_bf16 bits

@@ -70,7 +70,6 @@ struct Args {
     float eps, momentum, slope;
     int nwg;
     int f16;  // the half type is IEEE float16 instead of bfloat16 (gemm16.h: pack_h)
-    unsigned long long* stamps;  // diagnostic, or null: cycles of block 0 / wave 0 - prologue, K loop, epilogue
 };
 
 // sum over the 16 lanes that share lane >> 4 (the 16 rows of a block), fixed butterfly order; every lane gets the sum
@@ -110,9 +109,6 @@ __global__ void __launch_bounds__(512) tower_col_kernel(Args a) {
     const int K = a.K, N = a.N, M = a.M;
     const int nkt = K / BK;
     const int NS = NP * nkt;
-
-    const unsigned long long ts0 = a.stamps ? __builtin_readcyclecounter() : 0ull;
-    const unsigned long long wc0 = a.stamps ? wall_clock64() : 0ull;
 
     // ---- DMA sources
     const char* sa = reinterpret_cast<const char*>(P.A) + 2L * (long)(w * RW) * K;
@@ -186,7 +182,6 @@ __global__ void __launch_bounds__(512) tower_col_kernel(Args a) {
     // ---- prologue: NBUF - 1 stages in flight
     TC_ISSUE();
     if (NBUF == 3 && NS > 1) TC_ISSUE();
-    const unsigned long long ts1 = a.stamps ? __builtin_readcyclecounter() : 0ull;
 
     int step = 0, buf = 0;
 #pragma unroll
@@ -224,8 +219,6 @@ __global__ void __launch_bounds__(512) tower_col_kernel(Args a) {
     }
 #undef TC_ISSUE
 #undef TC_TR
-    const unsigned long long ts2 = a.stamps ? __builtin_readcyclecounter() : 0ull;
-    const unsigned long long wc1 = a.stamps ? wall_clock64() : 0ull;
 
     // ---- epilogue. lane = row 16 i + l15 of the wave's rows; registers = columns 16 j + 4 g4 .. + 3 of the tile.
     __syncthreads();  // every wave is done reading the last stage: the ring is free
@@ -467,17 +460,6 @@ __global__ void __launch_bounds__(512) tower_col_kernel(Args a) {
         }
         store_image();
     }
-    if (a.stamps && blockIdx.x == 0 && tid == 0) {
-        a.stamps[0] = ts1 - ts0; a.stamps[1] = ts2 - ts1; a.stamps[2] = __builtin_readcyclecounter() - ts2;
-        a.stamps[3] = (unsigned long long)NS;
-    }
-    if (a.stamps) {  // every block: start / loop end / end on the 100 MHz clock (waves may end apart: the last one wins)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) {
-            if (w == 0) { a.stamps[4 + 4 * blockIdx.x] = wc0; a.stamps[5 + 4 * blockIdx.x] = wc1; }
-            atomicMax(&a.stamps[6 + 4 * blockIdx.x], wall_clock64());
-        }
-    }
 #undef TC_WAIT_BARRIER
 }
 
@@ -522,16 +504,14 @@ inline int launch(const Args& a0, hipStream_t s) {
             return NSVD_EINVAL;
     }
     a.nwg = a.nt * (a.N / TN);
-    // stages: at 128 rows per wave two passes of 4 row blocks with two 72 KB buffers, or four passes of 2 with three
-    // 40 KB buffers (NSVD_TCOL_FORM=b)
-    static const char* form = getenv("NSVD_TCOL_FORM");
-    const bool fb = form && form[0] == 'b';
+    // stages: at 64 and 128 rows per wave, passes of 4 row blocks with two 72 KB buffers (passes of 2 with three 40 KB
+    // buffers lost the A/B measurement)
     int rc;
     switch (a.M / 128) {
         case 2: rc = launch_inst<BWD, 2, 2, 3>(a, s); break;
-        case 4: rc = fb ? launch_inst<BWD, 4, 2, 3>(a, s) : launch_inst<BWD, 4, 4, 2>(a, s); break;
+        case 4: rc = launch_inst<BWD, 4, 4, 2>(a, s); break;
         case 6: rc = launch_inst<BWD, 6, 3, 2>(a, s); break;
-        default: rc = fb ? launch_inst<BWD, 8, 2, 3>(a, s) : launch_inst<BWD, 8, 4, 2>(a, s); break;
+        default: rc = launch_inst<BWD, 8, 4, 2>(a, s); break;
     }
     if (rc) return rc;
     NSVD_CHECK_LAUNCH();

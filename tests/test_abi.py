@@ -20,6 +20,15 @@ def test_header_declares_what_binding_binds():
     assert _declared() == sorted(_lib.SIGNATURES.keys())
 
 
+def _exported(path):
+    """the nsvd_* symbols the library defines in its dynamic symbol table"""
+    import subprocess
+    objdump = os.environ.get("LLVM_OBJDUMP", "/opt/rocm/lib/llvm/bin/llvm-objdump")
+    out = subprocess.check_output([objdump, "-T", path], text=True)
+    return sorted({ln.split()[-1] for ln in out.splitlines()
+                   if ln.split() and ln.split()[-1].startswith("nsvd_") and "*UND*" not in ln})
+
+
 def test_library_exports_every_declared_symbol():
     from neural_svd_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):
@@ -28,6 +37,7 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in _declared():
         assert hasattr(lib, name), name
+    assert _exported(_lib.LIB_PATH) == _declared()
     typed = _lib.load()
     assert typed.nsvd_abi_version() == _lib.ABI_VERSION
 
