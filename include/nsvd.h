@@ -583,8 +583,9 @@ typedef struct nsvd_cdk_step_desc {
  *     growth_tracker += 1 and at growth_interval: scale *= growth_factor, growth_tracker = 0 (GradScaler.update()).
  *   desc.first_step is ignored: the momentum buffers start with the first step TAKEN (steps_ok == 0), as torch.optim.SGD
  *   creates them in its first executed step().
- * The loss values reported are unscaled. Needs the mixed-precision step with the fused narrow end (B % 8 == 0,
- * d2 % 64 == 0, d2 <= 1024), NSVD_EUNSUPPORTED otherwise. Read the state back with a device-to-host copy. */
+ * The loss values reported are unscaled. Needs the mixed-precision step with the fused narrow end (cdk_narrow.hip:
+ * B % 8 == 0, d2 <= 1024 and d2 / 4 dividing 256 - with the mixed-precision rule d2 % 256 == 0: d2 in {256, 512, 1024}),
+ * NSVD_EUNSUPPORTED otherwise. Read the state back with a device-to-host copy. */
 typedef struct nsvd_grad_scaler {
     float scale;
     float growth_factor;      /* torch default 2 */

@@ -358,12 +358,14 @@ class FusedCdkStep:
     growth_interval clean steps (main_sketchy.py:194-208; torch defaults 65536 / 2 / 0.5 / 2000). All of it on the
     device: ``scaler_state()`` reads it back. The learning-rate schedule advances on every iteration, skipped or not,
     as the script's does (main_sketchy.py:205-206: no scheduler gate there, unlike the PDE loop). Same kernels as the bfloat16 mode with the float16 MFMA; pinned to the float64 oracle
-    with the same roundings and the same scaler arithmetic (oracle.cdk_train_step(half="f16", scaler=...))."""
+    with the same roundings and the same scaler arithmetic (oracle.cdk_train_step(half="f16", scaler=...)). The
+    GradScaler needs the towers' output width d2 in SCALER_WIDTHS (256, 512, 1024): at any other width float16 is
+    refused with that reason unless grad_scaler=False is passed (it is never dropped silently)."""
 
     def __init__(self, method: "NestedLoRAForCDK", lr: float, momentum: float = 0.9, max_grad_norm: float = 1.0,
                  t_max: int = 0, batch_size: int = 1024, use_amp: bool = False, amp_dtype: str = "bfloat16",
                  grad_scaler=None, init_scale: float = 65536.0, growth_interval: int = 2000):
-        ok, why = self.supported(method, batch_size, use_amp)
+        ok, why = self.supported(method, batch_size, use_amp, amp_dtype, grad_scaler)
         if not ok:
             raise H.NsvdError(f"FusedCdkStep: {why}")
         if amp_dtype not in ("bfloat16", "float16"):
@@ -404,8 +406,16 @@ class FusedCdkStep:
                 H.GradScaler(dev, init_scale=init_scale, growth_interval=growth_interval)
         self.ws = H.cdk_step_workspace(self._desc(self.lr0, True), dev)
 
+    # output widths the GradScaler takes: the loss scale enters where the backward starts, inside the fused narrow end
+    # of the mixed-precision step (cdk_narrow.hip: its 256 threads a multiple of the d2 / 4 column quads, d2 <= 1024; with the
+    # mixed-precision rule d2 % 256 == 0 that leaves these three). Other widths run the stage kernels, which do not scale.
+    SCALER_WIDTHS = (256, 512, 1024)
+
     @staticmethod
-    def supported(method, batch_size: int, use_amp: bool = False):
+    def supported(method, batch_size: int, use_amp: bool = False, amp_dtype: str = "bfloat16", grad_scaler=None):
+        """(ok, reason): does the fused step take this method and batch with these options? grad_scaler as for the
+        constructor (None: on for use_amp with amp_dtype "float16"). A GradScaler needs the towers' output width d2 in
+        SCALER_WIDTHS: float16 at another width is refused unless the caller passes grad_scaler=False."""
         model = getattr(method, "model", None)
         if not isinstance(method, NestedLoRAForCDK) or not isinstance(model, HeteroNetwork):
             return False, "needs NestedLoRAForCDK over a HeteroNetwork"
@@ -429,6 +439,10 @@ class FusedCdkStep:
         if use_amp and not H.tower_mixed_supported(batch_size, d0, d1, d2):
             return False, (f"tower shape {(batch_size, d0, d1, d2)} outside the mixed-precision kernels (batch and the "
                            f"two output widths multiples of 256)")
+        scaled = (bool(use_amp) and amp_dtype == "float16") if grad_scaler is None else bool(grad_scaler)
+        if scaled and use_amp and d2 not in FusedCdkStep.SCALER_WIDTHS:
+            return False, (f"the GradScaler needs the towers' output width d2 in {FusedCdkStep.SCALER_WIDTHS} (got "
+                           f"{d2}); pass grad_scaler=False to run float16 without loss scaling")
         return True, ""
 
     def _weights(self):

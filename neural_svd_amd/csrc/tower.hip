@@ -403,21 +403,20 @@ __global__ void __launch_bounds__(NT) tower_bn_backward_kernel(BnBwd a) {
 // Wide layers (>= 4096 columns): 32-column strips in 512-thread workgroups - a row of the strip is one whole 128-byte
 // line (with 16-column strips the two halves of a line went to two workgroups, as a rule on two XCDs: every line
 // crossed the fabric twice) and 8 waves keep the rows-per-thread count at 16 float4 (8192 columns = 256 workgroups,
-// one per CU). Narrower strips below 4096 columns so that a 512-wide layer spreads over 128 (4 columns, batch a
-// multiple of 256) or 64 (8 columns) workgroups instead of 16.
+// one per CU; every tower width is a multiple of 128, so no wide layer needs a narrower strip). Narrower strips below
+// 4096 columns so that a 512-wide layer spreads over 128 (4 columns, batch a multiple of 256) or 64 (8 columns)
+// workgroups instead of 16.
 inline int launch_bn_forward(const BnFwd& f, hipStream_t s) {
-    if (f.B % 128 || f.B > 1024 || f.N % 16) return NSVD_EINVAL;
-    if (f.N >= 4096 && f.N % 32 == 0) hipLaunchKernelGGL((tower_bn_forward_kernel<32, 512>), dim3(f.N / 32), dim3(512), 0, s, f);
-    else if (f.N >= 4096) hipLaunchKernelGGL((tower_bn_forward_kernel<16, 256>), dim3(f.N / 16), dim3(256), 0, s, f);
+    if (f.B % 128 || f.B > 1024 || f.N % (f.N >= 4096 ? 32 : 16)) return NSVD_EINVAL;
+    if (f.N >= 4096) hipLaunchKernelGGL((tower_bn_forward_kernel<32, 512>), dim3(f.N / 32), dim3(512), 0, s, f);
     else if (f.B % 256 == 0) hipLaunchKernelGGL((tower_bn_forward_kernel<4, 256>), dim3(f.N / 4), dim3(256), 0, s, f);
     else hipLaunchKernelGGL((tower_bn_forward_kernel<8, 256>), dim3(f.N / 8), dim3(256), 0, s, f);
     NSVD_CHECK_LAUNCH();
     return 0;
 }
 inline int launch_bn_backward(const BnBwd& b, hipStream_t s) {
-    if (b.B % 128 || b.B > 1024 || b.N % 16) return NSVD_EINVAL;
-    if (b.N >= 4096 && b.N % 32 == 0) hipLaunchKernelGGL((tower_bn_backward_kernel<32, 512>), dim3(b.N / 32), dim3(512), 0, s, b);
-    else if (b.N >= 4096) hipLaunchKernelGGL((tower_bn_backward_kernel<16, 256>), dim3(b.N / 16), dim3(256), 0, s, b);
+    if (b.B % 128 || b.B > 1024 || b.N % (b.N >= 4096 ? 32 : 16)) return NSVD_EINVAL;
+    if (b.N >= 4096) hipLaunchKernelGGL((tower_bn_backward_kernel<32, 512>), dim3(b.N / 32), dim3(512), 0, s, b);
     else if (b.B % 256 == 0) hipLaunchKernelGGL((tower_bn_backward_kernel<4, 256>), dim3(b.N / 4), dim3(256), 0, s, b);
     else hipLaunchKernelGGL((tower_bn_backward_kernel<8, 256>), dim3(b.N / 8), dim3(256), 0, s, b);
     NSVD_CHECK_LAUNCH();

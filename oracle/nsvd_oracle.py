@@ -584,7 +584,7 @@ def tower_forward_backward(x, P, dz, slope, eps=1e-5, gemm_bf16=False, half="bf1
 
 
 def cdk_train_step(x, y, towers, bufs, running, v, M, mu, lr, momentum, max_norm, slope, first_step, eps=1e-5,
-                   bn_momentum=0.1, gemm_bf16=False, half="bf16", scaler=None):
+                   bn_momentum=0.1, gemm_bf16=False, half="bf16", scaler=None, mode="l2_ball", set_first_mode_const=True):
     """One Sketchy-style CDK training step (reference examples/cdk/sketchy/main_sketchy.py:180-212 with
     scripts/exps/sketchy.sh's switches, AMP off): two towers (get_mlp, examples/models/mlp.py:129-164) behind Identity
     projectors and normalize('l2_ball', sqrt(mu)) (examples/models/siam.py:156-183), NestedLoRAForCDK loss
@@ -599,7 +599,10 @@ def cdk_train_step(x, y, towers, bufs, running, v, M, mu, lr, momentum, max_norm
     growth_tracker, steps_ok, steps_skipped (updated in place): the loss gradient is multiplied by scale before the
     towers' backward; found_inf = the norm of the SCALED gradients is not finite -> nothing is updated, scale *= backoff;
     else gradients * (1 / scale), clip, SGD, steps_ok += 1, and every growth_interval clean steps scale *= growth.
-    first_step is then steps_ok == 0 (torch.optim.SGD creates its momentum buffers in the first step it executes)."""
+    first_step is then steps_ok == 0 (torch.optim.SGD creates its momentum buffers in the first step it executes).
+    mode: the normalisation, "l2_ball" (scripts/exps/sketchy.sh) or "l2_sphere" (siam.py:178-180);
+    set_first_mode_const: NestedLoRAForCDK's constant first mode (v, M must be the masks built with the same value:
+    cdk_masks). Both pinned by tests/golden/cdk_step_opts.npz."""
     r_up = float(mu) ** 0.5
     if scaler is not None:
         first_step = scaler["steps_ok"] == 0
@@ -609,8 +612,8 @@ def cdk_train_step(x, y, towers, bufs, running, v, M, mu, lr, momentum, max_norm
                                          gemm_bf16, half)
         zr = z.detach().clone().requires_grad_(True)
         zs.append(zr)
-        embs.append(row_normalize(zr, r_up, "l2_ball"))
-    loss, lop, lmet, _, _, gf, gg = cdk_loss(embs[0].detach(), embs[1].detach(), v, M, True)
+        embs.append(row_normalize(zr, r_up, mode))
+    loss, lop, lmet, _, _, gf, gg = cdk_loss(embs[0].detach(), embs[1].detach(), v, M, set_first_mode_const)
     grads = []
     for inp, P, zr, e, ge, run in ((x, towers[0], zs[0], embs[0], gf, running[0]),
                                    (y, towers[1], zs[1], embs[1], gg, running[1])):

@@ -575,6 +575,64 @@ def golden_cdk_step(out):
                 out[q + f"buf_{k}"] = a
 
 
+def golden_cdk_step_opts(out):
+    """The Sketchy training step of golden_cdk_step with the options it leaves at their sketchy.sh values: case oa -
+    regularize_mode='l2_sphere' (models/siam.py:178-180) with sequential nesting masks (methods/nestedlora.py:348-349);
+    case ob - 'l2_ball' with joint masks at step = 2 and set_first_mode_const=False (:350-358, --neuralsvd.step /
+    --neuralsvd.sequential). Two SGD steps each at a tiny shape, float64 only (the oracle is held to it at float64
+    precision). Stored: initial parameters and running statistics, inputs, masks, per-step loss triple and total gradient
+    norm, and every parameter / momentum buffer / running statistic after the last step."""
+    from examples.models.mlp import get_mlp
+    from examples.models.siam import HeteroNetwork
+    from methods.nestedlora import NestedLoRAForCDK
+    cases = dict(oa=dict(sizes=[8, 12, 6], B=10, mu=4.0, lr=5e-2, seed=43, T=10, mode="l2_sphere", seq=True, step=1,
+                         first=True),
+                 ob=dict(sizes=[8, 12, 6], B=10, mu=4.0, lr=5e-2, seed=44, T=10, mode="l2_ball", seq=False, step=2,
+                         first=False))
+    NSTEP = 2
+    for name, c in cases.items():
+        sizes, B, L = c["sizes"], c["B"], c["sizes"][-1]
+        g = torch.Generator().manual_seed(3000 + c["seed"])
+        xs = torch.randn(NSTEP, B, sizes[0], generator=g, dtype=torch.float64)
+        ys = torch.randn(NSTEP, B, sizes[0], generator=g, dtype=torch.float64)
+        out[f"{name}_x"], out[f"{name}_y"] = xs.numpy(), ys.numpy()
+        out[f"{name}_cfg"] = np.array([B, sizes[0], sizes[1], sizes[2], c["seed"], NSTEP, c["T"]])
+        out[f"{name}_hyper"] = np.array([c["mu"], c["lr"], 0.9, 1.0, 0.2])  # mu, lr, momentum, max_norm, slope
+        # mode (1 = l2_sphere), sequential, step, set_first_mode_const
+        out[f"{name}_opts"] = np.array([int(c["mode"] == "l2_sphere"), int(c["seq"]), c["step"], int(c["first"])])
+        torch.manual_seed(c["seed"])
+        model = HeteroNetwork(backbones=[get_mlp(sizes=sizes, bias=True, nonlinearity="lrelu0.2", use_bn=True),
+                                         get_mlp(sizes=sizes, bias=True, nonlinearity="lrelu0.2", use_bn=True)],
+                              projectors=[nn.Identity(), nn.Identity()], mu=c["mu"], regularize_mode=c["mode"])
+        for k, v in model.state_dict().items():
+            if "num_batches" not in k:
+                out[f"{name}_param0_{k}"] = v.detach().double().numpy()
+        model = model.double().train()
+        method = NestedLoRAForCDK(model, neigs=L, step=c["step"], sequential=c["seq"], set_first_mode_const=c["first"])
+        out[f"{name}_v"], out[f"{name}_M"] = np64(method.vector_mask), np64(method.matrix_mask)
+        method.vector_mask, method.matrix_mask = method.vector_mask.double(), method.matrix_mask.double()
+        opt = torch.optim.SGD(model.parameters(), lr=c["lr"], momentum=0.9, weight_decay=0.0)
+        sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, c["T"])
+        losses, norms = [], []
+        for t in range(NSTEP):
+            opt.zero_grad()
+            _, fx, _, fy = method(xs[t], ys[t])
+            loss, lop, lmet, rj, ri = method.compute_loss(fx, fy)
+            loss.backward()
+            total_norm = nn.utils.clip_grad_norm_(model.parameters(), max_norm=1.0)
+            opt.step()
+            sched.step()
+            losses.append([float(loss), float(lop), float(lmet)])
+            norms.append(float(total_norm))
+        q = f"{name}_f64_"
+        out[q + "loss"], out[q + "total_norm"] = np.array(losses), np.array(norms)
+        for k, v in model.state_dict().items():
+            if "num_batches" not in k:
+                out[q + f"param_{k}"] = np64(v)
+        for k, prm in model.named_parameters():
+            out[q + f"buf_{k}"] = np64(opt.state[prm]["momentum_buffer"])
+
+
 def golden_amp(out):
     """The reference's AMP branch (on by default in the Sketchy script: examples/cdk/sketchy/main_sketchy.py:161,182,
     194-208) run HERE, on the CPU: torch.cuda.amp.autocast disables itself without a CUDA device, so the same modules run
@@ -716,6 +774,12 @@ def main():
         np.savez_compressed(os.path.join(HERE, "cdk_step.npz"), **o)
         print("cdk_step", os.path.getsize(os.path.join(HERE, "cdk_step.npz")) // 1024, "KiB")
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "cdk_step_opts":
+        o = {}
+        golden_cdk_step_opts(o)
+        np.savez_compressed(os.path.join(HERE, "cdk_step_opts.npz"), **o)
+        print("cdk_step_opts", os.path.getsize(os.path.join(HERE, "cdk_step_opts.npz")) // 1024, "KiB")
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "tower":
         o = {}
         golden_tower(o)
@@ -752,6 +816,9 @@ def main():
     o = {}
     golden_cdk_step(o)
     np.savez_compressed(os.path.join(HERE, "cdk_step.npz"), **o)
+    o = {}
+    golden_cdk_step_opts(o)
+    np.savez_compressed(os.path.join(HERE, "cdk_step_opts.npz"), **o)
     o = {}
     golden_tower(o)
     np.savez_compressed(os.path.join(HERE, "tower.npz"), **o)

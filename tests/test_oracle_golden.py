@@ -393,7 +393,7 @@ def cdk_step_case(z, name, dtype=torch.float64):
     """initial state of golden case `name` of cdk_step.npz: towers, momentum buffers, running statistics, inputs"""
     B, d0, d1, d2, seed, nstep, T = [int(v) for v in z[f"{name}_cfg"]]
     towers, running = [], []
-    if name == "sa":
+    if f"{name}_param0_backbones.x.0.weight" in z:
         for side in "xy":
             p = f"{name}_param0_backbones.{side}."
             towers.append({k: torch.tensor(z[p + n]).to(dtype).clone() for k, n in CDK_KEYS.items()})
@@ -453,6 +453,58 @@ def test_cdk_train_step_matches_reference(name):
         for rk, n in (("rm1", "1.running_mean"), ("rv1", "1.running_var"), ("rm2", "4.running_mean"), ("rv2", "4.running_var")):
             got, want = R[rk].numpy(), z[q + f"param_backbones.{side}.{n}"]
             assert np.allclose(got.reshape(-1)[::5] if name == "sb" else got, want, rtol=1e-9, atol=1e-12), rk
+
+
+@pytest.mark.parametrize("name", ["oa", "ob"])
+def test_cdk_train_step_options_match_reference(name):
+    """oracle cdk_train_step(mode=, set_first_mode_const=) == the reference's Sketchy step with the options the other
+    fixture leaves at their defaults (tests/golden/cdk_step_opts.npz): oa - l2_sphere normalisation, sequential masks;
+    ob - l2_ball, joint masks at step 2, no constant first mode. Two steps each: losses, total gradient norms, every
+    parameter, momentum buffer and running statistic at float64 precision. The masks come from the oracle's own
+    cdk_masks and must equal the reference's."""
+    z = G.load("cdk_step_opts")
+    towers, bufs, running, xs, ys, nstep, T = cdk_step_case(z, name)
+    mu, lr0, mom, max_norm, slope = [float(v) for v in z[f"{name}_hyper"]]
+    sphere, seq, step, first = [int(v) for v in z[f"{name}_opts"]]
+    L = towers[0]["W2"].shape[0]
+    v, M = O.cdk_masks(L, bool(seq), step, bool(first))
+    assert np.array_equal(v.numpy(), z[f"{name}_v"]) and np.array_equal(M.numpy(), z[f"{name}_M"])
+    v, M = v.double(), M.double()
+    q = f"{name}_f64_"
+    for t in range(nstep):
+        lr = O.cosine_lr(lr0, t, T)
+        (loss, lop, lmet), total = O.cdk_train_step(xs[t], ys[t], towers, bufs, running, v, M, mu, lr, mom, max_norm, slope,
+                                                    first_step=(t == 0), mode="l2_sphere" if sphere else "l2_ball",
+                                                    set_first_mode_const=bool(first))
+        want = z[q + "loss"][t]
+        for got, w in zip((loss, lop, lmet), want):
+            assert abs(float(got) - w) < 1e-10 * max(1.0, abs(w)), (t, float(got), w)
+        assert abs(float(total) - z[q + "total_norm"][t]) < 1e-10 * z[q + "total_norm"][t]
+    for side, P, Bf, R in (("x", towers[0], bufs[0], running[0]), ("y", towers[1], bufs[1], running[1])):
+        for k, n in CDK_KEYS.items():
+            key = f"backbones.{side}.{n}"
+            assert np.allclose(P[k].numpy(), z[q + f"param_{key}"], rtol=1e-9, atol=1e-12), key
+            assert np.allclose(Bf[k].numpy(), z[q + f"buf_{key}"], rtol=1e-8, atol=1e-11), key
+        for rk, n in (("rm1", "1.running_mean"), ("rv1", "1.running_var"), ("rm2", "4.running_mean"), ("rv2", "4.running_var")):
+            assert np.allclose(R[rk].numpy(), z[q + f"param_backbones.{side}.{n}"], rtol=1e-9, atol=1e-12), rk
+
+
+def test_cdk_train_step_option_defaults_are_the_sketchy_switches():
+    """the new keywords' defaults leave the step as it was: l2_ball with a constant first mode, bit for bit"""
+    z = G.load("cdk_step")
+    runs = []
+    for kw in ({}, dict(mode="l2_ball", set_first_mode_const=True)):
+        towers, bufs, running, xs, ys, nstep, T = cdk_step_case(z, "sa")
+        mu, lr0, mom, max_norm, slope = [float(v) for v in z["sa_hyper"]]
+        v, M = torch.tensor(z["sa_v"]).double(), torch.tensor(z["sa_M"]).double()
+        out = [O.cdk_train_step(xs[t], ys[t], towers, bufs, running, v, M, mu, O.cosine_lr(lr0, t, T), mom, max_norm,
+                                slope, t == 0, **kw) for t in range(nstep)]
+        runs.append((out, towers, bufs))
+    (o1, t1, b1), (o2, t2, b2) = runs
+    for (l1, n1), (l2, n2) in zip(o1, o2):
+        assert all(torch.equal(a, b) for a, b in zip(l1, l2)) and torch.equal(n1, n2)
+    for a, b in zip(t1 + b1, t2 + b2):
+        assert all(torch.equal(a[k], b[k]) for k in a)
 
 
 # ------------------------------------------------------------------ the reference's AMP branch (float16 autocast + GradScaler)
