@@ -620,6 +620,43 @@ int nsvd_gemm_bf16(const void* A, const void* B, void* C, const float* bias, int
 /* out[i] = bfloat16(in[i]) (round to nearest even), n % 8 == 0, 16-byte aligned pointers */
 int nsvd_to_bf16(const float* in, void* out, size_t n, void* stream);
 
+/* ---- NeuralEF (mu-EigenGame) on the operator path: methods/neuralef.py, methods/utils.py:36-68 ------------------
+ * nsvd_nef_operator_forward: Tphi, phi = operator(BatchL2NormalizedFunctions(model), x, importance) in training mode
+ * (neuralef.py:139-152 -> diff_ops.py:25-52). Each of the 1 + 2D stencil points is divided by its own per-head batch
+ * norm n_e = ||u_e[:, l]|| / sqrt(B) of the WaveFunctions output u_e (utils.py:48-56); the shifted norms come from the
+ * even / odd rows (n_e^2 - n_0^2 formed per sample) and 1 / n_e is folded into the even / odd stencil. The running
+ * norms norm_biased / norm_unbiased (1, L) take 1 + 2D updates in stencil order (utils.py:58-68); *initialized == 0
+ * makes the first one a copy, and the call sets it to 1 (device int, so a step can be captured in a graph).
+ * Outputs phi, Tphi (B, L), and for nsvd_nef_operator_backward: h = u0 / n0, r = sqrt p / clamp(sqrt p, 1e-5) (B, L),
+ * stats ((1 + 2D) L: n0, then n0 / n_e - 1 per shifted point). ws: as for nsvd_operator_forward (always saved for the
+ * backward). Float32 stencil paths only (PATH_AUTO / FUSED / GENERIC; eps > 0). */
+int nsvd_nef_operator_forward(const nsvd_model_desc* desc, const nsvd_params* params, const nsvd_problem* prob,
+                              const float* x, int B, float* phi, float* Tphi, float* h, float* r, float* stats,
+                              float* norm_biased, float* norm_unbiased, int* initialized, float momentum, void* ws,
+                              size_t ws_bytes, int path, void* stream);
+
+/* Parameter gradients of sum(dphi * phi) through the centre evaluation and its batch normalisation (Tphi gets no
+ * gradient, neuralef.py:61-62): du0 = (dh - h mean_b(dh h)) / n0 with dh = r dphi, then nsvd_operator_backward's centre
+ * backward on du0 (du0: (B, L) scratch). Gradients are OVERWRITTEN. */
+int nsvd_nef_operator_backward(const nsvd_model_desc* desc, const nsvd_params* params, const nsvd_problem* prob,
+                               const float* x, int B, const float* dphi, const float* h, const float* r,
+                               const float* stats, float* du0, const nsvd_params* grads, void* ws, size_t ws_bytes,
+                               int path, void* stream);
+
+/* NeuralEigenfunctionsLossFunction (methods/neuralef.py:13-62): loss[0] and d loss / d phi. variance = -Tphi / B;
+ * unbiased: coeff_h = triu(phi_h^T phi_h / B_h, diagonal); biased: coeff_1 = triu(Q_2, diagonal) / (diag(Q_2) + 1e-5)
+ * by row, Q_h = phi_h^T Tphi_h / B_h (each half the other's); align_h = Tphi_h coeff_h / B_h;
+ * loss = sum(phi variance) + (sum(phi1 align_1) + sum(phi2 align_2)) / 2. phi1 / phi2 the two chunks of phi (B1 =
+ * ceil(B / 2)): dphi = 4 variance + 2 align_h by rows (dphi1 / dphi2 unused); otherwise independent halves: dphi = 4
+ * variance, dphi1 = 2 align_1, dphi2 = 2 align_2. The incoming gradient is ignored, as in the reference. L <= 64. */
+size_t nsvd_nef_loss_workspace_bytes(int B, int B1, int B2, int L);
+int nsvd_nef_loss(const float* phi, const float* Tphi, int B, const float* phi1, const float* Tphi1, int B1,
+                  const float* phi2, const float* Tphi2, int B2, int L, int unbiased, int diagonal, float* loss,
+                  float* dphi, float* dphi1, float* dphi2, void* scratch, size_t scratch_bytes, void* stream);
+
+/* f[b, l] /= norm[l], Tf[b, l] /= norm[l] in place: BatchL2NormalizedFunctions in evaluation mode (utils.py:54-56). */
+int nsvd_nef_scale_heads(float* f, float* Tf, const float* norm, int B, int L, void* stream);
+
 /* Measurement aid (bench.py): record the two hipEvent_t handles immediately before / after the
  * DOMINANT kernel of the next nsvd_operator_forward call made by this host thread (the fused MFMA
  * forward kernel, or the layer-0 GEMM on the generic path), on that call's stream - or, whichever

@@ -152,6 +152,13 @@ SIGNATURES = {
     "nsvd_cdk_step_workspace_bytes": (_Z, [C.POINTER(CdkStepDesc)]),
     "nsvd_cdk_step": (_I, [C.POINTER(CdkStepDesc), _P, _P, C.POINTER(TowerParams), C.POINTER(TowerParams), _P, _P, _P,
                            _P, _P, _P, _Z, _P]),
+    "nsvd_nef_operator_forward": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem), _P, _I, _P, _P, _P,
+                                       _P, _P, _P, _P, _P, _F, _P, _Z, _I, _P]),
+    "nsvd_nef_operator_backward": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem), _P, _I, _P, _P, _P,
+                                        _P, _P, C.POINTER(Params), _P, _Z, _I, _P]),
+    "nsvd_nef_loss_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "nsvd_nef_loss": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "nsvd_nef_scale_heads": (_I, [_P, _P, _P, _I, _I, _P]),
     "nsvd_tower_backward": (_I, [_P, C.POINTER(TowerParams), _P, _I, _I, _I, _I, _F, _I, C.POINTER(TowerParams), _P,
                                  _Z, _P]),
 }

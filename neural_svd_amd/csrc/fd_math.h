@@ -191,3 +191,94 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_exact(float base, const float* dbas
     o.dsc = has_mask ? w * base * mk * r0 / (s_l * s_l) : 0.f;
     return o;
 }
+
+// ---- NeuralEF (neuralef.hip): every stencil point divided by its own batch norm (methods/utils.py:48-56) ----------------
+// Even / odd parts of rho_+- = w(x_+-) / w(x0) - 1 along direction d: ev = rho_+ + rho_-, od = rho_+ - rho_-, with
+// w = sqrt p (qs = d log sqrt p / d |x|^2, 0 without importance) times the mask (has_mask) - nsvd_fd_evenodd's arithmetic
+struct NsvdEvenOdd {
+    float ev, od;
+};
+__device__ __forceinline__ NsvdEvenOdd nsvd_fd_ratio_eo(float xd, float r2, float r0, float eps, float qs, bool has_mask,
+                                                        float s_l) {
+    const float e2 = eps * eps;
+    const float b = 2.f * xd * eps;
+    float sv = qs * e2, av = qs * b;
+    if (has_mask) {
+        const float rp = sqrtf(fmaxf(r2 + (e2 + b), 0.f)), rm = sqrtf(fmaxf(r2 + (e2 - b), 0.f));
+        const float S = rp + rm, den = (rp + r0) * (rm + r0);
+        const float tsum = (e2 * (S + 2.f * r0) - 2.f * b * b / S) / den;
+        const float tdif = b * ((S + 2.f * r0) - 2.f * e2 / S) / den;
+        sv -= 0.5f * tsum / s_l;
+        av -= 0.5f * tdif / s_l;
+    }
+    const float sh = sinhf(0.5f * av), chm1 = 2.f * sh * sh, es1 = expm1f(sv);
+    NsvdEvenOdd o;
+    o.ev = 2.f * (es1 * (1.f + chm1) + chm1);
+    o.od = 2.f * (1.f + es1) * sinhf(av);
+    return o;
+}
+
+// Head output u = c base mask at x +- eps e_d minus the centre's, u_+- - u0 = P +- Q (mask ratio (evm, odm)):
+//   P = c mk0 [evm / 2 (base0 + bE) + odm / 2 bO + bE],  Q = c mk0 [odm / 2 (base0 + bE) + evm / 2 bO + bO]
+// so that the per-sample terms of n_+-^2 - n_0^2 = mean_b (u_+-^2 - u0^2) are formed without a difference of large numbers:
+//   u_+-^2 - u0^2 = (2 u0 P + P^2 + Q^2) +- (2 u0 Q + 2 P Q)
+struct NsvdNefDelta {
+    float even, odd;
+};
+__device__ __forceinline__ NsvdNefDelta nsvd_nef_sqdelta(float u0, float cmk0, float base0, float bE, float bO,
+                                                         NsvdEvenOdd m) {
+    const float be = base0 + bE;
+    const float P = cmk0 * (0.5f * m.ev * be + 0.5f * m.od * bO + bE);
+    const float Q = cmk0 * (0.5f * m.od * be + 0.5f * m.ev * bO + bO);
+    NsvdNefDelta o;
+    o.even = 2.f * u0 * P + P * P + Q * Q;
+    o.odd = 2.f * (u0 * Q + P * Q);
+    return o;
+}
+
+// nsvd_fd_evenodd with the stencil point x_e divided by its batch norm n_e = n0 / (1 + nu_e): g_+- = (c w0 / n0)
+// (1 + sig_+-)(base0 + bE +- bO), 1 + sig = (1 + rho)(1 + nu), so the central difference keeps its even / odd form:
+//     g_+ + g_- - 2 g_0 = (c w0 / n0) [ (sig_+ + sig_-)(base0 + bE) + 2 bE + (sig_+ - sig_-) bO ]
+// nu[2 d], nu[2 d + 1]: nu of x + eps e_d, x - eps e_d. Outputs phi, Tphi (f, Tf), h = u0 / n0, r = sqrt p / clamp(sqrt p),
+// and jac / dsc of u0 (d u0 / d base0, d u0 / d scales_l) - what the normalisation backward hands to the centre backward.
+struct NsvdNefOut {
+    float phi, Tphi, h, r, jac, dsc;
+};
+__device__ __forceinline__ NsvdNefOut nsvd_nef_evenodd(float base0, const float* bE, const float* bO, const float* xc,
+                                                       int D, bool has_mask, float s_l, const nsvd_problem& prob,
+                                                       float log_norm, float n0, const float* nu) {
+    float r2 = 0.f;
+    for (int d = 0; d < D; ++d) r2 = fmaf(xc[d], xc[d], r2);
+    const float r0 = sqrtf(r2);
+    const float c = prob.hard_mul_const;
+    const float sp0 = prob.use_importance ? nsvd_sqrt_gauss_pdf(xc, D, prob.sigma, log_norm) : 1.f;
+    const float mk0 = has_mask ? expf(-r0 / s_l) : 1.f;
+    const float qs = prob.use_importance ? -1.f / (4.f * prob.sigma * prob.sigma) : 0.f;
+    float acc = 0.f;
+    for (int d = 0; d < D; ++d) {
+        const NsvdEvenOdd w = nsvd_fd_ratio_eo(xc[d], r2, r0, prob.eps, qs, has_mask, s_l);
+        const float rp = 0.5f * (w.ev + w.od), rm = 0.5f * (w.ev - w.od);
+        const float np = nu[2 * d], nm = nu[2 * d + 1];
+        const float ev = w.ev + (np + nm) + (rp * np + rm * nm);
+        const float od = w.od + (np - nm) + (rp * np - rm * nm);
+        acc += ev * (base0 + bE[d]) + 2.f * bE[d] + od * bO[d];
+    }
+    const float eps2 = (float)((double)prob.eps * (double)prob.eps);
+    const float spc = prob.use_importance ? fmaxf(sp0, NSVD_SQRT_P_CLAMP) : 1.f;
+    const float u0 = c * base0 * mk0;
+    const float h = u0 / n0;
+    const float lap = ((c * (sp0 * mk0) / n0) * acc / eps2) / spc;
+    const float fs = (sp0 * h) / spc;
+    float V;
+    if (prob.potential == NSVD_POT_HYDROGEN) V = -(prob.charge_or_k / r0);
+    else V = prob.charge_or_k * (r0 * r0);
+    const float H = -prob.scale_kinetic * lap + V * fs;
+    NsvdNefOut o;
+    o.phi = fs;
+    o.Tphi = prob.op_scale * (-H) + prob.op_shift * fs;
+    o.h = h;
+    o.r = sp0 / spc;
+    o.jac = c * mk0;
+    o.dsc = has_mask ? c * base0 * mk0 * r0 / (s_l * s_l) : 0.f;
+    return o;
+}

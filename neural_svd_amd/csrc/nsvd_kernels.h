@@ -86,7 +86,22 @@ int nsvd_fused_features(const nsvd_model_desc& d, const nsvd_params& p, const ns
                         float* xout = nullptr);
 // save: bit 0 = keep what the backward needs, bit 1 = features already prepared by nsvd_fused_features
 int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
-                       int B, float* f, float* Tf, void* ws, int save, hipStream_t s, int bf3 = 0);
+                       int B, float* f, float* Tf, void* ws, int save, hipStream_t s, int bf3 = 0, int raw = 0);
+// NeuralEF: operator forward that stops at the raw head outputs (operator_api.hip: nsvd_operator_forward_raw)
+struct NsvdRawOut {
+    const float* raw;  // (L, ldr): rows e B + b, e = centre, even_0, odd_0, even_1, ...
+    int ldr;
+    float* jac;        // (B, L) where the centre backward reads d out / d base ...
+    float* dsc;        // ... and d out / d scales (null without the mask)
+};
+struct FusedWsView {
+    float* base_raw;
+    float* jac;
+    float* dsc;
+};
+FusedWsView nsvd_fused_ws_view(const nsvd_model_desc& d, int B, void* ws);
+int nsvd_operator_forward_raw(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
+                              int B, void* ws, int path, hipStream_t s, NsvdRawOut* out);
 // batch slices of the weight-gradient kernel (1: every tile contracts the whole batch)
 int nsvd_fused_wgrad_slices(const nsvd_model_desc& d, int B);
 int nsvd_fused_stream_bwd_slices(const nsvd_model_desc& d, int B);  // > 0: the streaming backward may take the step

@@ -251,6 +251,33 @@ extern "C" int nsvd_operator_forward(const nsvd_model_desc* desc, const nsvd_par
     return generic_forward(*desc, *params, *prob, x, B, f, Tf, ws, (hipStream_t)stream, ready);
 }
 
+// NeuralEF (neuralef.hip): the operator forward up to the raw head outputs - (L, ldr) rows e B + b in the even / odd
+// stencil form of nsvd_fd_epilogue's `base` - and where the centre backward reads jac / dsc (the caller fills them)
+int nsvd_operator_forward_raw(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
+                              int B, void* ws, int path, hipStream_t s, NsvdRawOut* out) {
+    const bool fused = want_fused(d, B, path, !(prob.eps > 0.f));
+    if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
+    if (path == NSVD_PATH_FUSED_BF16X3 || !(prob.eps > 0.f)) return NSVD_EUNSUPPORTED;
+    const int R = (1 + 2 * d.D) * B;
+    if (fused) {
+        const FusedWsView v = nsvd_fused_ws_view(d, B, ws);
+        out->raw = v.base_raw;
+        out->ldr = R;
+        out->jac = v.jac;
+        out->dsc = d.has_exp_mask ? v.dsc : nullptr;
+        return nsvd_fused_forward(d, p, prob, x, B, nullptr, nullptr, ws, 1, s, 0, 1);
+    }
+    const GenericWs w = carve(d, B, ws);
+    out->raw = w.z[d.nlayers - 1];
+    out->ldr = w.R;
+    out->jac = w.jac;
+    out->dsc = d.has_exp_mask ? w.dsc : nullptr;
+    nsvd_prof_begin(s);
+    const int rc = generic_mlp(d, p, x, B, prob.eps, 1 + 2 * d.D, w, s);
+    nsvd_prof_end(s);
+    return rc;
+}
+
 extern "C" int nsvd_operator_features(const nsvd_model_desc* desc, const nsvd_params* params,
                                       const nsvd_problem* prob, const float* x, int B, void* ws, size_t ws_bytes,
                                       int save_for_backward, int path, void* stream) {

@@ -70,6 +70,10 @@ struct FwdArgs {
     // launch the direction group that arrives LAST at a (head, sample block) reads the other groups' raw outputs and forms
     // f, Tf itself (fd_math.h: the arithmetic of fd_epilogue_kernel, same bits) - no epilogue launch (round 6)
     unsigned* tickets;
+    // NeuralEF (neuralef.hip): non-null in the plain stencil form = write the E raw head-output rows of the 128 -> 1 layer
+    // (centre, even / odd perturbations; base_raw's layout) here instead of forming f, Tf: the per-point batch norms need
+    // the whole batch before any point can be normalised
+    float* raw;
 };
 
 
@@ -827,6 +831,13 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
         // stencil mode: outputs of the 128 -> 1 layer in even / odd form (its bias joins the centre)
         if (tid < NC)
             gs[tid] = (red[tid] + red[NC + tid]) + (red[2 * NC + tid] + red[3 * NC + tid]) + (tid < BS ? a.b[nh][l] : 0.f);
+        if (a.raw) {
+            if (tid < NC) {
+                const int e_t = tid / BS;
+                a.raw[(size_t)l * a.ldr + (size_t)e_t * a.B + b0 + (tid - e_t * BS)] = gs[tid];
+            }
+            return;
+        }
         __syncthreads();
         if (tid < BS) {
             const int b = b0 + tid;
@@ -904,6 +915,15 @@ bool nsvd_fused_supported(const nsvd_model_desc& d, int B, bool exact) {
 
 size_t nsvd_fused_workspace_bytes(const nsvd_model_desc& d, int B) { return carve_fused(d, B, nullptr).bytes; }
 
+FusedWsView nsvd_fused_ws_view(const nsvd_model_desc& d, int B, void* ws) {
+    const FusedWs w = carve_fused(d, B, ws);
+    FusedWsView v;
+    v.base_raw = w.base_raw;
+    v.jac = w.jac;
+    v.dsc = w.dsc;
+    return v;
+}
+
 int nsvd_fused_features(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
                         int B, void* ws, int save, hipStream_t s, const NsvdSampler* sampler, float* xout) {
     const FusedWs w = carve_fused(d, B, ws);
@@ -912,7 +932,9 @@ int nsvd_fused_features(const nsvd_model_desc& d, const nsvd_params& p, const ns
 }
 
 int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
-                       int B, float* f, float* Tf, void* ws, int save, hipStream_t s, int bf3) {
+                       int B, float* f, float* Tf, void* ws, int save, hipStream_t s, int bf3, int raw) {
+    // raw (NeuralEF): leave the raw head outputs in w.base_raw, f / Tf not written (float32 stencil forms only)
+    if (raw && (bf3 || prob.eps <= 0.f)) return NSVD_EUNSUPPORTED;
     const FusedWs w = carve_fused(d, B, ws);
     const int E = 1 + 2 * d.D, R = E * B, F = 2 * d.m;
     int rc = 0;
@@ -987,7 +1009,7 @@ int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsv
         a.kpart = w.kpart;
         {
             const char* e = getenv("NSVD_KSPLIT_FOLD");  // "0": the separate epilogue launch (A/B measurements, tests)
-            a.tickets = (e && e[0] == '0') ? nullptr : w.tickets;
+            a.tickets = (e && e[0] == '0') || raw ? nullptr : w.tickets;
         }
         rc = launch_fwd<5, 0, 0, 0, 1>(a, s, 1);  // (the in-run bracket of bench.py spans both launches)
         if (rc) return rc;
@@ -997,7 +1019,7 @@ int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsv
         a.base_raw = w.base_raw;
         a.kplain = 1;
         rc = launch_fwd<3, 0, 0, 0, 2>(a, s, 2);
-        if (rc || a.tickets) return rc;  // (tickets: the last direction group of every tile has formed f, Tf)
+        if (rc || a.tickets || raw) return rc;  // (tickets: the last direction group of every tile has formed f, Tf)
         return nsvd_fd_epilogue(w.base_raw, R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L, f, Tf,
                                 save ? w.jac : nullptr, (save && d.has_exp_mask) ? w.dsc : nullptr, s, 1);
     }
@@ -1011,7 +1033,7 @@ int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsv
             a.kpart = w.kpart;
             {
                 const char* e = getenv("NSVD_KSPLIT_FOLD");
-                a.tickets = (e && e[0] == '0') ? nullptr : w.tickets;
+                a.tickets = (e && e[0] == '0') || raw ? nullptr : w.tickets;
             }
             rc = launch_fwd<3, 0, 0, 0, 1>(a, s, 1);  // (the in-run bracket of bench.py spans both launches)
             if (rc) return rc;
@@ -1020,10 +1042,11 @@ int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsv
         } else {
             rc = launch_fwd<3>(a, s);
         }
-        if (rc) return rc;
+        if (rc || raw) return rc;
         return nsvd_fd_epilogue(w.base_raw, R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L, f, Tf,
                                 save ? w.jac : nullptr, (save && d.has_exp_mask) ? w.dsc : nullptr, s, 1);
     }
+    if (raw) a.raw = w.base_raw;
     switch (E) {
         case 3: return launch_fwd<3>(a, s);
         case 5: return launch_fwd<5>(a, s);

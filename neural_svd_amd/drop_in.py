@@ -296,15 +296,18 @@ def _captured_plain_step(args, method, operator, importance_train, optimizer, sc
     OperatorWrapper with a generated nesting mask, GPU, float32), else None: the eager plain loop takes over."""
     from . import hip_ops as H
     from .nested_lowrank import NestedLoRA, _mask_kind
+    from .neuralef import NeuralEigenfunctions
     from .operators import OperatorWrapper
     if not getattr(args, "graph_loop", True) or torch.device(device).type != "cuda":
         return None
     if args.optimizer != "rmsprop" or float(getattr(args, "momentum", 0.0)) != 0.0:
         return None
-    if not isinstance(method, NestedLoRA) or not isinstance(operator, OperatorWrapper):
+    if not isinstance(method, (NestedLoRA, NeuralEigenfunctions)) or not isinstance(operator, OperatorWrapper):
         return None
-    if _mask_kind(method.vector_mask, method.matrix_mask) == H.MASK_CUSTOM:
+    if isinstance(method, NestedLoRA) and _mask_kind(method.vector_mask, method.matrix_mask) == H.MASK_CUSTOM:
         return None  # custom masks are copied to the device per call: a host copy cannot be captured
+    # (NeuralEF: the running norms' first-call flag lives on the device, so the warm-up's first step - the eager one
+    # that initialises them - and the replayed steps are the same launches)
     if any(p.dtype != torch.float32 or not p.is_contiguous() for p in method.parameters()):
         return None
     return CapturedPlainStep(args, method, operator, importance_train, optimizer, scheduler, ema, device)
@@ -335,8 +338,29 @@ def _refresh_from_trainer(tr, method, ema, optimizer, scheduler):
             g["lr"] = cosine_lr(tr.lr, tr.t, tr.num_iters)
 
 
+def _refuse_neuralef(args, method, operator):
+    """NeuralEF configurations this package does not build, refused up front with the reason."""
+    from .neuralef import BatchL2NormalizedFunctions, NeuralEigenfunctions
+    from .operators import OperatorWrapper
+    if not isinstance(method, NeuralEigenfunctions):
+        return
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NotImplementedError("NeuralEF on several ranks (WORLD_SIZE > 1): the per-stencil-point batch norms need "
+                                  "the whole batch on every rank (an all-reduce per stencil point); only one GPU is "
+                                  "built")
+    if getattr(args, "use_amp", False):
+        raise NotImplementedError("NeuralEF with use_amp: the mixed-precision forward (NSVD_PATH_FUSED_BF16X3) is "
+                                  "built for NestedLoRA only; the NeuralEF forward runs in float32")
+    if isinstance(method.model, BatchL2NormalizedFunctions) and isinstance(operator, OperatorWrapper) and \
+            float(operator.operator.laplacian_eps) <= 0:
+        raise NotImplementedError("NeuralEF with batch normalisation and the exact Laplacian (laplacian_eps <= 0): the "
+                                  "reference's autograd Laplacian includes cross-sample terms of the batch norm; not "
+                                  "built (use laplacian_eps > 0 or batchnorm_mode='none')")
+
+
 def train_operator(args, method, operator, make_batch_ftn_train, val_data, batch_ftn_val, log_writer, log_file,
                    device, importance_train, importance_val, ground_truth_spectrum=None):
+    _refuse_neuralef(args, method, operator)
     if getattr(args, "use_amp", False):
         # The reference's mixed-precision switch wraps the step in autocast + GradScaler (examples/operator/__init__.py:
         # 37-38,62-72): half-precision matmuls, loss scaling against their underflow. Here it selects this package's
@@ -474,9 +498,11 @@ def train_operator(args, method, operator, make_batch_ftn_train, val_data, batch
             method.eval()
             with ema.average_parameters():
                 if batch_ftn_val is not None:
+                    # (reference examples/operator/__init__.py:110: NeuralEF is evaluated without normalisation)
+                    normalize = getattr(method, "name", None) in ["nestedlora", "neuralsvd"]
                     outputs = compute_spectrum_evd(method, dataloader=batch_ftn_val(), operator=operator,
                                                    importance_train=importance_train, importance_val=importance_val,
-                                                   normalize=True, set_first_mode_const=False, device=device)
+                                                   normalize=normalize, set_first_mode_const=False, device=device)
                     if rank0:
                         print(f"it{it + 1} eigvals: {outputs['eigvals']}")
                         print(f"it{it + 1} norms: {outputs['norms']}")

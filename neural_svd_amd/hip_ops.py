@@ -1027,3 +1027,82 @@ for _name in ("fourier_features", "operator_forward", "operator_features", "oper
               "row_normalize_backward", "tower_forward", "tower_backward", "cdk_step", "to_bf16", "gemm_bf16"):
     globals()[_name] = _on_tensor_device(globals()[_name])
 del _name
+
+
+# ------------------------------------------------------------------------------------- NeuralEF (include/nsvd.h)
+@_on_tensor_device
+def nef_operator_forward(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor, ws: torch.Tensor,
+                         norm_biased: torch.Tensor, norm_unbiased: torch.Tensor, initialized: torch.Tensor,
+                         momentum: float, path: int = PATH_AUTO):
+    """Training-mode Tphi, phi = operator(BatchL2NormalizedFunctions(model), x, importance); updates the running norms
+    (1 + 2D times) and sets `initialized`. Returns (phi, Tphi, saved) - saved = (h, r, stats) for nef_operator_backward."""
+    B = x.shape[0]
+    if x.dim() != 2 or x.shape[1] != shape.D:
+        raise NsvdError(f"x must be (B, {shape.D})")
+    if norm_biased.numel() != shape.L or norm_unbiased.numel() != shape.L:
+        raise NsvdError(f"running norms must hold {shape.L} values")
+    dev = x.device
+    phi = torch.empty((B, shape.L), dtype=torch.float32, device=dev)
+    Tphi, h, r = torch.empty_like(phi), torch.empty_like(phi), torch.empty_like(phi)
+    stats = torch.empty((1 + 2 * shape.D, shape.L), dtype=torch.float32, device=dev)
+    d = shape.desc()
+    rc = _lib.load().nsvd_nef_operator_forward(C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(phi),
+                                               _ptr(Tphi), _ptr(h), _ptr(r), _ptr(stats),
+                                               _ptr(norm_biased, "norm_biased"), _ptr(norm_unbiased, "norm_unbiased"),
+                                               _ptr(initialized, "initialized", torch.int32), float(momentum),
+                                               ws.data_ptr(), ws.numel(), int(path), _stream())
+    check(rc, "nsvd_nef_operator_forward")
+    return phi, Tphi, (h, r, stats)
+
+
+@_on_tensor_device
+def nef_operator_backward(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor, dphi: torch.Tensor,
+                          saved, grads: Params, ws: torch.Tensor, path: int = PATH_AUTO) -> None:
+    h, r, stats = saved
+    B = x.shape[0]
+    if tuple(dphi.shape) != (B, shape.L):
+        raise NsvdError(f"dphi must be {(B, shape.L)}")
+    du0 = torch.empty_like(h)
+    d = shape.desc()
+    rc = _lib.load().nsvd_nef_operator_backward(C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B,
+                                                _ptr(dphi, "dphi"), _ptr(h), _ptr(r), _ptr(stats), _ptr(du0),
+                                                C.byref(grads), ws.data_ptr(), ws.numel(), int(path), _stream())
+    check(rc, "nsvd_nef_operator_backward")
+
+
+@_on_tensor_device
+def nef_loss(phi: torch.Tensor, Tphi: torch.Tensor, phi1: torch.Tensor, Tphi1: torch.Tensor, phi2: torch.Tensor,
+             Tphi2: torch.Tensor, unbiased: bool, diagonal: int):
+    """NeuralEigenfunctionsLossFunction on the HIP kernels. Returns (loss (1,), dphi, dphi1, dphi2): with phi1 / phi2
+    the two chunks of phi, dphi holds the whole d loss / d phi and dphi1 = dphi2 = None."""
+    B, L = phi.shape
+    B1, B2 = phi1.shape[0], phi2.shape[0]
+    for n, t, rows in (("Tphi", Tphi, B), ("phi1", phi1, B1), ("Tphi1", Tphi1, B1), ("phi2", phi2, B2),
+                       ("Tphi2", Tphi2, B2)):
+        if t.dim() != 2 or tuple(t.shape) != (rows, L):
+            raise NsvdError(f"{n} must be {(rows, L)} (got {tuple(t.shape)})")
+    dev = phi.device
+    chunked = (phi1.data_ptr() == phi.data_ptr() and Tphi1.data_ptr() == Tphi.data_ptr() and B1 + B2 == B and
+               phi2.data_ptr() == phi.data_ptr() + 4 * B1 * L and Tphi2.data_ptr() == Tphi.data_ptr() + 4 * B1 * L)
+    lib = _lib.load()
+    nbytes = lib.nsvd_nef_loss_workspace_bytes(B, B1, B2, L)
+    if nbytes == 0:
+        raise NsvdError(f"nsvd_nef_loss: unsupported shape B={B}, B1={B1}, B2={B2}, L={L} (L <= 64)")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    dphi = torch.empty_like(phi)
+    d1 = None if chunked else torch.empty_like(phi1)
+    d2 = None if chunked else torch.empty_like(phi2)
+    rc = lib.nsvd_nef_loss(_ptr(phi, "phi"), _ptr(Tphi, "Tphi"), B, _ptr(phi1, "phi1"), _ptr(Tphi1, "Tphi1"), B1,
+                           _ptr(phi2, "phi2"), _ptr(Tphi2, "Tphi2"), B2, L, int(bool(unbiased)), int(diagonal),
+                           _ptr(loss), _ptr(dphi), _ptr(d1), _ptr(d2), scratch.data_ptr(), nbytes, _stream())
+    check(rc, "nsvd_nef_loss")
+    return loss, dphi, d1, d2
+
+
+@_on_tensor_device
+def nef_scale_heads(f: torch.Tensor, Tf: torch.Tensor, norm: torch.Tensor) -> None:
+    """f /= norm, Tf /= norm per head, in place (BatchL2NormalizedFunctions in evaluation mode)."""
+    B, L = f.shape
+    rc = _lib.load().nsvd_nef_scale_heads(_ptr(f, "f"), _ptr(Tf, "Tf"), _ptr(norm.reshape(-1), "norm"), B, L, _stream())
+    check(rc, "nsvd_nef_scale_heads")

@@ -1,7 +1,7 @@
 """Drop-in surface of the reference's ``methods/`` package for the NestedLoRA (NeuralSVD) path,
 backed by the HIP C ABI.  Same names, argument meaning and return values as the reference:
 
-    get_evd_method(args, 'neuralsvd', model)                     methods/general.py:7-39
+    get_evd_method(args, 'neuralsvd' | 'neuralef', model)        methods/general.py:7-39 (NeuralEF: neuralef.py)
     NestedLoRA(model, neigs, step, sort, sequential)             methods/nestedlora.py:167-267
     NestedLoRALossFunctionEVD.apply(f, Tf, f1, f2, vmask, mmask) methods/nestedlora.py:67-111
     get_sequential_nesting_masks / get_joint_nesting_masks       methods/nestedlora.py:40-54
@@ -345,7 +345,11 @@ class NestedLoRA(nn.Module):
 
 
 def get_evd_method(args, method_name, model):
+    if method_name == "neuralef":  # methods/general.py:21-28 (include_diag not passed: diagonal 1)
+        from .neuralef import NeuralEigenfunctions
+        return NeuralEigenfunctions(model=model, neigs=args.neigs, batchnorm_mode=args.loss.neuralef.batchnorm_mode,
+                                    unbiased=args.loss.neuralef.unbiased, sort=args.sort)
     if method_name != "neuralsvd":
-        raise NotImplementedError(f"{method_name}: only 'neuralsvd' (NestedLoRA) is built on this path")
+        raise NotImplementedError(f"{method_name}: only 'neuralsvd' (NestedLoRA) and 'neuralef' are built on this path")
     return NestedLoRA(model=model, neigs=args.neigs, step=args.loss.neuralsvd.step, sort=args.sort,
                       sequential=args.loss.neuralsvd.sequential)

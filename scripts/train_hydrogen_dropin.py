@@ -3,6 +3,7 @@ train_operator with the hyper-parameters of scripts/exps/pde/hydrogen.sh (neigs 
 compute_spectrum_evd under the EMA weights inside train_operator, relative eigenvalue error of its last evaluation.
 
     python scripts/train_hydrogen_dropin.py --steps 500000 --out gpurun_out/train_cfg2_dropin.json [--sequential]
+    python scripts/train_hydrogen_dropin.py --loss neuralef --steps 500000 --out ...   (NeuralEF, plain captured loop)
 """
 import argparse
 import json
@@ -29,6 +30,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--problem", default="hydrogen", choices=["hydrogen", "oscillator"],
                     help="oscillator: configs[2] on one GPU (scripts/exps/pde/oscillator.sh with neigs 32, batch 4096)")
+    ap.add_argument("--loss", default="neuralsvd", choices=["neuralsvd", "neuralef"],
+                    help="neuralef: NeuralEF as scripts/exps/pde/hydrogen.sh runs it (unbiased, batchnorm 'unbiased')")
     ap.add_argument("--out", default=None)
     o = ap.parse_args()
     dev = "cuda:0"
@@ -45,12 +48,13 @@ def main():
         vars(a).update(potential_type="harmonic_oscillator", neigs=32, operator_scale=1.0, operator_shift=16.0,
                        sampling_scale=4.0, batch_size=4096, lim=5.0, fourier_mapping_size=256, fourier_scale=1.0,
                        apply_exp_mask=1, exp_mask_init_scale=10.0)
-    a.loss = argparse.Namespace(name="neuralsvd", neuralsvd=argparse.Namespace(step=1, sequential=o.sequential))
+    a.loss = argparse.Namespace(name=o.loss, neuralsvd=argparse.Namespace(step=1, sequential=o.sequential),
+                                neuralef=argparse.Namespace(unbiased=1, batchnorm_mode="unbiased"))
     torch.manual_seed(o.seed)
     operator, gt = get_problem(a, dev)
     model = get_wavefunctions(a)
     make_batch, val_data, batch_ftn_val, imp_train, imp_val = get_dataloader(a, dev)
-    method = get_evd_method(a, "neuralsvd", model).to(dev)
+    method = get_evd_method(a, o.loss, model).to(dev)
     t0 = time.perf_counter()
     eigs, norms = train_operator(a, method, operator, make_batch, val_data, batch_ftn_val, None, None, dev, imp_train,
                                  imp_val, ground_truth_spectrum=gt)
@@ -61,8 +65,8 @@ def main():
     gt = np.asarray(gt, dtype=np.float64)[:L]
     nz = np.abs(gt) > 0  # the oscillator's 8th shell sits at eigenvalue 0: no relative error there
     rel = (np.abs(ev - gt) / np.where(nz, np.abs(gt), 1.0))[nz]
-    rec = dict(api="drop_in.train_operator (fused loop body)" if a.fused_loop else "drop_in.train_operator (plain loop body)",
-               nesting="sequential" if o.sequential else "joint", steps=o.steps, evaluations=len(eigs),
+    rec = dict(api="drop_in.train_operator (fused loop body)" if (a.fused_loop and o.loss == "neuralsvd") else "drop_in.train_operator (plain loop body)",
+               loss=o.loss, nesting="sequential" if o.sequential else "joint", steps=o.steps, steps_per_second=round(o.steps / dt, 1), evaluations=len(eigs),
                wall_seconds_including_evaluations=round(dt, 1), eigvals=[float(v) for v in ev],
                ground_truth=[float(v) for v in gt], problem=o.problem, seed=o.seed, rel_err_mean=float(rel.mean()), rel_err_max=float(rel.max()))
     print(json.dumps(rec))
