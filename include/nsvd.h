@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define NSVD_ABI_VERSION 2
+#define NSVD_ABI_VERSION 3
 #define NSVD_MAX_LAYERS 8
 
 #define NSVD_EINVAL (-10001)
@@ -55,6 +55,18 @@ extern "C" {
 /* potentials: examples/operator/pde/schrodinger/potentials.py:5-8 and :24-27 */
 #define NSVD_POT_HYDROGEN 0 /* V = -Z / |x|  */
 #define NSVD_POT_HARMONIC 1 /* V = k |x|^2   */
+#define NSVD_POT_ZERO 2     /* V = 0: the infinite well (potentials.py:20-21); the walls are the model's box mask */
+
+/* Dirichlet box mask of the model (examples/operator/pde/boundary.py:16-36, --apply_boundary / --boundary_mode):
+ * M(x) = prod_d m(clamp(x_d, -lim, lim)), 0 at and beyond the wall, multiplies the model output at every point */
+#define NSVD_BOX_NONE 0
+#define NSVD_BOX_SQRT 1 /* dir_box_sqrt: m(t) = max((sqrt(2 lim^2 - t^2) - lim) / lim, 0)        */
+#define NSVD_BOX_EXP 2  /* dir_box_exp:  m(t) = (1 - exp(-(lim - t))) (1 - exp(-(lim + t)))       */
+
+/* nsvd_problem.use_importance: the density the batch is drawn from and re-weighted by (main_pde.py:89-118) */
+#define NSVD_IMP_NONE 0
+#define NSVD_IMP_GAUSSIAN 1 /* N(0, sigma^2 I)                                                               */
+#define NSVD_IMP_UNIFORM 2  /* uniform on [-sigma, sigma]^D: p = (2 sigma)^-D (sigma = --sampling_scale)      */
 
 /* nesting masks: methods/nestedlora.py:40-54 */
 #define NSVD_MASK_CUSTOM 0     /* v (L) and M (L,L) given by pointer                    */
@@ -80,6 +92,10 @@ typedef struct nsvd_model_desc {
     int32_t nlayers;                 /* number of weight matrices = len(hidden) + 1    */
     int32_t dims[NSVD_MAX_LAYERS];   /* h_0 .. h_{nlayers-1}; the last one must be 1   */
     int32_t has_exp_mask;            /* --apply_exp_mask                               */
+    /* ABI 3 (appended; zero = no box mask): the mask belongs to the model, like has_exp_mask - nsvd_model_forward /
+     * _backward never see the problem. Alone or inside the exponential mask (boundary.py:51-52). */
+    int32_t box_mask;                /* NSVD_BOX_*: --apply_boundary / --boundary_mode */
+    float box_lim;                   /* --lim: half-width of the box                   */
 } nsvd_model_desc;
 
 /* Device pointers of one parameter set (weights, their gradients, RMSprop state or EMA shadow
@@ -104,7 +120,9 @@ typedef struct nsvd_problem {
     float op_shift;                  /* --operator_shift                               */
     float sigma;                     /* --sampling_scale of the Gaussian sampler       */
     float hard_mul_const;            /* --hard_mul_const                               */
-    int32_t use_importance;          /* 1: importance = N(0, sigma^2 I) pdf; 0: None   */
+    int32_t use_importance;          /* NSVD_IMP_*: 0 None, 1 the N(0, sigma^2 I) pdf, 2 the uniform density
+                                      * (2 sigma)^-D; sqrt p / max(sqrt p, 1e-5) is kept for all of them. The device
+                                      * samplers draw from the same density. */
 } nsvd_problem;
 
 int nsvd_abi_version(void);
@@ -112,7 +130,9 @@ int nsvd_abi_version(void);
 /* Name of the implementation nsvd_operator_forward would take ("fused_mfma", "generic"). host */
 const char* nsvd_path_name(const nsvd_model_desc* desc, int B, int path);
 /* The same for a given problem: the exact-Laplacian mode (prob->eps <= 0) exists on the MFMA path only (D <= 3, as the
- * stencil mode: its 3-D form runs one direction per workgroup); "unsupported" when it has no path. */
+ * stencil mode: its 3-D form runs one direction per workgroup); "unsupported" when it has no path; "invalid" for a
+ * potential, importance or box mask value this library does not know. Every path implements every box mask, potential
+ * and importance; entry points that do not (NeuralEF) return NSVD_EUNSUPPORTED. */
 const char* nsvd_path_name_for(const nsvd_model_desc* desc, const nsvd_problem* prob, int B, int path);
 
 /* Bytes of scratch nsvd_operator_forward / _backward need for batches of up to B rows. */
@@ -176,7 +196,9 @@ int nsvd_model_forward(const nsvd_model_desc* desc, const nsvd_params* params, c
                        float hard_mul_const, float* out, void* ws, size_t ws_bytes, int save_for_backward,
                        void* stream);
 
-/* Draws the batch AND prepares its features in one launch: x[b][d] = sigma * N(0,1) with sigma = prob->sigma,
+/* Draws the batch AND prepares its features in one launch: x[b][d] = sigma * N(0,1) with sigma = prob->sigma
+ * (prob->use_importance == NSVD_IMP_UNIFORM: sigma * (2 u - 1), u = (23 bits + 1/2) / 2^23 of the same Philox block,
+ * never exactly +-sigma: main_pde.py:113-115),
  * from a counter-based generator (Philox4x32-10 + Box-Muller) keyed by (seed, offset, b): the device-side form of
  * `x = sampling_scale * torch.randn(batch_size, ndim)` + host->device copy (examples/operator/pde/main_pde.py:92-93,
  * examples/operator/__init__.py:58). x (B, D) is an OUTPUT; follow with nsvd_operator_forward(... |

@@ -10,12 +10,14 @@ import os
 from typing import Optional
 
 NSVD_MAX_LAYERS = 8
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 EINVAL = -10001
 EUNSUPPORTED = -10002
 
-POT_HYDROGEN, POT_HARMONIC = 0, 1
+POT_HYDROGEN, POT_HARMONIC, POT_ZERO = 0, 1, 2
+BOX_NONE, BOX_SQRT, BOX_EXP = 0, 1, 2
+IMP_NONE, IMP_GAUSSIAN, IMP_UNIFORM = 0, 1, 2
 MASK_CUSTOM, MASK_SEQUENTIAL, MASK_JOINT = 0, 1, 2
 PATH_AUTO, PATH_GENERIC, PATH_FUSED, PATH_FUSED_BF16X3 = 0, 1, 2, 3
 NORMALIZE_L2_BALL, NORMALIZE_L2_SPHERE = 0, 1
@@ -28,7 +30,8 @@ LIB_PATH = os.path.join(_PKG_DIR, "libnsvd_hip.so")
 
 class ModelDesc(C.Structure):
     _fields_ = [("L", C.c_int32), ("D", C.c_int32), ("m", C.c_int32), ("nlayers", C.c_int32),
-                ("dims", C.c_int32 * NSVD_MAX_LAYERS), ("has_exp_mask", C.c_int32)]
+                ("dims", C.c_int32 * NSVD_MAX_LAYERS), ("has_exp_mask", C.c_int32),
+                ("box_mask", C.c_int32), ("box_lim", C.c_float)]
 
 
 class Params(C.Structure):

@@ -16,7 +16,7 @@ __global__ void __launch_bounds__(256) fd_epilogue_kernel(const float* __restric
                                                           const float* __restrict__ scales, nsvd_problem prob,
                                                           float log_norm, int B, int D, int L, float* __restrict__ f,
                                                           float* __restrict__ Tf, float* __restrict__ jac,
-                                                          float* __restrict__ dsc, int evenodd) {
+                                                          float* __restrict__ dsc, int evenodd, NsvdBox box) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= B * L) return;
     const int b = idx / L, l = idx - b * L;
@@ -33,9 +33,9 @@ __global__ void __launch_bounds__(256) fd_epilogue_kernel(const float* __restric
             bE[d] = bv[1 + 2 * d];
             bO[d] = bv[2 + 2 * d];
         }
-        o = nsvd_fd_evenodd(bv[0], bE, bO, xc, D, scales != nullptr, s_l, prob, log_norm);
+        o = nsvd_fd_evenodd(bv[0], bE, bO, xc, D, scales != nullptr, s_l, prob, log_norm, box);
     } else {
-        o = nsvd_fd_point(bv, xc, D, scales != nullptr, s_l, prob, log_norm);
+        o = nsvd_fd_point(bv, xc, D, scales != nullptr, s_l, prob, log_norm, box);
     }
     f[idx] = o.f;
     Tf[idx] = o.Tf;
@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(256) model_out_kernel(const float* __restrict_
                                                         const float* __restrict__ x,
                                                         const float* __restrict__ scales, float c, int B, int D, int L,
                                                         float* __restrict__ out, float* __restrict__ jac,
-                                                        float* __restrict__ dsc) {
+                                                        float* __restrict__ dsc, NsvdBox box) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= B * L) return;
     const int b = idx / L, l = idx - b * L;
@@ -80,6 +80,14 @@ __global__ void __launch_bounds__(256) model_out_kernel(const float* __restrict_
         r = sqrtf(r2);
         mk = expf(-r / scales[l]);
     }
+    if (box.mode) {  // the box mask is a plain factor of the model output: it joins mk (and with it jac, dsc)
+        float M = 1.f;
+        for (int d = 0; d < D; ++d) {
+            const float xv = x[(size_t)b * D + d];
+            M *= nsvd_box_m1(box.lim - xv, box.lim + xv, box);
+        }
+        mk *= M;
+    }
     out[idx] = c * bv * mk;
     if (jac) jac[idx] = c * mk;                                              // d out / d base
     if (dsc) dsc[idx] = scales ? c * bv * mk * r / (scales[l] * scales[l]) : 0.f;  // d out / d scales_l
@@ -88,19 +96,20 @@ __global__ void __launch_bounds__(256) model_out_kernel(const float* __restrict_
 }  // namespace
 
 int nsvd_model_out(const float* base, int ldr, const float* x, const float* scales, float c, int B, int D, int L,
-                   float* out, float* jac, float* dsc, hipStream_t s) {
+                   float* out, float* jac, float* dsc, hipStream_t s, NsvdBox box) {
     hipLaunchKernelGGL(model_out_kernel, dim3(nsvd_cdiv(B * L, 256)), dim3(256), 0, s, base, ldr, x, scales, c, B, D,
-                       L, out, jac, dsc);
+                       L, out, jac, dsc, box);
     NSVD_CHECK_LAUNCH();
     return 0;
 }
 
 int nsvd_fd_epilogue(const float* base, int ldr, const float* x, const float* scales, const nsvd_problem& prob,
-                     int B, int D, int L, float* f, float* Tf, float* jac, float* dsc, hipStream_t s, int evenodd) {
+                     int B, int D, int L, float* f, float* Tf, float* jac, float* dsc, hipStream_t s, int evenodd,
+                     NsvdBox box) {
     if (D > NSVD_FD_MAXD) return NSVD_EUNSUPPORTED;
-    const float log_norm = nsvd_gauss_log_norm(D, prob.sigma);
+    const float log_norm = nsvd_importance_log_norm(D, prob);
     hipLaunchKernelGGL(fd_epilogue_kernel, dim3(nsvd_cdiv(B * L, 256)), dim3(256), 0, s, base, ldr, x, scales, prob,
-                       log_norm, B, D, L, f, Tf, jac, dsc, evenodd);
+                       log_norm, B, D, L, f, Tf, jac, dsc, evenodd, box);
     NSVD_CHECK_LAUNCH();
     return 0;
 }

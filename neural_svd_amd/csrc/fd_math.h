@@ -9,6 +9,91 @@ struct NsvdFdOut {
     float f, Tf, jac, dsc;
 };
 
+// sqrt p(x) of the problem's importance density: Gaussian (log_norm = nsvd_gauss_log_norm), uniform (a constant,
+// log_norm = log p = -D log(2 sigma): main_pde.py:116-118) or none; host: nsvd_importance_log_norm
+__device__ __forceinline__ float nsvd_sqrt_p(const nsvd_problem& prob, const float* xr, int D, float log_norm) {
+    if (prob.use_importance == NSVD_IMP_GAUSSIAN) return nsvd_sqrt_gauss_pdf(xr, D, prob.sigma, log_norm);
+    if (prob.use_importance == NSVD_IMP_UNIFORM) return sqrtf(expf(log_norm));
+    return 1.f;
+}
+static inline float nsvd_importance_log_norm(int D, const nsvd_problem& prob) {
+    if (prob.use_importance == NSVD_IMP_UNIFORM) return (float)(-(double)D * log(2.0 * (double)prob.sigma));
+    return nsvd_gauss_log_norm(D, prob.sigma);
+}
+
+// V(x) at |x| = r0 (potentials.py:5-8, 20-21, 24-27)
+__device__ __forceinline__ float nsvd_potential(const nsvd_problem& prob, float r0) {
+    if (prob.potential == NSVD_POT_HYDROGEN) return -(prob.charge_or_k / r0);
+    if (prob.potential == NSVD_POT_ZERO) return 0.f;
+    return prob.charge_or_k * (r0 * r0);
+}
+
+// ---- Dirichlet box mask (boundary.py:16-36): M(x) = prod_d m(clamp(x_d, -lim, lim)) --------------------------------
+// Everything is written in the distances to the two walls a = lim - t, b = lim + t (a b = lim^2 - t^2): a is exact in
+// float32 near the right wall, b near the left one (Sterbenz), and the shifted points take a -+ eps, b +- eps - so the
+// mask near a wall, where it is ~ eps / lim, keeps its relative accuracy. At and beyond the wall m = 0 exactly.
+//   sqrt: m = (sqrt(lim^2 + a b) - lim) / lim = a b / (lim (sqrt(lim^2 + a b) + lim))     (no difference of O(lim) numbers)
+//   exp:  m = (1 - e^-a)(1 - e^-b) = expm1(-a) expm1(-b)
+__device__ __forceinline__ float nsvd_box_m1(float a, float b, const NsvdBox& bx) {
+    if (!(a > 0.f) || !(b > 0.f)) return 0.f;
+    if (bx.mode == NSVD_BOX_SQRT) {
+        const float ab = a * b;
+        return ab / (bx.lim * (sqrtf(fmaf(bx.lim, bx.lim, ab)) + bx.lim));
+    }
+    return expm1f(-a) * expm1f(-b);
+}
+// M at stencil point e of the row xc
+__device__ __forceinline__ float nsvd_box_point(const float* xc, int D, int e, float eps, const NsvdBox& bx) {
+    float M = 1.f;
+    for (int d = 0; d < D; ++d) {
+        float a = bx.lim - xc[d], b = bx.lim + xc[d];
+        if (e > 0 && ((e - 1) >> 1) == d) {
+            const float sh = ((e - 1) & 1) ? -eps : eps;
+            a -= sh;
+            b += sh;
+        }
+        M *= nsvd_box_m1(a, b, bx);
+    }
+    return M;
+}
+// Along one direction: m0 = m(x_d) and delta_+- = m(x_d +- eps) - m0 as their sum ds (O(eps^2) inside the box) and
+// difference dd, neither formed by subtracting two O(1) numbers. With bb = 2 x_d eps, e2 = eps^2:
+//   sqrt: A = lim^2 + a b, A_+- = A - (e2 +- bb), sqrt(A_+-) - sqrt(A) = -(e2 +- bb) / (s_+- + s0)  (the tsum / tdif algebra):
+//         ds = -[e2 (S + 2 s0) + 2 bb^2 / S] / (lim den),  dd = -bb [(S + 2 s0) + 2 e2 / S] / (lim den),
+//         S = s_+ + s_-, den = (s_+ + s0)(s_- + s0)
+//   exp:  m = 1 + e^-2lim - 2 e^-lim cosh t:  ds = -8 e^-lim cosh x sinh^2(eps / 2),  dd = -4 e^-lim sinh x sinh eps,
+//         e^-lim cosh x = (e^-a + e^-b) / 2, e^-lim sinh x = (e^-a - e^-b) / 2
+// A stencil point at or beyond the wall has m = 0 exactly (delta = -m0), a centre outside m0 = 0 with its inner
+// neighbour still counting: the kink makes that row's Laplacian O(1 / eps), not a small difference, so the point-wise
+// deltas are exact enough there - and they are what the reference computes.
+struct NsvdBoxEO {
+    float m0, ds, dd;
+};
+__device__ __forceinline__ NsvdBoxEO nsvd_box_eo(float xd, float eps, const NsvdBox& bx) {
+    const float lim = bx.lim, a = lim - xd, b = lim + xd;
+    NsvdBoxEO o;
+    o.m0 = nsvd_box_m1(a, b, bx);
+    const bool smooth = a > 0.f && b > 0.f && (a - eps) > 0.f && (b - eps) > 0.f;
+    if (!smooth) {
+        const float dp = nsvd_box_m1(a - eps, b + eps, bx) - o.m0, dm = nsvd_box_m1(a + eps, b - eps, bx) - o.m0;
+        o.ds = dp + dm;
+        o.dd = dp - dm;
+    } else if (bx.mode == NSVD_BOX_SQRT) {
+        const float e2 = eps * eps, bb = 2.f * xd * eps;
+        const float A0 = fmaf(lim, lim, a * b);
+        const float s0 = sqrtf(A0), sp = sqrtf(A0 - (e2 + bb)), sm = sqrtf(A0 - (e2 - bb));
+        const float S = sp + sm, den = lim * ((sp + s0) * (sm + s0));
+        o.ds = -(e2 * (S + 2.f * s0) + 2.f * bb * bb / S) / den;
+        o.dd = -bb * ((S + 2.f * s0) + 2.f * e2 / S) / den;
+    } else {
+        const float ea = expf(-a), eb = expf(-b);
+        const float sh = sinhf(0.5f * eps);
+        o.ds = -4.f * (ea + eb) * sh * sh;
+        o.dd = -2.f * (ea - eb) * sinhf(eps);
+    }
+    return o;
+}
+
 // bv[e]: raw head output base_l(x_e) at the stencil points (e = 0 centre, 1+2i: +eps e_i, 2+2i: -eps e_i)
 // xc: centre coordinates. Follows the reference's operation order:
 //   g_e   = sqrt(p(x_e)) * (c * base_e * mask_l(x_e))          pde/__init__.py:16, diff_ops.py:13
@@ -20,7 +105,7 @@ struct NsvdFdG {
     float g, sp, mk, r;
 };
 __device__ __forceinline__ NsvdFdG nsvd_fd_g(int e, float bve, const float* xc, int D, bool has_mask, float s_l,
-                                             const nsvd_problem& prob, float log_norm) {
+                                             const nsvd_problem& prob, float log_norm, const NsvdBox& box) {
     float xe[NSVD_FD_MAXD];
     float r2 = 0.f;
     for (int d = 0; d < D; ++d) {
@@ -28,7 +113,7 @@ __device__ __forceinline__ NsvdFdG nsvd_fd_g(int e, float bve, const float* xc, 
         r2 = fmaf(xe[d], xe[d], r2);
     }
     NsvdFdG o;
-    o.sp = prob.use_importance ? nsvd_sqrt_gauss_pdf(xe, D, prob.sigma, log_norm) : 1.f;
+    o.sp = nsvd_sqrt_p(prob, xe, D, log_norm);
     float model = prob.hard_mul_const * bve;
     o.mk = 1.f;
     o.r = sqrtf(r2);
@@ -36,13 +121,15 @@ __device__ __forceinline__ NsvdFdG nsvd_fd_g(int e, float bve, const float* xc, 
         o.mk = expf(-o.r / s_l);
         model *= o.mk;
     }
+    if (box.mode) model *= nsvd_box_point(xc, D, e, prob.eps, box);
     o.g = o.sp * model;
     return o;
 }
 
 // stencil combination; g[e] from nsvd_fd_g, (sp0, mask0, r0) of the centre point, bv0 = bv[0]
+// (M0: the box mask at the centre, 1 without one)
 __device__ __forceinline__ NsvdFdOut nsvd_fd_combine(const float* g, float sp0, float mask0, float r0, float bv0, int D,
-                                                     bool has_mask, float s_l, const nsvd_problem& prob) {
+                                                     bool has_mask, float s_l, const nsvd_problem& prob, float M0) {
     float lap = -2.f * (float)D * g[0];
     for (int i = 0; i < D; ++i) lap += (g[1 + 2 * i] + g[2 + 2 * i]);
     const float eps2 = (float)((double)prob.eps * (double)prob.eps);
@@ -50,17 +137,15 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_combine(const float* g, float sp0, 
     const float spc = prob.use_importance ? fmaxf(sp0, NSVD_SQRT_P_CLAMP) : 1.f;
     lap = lap / spc;
     const float fs = g[0] / spc;
-    float V;
-    if (prob.potential == NSVD_POT_HYDROGEN) V = -(prob.charge_or_k / r0);
-    else V = prob.charge_or_k * (r0 * r0);
+    const float V = nsvd_potential(prob, r0);
     const float kinetic = -prob.scale_kinetic * lap;
     const float H = kinetic + V * fs;
     NsvdFdOut o;
     o.f = fs;
     o.Tf = prob.op_scale * (-H) + prob.op_shift * fs;
     const float w = (sp0 / spc) * prob.hard_mul_const;
-    o.jac = w * mask0;
-    o.dsc = has_mask ? w * bv0 * mask0 * r0 / (s_l * s_l) : 0.f;
+    o.jac = w * mask0 * M0;
+    o.dsc = has_mask ? w * bv0 * mask0 * r0 / (s_l * s_l) * M0 : 0.f;
     return o;
 }
 
@@ -71,19 +156,30 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_combine(const float* g, float sp0, 
 //     g_+ + g_- - 2 g_0 = c w0 [ (rho_+ + rho_-)(base0 + bE) + 2 bE + (rho_+ - rho_-) bO ]
 // - every term small, none the difference of two large numbers: the float32 result carries the Laplacian to ~1e-6 where
 // the point-wise form (nsvd_fd_combine, the reference's own float32 arithmetic) carries it to a few per cent.
+// With a box mask the weight at x +- eps e_d is w0 (1 + rho_+-) M_rest (m0 + delta_+-) - along d only m(x_d) changes,
+// M_rest = prod_{j != d} m(x_j) - and (1 + rho)(m0 + delta) = m0 + sigma, sigma = m0 rho + delta + rho delta:
+//     g_+ + g_- - 2 g_0 = c w0 M_rest [ (sigma_+ + sigma_-)(base0 + bE) + 2 m0 bE + (sigma_+ - sigma_-) bO ]
+// with sigma_+ +- sigma_- from the even / odd parts of rho (ev, od) and of delta (nsvd_box_eo: ds, dd):
+//     rho_+ delta_+ +- rho_- delta_- = (ev ds + od dd) / 2, (ev dd + od ds) / 2
 __device__ __forceinline__ NsvdFdOut nsvd_fd_evenodd(float base0, const float* bE, const float* bO, const float* xc,
                                                      int D, bool has_mask, float s_l, const nsvd_problem& prob,
-                                                     float log_norm) {
+                                                     float log_norm, const NsvdBox& box) {
     float r2 = 0.f;
     for (int d = 0; d < D; ++d) r2 = fmaf(xc[d], xc[d], r2);
     const float r0 = sqrtf(r2);
     const float c = prob.hard_mul_const;
-    const float sp0 = prob.use_importance ? nsvd_sqrt_gauss_pdf(xc, D, prob.sigma, log_norm) : 1.f;
+    const float sp0 = nsvd_sqrt_p(prob, xc, D, log_norm);
     const float mk0 = has_mask ? expf(-r0 / s_l) : 1.f;
     const float eps = prob.eps;
-    const float qs = prob.use_importance ? -1.f / (4.f * prob.sigma * prob.sigma) : 0.f;  // d log sqrt p / d |x|^2
+    // d log sqrt p / d |x|^2 (the uniform density is a constant)
+    const float qs = prob.use_importance == NSVD_IMP_GAUSSIAN ? -1.f / (4.f * prob.sigma * prob.sigma) : 0.f;
     const float e2 = eps * eps;
     float acc = 0.f;
+    // (no per-direction arrays for the box mask: indexed by a run-time d they would live in scratch memory, in every
+    // instance of the fused forward, the headline's included - M_rest is recomputed from xc instead)
+    float M0 = 1.f;
+    if (box.mode)
+        for (int d = 0; d < D; ++d) M0 *= nsvd_box_m1(box.lim - xc[d], box.lim + xc[d], box);
     for (int d = 0; d < D; ++d) {
         // log w(x_+-) - log w(x0) = s +- a, split into its even part s = O(eps^2) and odd part a = O(eps) BEFORE any
         // exponential: rho_+ + rho_- is O(eps^2) while each rho is O(eps), so expm1(s + a) + expm1(s - a) loses
@@ -107,32 +203,41 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_evenodd(float base0, const float* b
         const float sh = sinhf(0.5f * av), chm1 = 2.f * sh * sh, es1 = expm1f(sv);
         const float ev = 2.f * (es1 * (1.f + chm1) + chm1);  // rho_+ + rho_-
         const float od = 2.f * (1.f + es1) * sinhf(av);      // rho_+ - rho_-
-        acc += ev * (base0 + bE[d]) + 2.f * bE[d] + od * bO[d];
+        if (box.mode) {
+            float Mrest = 1.f;
+            for (int j = 0; j < D; ++j)
+                if (j != d) Mrest *= nsvd_box_m1(box.lim - xc[j], box.lim + xc[j], box);
+            const NsvdBoxEO bm = nsvd_box_eo(xc[d], eps, box);
+            const float m0 = bm.m0, ds = bm.ds, dd = bm.dd;
+            const float sgs = m0 * ev + ds + 0.5f * (ev * ds + od * dd);  // sigma_+ + sigma_-
+            const float sgd = m0 * od + dd + 0.5f * (ev * dd + od * ds);  // sigma_+ - sigma_-
+            acc += Mrest * (sgs * (base0 + bE[d]) + 2.f * m0 * bE[d] + sgd * bO[d]);
+        } else {
+            acc += ev * (base0 + bE[d]) + 2.f * bE[d] + od * bO[d];
+        }
     }
     const float eps2 = (float)((double)prob.eps * (double)prob.eps);
     const float spc = prob.use_importance ? fmaxf(sp0, NSVD_SQRT_P_CLAMP) : 1.f;
     const float lap = ((c * (sp0 * mk0)) * acc / eps2) / spc;
-    const float fs = (sp0 * (c * base0 * mk0)) / spc;
-    float V;
-    if (prob.potential == NSVD_POT_HYDROGEN) V = -(prob.charge_or_k / r0);
-    else V = prob.charge_or_k * (r0 * r0);
+    const float fs = (sp0 * (c * base0 * (mk0 * M0))) / spc;
+    const float V = nsvd_potential(prob, r0);
     const float H = -prob.scale_kinetic * lap + V * fs;
     NsvdFdOut o;
     o.f = fs;
     o.Tf = prob.op_scale * (-H) + prob.op_shift * fs;
     const float w = (sp0 / spc) * c;
-    o.jac = w * mk0;
-    o.dsc = has_mask ? w * base0 * mk0 * r0 / (s_l * s_l) : 0.f;
+    o.jac = w * (mk0 * M0);
+    o.dsc = has_mask ? w * base0 * (mk0 * M0) * r0 / (s_l * s_l) : 0.f;
     return o;
 }
 
 __device__ __forceinline__ NsvdFdOut nsvd_fd_point(const float* bv, const float* xc, int D, bool has_mask, float s_l,
-                                                   const nsvd_problem& prob, float log_norm) {
+                                                   const nsvd_problem& prob, float log_norm, const NsvdBox& box) {
     const int E = 1 + 2 * D;
     float g[2 * NSVD_FD_MAXD + 1];
     float sp0 = 1.f, mask0 = 1.f, r0 = 0.f;
     for (int e = 0; e < E; ++e) {
-        const NsvdFdG o = nsvd_fd_g(e, bv[e], xc, D, has_mask, s_l, prob, log_norm);
+        const NsvdFdG o = nsvd_fd_g(e, bv[e], xc, D, has_mask, s_l, prob, log_norm, box);
         g[e] = o.g;
         if (e == 0) {
             sp0 = o.sp;
@@ -140,7 +245,8 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_point(const float* bv, const float*
             r0 = o.r;
         }
     }
-    return nsvd_fd_combine(g, sp0, mask0, r0, bv[0], D, has_mask, s_l, prob);
+    return nsvd_fd_combine(g, sp0, mask0, r0, bv[0], D, has_mask, s_l, prob,
+                           box.mode ? nsvd_box_point(xc, D, 0, prob.eps, box) : 1.f);
 }
 
 // Exact-Laplacian mode (laplacian_eps <= 0: VectorizedLaplacian.exact_laplacian, diff_ops.py:54-61): the model's
@@ -149,18 +255,25 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_point(const float* bv, const float*
 //   sqrt p = C exp(-|x|^2 / (4 sigma^2)):  grad = -x / (2 sigma^2) sqrt p,  Lap = (-D / (2 sigma^2) + |x|^2 / (4 sigma^4)) sqrt p
 //   mask   = exp(-r / s):                  grad = -(x / r) / s mask,        Lap = (1 / s^2 - (D - 1) / (r s)) mask
 //   Lap(u v) = u Lap v + 2 grad u . grad v + v Lap u;  then lap / clamp(sqrt p), f = g / clamp(sqrt p), Tf as above.
+// Box mask: U = u M, grad M_d = m'(x_d) prod_{j != d} m(x_j) =: G_d, Lap M = sum_d m''(x_d) prod_{j != d} m(x_j) (no
+// division by m_d), grad U = u (M gu x + G), Lap U = u (M lu + 2 gu x . G + Lap M); outside the box all of it is 0:
+//   sqrt: A = lim^2 + a b, m' = -t / (lim sqrt A), m'' = -2 lim / A^(3/2)
+//   exp:  m' = -(e^-a - e^-b), m'' = -(e^-a + e^-b)
 __device__ __forceinline__ NsvdFdOut nsvd_fd_exact(float base, const float* dbase, float lbase, const float* xc, int D,
-                                                   bool has_mask, float s_l, const nsvd_problem& prob, float log_norm) {
+                                                   bool has_mask, float s_l, const nsvd_problem& prob, float log_norm,
+                                                   const NsvdBox& box) {
     float r2 = 0.f;
     for (int d = 0; d < D; ++d) r2 = fmaf(xc[d], xc[d], r2);
     const float r0 = sqrtf(r2);
     const float c = prob.hard_mul_const;
     float sp = 1.f, lsp_f = 0.f, dsp_f = 0.f;  // sqrt p, Lap sqrt p / sqrt p, and grad sqrt p = dsp_f * x * sqrt p
-    if (prob.use_importance) {
+    if (prob.use_importance == NSVD_IMP_GAUSSIAN) {
         sp = nsvd_sqrt_gauss_pdf(xc, D, prob.sigma, log_norm);
         const float is2 = 1.f / (2.f * prob.sigma * prob.sigma);
         dsp_f = -is2;
         lsp_f = -(float)D * is2 + r2 * is2 * is2;
+    } else if (prob.use_importance == NSVD_IMP_UNIFORM) {
+        sp = nsvd_sqrt_p(prob, xc, D, log_norm);
     }
     float mk = 1.f, lmk_f = 0.f, dmk_f = 0.f;  // mask, Lap mask / mask, grad mask = dmk_f * x * mask
     if (has_mask) {
@@ -174,21 +287,51 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_exact(float base, const float* dbas
     float dot = 0.f;
     for (int d = 0; d < D; ++d) dot = fmaf(xc[d], dbase[d], dot);
     const float lu = lsp_f + 2.f * dsp_f * dmk_f * r2 + lmk_f;
-    const float g = u * base;
+    float g = u * base;
     float lap = u * (lbase + 2.f * gu * dot + base * lu);
+    float M = 1.f;
+    if (box.mode) {
+        float m[NSVD_FD_MAXD], m1[NSVD_FD_MAXD], m2[NSVD_FD_MAXD];
+        for (int d = 0; d < D; ++d) {
+            const float a = box.lim - xc[d], b = box.lim + xc[d];
+            m[d] = nsvd_box_m1(a, b, box);
+            m1[d] = m2[d] = 0.f;
+            if (a > 0.f && b > 0.f) {
+                if (box.mode == NSVD_BOX_SQRT) {
+                    const float A = fmaf(box.lim, box.lim, a * b), sA = sqrtf(A);
+                    m1[d] = -xc[d] / (box.lim * sA);
+                    m2[d] = -2.f * box.lim / (A * sA);
+                } else {
+                    const float ea = expf(-a), eb = expf(-b);
+                    m1[d] = -(ea - eb);
+                    m2[d] = -(ea + eb);
+                }
+            }
+            M *= m[d];
+        }
+        float gdot = 0.f, xG = 0.f, lM = 0.f;  // G . grad base, x . G, Lap M
+        for (int d = 0; d < D; ++d) {
+            float Mrest = 1.f;
+            for (int j = 0; j < D; ++j)
+                if (j != d) Mrest *= m[j];
+            gdot = fmaf(m1[d] * Mrest, dbase[d], gdot);
+            xG = fmaf(m1[d] * Mrest, xc[d], xG);
+            lM = fmaf(m2[d], Mrest, lM);
+        }
+        g = u * M * base;
+        lap = u * (M * lbase + 2.f * (M * gu * dot + gdot) + base * (M * lu + 2.f * gu * xG + lM));
+    }
     const float spc = prob.use_importance ? fmaxf(sp, NSVD_SQRT_P_CLAMP) : 1.f;
     lap = lap / spc;
     const float fs = g / spc;
-    float V;
-    if (prob.potential == NSVD_POT_HYDROGEN) V = -(prob.charge_or_k / r0);
-    else V = prob.charge_or_k * (r0 * r0);
+    const float V = nsvd_potential(prob, r0);
     const float H = -prob.scale_kinetic * lap + V * fs;
     NsvdFdOut o;
     o.f = fs;
     o.Tf = prob.op_scale * (-H) + prob.op_shift * fs;
     const float w = (sp / spc) * c;
-    o.jac = w * mk;
-    o.dsc = has_mask ? w * base * mk * r0 / (s_l * s_l) : 0.f;
+    o.jac = w * (mk * M);
+    o.dsc = has_mask ? w * base * (mk * M) * r0 / (s_l * s_l) : 0.f;
     return o;
 }
 
@@ -269,9 +412,7 @@ __device__ __forceinline__ NsvdNefOut nsvd_nef_evenodd(float base0, const float*
     const float h = u0 / n0;
     const float lap = ((c * (sp0 * mk0) / n0) * acc / eps2) / spc;
     const float fs = (sp0 * h) / spc;
-    float V;
-    if (prob.potential == NSVD_POT_HYDROGEN) V = -(prob.charge_or_k / r0);
-    else V = prob.charge_or_k * (r0 * r0);
+    const float V = nsvd_potential(prob, r0);
     const float H = -prob.scale_kinetic * lap + V * fs;
     NsvdNefOut o;
     o.phi = fs;

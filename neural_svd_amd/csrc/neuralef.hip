@@ -364,7 +364,9 @@ extern "C" int nsvd_nef_operator_forward(const nsvd_model_desc* desc, const nsvd
     if (desc->D < 1 || desc->D > NSVD_FD_MAXD || desc->L <= 0) return NSVD_EINVAL;
     if (desc->has_exp_mask && !params->scales) return NSVD_EINVAL;
     if (ws_bytes < nsvd_workspace_bytes(desc, B) || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
-    if (prob->potential != NSVD_POT_HYDROGEN && prob->potential != NSVD_POT_HARMONIC) return NSVD_EINVAL;
+    if (prob->potential < NSVD_POT_HYDROGEN || prob->potential > NSVD_POT_ZERO) return NSVD_EINVAL;
+    // the per-point batch norms know neither the box mask nor the uniform density (nsvd_operator_forward_raw refuses too)
+    if (desc->box_mask != NSVD_BOX_NONE || prob->use_importance > NSVD_IMP_GAUSSIAN) return NSVD_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     NsvdRawOut o;
     int rc = nsvd_operator_forward_raw(*desc, *params, *prob, x, B, ws, path, s, &o);

@@ -16,6 +16,18 @@
     } while (0)
 
 static inline int nsvd_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// the model's Dirichlet box mask as the kernels take it (fd_math.h); mode 0: none
+struct NsvdBox {
+    int mode;   // NSVD_BOX_*
+    float lim;  // half-width
+};
+static inline NsvdBox nsvd_box_of(const nsvd_model_desc& d) {
+    NsvdBox b;
+    b.mode = d.box_mask;
+    b.lim = d.box_lim;
+    return b;
+}
 static inline size_t nsvd_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 // softplus(z) = log(1 + e^z) with torch's threshold. Hardware exp2/log2 (v_exp_f32 / v_log_f32, ~1 ulp) plus the
@@ -173,6 +185,7 @@ struct NsvdSampler {
     unsigned long long offset;  // call counter (one per batch)
     float sigma;
     int on;                     // 0: coordinates are read from x
+    int kind;                   // nsvd_problem.use_importance: NSVD_IMP_UNIFORM draws sigma (2 u - 1), else sigma N(0, 1)
     // device counter added to `offset` (nsvd_step_state::step), or null: the batch counter of a step captured in a
     // HIP graph lives on the device, `offset` is then the constant base
     const unsigned long long* offset_add;
@@ -201,6 +214,14 @@ __device__ __forceinline__ void nsvd_sample_row(const NsvdSampler& s, int b, int
     const unsigned long long off = s.offset + (s.offset_add ? *s.offset_add : 0ull);
     nsvd_philox4x32_10((unsigned)b, (unsigned)off, (unsigned)(off >> 32), 0x6e737664u, (unsigned)s.seed,
                        (unsigned)(s.seed >> 32), r);
+    if (s.kind == NSVD_IMP_UNIFORM) {
+        // uniform on (-sigma, sigma) (main_pde.py:113-115): u = (23 bits + 1/2) / 2^23 in (0, 1), 2 u - 1 exact in
+        // float32 and at most 1 - 2^-23 in magnitude - a draw never lands on a wall of the box
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+            if (d < D) xr[d] = s.sigma * (2.0f * (((float)(r[d] >> 9) + 0.5f) * (1.0f / 8388608.0f)) - 1.0f);
+        return;
+    }
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
         if (2 * pr >= D) break;

@@ -59,15 +59,16 @@ int nsvd_rowsum(const float* in, float* out, int rows, int n, long ld, hipStream
 // evenodd != 0: rows 1 + 2 d / 2 + 2 d of `base` hold the EVEN / ODD perturbations of the head output along direction d
 // (base(x +- eps e_d) = base[0] + even_d +- odd_d: the fused kernels' split-stencil form) instead of the point values
 int nsvd_fd_epilogue(const float* base, int ldr, const float* x, const float* scales, const nsvd_problem& prob,
-                     int B, int D, int L, float* f, float* Tf, float* jac, float* dsc, hipStream_t s, int evenodd = 0);
+                     int B, int D, int L, float* f, float* Tf, float* jac, float* dsc, hipStream_t s, int evenodd = 0,
+                     NsvdBox box = NsvdBox{0, 0.f});
 // dzT[l][b] = df[b][l] * jac[b][l]; dscales[l] = sum_b df[b][l] * dsc[b][l] (when dscales != null)
 int nsvd_head_backward(const float* df, const float* jac, const float* dsc, int B, int L, float* dzT,
                        float* dscales, hipStream_t s);
 
-// out[b][l] = c * base[l*ldr + b] * exp(-|x_b| / scales[l])   (WaveFunctions.forward at the centre rows)
+// out[b][l] = c * base[l*ldr + b] * exp(-|x_b| / scales[l]) * box mask(x_b)   (WaveFunctions.forward at the centre rows)
 // optional jac = d out / d base, dsc = d out / d scales (both (B, L)) for nsvd_model_backward
 int nsvd_model_out(const float* base, int ldr, const float* x, const float* scales, float c, int B, int D, int L,
-                   float* out, float* jac, float* dsc, hipStream_t s);
+                   float* out, float* jac, float* dsc, hipStream_t s, NsvdBox box = NsvdBox{0, 0.f});
 
 // reduce the per-chunk partial moments of nsvd_evd_partial into the (2 L^2 + 1) vector (evd_loss.hip)
 int nsvd_evd_reduce_partials(const void* scratch, int B, int L, float* moments, hipStream_t s);

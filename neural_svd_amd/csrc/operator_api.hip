@@ -47,8 +47,29 @@ int validate(const nsvd_model_desc* d, int max_d = 4) {
     for (int i = 0; i < d->nlayers; ++i)
         if (d->dims[i] <= 0) return NSVD_EINVAL;
     if (d->dims[d->nlayers - 1] != 1) return NSVD_EINVAL;
+    if (d->box_mask < NSVD_BOX_NONE || d->box_mask > NSVD_BOX_EXP) return NSVD_EINVAL;
+    if (d->box_mask != NSVD_BOX_NONE && !(d->box_lim > 0.f)) return NSVD_EINVAL;
     if (d->D > max_d) return NSVD_EUNSUPPORTED;
     return 0;
+}
+
+// every operator path implements every potential and importance below; anything else is refused, never ignored
+int validate_problem(const nsvd_problem* p) {
+    if (!p) return NSVD_EINVAL;
+    if (p->potential < NSVD_POT_HYDROGEN || p->potential > NSVD_POT_ZERO) return NSVD_EINVAL;
+    if (p->use_importance < NSVD_IMP_NONE || p->use_importance > NSVD_IMP_UNIFORM) return NSVD_EINVAL;
+    return 0;
+}
+
+NsvdSampler make_sampler(const nsvd_problem& prob, unsigned long long seed, unsigned long long offset) {
+    NsvdSampler smp;
+    memset(&smp, 0, sizeof(smp));
+    smp.seed = seed;
+    smp.offset = offset;
+    smp.sigma = prob.sigma;
+    smp.on = 1;
+    smp.kind = prob.use_importance;  // the batch is drawn from the density the problem names
+    return smp;
 }
 
 // erows: stencil blocks the layout holds (1 + 2D for the operator, 1 for plain model evaluation)
@@ -139,7 +160,7 @@ int generic_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_p
     int rc = generic_mlp(d, p, x, B, prob.eps, E, w, s, features_ready);
     if (rc) return rc;
     rc = nsvd_fd_epilogue(w.z[d.nlayers - 1], R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L, f, Tf,
-                          w.jac, w.dsc, s, 1);
+                          w.jac, w.dsc, s, 1, nsvd_box_of(d));
     nsvd_prof_end(s);
     return rc;
 }
@@ -207,7 +228,7 @@ extern "C" int nsvd_step_emits_planes(const nsvd_model_desc* desc, int B, int pa
 }
 
 extern "C" const char* nsvd_path_name_for(const nsvd_model_desc* desc, const nsvd_problem* prob, int B, int path) {
-    if (validate(desc) != 0 || B <= 0 || !prob) return "invalid";
+    if (validate(desc) != 0 || B <= 0 || validate_problem(prob) != 0) return "invalid";
     const bool exact = !(prob->eps > 0.f);
     if (want_fused(*desc, B, path, exact)) return "fused_mfma";
     return exact ? "unsupported" : "generic";
@@ -233,7 +254,8 @@ extern "C" int nsvd_operator_forward(const nsvd_model_desc* desc, const nsvd_par
     int rc = validate(desc);
     if (rc) return rc;
     if (!prob || !x || !f || !Tf || !ws || B <= 0) return NSVD_EINVAL;
-    if (prob->potential != NSVD_POT_HYDROGEN && prob->potential != NSVD_POT_HARMONIC) return NSVD_EINVAL;
+    rc = validate_problem(prob);
+    if (rc) return rc;
     rc = check_params(*desc, params, true);
     if (rc) return rc;
     if (ws_bytes < nsvd_workspace_bytes(desc, B)) return NSVD_EINVAL;
@@ -258,6 +280,8 @@ int nsvd_operator_forward_raw(const nsvd_model_desc& d, const nsvd_params& p, co
     const bool fused = want_fused(d, B, path, !(prob.eps > 0.f));
     if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
     if (path == NSVD_PATH_FUSED_BF16X3 || !(prob.eps > 0.f)) return NSVD_EUNSUPPORTED;
+    // the per-point batch norms know neither the box mask nor the uniform density
+    if (d.box_mask != NSVD_BOX_NONE || prob.use_importance > NSVD_IMP_GAUSSIAN) return NSVD_EUNSUPPORTED;
     const int R = (1 + 2 * d.D) * B;
     if (fused) {
         const FusedWsView v = nsvd_fused_ws_view(d, B, ws);
@@ -303,15 +327,13 @@ int sample_features_impl(const nsvd_model_desc* desc, const nsvd_params* params,
     int rc = validate(desc);
     if (rc) return rc;
     if (!prob || !x || !ws || !params || !params->fourier_B || B <= 0) return NSVD_EINVAL;
+    rc = validate_problem(prob);
+    if (rc) return rc;
     if (ws_bytes < nsvd_workspace_bytes(desc, B)) return NSVD_EINVAL;
     if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
     const bool fused = want_fused(*desc, B, path, !(prob->eps > 0.f));
     if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
-    NsvdSampler smp;
-    smp.seed = seed;
-    smp.offset = offset;
-    smp.sigma = prob->sigma;
-    smp.on = 1;
+    NsvdSampler smp = make_sampler(*prob, seed, offset);
     smp.offset_add = state ? (const unsigned long long*)&state->step : nullptr;
     hipStream_t s = (hipStream_t)stream;
     if (fused) return nsvd_fused_features(*desc, *params, *prob, x, B, ws, save_for_backward & 1, s, &smp, x);
@@ -363,7 +385,8 @@ extern "C" int nsvd_model_forward(const nsvd_model_desc* desc, const nsvd_params
     if (rc) return rc;
     return nsvd_model_out(w.z[desc->nlayers - 1], R, x, desc->has_exp_mask ? params->scales : nullptr,
                           hard_mul_const, B, desc->D, desc->L, out, save_for_backward ? w.jac : nullptr,
-                          (save_for_backward && desc->has_exp_mask) ? w.dsc : nullptr, (hipStream_t)stream);
+                          (save_for_backward && desc->has_exp_mask) ? w.dsc : nullptr, (hipStream_t)stream,
+                          nsvd_box_of(*desc));
 }
 
 extern "C" int nsvd_model_backward(const nsvd_model_desc* desc, const nsvd_params* params, const float* x, int B,
@@ -594,11 +617,9 @@ extern "C" int nsvd_operator_backward_evd_step_window(const nsvd_model_desc* des
     if (x_next) {  // the next batch rides in THIS window's chain launch (pass it to one window of the step only)
         if (!ws_next || ws_next == ws) return NSVD_EINVAL;
         if (ws_next_bytes < nsvd_workspace_bytes(desc, B) || ((uintptr_t)ws_next & 255) != 0) return NSVD_EINVAL;
+        if (validate_problem(prob) != 0) return NSVD_EINVAL;
         memset(&nb, 0, sizeof(nb));
-        nb.smp.seed = next_seed;
-        nb.smp.offset = next_offset;
-        nb.smp.sigma = prob->sigma;
-        nb.smp.on = 1;
+        nb.smp = make_sampler(*prob, next_seed, next_offset);
         nb.x = x_next;
         nb.ws = ws_next;
         nb.eps = prob->eps;
@@ -620,12 +641,10 @@ extern "C" int nsvd_operator_backward_evd_step_next(const nsvd_model_desc* desc,
                                                     size_t ws_next_bytes, void* stream) {
     if (!opt || !prob || !x_next || !ws_next || ws_next == ws) return NSVD_EINVAL;
     if (ws_next_bytes < nsvd_workspace_bytes(desc, B) || ((uintptr_t)ws_next & 255) != 0) return NSVD_EINVAL;
+    if (validate_problem(prob) != 0) return NSVD_EINVAL;
     NsvdNextBatch nb;
     memset(&nb, 0, sizeof(nb));
-    nb.smp.seed = next_seed;
-    nb.smp.offset = next_offset;
-    nb.smp.sigma = prob->sigma;
-    nb.smp.on = 1;
+    nb.smp = make_sampler(*prob, next_seed, next_offset);
     nb.x = x_next;
     nb.ws = ws_next;
     nb.eps = prob->eps;

@@ -40,6 +40,7 @@ struct FwdArgs {
     const float* scales;
     nsvd_problem prob;
     float log_norm;
+    NsvdBox box;         // the model's Dirichlet box mask (epilogues only; mode 0: none)
     int B, D, L, F;
     float* f;
     float* Tf;
@@ -766,7 +767,8 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
                     bO[dd] = __builtin_nontemporal_load(br + (size_t)(2 + 2 * dd) * a.B);
                 }
                 const float s_l = a.scales ? a.scales[l] : 0.f;
-                const NsvdFdOut o = nsvd_fd_evenodd(b0v, bE, bO, xc, a.D, a.scales != nullptr, s_l, a.prob, a.log_norm);
+                const NsvdFdOut o = nsvd_fd_evenodd(b0v, bE, bO, xc, a.D, a.scales != nullptr, s_l, a.prob, a.log_norm,
+                                                    a.box);
                 const size_t idx = (size_t)b * a.L + l;
                 a.f[idx] = o.f;
                 a.Tf[idx] = o.Tf;
@@ -797,6 +799,14 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
                 s_l = a.scales[l];
                 mk = expf(-r / s_l);
             }
+            if (a.box.mode) {  // the box mask is a plain factor of the output: it joins mk (and with it jac, dsc)
+                float M = 1.f;
+                for (int d = 0; d < a.D; ++d) {
+                    const float xv = a.x[(size_t)b * a.D + d];
+                    M *= nsvd_box_m1(a.box.lim - xv, a.box.lim + xv, a.box);
+                }
+                mk *= M;
+            }
             const size_t idx = (size_t)b * a.L + l;
             a.f[idx] = c * bv * mk;
             if (a.jac) a.jac[idx] = c * mk;
@@ -818,7 +828,7 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
             }
             const float s_l = a.scales ? a.scales[l] : 0.f;
             const NsvdFdOut o = nsvd_fd_exact(gs[tid], db, gs[(E - 1) * BS + tid], xc, a.D, a.scales != nullptr, s_l,
-                                              a.prob, a.log_norm);
+                                              a.prob, a.log_norm, a.box);
             const size_t idx = (size_t)b * a.L + l;
             a.f[idx] = o.f;
             a.Tf[idx] = o.Tf;
@@ -848,7 +858,8 @@ __global__ void __launch_bounds__(256, 1) pmlp_fused_fwd_kernel(FwdArgs a) {
                 bO[d] = gs[(2 + 2 * d) * BS + tid];
             }
             const float s_l = a.scales ? a.scales[l] : 0.f;
-            const NsvdFdOut o = nsvd_fd_evenodd(gs[tid], bE, bO, xc, a.D, a.scales != nullptr, s_l, a.prob, a.log_norm);
+            const NsvdFdOut o = nsvd_fd_evenodd(gs[tid], bE, bO, xc, a.D, a.scales != nullptr, s_l, a.prob, a.log_norm,
+                                                a.box);
             const size_t idx = (size_t)b * a.L + l;
             a.f[idx] = o.f;
             a.Tf[idx] = o.Tf;
@@ -959,7 +970,8 @@ int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsv
     a.x = x;
     a.scales = d.has_exp_mask ? p.scales : nullptr;
     a.prob = prob;
-    a.log_norm = nsvd_gauss_log_norm(d.D, prob.sigma);
+    a.log_norm = nsvd_importance_log_norm(d.D, prob);
+    a.box = nsvd_box_of(d);
     a.B = B; a.D = d.D; a.L = d.L; a.F = F;
     a.f = f; a.Tf = Tf;
     a.jac = save ? w.jac : nullptr;
@@ -1021,7 +1033,7 @@ int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsv
         rc = launch_fwd<3, 0, 0, 0, 2>(a, s, 2);
         if (rc || a.tickets || raw) return rc;  // (tickets: the last direction group of every tile has formed f, Tf)
         return nsvd_fd_epilogue(w.base_raw, R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L, f, Tf,
-                                save ? w.jac : nullptr, (save && d.has_exp_mask) ? w.dsc : nullptr, s, 1);
+                                save ? w.jac : nullptr, (save && d.has_exp_mask) ? w.dsc : nullptr, s, 1, a.box);
     }
     // split-stencil form: D = 3 (7 stencil columns do not fit one workgroup's LDS image), and D = 2 when the plain grid
     // would leave at least half of the CUs without a workgroup (cfg1: 64 -> 128 workgroups of three column tiles)
@@ -1044,7 +1056,7 @@ int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsv
         }
         if (rc || raw) return rc;
         return nsvd_fd_epilogue(w.base_raw, R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L, f, Tf,
-                                save ? w.jac : nullptr, (save && d.has_exp_mask) ? w.dsc : nullptr, s, 1);
+                                save ? w.jac : nullptr, (save && d.has_exp_mask) ? w.dsc : nullptr, s, 1, a.box);
     }
     if (raw) a.raw = w.base_raw;
     switch (E) {
@@ -1079,6 +1091,7 @@ int nsvd_fused_model_forward(const nsvd_model_desc& d, const nsvd_params& p, con
     a.x = x;
     a.scales = d.has_exp_mask ? p.scales : nullptr;
     a.prob.hard_mul_const = c;
+    a.box = nsvd_box_of(d);
     a.plain = 1;
     a.B = B; a.D = d.D; a.L = d.L; a.F = F;
     a.f = out;
@@ -1093,7 +1106,7 @@ int nsvd_fused_model_forward(const nsvd_model_desc& d, const nsvd_params& p, con
             memset(&pa, 0, sizeof(pa));
             pa.phi = w.phi;
             pa.W0 = p.W[0]; pa.b0 = p.b[0]; pa.W1 = p.W[1]; pa.b1 = p.b[1]; pa.Wl = p.W[2]; pa.bl = p.b[2];
-            pa.x = x; pa.scales = a.scales; pa.D = d.D; pa.c = c;
+            pa.x = x; pa.scales = a.scales; pa.D = d.D; pa.c = c; pa.box = a.box;
             pa.out = out; pa.jac = a.jac; pa.dsc = a.dsc;
             pa.z0 = a.zsave[0]; pa.z1 = a.zsave[1];
             pa.B = B; pa.L = d.L; pa.tpw = tpw;

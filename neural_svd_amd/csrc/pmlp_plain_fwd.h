@@ -16,7 +16,8 @@
 struct PlainFwdArgs {
     const float* phi;     // (B, 128) features, sample-major
     const float *W0, *b0, *W1, *b1, *Wl, *bl;  // (L,128,128) (L,128) (L,128,128) (L,128) (L,128) (L)
-    const float* x;       // (B, D), read only with the exponential mask
+    const float* x;       // (B, D), read only with the exponential mask or the box mask
+    NsvdBox box;          // the model's Dirichlet box mask (mode 0: none)
     const float* scales;  // (L) or null
     int D;
     float c;
@@ -166,6 +167,14 @@ __global__ void __launch_bounds__(256, 2) pmlp_plain_stream_fwd_kernel(PlainFwdA
                 r = sqrtf(r2);
                 s_l = a.scales[l];
                 mk = expf(-r / s_l);
+            }
+            if (a.box.mode) {  // the box mask is a plain factor of the output: it joins mk (and with it jac, dsc)
+                float M = 1.f;
+                for (int d = 0; d < a.D; ++d) {
+                    const float xv = a.x[(size_t)b * a.D + d];
+                    M *= nsvd_box_m1(a.box.lim - xv, a.box.lim + xv, a.box);
+                }
+                mk *= M;
             }
             const size_t idx = (size_t)b * a.L + l;
             a.out[idx] = a.c * bv * mk;

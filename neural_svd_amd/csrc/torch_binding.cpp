@@ -59,12 +59,14 @@ void* bytes(Dev& d, const at::Tensor& t, const char* name) {
 // WaveFunctions(ParallelMLP(FourierFeatures)) shape: examples/operator/pde/__init__.py:19-55
 struct Shape {
     nsvd_model_desc d;
-    Shape(int L, int D, int m, std::vector<int> dims, bool has_exp_mask) {
+    Shape(int L, int D, int m, std::vector<int> dims, bool has_exp_mask, int box_mask, double box_lim) {
         memset(&d, 0, sizeof(d));
         TORCH_CHECK(dims.size() >= 1 && dims.size() <= NSVD_MAX_LAYERS, "at most ", NSVD_MAX_LAYERS, " layers");
         d.L = L; d.D = D; d.m = m; d.nlayers = (int)dims.size();
         for (size_t i = 0; i < dims.size(); ++i) d.dims[i] = dims[i];
         d.has_exp_mask = has_exp_mask ? 1 : 0;
+        d.box_mask = box_mask;
+        d.box_lim = (float)box_lim;
     }
 };
 
@@ -110,7 +112,7 @@ struct ParamSet {
 struct Problem {
     nsvd_problem q;
     Problem(int potential, double charge_or_k, double eps, double op_scale, double op_shift, double sigma,
-            double scale_kinetic, double hard_mul_const, bool use_importance) {
+            double scale_kinetic, double hard_mul_const, int use_importance) {
         memset(&q, 0, sizeof(q));
         q.potential = potential;
         q.charge_or_k = (float)charge_or_k;
@@ -120,7 +122,7 @@ struct Problem {
         q.op_shift = (float)op_shift;
         q.sigma = (float)sigma;
         q.hard_mul_const = (float)hard_mul_const;
-        q.use_importance = use_importance ? 1 : 0;
+        q.use_importance = use_importance;  // NSVD_IMP_*
     }
 };
 
@@ -300,11 +302,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                         "nsvd_operator_backward_evd_step_next", "nsvd_rmsprop_ema_step",
                                         "nsvd_spectrum_accumulate"};
     });
-    py::class_<Shape>(m, "Shape").def(py::init<int, int, int, std::vector<int>, bool>());
+    py::class_<Shape>(m, "Shape")
+        .def(py::init<int, int, int, std::vector<int>, bool, int, double>(), py::arg("L"), py::arg("D"), py::arg("m"),
+             py::arg("dims"), py::arg("has_exp_mask"), py::arg("box_mask") = 0, py::arg("box_lim") = 0.0);
     py::class_<ParamSet>(m, "ParamSet")
         .def(py::init<const Shape&, std::vector<at::Tensor>, std::vector<at::Tensor>, c10::optional<at::Tensor>,
                       c10::optional<at::Tensor>>());
-    py::class_<Problem>(m, "Problem").def(py::init<int, double, double, double, double, double, double, double, bool>());
+    py::class_<Problem>(m, "Problem").def(py::init<int, double, double, double, double, double, double, double, int>());
     py::class_<Rmsprop>(m, "Rmsprop")
         .def(py::init<const ParamSet&, const ParamSet*, double, double, double, double, c10::optional<at::Tensor>>(),
              py::keep_alive<1, 2>(), py::keep_alive<1, 3>());

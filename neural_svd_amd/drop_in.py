@@ -135,7 +135,7 @@ def _fused_loop_trainer(args, method, operator, importance_train, device, comm=N
     """A FusedTrainer over the SAME weights when the configuration is one it implements, else None."""
     from .models import WaveFunctions
     from .nested_lowrank import NestedLoRA, nesting_masks
-    from .operators import GaussianImportance, OperatorWrapper, fused_problem_of
+    from .operators import GaussianImportance, OperatorWrapper, UniformImportance, fused_problem_of
     from .trainer import FusedTrainer
     if not getattr(args, "fused_loop", True):
         return None
@@ -143,7 +143,8 @@ def _fused_loop_trainer(args, method, operator, importance_train, device, comm=N
         return None
     if not (isinstance(method, NestedLoRA) and isinstance(method.model, WaveFunctions)) or method.sort_indices is not None:
         return None
-    if not isinstance(operator, OperatorWrapper) or not isinstance(importance_train, GaussianImportance):
+    if not isinstance(operator, OperatorWrapper) or \
+            not isinstance(importance_train, (GaussianImportance, UniformImportance)):
         return None
     if torch.device(device).type != "cuda":
         return None
@@ -340,10 +341,16 @@ def _refresh_from_trainer(tr, method, ema, optimizer, scheduler):
 
 def _refuse_neuralef(args, method, operator):
     """NeuralEF configurations this package does not build, refused up front with the reason."""
+    from .models import WaveFunctions
     from .neuralef import BatchL2NormalizedFunctions, NeuralEigenfunctions
     from .operators import OperatorWrapper
     if not isinstance(method, NeuralEigenfunctions):
         return
+    inner = method.model.base_model if isinstance(method.model, BatchL2NormalizedFunctions) else method.model
+    if isinstance(inner, WaveFunctions) and inner.box is not None:
+        raise NotImplementedError("NeuralEF with a Dirichlet box mask (--apply_boundary 1): the per-stencil-point batch "
+                                  "norms of the NeuralEF forward (nsvd_nef_operator_forward) are built for the "
+                                  "exponential mask only; train this problem with NestedLoRA, or --apply_boundary 0")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise NotImplementedError("NeuralEF on several ranks (WORLD_SIZE > 1): the per-stencil-point batch norms need "
                                   "the whole batch on every rank (an all-reduce per stencil point); only one GPU is "

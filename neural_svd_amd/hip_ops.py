@@ -14,7 +14,8 @@ import torch
 from . import _lib
 from ._lib import (MASK_CUSTOM, MASK_JOINT, MASK_SEQUENTIAL, PATH_AUTO, PATH_FUSED, PATH_FUSED_BF16X3,  # noqa: F401
                    PATH_GENERIC,
-                   POT_HARMONIC, POT_HYDROGEN, ModelDesc, NsvdError, Params, Problem, check)
+                   BOX_EXP, BOX_NONE, BOX_SQRT, IMP_GAUSSIAN, IMP_NONE, IMP_UNIFORM, POT_HARMONIC, POT_HYDROGEN, POT_ZERO,
+                   ModelDesc, NsvdError, Params, Problem, check)
 
 
 # ---- which binding carries the hot-path calls: ctypes (default) or the tensor-level torch extension -----------------
@@ -49,7 +50,8 @@ def torch_binding():
 def _tb_shape(shape: "ModelShape"):
     sh = _TB_SHAPES.get(shape)
     if sh is None:
-        sh = _TB_SHAPES[shape] = _TB.Shape(shape.L, shape.D, shape.m, list(shape.dims), bool(shape.has_exp_mask))
+        sh = _TB_SHAPES[shape] = _TB.Shape(shape.L, shape.D, shape.m, list(shape.dims), bool(shape.has_exp_mask),
+                                               int(shape.box_mask), float(shape.box_lim))
     return sh
 
 
@@ -66,7 +68,7 @@ def _tb_problem(prob: Problem):
     q = getattr(prob, "_tb", None)
     if q is None:
         q = prob._tb = _TB.Problem(prob.potential, prob.charge_or_k, prob.eps, prob.op_scale, prob.op_shift, prob.sigma,
-                                   prob.scale_kinetic, prob.hard_mul_const, bool(prob.use_importance))
+                                   prob.scale_kinetic, prob.hard_mul_const, int(prob.use_importance))
     return q
 
 
@@ -117,12 +119,16 @@ def _on_tensor_device(fn):
 
 @dataclass(frozen=True)
 class ModelShape:
-    """Shape of WaveFunctions(ParallelMLP(FourierFeatures)); ``hidden`` excludes the final width 1."""
+    """Shape of WaveFunctions(ParallelMLP(FourierFeatures)); ``hidden`` excludes the final width 1.
+    box_mask / box_lim: the Dirichlet box mask (BOX_SQRT / BOX_EXP on [-box_lim, box_lim]^D), alone or inside the
+    exponential mask; it has no parameters."""
     L: int
     D: int
     m: int
     hidden: Tuple[int, ...]
     has_exp_mask: bool = False
+    box_mask: int = 0
+    box_lim: float = 0.0
 
     @property
     def dims(self) -> Tuple[int, ...]:
@@ -138,6 +144,8 @@ class ModelShape:
         for i, h in enumerate(dims):
             d.dims[i] = h
         d.has_exp_mask = int(self.has_exp_mask)
+        d.box_mask = int(self.box_mask)
+        d.box_lim = float(self.box_lim)
         return d
 
     def param_shapes(self) -> List[Tuple[int, ...]]:
@@ -154,7 +162,10 @@ class ModelShape:
 
 
 def make_problem(potential: int, charge_or_k: float, eps: float, op_scale: float, op_shift: float, sigma: float,
-                 scale_kinetic: float = 1.0, hard_mul_const: float = 1.0, use_importance: bool = True) -> Problem:
+                 scale_kinetic: float = 1.0, hard_mul_const: float = 1.0, use_importance: bool = True,
+                 importance_kind: Optional[int] = None) -> Problem:
+    """importance_kind (IMP_NONE / IMP_GAUSSIAN / IMP_UNIFORM) names the density when given; otherwise use_importance
+    chooses between none and the Gaussian. ``sigma`` is the sampling scale of either density."""
     p = Problem()
     p.potential = int(potential)
     p.charge_or_k = float(charge_or_k)
@@ -164,7 +175,11 @@ def make_problem(potential: int, charge_or_k: float, eps: float, op_scale: float
     p.op_shift = float(op_shift)
     p.sigma = float(sigma)
     p.hard_mul_const = float(hard_mul_const)
-    p.use_importance = int(bool(use_importance))
+    if importance_kind is None:
+        importance_kind = IMP_GAUSSIAN if use_importance else IMP_NONE
+    if int(importance_kind) not in (IMP_NONE, IMP_GAUSSIAN, IMP_UNIFORM):
+        raise NsvdError(f"importance_kind {importance_kind}: IMP_NONE, IMP_GAUSSIAN or IMP_UNIFORM")
+    p.use_importance = int(importance_kind)
     return p
 
 

@@ -5,6 +5,7 @@ every evaluation done by the HIP library.
 
     GaussianFourierFeatureTransform   examples/utils.py:90-143
     ParallelMLP                       examples/models/mlp.py:167-221
+    DirichletBoundaryMaskBox          examples/operator/pde/boundary.py:16-36
     ExponentialMask                   examples/operator/pde/boundary.py:39-53
     WaveFunctions / get_wavefunctions examples/operator/pde/__init__.py:8-55
 """
@@ -72,10 +73,10 @@ class ParallelMLP(nn.Module):
         self.ws, self.bs = ws, bs
         self.bias, self.weight_normalization = True, False
 
-    def model_shape(self, has_exp_mask: bool) -> H.ModelShape:
+    def model_shape(self, has_exp_mask: bool, box_mask: int = 0, box_lim: float = 0.0) -> H.ModelShape:
         fm = self.feature_map
         return H.ModelShape(L=self.num_copies, D=fm._B.shape[0], m=fm._B.shape[1], hidden=self.hidden,
-                            has_exp_mask=has_exp_mask)
+                            has_exp_mask=has_exp_mask, box_mask=int(box_mask), box_lim=float(box_lim))
 
     @torch.no_grad()
     def forward(self, x):
@@ -85,18 +86,51 @@ class ParallelMLP(nn.Module):
         return H.model_forward(shape, p, x, 1.0, H.model_workspace(shape, x.shape[0], x.device))
 
 
+class DirichletBoundaryMaskBox(nn.Module):
+    """Zero Dirichlet condition on the box [-lim, lim]^D (boundary.py:16-36): M(x) = prod_d m(clamp(x_d, -lim, lim)),
+    dir_box_sqrt: m(t) = max((sqrt(2 lim^2 - t^2) - lim) / lim, 0); dir_box_exp: m(t) = (1 - e^-(lim - t))(1 - e^-(lim + t)).
+    No parameters, no buffers. Inside WaveFunctions the HIP kernels evaluate it (include/nsvd.h: box_mask); this torch
+    ``forward`` serves foreign callers."""
+    MODES = {"dir_box_sqrt": H.BOX_SQRT, "dir_box_exp": H.BOX_EXP}
+
+    def __init__(self, lim, mode="dir_box_sqrt"):
+        super().__init__()
+        assert mode in self.MODES, mode
+        if not float(lim) > 0:
+            raise ValueError(f"DirichletBoundaryMaskBox: lim must be positive (got {lim})")
+        self.lim = lim
+        self.mode = mode
+
+    @property
+    def kind(self) -> int:
+        return self.MODES[self.mode]
+
+    def forward(self, x):
+        lim = self.lim
+        x = torch.clamp(x, min=-lim, max=lim).reshape(x.shape[0], -1)
+        if self.mode == "dir_box_sqrt":
+            m = torch.clamp(((2 * lim ** 2 - x ** 2).sqrt() - lim) / lim, min=0.0)
+        else:
+            m = (1 - torch.exp(-(lim - x))) * (1 - torch.exp(-(x + lim)))
+        return m.prod(dim=1).reshape(-1, 1)
+
+
 class ExponentialMask(nn.Module):
     def __init__(self, output_dim, init_scale=1000, boundary_mask=None):
         super().__init__()
-        if boundary_mask is not None and not _is_unit_mask(boundary_mask):
-            raise NotImplementedError("Dirichlet box masks are off in both PDE scripts and not on the HIP path")
+        if boundary_mask is not None and not isinstance(boundary_mask, DirichletBoundaryMaskBox) \
+                and not _is_unit_mask(boundary_mask):
+            raise NotImplementedError("HIP path: ExponentialMask(boundary_mask=) takes a DirichletBoundaryMaskBox, the "
+                                      "constant 1 or None (the general DirichletBoundaryMask is not built)")
         self.output_dim = output_dim
         self.scales = nn.Parameter(init_scale * torch.ones(output_dim))
-        self.boundary_mask = None
+        # the box mask has no state: state_dict keys stay `scales` alone
+        self.boundary_mask = boundary_mask if isinstance(boundary_mask, DirichletBoundaryMaskBox) else None
 
     def forward(self, x):
         r = torch.norm(x, p=2, dim=-1).view(-1, 1)
-        return torch.exp(-r / self.scales.view(1, -1))
+        mask = torch.exp(-r / self.scales.view(1, -1))
+        return mask * self.boundary_mask(x) if self.boundary_mask is not None else mask
 
 
 def _is_unit_mask(fn) -> bool:
@@ -122,12 +156,13 @@ class WaveFunctions(nn.Module):
         if not isinstance(base, ParallelMLP):
             raise NotImplementedError("HIP path: base must be this package's ParallelMLP (--parallel 1)")
         self.base = base
-        if isinstance(boundary_mask, ExponentialMask):
+        if isinstance(boundary_mask, (ExponentialMask, DirichletBoundaryMaskBox)):
             self.boundary_mask = boundary_mask
         elif _is_unit_mask(boundary_mask):
             self.boundary_mask = boundary_mask  # plain callable: not a submodule, like the reference
         else:
-            raise NotImplementedError("HIP path: boundary_mask must be ExponentialMask or the constant 1")
+            raise NotImplementedError("HIP path: boundary_mask must be ExponentialMask, DirichletBoundaryMaskBox or the "
+                                      "constant 1")
         self.hard_mul_const = hard_mul_const
 
     @property
@@ -135,8 +170,21 @@ class WaveFunctions(nn.Module):
         return isinstance(self.boundary_mask, ExponentialMask)
 
     @property
+    def box(self) -> Optional[DirichletBoundaryMaskBox]:
+        """the Dirichlet box mask: the boundary mask itself, or the one inside the exponential mask; else None"""
+        bm = self.boundary_mask
+        if isinstance(bm, DirichletBoundaryMaskBox):
+            return bm
+        if isinstance(bm, ExponentialMask):
+            return bm.boundary_mask
+        return None
+
+    @property
     def shape(self) -> H.ModelShape:
-        return self.base.model_shape(self.has_exp_mask)
+        box = self.box
+        if box is None:
+            return self.base.model_shape(self.has_exp_mask)
+        return self.base.model_shape(self.has_exp_mask, box.kind, float(box.lim))
 
     def trainable_tensors(self) -> List[torch.Tensor]:
         t = list(self.base.ws) + list(self.base.bs)
@@ -189,8 +237,6 @@ def get_wavefunctions(args):
         raise NotImplementedError("HIP path: --use_fourier_feature is required (both PDE scripts set it)")
     if not args.parallel:
         raise NotImplementedError("HIP path: --parallel 1 (ParallelMLP) is required")
-    if getattr(args, "apply_boundary", 0):
-        raise NotImplementedError("HIP path: --apply_boundary 0 (both PDE scripts)")
     fm = GaussianFourierFeatureTransform(input_dim=args.ndim * args.n_particles,
                                          mapping_size=args.fourier_mapping_size, scale=args.fourier_scale,
                                          deterministic=args.fourier_deterministic,
@@ -198,7 +244,12 @@ def get_wavefunctions(args):
     base = ParallelMLP(input_dim=args.ndim * args.n_particles, mlp_hidden_dims=parse_str(args.mlp_hidden_dims),
                        output_dim=1, num_copies=args.neigs, bias=True, nonlinearity=args.nonlinearity,
                        weight_normalization=bool(getattr(args, "weight_normalization", False)), feature_map=fm)
-    mask = lambda x: 1.0  # noqa: E731
+    if getattr(args, "apply_boundary", 0):
+        # (the reference's argparse default 'sqrt' fails this assert there too: __init__.py:40)
+        assert args.boundary_mode in ["dir_box_sqrt", "dir_box_exp"], args.boundary_mode
+        mask = DirichletBoundaryMaskBox(lim=args.lim, mode=args.boundary_mode)
+    else:
+        mask = lambda x: 1.0  # noqa: E731
     if args.apply_exp_mask:
         mask = ExponentialMask(output_dim=args.neigs, init_scale=args.exp_mask_init_scale, boundary_mask=mask)
     return WaveFunctions(base, boundary_mask=mask, hard_mul_const=args.hard_mul_const)

@@ -167,12 +167,13 @@ class BatchL2NormalizedFunctions(nn.Module):
         """Tphi, phi = operator(self, x, importance): fused for OperatorWrapper with Gaussian or no importance in
         training mode; evaluation mode divides the operator's (Tf, f) by the biased running norm (the scale is per head,
         the operator linear); any other density or callable: the reference's op sequence through forward()."""
-        from .operators import OperatorWrapper, fused_problem_of
+        from .operators import OperatorWrapper, UniformImportance, fused_problem_of
         if not isinstance(operator, OperatorWrapper):
             if not callable(operator):
                 raise NsvdError("compute_loss_operator: operator must be callable as operator(model, x, importance)")
             return operator(self, x, importance=importance) if importance is not None else operator(self, x)
-        if not operator.fused(importance):
+        # (the uniform density is in the operator kernels' epilogue, not in nsvd_nef_operator_forward's)
+        if not operator.fused(importance) or (self.training and isinstance(importance, UniformImportance)):
             Tphi, phi = operator.apply_stencil(self, x, importance)
             return Tphi.contiguous(), phi.contiguous()
         model = self.base_model

@@ -2,15 +2,17 @@
 OperatorWrapper, get_problem, the Gaussian sampler / importance and the analytic spectra.
 
     hydrogen_potential / harmonic_oscillator_potential  examples/operator/pde/schrodinger/potentials.py:5-8,24-27
+    infinite_well_potential                             examples/operator/pde/schrodinger/potentials.py:20-21
     NegativeHamiltonian                                 examples/operator/pde/schrodinger/__init__.py:4-22
     OperatorWrapper                                     examples/__init__.py:1-9
     get_problem                                         examples/operator/pde/problems.py:23-130 (sch: hydrogen, oscillator)
     get_dataloader                                      examples/operator/pde/main_pde.py:89-130 (gaussian sampler)
     Hydrogen2D / HarmonicOscillator .get_eigvals        examples/operator/pde/schrodinger/ground_truths.py:78-90,120-132
+    InfiniteWell2D.get_eigvals                          examples/operator/pde/schrodinger/ground_truths.py:40-58
 
-These objects are DESCRIPTORS on the scripts' configuration (Gaussian sampler / importance, or none): calling
-``operator(method, x, importance)`` forwards to the fused HIP kernel (nsvd_operator_forward). With the two other
-samplers of main_pde.py:101-118 (`--sampling_mode laplacian / uniform`: their importance densities are not in the fused
+These objects are DESCRIPTORS on the scripts' configuration (Gaussian or uniform sampler / importance, or none): calling
+``operator(method, x, importance)`` forwards to the fused HIP kernel (nsvd_operator_forward). With the Laplace
+sampler of main_pde.py:101-112 (`--sampling_mode laplacian`: its importance density is not in the fused
 kernel's epilogue) the wrapper applies the reference's finite-difference stencil itself (diff_ops.py:9-52,
 schrodinger/__init__.py:16-22, examples/__init__.py:7-9) around 1 + 2D evaluations of the HIP model
 (nsvd_model_forward / _backward): "python operator + fused loss kernel"  - still all on the GPU.
@@ -41,6 +43,11 @@ def harmonic_oscillator_potential(x, k=1.0):
     return (k * x.norm(dim=1, p=2) ** 2).reshape(-1, 1)
 
 
+def infinite_well_potential(x):
+    """V = 0 inside the well (potentials.py:20-21); the walls are the model's Dirichlet box mask."""
+    return torch.zeros((x.shape[0],), device=x.device)
+
+
 def _potential_kind(ftn):
     base, kw = ftn, {}
     if isinstance(ftn, partial):
@@ -49,7 +56,10 @@ def _potential_kind(ftn):
         return H.POT_HYDROGEN, float(kw.get("charge", 1.0))
     if base is harmonic_oscillator_potential:
         return H.POT_HARMONIC, float(kw.get("k", 1.0))
-    raise NsvdError("HIP path supports hydrogen_potential and harmonic_oscillator_potential only")
+    if base is infinite_well_potential:
+        return H.POT_ZERO, 0.0
+    raise NsvdError("HIP path supports hydrogen_potential, harmonic_oscillator_potential and infinite_well_potential "
+                    "only")
 
 
 class NegativeHamiltonian:
@@ -77,7 +87,7 @@ class OperatorWrapper:
 
     def fused(self, importance) -> bool:
         """does the fused kernel (nsvd_operator_forward) implement this importance density?"""
-        return importance is None or isinstance(importance, GaussianImportance)
+        return importance is None or isinstance(importance, (GaussianImportance, UniformImportance))
 
     def apply_stencil(self, model, x, importance):
         """The reference's own op sequence for densities the fused kernel does not carry (Laplace, uniform, any
@@ -147,6 +157,11 @@ class UniformImportance:
     def __init__(self, scale: float, ndim: int):
         self.scale, self.ndim = float(scale), int(ndim)
 
+    @property
+    def sigma(self) -> float:
+        """the sampling scale, under the name nsvd_problem carries it (NSVD_IMP_UNIFORM)"""
+        return self.scale
+
     def __call__(self, x):
         return torch.full((x.shape[0], 1), 1.0 / (2 * self.scale) ** self.ndim, device=x.device).float()
 
@@ -166,13 +181,19 @@ def fused_problem_of(operator, importance, model) -> H.Problem:
     if not isinstance(operator, OperatorWrapper):
         raise NsvdError("fused operator kernel: operator must be neural_svd_amd.operators.OperatorWrapper (other "
                         "callables go through NestedLoRA.apply_operator's call-through, not this translation)")
-    if importance is not None and not isinstance(importance, GaussianImportance):
-        raise NsvdError("fused operator kernel: importance must be None or GaussianImportance (other densities go "
-                        "through OperatorWrapper.apply_stencil)")
+    if importance is not None and not isinstance(importance, (GaussianImportance, UniformImportance)):
+        raise NsvdError("fused operator kernel: importance must be None, GaussianImportance or UniformImportance (other "
+                        "densities go through OperatorWrapper.apply_stencil)")
     ham = operator.operator
+    kind = H.IMP_NONE if importance is None else \
+        (H.IMP_UNIFORM if isinstance(importance, UniformImportance) else H.IMP_GAUSSIAN)
+    if kind == H.IMP_UNIFORM and importance.ndim != model.shape.D:
+        # the kernel's exponent is the model's input dimension; the reference's is args.ndim (equal: n_particles is 1)
+        raise NsvdError(f"fused operator kernel: UniformImportance(ndim={importance.ndim}) on a model of input "
+                        f"dimension {model.shape.D}")
     return H.make_problem(ham.potential_kind, ham.potential_param, ham.laplacian_eps, operator.scale, operator.shift,
                           importance.sigma if importance is not None else 1.0, ham.scale_kinetic,
-                          float(model.hard_mul_const), importance is not None)
+                          float(model.hard_mul_const), importance_kind=kind)
 
 
 # ----------------------------------------------------------------------------------- ground truths
@@ -208,6 +229,18 @@ class HarmonicOscillator:
         return math.sqrt(self.k) * np.array(vals, dtype=np.float64)
 
 
+class InfiniteWell2D:
+    def __init__(self, L=1.0):
+        self.L = L
+
+    def get_eigvals(self, neigs):
+        """(n_x^2 + n_y^2) pi^2 / L^2 over n_x, n_y >= 1, ascending, first ``neigs`` values (ground_truths.py:40-58)."""
+        # n_x, n_y <= neigs covers them: the neigs smallest values all have n_x, n_y <= neigs (each (n, 1) is one)
+        n = np.arange(1, int(neigs) + 1, dtype=np.float64)
+        vals = np.sort((n[:, None] ** 2 + n[None, :] ** 2).reshape(-1))[:int(neigs)]
+        return vals * np.pi ** 2 / float(self.L) ** 2
+
+
 def get_problem(args, device=None):
     if args.problem != "sch":
         raise NotImplementedError("only the Schroedinger problems are on the HIP path")
@@ -220,6 +253,10 @@ def get_problem(args, device=None):
     elif args.potential_type == "harmonic_oscillator":
         pot = partial(harmonic_oscillator_potential, k=1.0)
         gt = -HarmonicOscillator(k=1.0, ndim=args.ndim).get_eigvals(args.neigs)
+    elif args.potential_type == "infinite_well":
+        assert args.ndim == 2  # as the reference (problems.py:30)
+        pot = infinite_well_potential
+        gt = -InfiniteWell2D(L=2 * args.lim).get_eigvals(args.neigs)
     else:
         raise NotImplementedError(f"potential_type {args.potential_type}: not in scope of the HIP path")
     ham = NegativeHamiltonian(local_potential_ftn=pot, scale_kinetic=1.0, laplacian_eps=args.laplacian_eps,

@@ -12,6 +12,7 @@ class is their HIP compute backend, so a single-GPU step is parallel.dp_step wit
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from typing import Dict, List, Optional
 
@@ -183,7 +184,7 @@ class FusedTrainer:
             # any L >= world: L // world heads each, the first L % world ranks one more (parallel.head_range)
             from .parallel import head_range
             self.l_off, Ll = head_range(shape.L, rank, world)
-            shape = H.ModelShape(L=Ll, D=shape.D, m=shape.m, hidden=shape.hidden, has_exp_mask=shape.has_exp_mask)
+            shape = dataclasses.replace(shape, L=Ll)  # (every other field - masks included - carries over)
             batch_size = int(batch_size) * world
         self.shape, self.problem, self.B = shape, problem, int(batch_size)
         self.lr, self.alpha, self.eps = lr, rmsprop_decay, rmsprop_eps
@@ -345,8 +346,12 @@ class FusedTrainer:
 
     # -- stages -------------------------------------------------------------------------------
     def sample(self) -> torch.Tensor:
-        """x = sigma * randn(B, D) on the device (reference: host randn + H2D copy, main_pde.py:92-93)."""
-        self.x.normal_(0.0, self.sigma, generator=self.gen)  # one kernel (randn + scale)
+        """x = sigma * randn(B, D) on the device (reference: host randn + H2D copy, main_pde.py:92-93); with the
+        uniform density, x = sigma * (2 rand - 1) (main_pde.py:113-115)."""
+        if self.problem.use_importance == H.IMP_UNIFORM:
+            self.x.uniform_(-self.sigma, self.sigma, generator=self.gen)
+        else:
+            self.x.normal_(0.0, self.sigma, generator=self.gen)  # one kernel (randn + scale)
         return self.x
 
     def _masks(self):
@@ -706,6 +711,12 @@ def _spectrum_of(shape, params, problem, device, path, lim, val_eps, chunk):
             # (a ragged last chunk: hip_ops.operator_forward pads it for the MFMA kernels and drops the padding)
             wsb = ws if xb.shape[0] == chunk else H.new_workspace(shape, xb.shape[0], device)
             f, Tf = H.operator_forward(shape, params, problem, xb, wsb, False, path)
+            if problem.use_importance == H.IMP_UNIFORM:
+                # the accumulation kernel evaluates the Gaussian density only: the constant sqrt p_train = (2 sigma)^(-D/2)
+                # of the uniform one weights the rows here (spectrum.compute_spectrum_evd does the same)
+                sw = (2.0 * problem.sigma) ** (-0.5 * D)
+                H.spectrum_accumulate(f * sw, Tf * sw, xb, 1.0, False, lim, cov, quad)
+                continue
             H.spectrum_accumulate(f, Tf, xb, problem.sigma, bool(problem.use_importance), lim, cov, quad)
     n = grid.shape[0]
     cov, quad = cov.cpu() / n, quad.cpu() / n
