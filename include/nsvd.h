@@ -679,6 +679,34 @@ int nsvd_nef_loss(const float* phi, const float* Tphi, int B, const float* phi1,
 /* f[b, l] /= norm[l], Tf[b, l] /= norm[l] in place: BatchL2NormalizedFunctions in evaluation mode (utils.py:54-56). */
 int nsvd_nef_scale_heads(float* f, float* Tf, const float* norm, int B, int L, void* stream);
 
+/* ---- Retrieval metrics of the CDK towers: examples/cdk/sketchy/retrieve.py ----------------------------------------
+ * For each of the Nq queries the WHOLE gallery is ranked by descending key, ties by ASCENDING gallery index (a stable
+ * sort; faiss leaves ties open, here the rule is part of the contract). Key s_ij: NSVD_RETR_INNER_PRODUCT x_i . y_j
+ * (IndexFlatIP), NSVD_RETR_EUCLIDEAN x_i . y_j - |y_j|^2 / 2 (the order of ascending |x_i - y_j|^2), float32 on the
+ * fp32-input MFMA. zq (Nq, d), zg (Ng, d): float32 rows with leading dimensions ldq, ldg >= d, 4-byte aligned - a
+ * truncation of an embedding is the window (z + col0, ld, d), no copy. 1 <= d <= nsvd_retrieval_max_d(),
+ * 1 <= K <= min(Ng, nsvd_retrieval_max_k()), Ng <= nsvd_retrieval_max_gallery() (else NSVD_EUNSUPPORTED); Nq = 0 launches nothing.
+ * With rel_j = (g_cls[j] == q_cls[i]), r_1 < ... < r_R the 1-based ranks of the relevant rows, p_m = m / r_m:
+ *   topk_idx / topk_rel (Nq, K): gallery index at rank k + 1 and its relevance (either may be NULL);
+ *   prec_at_k (Nq): #{m : r_m <= K} / K; hits_at_k (Nq) or NULL: that count itself;
+ *   avg_prec (3, Nq) FLOAT64 or NULL - compute_average_precisions over the whole ranking: ver 1 = sum_m max_{m' >= m} p_m' / R,
+ *     ver 2 = sum_m p_m / min(Ng, n_relevant_items[i]), ver 3 = sum_m p_m / R (float64 sums; R = 0: NaN, 0 / n, NaN);
+ *   n_relevant_found (Nq) or NULL: R.
+ * n_relevant_items (Nq) is an INPUT (the reference counts the query's class among the queries); needed with avg_prec.
+ * ws: nsvd_retrieval_workspace_bytes(Nq, Ng, d, K) bytes (0: invalid description), 256-byte aligned; it holds one
+ * chunk of query rows (about 64 MiB, at least 64 rows), never Nq x Ng. No atomics: bit-identical from run to run;
+ * no allocation, synchronisation or read-back: capturable in a graph. */
+#define NSVD_RETR_INNER_PRODUCT 0
+#define NSVD_RETR_EUCLIDEAN 1
+int nsvd_retrieval_max_gallery(void);
+int nsvd_retrieval_max_k(void); /* 2048 */
+int nsvd_retrieval_max_d(void); /* 1024 */
+size_t nsvd_retrieval_workspace_bytes(int Nq, int Ng, int d, int K);
+int nsvd_retrieval_eval(const float* zq, long ldq, const float* zg, long ldg, int Nq, int Ng, int d,
+                        const int32_t* q_cls, const int32_t* g_cls, const int32_t* n_relevant_items, int metric, int K,
+                        int32_t* topk_idx, uint8_t* topk_rel, float* prec_at_k, int32_t* hits_at_k, double* avg_prec,
+                        int32_t* n_relevant_found, void* ws, size_t ws_bytes, void* stream);
+
 /* Measurement aid (bench.py): record the two hipEvent_t handles immediately before / after the
  * DOMINANT kernel of the next nsvd_operator_forward call made by this host thread (the fused MFMA
  * forward kernel, or the layer-0 GEMM on the generic path), on that call's stream - or, whichever

@@ -5,4 +5,13 @@ this package is the host-side mirror of the reference's Python interface for tha
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib"]
+__all__ = ["_lib", "SketchyRetrieval", "evaluate_truncations"]
+
+
+def __getattr__(name):
+    # the retrieval evaluation (retrieval.py) is exported here; resolved on first use, so that importing the package
+    # stays as light as the ctypes binding
+    if name in ("SketchyRetrieval", "evaluate_truncations"):
+        from . import retrieval
+        return getattr(retrieval, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -162,6 +162,12 @@ SIGNATURES = {
     "nsvd_nef_loss_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "nsvd_nef_loss": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "nsvd_nef_scale_heads": (_I, [_P, _P, _P, _I, _I, _P]),
+    "nsvd_retrieval_max_gallery": (_I, []),
+    "nsvd_retrieval_max_k": (_I, []),
+    "nsvd_retrieval_max_d": (_I, []),
+    "nsvd_retrieval_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "nsvd_retrieval_eval": (_I, [_P, C.c_long, _P, C.c_long, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P,
+                                 _Z, _P]),
     "nsvd_tower_backward": (_I, [_P, C.POINTER(TowerParams), _P, _I, _I, _I, _I, _F, _I, C.POINTER(TowerParams), _P,
                                  _Z, _P]),
 }

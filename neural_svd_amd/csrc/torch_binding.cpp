@@ -282,6 +282,56 @@ void spectrum_accumulate(const at::Tensor& f, const at::Tensor& Tf, const at::Te
              "nsvd_spectrum_accumulate");
 }
 
+// retrieval metrics (nsvd_retrieval_eval): zq / zg may be column windows (unit column stride); outputs as passed
+void retrieval_eval(const at::Tensor& zq, const at::Tensor& zg, const at::Tensor& q_cls, const at::Tensor& g_cls,
+                    c10::optional<at::Tensor> n_relevant_items, int64_t metric, int64_t K,
+                    c10::optional<at::Tensor> topk_idx, c10::optional<at::Tensor> topk_rel, at::Tensor prec_at_k,
+                    c10::optional<at::Tensor> hits_at_k,
+                    c10::optional<at::Tensor> avg_prec, c10::optional<at::Tensor> n_relevant_found, at::Tensor ws) {
+    Dev dv;
+    auto window = [&](const at::Tensor& t, const char* name) {
+        dv.see(t, name);
+        TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 2 && t.size(1) >= 1 && t.stride(1) == 1, name,
+                    " must be a float32 (rows, d) matrix with unit column stride");
+        return t.data_ptr<float>();
+    };
+    auto i32 = [&](const c10::optional<at::Tensor>& t, const char* name) -> int32_t* {
+        if (!t.has_value()) return nullptr;
+        dv.see(*t, name);
+        TORCH_CHECK(t->scalar_type() == at::kInt && t->is_contiguous(), name, " must be contiguous int32");
+        return t->data_ptr<int32_t>();
+    };
+    const float *qp = window(zq, "zq"), *gp = window(zg, "zg");
+    const int Nq = (int)zq.size(0), Ng = (int)zg.size(0), d = (int)zq.size(1);
+    TORCH_CHECK(zg.size(1) == d, "zq and zg must share the embedding width");
+    TORCH_CHECK(q_cls.numel() == Nq && g_cls.numel() == Ng, "one class id per row");
+    const long ldq = Nq > 1 ? (long)zq.stride(0) : d, ldg = Ng > 1 ? (long)zg.stride(0) : d;
+    int32_t *qc = i32(q_cls, "q_cls"), *gc = i32(g_cls, "g_cls"), *nri = i32(n_relevant_items, "n_relevant_items");
+    int32_t *ti = i32(topk_idx, "topk_idx"), *nf = i32(n_relevant_found, "n_relevant_found");
+    int32_t* hk = i32(hits_at_k, "hits_at_k");
+    uint8_t* tr = nullptr;
+    if (topk_rel.has_value()) {
+        dv.see(*topk_rel, "topk_rel");
+        TORCH_CHECK(topk_rel->element_size() == 1 && topk_rel->is_contiguous(), "topk_rel must be contiguous bool / uint8");
+        tr = (uint8_t*)topk_rel->data_ptr();
+    }
+    TORCH_CHECK((!ti || topk_idx->numel() == (int64_t)Nq * K) && (!tr || topk_rel->numel() == (int64_t)Nq * K) &&
+                    prec_at_k.numel() == Nq && (!avg_prec.has_value() || avg_prec->numel() == 3 * (int64_t)Nq) &&
+                    (!nf || n_relevant_found->numel() == Nq) && (!hk || hits_at_k->numel() == Nq),
+                "retrieval_eval: output sizes");
+    float* pp = f32(dv, prec_at_k, "prec_at_k");
+    double* ap = nullptr;
+    if (avg_prec.has_value()) {
+        dv.see(*avg_prec, "avg_prec");
+        TORCH_CHECK(avg_prec->scalar_type() == at::kDouble && avg_prec->is_contiguous(), "avg_prec must be contiguous float64");
+        ap = avg_prec->data_ptr<double>();
+    }
+    void* wp = bytes(dv, ws, "ws");
+    check_rc(nsvd_retrieval_eval(qp, ldq, gp, ldg, Nq, Ng, d, qc, gc, nri, (int)metric, (int)K, ti, tr, pp, hk, ap, nf, wp,
+                                 (size_t)ws.numel() * ws.element_size(), dv.stream()),
+             "nsvd_retrieval_eval");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -300,7 +350,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                         "nsvd_operator_sample_features", "nsvd_operator_sample_features_dev",
                                         "nsvd_evd_moments", "nsvd_evd_loss_grad", "nsvd_operator_backward_evd_step",
                                         "nsvd_operator_backward_evd_step_next", "nsvd_rmsprop_ema_step",
-                                        "nsvd_spectrum_accumulate"};
+                                        "nsvd_spectrum_accumulate", "nsvd_retrieval_eval",
+                                        "nsvd_retrieval_workspace_bytes", "nsvd_retrieval_max_gallery",
+                                        "nsvd_retrieval_max_k", "nsvd_retrieval_max_d"};
     });
     py::class_<Shape>(m, "Shape")
         .def(py::init<int, int, int, std::vector<int>, bool, int, double>(), py::arg("L"), py::arg("D"), py::arg("m"),
@@ -322,4 +374,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("operator_backward_evd_step", &operator_backward_evd_step);
     m.def("rmsprop_ema_step", &rmsprop_ema_step);
     m.def("spectrum_accumulate", &spectrum_accumulate);
+    m.def("retrieval_eval", &retrieval_eval);
+    m.def("retrieval_workspace_bytes",
+          [](int Nq, int Ng, int d, int K) { return (int64_t)nsvd_retrieval_workspace_bytes(Nq, Ng, d, K); });
+    m.def("retrieval_max_gallery", []() { return nsvd_retrieval_max_gallery(); });
+    m.def("retrieval_limits", []() { return std::vector<int>{nsvd_retrieval_max_k(), nsvd_retrieval_max_d()}; });
 }

@@ -1121,3 +1121,97 @@ def nef_scale_heads(f: torch.Tensor, Tf: torch.Tensor, norm: torch.Tensor) -> No
     B, L = f.shape
     rc = _lib.load().nsvd_nef_scale_heads(_ptr(f, "f"), _ptr(Tf, "Tf"), _ptr(norm.reshape(-1), "norm"), B, L, _stream())
     check(rc, "nsvd_nef_scale_heads")
+
+
+# ------------------------------------------------------------------------ retrieval metrics (include/nsvd.h)
+RETR_INNER_PRODUCT, RETR_EUCLIDEAN = 0, 1
+
+
+def retrieval_max_gallery() -> int:
+    """the largest gallery nsvd_retrieval_eval ranks (host-side query, no GPU needed)"""
+    return int(_lib.load().nsvd_retrieval_max_gallery())
+
+
+def retrieval_max_k() -> int:
+    """the largest K nsvd_retrieval_eval returns top-K lists for (host-side query)"""
+    return int(_lib.load().nsvd_retrieval_max_k())
+
+
+def retrieval_max_d() -> int:
+    """the widest embedding nsvd_retrieval_eval takes (host-side query)"""
+    return int(_lib.load().nsvd_retrieval_max_d())
+
+
+def retrieval_workspace_bytes(Nq: int, Ng: int, d: int, K: int) -> int:
+    """bytes of workspace for one nsvd_retrieval_eval call (host-side query); raises for an invalid description"""
+    n = _lib.load().nsvd_retrieval_workspace_bytes(int(Nq), int(Ng), int(d), int(K))
+    if n == 0:
+        raise NsvdError(f"retrieval: invalid or unsupported description Nq={Nq}, Ng={Ng}, d={d}, K={K} (d <= "
+                        f"{retrieval_max_d()}, 1 <= K <= min(Ng, {retrieval_max_k()}), Ng <= {retrieval_max_gallery()})")
+    return int(n)
+
+
+def _retr_matrix(z: torch.Tensor, name: str):
+    if not isinstance(z, torch.Tensor) or not z.is_cuda:
+        raise NsvdError(f"{name} must live on the GPU (got {getattr(z, 'device', type(z))}); neural_svd_amd has no CPU path")
+    if z.dtype != torch.float32:
+        raise NsvdError(f"{name} must be float32 (got {z.dtype})")
+    if z.dim() != 2 or z.shape[1] < 1:
+        raise NsvdError(f"{name} must be a (rows, d) matrix with d >= 1")
+    if z.stride(1) != 1 or (z.shape[0] > 1 and z.stride(0) < z.shape[1]):
+        raise NsvdError(f"{name}: unit column stride and a row stride >= d (a column window of a contiguous matrix)")
+    return z.data_ptr(), (int(z.stride(0)) if z.shape[0] > 1 else int(z.shape[1]))
+
+
+@_on_tensor_device
+def retrieval_eval(zq: torch.Tensor, zg: torch.Tensor, q_cls: torch.Tensor, g_cls: torch.Tensor,
+                   n_relevant_items: Optional[torch.Tensor] = None, metric: int = RETR_INNER_PRODUCT, K: int = 100,
+                   want_topk: bool = True, want_ap: bool = True, ws: Optional[torch.Tensor] = None):
+    """nsvd_retrieval_eval: every query's whole-gallery ranking (descending key, ties by ascending gallery index).
+    zq (Nq, d), zg (Ng, d): float32 with unit column stride (column windows of a wider matrix are taken as they are);
+    q_cls (Nq), g_cls (Ng), n_relevant_items (Nq): int32. Returns a dict: prec_at_k (Nq), hits_at_k (Nq) int32 (the count behind it), n_relevant_found (Nq) and,
+    when asked for, topk_idx (Nq, K) int32, topk_rel (Nq, K) bool, avg_prec (3, Nq) float64 = ap_ver 1, 2, 3."""
+    pq, ldq = _retr_matrix(zq, "zq")
+    pg, ldg = _retr_matrix(zg, "zg")
+    Nq, d = zq.shape
+    Ng = zg.shape[0]
+    if zg.shape[1] != d:
+        raise NsvdError(f"zq and zg must share the embedding width (got {d} and {zg.shape[1]})")
+    if metric not in (RETR_INNER_PRODUCT, RETR_EUCLIDEAN):
+        raise NsvdError(f"retrieval_eval: unknown metric {metric}")
+    if q_cls.numel() != Nq or g_cls.numel() != Ng:
+        raise NsvdError("retrieval_eval: q_cls / g_cls must hold one class id per row")
+    if want_ap and (n_relevant_items is None or n_relevant_items.numel() != Nq):
+        raise NsvdError("retrieval_eval: the average precisions need n_relevant_items (Nq)")
+    lib = _lib.load()
+    K = int(K)
+    nbytes = lib.nsvd_retrieval_workspace_bytes(Nq, Ng, d, K)
+    if nbytes == 0:
+        if 1 <= K <= min(Ng, retrieval_max_k()) and 1 <= d <= retrieval_max_d() and Ng > lib.nsvd_retrieval_max_gallery():
+            check(_lib.EUNSUPPORTED, f"nsvd_retrieval_eval (Ng = {Ng} > {lib.nsvd_retrieval_max_gallery()})")
+        check(_lib.EINVAL, f"nsvd_retrieval_eval (Nq={Nq}, Ng={Ng}, d={d}, K={K})")
+    dev = zq.device
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif ws.numel() * ws.element_size() < nbytes:
+        raise NsvdError(f"retrieval_eval: workspace of {ws.numel() * ws.element_size()} bytes, {nbytes} needed")
+    out = {"prec_at_k": torch.empty(Nq, dtype=torch.float32, device=dev),
+           "hits_at_k": torch.empty(Nq, dtype=torch.int32, device=dev),
+           "n_relevant_found": torch.empty(Nq, dtype=torch.int32, device=dev)}
+    if want_topk:
+        out["topk_idx"] = torch.empty((Nq, K), dtype=torch.int32, device=dev)
+        out["topk_rel"] = torch.empty((Nq, K), dtype=torch.uint8, device=dev)
+    if want_ap:
+        out["avg_prec"] = torch.empty((3, Nq), dtype=torch.float64, device=dev)
+    rc = lib.nsvd_retrieval_eval(pq, ldq, pg, ldg, Nq, Ng, d, _ptr(q_cls, "q_cls", torch.int32),
+                                 _ptr(g_cls, "g_cls", torch.int32),
+                                 _ptr(n_relevant_items if want_ap else None, "n_relevant_items", torch.int32),
+                                 int(metric), K, _ptr(out.get("topk_idx"), "topk_idx", torch.int32),
+                                 _ptr(out.get("topk_rel"), "topk_rel", torch.uint8), _ptr(out["prec_at_k"]),
+                                 _ptr(out["hits_at_k"], "hits_at_k", torch.int32),
+                                 _ptr(out.get("avg_prec"), "avg_prec", torch.float64), _ptr(out["n_relevant_found"], "n", torch.int32),
+                                 ws.data_ptr(), ws.numel() * ws.element_size(), _stream())
+    check(rc, "nsvd_retrieval_eval")
+    if want_topk:
+        out["topk_rel"] = out["topk_rel"].view(torch.bool)
+    return out

@@ -80,3 +80,35 @@ def post_alignment(eigfuncs, cov, quad):
     ev = np.sqrt(ev[::-1])
     V = V[:, ::-1]
     return eigfuncs @ (V.T @ whitening).T, ev, np.eye(quad.shape[0])
+
+
+@torch.no_grad()
+def compute_spectrum_svd(model, dataloader, gpu=None, device=None, sort=False, set_first_mode_const=False):
+    """methods/spectrum.py:106-158 for the CDK path: over batches (x, y, cls), f, g = model(x, y); the second moments
+    Mx = f^T f / n, My = g^T g / n; singular values sqrt(diag Mx * diag My) and the two orthogonality matrices
+    M / sqrt(diag diag^T). The Sketchy loop calls it beside the retrieval (main_sketchy.py:304-309) with
+    set_first_mode_const=True (a constant column of ones in front). float64 accumulators, as compute_spectrum_evd's,
+    rounded to the reference's float32 once at the end. Returns (spectrum, orthogonality_x, orthogonality_y)."""
+    if (gpu is None) == (device is None):
+        raise ValueError("exactly one of gpu / device")
+    dev = torch.device(f"cuda:{gpu}") if gpu is not None else torch.device(device)
+    mx = my = None
+    n = 0
+    for (x, y, _cls) in dataloader:
+        f, g = model(x.to(dev), y.to(dev))
+        f, g = f.double(), g.double()
+        if set_first_mode_const:
+            f = torch.nn.functional.pad(f, (1, 0), value=1.0)
+            g = torch.nn.functional.pad(g, (1, 0), value=1.0)
+        mx = f.T @ f if mx is None else mx + f.T @ f
+        my = g.T @ g if my is None else my + g.T @ g
+        n += x.shape[0]
+    mx, my = mx / n, my / n
+    dx, dy = torch.diag(mx).unsqueeze(1), torch.diag(my).unsqueeze(1)
+    spectrum = (dx * dy).sqrt().reshape(-1).float().cpu().numpy()
+    orth_x = (mx / (dx @ dx.T).sqrt()).float().cpu().numpy()
+    orth_y = (my / (dy @ dy.T).sqrt()).float().cpu().numpy()
+    if sort:
+        idx = np.argsort(spectrum)[::-1]
+        spectrum, orth_x, orth_y = spectrum[idx], orth_x[idx, :][:, idx], orth_y[idx, :][:, idx]
+    return spectrum, orth_x, orth_y
