@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define NSVD_ABI_VERSION 3
+#define NSVD_ABI_VERSION 4
 #define NSVD_MAX_LAYERS 8
 
 #define NSVD_EINVAL (-10001)
@@ -56,6 +56,17 @@ extern "C" {
 #define NSVD_POT_HYDROGEN 0 /* V = -Z / |x|  */
 #define NSVD_POT_HARMONIC 1 /* V = k |x|^2   */
 #define NSVD_POT_ZERO 2     /* V = 0: the infinite well (potentials.py:20-21); the walls are the model's box mask */
+#define NSVD_POT_COSINE 3   /* V = sum_d pot_coef[d] cos x_d (potentials.py:30-31)                                     */
+#define NSVD_POT_H2_ION 4   /* V = -q / |x - R e_last| - q / |x + R e_last|, q = charge_or_k, R = pot_coef[0]
+                             * (potentials.py:11-17)                                                                  */
+#define NSVD_POT_SIN_OF_COS 5 /* V = sin(sum_d pot_coef[d] cos x_d) (others.py:33-34): the drift potential of
+                               * NSVD_OP_FOKKER_PLANCK, valid with that operator kind only                             */
+
+/* nsvd_problem.operator_kind */
+#define NSVD_OP_SCHROEDINGER 0  /* Tf = -(-scale_kinetic Lap f + V f)            (schrodinger/__init__.py:16-22)      */
+#define NSVD_OP_FOKKER_PLANCK 1 /* Tf = fp_scale (Lap f + grad V . grad f + f Lap V), every derivative - those of V
+                                 * too - the central difference with step eps (others.py:6-30). Needs eps > 0, no
+                                 * Gaussian importance, no box mask and sqrt p >= 1e-5 ("unsupported" otherwise)      */
 
 /* Dirichlet box mask of the model (examples/operator/pde/boundary.py:16-36, --apply_boundary / --boundary_mode):
  * M(x) = prod_d m(clamp(x_d, -lim, lim)), 0 at and beyond the wall, multiplies the model output at every point */
@@ -123,6 +134,11 @@ typedef struct nsvd_problem {
     int32_t use_importance;          /* NSVD_IMP_*: 0 None, 1 the N(0, sigma^2 I) pdf, 2 the uniform density
                                       * (2 sigma)^-D; sqrt p / max(sqrt p, 1e-5) is kept for all of them. The device
                                       * samplers draw from the same density. */
+    /* ABI 4 (appended; all zero = the Schroedinger operator with one of the radial potentials, as before) */
+    int32_t operator_kind;           /* NSVD_OP_*                                      */
+    float fp_scale;                  /* NegativeLinearFokkerPlanck(scale=...)          */
+    float pot_coef[4];               /* cs[d] (cosine, sin-of-cos: float32 values, as torch.tensor(cs) makes them), or R
+                                      * in [0] (H2+); entries past D are ignored       */
 } nsvd_problem;
 
 int nsvd_abi_version(void);
@@ -131,8 +147,10 @@ int nsvd_abi_version(void);
 const char* nsvd_path_name(const nsvd_model_desc* desc, int B, int path);
 /* The same for a given problem: the exact-Laplacian mode (prob->eps <= 0) exists on the MFMA path only (D <= 3, as the
  * stencil mode: its 3-D form runs one direction per workgroup); "unsupported" when it has no path; "invalid" for a
- * potential, importance or box mask value this library does not know. Every path implements every box mask, potential
- * and importance; entry points that do not (NeuralEF) return NSVD_EUNSUPPORTED. */
+ * potential, importance, operator kind or box mask value this library does not know (and for NSVD_POT_SIN_OF_COS
+ * outside the Fokker-Planck kind). Every path implements every box mask, potential and importance; entry points that do
+ * not (NeuralEF) return NSVD_EUNSUPPORTED. The Fokker-Planck kind is "unsupported" with eps <= 0, Gaussian importance,
+ * a box mask, sqrt p < 1e-5 or another potential than NSVD_POT_SIN_OF_COS; the entry points return NSVD_EUNSUPPORTED. */
 const char* nsvd_path_name_for(const nsvd_model_desc* desc, const nsvd_problem* prob, int B, int path);
 
 /* Bytes of scratch nsvd_operator_forward / _backward need for batches of up to B rows. */

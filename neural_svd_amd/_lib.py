@@ -10,12 +10,13 @@ import os
 from typing import Optional
 
 NSVD_MAX_LAYERS = 8
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 EINVAL = -10001
 EUNSUPPORTED = -10002
 
-POT_HYDROGEN, POT_HARMONIC, POT_ZERO = 0, 1, 2
+POT_HYDROGEN, POT_HARMONIC, POT_ZERO, POT_COSINE, POT_H2_ION, POT_SIN_OF_COS = 0, 1, 2, 3, 4, 5
+OP_SCHROEDINGER, OP_FOKKER_PLANCK = 0, 1
 BOX_NONE, BOX_SQRT, BOX_EXP = 0, 1, 2
 IMP_NONE, IMP_GAUSSIAN, IMP_UNIFORM = 0, 1, 2
 MASK_CUSTOM, MASK_SEQUENTIAL, MASK_JOINT = 0, 1, 2
@@ -42,7 +43,9 @@ class Params(C.Structure):
 class Problem(C.Structure):
     _fields_ = [("potential", C.c_int32), ("charge_or_k", C.c_float), ("scale_kinetic", C.c_float),
                 ("eps", C.c_float), ("op_scale", C.c_float), ("op_shift", C.c_float), ("sigma", C.c_float),
-                ("hard_mul_const", C.c_float), ("use_importance", C.c_int32)]
+                ("hard_mul_const", C.c_float), ("use_importance", C.c_int32),
+                # ABI 4 (all zero: the Schroedinger operator with a radial potential)
+                ("operator_kind", C.c_int32), ("fp_scale", C.c_float), ("pot_coef", C.c_float * 4)]
 
 
 class TowerParams(C.Structure):

@@ -11,6 +11,8 @@
 
 namespace {
 
+// TRIG: the instance of the periodic problems (cosine potential, Fokker-Planck kind: fd_math.h)
+template <bool TRIG>
 __global__ void __launch_bounds__(256) fd_epilogue_kernel(const float* __restrict__ base, int ldr,
                                                           const float* __restrict__ x,
                                                           const float* __restrict__ scales, nsvd_problem prob,
@@ -33,9 +35,9 @@ __global__ void __launch_bounds__(256) fd_epilogue_kernel(const float* __restric
             bE[d] = bv[1 + 2 * d];
             bO[d] = bv[2 + 2 * d];
         }
-        o = nsvd_fd_evenodd(bv[0], bE, bO, xc, D, scales != nullptr, s_l, prob, log_norm, box);
+        o = nsvd_fd_evenodd<TRIG>(bv[0], bE, bO, xc, D, scales != nullptr, s_l, prob, log_norm, box);
     } else {
-        o = nsvd_fd_point(bv, xc, D, scales != nullptr, s_l, prob, log_norm, box);
+        o = nsvd_fd_point<TRIG>(bv, xc, D, scales != nullptr, s_l, prob, log_norm, box);
     }
     f[idx] = o.f;
     Tf[idx] = o.Tf;
@@ -108,8 +110,9 @@ int nsvd_fd_epilogue(const float* base, int ldr, const float* x, const float* sc
                      NsvdBox box) {
     if (D > NSVD_FD_MAXD) return NSVD_EUNSUPPORTED;
     const float log_norm = nsvd_importance_log_norm(D, prob);
-    hipLaunchKernelGGL(fd_epilogue_kernel, dim3(nsvd_cdiv(B * L, 256)), dim3(256), 0, s, base, ldr, x, scales, prob,
-                       log_norm, B, D, L, f, Tf, jac, dsc, evenodd, box);
+    const bool trig = prob.potential == NSVD_POT_COSINE || prob.operator_kind == NSVD_OP_FOKKER_PLANCK;
+    hipLaunchKernelGGL(trig ? fd_epilogue_kernel<true> : fd_epilogue_kernel<false>, dim3(nsvd_cdiv(B * L, 256)),
+                       dim3(256), 0, s, base, ldr, x, scales, prob, log_norm, B, D, L, f, Tf, jac, dsc, evenodd, box);
     NSVD_CHECK_LAUNCH();
     return 0;
 }

@@ -21,11 +21,68 @@ static inline float nsvd_importance_log_norm(int D, const nsvd_problem& prob) {
     return nsvd_gauss_log_norm(D, prob.sigma);
 }
 
-// V(x) at |x| = r0 (potentials.py:5-8, 20-21, 24-27)
-__device__ __forceinline__ float nsvd_potential(const nsvd_problem& prob, float r0) {
+// pot_coef[d] by a chain of selects on the uniform d: constant indices only, so the by-value nsvd_problem of the
+// kernel arguments is read where it lies (scalar registers) and never copied into a per-thread array
+__device__ __forceinline__ float nsvd_pot_coef(const nsvd_problem& prob, int d) {
+    return d == 0 ? prob.pot_coef[0] : d == 1 ? prob.pot_coef[1] : d == 2 ? prob.pot_coef[2] : prob.pot_coef[3];
+}
+// S(x) = sum_d cs[d] cos x_d: the cosine potential (potentials.py:30-31) and the argument of sin-of-cos (others.py:33-34)
+__device__ __forceinline__ float nsvd_cos_sum(const nsvd_problem& prob, const float* xc, int D) {
+    float S = 0.f;
+    for (int d = 0; d < D; ++d) S = fmaf(nsvd_pot_coef(prob, d), cosf(xc[d]), S);
+    return S;
+}
+
+// V(x) of the Schroedinger kind at the centre xc, |xc| = r0 (potentials.py:5-8, 11-17, 20-21, 24-27, 30-31)
+// TRIG (here and in the finite-difference forms below): false compiles the periodic problems - the cosine potential
+// and the Fokker-Planck kind, whose sinf / cosf carry their own argument reduction - out of an instance; a kernel that
+// has such an instance (fd_epilogue.hip) keeps the registers and occupancy of its other problems.
+template <bool TRIG = true>
+__device__ __forceinline__ float nsvd_potential(const nsvd_problem& prob, const float* xc, int D, float r0) {
     if (prob.potential == NSVD_POT_HYDROGEN) return -(prob.charge_or_k / r0);
     if (prob.potential == NSVD_POT_ZERO) return 0.f;
+    if (TRIG && prob.potential == NSVD_POT_COSINE) return nsvd_cos_sum(prob, xc, D);
+    if (prob.potential == NSVD_POT_H2_ION) {
+        // the nuclei sit at +-R on the last axis; x_last -+ R is exact next to a nucleus (Sterbenz), where
+        // |x|^2 -+ 2 R x_last + R^2 would be a difference of O(1) numbers
+        const float R = prob.pot_coef[0];
+        float rest = 0.f, xl = 0.f;
+        for (int d = 0; d < D; ++d) {
+            const bool last = d == D - 1;
+            rest = last ? rest : fmaf(xc[d], xc[d], rest);
+            xl = last ? xc[d] : xl;
+        }
+        const float dm = xl - R, dp = xl + R;
+        return -(prob.charge_or_k / sqrtf(fmaf(dm, dm, rest))) - prob.charge_or_k / sqrtf(fmaf(dp, dp, rest));
+    }
     return prob.charge_or_k * (r0 * r0);
+}
+
+// ---- Fokker-Planck kind (others.py:6-30): Tf = fp_scale (Lap f + grad V . grad f + f Lap V), V = sin S ---------------
+// The reference differences V with the stencil it uses for f. Along direction d, S(x +- eps e_d) = S + a -+ b with
+//   a = cs_d (cos x_d cos eps - cos x_d) = -2 cs_d cos x_d sin^2(eps / 2),   b = cs_d sin x_d sin eps
+// and the differences of sin follow without subtracting two O(1) numbers:
+//   V_+ - V_-       = sin(S + a - b) - sin(S + a + b) = -2 cos(S + a) sin b
+//   V_+ + V_- - 2 V = 2 sin(S + a) cos b - 2 sin S    = 4 cos(S + a / 2) sin(a / 2) cos b - 4 sin S sin^2(b / 2)
+struct NsvdPotDiff {
+    float dif, sum2;  // V_+ - V_-,  V_+ + V_- - 2 V_0
+};
+__device__ __forceinline__ NsvdPotDiff nsvd_sin_of_cos_diff(const nsvd_problem& prob, float S, float xd, int d) {
+    const float cs = nsvd_pot_coef(prob, d), eps = prob.eps;
+    const float she = sinf(0.5f * eps);
+    const float a = -2.f * cs * cosf(xd) * (she * she), b = cs * sinf(xd) * sinf(eps);
+    const float shb = sinf(0.5f * b);
+    NsvdPotDiff o;
+    o.dif = -2.f * cosf(S + a) * sinf(b);
+    o.sum2 = 4.f * cosf(S + 0.5f * a) * sinf(0.5f * a) * cosf(b) - 4.f * sinf(S) * (shb * shb);
+    return o;
+}
+// from the per-direction sums adv = sum_d (V_+ - V_-)(g_+ - g_-) / u and lv = sum_d (V_+ + V_- - 2 V), with
+// lap = Lap g / sqrt p and fs as the Schroedinger kind forms them, u the factor adv still lacks (c w0 / sqrt p):
+//   grad V . grad f = u adv / (2 eps)^2,   Lap V = lv / eps^2
+__device__ __forceinline__ float nsvd_fp_apply(const nsvd_problem& prob, float lap, float fs, float u, float adv,
+                                               float lv, float eps2) {
+    return prob.fp_scale * (lap + u * adv / (4.f * eps2) + fs * (lv / eps2));
 }
 
 // ---- Dirichlet box mask (boundary.py:16-36): M(x) = prod_d m(clamp(x_d, -lim, lim)) --------------------------------
@@ -128,8 +185,11 @@ __device__ __forceinline__ NsvdFdG nsvd_fd_g(int e, float bve, const float* xc, 
 
 // stencil combination; g[e] from nsvd_fd_g, (sp0, mask0, r0) of the centre point, bv0 = bv[0]
 // (M0: the box mask at the centre, 1 without one)
+// (xc: the centre coordinates, for the potentials that are no function of r0)
+template <bool TRIG = true>
 __device__ __forceinline__ NsvdFdOut nsvd_fd_combine(const float* g, float sp0, float mask0, float r0, float bv0, int D,
-                                                     bool has_mask, float s_l, const nsvd_problem& prob, float M0) {
+                                                     bool has_mask, float s_l, const nsvd_problem& prob, float M0,
+                                                     const float* xc) {
     float lap = -2.f * (float)D * g[0];
     for (int i = 0; i < D; ++i) lap += (g[1 + 2 * i] + g[2 + 2 * i]);
     const float eps2 = (float)((double)prob.eps * (double)prob.eps);
@@ -137,12 +197,23 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_combine(const float* g, float sp0, 
     const float spc = prob.use_importance ? fmaxf(sp0, NSVD_SQRT_P_CLAMP) : 1.f;
     lap = lap / spc;
     const float fs = g[0] / spc;
-    const float V = nsvd_potential(prob, r0);
-    const float kinetic = -prob.scale_kinetic * lap;
-    const float H = kinetic + V * fs;
     NsvdFdOut o;
     o.f = fs;
-    o.Tf = prob.op_scale * (-H) + prob.op_shift * fs;
+    if (TRIG && prob.operator_kind == NSVD_OP_FOKKER_PLANCK) {
+        const float S = nsvd_cos_sum(prob, xc, D);
+        float adv = 0.f, lv = 0.f;
+        for (int i = 0; i < D; ++i) {
+            const NsvdPotDiff v = nsvd_sin_of_cos_diff(prob, S, xc[i], i);
+            adv = fmaf(v.dif, g[1 + 2 * i] - g[2 + 2 * i], adv);
+            lv += v.sum2;
+        }
+        o.Tf = prob.op_scale * nsvd_fp_apply(prob, lap, fs, 1.f / spc, adv, lv, eps2) + prob.op_shift * fs;
+    } else {
+        const float V = nsvd_potential<TRIG>(prob, xc, D, r0);
+        const float kinetic = -prob.scale_kinetic * lap;
+        const float H = kinetic + V * fs;
+        o.Tf = prob.op_scale * (-H) + prob.op_shift * fs;
+    }
     const float w = (sp0 / spc) * prob.hard_mul_const;
     o.jac = w * mask0 * M0;
     o.dsc = has_mask ? w * bv0 * mask0 * r0 / (s_l * s_l) * M0 : 0.f;
@@ -161,6 +232,9 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_combine(const float* g, float sp0, 
 //     g_+ + g_- - 2 g_0 = c w0 M_rest [ (sigma_+ + sigma_-)(base0 + bE) + 2 m0 bE + (sigma_+ - sigma_-) bO ]
 // with sigma_+ +- sigma_- from the even / odd parts of rho (ev, od) and of delta (nsvd_box_eo: ds, dd):
 //     rho_+ delta_+ +- rho_- delta_- = (ev ds + od dd) / 2, (ev dd + od ds) / 2
+// The Fokker-Planck kind (no box mask) also needs the first difference, the odd part of the same expansion:
+//     g_+ - g_- = c w0 [ od (base0 + bE) + (2 + ev) bO ]
+template <bool TRIG = true>
 __device__ __forceinline__ NsvdFdOut nsvd_fd_evenodd(float base0, const float* bE, const float* bO, const float* xc,
                                                      int D, bool has_mask, float s_l, const nsvd_problem& prob,
                                                      float log_norm, const NsvdBox& box) {
@@ -175,6 +249,9 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_evenodd(float base0, const float* b
     const float qs = prob.use_importance == NSVD_IMP_GAUSSIAN ? -1.f / (4.f * prob.sigma * prob.sigma) : 0.f;
     const float e2 = eps * eps;
     float acc = 0.f;
+    const bool fp = TRIG && prob.operator_kind == NSVD_OP_FOKKER_PLANCK;
+    const float S = fp ? nsvd_cos_sum(prob, xc, D) : 0.f;
+    float adv = 0.f, lv = 0.f;
     // (no per-direction arrays for the box mask: indexed by a run-time d they would live in scratch memory, in every
     // instance of the fused forward, the headline's included - M_rest is recomputed from xc instead)
     float M0 = 1.f;
@@ -214,23 +291,33 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_evenodd(float base0, const float* b
             acc += Mrest * (sgs * (base0 + bE[d]) + 2.f * m0 * bE[d] + sgd * bO[d]);
         } else {
             acc += ev * (base0 + bE[d]) + 2.f * bE[d] + od * bO[d];
+            if (fp) {
+                const NsvdPotDiff v = nsvd_sin_of_cos_diff(prob, S, xc[d], d);
+                adv = fmaf(v.dif, od * (base0 + bE[d]) + (2.f + ev) * bO[d], adv);
+                lv += v.sum2;
+            }
         }
     }
     const float eps2 = (float)((double)prob.eps * (double)prob.eps);
     const float spc = prob.use_importance ? fmaxf(sp0, NSVD_SQRT_P_CLAMP) : 1.f;
     const float lap = ((c * (sp0 * mk0)) * acc / eps2) / spc;
     const float fs = (sp0 * (c * base0 * (mk0 * M0))) / spc;
-    const float V = nsvd_potential(prob, r0);
-    const float H = -prob.scale_kinetic * lap + V * fs;
     NsvdFdOut o;
     o.f = fs;
-    o.Tf = prob.op_scale * (-H) + prob.op_shift * fs;
+    if (fp) {
+        o.Tf = prob.op_scale * nsvd_fp_apply(prob, lap, fs, (c * (sp0 * mk0)) / spc, adv, lv, eps2) + prob.op_shift * fs;
+    } else {
+        const float V = nsvd_potential<TRIG>(prob, xc, D, r0);
+        const float H = -prob.scale_kinetic * lap + V * fs;
+        o.Tf = prob.op_scale * (-H) + prob.op_shift * fs;
+    }
     const float w = (sp0 / spc) * c;
     o.jac = w * (mk0 * M0);
     o.dsc = has_mask ? w * base0 * (mk0 * M0) * r0 / (s_l * s_l) : 0.f;
     return o;
 }
 
+template <bool TRIG = true>
 __device__ __forceinline__ NsvdFdOut nsvd_fd_point(const float* bv, const float* xc, int D, bool has_mask, float s_l,
                                                    const nsvd_problem& prob, float log_norm, const NsvdBox& box) {
     const int E = 1 + 2 * D;
@@ -245,8 +332,8 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_point(const float* bv, const float*
             r0 = o.r;
         }
     }
-    return nsvd_fd_combine(g, sp0, mask0, r0, bv[0], D, has_mask, s_l, prob,
-                           box.mode ? nsvd_box_point(xc, D, 0, prob.eps, box) : 1.f);
+    return nsvd_fd_combine<TRIG>(g, sp0, mask0, r0, bv[0], D, has_mask, s_l, prob,
+                           box.mode ? nsvd_box_point(xc, D, 0, prob.eps, box) : 1.f, xc);
 }
 
 // Exact-Laplacian mode (laplacian_eps <= 0: VectorizedLaplacian.exact_laplacian, diff_ops.py:54-61): the model's
@@ -324,7 +411,7 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_exact(float base, const float* dbas
     const float spc = prob.use_importance ? fmaxf(sp, NSVD_SQRT_P_CLAMP) : 1.f;
     lap = lap / spc;
     const float fs = g / spc;
-    const float V = nsvd_potential(prob, r0);
+    const float V = nsvd_potential(prob, xc, D, r0);
     const float H = -prob.scale_kinetic * lap + V * fs;
     NsvdFdOut o;
     o.f = fs;
@@ -412,7 +499,7 @@ __device__ __forceinline__ NsvdNefOut nsvd_nef_evenodd(float base0, const float*
     const float h = u0 / n0;
     const float lap = ((c * (sp0 * mk0) / n0) * acc / eps2) / spc;
     const float fs = (sp0 * h) / spc;
-    const float V = nsvd_potential(prob, r0);
+    const float V = nsvd_potential(prob, xc, D, r0);
     const float H = -prob.scale_kinetic * lap + V * fs;
     NsvdNefOut o;
     o.phi = fs;

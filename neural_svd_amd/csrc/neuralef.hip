@@ -364,7 +364,10 @@ extern "C" int nsvd_nef_operator_forward(const nsvd_model_desc* desc, const nsvd
     if (desc->D < 1 || desc->D > NSVD_FD_MAXD || desc->L <= 0) return NSVD_EINVAL;
     if (desc->has_exp_mask && !params->scales) return NSVD_EINVAL;
     if (ws_bytes < nsvd_workspace_bytes(desc, B) || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
-    if (prob->potential < NSVD_POT_HYDROGEN || prob->potential > NSVD_POT_ZERO) return NSVD_EINVAL;
+    const int st = nsvd_problem_status(*desc, *prob);
+    if (st) return st;
+    // NeuralEF is built on the Schroedinger kind (every potential of nsvd_potential)
+    if (prob->operator_kind != NSVD_OP_SCHROEDINGER) return NSVD_EUNSUPPORTED;
     // the per-point batch norms know neither the box mask nor the uniform density (nsvd_operator_forward_raw refuses too)
     if (desc->box_mask != NSVD_BOX_NONE || prob->use_importance > NSVD_IMP_GAUSSIAN) return NSVD_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;

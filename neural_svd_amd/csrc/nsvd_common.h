@@ -1,6 +1,7 @@
 // Shared host/device helpers for libnsvd_hip (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include "../../include/nsvd.h"
 
@@ -27,6 +28,26 @@ static inline NsvdBox nsvd_box_of(const nsvd_model_desc& d) {
     b.mode = d.box_mask;
     b.lim = d.box_lim;
     return b;
+}
+// Is (desc, prob) an operator this library carries? 0, NSVD_EINVAL for a value it does not know (or the sin-of-cos
+// potential outside the Fokker-Planck kind), NSVD_EUNSUPPORTED for a Fokker-Planck problem outside what the epilogue
+// implements: others.py:23-24 divides by the UNCLAMPED sqrt p (equal to the clamped one only from 1e-5 up), takes every
+// derivative by central differences (eps > 0; with eps <= 0 the reference's own einsum fails) and main's problems.py
+// asserts against the Gaussian sampler; no box mask is defined for the periodic problems.
+static inline int nsvd_problem_status(const nsvd_model_desc& d, const nsvd_problem& p) {
+    if (p.potential < NSVD_POT_HYDROGEN || p.potential > NSVD_POT_SIN_OF_COS) return NSVD_EINVAL;
+    if (p.use_importance < NSVD_IMP_NONE || p.use_importance > NSVD_IMP_UNIFORM) return NSVD_EINVAL;
+    if (p.operator_kind < NSVD_OP_SCHROEDINGER || p.operator_kind > NSVD_OP_FOKKER_PLANCK) return NSVD_EINVAL;
+    if (p.operator_kind != NSVD_OP_FOKKER_PLANCK) return p.potential == NSVD_POT_SIN_OF_COS ? NSVD_EINVAL : 0;
+    if (p.potential != NSVD_POT_SIN_OF_COS || !(p.eps > 0.f) || p.use_importance == NSVD_IMP_GAUSSIAN ||
+        d.box_mask != NSVD_BOX_NONE)
+        return NSVD_EUNSUPPORTED;
+    if (p.use_importance == NSVD_IMP_UNIFORM) {
+        if (!(p.sigma > 0.f)) return NSVD_EINVAL;
+        const double sqrt_p = exp(-0.5 * (double)d.D * log(2.0 * (double)p.sigma));
+        if (sqrt_p < (double)NSVD_SQRT_P_CLAMP) return NSVD_EUNSUPPORTED;
+    }
+    return 0;
 }
 static inline size_t nsvd_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 

@@ -54,11 +54,10 @@ int validate(const nsvd_model_desc* d, int max_d = 4) {
 }
 
 // every operator path implements every potential and importance below; anything else is refused, never ignored
-int validate_problem(const nsvd_problem* p) {
+// (the Fokker-Planck kind only inside nsvd_problem_status' conditions: NSVD_EUNSUPPORTED outside them)
+int validate_problem(const nsvd_model_desc* d, const nsvd_problem* p) {
     if (!p) return NSVD_EINVAL;
-    if (p->potential < NSVD_POT_HYDROGEN || p->potential > NSVD_POT_ZERO) return NSVD_EINVAL;
-    if (p->use_importance < NSVD_IMP_NONE || p->use_importance > NSVD_IMP_UNIFORM) return NSVD_EINVAL;
-    return 0;
+    return nsvd_problem_status(*d, *p);
 }
 
 NsvdSampler make_sampler(const nsvd_problem& prob, unsigned long long seed, unsigned long long offset) {
@@ -228,7 +227,9 @@ extern "C" int nsvd_step_emits_planes(const nsvd_model_desc* desc, int B, int pa
 }
 
 extern "C" const char* nsvd_path_name_for(const nsvd_model_desc* desc, const nsvd_problem* prob, int B, int path) {
-    if (validate(desc) != 0 || B <= 0 || validate_problem(prob) != 0) return "invalid";
+    if (validate(desc) != 0 || B <= 0 || !prob) return "invalid";
+    const int st = validate_problem(desc, prob);
+    if (st) return st == NSVD_EUNSUPPORTED ? "unsupported" : "invalid";
     const bool exact = !(prob->eps > 0.f);
     if (want_fused(*desc, B, path, exact)) return "fused_mfma";
     return exact ? "unsupported" : "generic";
@@ -254,7 +255,7 @@ extern "C" int nsvd_operator_forward(const nsvd_model_desc* desc, const nsvd_par
     int rc = validate(desc);
     if (rc) return rc;
     if (!prob || !x || !f || !Tf || !ws || B <= 0) return NSVD_EINVAL;
-    rc = validate_problem(prob);
+    rc = validate_problem(desc, prob);
     if (rc) return rc;
     rc = check_params(*desc, params, true);
     if (rc) return rc;
@@ -327,7 +328,7 @@ int sample_features_impl(const nsvd_model_desc* desc, const nsvd_params* params,
     int rc = validate(desc);
     if (rc) return rc;
     if (!prob || !x || !ws || !params || !params->fourier_B || B <= 0) return NSVD_EINVAL;
-    rc = validate_problem(prob);
+    rc = validate_problem(desc, prob);
     if (rc) return rc;
     if (ws_bytes < nsvd_workspace_bytes(desc, B)) return NSVD_EINVAL;
     if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
@@ -617,7 +618,8 @@ extern "C" int nsvd_operator_backward_evd_step_window(const nsvd_model_desc* des
     if (x_next) {  // the next batch rides in THIS window's chain launch (pass it to one window of the step only)
         if (!ws_next || ws_next == ws) return NSVD_EINVAL;
         if (ws_next_bytes < nsvd_workspace_bytes(desc, B) || ((uintptr_t)ws_next & 255) != 0) return NSVD_EINVAL;
-        if (validate_problem(prob) != 0) return NSVD_EINVAL;
+        if (!desc) return NSVD_EINVAL;
+        if (const int st = validate_problem(desc, prob)) return st;
         memset(&nb, 0, sizeof(nb));
         nb.smp = make_sampler(*prob, next_seed, next_offset);
         nb.x = x_next;
@@ -641,7 +643,8 @@ extern "C" int nsvd_operator_backward_evd_step_next(const nsvd_model_desc* desc,
                                                     size_t ws_next_bytes, void* stream) {
     if (!opt || !prob || !x_next || !ws_next || ws_next == ws) return NSVD_EINVAL;
     if (ws_next_bytes < nsvd_workspace_bytes(desc, B) || ((uintptr_t)ws_next & 255) != 0) return NSVD_EINVAL;
-    if (validate_problem(prob) != 0) return NSVD_EINVAL;
+    if (!desc) return NSVD_EINVAL;
+    if (const int st = validate_problem(desc, prob)) return st;
     NsvdNextBatch nb;
     memset(&nb, 0, sizeof(nb));
     nb.smp = make_sampler(*prob, next_seed, next_offset);

@@ -112,7 +112,8 @@ struct ParamSet {
 struct Problem {
     nsvd_problem q;
     Problem(int potential, double charge_or_k, double eps, double op_scale, double op_shift, double sigma,
-            double scale_kinetic, double hard_mul_const, int use_importance) {
+            double scale_kinetic, double hard_mul_const, int use_importance, int operator_kind, double fp_scale,
+            std::vector<double> pot_coef) {
         memset(&q, 0, sizeof(q));
         q.potential = potential;
         q.charge_or_k = (float)charge_or_k;
@@ -123,6 +124,10 @@ struct Problem {
         q.sigma = (float)sigma;
         q.hard_mul_const = (float)hard_mul_const;
         q.use_importance = use_importance;  // NSVD_IMP_*
+        TORCH_CHECK(pot_coef.size() <= 4, "pot_coef: at most 4 coefficients");
+        q.operator_kind = operator_kind;  // NSVD_OP_*
+        q.fp_scale = (float)fp_scale;
+        for (size_t i = 0; i < pot_coef.size(); ++i) q.pot_coef[i] = (float)pot_coef[i];
     }
 };
 
@@ -360,7 +365,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     py::class_<ParamSet>(m, "ParamSet")
         .def(py::init<const Shape&, std::vector<at::Tensor>, std::vector<at::Tensor>, c10::optional<at::Tensor>,
                       c10::optional<at::Tensor>>());
-    py::class_<Problem>(m, "Problem").def(py::init<int, double, double, double, double, double, double, double, int>());
+    py::class_<Problem>(m, "Problem").def(py::init<int, double, double, double, double, double, double, double, int, int, double, std::vector<double>>());
     py::class_<Rmsprop>(m, "Rmsprop")
         .def(py::init<const ParamSet&, const ParamSet*, double, double, double, double, c10::optional<at::Tensor>>(),
              py::keep_alive<1, 2>(), py::keep_alive<1, 3>());

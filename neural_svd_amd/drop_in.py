@@ -146,6 +146,8 @@ def _fused_loop_trainer(args, method, operator, importance_train, device, comm=N
     if not isinstance(operator, OperatorWrapper) or \
             not isinstance(importance_train, (GaussianImportance, UniformImportance)):
         return None
+    if not operator.fused(importance_train):  # (Fokker-Planck with the Gaussian density: the stencil outside the kernel)
+        return None
     if torch.device(device).type != "cuda":
         return None
     try:

@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import (MASK_CUSTOM, MASK_JOINT, MASK_SEQUENTIAL, PATH_AUTO, PATH_FUSED, PATH_FUSED_BF16X3,  # noqa: F401
                    PATH_GENERIC,
-                   BOX_EXP, BOX_NONE, BOX_SQRT, IMP_GAUSSIAN, IMP_NONE, IMP_UNIFORM, POT_HARMONIC, POT_HYDROGEN, POT_ZERO,
+                   BOX_EXP, BOX_NONE, BOX_SQRT, IMP_GAUSSIAN, IMP_NONE, IMP_UNIFORM, POT_HARMONIC, POT_HYDROGEN, POT_ZERO, POT_COSINE, POT_H2_ION, POT_SIN_OF_COS, OP_SCHROEDINGER, OP_FOKKER_PLANCK,
                    ModelDesc, NsvdError, Params, Problem, check)
 
 
@@ -68,7 +68,8 @@ def _tb_problem(prob: Problem):
     q = getattr(prob, "_tb", None)
     if q is None:
         q = prob._tb = _TB.Problem(prob.potential, prob.charge_or_k, prob.eps, prob.op_scale, prob.op_shift, prob.sigma,
-                                   prob.scale_kinetic, prob.hard_mul_const, int(prob.use_importance))
+                                   prob.scale_kinetic, prob.hard_mul_const, int(prob.use_importance),
+                                   int(prob.operator_kind), prob.fp_scale, [float(c) for c in prob.pot_coef])
     return q
 
 
@@ -163,9 +164,12 @@ class ModelShape:
 
 def make_problem(potential: int, charge_or_k: float, eps: float, op_scale: float, op_shift: float, sigma: float,
                  scale_kinetic: float = 1.0, hard_mul_const: float = 1.0, use_importance: bool = True,
-                 importance_kind: Optional[int] = None) -> Problem:
+                 importance_kind: Optional[int] = None, operator_kind: int = OP_SCHROEDINGER, fp_scale: float = 0.0,
+                 pot_coef: Sequence[float] = ()) -> Problem:
     """importance_kind (IMP_NONE / IMP_GAUSSIAN / IMP_UNIFORM) names the density when given; otherwise use_importance
-    chooses between none and the Gaussian. ``sigma`` is the sampling scale of either density."""
+    chooses between none and the Gaussian. ``sigma`` is the sampling scale of either density. ``pot_coef``: cs of
+    POT_COSINE / POT_SIN_OF_COS (one per input dimension) or (R,) of POT_H2_ION; ``operator_kind`` OP_FOKKER_PLANCK
+    (with POT_SIN_OF_COS) applies fp_scale (Lap f + grad V . grad f + f Lap V) instead of the Hamiltonian."""
     p = Problem()
     p.potential = int(potential)
     p.charge_or_k = float(charge_or_k)
@@ -180,6 +184,12 @@ def make_problem(potential: int, charge_or_k: float, eps: float, op_scale: float
     if int(importance_kind) not in (IMP_NONE, IMP_GAUSSIAN, IMP_UNIFORM):
         raise NsvdError(f"importance_kind {importance_kind}: IMP_NONE, IMP_GAUSSIAN or IMP_UNIFORM")
     p.use_importance = int(importance_kind)
+    if len(pot_coef) > 4:
+        raise NsvdError(f"pot_coef: at most 4 coefficients (the stencil's input dimensions), got {len(pot_coef)}")
+    p.operator_kind = int(operator_kind)
+    p.fp_scale = float(fp_scale)
+    for i, c in enumerate(pot_coef):
+        p.pot_coef[i] = float(c)
     return p
 
 

@@ -5,10 +5,13 @@ OperatorWrapper, get_problem, the Gaussian sampler / importance and the analytic
     infinite_well_potential                             examples/operator/pde/schrodinger/potentials.py:20-21
     NegativeHamiltonian                                 examples/operator/pde/schrodinger/__init__.py:4-22
     OperatorWrapper                                     examples/__init__.py:1-9
-    get_problem                                         examples/operator/pde/problems.py:23-130 (sch: hydrogen, oscillator)
+    cosine_potential / hydrogen_mol_ion_potential       examples/operator/pde/schrodinger/potentials.py:11-17,30-31
+    NegativeLinearFokkerPlanck / sin_of_cos_potential   examples/operator/pde/others.py:6-34
+    get_problem                                         examples/operator/pde/problems.py:23-130 (all but quantum_chemistry)
     get_dataloader                                      examples/operator/pde/main_pde.py:89-130 (gaussian sampler)
     Hydrogen2D / HarmonicOscillator .get_eigvals        examples/operator/pde/schrodinger/ground_truths.py:78-90,120-132
     InfiniteWell2D.get_eigvals                          examples/operator/pde/schrodinger/ground_truths.py:40-58
+    Hydrogen3D.get_eigvals                              examples/operator/pde/schrodinger/ground_truths.py (3-D hydrogen)
 
 These objects are DESCRIPTORS on the scripts' configuration (Gaussian or uniform sampler / importance, or none): calling
 ``operator(method, x, importance)`` forwards to the fused HIP kernel (nsvd_operator_forward). With the Laplace
@@ -48,23 +51,70 @@ def infinite_well_potential(x):
     return torch.zeros((x.shape[0],), device=x.device)
 
 
+def hydrogen_mol_ion_potential(x, R, charge=2.0):
+    """H2+: -q / |x - R e_last| - q / |x + R e_last|, the nuclei on the last axis (potentials.py:11-17)."""
+    x = x.reshape(x.shape[0], -1)
+    e = torch.zeros((x.shape[-1],), device=x.device, dtype=x.dtype)
+    e[-1] = 1.0
+    return hydrogen_potential(x - R * e, charge) + hydrogen_potential(x + R * e, charge)
+
+
+def _coefs(cs, x):
+    """torch.tensor(cs): float32 roundings of the literals whatever the dtype of x, as the reference makes them"""
+    return torch.tensor(cs, device=x.device).view(1, -1)
+
+
+def cosine_potential(x, cs):
+    """sum_d cs[d] cos x_d (potentials.py:30-31)."""
+    return (torch.cos(x.view(x.shape[0], -1)) * _coefs(cs, x)).sum(-1)
+
+
+def sin_of_cos_potential(xs, cs):
+    """sin(sum_d cs[d] cos x_d): the drift potential of NegativeLinearFokkerPlanck (others.py:33-34)."""
+    return torch.sin((torch.cos(xs) * _coefs(cs, xs)).sum(-1))
+
+
 def _potential_kind(ftn):
+    """-> (NSVD_POT_*, charge_or_k, pot_coef) of a potential function of this module (or a partial of one)"""
     base, kw = ftn, {}
     if isinstance(ftn, partial):
         base, kw = ftn.func, ftn.keywords
     if base is hydrogen_potential:
-        return H.POT_HYDROGEN, float(kw.get("charge", 1.0))
+        return H.POT_HYDROGEN, float(kw.get("charge", 1.0)), ()
     if base is harmonic_oscillator_potential:
-        return H.POT_HARMONIC, float(kw.get("k", 1.0))
+        return H.POT_HARMONIC, float(kw.get("k", 1.0)), ()
     if base is infinite_well_potential:
-        return H.POT_ZERO, 0.0
-    raise NsvdError("HIP path supports hydrogen_potential, harmonic_oscillator_potential and infinite_well_potential "
-                    "only")
+        return H.POT_ZERO, 0.0, ()
+    if base in (cosine_potential, sin_of_cos_potential):
+        if "cs" not in kw:
+            raise NsvdError(f"{base.__name__}: bind the coefficients, partial({base.__name__}, cs=[...])")
+        cs = tuple(float(c) for c in kw["cs"])
+        if len(cs) > _MAX_STENCIL_DIM:
+            raise NotImplementedError(f"{base.__name__} with {len(cs)} coefficients: {_TOO_MANY_DIMS}")
+        return (H.POT_COSINE if base is cosine_potential else H.POT_SIN_OF_COS), 0.0, cs
+    if base is hydrogen_mol_ion_potential:
+        if "R" not in kw:
+            raise NsvdError("hydrogen_mol_ion_potential: bind the half-distance, partial(..., R=..., charge=...)")
+        return H.POT_H2_ION, float(kw.get("charge", 2.0)), (float(kw["R"]),)
+    raise NsvdError("HIP path supports hydrogen_potential, harmonic_oscillator_potential, infinite_well_potential, "
+                    "cosine_potential, hydrogen_mol_ion_potential and (Fokker-Planck) sin_of_cos_potential only")
+
+
+_MAX_STENCIL_DIM = 4  # NSVD_FD_MAXD (csrc/fd_math.h); the fused MFMA kernels take D <= 3
+_TOO_MANY_DIMS = ("the finite-difference stencil of the HIP kernels carries at most 4 input dimensions (NSVD_FD_MAXD; "
+                  "the fused MFMA kernels 3) - ndim 5 and 10 are not built")
+
+
+class ProblemConfigError(AssertionError, NotImplementedError):
+    """A configuration get_problem refuses. The reference refuses the same ones with a bare ``assert``; earlier versions
+    of this package raised NotImplementedError for the problems themselves - a handler written for either catches it."""
 
 
 class NegativeHamiltonian:
     def __init__(self, local_potential_ftn, scale_kinetic=1.0, laplacian_eps=1e-5, n_particles=1):
-        self.potential_kind, self.potential_param = _potential_kind(local_potential_ftn)
+        self.potential_kind, self.potential_param, self.potential_coef = _potential_kind(local_potential_ftn)
+        if self.potential_kind == H.POT_SIN_OF_COS:
+            raise NsvdError("sin_of_cos_potential is the drift potential of NegativeLinearFokkerPlanck")
         self.local_potential_ftn = local_potential_ftn
         self.scale_kinetic = scale_kinetic
         self.laplacian_eps = laplacian_eps
@@ -75,11 +125,39 @@ class NegativeHamiltonian:
         return OperatorWrapper(self)(f, xs, importance)
 
 
+class NegativeLinearFokkerPlanck:
+    """others.py:6-30: T f = scale (Lap f + grad V . grad f + f Lap V) with V = local_potential_ftn, every derivative -
+    those of V too - the central difference with step ``laplacian_eps``; with an importance density p the stencil runs
+    on g = sqrt(p) f and everything is divided by the UNCLAMPED sqrt p(x). ``laplacian_eps <= 0`` does not exist (the
+    reference's own einsum fails on the exact-Laplacian gradient's shape)."""
+
+    def __init__(self, local_potential_ftn, scale=1.0, laplacian_eps=1e-5):
+        self.potential_kind, self.potential_param, self.potential_coef = _potential_kind(local_potential_ftn)
+        if self.potential_kind != H.POT_SIN_OF_COS:
+            raise NsvdError("HIP path: NegativeLinearFokkerPlanck takes partial(sin_of_cos_potential, cs=[...])")
+        if not laplacian_eps > 0:
+            raise NotImplementedError("NegativeLinearFokkerPlanck needs laplacian_eps > 0 (the reference has no exact-"
+                                      "Laplacian Fokker-Planck either: others.py:27 fails there)")
+        self.local_potential_ftn = local_potential_ftn
+        self.scale = scale
+        self.laplacian_eps = laplacian_eps
+        self.n_particles = 1
+        self.scale_kinetic = 1.0  # (unused by this operator; nsvd_problem carries the field)
+
+    def __call__(self, f, xs, importance=None):
+        return OperatorWrapper(self)(f, xs, importance)
+
+
 class OperatorWrapper:
     def __init__(self, operator, scale=1.0, shift=0.0):
-        if not isinstance(operator, NegativeHamiltonian):
-            raise NotImplementedError("HIP path: OperatorWrapper wraps this package's NegativeHamiltonian")
+        if not isinstance(operator, (NegativeHamiltonian, NegativeLinearFokkerPlanck)):
+            raise NotImplementedError("HIP path: OperatorWrapper wraps this package's NegativeHamiltonian or "
+                                      "NegativeLinearFokkerPlanck")
         self.operator, self.scale, self.shift = operator, scale, shift
+
+    @property
+    def fokker_planck(self) -> bool:
+        return isinstance(self.operator, NegativeLinearFokkerPlanck)
 
     def __call__(self, model, x, importance=None):
         """returns (scale * Tf + shift * f, f) like the reference; ``model`` is the NestedLoRA method."""
@@ -87,6 +165,8 @@ class OperatorWrapper:
 
     def fused(self, importance) -> bool:
         """does the fused kernel (nsvd_operator_forward) implement this importance density?"""
+        if self.fokker_planck:  # (with the Gaussian density the kernel refuses it: nsvd_path_name_for "unsupported")
+            return importance is None or isinstance(importance, UniformImportance)
         return importance is None or isinstance(importance, (GaussianImportance, UniformImportance))
 
     def apply_stencil(self, model, x, importance):
@@ -109,15 +189,33 @@ class OperatorWrapper:
             return importance(z).sqrt() * model(z)
         gs = g(x)
         lap = -2.0 * D * gs.detach()
+        fp = self.fokker_planck
         with torch.no_grad():
+            adv = torch.zeros_like(lap)
+            if fp:  # V differenced by the same stencil (others.py:25)
+                def pot(z):
+                    return ham.local_potential_ftn(z).view(-1, 1)
+                V0 = pot(x)
+                lap_v = -2.0 * D * V0
             for i in range(D):
                 e = torch.zeros((1, D), device=x.device)
                 e[0, i] = eps
-                lap = lap + g(x + e) + g(x - e)
+                gp, gm = g(x + e), g(x - e)
+                lap = lap + gp + gm
+                if fp:
+                    vp, vm = pot(x + e), pot(x - e)
+                    lap_v = lap_v + vp + vm
+                    adv = adv + ((vp - vm) / (2 * eps)) * ((gp - gm) / (2 * eps))
             lap = lap / eps ** 2
-            sw = torch.clamp(importance(x).sqrt(), min=1e-5)
+            # (the Fokker-Planck operator divides by the unclamped sqrt p: others.py:23-24)
+            sw = importance(x).sqrt() if fp else torch.clamp(importance(x).sqrt(), min=1e-5)
             lap = lap / sw
         fs = gs / sw
+        if fp:
+            with torch.no_grad():
+                Tf = ham.scale * (lap + adv / sw + fs * (lap_v / eps ** 2))
+                Tf = self.scale * Tf + self.shift * fs
+            return Tf, fs
         with torch.no_grad():
             V = ham.local_potential_ftn(x.reshape(x.shape[0], ham.n_particles, -1)).view(-1, 1)
             Tf = -(-ham.scale_kinetic * lap + V * fs)
@@ -191,9 +289,18 @@ def fused_problem_of(operator, importance, model) -> H.Problem:
         # the kernel's exponent is the model's input dimension; the reference's is args.ndim (equal: n_particles is 1)
         raise NsvdError(f"fused operator kernel: UniformImportance(ndim={importance.ndim}) on a model of input "
                         f"dimension {model.shape.D}")
+    if len(ham.potential_coef) != (1 if ham.potential_kind == H.POT_H2_ION else model.shape.D) and ham.potential_coef:
+        raise NsvdError(f"fused operator kernel: {len(ham.potential_coef)} potential coefficients on a model of input "
+                        f"dimension {model.shape.D}")
+    fp = operator.fokker_planck
+    if fp and kind == H.IMP_GAUSSIAN:
+        raise NsvdError("fused operator kernel: the Fokker-Planck operator with the Gaussian density goes through "
+                        "OperatorWrapper.apply_stencil (the reference's problems assert against that sampler)")
     return H.make_problem(ham.potential_kind, ham.potential_param, ham.laplacian_eps, operator.scale, operator.shift,
                           importance.sigma if importance is not None else 1.0, ham.scale_kinetic,
-                          float(model.hard_mul_const), importance_kind=kind)
+                          float(model.hard_mul_const), importance_kind=kind,
+                          operator_kind=H.OP_FOKKER_PLANCK if fp else H.OP_SCHROEDINGER,
+                          fp_scale=float(ham.scale) if fp else 0.0, pot_coef=ham.potential_coef)
 
 
 # ----------------------------------------------------------------------------------- ground truths
@@ -209,6 +316,19 @@ class Hydrogen2D:
             n += 1
         q = np.array(shells[:neigs], dtype=np.float64)
         return -self.charge ** 2 / (4 * (q + 0.5) ** 2)
+
+
+class Hydrogen3D:
+    def __init__(self, charge=1.0):
+        self.charge = charge
+
+    def get_eigvals(self, neigs):
+        """E_n = -Z^2 / (4 n^2), degeneracy n^2. Like the reference the shells run over n < ceil(neigs^(1/3)) + 1 - its
+        bound on sum n^2 - and the list is then cut to ``neigs``: when those shells hold fewer states it comes back
+        SHORT (14 values for neigs = 16, 5 for neigs = 6). Kept: compare with ``[:len(result)]``."""
+        max_n = int(np.ceil(neigs ** (1.0 / 3))) + 1
+        q = np.array([n for n in range(1, max_n) for _ in range(n * n)], dtype=np.float64)
+        return -self.charge ** 2 / (4 * q[:neigs] ** 2)
 
 
 class HarmonicOscillator:
@@ -241,15 +361,57 @@ class InfiniteWell2D:
         return vals * np.pi ** 2 / float(self.L) ** 2
 
 
+# cs and -eigenvalues of the periodic benchmark pair (Han, Lu and Zhou 2020), as problems.py:49-61 tabulates them
+_COSINE_2D_CS = (0.814723686393179, 0.905791937075619)
+_COSINE_2D_EIGVALS = (
+    -0.591624518674115, 0.623365592493771, 0.662887867122419, 0.891545971509540, 0.982541637674317,
+    1.877877978290306, 2.146058357306075, 2.197531748842203, 2.465712127857973, 3.699555061533076,
+    3.701057706578779, 3.756708397099993, 3.758994296902169, 4.954067447329610, 4.955570092375313,
+    4.971698508267879, 4.973984408070056, 5.239878887283648, 5.242164787085825, 5.273721217881508,
+    5.275223862927211, 8.047887977307184, 8.049390622352888, 8.050173877109360, 8.051676522155063)
+
+
+def _require(cond, what):
+    if not cond:
+        raise ProblemConfigError(what)
+
+
+def _periodic_asserts(args, name):
+    """the asserts the cosine and Fokker-Planck branches share (problems.py:39-44, 100-105)"""
+    _require(args.lim == np.pi, f"{name}: --lim must be pi")
+    _require(not args.apply_boundary, f"{name}: periodic problem, no --apply_boundary")
+    _require(args.use_fourier_feature and args.fourier_deterministic,
+             f"{name}: needs --use_fourier_feature and --fourier_deterministic (integer harmonics)")
+    _require(args.sampling_mode != "gaussian", f"{name}: not with the Gaussian sampler")
+    _require(args.ndim in (1, 2, 5, 10), f"{name}: ndim 1, 2, 5 or 10")
+    if args.ndim > 2:
+        raise ProblemConfigError(f"{name} with ndim {args.ndim}: {_TOO_MANY_DIMS}")
+
+
 def get_problem(args, device=None):
-    if args.problem != "sch":
-        raise NotImplementedError("only the Schroedinger problems are on the HIP path")
+    """problems.py:23-130 without its quantum_chemistry branch. The cosine and Fokker-Planck branches of the reference
+    read two names its own parser (main_pde.py) never defines; here ``args.use_gaussian_sampling`` is read as
+    ``args.sampling_mode == "gaussian"`` and ``args.scale_operator`` as ``getattr(args, "scale_operator", 1.0)``.
+    Refusals raise ProblemConfigError (an AssertionError, as the reference's asserts, and a NotImplementedError)."""
+    gt = None
     args.n_particles = 1
+    if args.problem == "fp":
+        _periodic_asserts(args, "problem fp")
+        cs = {1: [1.0], 2: [1.0, 1.0]}[args.ndim]
+        gt = np.array([0.0] + (args.neigs - 1) * [0.0])
+        inner = NegativeLinearFokkerPlanck(local_potential_ftn=partial(sin_of_cos_potential, cs=cs),
+                                           scale=getattr(args, "scale_operator", 1.0),
+                                           laplacian_eps=args.laplacian_eps)
+        op = OperatorWrapper(inner, scale=args.operator_scale, shift=args.operator_shift)
+        return op, args.operator_scale * gt + args.operator_shift
+    if args.problem != "sch":
+        raise NotImplementedError(f"problem {args.problem}: 'sch' and 'fp' are on the HIP path")
     if args.potential_type == "hydrogen":
         pot = partial(hydrogen_potential, charge=args.charge)
-        if args.ndim != 2:
-            raise NotImplementedError("hydrogen: ndim 2 only")
-        gt = -Hydrogen2D(charge=args.charge).get_eigvals(args.neigs)
+        if args.ndim == 2:
+            gt = -Hydrogen2D(charge=args.charge).get_eigvals(args.neigs)
+        elif args.ndim == 3:
+            gt = -Hydrogen3D(charge=args.charge).get_eigvals(args.neigs)
     elif args.potential_type == "harmonic_oscillator":
         pot = partial(harmonic_oscillator_potential, k=1.0)
         gt = -HarmonicOscillator(k=1.0, ndim=args.ndim).get_eigvals(args.neigs)
@@ -257,12 +419,24 @@ def get_problem(args, device=None):
         assert args.ndim == 2  # as the reference (problems.py:30)
         pot = infinite_well_potential
         gt = -InfiniteWell2D(L=2 * args.lim).get_eigvals(args.neigs)
+    elif args.potential_type == "cosine":
+        _periodic_asserts(args, "potential_type cosine")
+        if args.ndim == 1:
+            cs = [1.0]
+        else:
+            _require(args.neigs <= 25, "potential_type cosine: 25 eigenvalues are tabulated for ndim 2")
+            cs = list(_COSINE_2D_CS)
+            gt = -np.array(_COSINE_2D_EIGVALS[:args.neigs])
+        pot = partial(cosine_potential, cs=cs)
+    elif args.potential_type == "hydrogen_mol_ion":
+        # (each nucleus gets 2 * args.charge, as problems.py:77 passes it)
+        pot = partial(hydrogen_mol_ion_potential, R=args.hydrogen_mol_ion_R, charge=2 * args.charge)
     else:
         raise NotImplementedError(f"potential_type {args.potential_type}: not in scope of the HIP path")
     ham = NegativeHamiltonian(local_potential_ftn=pot, scale_kinetic=1.0, laplacian_eps=args.laplacian_eps,
                               n_particles=1)
     op = OperatorWrapper(ham, scale=args.operator_scale, shift=args.operator_shift)
-    return op, args.operator_scale * gt + args.operator_shift
+    return op, (args.operator_scale * gt + args.operator_shift if gt is not None else None)
 
 
 def get_dataloader(args, device):
