@@ -397,6 +397,97 @@ int nsvd_operator_sample_features_dev(const nsvd_model_desc* desc, const nsvd_pa
 int nsvd_rmsprop_ema_step(float* p, const float* grad, float* sq, float* ema, size_t n, double lr,
                           double alpha, double eps, double ema_decay, double grad_scale, void* stream);
 
+/* ---- the other optimisers of the reference's PDE loop (examples/utils.py:48-72: --optimizer rmsprop | adam | sgd,
+ * --momentum), stand-alone over n contiguous floats. torch.optim's rules as get_optimizer configures them (weight_decay
+ * 0, dampening 0, no Nesterov, no amsgrad, not centred), followed by the torch_ema update; g = grad_scale * grad:
+ *   NSVD_OPT_SGD,     momentum 0: p -= lr g                                                        (no state)
+ *   NSVD_OPT_SGD,     momentum u: mom = g on the first step taken, else u mom + g; p -= lr mom      (mom)
+ *   NSVD_OPT_RMSPROP, momentum 0: nsvd_rmsprop_ema_step                                            (sq)
+ *   NSVD_OPT_RMSPROP, momentum u: sq = alpha sq + (1-alpha) g^2; mom = u mom + g / (sqrt(sq) + eps); p -= lr mom
+ *                                                                                                   (sq, mom)
+ *   NSVD_OPT_ADAM: mom += (1-beta1)(g - mom); sq = beta2 sq + (1-beta2) g^2; t = steps taken + 1;
+ *                  p -= (lr / (1 - beta1^t)) mom / (sqrt(sq) / sqrt(1 - beta2^t) + eps)             (sq = v, mom = m)
+ * State slots a rule does not use may be NULL and are never touched. Host scalars are doubles (Python floats); lr /
+ * (1 - beta1^t) and sqrt(1 - beta2^t) are formed in double precision, and everything is rounded to float32 where torch
+ * rounds: lr, alpha, 1 - alpha, eps, momentum, 1 - beta1, beta2, 1 - beta2, the two Adam scalars, 1 - ema_decay. */
+#define NSVD_OPT_RMSPROP 0
+#define NSVD_OPT_SGD 1
+#define NSVD_OPT_ADAM 2
+typedef struct nsvd_opt_config {
+    int32_t kind;          /* NSVD_OPT_*; anything else: NSVD_EINVAL                                              */
+    int32_t reserved0;
+    double lr;             /* nsvd_opt_step: the step's already scheduled learning rate; _state_init: the base one */
+    double alpha;          /* RMSprop alpha (--rmsprop_decay)                                                      */
+    double eps;            /* RMSprop eps (1e-10: examples/utils.py:52) / Adam eps (--adam_eps)                    */
+    double momentum;       /* SGD / RMSprop --momentum                                                             */
+    double beta1, beta2;   /* Adam betas (0.9, 0.999)                                                              */
+    double ema_decay;      /* nsvd_opt_step: the already warmed-up decay; _state_init: --ema_decay                 */
+} nsvd_opt_config;
+/* One step of cfg's rule; steps_taken: optimiser steps before this one (SGD's first-step rule, Adam's t - 1). */
+int nsvd_opt_step(float* p, const float* grad, float* sq, float* mom, float* ema, size_t n, const nsvd_opt_config* cfg,
+                  unsigned long long steps_taken, double grad_scale, void* stream);
+
+/* The device-resident schedule of any rule (what nsvd_step_state is for RMSprop without momentum): beside the cosine
+ * learning rate and the EMA warm-up, Adam's bias corrections and SGD's first-step flag move along with `step`. Derived
+ * in double precision by one thread, with the expressions nsvd_opt_step evaluates on the host. DEVICE memory,
+ * sizeof(nsvd_opt_state) bytes, 8-byte aligned, filled by nsvd_opt_state_init. */
+typedef struct nsvd_opt_state {
+    uint64_t step;                   /* optimiser steps taken = scheduler steps = torch_ema.num_updates             */
+    uint64_t T_max;                  /* CosineAnnealingLR T_max; 0: constant learning rate                           */
+    double lr0, eta_min;
+    double alpha, eps, ema_decay, momentum, beta1, beta2;
+    int32_t kind;                    /* NSVD_OPT_*                                                                   */
+    int32_t mismatch;                /* set by a nsvd_opt_step_dev launch whose cfg names another rule (it did nothing) */
+    /* the values of the step being taken, derived from `step` by nsvd_opt_state_begin: */
+    struct {
+        float lr, alpha, one_minus_alpha, eps, one_minus_decay, grad_scale;
+        float momentum, one_minus_beta1, beta2, one_minus_beta2, step_size, bc2_sqrt;
+        int32_t first_step, rule;
+    } cur;
+} nsvd_opt_state;
+/* Fill a device-resident state (one tiny launch): counters at `step`, `cur` = the values of step `step`. */
+int nsvd_opt_state_init(nsvd_opt_state* state, const nsvd_opt_config* cfg, double eta_min, unsigned long long T_max,
+                        unsigned long long step, void* stream);
+/* state->cur <- the values of step state->step (one tiny launch; first thing in a captured loop body). */
+int nsvd_opt_state_begin(nsvd_opt_state* state, void* stream);
+/* nsvd_opt_step with the step's scalars read from state->cur (capturable: nothing host-side changes between replays).
+ * cfg: the configuration the state was initialised with - it selects the kernel and which slots must be non-NULL; a
+ * launch whose rule is not the state's touches nothing but state->mismatch. advance != 0: last optimiser launch of the
+ * step - one thread increments state->step when the kernel is done with it. */
+int nsvd_opt_step_dev(float* p, const float* grad, float* sq, float* mom, float* ema, size_t n,
+                      const nsvd_opt_config* cfg, nsvd_opt_state* state, double grad_scale, int advance, void* stream);
+
+/* nsvd_operator_backward_evd_step for any rule of nsvd_opt_config: the optimiser + EMA update taken inside the
+ * backward. On the MFMA kernels every gradient element is applied to its parameter in the weight-gradient kernel's
+ * epilogue (with `grads` NULL no gradient reaches memory); on the generic kernels the gradients are stored (`grads`
+ * required) and one stand-alone launch per tensor follows. State tensors are in the parameters' layouts; tables of
+ * slots the rule does not use are ignored. */
+typedef struct nsvd_optimizer {
+    nsvd_opt_config cfg;      /* lr: the step's scheduled learning rate, ema_decay: the already warmed-up decay      */
+    nsvd_params sq;           /* RMSprop's square averages / Adam's exp_avg_sq                                        */
+    nsvd_params mom;          /* momentum buffers / Adam's exp_avg                                                    */
+    nsvd_params ema;          /* EMA shadow (has_ema != 0)                                                            */
+    int32_t has_ema;
+    int32_t reserved0;
+    uint64_t steps_taken;     /* optimiser steps before this one (SGD's first-step rule, Adam's t - 1)                */
+    /* Non-NULL (DEVICE pointer, nsvd_opt_state_init with this cfg's rule): cfg.lr, cfg.ema_decay and steps_taken are
+     * ignored - the step's scalars are derived on the device (one tiny launch before the step's first kernel) and the
+     * step's last kernel increments state->step. NSVD_OPT_RMSPROP without momentum has its own device-resident form
+     * (nsvd_rmsprop::state of nsvd_operator_backward_evd_step): with a state here it returns NSVD_EUNSUPPORTED. */
+    nsvd_opt_state* state;
+} nsvd_optimizer;
+/* x_next NULL: the counterpart of nsvd_operator_backward_evd_step. x_next non-NULL: the counterpart of
+ * nsvd_operator_backward_evd_step_next (the next batch's draw and features ride in the chain launch; MFMA kernels
+ * only). NSVD_OPT_RMSPROP without momentum takes the kernels of nsvd_operator_backward_evd_step: same bits. */
+int nsvd_operator_backward_evd_opt_step(const nsvd_model_desc* desc, const nsvd_params* params,
+                                        const nsvd_problem* prob, const float* x, int B, const float* f,
+                                        const float* Tf, int mask_kind, const float* v, const float* M,
+                                        float* moments, int moments_reduced, const void* evd_scratch, int L_total,
+                                        int l_offset, float grad_scale, float* loss, const nsvd_params* grads,
+                                        const nsvd_optimizer* opt, void* ws, size_t ws_bytes, int path,
+                                        unsigned long long next_seed, unsigned long long next_offset, float* x_next,
+                                        void* ws_next, size_t ws_next_bytes, void* stream);
+
 /* compute_spectrum_evd accumulation for one chunk (methods/spectrum.py:56-75):
  *   w = sqrt(p_train(x)) / sqrt(p_val), phi = nan_to_num(w f), Tphi = nan_to_num(w Tf),
  *   Tphi rows with x ~ 0 zeroed, cov += phi^T phi, quad += phi^T Tphi   (cov, quad: (L, L)).

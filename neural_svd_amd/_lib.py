@@ -22,6 +22,7 @@ IMP_NONE, IMP_GAUSSIAN, IMP_UNIFORM = 0, 1, 2
 MASK_CUSTOM, MASK_SEQUENTIAL, MASK_JOINT = 0, 1, 2
 PATH_AUTO, PATH_GENERIC, PATH_FUSED, PATH_FUSED_BF16X3 = 0, 1, 2, 3
 NORMALIZE_L2_BALL, NORMALIZE_L2_SPHERE = 0, 1
+OPT_RMSPROP, OPT_SGD, OPT_ADAM = 0, 1, 2
 FEATURES_READY = 0x100
 W_PLANES_READY = 0x200
 
@@ -83,6 +84,33 @@ class StepState(C.Structure):
                 ("reserved", C.c_uint64)]
 
 
+class OptConfig(C.Structure):
+    """nsvd_opt_config: the scalars of one optimiser rule (include/nsvd.h)"""
+    _fields_ = [("kind", C.c_int32), ("reserved0", C.c_int32), ("lr", C.c_double), ("alpha", C.c_double),
+                ("eps", C.c_double), ("momentum", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("ema_decay", C.c_double)]
+
+
+class OptStateCur(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("lr", "alpha", "one_minus_alpha", "eps", "one_minus_decay", "grad_scale",
+                                         "momentum", "one_minus_beta1", "beta2", "one_minus_beta2", "step_size",
+                                         "bc2_sqrt")] + [("first_step", C.c_int32), ("rule", C.c_int32)]
+
+
+class OptState(C.Structure):
+    """host mirror of the DEVICE-resident nsvd_opt_state (sizes / offsets only: the library fills and advances it)"""
+    _fields_ = [("step", C.c_uint64), ("T_max", C.c_uint64), ("lr0", C.c_double), ("eta_min", C.c_double),
+                ("alpha", C.c_double), ("eps", C.c_double), ("ema_decay", C.c_double), ("momentum", C.c_double),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("kind", C.c_int32), ("mismatch", C.c_int32),
+                ("cur", OptStateCur)]
+
+
+class Optimizer(C.Structure):
+    """nsvd_optimizer: the optimiser step of any rule taken inside the backward (include/nsvd.h)"""
+    _fields_ = [("cfg", OptConfig), ("sq", Params), ("mom", Params), ("ema", Params), ("has_ema", C.c_int32),
+                ("reserved0", C.c_int32), ("steps_taken", C.c_uint64), ("state", C.c_void_p)]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against include/nsvd.h
 _P, _I, _F, _Z, _Dbl = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_double
 SIGNATURES = {
@@ -126,11 +154,19 @@ SIGNATURES = {
                                                   _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _F, _P, C.POINTER(Params),
                                                   C.POINTER(Rmsprop), _P, _Z, _I, C.c_uint64, C.c_uint64, _P, _P, _Z,
                                                   _P]),
+    "nsvd_operator_backward_evd_opt_step": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem), _P, _I,
+                                                 _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _F, _P, C.POINTER(Params),
+                                                 C.POINTER(Optimizer), _P, _Z, _I, C.c_uint64, C.c_uint64, _P, _P, _Z,
+                                                 _P]),
     "nsvd_evd_loss_fused": (_I, [_P, _P, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P]),
     "nsvd_rmsprop_ema_step": (_I, [_P, _P, _P, _P, _Z, _Dbl, _Dbl, _Dbl, _Dbl, _Dbl, _P]),
     "nsvd_step_state_init": (_I, [_P, _Dbl, _Dbl, C.c_uint64, _Dbl, _Dbl, _Dbl, C.c_uint64, _P]),
     "nsvd_step_state_begin": (_I, [_P, _P]),
     "nsvd_rmsprop_ema_step_dev": (_I, [_P, _P, _P, _P, _Z, _P, _Dbl, _I, _P]),
+    "nsvd_opt_step": (_I, [_P, _P, _P, _P, _P, _Z, C.POINTER(OptConfig), C.c_uint64, _Dbl, _P]),
+    "nsvd_opt_state_init": (_I, [_P, C.POINTER(OptConfig), _Dbl, C.c_uint64, C.c_uint64, _P]),
+    "nsvd_opt_state_begin": (_I, [_P, _P]),
+    "nsvd_opt_step_dev": (_I, [_P, _P, _P, _P, _P, _Z, C.POINTER(OptConfig), _P, _Dbl, _I, _P]),
     "nsvd_operator_sample_features_dev": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem), C.c_uint64,
                                                C.c_uint64, _P, _P, _I, _P, _Z, _I, _I, _P]),
     "nsvd_profile_next_forward": (_I, [_P, _P]),

@@ -133,6 +133,10 @@ bool nsvd_fused_backward_window_ok(const nsvd_model_desc& d, int B, int l_count)
 // stand-alone optimiser launch over n contiguous floats (optimizer.hip)
 int nsvd_rmsprop_launch(float* p, const float* grad, float* sq, float* ema, size_t n, const NsvdHyper& h,
                         hipStream_t s, nsvd_step_state* state = nullptr, int advance = 0);
+// any rule of opt_math.h (NsvdOptRule) over n contiguous floats; state: device-resident schedule or null
+struct NsvdOptHyper;
+int nsvd_opt_launch(int rule, float* p, const float* grad, float* sq, float* mom, float* ema, size_t n,
+                    const NsvdOptHyper& h, hipStream_t s, nsvd_opt_state* state = nullptr, int advance = 0);
 
 // the same update over a table of tensors in ONE launch (start[] is filled by the launcher; every pointer 16-byte aligned,
 // else NSVD_EUNSUPPORTED and nothing is launched)

@@ -435,7 +435,9 @@ int backward_evd_impl(const nsvd_model_desc* desc, const nsvd_params* params, co
                       int l_offset, float grad_scale, float* loss, const nsvd_params* grads,
                       const nsvd_rmsprop* opt, void* ws, size_t ws_bytes, int path, void* stream, int l_begin = 0,
                       int l_count = 0, const NsvdNextBatch* next = nullptr, bool model_mode = false,
-                      int window_of_step = 0, int not_last = 0, void* ev_after_chain = nullptr) {
+                      int window_of_step = 0, int not_last = 0, void* ev_after_chain = nullptr,
+                      const nsvd_optimizer* opt2 = nullptr) {
+    // opt2: the step of any rule (nsvd_operator_backward_evd_opt_step) - instead of `opt`, never both
     // model_mode: the forward was nsvd_model_forward (plain model evaluation, any input dimension up to 64, no
     // Hamiltonian): Tf is whatever operator output the caller computed from f (the kernel-operator path)
     int rc = validate(desc, model_mode ? MODEL_MAX_D : 4);
@@ -449,7 +451,8 @@ int backward_evd_impl(const nsvd_model_desc* desc, const nsvd_params* params, co
     if (mask_kind == NSVD_MASK_CUSTOM && (!v || !M)) return NSVD_EINVAL;
     rc = check_params(*desc, params, true);
     if (rc) return rc;
-    if (grads || !opt) {
+    if (opt && opt2) return NSVD_EINVAL;
+    if (grads || !(opt || opt2)) {
         rc = check_params(*desc, grads, false);
         if (rc) return rc;
     }
@@ -469,6 +472,38 @@ int backward_evd_impl(const nsvd_model_desc* desc, const nsvd_params* params, co
         if (st.state && ((uintptr_t)st.state & 7) != 0) return NSVD_EINVAL;
         st.emit_planes = !model_mode && path == NSVD_PATH_FUSED_BF16X3;
     }
+    if (opt2) {
+        const nsvd_opt_config& c = opt2->cfg;
+        const int rule = nsvd_opt_rule(c.kind, c.momentum);
+        if (rule < 0) return NSVD_EINVAL;
+        if (nsvd_rule_uses_sq(rule)) {
+            rc = check_params(*desc, &opt2->sq, false);
+            if (rc) return rc;
+            st.sq = opt2->sq;
+        }
+        if (nsvd_rule_uses_mom(rule)) {
+            rc = check_params(*desc, &opt2->mom, false);
+            if (rc) return rc;
+            st.mom = &opt2->mom;
+        }
+        if (opt2->has_ema) {
+            rc = check_params(*desc, &opt2->ema, false);
+            if (rc) return rc;
+            st.ema = &opt2->ema;
+        }
+        if (opt2->state && ((uintptr_t)opt2->state & 7) != 0) return NSVD_EINVAL;
+        st.rule = rule;
+        if (rule == NSVD_RULE_RMSPROP) {
+            if (opt2->state) return NSVD_EUNSUPPORTED;  // (its device-resident schedule is nsvd_rmsprop::state)
+            st.h = nsvd_make_hyper(c.lr, c.alpha, c.eps, opt2->has_ema ? c.ema_decay : 0.0, 1.0);
+        } else {
+            st.oh = nsvd_make_opt_hyper(rule, c.lr, c.alpha, c.eps, c.momentum, c.beta1, c.beta2,
+                                        opt2->has_ema ? c.ema_decay : 0.0, 1.0, opt2->steps_taken);
+            st.ostate = opt2->state;
+        }
+        st.emit_planes = !model_mode && path == NSVD_PATH_FUSED_BF16X3;
+    }
+    const bool take_step = opt || opt2;
     if (ws_bytes < (model_mode ? nsvd_model_workspace_bytes(desc, B) : nsvd_workspace_bytes(desc, B))) return NSVD_EINVAL;
     if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
@@ -498,7 +533,11 @@ int backward_evd_impl(const nsvd_model_desc* desc, const nsvd_params* params, co
             in.moments_out = moments;
         }
         if (l_count < 0 || l_begin < 0 || l_begin + l_count > desc->L) return NSVD_EINVAL;
-        return nsvd_fused_backward_evd(*desc, *params, B, in, grads, opt ? &st : nullptr, ws, s, l_begin, l_count,
+        if (st.ostate) {  // the step's scalars, derived before the step's first kernel
+            rc = nsvd_opt_state_begin(st.ostate, stream);
+            if (rc) return rc;
+        }
+        return nsvd_fused_backward_evd(*desc, *params, B, in, grads, take_step ? &st : nullptr, ws, s, l_begin, l_count,
                                        next, window_of_step, not_last, ev_after_chain);
     }
     if (window_of_step) return NSVD_EUNSUPPORTED;  // windows of a fused step exist on the fused kernels only
@@ -517,7 +556,36 @@ int backward_evd_impl(const nsvd_model_desc* desc, const nsvd_params* params, co
     if (rc) return rc;
     if (!grads) return NSVD_EINVAL;  // the generic path needs somewhere to put the gradients
     rc = generic_backward(*desc, *params, x, B, w.df, *grads, ws, s);
-    if (rc || !opt) return rc;
+    if (rc || !take_step) return rc;
+    if (st.rule != NSVD_RULE_RMSPROP) {
+        // the other rules: one stand-alone launch per tensor (scalars from the device-resident schedule when there is
+        // one: derived first, advanced by the last launch)
+        if (st.ostate) {
+            rc = nsvd_opt_state_begin(st.ostate, stream);
+            if (rc) return rc;
+        }
+        const int F = 2 * desc->m;
+        const int last = 2 * desc->nlayers - 1 + (desc->has_exp_mask ? 1 : 0);
+        int k = 0;
+        auto one = [&](float* pp, const float* gg, float* qq, float* mm, float* ee, size_t n) {
+            const int r = nsvd_opt_launch(st.rule, pp, gg, qq, mm, ee, n, st.oh, s, st.ostate, k == last);
+            ++k;
+            return r;
+        };
+        for (int i = 0; i < desc->nlayers; ++i) {
+            const size_t hin = i == 0 ? (size_t)F : (size_t)desc->dims[i - 1], hout = (size_t)desc->dims[i];
+            rc = one(params->W[i], grads->W[i], st.sq.W[i], st.mom ? st.mom->W[i] : nullptr,
+                     st.ema ? st.ema->W[i] : nullptr, (size_t)desc->L * hout * hin);
+            if (rc) return rc;
+            rc = one(params->b[i], grads->b[i], st.sq.b[i], st.mom ? st.mom->b[i] : nullptr,
+                     st.ema ? st.ema->b[i] : nullptr, (size_t)desc->L * hout);
+            if (rc) return rc;
+        }
+        if (desc->has_exp_mask)
+            rc = one(params->scales, grads->scales, st.sq.scales, st.mom ? st.mom->scales : nullptr,
+                     st.ema ? st.ema->scales : nullptr, (size_t)desc->L);
+        return rc;
+    }
     // generic path + fused-step request: ONE stand-alone optimiser launch over the table of tensors (unaligned tensors -
     // never with torch allocations -: one launch per tensor)
     const int F = 2 * desc->m;
@@ -666,4 +734,31 @@ extern "C" int nsvd_model_backward_evd_step(const nsvd_model_desc* desc, const n
     return backward_evd_impl(desc, params, nullptr, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch,
                              L_total, l_offset, grad_scale, loss, grads, opt, ws, ws_bytes, NSVD_PATH_AUTO, stream, 0, 0,
                              nullptr, true);
+}
+
+extern "C" int nsvd_operator_backward_evd_opt_step(const nsvd_model_desc* desc, const nsvd_params* params,
+                                                   const nsvd_problem* prob, const float* x, int B, const float* f,
+                                                   const float* Tf, int mask_kind, const float* v, const float* M,
+                                                   float* moments, int moments_reduced, const void* evd_scratch,
+                                                   int L_total, int l_offset, float grad_scale, float* loss,
+                                                   const nsvd_params* grads, const nsvd_optimizer* opt, void* ws,
+                                                   size_t ws_bytes, int path, unsigned long long next_seed,
+                                                   unsigned long long next_offset, float* x_next, void* ws_next,
+                                                   size_t ws_next_bytes, void* stream) {
+    if (!opt || !prob) return NSVD_EINVAL;
+    if (nsvd_opt_rule(opt->cfg.kind, opt->cfg.momentum) < 0) return NSVD_EINVAL;
+    NsvdNextBatch nb;
+    if (x_next) {
+        if (!ws_next || ws_next == ws || !desc) return NSVD_EINVAL;
+        if (ws_next_bytes < nsvd_workspace_bytes(desc, B) || ((uintptr_t)ws_next & 255) != 0) return NSVD_EINVAL;
+        if (const int st = validate_problem(desc, prob)) return st;
+        memset(&nb, 0, sizeof(nb));
+        nb.smp = make_sampler(*prob, next_seed, next_offset);
+        nb.x = x_next;
+        nb.ws = ws_next;
+        nb.eps = prob->eps;
+    }
+    return backward_evd_impl(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced,
+                             evd_scratch, L_total, l_offset, grad_scale, loss, grads, nullptr, ws, ws_bytes, path,
+                             stream, 0, 0, x_next ? &nb : nullptr, false, 0, 0, nullptr, opt);
 }

@@ -429,7 +429,19 @@ struct WgradArgs {
     // split launch (9 us, 17 MB read + 26 MB written per step): same rounding, same bits
     unsigned short* w0p;
     unsigned short* whp;
+    // rules other than RMSprop without momentum (the RULE instantiations; opt_math.h): the step's scalars, or the
+    // device-resident schedule they are read from (ostate; ostate_adv: non-null in the launch that ends the step - ONE
+    // thread increments its step counter)
+    NsvdOptHyper oh;
+    nsvd_opt_state* ostate;
+    nsvd_opt_state* ostate_adv;
+    // their `mom` slot (momentum buffers, Adam's exp_avg), tensor by tensor as oW / ob / oscales; null for rules without
+    float* mW[NSVD_MAX_LAYERS];
+    float* mb[NSVD_MAX_LAYERS];
+    float* mscales;
 };
+
+template <int RULE> using HyperOf = typename NsvdRuleHyper<RULE>::type;
 
 // where a gradient element goes: the caller's gradient tensor (+ fused optimiser) or this slice's partial buffer
 struct WgDst {
@@ -442,15 +454,18 @@ __device__ __forceinline__ WgDst wg_dst(const WgradArgs& a, float* g, size_t par
 }
 
 // one gradient element: store it and / or take the optimiser step on its parameter
-__device__ __forceinline__ void wg_emit1(const NsvdHyper& h, const WgDst& d, const NsvdOptPtrs& o, size_t off,
-                                         float val) {
+template <int RULE>
+__device__ __forceinline__ void wg_emit1(const HyperOf<RULE>& h, const WgDst& d, const NsvdOptPtrs& o, float* mom,
+                                         size_t off, float val) {
+    constexpr bool SQ = nsvd_rule_uses_sq(RULE), MOM = nsvd_rule_uses_mom(RULE);
     float* g = d.g;
     if (g) g[off] = val;
     if (d.opt) {
-        float pv = o.p[off], sv = o.sq[off], ev = o.ema ? o.ema[off] : 0.f;
-        nsvd_rmsprop_upd(pv, val, sv, ev, o.ema != nullptr, h);
+        float pv = o.p[off], sv = SQ ? o.sq[off] : 0.f, mv = MOM ? mom[off] : 0.f, ev = o.ema ? o.ema[off] : 0.f;
+        nsvd_rule_upd<RULE>(pv, val, sv, mv, ev, o.ema != nullptr, h);
         o.p[off] = pv;
-        o.sq[off] = sv;
+        if (SQ) o.sq[off] = sv;
+        if (MOM) mom[off] = mv;
         if (o.ema) o.ema[off] = ev;
     }
 }
@@ -513,38 +528,72 @@ __device__ __forceinline__ void wg_planes_store(const WgPlanes& pl, int r, int h
     *reinterpret_cast<unsigned short*>(q + 2 * pl.plane) = (unsigned short)h2;
 }
 
-template <bool EMA>
-__device__ __forceinline__ void wg_opt16(const NsvdHyper& h, const NsvdOptPtrs& o, unsigned base, unsigned ld, int hi,
-                                         const f32x16& acc, const WgPlanes pl = WgPlanes{nullptr, 0, 0}) {
-    float pv[16], sv[16], ev[16];
+// Rules with both a square average and a momentum buffer (RMSprop with momentum, Adam) have four state streams: 64
+// loads in flight over 16 rows where 48 were already at the edge of spilling, so those take the rows in two halves
+// (2 x 32 loads in flight); every other rule takes the 16 rows at once, as RMSprop without momentum always has.
+template <int RULE, bool EMA>
+__device__ __forceinline__ void wg_opt16(const HyperOf<RULE>& h, const NsvdOptPtrs& o, float* mom, unsigned base,
+                                         unsigned ld, int hi, const f32x16& acc,
+                                         const WgPlanes pl = WgPlanes{nullptr, 0, 0}) {
+    if constexpr (RULE == NSVD_RULE_RMSPROP) {  // (the epilogue as it has always been)
+        constexpr bool EMA_ = EMA;
+        float pv[16], sv[16], ev[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {  // 48 independent loads in flight
-        const unsigned off = 4u * (base + (unsigned)acc_row(r, hi) * ld);
-        pv[r] = wg_ld(o.p, off);
-        sv[r] = wg_ld(o.sq, off);
-        ev[r] = EMA ? wg_ld(o.ema, off) : 0.f;
+        for (int r = 0; r < 16; ++r) {  // 48 independent loads in flight
+            const unsigned off = 4u * (base + (unsigned)acc_row(r, hi) * ld);
+            pv[r] = wg_ld(o.p, off);
+            sv[r] = wg_ld(o.sq, off);
+            ev[r] = EMA_ ? wg_ld(o.ema, off) : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const unsigned off = 4u * (base + (unsigned)acc_row(r, hi) * ld);
+            nsvd_rmsprop_upd(pv[r], acc[r], sv[r], ev[r], EMA_, h);
+            wg_st(o.p, off, pv[r]);
+            wg_st(o.sq, off, sv[r]);
+            if (EMA_) wg_st(o.ema, off, ev[r]);
+            if (pl.base) wg_planes_store(pl, r, hi, pv[r]);
+        }
+        return;
     }
+    constexpr bool SQ = nsvd_rule_uses_sq(RULE), MOM = nsvd_rule_uses_mom(RULE);
+    constexpr int RH = (SQ && MOM) ? 8 : 16;  // rows per pass
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const unsigned off = 4u * (base + (unsigned)acc_row(r, hi) * ld);
-        nsvd_rmsprop_upd(pv[r], acc[r], sv[r], ev[r], EMA, h);
-        wg_st(o.p, off, pv[r]);
-        wg_st(o.sq, off, sv[r]);
-        if (EMA) wg_st(o.ema, off, ev[r]);
-        if (pl.base) wg_planes_store(pl, r, hi, pv[r]);
+    for (int r0 = 0; r0 < 16; r0 += RH) {
+        float pv[RH], sv[RH], mv[RH], ev[RH];
+#pragma unroll
+        for (int r = 0; r < RH; ++r) {  // at most 32 (two-half rules) or 48 independent loads in flight
+            const unsigned off = 4u * (base + (unsigned)acc_row(r0 + r, hi) * ld);
+            pv[r] = wg_ld(o.p, off);
+            sv[r] = SQ ? wg_ld(o.sq, off) : 0.f;
+            mv[r] = MOM ? wg_ld(mom, off) : 0.f;
+            ev[r] = EMA ? wg_ld(o.ema, off) : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < RH; ++r) {
+            const unsigned off = 4u * (base + (unsigned)acc_row(r0 + r, hi) * ld);
+            nsvd_rule_upd<RULE>(pv[r], acc[r0 + r], sv[r], mv[r], ev[r], EMA, h);
+            wg_st(o.p, off, pv[r]);
+            if (SQ) wg_st(o.sq, off, sv[r]);
+            if (MOM) wg_st(mom, off, mv[r]);
+            if (EMA) wg_st(o.ema, off, ev[r]);
+            if (pl.base) wg_planes_store(pl, r0 + r, hi, pv[r]);
+        }
     }
 }
 
-__device__ __forceinline__ void wg_emit16(const NsvdHyper& h, const WgDst& d, const NsvdOptPtrs& o, size_t base,
-                                          size_t ld, int hi, const f32x16& acc, const WgPlanes pl = WgPlanes{nullptr, 0, 0}) {
+template <int RULE>
+__device__ __forceinline__ void wg_emit16(const HyperOf<RULE>& h, const WgDst& d, const NsvdOptPtrs& o, float* mom,
+                                          size_t base, size_t ld, int hi, const f32x16& acc,
+                                          const WgPlanes pl = WgPlanes{nullptr, 0, 0}) {
     float* g = d.g;
     if (g) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) wg_st(g, 4u * ((unsigned)base + (unsigned)acc_row(r, hi) * (unsigned)ld), acc[r]);
     }
     if (!d.opt) return;
-    if (o.ema) wg_opt16<true>(h, o, (unsigned)base, (unsigned)ld, hi, acc, pl);
-    else wg_opt16<false>(h, o, (unsigned)base, (unsigned)ld, hi, acc, pl);
+    if (o.ema) wg_opt16<RULE, true>(h, o, mom, (unsigned)base, (unsigned)ld, hi, acc, pl);
+    else wg_opt16<RULE, false>(h, o, mom, (unsigned)base, (unsigned)ld, hi, acc, pl);
 }
 
 // stage one 32-row x 32-column (float4 per thread) slab global -> registers
@@ -608,8 +657,10 @@ __device__ __forceinline__ void wg_opt16_apply(const NsvdHyper& h, const NsvdOpt
 // shadow, the state of two blocks prefetched under the K loop (needs the pipelined loop, i.e. >= 4 chunks, and no
 // gradient output). NJ = 2: 128 x 128 tile (hidden units x features); NJ = 1: 128 x 64, chosen by the host when the
 // 128-wide tiles would leave half the CUs without one. The bias gradient db_0 is taken by the C workgroups.
-template <int MODE, int NJ, bool EMIT = false>
-__device__ __forceinline__ void wgrad_tile_A(const WgradArgs& a, const NsvdHyper& h, float* lds, int unit, int slice) {
+// RULE: the optimiser rule of the epilogue (opt_math.h); the prefetching modes exist for RMSprop without momentum only
+template <int MODE, int NJ, bool EMIT = false, int RULE = NSVD_RULE_RMSPROP>
+__device__ __forceinline__ void wgrad_tile_A(const WgradArgs& a, const HyperOf<RULE>& h, float* lds, int unit, int slice) {
+    static_assert(MODE == 0 || RULE == NSVD_RULE_RMSPROP, "state prefetch under the K loop: RMSprop without momentum");
     constexpr int TW = 64 * NJ;  // features per tile
     const int tid = threadIdx.x;
     const int lane = tid & 63, w = tid >> 6;
@@ -630,14 +681,14 @@ __device__ __forceinline__ void wgrad_tile_A(const WgradArgs& a, const NsvdHyper
     const float* a_base = a.dz[0] + (size_t)l * HID * a.B + (size_t)slice * a.Bs;
     const float* b_base = a.phiTc + (size_t)kf0 * a.B + (size_t)slice * a.Bs;
     const size_t o = ((size_t)l * HID + 64 * wm) * a.F + kf0 + 32 * NJ * wn + li;
-    if (MODE == 0) {
+    if constexpr (MODE == 0) {
         nsvd_tile128_dma(a_base, b_base, (unsigned)a.B, (unsigned)a.B, a.Bs / BK, lds, acc);
         const WgDst dW = wg_dst(a, a.gW[0], a.poW[0], slice);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
-                wg_emit16(h, dW, a.oW[0], o + (size_t)(32 * i) * a.F + 32 * j, a.F, hi, acc[i][j],
+                wg_emit16<RULE>(h, dW, a.oW[0], a.mW[0], o + (size_t)(32 * i) * a.F + 32 * j, a.F, hi, acc[i][j],
                           wg_planes_w0(EMIT ? a.w0p : nullptr, l, 2 * wm + i, kf0 + 32 * NJ * wn + 32 * j, a.F / 2, li));
     } else {
         constexpr bool EMA = MODE == 2;
@@ -669,8 +720,8 @@ __device__ __forceinline__ void wgrad_tile_A(const WgradArgs& a, const NsvdHyper
 // dW_i quadrant through the shared C = A B^T tile routine (tile_nt.h): both operands are plain (L, 128, B) rows now
 // that the forward saves activations - no softplus while staging, loads two chunks ahead, four accumulator chains.
 // Needs the slice length to be a multiple of 64 (the 32-chunk form below takes the rest).
-template <bool EMIT = false>
-__device__ __forceinline__ void wgrad_tile_B64(const WgradArgs& a, const NsvdHyper& h, float* lds, int unit, int slice) {
+template <bool EMIT = false, int RULE = NSVD_RULE_RMSPROP>
+__device__ __forceinline__ void wgrad_tile_B64(const WgradArgs& a, const HyperOf<RULE>& h, float* lds, int unit, int slice) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, wv = tid >> 6;
     const int li = lane & 31, hi = lane >> 5;
@@ -688,7 +739,7 @@ __device__ __forceinline__ void wgrad_tile_B64(const WgradArgs& a, const NsvdHyp
     const int b0 = slice * a.Bs;
     if (k0 == 0) nsvd_tile_nt<true>(A, a.B, Bm, a.B, b0, b0 + a.Bs, lds, acc, rs);
     else nsvd_tile_nt<false>(A, a.B, Bm, a.B, b0, b0 + a.Bs, lds, acc, rs);
-    wg_emit16(h, wg_dst(a, a.gW[i], a.poW[i], slice), a.oW[i],
+    wg_emit16<RULE>(h, wg_dst(a, a.gW[i], a.poW[i], slice), a.oW[i], a.mW[i],
               ((size_t)l * HID + n0 + 32 * (wv & 1)) * HID + k0 + 32 * (wv >> 1) + li, HID, hi, acc,
               wg_planes_wh(EMIT ? a.whp : nullptr, i - 1, a.L, l, n0 / 32 + (wv & 1), k0 + 32 * (wv >> 1), li));
     if (k0 == 0) {
@@ -701,13 +752,13 @@ __device__ __forceinline__ void wgrad_tile_B64(const WgradArgs& a, const NsvdHyp
             const WgDst db = wg_dst(a, a.gb[i], a.pob[i], slice);
             const size_t gb = (size_t)l * HID + n0 + (tid >> 4);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) wg_emit1(h, db, a.ob[i], gb + 16 * j, rs[j]);
+            for (int j = 0; j < 4; ++j) wg_emit1<RULE>(h, db, a.ob[i], a.mb[i], gb + 16 * j, rs[j]);
         }
     }
 }
 
-template <bool EMIT = false>
-__device__ __forceinline__ void wgrad_tile_B(const WgradArgs& a, const NsvdHyper& h, float* As, float* Bs, int unit, int slice) {
+template <bool EMIT = false, int RULE = NSVD_RULE_RMSPROP>
+__device__ __forceinline__ void wgrad_tile_B(const WgradArgs& a, const HyperOf<RULE>& h, float* As, float* Bs, int unit, int slice) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, w = tid >> 6;
     const int li = lane & 31, hi = lane >> 5;
@@ -783,7 +834,7 @@ __device__ __forceinline__ void wgrad_tile_B(const WgradArgs& a, const NsvdHyper
 #undef WB_COMPUTE
 #undef WB_LOAD
 #undef WB_STORE
-    wg_emit16(h, wg_dst(a, a.gW[i], a.poW[i], slice), a.oW[i],
+    wg_emit16<RULE>(h, wg_dst(a, a.gW[i], a.poW[i], slice), a.oW[i], a.mW[i],
               ((size_t)l * HID + n0 + 32 * wm) * HID + k0 + 32 * wn + li, HID, hi, acc,
               wg_planes_wh(EMIT ? a.whp : nullptr, i - 1, a.L, l, n0 / 32 + wm, k0 + 32 * wn, li));
     if (k0 == 0) {
@@ -795,13 +846,14 @@ __device__ __forceinline__ void wgrad_tile_B(const WgradArgs& a, const NsvdHyper
         if (s_c4 == 0) {
             const size_t gb = (size_t)l * HID + n0 + s_row;
             const WgDst db = wg_dst(a, a.gb[i], a.pob[i], slice);
-            wg_emit1(h, db, a.ob[i], gb, rs0);
-            wg_emit1(h, db, a.ob[i], gb + 32, rs1);
+            wg_emit1<RULE>(h, db, a.ob[i], a.mb[i], gb, rs0);
+            wg_emit1<RULE>(h, db, a.ob[i], a.mb[i], gb + 32, rs1);
         }
     }
 }
 
-__device__ __forceinline__ void wgrad_tile_C(const WgradArgs& a, const NsvdHyper& h, float* lds, int unit, int slice) {
+template <int RULE = NSVD_RULE_RMSPROP>
+__device__ __forceinline__ void wgrad_tile_C(const WgradArgs& a, const HyperOf<RULE>& h, float* lds, int unit, int slice) {
     const int l = unit >> 2, part = unit & 3;  // 4 workgroups per head: 32 of the 128 rows each
     const int tid = threadIdx.x;
     const int lane = tid & 63, w = tid >> 6;
@@ -824,9 +876,9 @@ __device__ __forceinline__ void wgrad_tile_C(const WgradArgs& a, const NsvdHyper
     }
     __syncthreads();
     if (tid == 0 && part == 0) {
-        wg_emit1(h, wg_dst(a, a.gb[nh], a.pob[nh], slice), a.ob[nh], l, (red[0] + red[1]) + (red[2] + red[3]));
+        wg_emit1<RULE>(h, wg_dst(a, a.gb[nh], a.pob[nh], slice), a.ob[nh], a.mb[nh], l, (red[0] + red[1]) + (red[2] + red[3]));
         if (a.dfsc)
-            wg_emit1(h, wg_dst(a, a.gscales, a.poscales, slice), a.oscales, l,
+            wg_emit1<RULE>(h, wg_dst(a, a.gscales, a.poscales, slice), a.oscales, a.mscales, l,
                      (red[4] + red[5]) + (red[6] + red[7]));
     }
     if (a.loss_part && unit == 0 && slice == 0 && w == 0) {
@@ -846,7 +898,11 @@ __device__ __forceinline__ void wgrad_tile_C(const WgradArgs& a, const NsvdHyper
     }
     if (tid == 0 && unit == 0 && slice == 0) {
         // last kernel of the step (no second pass): nothing in this launch reads `step`
-        if (a.state && a.S == 1) a.state->step += 1;
+        if constexpr (RULE == NSVD_RULE_RMSPROP) {
+            if (a.state && a.S == 1) a.state->step += 1;
+        } else {
+            if (a.ostate_adv && a.S == 1) a.ostate_adv->step += 1;
+        }
     }
     // dW_last[n] = sum_b dbase[b] softplus(z[n][b]): each wave owns 32 rows and walks them 8 at a time so
     // that 8 independent 16-B loads are in flight per lane (a row-at-a-time loop is pure L2 latency)
@@ -885,16 +941,17 @@ __device__ __forceinline__ void wgrad_tile_C(const WgradArgs& a, const NsvdHyper
             if (lane == 8 + j) mine = t0;
         }
         if (lane < 8)
-            wg_emit1(h, wg_dst(a, a.gW[nh], a.poW[nh], slice), a.oW[nh], (size_t)l * HID + n0 + lane, mine);
+            wg_emit1<RULE>(h, wg_dst(a, a.gW[nh], a.poW[nh], slice), a.oW[nh], a.mW[nh], (size_t)l * HID + n0 + lane, mine);
         else if (lane < 16)
-            wg_emit1(h, wg_dst(a, a.gb[0], a.pob[0], slice), a.ob[0], (size_t)l * HID + n0 + lane - 8, mine);
+            wg_emit1<RULE>(h, wg_dst(a, a.gb[0], a.pob[0], slice), a.ob[0], a.mb[0], (size_t)l * HID + n0 + lane - 8, mine);
     }
 }
 
 // NJ: the dW_0 tile shape (2: 128 x 128, 1: 128 x 64 = WgradArgs::tw 64); two kernels rather than one with both shapes
 // inside - with all six tile variants in one function the register allocator spills in the 128 x 128 ones
 // EMIT: bf16x3 steps - the optimiser epilogues of W_0 and W_1 .. also write the bf16 planes of the updated values
-template <int NJ, bool EMIT = false>
+// RULE: the optimiser rule of the epilogues (opt_math.h: NsvdOptRule); RMSprop without momentum is the kernel as it was
+template <int NJ, bool EMIT = false, int RULE = NSVD_RULE_RMSPROP>
 __global__ void __launch_bounds__(256, 2) pmlp_fused_wgrad_kernel(WgradArgs a) {
     __shared__ __attribute__((aligned(16))) float smem_wg[4 * HID * A_LD];  // 72 KB: two blocks per CU
     static_assert(4 * HID * A_LD >= NSVD_TNT_FLOATS, "tile_nt buffers must fit the weight-gradient LDS");
@@ -902,8 +959,14 @@ __global__ void __launch_bounds__(256, 2) pmlp_fused_wgrad_kernel(WgradArgs a) {
     float* As = smem_wg;
     float* Bs = smem_wg + 2 * HID * A_LD;
     // the step's optimiser scalars: launch arguments, or read from the device-resident schedule (uniform loads)
-    NsvdHyper h = a.h;
-    if (a.hstate) h = *nsvd_state_hyper(a.hstate);
+    HyperOf<RULE> h;
+    if constexpr (RULE == NSVD_RULE_RMSPROP) {
+        h = a.h;
+        if (a.hstate) h = *nsvd_state_hyper(a.hstate);
+    } else {
+        h = a.oh;
+        if (a.ostate) h = *nsvd_opt_state_hyper(a.ostate);
+    }
     // grid = S x (nA | nB | 4 L) blocks, kind-major so that the long dW_0 tiles are dispatched first
     int bid = blockIdx.x + a.bid0;
     if (bid < a.nA * a.S) {
@@ -915,20 +978,25 @@ __global__ void __launch_bounds__(256, 2) pmlp_fused_wgrad_kernel(WgradArgs a) {
         const int unit = tl * (a.nA / a.L) + tk;
         // the optimiser state rides under the K loop when the step is fused, nothing else is written and the
         // loop has the four peeled chunks the prefetch hangs on
-        const bool pf = a.S == 1 && a.opt && !a.gW[0] && a.Bs >= 4 * BK;
-        if (!pf) wgrad_tile_A<0, NJ, EMIT>(a, h, smem_wg, unit, slice);
-        else if (a.oW[0].ema) wgrad_tile_A<2, NJ, EMIT>(a, h, smem_wg, unit, slice);
-        else wgrad_tile_A<1, NJ, EMIT>(a, h, smem_wg, unit, slice);
+        if constexpr (RULE == NSVD_RULE_RMSPROP) {
+            const bool pf = a.S == 1 && a.opt && !a.gW[0] && a.Bs >= 4 * BK;
+            if (!pf) wgrad_tile_A<0, NJ, EMIT>(a, h, smem_wg, unit, slice);
+            else if (a.oW[0].ema) wgrad_tile_A<2, NJ, EMIT>(a, h, smem_wg, unit, slice);
+            else wgrad_tile_A<1, NJ, EMIT>(a, h, smem_wg, unit, slice);
+        } else {
+            // (the other rules take their state in the epilogue: no prefetch under the K loop)
+            wgrad_tile_A<0, NJ, EMIT, RULE>(a, h, smem_wg, unit, slice);
+        }
         return;
     }
     bid -= a.nA * a.S;
     if (bid < a.nB * a.S) {
-        if (a.Bs % NSVD_TNT_KC == 0) wgrad_tile_B64<EMIT>(a, h, smem_wg, bid % a.nB, bid / a.nB);
-        else wgrad_tile_B<EMIT>(a, h, As, Bs, bid % a.nB, bid / a.nB);
+        if (a.Bs % NSVD_TNT_KC == 0) wgrad_tile_B64<EMIT, RULE>(a, h, smem_wg, bid % a.nB, bid / a.nB);
+        else wgrad_tile_B<EMIT, RULE>(a, h, As, Bs, bid % a.nB, bid / a.nB);
         return;
     }
     bid -= a.nB * a.S;
-    wgrad_tile_C(a, h, As, bid % (4 * a.L), bid / (4 * a.L));
+    wgrad_tile_C<RULE>(a, h, As, bid % (4 * a.L), bid / (4 * a.L));
 }
 
 // Split-K second pass: gradient = sum of the S partial slices (in slice order), then stored and / or applied
@@ -943,11 +1011,22 @@ struct ReduceArgs {
     NsvdOptPtrs o[2 * NSVD_MAX_LAYERS + 1];
     size_t total4;  // float4 groups over all tensors
     nsvd_step_state* state;  // device-resident schedule (or null): h from state->cur, step incremented here
+    NsvdOptHyper oh;         // rules other than RMSprop without momentum: scalars / device-resident schedule
+    nsvd_opt_state* ostate;
+    float* m[2 * NSVD_MAX_LAYERS + 1];  // their `mom` slot, tensor by tensor as o[]
 };
 
+template <int RULE = NSVD_RULE_RMSPROP>
 __global__ void __launch_bounds__(256) wgrad_reduce_kernel(ReduceArgs a) {
-    NsvdHyper h = a.h;
-    if (a.state) h = *nsvd_state_hyper(a.state);
+    constexpr bool SQ = nsvd_rule_uses_sq(RULE), MOM = nsvd_rule_uses_mom(RULE);
+    HyperOf<RULE> h;
+    if constexpr (RULE == NSVD_RULE_RMSPROP) {
+        h = a.h;
+        if (a.state) h = *nsvd_state_hyper(a.state);
+    } else {
+        h = a.oh;
+        if (a.ostate) h = *nsvd_opt_state_hyper(a.ostate);
+    }
     for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < a.total4; q += (size_t)gridDim.x * 256) {
         // tensors are laid out back to back (padded to 4 floats) inside a slice: find the one holding group q
         int t = 0;
@@ -967,15 +1046,20 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(ReduceArgs a) {
             // the common case as 16-byte accesses (one group of four per thread: 4-byte accesses 16 bytes apart use a
             // quarter of every line per instruction)
             const NsvdOptPtrs& o = a.o[t];
-            if ((((uintptr_t)(o.p + e) | (uintptr_t)(o.sq + e) | (uintptr_t)(o.ema ? o.ema + e : o.p + e)) & 15) == 0) {
-                float4 pv = *reinterpret_cast<const float4*>(o.p + e), sv = *reinterpret_cast<const float4*>(o.sq + e);
-                float4 ev = o.ema ? *reinterpret_cast<const float4*>(o.ema + e) : make_float4(0.f, 0.f, 0.f, 0.f);
-                nsvd_rmsprop_upd(pv.x, gv[0], sv.x, ev.x, o.ema != nullptr, h);
-                nsvd_rmsprop_upd(pv.y, gv[1], sv.y, ev.y, o.ema != nullptr, h);
-                nsvd_rmsprop_upd(pv.z, gv[2], sv.z, ev.z, o.ema != nullptr, h);
-                nsvd_rmsprop_upd(pv.w, gv[3], sv.w, ev.w, o.ema != nullptr, h);
+            if ((((uintptr_t)(o.p + e) | (uintptr_t)(SQ ? o.sq + e : o.p + e) | (uintptr_t)(MOM ? a.m[t] + e : o.p + e) |
+                  (uintptr_t)(o.ema ? o.ema + e : o.p + e)) & 15) == 0) {
+                const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                float4 pv = *reinterpret_cast<const float4*>(o.p + e);
+                float4 sv = SQ ? *reinterpret_cast<const float4*>(o.sq + e) : zero4;
+                float4 mv = MOM ? *reinterpret_cast<const float4*>(a.m[t] + e) : zero4;
+                float4 ev = o.ema ? *reinterpret_cast<const float4*>(o.ema + e) : zero4;
+                nsvd_rule_upd<RULE>(pv.x, gv[0], sv.x, mv.x, ev.x, o.ema != nullptr, h);
+                nsvd_rule_upd<RULE>(pv.y, gv[1], sv.y, mv.y, ev.y, o.ema != nullptr, h);
+                nsvd_rule_upd<RULE>(pv.z, gv[2], sv.z, mv.z, ev.z, o.ema != nullptr, h);
+                nsvd_rule_upd<RULE>(pv.w, gv[3], sv.w, mv.w, ev.w, o.ema != nullptr, h);
                 *reinterpret_cast<float4*>(o.p + e) = pv;
-                *reinterpret_cast<float4*>(o.sq + e) = sv;
+                if (SQ) *reinterpret_cast<float4*>(o.sq + e) = sv;
+                if (MOM) *reinterpret_cast<float4*>(a.m[t] + e) = mv;
                 if (o.ema) *reinterpret_cast<float4*>(o.ema + e) = ev;
                 continue;
             }
@@ -984,15 +1068,34 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(ReduceArgs a) {
             if (a.g[t]) a.g[t][e + c] = gv[c];
             if (a.opt) {
                 const NsvdOptPtrs& o = a.o[t];
-                float pv = o.p[e + c], sv = o.sq[e + c], ev = o.ema ? o.ema[e + c] : 0.f;
-                nsvd_rmsprop_upd(pv, gv[c], sv, ev, o.ema != nullptr, h);
+                float pv = o.p[e + c], sv = SQ ? o.sq[e + c] : 0.f, mv = MOM ? a.m[t][e + c] : 0.f;
+                float ev = o.ema ? o.ema[e + c] : 0.f;
+                nsvd_rule_upd<RULE>(pv, gv[c], sv, mv, ev, o.ema != nullptr, h);
                 o.p[e + c] = pv;
-                o.sq[e + c] = sv;
+                if (SQ) o.sq[e + c] = sv;
+                if (MOM) a.m[t][e + c] = mv;
                 if (o.ema) o.ema[e + c] = ev;
             }
         }
     }
-    if (a.state && blockIdx.x == 0 && threadIdx.x == 0) a.state->step += 1;  // last kernel of the step
+    // last kernel of the step
+    if constexpr (RULE == NSVD_RULE_RMSPROP) {
+        if (a.state && blockIdx.x == 0 && threadIdx.x == 0) a.state->step += 1;
+    } else {
+        if (a.ostate && blockIdx.x == 0 && threadIdx.x == 0) a.ostate->step += 1;
+    }
+}
+
+// the weight-gradient / second-pass launches of one rule
+template <int RULE>
+void launch_wgrad(const WgradArgs& wa, bool emit, dim3 wgrid, hipStream_t s) {
+    if (wa.tw == 64) {
+        if (emit) hipLaunchKernelGGL((pmlp_fused_wgrad_kernel<1, true, RULE>), wgrid, dim3(256), 0, s, wa);
+        else hipLaunchKernelGGL((pmlp_fused_wgrad_kernel<1, false, RULE>), wgrid, dim3(256), 0, s, wa);
+    } else {
+        if (emit) hipLaunchKernelGGL((pmlp_fused_wgrad_kernel<2, true, RULE>), wgrid, dim3(256), 0, s, wa);
+        else hipLaunchKernelGGL((pmlp_fused_wgrad_kernel<2, false, RULE>), wgrid, dim3(256), 0, s, wa);
+    }
 }
 #undef WG_LD
 #undef WG_ST
@@ -1064,6 +1167,7 @@ static int fused_backward_impl(const nsvd_model_desc& dfull, const nsvd_params& 
         a.feat.fB = p.fourier_B; a.feat.phi = wn.phi; a.feat.phiTc = wn.phiTc; a.feat.sctab = wn.sctab;
         a.feat.B = B; a.feat.m = d.m; a.feat.D = d.D; a.feat.eps = next->eps;
         if (opt && opt->state) a.feat.smp.offset_add = (const unsigned long long*)&opt->state->step;
+        else if (opt && opt->ostate) a.feat.smp.offset_add = (const unsigned long long*)&opt->ostate->step;
         a.feat_nx = (d.m + nsvd_feat::FJ - 1) / nsvd_feat::FJ;
         a.feat_blocks = a.feat_nx * ((B + nsvd_feat::FB - 1) / nsvd_feat::FB);
         chain_grid += a.feat_blocks;
@@ -1121,15 +1225,25 @@ static int fused_backward_impl(const nsvd_model_desc& dfull, const nsvd_params& 
     wa.dfsc = d.has_exp_mask ? w.dfsc + offv : nullptr;
     wa.gscales = (d.has_exp_mask && g.scales) ? g.scales + l0 : nullptr;
     wa.nlayers = d.nlayers; wa.B = B; wa.L = d.L; wa.F = F;
+    const int rule = opt ? opt->rule : NSVD_RULE_RMSPROP;
+    if (rule < 0 || rule >= NSVD_RULE_COUNT) return NSVD_EINVAL;
     if (opt) {
         wa.opt = 1;
         wa.h = opt->h;
+        wa.oh = opt->oh;
+        auto at = [](float* q, size_t o) { return q ? q + o : nullptr; };  // (slots a rule has none of stay null)
         for (int i = 0; i < d.nlayers; ++i) {
-            wa.oW[i] = NsvdOptPtrs{p.W[i] + offW(i), opt->sq.W[i] + offW(i), opt->ema ? opt->ema->W[i] + offW(i) : nullptr};
-            wa.ob[i] = NsvdOptPtrs{p.b[i] + offb(i), opt->sq.b[i] + offb(i), opt->ema ? opt->ema->b[i] + offb(i) : nullptr};
+            wa.oW[i] = NsvdOptPtrs{p.W[i] + offW(i), at(opt->sq.W[i], offW(i)), opt->ema ? opt->ema->W[i] + offW(i) : nullptr};
+            wa.ob[i] = NsvdOptPtrs{p.b[i] + offb(i), at(opt->sq.b[i], offb(i)), opt->ema ? opt->ema->b[i] + offb(i) : nullptr};
+            wa.mW[i] = opt->mom ? at(opt->mom->W[i], offW(i)) : nullptr;
+            wa.mb[i] = opt->mom ? at(opt->mom->b[i], offb(i)) : nullptr;
         }
-        if (d.has_exp_mask)
-            wa.oscales = NsvdOptPtrs{p.scales + l0, opt->sq.scales + l0, opt->ema ? opt->ema->scales + l0 : nullptr};
+        if (d.has_exp_mask) {
+            wa.oscales = NsvdOptPtrs{p.scales + l0, at(opt->sq.scales, l0), opt->ema ? opt->ema->scales + l0 : nullptr};
+            wa.mscales = opt->mom ? at(opt->mom->scales, l0) : nullptr;
+        }
+        wa.ostate = opt->ostate;
+        wa.ostate_adv = (win && win->not_last) ? nullptr : opt->ostate;
     }
     wa.state = (win && win->not_last) ? nullptr : state;  // (the optimiser reads the schedule through wa.hstate)
     wa.hstate = state;
@@ -1173,12 +1287,14 @@ static int fused_backward_impl(const nsvd_model_desc& dfull, const nsvd_params& 
     const dim3 wgrid(wa.S * (wa.nA + wa.nB + 4 * d.L));
     if (SS) {
         // (the streaming kernel has written every slice)
-    } else if (wa.tw == 64) {
-        if (emit) hipLaunchKernelGGL((pmlp_fused_wgrad_kernel<1, true>), wgrid, dim3(256), 0, s, wa);
-        else hipLaunchKernelGGL(pmlp_fused_wgrad_kernel<1>, wgrid, dim3(256), 0, s, wa);
     } else {
-        if (emit) hipLaunchKernelGGL((pmlp_fused_wgrad_kernel<2, true>), wgrid, dim3(256), 0, s, wa);
-        else hipLaunchKernelGGL(pmlp_fused_wgrad_kernel<2>, wgrid, dim3(256), 0, s, wa);
+        switch (rule) {
+            case NSVD_RULE_RMSPROP: launch_wgrad<NSVD_RULE_RMSPROP>(wa, emit, wgrid, s); break;
+            case NSVD_RULE_RMSPROP_MOM: launch_wgrad<NSVD_RULE_RMSPROP_MOM>(wa, emit, wgrid, s); break;
+            case NSVD_RULE_SGD: launch_wgrad<NSVD_RULE_SGD>(wa, emit, wgrid, s); break;
+            case NSVD_RULE_SGD_MOM: launch_wgrad<NSVD_RULE_SGD_MOM>(wa, emit, wgrid, s); break;
+            default: launch_wgrad<NSVD_RULE_ADAM>(wa, emit, wgrid, s); break;
+        }
     }
     NSVD_CHECK_LAUNCH();
     if (wa.S == 1 && !SS) return 0;
@@ -1190,22 +1306,31 @@ static int fused_backward_impl(const nsvd_model_desc& dfull, const nsvd_params& 
     ra.opt = wa.opt;
     ra.h = wa.h;
     ra.state = state;
+    ra.oh = wa.oh;
+    ra.ostate = wa.ostate;
     int t = 0;
     for (int i = 0; i < d.nlayers; ++i, ++t) {
-        ra.off[t] = pl.oW[i]; ra.n[t] = pl.nW[i]; ra.g[t] = g.W[i]; ra.o[t] = wa.oW[i];
+        ra.off[t] = pl.oW[i]; ra.n[t] = pl.nW[i]; ra.g[t] = g.W[i]; ra.o[t] = wa.oW[i]; ra.m[t] = wa.mW[i];
     }
     for (int i = 0; i < d.nlayers; ++i, ++t) {
-        ra.off[t] = pl.ob[i]; ra.n[t] = pl.nb[i]; ra.g[t] = g.b[i]; ra.o[t] = wa.ob[i];
+        ra.off[t] = pl.ob[i]; ra.n[t] = pl.nb[i]; ra.g[t] = g.b[i]; ra.o[t] = wa.ob[i]; ra.m[t] = wa.mb[i];
     }
     if (d.has_exp_mask) {
-        ra.off[t] = pl.oscales; ra.n[t] = pl.nscales; ra.g[t] = g.scales; ra.o[t] = wa.oscales;
+        ra.off[t] = pl.oscales; ra.n[t] = pl.nscales; ra.g[t] = g.scales; ra.o[t] = wa.oscales; ra.m[t] = wa.mscales;
         ++t;
     }
     ra.ntensors = t;
     ra.total4 = (pl.oscales + (pl.nscales + 3) / 4 * 4) / 4;
     size_t blocks = (ra.total4 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ra);
+    const dim3 rgrid((unsigned)blocks);
+    switch (rule) {
+        case NSVD_RULE_RMSPROP: hipLaunchKernelGGL(wgrad_reduce_kernel<NSVD_RULE_RMSPROP>, rgrid, dim3(256), 0, s, ra); break;
+        case NSVD_RULE_RMSPROP_MOM: hipLaunchKernelGGL(wgrad_reduce_kernel<NSVD_RULE_RMSPROP_MOM>, rgrid, dim3(256), 0, s, ra); break;
+        case NSVD_RULE_SGD: hipLaunchKernelGGL(wgrad_reduce_kernel<NSVD_RULE_SGD>, rgrid, dim3(256), 0, s, ra); break;
+        case NSVD_RULE_SGD_MOM: hipLaunchKernelGGL(wgrad_reduce_kernel<NSVD_RULE_SGD_MOM>, rgrid, dim3(256), 0, s, ra); break;
+        default: hipLaunchKernelGGL(wgrad_reduce_kernel<NSVD_RULE_ADAM>, rgrid, dim3(256), 0, s, ra); break;
+    }
     NSVD_CHECK_LAUNCH();
     return 0;
 }

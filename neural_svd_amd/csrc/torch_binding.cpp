@@ -11,6 +11,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
+#include <string.h>
 #include <string>
 #include <vector>
 
@@ -276,6 +277,26 @@ void rmsprop_ema_step(at::Tensor p, const at::Tensor& grad, at::Tensor sq, c10::
              "nsvd_rmsprop_ema_step");
 }
 
+// one step of any optimiser rule of examples/utils.py:48-72 + the torch_ema update (nsvd_opt_step); kind: NSVD_OPT_*
+void opt_step(int64_t kind, at::Tensor p, const at::Tensor& grad, c10::optional<at::Tensor> sq,
+              c10::optional<at::Tensor> mom, c10::optional<at::Tensor> ema, double lr, double alpha, double eps,
+              double momentum, double beta1, double beta2, double ema_decay, int64_t steps_taken, double grad_scale) {
+    Dev dv;
+    const size_t n = (size_t)p.numel();
+    TORCH_CHECK((size_t)grad.numel() == n && (!sq.has_value() || (size_t)sq->numel() == n) &&
+                    (!mom.has_value() || (size_t)mom->numel() == n) && (!ema.has_value() || (size_t)ema->numel() == n),
+                "opt_step: size mismatch");
+    nsvd_opt_config c;
+    memset(&c, 0, sizeof(c));
+    c.kind = (int32_t)kind;
+    c.lr = lr; c.alpha = alpha; c.eps = eps; c.momentum = momentum; c.beta1 = beta1; c.beta2 = beta2;
+    c.ema_decay = ema_decay;
+    float *pp = f32(dv, p, "p"), *gp = f32(dv, grad, "grad");
+    check_rc(nsvd_opt_step(pp, gp, f32_opt(dv, sq, "sq"), f32_opt(dv, mom, "mom"), f32_opt(dv, ema, "ema"), n, &c,
+                           (unsigned long long)steps_taken, grad_scale, dv.stream()),
+             "nsvd_opt_step");
+}
+
 void spectrum_accumulate(const at::Tensor& f, const at::Tensor& Tf, const at::Tensor& x, double sigma,
                          bool use_importance, double lim, at::Tensor cov, at::Tensor quad) {
     Dev dv;
@@ -354,7 +375,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                         "nsvd_operator_forward", "nsvd_operator_backward",
                                         "nsvd_operator_sample_features", "nsvd_operator_sample_features_dev",
                                         "nsvd_evd_moments", "nsvd_evd_loss_grad", "nsvd_operator_backward_evd_step",
-                                        "nsvd_operator_backward_evd_step_next", "nsvd_rmsprop_ema_step",
+                                        "nsvd_operator_backward_evd_step_next", "nsvd_rmsprop_ema_step", "nsvd_opt_step",
                                         "nsvd_spectrum_accumulate", "nsvd_retrieval_eval",
                                         "nsvd_retrieval_workspace_bytes", "nsvd_retrieval_max_gallery",
                                         "nsvd_retrieval_max_k", "nsvd_retrieval_max_d"};
@@ -378,6 +399,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("evd_loss_grad", &evd_loss_grad);
     m.def("operator_backward_evd_step", &operator_backward_evd_step);
     m.def("rmsprop_ema_step", &rmsprop_ema_step);
+    m.def("opt_step", &opt_step);
     m.def("spectrum_accumulate", &spectrum_accumulate);
     m.def("retrieval_eval", &retrieval_eval);
     m.def("retrieval_workspace_bytes",

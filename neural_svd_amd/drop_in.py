@@ -131,6 +131,10 @@ def _comm_from_env(device):
     return Communicator.from_env(torch.device(device), backend=os.environ.get("NSVD_DIST_BACKEND"))
 
 
+def _plain_rmsprop(args) -> bool:
+    return args.optimizer == "rmsprop" and float(getattr(args, "momentum", 0.0)) == 0.0
+
+
 def _fused_loop_trainer(args, method, operator, importance_train, device, comm=None):
     """A FusedTrainer over the SAME weights when the configuration is one it implements, else None."""
     from .models import WaveFunctions
@@ -139,8 +143,11 @@ def _fused_loop_trainer(args, method, operator, importance_train, device, comm=N
     from .trainer import FusedTrainer
     if not getattr(args, "fused_loop", True):
         return None
-    if args.optimizer != "rmsprop" or float(getattr(args, "momentum", 0.0)) != 0.0:
-        return None
+    if not _plain_rmsprop(args):
+        # the other optimisers of get_optimizer: opt-in (args.fused_optimizers), one process only
+        if not getattr(args, "fused_optimizers", False) or comm is not None or \
+                args.optimizer not in ("rmsprop", "adam", "sgd"):
+            return None
     if not (isinstance(method, NestedLoRA) and isinstance(method.model, WaveFunctions)) or method.sort_indices is not None:
         return None
     if not isinstance(operator, OperatorWrapper) or \
@@ -192,7 +199,17 @@ def _make_fused(FusedTrainer, args, method, model, operator, importance_train, s
                         use_lr_scheduler=bool(args.use_lr_scheduler), sampling_scale=importance_train.sigma, seed=0,
                         device=device, path=method.path, device_sampler=False, comm=comm, parallelism=parallelism,
                         sync_collectives=True,
-                        exp_mask_init=1.0 if model.has_exp_mask else None)  # initial values: replaced by the caller
+                        exp_mask_init=1.0 if model.has_exp_mask else None,  # initial values: replaced by the caller
+                        **_optimizer_kwargs(args))
+
+
+def _optimizer_kwargs(args):
+    """FusedTrainer's optimiser arguments for get_optimizer(args, ...); none for RMSprop without momentum (the
+    trainer's defaults, constructed exactly as before)"""
+    if _plain_rmsprop(args):
+        return {}
+    return dict(optimizer=args.optimizer, momentum=float(getattr(args, "momentum", 0.0)) if args.optimizer != "adam" else 0.0,
+                adam_eps=float(getattr(args, "adam_eps", 1e-8)))
 
 
 class CaptureUnavailable(RuntimeError):
@@ -220,14 +237,41 @@ class CapturedPlainStep:
         self.device = torch.device(device)
         self.params = [p for p in method.parameters() if p.requires_grad]
         assert len(self.params) == len(ema.shadow_params)
-        self.state = H.StepState(self.device, args.lr, args.num_iters if args.use_lr_scheduler else 0,
-                                 args.rmsprop_decay, 1e-10, args.ema_decay)
-        for p in self.params:  # torch.optim.RMSprop's state layout, created up front (it is lazy)
-            st = optimizer.state[p]
-            if "square_avg" not in st:
-                st["step"] = torch.tensor(0.0)
-                st["square_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        self.sq = [optimizer.state[p]["square_avg"] for p in self.params]
+        T_max = args.num_iters if args.use_lr_scheduler else 0
+        self.other_rule = not _plain_rmsprop(args)
+        zeros = lambda p: torch.zeros_like(p, memory_format=torch.preserve_format)  # noqa: E731
+        if not self.other_rule:
+            self.state = H.StepState(self.device, args.lr, T_max, args.rmsprop_decay, 1e-10, args.ema_decay)
+            for p in self.params:  # torch.optim.RMSprop's state layout, created up front (it is lazy)
+                st = optimizer.state[p]
+                if "square_avg" not in st:
+                    st["step"] = torch.tensor(0.0)
+                    st["square_avg"] = zeros(p)
+            self.sq = [optimizer.state[p]["square_avg"] for p in self.params]
+            self.mom = [None] * len(self.params)
+        else:
+            # the other optimisers of get_optimizer (args.fused_optimizers): one launch per tensor of nsvd_opt_step_dev,
+            # the state in torch.optim's own tensors and under its own keys (torch/optim/{rmsprop,adam,sgd}.py)
+            kw = _optimizer_kwargs(args)
+            cfg = H.opt_config(args.optimizer, args.lr, args.rmsprop_decay,
+                               kw["adam_eps"] if args.optimizer == "adam" else 1e-10, kw["momentum"],
+                               ema_decay=args.ema_decay)
+            uses_sq, uses_mom = H.opt_uses(cfg)
+            sq_key, mom_key = ("exp_avg_sq", "exp_avg") if args.optimizer == "adam" else ("square_avg", "momentum_buffer")
+            taken = 0
+            for p in self.params:
+                st = optimizer.state[p]
+                if args.optimizer != "sgd" and "step" not in st:
+                    st["step"] = torch.tensor(0.0)
+                if uses_sq and sq_key not in st:
+                    st[sq_key] = zeros(p)
+                if uses_mom and st.get(mom_key) is None:
+                    st[mom_key] = zeros(p)
+                if "step" in st:
+                    taken = int(st["step"])
+            self.sq = [optimizer.state[p][sq_key] if uses_sq else None for p in self.params]
+            self.mom = [optimizer.state[p][mom_key] if uses_mom else None for p in self.params]
+            self.state = H.OptState(self.device, cfg, T_max, step=taken)
         self.x = None
         self.graph = None
         self.loss = None
@@ -246,7 +290,12 @@ class CapturedPlainStep:
             # a trainable parameter the loss does not reach (torch's RMSprop would skip it): nothing has been updated
             # yet - the caller takes this and every later step with the eager plain loop
             raise CaptureUnavailable("a trainable parameter received no gradient")
-        for i, (p, sq, sh) in enumerate(zip(self.params, self.sq, self.ema.shadow_params)):
+        flat = lambda t: None if t is None else t.view(-1)  # noqa: E731
+        for i, (p, sq, mb, sh) in enumerate(zip(self.params, self.sq, self.mom, self.ema.shadow_params)):
+            if self.other_rule:
+                H.opt_step_dev(p.data.view(-1), p.grad.view(-1), flat(sq), flat(mb), sh.view(-1), self.state, 1.0,
+                               advance=(i == n - 1))
+                continue
             H.rmsprop_ema_step_dev(p.data.view(-1), p.grad.view(-1), sq.view(-1), sh.view(-1), self.state, 1.0,
                                    advance=(i == n - 1))
         self.total += loss.detach()
@@ -286,7 +335,8 @@ class CapturedPlainStep:
         """the torch objects' Python-side counters <- the steps taken (their tensors were updated in place)"""
         from .trainer import cosine_lr
         for p in self.params:
-            self.optimizer.state[p]["step"] = torch.tensor(float(self.steps))
+            if "step" in self.optimizer.state[p]:  # (torch.optim.SGD keeps none)
+                self.optimizer.state[p]["step"] = torch.tensor(float(self.steps))
         self.ema.num_updates = self.steps
         if self.args.use_lr_scheduler:
             self.scheduler.last_epoch = self.steps
@@ -303,8 +353,9 @@ def _captured_plain_step(args, method, operator, importance_train, optimizer, sc
     from .operators import OperatorWrapper
     if not getattr(args, "graph_loop", True) or torch.device(device).type != "cuda":
         return None
-    if args.optimizer != "rmsprop" or float(getattr(args, "momentum", 0.0)) != 0.0:
-        return None
+    if not _plain_rmsprop(args) and not (getattr(args, "fused_optimizers", False) and
+                                         args.optimizer in ("rmsprop", "adam", "sgd")):
+        return None  # (the other optimisers are opt-in: args.fused_optimizers)
     if not isinstance(method, (NestedLoRA, NeuralEigenfunctions)) or not isinstance(operator, OperatorWrapper):
         return None
     if isinstance(method, NestedLoRA) and _mask_kind(method.vector_mask, method.matrix_mask) == H.MASK_CUSTOM:
@@ -325,14 +376,26 @@ def _refresh_from_trainer(tr, method, ema, optimizer, scheduler):
 
     whole = tr.gather_heads_tensor  # heads sharded: every rank's slice of a tensor -> the (L, ...) tensor, on every rank
 
-    for n, w, e, q in zip(tr.P.names, tr.P.views(tr.P.flat), tr.P.views(tr.P.ema), tr.P.views(tr.P.sq)):
+    moms = tr.P.views(tr.P.mom) if tr.P.mom is not None else [None] * len(tr.P.names)
+    for n, w, e, q, mb in zip(tr.P.names, tr.P.views(tr.P.flat), tr.P.views(tr.P.ema), tr.P.views(tr.P.sq), moms):
         w, e, q = whole(w), whole(e), whole(q)
         p = named[n]
         p.data.copy_(w.view_as(p))
         shadow[id(p)].copy_(e.view_as(p))
         st = optimizer.state[p]
-        st["step"] = torch.tensor(float(tr.t))
-        st["square_avg"] = q.view_as(p).clone()
+        # torch.optim's own keys (torch/optim/{rmsprop,adam,sgd}.py): SGD keeps no step counter, and no state at all
+        # without momentum
+        if tr.optimizer == "rmsprop":
+            st["step"] = torch.tensor(float(tr.t))
+            st["square_avg"] = q.view_as(p).clone()
+            if mb is not None:
+                st["momentum_buffer"] = mb.view_as(p).clone()
+        elif tr.optimizer == "adam":
+            st["step"] = torch.tensor(float(tr.t))
+            st["exp_avg"] = mb.view_as(p).clone()
+            st["exp_avg_sq"] = q.view_as(p).clone()
+        elif mb is not None:
+            st["momentum_buffer"] = mb.view_as(p).clone()
     ema.num_updates = tr.num_updates
     if tr.use_sched:
         from .trainer import cosine_lr
@@ -407,7 +470,8 @@ def train_operator(args, method, operator, make_batch_ftn_train, val_data, batch
         captured = _captured_plain_step(args, method, operator, importance_train, optimizer, scheduler, ema, device)
     if comm is not None and fused is None:
         raise NotImplementedError("several ranks (WORLD_SIZE > 1) need the fused loop: this configuration is not one "
-                                  "it implements (rmsprop without momentum, NestedLoRA on WaveFunctions, GPU)")
+                                  "it implements (rmsprop without momentum - adam, sgd and momentum run on one GPU "
+                                  "only, with args.fused_optimizers -, NestedLoRA on WaveFunctions, GPU)")
     rank0 = comm is None or comm.rank == 0
     # per-GPU batch = args.batch_size (weak scaling). Heads sharded: every rank steps on the SAME global batch of
     # world x batch_size rows - the sampler is called world times per step, and equally seeded ranks draw equal rows.

@@ -677,6 +677,58 @@ def operator_backward_evd_step_next(shape: ModelShape, params: Params, prob: Pro
     check(rc, "nsvd_operator_backward_evd_step_next")
 
 
+def optimizer_state(cfg: "_lib.OptConfig", sq: Optional[Params], mom: Optional[Params], ema: Optional[Params],
+                    steps_taken: int = 0, lr: Optional[float] = None, ema_decay: Optional[float] = None,
+                    state: Optional["OptState"] = None) -> "_lib.Optimizer":
+    """nsvd_optimizer for operator_backward_evd_opt_step; sq / mom / ema are pack_params() sets in the parameters'
+    layouts (None for slots the rule has none of); lr / ema_decay: the step's scheduled values when they differ from
+    cfg's; state: the device-resident schedule - the step's scalars are then derived (and advanced) on the device."""
+    o = _lib.Optimizer()
+    o.cfg = cfg
+    if lr is not None:
+        o.cfg.lr = float(lr)
+    if ema_decay is not None:
+        o.cfg.ema_decay = float(ema_decay)
+    if sq is not None:
+        o.sq = sq
+    if mom is not None:
+        o.mom = mom
+    if ema is not None:
+        o.ema = ema
+    o.has_ema = int(ema is not None)
+    o.steps_taken = int(steps_taken)
+    o.state = state.ptr if state is not None else None
+    o._keepalive = (sq, mom, ema, state)
+    return o
+
+
+def operator_backward_evd_opt_step(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor,
+                                   f: torch.Tensor, Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor],
+                                   M: Optional[torch.Tensor], moments: Optional[torch.Tensor], moments_reduced: bool,
+                                   evd_scratch: Optional[torch.Tensor], loss: torch.Tensor, grads: Optional[Params],
+                                   opt: "_lib.Optimizer", ws: torch.Tensor, grad_scale: float = 1.0,
+                                   path: int = PATH_AUTO, l_offset: int = 0, next_seed: int = 0, next_offset: int = 0,
+                                   x_next: Optional[torch.Tensor] = None, ws_next: Optional[torch.Tensor] = None) -> None:
+    """operator_backward_evd_step for any optimiser rule (nsvd_operator_backward_evd_opt_step); with x_next / ws_next
+    the next batch's draw and features ride along as in operator_backward_evd_step_next (MFMA path only)."""
+    B = x.shape[0]
+    L_total = f.shape[1]
+    if tuple(Tf.shape) != (B, L_total) or L_total < shape.L or \
+            (moments is not None and moments.numel() != 2 * L_total * L_total + 1) or \
+            (x_next is not None and (ws_next is None or tuple(x_next.shape) != tuple(x.shape))):
+        raise NsvdError("operator_backward_evd_opt_step: f/Tf (B, L_total), moments 2*L_total^2+1, x_next like x")
+    d = shape.desc()
+    rc = _lib.load().nsvd_operator_backward_evd_opt_step(
+        C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(f, "f"), _ptr(Tf, "Tf"), int(mask_kind),
+        _ptr(v, "v"), _ptr(M, "M"), _ptr(moments, "moments"), int(bool(moments_reduced)),
+        evd_scratch.data_ptr() if evd_scratch is not None else None, int(L_total), int(l_offset),
+        float(grad_scale), _ptr(loss, "loss"), C.byref(grads) if grads is not None else None, C.byref(opt),
+        ws.data_ptr(), ws.numel(), int(path), int(next_seed) & (2 ** 64 - 1), int(next_offset) & (2 ** 64 - 1),
+        _ptr(x_next, "x_next"), ws_next.data_ptr() if ws_next is not None else None,
+        ws_next.numel() if ws_next is not None else 0, _stream())
+    check(rc, "nsvd_operator_backward_evd_opt_step")
+
+
 def model_backward_evd_step(shape: ModelShape, params: Params, x: torch.Tensor, f: torch.Tensor, Tf: torch.Tensor,
                             mask_kind: int, v: Optional[torch.Tensor], M: Optional[torch.Tensor],
                             moments: torch.Tensor, moments_reduced: bool, evd_scratch: Optional[torch.Tensor],
@@ -790,6 +842,99 @@ def rmsprop_ema_step_dev(p: torch.Tensor, grad: torch.Tensor, sq: torch.Tensor, 
     rc = _lib.load().nsvd_rmsprop_ema_step_dev(_ptr(p, "p"), _ptr(grad, "grad"), _ptr(sq, "sq"), _ptr(ema, "ema"), n,
                                                state.ptr, float(grad_scale), int(bool(advance)), _stream())
     check(rc, "nsvd_rmsprop_ema_step_dev")
+
+
+OPTIMIZER_KINDS = {"rmsprop": _lib.OPT_RMSPROP, "sgd": _lib.OPT_SGD, "adam": _lib.OPT_ADAM}
+
+
+def opt_config(optimizer: str, lr: float, alpha: float = 0.99, eps: float = 1e-10, momentum: float = 0.0,
+               betas: Tuple[float, float] = (0.9, 0.999), ema_decay: float = 0.0) -> _lib.OptConfig:
+    """nsvd_opt_config of one of the reference's optimisers (examples/utils.py:48-72): "rmsprop" | "adam" | "sgd";
+    eps is RMSprop's (1e-10 in the reference) or Adam's (--adam_eps)."""
+    if optimizer not in OPTIMIZER_KINDS:
+        raise NsvdError(f"unknown optimizer {optimizer!r}: one of {sorted(OPTIMIZER_KINDS)}")
+    c = _lib.OptConfig()
+    c.kind = OPTIMIZER_KINDS[optimizer]
+    c.lr, c.alpha, c.eps, c.momentum = float(lr), float(alpha), float(eps), float(momentum)
+    c.beta1, c.beta2 = float(betas[0]), float(betas[1])
+    c.ema_decay = float(ema_decay)
+    return c
+
+
+def opt_uses(cfg: _lib.OptConfig) -> Tuple[bool, bool]:
+    """(uses the sq slot, uses the mom slot) of cfg's rule"""
+    if cfg.kind == _lib.OPT_ADAM:
+        return True, True
+    if cfg.kind == _lib.OPT_RMSPROP:
+        return True, cfg.momentum != 0.0
+    return False, cfg.momentum != 0.0
+
+
+def _opt_sizes(what, p, grad, sq, mom, ema):
+    n = p.numel()
+    for t in (grad, sq, mom, ema):
+        if t is not None and t.numel() != n:
+            raise NsvdError(f"{what}: size mismatch")
+    return n
+
+
+def opt_step(cfg: _lib.OptConfig, p: torch.Tensor, grad: torch.Tensor, sq: Optional[torch.Tensor],
+             mom: Optional[torch.Tensor], ema: Optional[torch.Tensor], steps_taken: int, lr: Optional[float] = None,
+             ema_decay: Optional[float] = None, grad_scale: float = 1.0) -> None:
+    """one step of cfg's rule + the EMA update over a flat tensor (nsvd_opt_step); lr / ema_decay: the step's scheduled
+    values when they differ from cfg's; steps_taken: optimiser steps before this one"""
+    n = _opt_sizes("opt_step", p, grad, sq, mom, ema)
+    c = cfg
+    if lr is not None or ema_decay is not None:
+        c = _lib.OptConfig.from_buffer_copy(cfg)
+        c.lr = cfg.lr if lr is None else float(lr)
+        c.ema_decay = cfg.ema_decay if ema_decay is None else float(ema_decay)
+    if torch_binding() is not None:
+        _TB.opt_step(int(c.kind), p, grad, sq, mom, ema, c.lr, c.alpha, c.eps, c.momentum, c.beta1, c.beta2, c.ema_decay,
+                     int(steps_taken), float(grad_scale))
+        return
+    rc = _lib.load().nsvd_opt_step(_ptr(p, "p"), _ptr(grad, "grad"), _ptr(sq, "sq"), _ptr(mom, "mom"), _ptr(ema, "ema"),
+                                   n, C.byref(c), int(steps_taken), float(grad_scale), _stream())
+    check(rc, "nsvd_opt_step")
+
+
+class OptState:
+    """The device-resident schedule of any optimiser rule (include/nsvd.h: nsvd_opt_state): what StepState is for
+    RMSprop without momentum, plus Adam's bias corrections and SGD's first-step flag."""
+
+    def __init__(self, device, cfg: _lib.OptConfig, T_max: int, eta_min: float = 0.0, step: int = 0):
+        self.buf = torch.zeros(C.sizeof(_lib.OptState) // 8, dtype=torch.int64, device=device)
+        self.cfg, self.T_max, self.eta_min = cfg, int(T_max), float(eta_min)
+        self.reset(step)
+
+    @property
+    def ptr(self) -> int:
+        return self.buf.data_ptr()
+
+    def reset(self, step: int) -> None:
+        with torch.cuda.device(self.buf.device):
+            check(_lib.load().nsvd_opt_state_init(self.ptr, C.byref(self.cfg), self.eta_min, self.T_max, int(step),
+                                                  _stream()), "nsvd_opt_state_init")
+
+    def begin(self) -> None:
+        """cur <- the scheduled values of step `step` (first launch of a loop body)"""
+        with torch.cuda.device(self.buf.device):
+            check(_lib.load().nsvd_opt_state_begin(self.ptr, _stream()), "nsvd_opt_state_begin")
+
+    def read(self) -> "_lib.OptState":
+        """host copy (synchronises)"""
+        return _lib.OptState.from_buffer_copy(self.buf.cpu().numpy().tobytes())
+
+
+def opt_step_dev(p: torch.Tensor, grad: torch.Tensor, sq: Optional[torch.Tensor], mom: Optional[torch.Tensor],
+                 ema: Optional[torch.Tensor], state: OptState, grad_scale: float = 1.0, advance: bool = True) -> None:
+    """opt_step with the step's scalars read from the device-resident schedule; advance: last optimiser launch of the
+    step (state.step += 1 on the device)."""
+    n = _opt_sizes("opt_step_dev", p, grad, sq, mom, ema)
+    rc = _lib.load().nsvd_opt_step_dev(_ptr(p, "p"), _ptr(grad, "grad"), _ptr(sq, "sq"), _ptr(mom, "mom"),
+                                       _ptr(ema, "ema"), n, C.byref(state.cfg), state.ptr, float(grad_scale),
+                                       int(bool(advance)), _stream())
+    check(rc, "nsvd_opt_step_dev")
 
 
 def spectrum_accumulate(f: torch.Tensor, Tf: torch.Tensor, x: torch.Tensor, sigma: float, use_importance: bool,
@@ -1045,10 +1190,10 @@ def cdk_step(desc: "_lib.CdkStepDesc", x: torch.Tensor, y: torch.Tensor, towers:
 
 # every wrapper that launches kernels runs on the device of its tensors (see _on_tensor_device)
 for _name in ("fourier_features", "operator_forward", "operator_features", "operator_sample_features",
-              "operator_sample_features_dev", "rmsprop_ema_step_dev",
+              "operator_sample_features_dev", "rmsprop_ema_step_dev", "opt_step_dev",
               "operator_backward", "model_forward", "model_backward", "evd_moments", "evd_loss_grad", "evd_loss_fused",
-              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "cdk_loss_forward",
-              "cdk_loss_backward", "rmsprop_ema_step", "spectrum_accumulate", "row_normalize",
+              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_opt_step", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "cdk_loss_forward",
+              "cdk_loss_backward", "rmsprop_ema_step", "opt_step", "spectrum_accumulate", "row_normalize",
               "row_normalize_backward", "tower_forward", "tower_backward", "cdk_step", "to_bf16", "gemm_bf16"):
     globals()[_name] = _on_tensor_device(globals()[_name])
 del _name

@@ -49,7 +49,7 @@ class FlatParams:
     RMSprop square-average and EMA shadow buffers). Names follow the reference's state_dict:
     model.base.ws.{i}, model.base.bs.{i}, model.boundary_mask.scales, model.base.feature_map._B."""
 
-    def __init__(self, shape: H.ModelShape, device, with_state: bool = True):
+    def __init__(self, shape: H.ModelShape, device, with_state: bool = True, with_mom: bool = False):
         self.shape = shape
         self.device = torch.device(device)
         self.version = 0  # bumped by every change of the parameters that is not a fused training step (derived copies
@@ -70,6 +70,8 @@ class FlatParams:
         self.grad = torch.zeros_like(self.flat)
         self.sq = torch.zeros_like(self.flat) if with_state else None
         self.ema = torch.zeros_like(self.flat) if with_state else None
+        # momentum buffers / Adam's exp_avg: only for the optimiser rules that have them
+        self.mom = torch.zeros_like(self.flat) if (with_state and with_mom) else None
         self.fourier_B = torch.zeros((shape.D, shape.m), dtype=torch.float32, device=self.device)
         self.state_sharded = False  # set by the trainer while sq / ema are valid on this rank's shards only
         nl = len(shape.dims)
@@ -121,6 +123,8 @@ class FlatParams:
                 self.ema.copy_(self.flat)
         if self.sq is not None and reset_optimizer:
             self.sq.zero_()
+        if self.mom is not None and reset_optimizer:
+            self.mom.zero_()
 
 
 class FusedTrainer:
@@ -135,7 +139,8 @@ class FusedTrainer:
                  parallelism: str = "dp", fused_step: bool = True, keep_grads: bool = False,
                  device_sampler: bool = True, overlap: bool = True, grad_buckets: int = 4,
                  dp_exchange: str = "allreduce", grad_windows: Optional[int] = None, sync_collectives: bool = False,
-                 device_schedule: bool = False, backward_windows: int = 1):
+                 device_schedule: bool = False, backward_windows: int = 1, optimizer: str = "rmsprop",
+                 momentum: float = 0.0, adam_eps: float = 1e-8, betas=(0.9, 0.999)):
         """batch_size is the per-GPU batch. parallelism (only with comm.world > 1): "dp" = every rank draws its
         own batch_size rows (moments + gradient all-reduce); "hp" = every rank owns L/world heads and evaluates
         them on the same global batch of batch_size * world rows (one all-gather of f, Tf; see parallel.py).
@@ -160,7 +165,23 @@ class FusedTrainer:
         sampler's batch counter live in DEVICE memory (hip_ops.StepState; the backward's first kernel derives the step's
         values, its last one advances the counter) instead of travelling as launch arguments - what makes a step
         replayable from a captured HIP graph (capture_graph). The values are the host path's except that the device
-        cosine may differ from libm's in the last bit of the double (include/nsvd.h)."""
+        cosine may differ from libm's in the last bit of the double (include/nsvd.h).
+        optimizer / momentum / adam_eps / betas: the reference's get_optimizer (examples/utils.py:48-72): "rmsprop"
+        (rmsprop_decay, rmsprop_eps, momentum), "adam" (betas, adam_eps) or "sgd" (momentum); weight_decay 0, no
+        Nesterov, no amsgrad. RMSprop without momentum (the default) is the trainer as it has always been; the other
+        rules run on one process only, in the same kernels' epilogues (nsvd_operator_backward_evd_opt_step), with their
+        momentum buffers / first moments in P.mom."""
+        if optimizer not in H.OPTIMIZER_KINDS:
+            raise ValueError(f"optimizer must be one of {sorted(H.OPTIMIZER_KINDS)}")
+        self.optimizer, self.momentum = optimizer, float(momentum)
+        # any rule but RMSprop without momentum: nsvd_opt_config / nsvd_optimizer instead of nsvd_rmsprop
+        self._other_rule = not (optimizer == "rmsprop" and self.momentum == 0.0)
+        self._cfg = H.opt_config(optimizer, lr, rmsprop_decay, adam_eps if optimizer == "adam" else rmsprop_eps,
+                                 self.momentum, betas, ema_decay)
+        self._uses_sq, self._uses_mom = H.opt_uses(self._cfg)
+        if self._other_rule and comm is not None and comm.multi:
+            raise NotImplementedError(f"FusedTrainer(optimizer={optimizer!r}, momentum={momentum}) on several ranks: "
+                                      "only rmsprop without momentum is built for sharded runs")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise H.NsvdError(f"FusedTrainer needs a GPU device (got {self.device}); there is no CPU path")
@@ -203,7 +224,7 @@ class FusedTrainer:
     def _build(self, shape, problem, fourier_scale, exp_mask_init, seed, sample_seed, sequential, step, fused_step,
                keep_grads, device_sampler, overlap, grad_buckets, world, rank, dp_exchange, grad_windows):
         path, multi = self.path, self.multi
-        self.P = FlatParams(shape, self.device)
+        self.P = FlatParams(shape, self.device, with_mom=self._uses_mom)
         fB0, ws0, bs0, sc0 = reference_init(self.full_shape, fourier_scale, exp_mask_init, seed)
         if self.hp:  # this rank's heads of the (identically seeded) full model
             sl = slice(self.l_off, self.l_off + shape.L)
@@ -221,6 +242,8 @@ class FusedTrainer:
         self._grads = self.P.pack(self.P.grad, False)
         self._ema_params = self.P.pack(self.P.ema, True)
         self._sq_params = self.P.pack(self.P.sq, False)
+        self._mom_params = self.P.pack(self.P.mom, False) if self._uses_mom else None
+        self._opt_desc = None  # the nsvd_optimizer of the other rules (built once, scalars refreshed per step)
         self.fused_step = bool(fused_step) and (not multi or self.hp)
         # the generic (non-MFMA) path takes the step with per-tensor optimiser launches and needs the gradients
         self.keep_grads = bool(keep_grads) or H.path_name(shape, self.B, path, problem) != "fused_mfma"
@@ -299,8 +322,11 @@ class FusedTrainer:
             if not (self.fused_step and H.path_name(shape, self.B, path, problem) == "fused_mfma"):
                 raise H.NsvdError("device_schedule needs the fused optimiser step on the MFMA path (single GPU or "
                                   "heads sharded, 128-wide hidden layers)")
-            self.state = H.StepState(self.device, self.lr, self.num_iters if self.use_sched else 0, self.alpha,
-                                     self.eps, self.ema_decay)
+            if self._other_rule:  # (both states begin with the step counter the device sampler reads)
+                self.state = H.OptState(self.device, self._cfg, self.num_iters if self.use_sched else 0)
+            else:
+                self.state = H.StepState(self.device, self.lr, self.num_iters if self.use_sched else 0, self.alpha,
+                                         self.eps, self.ema_decay)
         # dp gradient buckets: W_0 (89 % of the bytes, first in the flat buffer) cut on head boundaries, the small
         # tensors ride with the last cut
         nb = max(1, min(int(grad_buckets), shape.L))
@@ -392,6 +418,9 @@ class FusedTrainer:
             t_before = self.t
             lr, decay = self._advance_schedule()
             # (device schedule: lr / decay are read on the device, the host values only keep the counters in step)
+            if self._other_rule:
+                self._backward_other_rule(x, v, M, moments, reduced, scratch, loss, lr, decay, t_before)
+                return
             opt = H.rmsprop_state(self._sq_params, self._ema_params, lr, self.alpha, self.eps, decay, self.state)
             if self._two_windows():
                 ride = self.guest_features and self._own_batch and not self._next_ready
@@ -428,8 +457,28 @@ class FusedTrainer:
             self.begin_apply()
             self.apply(0, self.P.numel, 1.0)
 
+    def _backward_other_rule(self, x, v, M, moments, reduced, scratch, loss, lr, decay, t_before) -> None:
+        """the fused step of any rule but RMSprop without momentum (nsvd_operator_backward_evd_opt_step)"""
+        if self._opt_desc is None:
+            self._opt_desc = H.optimizer_state(self._cfg, self._sq_params if self._uses_sq else None, self._mom_params,
+                                               self._ema_params, state=self.state)
+        opt = self._opt_desc
+        opt.cfg.lr, opt.cfg.ema_decay, opt.steps_taken = float(lr), float(decay), int(t_before)
+        ride = self.guest_features and self._own_batch and not self._next_ready
+        H.operator_backward_evd_opt_step(self.shape, self._params, self.problem, x, self.f_g, self.Tf_g, self.mask_kind,
+                                         v, M, moments, reduced, scratch, loss,
+                                         self._grads if self.keep_grads else None, opt, self.ws, 1.0, self.path,
+                                         l_offset=self.l_off, next_seed=self.sample_key,
+                                         next_offset=self.batches_drawn - (t_before if self.state is not None else 0),
+                                         x_next=self._x_other if ride else None,
+                                         ws_next=self._ws_other if ride else None)
+        if ride:
+            self.batches_drawn += 1
+            self._next_ready = True
+        self._note_planes(self._ws_other if ride else self.ws)
+
     def _two_windows(self) -> bool:
-        if self.backward_windows != 2 or self.multi or self.keep_grads or self.shape.L % 2:
+        if self.backward_windows != 2 or self._other_rule or self.multi or self.keep_grads or self.shape.L % 2:
             return False
         if self._side_stream is None:
             ok = H.path_name(self.shape, self.B, self.path, self.problem) == "fused_mfma" and \
@@ -542,6 +591,29 @@ class FusedTrainer:
             sd[n] = self.gather_heads_tensor(sd[n])
         return sd
 
+    def optimizer_state_dict(self) -> Dict[str, object]:
+        """What resuming needs beside state_dict() / state_dict(ema=True): the rule's state buffers (flat, in the
+        parameters' layout) and the counters. Single process (sharded optimiser states: gather_optimizer_state first)."""
+        return dict(optimizer=self.optimizer, momentum=self.momentum, t=self.t, num_updates=self.num_updates,
+                    batches_drawn=self.batches_drawn, sq=self.P.sq.clone(),
+                    mom=self.P.mom.clone() if self.P.mom is not None else None)
+
+    def load_optimizer_state_dict(self, sd: Dict[str, object]) -> None:
+        """counterpart of optimizer_state_dict (after P.load_state_dict(..., reset_optimizer=False))"""
+        if sd["optimizer"] != self.optimizer or float(sd["momentum"]) != self.momentum:
+            raise ValueError(f"optimizer state of {sd['optimizer']!r} (momentum {sd['momentum']}) loaded into "
+                             f"{self.optimizer!r} (momentum {self.momentum})")
+        if (sd["mom"] is None) != (self.P.mom is None):
+            raise ValueError("optimizer state: momentum buffers do not match the rule")
+        self.P.sq.copy_(sd["sq"])
+        if self.P.mom is not None:
+            self.P.mom.copy_(sd["mom"])
+        self.t, self.num_updates, self.batches_drawn = int(sd["t"]), int(sd["num_updates"]), int(sd["batches_drawn"])
+        self._next_ready = False
+        if self.state is not None:
+            with torch.cuda.device(self.device):
+                self.state.reset(self.t)
+
     def gather_heads_tensor(self, v: torch.Tensor) -> torch.Tensor:
         """heads sharded: every rank's (n_r, ...) slice of a per-head tensor -> the (L, ...) tensor, on every rank (a
         collective: call on every rank). Ranks own L // world or L // world + 1 heads (parallel.head_range): the
@@ -565,6 +637,11 @@ class FusedTrainer:
 
     def apply(self, lo: int, hi: int, grad_scale: float) -> None:
         self.P.version += 1
+        if self._other_rule:  # (self.t was advanced by begin_apply: t - 1 steps were taken before this one)
+            H.opt_step(self._cfg, self.P.flat[lo:hi], self.P.grad[lo:hi], self.P.sq[lo:hi] if self._uses_sq else None,
+                       self.P.mom[lo:hi] if self._uses_mom else None, self.P.ema[lo:hi], self.t - 1, self._lr_now,
+                       self._decay_now, grad_scale)
+            return
         H.rmsprop_ema_step(self.P.flat[lo:hi], self.P.grad[lo:hi], self.P.sq[lo:hi], self.P.ema[lo:hi], self._lr_now,
                            self.alpha, self.eps, self._decay_now, grad_scale)
 
