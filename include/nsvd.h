@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define NSVD_ABI_VERSION 4
+#define NSVD_ABI_VERSION 5
 #define NSVD_MAX_LAYERS 8
 
 #define NSVD_EINVAL (-10001)
@@ -61,6 +61,10 @@ extern "C" {
                              * (potentials.py:11-17)                                                                  */
 #define NSVD_POT_SIN_OF_COS 5 /* V = sin(sum_d pot_coef[d] cos x_d) (others.py:33-34): the drift potential of
                                * NSVD_OP_FOKKER_PLANCK, valid with that operator kind only                             */
+/* (6 is unassigned) */
+#define NSVD_POT_MOLECULE 7 /* V = pot_const - sum_i sum_a Z_a / |r_i - R_a| + sum_{i<j} 1 / |r_i - r_j| over the
+                             * n_particles electrons r_i (d = D / n_particles coordinates each) and the n_nuclei rows
+                             * (R_a, Z_a) of pot_table (potentials.py:35-57); Schroedinger kind only                    */
 
 /* nsvd_problem.operator_kind */
 #define NSVD_OP_SCHROEDINGER 0  /* Tf = -(-scale_kinetic Lap f + V f)            (schrodinger/__init__.py:16-22)      */
@@ -139,13 +143,33 @@ typedef struct nsvd_problem {
     float fp_scale;                  /* NegativeLinearFokkerPlanck(scale=...)          */
     float pot_coef[4];               /* cs[d] (cosine, sin-of-cos: float32 values, as torch.tensor(cs) makes them), or R
                                       * in [0] (H2+); entries past D are ignored       */
+    /* ABI 5 (appended; all zero = the problems of ABI 4): input dimensions 5 .. 12 in the finite-difference mode and the
+     * many-electron potential. Tables longer than pot_coef travel by pointer: the kernels read them with a uniform
+     * index from global memory, nothing by-value grows and nothing is copied into a per-thread array. */
+    int32_t n_particles;             /* electrons sharing the D coordinates (0 is read as 1): d = D / n_particles is the
+                                      * space dimension, and the exponent of the uniform density (2 sigma)^-d
+                                      * (main_pde.py:118); the Gaussian density is over all D coordinates */
+    int32_t n_nuclei;                /* NSVD_POT_MOLECULE: rows of pot_table           */
+    int32_t pot_table_len;           /* floats in pot_table                            */
+    float pot_const;                 /* NSVD_POT_MOLECULE: the nuclear repulsion energy (nuclear_energy, host-evaluated) */
+    const float* pot_table;          /* DEVICE pointer owned by the caller, stable across graph replays.
+                                      * NSVD_POT_COSINE / NSVD_POT_SIN_OF_COS with D > 4: cs[0..D) (float32 values, as
+                                      * torch.tensor(cs) makes them; pot_coef is then ignored). NSVD_POT_MOLECULE:
+                                      * n_nuclei rows (R_0, .., R_{d-1}, Z). NULL otherwise. */
 } nsvd_problem;
 
 int nsvd_abi_version(void);
 
 /* Name of the implementation nsvd_operator_forward would take ("fused_mfma", "generic"). host */
 const char* nsvd_path_name(const nsvd_model_desc* desc, int B, int path);
-/* The same for a given problem: the exact-Laplacian mode (prob->eps <= 0) exists on the MFMA path only (D <= 3, as the
+/* The same for a given problem. Input dimensions 5 .. 12 exist in the finite-difference mode (eps > 0): on the generic
+ * kernels (NSVD_PATH_AUTO too), and for models the MFMA kernels take on NSVD_PATH_FUSED (the forward in split form, one
+ * direction per workgroup); "unsupported" there with eps <= 0, NSVD_PATH_FUSED_BF16X3, NSVD_PATH_FUSED on any other
+ * shape, and beyond D = 12; "invalid" for a D > 4
+ * cosine / sin-of-cos problem whose pot_table is NULL or not D long, and for a NSVD_POT_MOLECULE problem with
+ * n_nuclei < 1, D not a multiple of n_particles, d = D / n_particles not 2 or 3, pot_table_len != n_nuclei (d + 1), a
+ * NULL table, or inside the Fokker-Planck kind.
+ * The exact-Laplacian mode (prob->eps <= 0) exists on the MFMA path only (D <= 3, as the
  * stencil mode: its 3-D form runs one direction per workgroup); "unsupported" when it has no path; "invalid" for a
  * potential, importance, operator kind or box mask value this library does not know (and for NSVD_POT_SIN_OF_COS
  * outside the Fokker-Planck kind). Every path implements every box mask, potential and importance; entry points that do
@@ -228,7 +252,7 @@ int nsvd_operator_sample_features(const nsvd_model_desc* desc, const nsvd_params
                                   size_t ws_bytes, int save_for_backward, int path, void* stream);
 
 /* Workspace of nsvd_model_forward / nsvd_model_backward alone (no stencil rows): smaller than
- * nsvd_workspace_bytes, and defined for input dimensions up to 64 (the operator entry points stop at D = 4). */
+ * nsvd_workspace_bytes, and defined for input dimensions up to 64 (the operator entry points stop at D = 12). */
 size_t nsvd_model_workspace_bytes(const nsvd_model_desc* desc, int B);
 
 /* Parameter gradients of sum(dout * model(x)) for the matching nsvd_model_forward(save_for_backward=1). */

@@ -10,12 +10,13 @@ import os
 from typing import Optional
 
 NSVD_MAX_LAYERS = 8
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 EINVAL = -10001
 EUNSUPPORTED = -10002
 
 POT_HYDROGEN, POT_HARMONIC, POT_ZERO, POT_COSINE, POT_H2_ION, POT_SIN_OF_COS = 0, 1, 2, 3, 4, 5
+POT_MOLECULE = 7  # (6 is unassigned)
 OP_SCHROEDINGER, OP_FOKKER_PLANCK = 0, 1
 BOX_NONE, BOX_SQRT, BOX_EXP = 0, 1, 2
 IMP_NONE, IMP_GAUSSIAN, IMP_UNIFORM = 0, 1, 2
@@ -46,7 +47,10 @@ class Problem(C.Structure):
                 ("eps", C.c_float), ("op_scale", C.c_float), ("op_shift", C.c_float), ("sigma", C.c_float),
                 ("hard_mul_const", C.c_float), ("use_importance", C.c_int32),
                 # ABI 4 (all zero: the Schroedinger operator with a radial potential)
-                ("operator_kind", C.c_int32), ("fp_scale", C.c_float), ("pot_coef", C.c_float * 4)]
+                ("operator_kind", C.c_int32), ("fp_scale", C.c_float), ("pot_coef", C.c_float * 4),
+                # ABI 5 (all zero: the problems of ABI 4): several particles, the molecule, tables by device pointer
+                ("n_particles", C.c_int32), ("n_nuclei", C.c_int32), ("pot_table_len", C.c_int32),
+                ("pot_const", C.c_float), ("pot_table", C.c_void_p)]
 
 
 class TowerParams(C.Structure):

@@ -45,6 +45,60 @@ __global__ void __launch_bounds__(256) fd_epilogue_kernel(const float* __restric
     if (dsc) dsc[idx] = o.dsc;
 }
 
+// ---- 5 <= D <= NSVD_MAX_D: the direction-loop form (fd_math.h: nsvd_fd_evenodd_nd), even / odd rows only ---------------
+// A workgroup takes ND_ROWS samples; wave g of its four takes the heads l = g (mod 4). Within a wave the lane is the
+// sample, so each of the 2 D + 1 loads of `base` per head is one contiguous run of ND_ROWS floats, and what the L heads
+// of a row share is computed once: per row by every thread (nsvd_fd_row_nd), per row and direction by one of the four
+// waves into LDS (nsvd_fd_dir_nd). The (B, L) row-major outputs go through an LDS tile of
+// ND_ROWS x ND_HEADS per output and leave as runs of ND_HEADS floats per row.
+constexpr int ND_ROWS = 64, ND_HEADS = 16;
+template <bool TRIG>
+__global__ void __launch_bounds__(256) fd_epilogue_nd_kernel(const float* __restrict__ base, int ldr,
+                                                             const float* __restrict__ x,
+                                                             const float* __restrict__ scales, nsvd_problem prob,
+                                                             float log_norm, int B, int D, int L, float* __restrict__ f,
+                                                             float* __restrict__ Tf, float* __restrict__ jac,
+                                                             float* __restrict__ dsc, NsvdBox box) {
+    __shared__ float tile[4][ND_ROWS][ND_HEADS + 1];
+    __shared__ float dirs[NSVD_MAX_D * NSVD_FD_DIR_FIELDS][ND_ROWS];  // nsvd_fd_dir_nd's table, the row fastest
+    const int bl = threadIdx.x & (ND_ROWS - 1), g = threadIdx.x >> 6;
+    const int b0 = blockIdx.x * ND_ROWS, b = b0 + bl;
+    const bool bok = b < B;
+    const float* xr = x + (size_t)(bok ? b : 0) * D;
+    NsvdFdRowNd w;
+    if (bok) {
+        w = nsvd_fd_row_nd<TRIG>(xr, D, prob, log_norm, box);
+        // wave g fills the directions d = g (mod 4) of its 64 rows: what the heads share along a direction, once
+        for (int d = g; d < D; d += 4) nsvd_fd_dir_nd<TRIG>(w, xr, d, D, scales != nullptr, prob, box, &dirs[0][bl], ND_ROWS);
+    }
+    __syncthreads();
+    for (int l0 = 0; l0 < L; l0 += ND_HEADS) {
+        for (int lh = g; lh < ND_HEADS; lh += 4) {
+            const int l = l0 + lh;
+            if (!bok || l >= L) continue;
+            const NsvdFdOut o = nsvd_fd_evenodd_nd<TRIG>(w, xr, base + (size_t)l * ldr + b, (size_t)B, D,
+                                                         scales != nullptr, scales ? scales[l] : 0.f, prob, box,
+                                                         &dirs[0][bl], ND_ROWS);
+            tile[0][bl][lh] = o.f;
+            tile[1][bl][lh] = o.Tf;
+            tile[2][bl][lh] = o.jac;
+            tile[3][bl][lh] = o.dsc;
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < ND_ROWS * ND_HEADS; i += 256) {
+            const int r = i / ND_HEADS, h = i - r * ND_HEADS;
+            if (b0 + r < B && l0 + h < L) {
+                const size_t o = (size_t)(b0 + r) * L + l0 + h;
+                f[o] = tile[0][r][h];
+                Tf[o] = tile[1][r][h];
+                if (jac) jac[o] = tile[2][r][h];
+                if (dsc) dsc[o] = tile[3][r][h];
+            }
+        }
+        __syncthreads();
+    }
+}
+
 __global__ void __launch_bounds__(256) head_backward_kernel(const float* __restrict__ df,
                                                             const float* __restrict__ jac, int B, int L,
                                                             float* __restrict__ dzT) {
@@ -108,9 +162,16 @@ int nsvd_model_out(const float* base, int ldr, const float* x, const float* scal
 int nsvd_fd_epilogue(const float* base, int ldr, const float* x, const float* scales, const nsvd_problem& prob,
                      int B, int D, int L, float* f, float* Tf, float* jac, float* dsc, hipStream_t s, int evenodd,
                      NsvdBox box) {
-    if (D > NSVD_FD_MAXD) return NSVD_EUNSUPPORTED;
     const float log_norm = nsvd_importance_log_norm(D, prob);
     const bool trig = prob.potential == NSVD_POT_COSINE || prob.operator_kind == NSVD_OP_FOKKER_PLANCK;
+    if (D > NSVD_FD_MAXD) {  // the direction-loop form: even / odd rows, the finite-difference mode
+        if (D > NSVD_MAX_D || !evenodd || !(prob.eps > 0.f)) return NSVD_EUNSUPPORTED;
+        hipLaunchKernelGGL(trig ? fd_epilogue_nd_kernel<true> : fd_epilogue_nd_kernel<false>,
+                           dim3(nsvd_cdiv(B, ND_ROWS)), dim3(256), 0, s, base, ldr, x, scales, prob, log_norm, B, D, L,
+                           f, Tf, jac, dsc, box);
+        NSVD_CHECK_LAUNCH();
+        return 0;
+    }
     hipLaunchKernelGGL(trig ? fd_epilogue_kernel<true> : fd_epilogue_kernel<false>, dim3(nsvd_cdiv(B * L, 256)),
                        dim3(256), 0, s, base, ldr, x, scales, prob, log_norm, B, D, L, f, Tf, jac, dsc, evenodd, box);
     NSVD_CHECK_LAUNCH();

@@ -4,6 +4,9 @@
 #include "nsvd_common.h"
 
 #define NSVD_FD_MAXD 4
+#ifdef NSVD_SMALL_D
+static_assert(NSVD_FD_MAXD == NSVD_SMALL_D, "nsvd_problem_status routes D > NSVD_SMALL_D to the direction-loop form");
+#endif
 
 struct NsvdFdOut {
     float f, Tf, jac, dsc;
@@ -17,7 +20,9 @@ __device__ __forceinline__ float nsvd_sqrt_p(const nsvd_problem& prob, const flo
     return 1.f;
 }
 static inline float nsvd_importance_log_norm(int D, const nsvd_problem& prob) {
-    if (prob.use_importance == NSVD_IMP_UNIFORM) return (float)(-(double)D * log(2.0 * (double)prob.sigma));
+    // (the exponent of the uniform density is the SPACE dimension D / n_particles: main_pde.py:118)
+    if (prob.use_importance == NSVD_IMP_UNIFORM)
+        return (float)(-(double)(prob.n_particles > 1 ? D / prob.n_particles : D) * log(2.0 * (double)prob.sigma));
     return nsvd_gauss_log_norm(D, prob.sigma);
 }
 
@@ -33,6 +38,41 @@ __device__ __forceinline__ float nsvd_cos_sum(const nsvd_problem& prob, const fl
     return S;
 }
 
+// ---- the many-electron potential (potentials.py:35-57): x holds n_particles electrons of sd = D / n_particles
+// coordinates each, pot_table n_nuclei rows (R_0, .., R_{sd-1}, Z):
+//   V = pot_const - sum_i sum_a Z_a / |r_i - R_a| + sum_{i<j} 1 / |r_i - r_j|
+// Every distance from coordinate DIFFERENCES (exact beside a nucleus and at a coalescence: Sterbenz), never from
+// expanded squares. X: coordinate k of the row - a chain of selects over a register array (NsvdCoordArr: constant
+// indices only, D <= NSVD_FD_MAXD) or a load (NsvdCoordMem); the table is read with uniform indices from global memory.
+struct NsvdCoordArr {
+    float x0, x1, x2, x3;
+    __device__ __forceinline__ float operator()(int k) const { return k == 0 ? x0 : k == 1 ? x1 : k == 2 ? x2 : x3; }
+};
+struct NsvdCoordMem {
+    const float* xr;
+    __device__ __forceinline__ float operator()(int k) const { return xr[k]; }
+};
+template <class X>
+__device__ __forceinline__ float nsvd_molecule_potential(const nsvd_problem& prob, X x, int D) {
+    const int np = prob.n_particles > 0 ? prob.n_particles : 1, sd = D / np;
+    const bool three = sd > 2;
+    const float* tab = prob.pot_table;
+    float V = prob.pot_const;
+    for (int i = 0; i < np; ++i) {
+        const float x0 = x(i * sd), x1 = x(i * sd + 1), x2 = three ? x(i * sd + 2) : 0.f;
+        for (int a = 0; a < prob.n_nuclei; ++a) {
+            const float* row = tab + a * (sd + 1);
+            const float d0 = x0 - row[0], d1 = x1 - row[1], d2 = three ? x2 - row[2] : 0.f;
+            V -= row[sd] / sqrtf(fmaf(d2, d2, fmaf(d1, d1, d0 * d0)));
+        }
+        for (int j = i + 1; j < np; ++j) {
+            const float d0 = x0 - x(j * sd), d1 = x1 - x(j * sd + 1), d2 = three ? x2 - x(j * sd + 2) : 0.f;
+            V += 1.f / sqrtf(fmaf(d2, d2, fmaf(d1, d1, d0 * d0)));
+        }
+    }
+    return V;
+}
+
 // V(x) of the Schroedinger kind at the centre xc, |xc| = r0 (potentials.py:5-8, 11-17, 20-21, 24-27, 30-31)
 // TRIG (here and in the finite-difference forms below): false compiles the periodic problems - the cosine potential
 // and the Fokker-Planck kind, whose sinf / cosf carry their own argument reduction - out of an instance; a kernel that
@@ -42,6 +82,11 @@ __device__ __forceinline__ float nsvd_potential(const nsvd_problem& prob, const 
     if (prob.potential == NSVD_POT_HYDROGEN) return -(prob.charge_or_k / r0);
     if (prob.potential == NSVD_POT_ZERO) return 0.f;
     if (TRIG && prob.potential == NSVD_POT_COSINE) return nsvd_cos_sum(prob, xc, D);
+    if (prob.potential == NSVD_POT_MOLECULE) {
+        // (a molecule has at least two coordinates; entries past D are never selected)
+        const NsvdCoordArr xa{xc[0], xc[1], D > 2 ? xc[2] : 0.f, D > 3 ? xc[3] : 0.f};
+        return nsvd_molecule_potential(prob, xa, D);
+    }
     if (prob.potential == NSVD_POT_H2_ION) {
         // the nuclei sit at +-R on the last axis; x_last -+ R is exact next to a nucleus (Sterbenz), where
         // |x|^2 -+ 2 R x_last + R^2 would be a difference of O(1) numbers
@@ -67,8 +112,7 @@ __device__ __forceinline__ float nsvd_potential(const nsvd_problem& prob, const 
 struct NsvdPotDiff {
     float dif, sum2;  // V_+ - V_-,  V_+ + V_- - 2 V_0
 };
-__device__ __forceinline__ NsvdPotDiff nsvd_sin_of_cos_diff(const nsvd_problem& prob, float S, float xd, int d) {
-    const float cs = nsvd_pot_coef(prob, d), eps = prob.eps;
+__device__ __forceinline__ NsvdPotDiff nsvd_sin_of_cos_diff_cs(float cs, float eps, float S, float xd) {
     const float she = sinf(0.5f * eps);
     const float a = -2.f * cs * cosf(xd) * (she * she), b = cs * sinf(xd) * sinf(eps);
     const float shb = sinf(0.5f * b);
@@ -76,6 +120,9 @@ __device__ __forceinline__ NsvdPotDiff nsvd_sin_of_cos_diff(const nsvd_problem& 
     o.dif = -2.f * cosf(S + a) * sinf(b);
     o.sum2 = 4.f * cosf(S + 0.5f * a) * sinf(0.5f * a) * cosf(b) - 4.f * sinf(S) * (shb * shb);
     return o;
+}
+__device__ __forceinline__ NsvdPotDiff nsvd_sin_of_cos_diff(const nsvd_problem& prob, float S, float xd, int d) {
+    return nsvd_sin_of_cos_diff_cs(nsvd_pot_coef(prob, d), prob.eps, S, xd);
 }
 // from the per-direction sums adv = sum_d (V_+ - V_-)(g_+ - g_-) / u and lv = sum_d (V_+ + V_- - 2 V), with
 // lap = Lap g / sqrt p and fs as the Schroedinger kind forms them, u the factor adv still lacks (c w0 / sqrt p):
@@ -314,6 +361,153 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_evenodd(float base0, const float* b
     const float w = (sp0 / spc) * c;
     o.jac = w * (mk0 * M0);
     o.dsc = has_mask ? w * base0 * (mk0 * M0) * r0 / (s_l * s_l) : 0.f;
+    return o;
+}
+
+// ---- the even / odd form for 5 <= D <= NSVD_MAX_D: a loop over directions that reads xr[d], bE[d], bO[d] from MEMORY --------
+// nsvd_fd_evenodd's expressions, term for term; no per-thread array indexed by a run-time d exists (a 12-entry one would
+// live in scratch memory). xr: the row's D coordinates; the head's raw outputs are base0 = bcol[0], bE[d] =
+// bcol[(1 + 2 d) bs], bO[d] = bcol[(2 + 2 d) bs] (bs = B in the (L, E B) layout of the generic path). The cosine /
+// sin-of-cos coefficients come from prob.pot_table (D floats).
+// What a row's L heads share is computed once: per row (nsvd_fd_row_nd) |x|, sqrt p, the potential, the box mask at the
+// centre; per row and direction (nsvd_fd_dir_nd) everything of the loop body that does not depend on the head.
+struct NsvdFdRowNd {
+    float r2, r0, sp0, V, M0, S;  // S: the cosine sum of the Fokker-Planck drift potential
+};
+template <bool TRIG>
+__device__ __forceinline__ NsvdFdRowNd nsvd_fd_row_nd(const float* xr, int D, const nsvd_problem& prob, float log_norm,
+                                                      const NsvdBox& box) {
+    NsvdFdRowNd w;
+    float r2 = 0.f;
+    for (int d = 0; d < D; ++d) r2 = fmaf(xr[d], xr[d], r2);
+    w.r2 = r2;
+    w.r0 = sqrtf(r2);
+    w.sp0 = nsvd_sqrt_p(prob, xr, D, log_norm);
+    w.M0 = 1.f;
+    if (box.mode)
+        for (int d = 0; d < D; ++d) w.M0 *= nsvd_box_m1(box.lim - xr[d], box.lim + xr[d], box);
+    float S = 0.f;
+    if (TRIG && (prob.potential == NSVD_POT_COSINE || prob.potential == NSVD_POT_SIN_OF_COS))
+        for (int d = 0; d < D; ++d) S = fmaf(prob.pot_table[d], cosf(xr[d]), S);
+    w.S = S;
+    w.V = 0.f;
+    if (prob.operator_kind != NSVD_OP_FOKKER_PLANCK) {
+        if (prob.potential == NSVD_POT_HYDROGEN) w.V = -(prob.charge_or_k / w.r0);
+        else if (prob.potential == NSVD_POT_ZERO) w.V = 0.f;
+        else if (prob.potential == NSVD_POT_COSINE) w.V = S;
+        else if (prob.potential == NSVD_POT_MOLECULE) w.V = nsvd_molecule_potential(prob, NsvdCoordMem{xr}, D);
+        else if (prob.potential == NSVD_POT_H2_ION) {
+            const float R = prob.pot_coef[0], xl = xr[D - 1];
+            float rest = 0.f;
+            for (int d = 0; d < D - 1; ++d) rest = fmaf(xr[d], xr[d], rest);
+            const float dm = xl - R, dp = xl + R;
+            w.V = -(prob.charge_or_k / sqrtf(fmaf(dm, dm, rest))) - prob.charge_or_k / sqrtf(fmaf(dp, dp, rest));
+        } else w.V = prob.charge_or_k * (w.r0 * w.r0);
+    }
+    return w;
+}
+// What the L heads of a row share along direction d (nsvd_fd_dir_nd), NSVD_FD_DIR_FIELDS floats: field k of direction d
+// lies at dir[(d NSVD_FD_DIR_FIELDS + k) es] - es = 1: one row's table, contiguous; the kernel keeps the table of its
+// 64 rows in LDS with the row fastest (es = 64). Without the exponential mask rho's even / odd parts (ev, od: two
+// sinhf and one expm1f) do not depend on the head; nor do the box mask's M_rest, m0, ds, dd (O(D) mask values per
+// direction) and the Fokker-Planck differences of V (six sinf / cosf). With the mask ev / od depend on scales_l and
+// stay in the head's loop.
+// (the Fokker-Planck kind has no box mask: its two values share the slots of M_rest and m0)
+#define NSVD_FD_DIR_FIELDS 6
+enum { NSVD_DIR_EV = 0, NSVD_DIR_OD, NSVD_DIR_MREST, NSVD_DIR_M0, NSVD_DIR_DS, NSVD_DIR_DD,
+       NSVD_DIR_VDIF = NSVD_DIR_MREST, NSVD_DIR_VSUM2 = NSVD_DIR_M0 };
+template <bool TRIG>
+__device__ __forceinline__ void nsvd_fd_dir_nd(const NsvdFdRowNd& w, const float* xr, int d, int D, bool has_mask,
+                                               const nsvd_problem& prob, const NsvdBox& box, float* dir, size_t es) {
+    const float xd = xr[d], eps = prob.eps;
+    float* q = dir + (size_t)d * NSVD_FD_DIR_FIELDS * es;
+    if (!has_mask) {
+        const float qs = prob.use_importance == NSVD_IMP_GAUSSIAN ? -1.f / (4.f * prob.sigma * prob.sigma) : 0.f;
+        const float e2 = eps * eps, b = 2.f * xd * eps;
+        const float sv = qs * e2, av = qs * b;
+        const float sh = sinhf(0.5f * av), chm1 = 2.f * sh * sh, es1 = expm1f(sv);
+        q[NSVD_DIR_EV * es] = 2.f * (es1 * (1.f + chm1) + chm1);
+        q[NSVD_DIR_OD * es] = 2.f * (1.f + es1) * sinhf(av);
+    }
+    if (box.mode) {
+        float Mrest = 1.f;
+        for (int j = 0; j < D; ++j)
+            if (j != d) Mrest *= nsvd_box_m1(box.lim - xr[j], box.lim + xr[j], box);
+        const NsvdBoxEO bm = nsvd_box_eo(xd, eps, box);
+        q[NSVD_DIR_MREST * es] = Mrest;
+        q[NSVD_DIR_M0 * es] = bm.m0;
+        q[NSVD_DIR_DS * es] = bm.ds;
+        q[NSVD_DIR_DD * es] = bm.dd;
+    } else if (TRIG && prob.operator_kind == NSVD_OP_FOKKER_PLANCK) {
+        const NsvdPotDiff v = nsvd_sin_of_cos_diff_cs(prob.pot_table[d], eps, w.S, xd);
+        q[NSVD_DIR_VDIF * es] = v.dif;
+        q[NSVD_DIR_VSUM2 * es] = v.sum2;
+    }
+}
+template <bool TRIG>
+__device__ __forceinline__ NsvdFdOut nsvd_fd_evenodd_nd(const NsvdFdRowNd& w, const float* xr, const float* bcol,
+                                                        size_t bs, int D, bool has_mask, float s_l,
+                                                        const nsvd_problem& prob, const NsvdBox& box,
+                                                        const float* dir, size_t es) {
+    const float r2 = w.r2, r0 = w.r0, sp0 = w.sp0;
+    const float base0 = bcol[0];
+    const float c = prob.hard_mul_const;
+    const float mk0 = has_mask ? expf(-r0 / s_l) : 1.f;
+    const float eps = prob.eps;
+    const float qs = prob.use_importance == NSVD_IMP_GAUSSIAN ? -1.f / (4.f * prob.sigma * prob.sigma) : 0.f;
+    const float e2 = eps * eps;
+    float acc = 0.f;
+    const bool fp = TRIG && prob.operator_kind == NSVD_OP_FOKKER_PLANCK;
+    float adv = 0.f, lv = 0.f;
+    for (int d = 0; d < D; ++d) {
+        const float bEd = bcol[(size_t)(1 + 2 * d) * bs], bOd = bcol[(size_t)(2 + 2 * d) * bs];
+        const float* q = dir + (size_t)d * NSVD_FD_DIR_FIELDS * es;
+        float ev, od;
+        if (has_mask) {  // rho depends on scales_l: nsvd_fd_evenodd's expressions, per head
+            const float b = 2.f * xr[d] * eps;
+            float sv = qs * e2, av = qs * b;
+            const float rp = sqrtf(fmaxf(r2 + (e2 + b), 0.f)), rm = sqrtf(fmaxf(r2 + (e2 - b), 0.f));
+            const float S = rp + rm, den = (rp + r0) * (rm + r0);
+            const float tsum = (e2 * (S + 2.f * r0) - 2.f * b * b / S) / den;
+            const float tdif = b * ((S + 2.f * r0) - 2.f * e2 / S) / den;
+            sv -= 0.5f * tsum / s_l;
+            av -= 0.5f * tdif / s_l;
+            const float sh = sinhf(0.5f * av), chm1 = 2.f * sh * sh, es1 = expm1f(sv);
+            ev = 2.f * (es1 * (1.f + chm1) + chm1);  // rho_+ + rho_-
+            od = 2.f * (1.f + es1) * sinhf(av);      // rho_+ - rho_-
+        } else {
+            ev = q[NSVD_DIR_EV * es];
+            od = q[NSVD_DIR_OD * es];
+        }
+        if (box.mode) {
+            const float Mrest = q[NSVD_DIR_MREST * es], m0 = q[NSVD_DIR_M0 * es];
+            const float ds = q[NSVD_DIR_DS * es], dd = q[NSVD_DIR_DD * es];
+            const float sgs = m0 * ev + ds + 0.5f * (ev * ds + od * dd);
+            const float sgd = m0 * od + dd + 0.5f * (ev * dd + od * ds);
+            acc += Mrest * (sgs * (base0 + bEd) + 2.f * m0 * bEd + sgd * bOd);
+        } else {
+            acc += ev * (base0 + bEd) + 2.f * bEd + od * bOd;
+            if (fp) {
+                adv = fmaf(q[NSVD_DIR_VDIF * es], od * (base0 + bEd) + (2.f + ev) * bOd, adv);
+                lv += q[NSVD_DIR_VSUM2 * es];
+            }
+        }
+    }
+    const float eps2 = (float)((double)prob.eps * (double)prob.eps);
+    const float spc = prob.use_importance ? fmaxf(sp0, NSVD_SQRT_P_CLAMP) : 1.f;
+    const float lap = ((c * (sp0 * mk0)) * acc / eps2) / spc;
+    const float fs = (sp0 * (c * base0 * (mk0 * w.M0))) / spc;
+    NsvdFdOut o;
+    o.f = fs;
+    if (fp) {
+        o.Tf = prob.op_scale * nsvd_fp_apply(prob, lap, fs, (c * (sp0 * mk0)) / spc, adv, lv, eps2) + prob.op_shift * fs;
+    } else {
+        const float H = -prob.scale_kinetic * lap + w.V * fs;
+        o.Tf = prob.op_scale * (-H) + prob.op_shift * fs;
+    }
+    const float wt = (sp0 / spc) * c;
+    o.jac = wt * (mk0 * w.M0);
+    o.dsc = has_mask ? wt * base0 * (mk0 * w.M0) * r0 / (s_l * s_l) : 0.f;
     return o;
 }
 

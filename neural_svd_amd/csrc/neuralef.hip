@@ -361,7 +361,8 @@ extern "C" int nsvd_nef_operator_forward(const nsvd_model_desc* desc, const nsvd
     if (!desc || !params || !prob || !x || !phi || !Tphi || !h || !r || !stats || !norm_biased || !norm_unbiased ||
         !initialized || !ws || B <= 0)
         return NSVD_EINVAL;
-    if (desc->D < 1 || desc->D > NSVD_FD_MAXD || desc->L <= 0) return NSVD_EINVAL;
+    if (desc->D < 1 || desc->L <= 0) return NSVD_EINVAL;
+    if (desc->D > NSVD_FD_MAXD) return NSVD_EUNSUPPORTED;  // (the per-point batch norms stop at the small stencil)
     if (desc->has_exp_mask && !params->scales) return NSVD_EINVAL;
     if (ws_bytes < nsvd_workspace_bytes(desc, B) || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
     const int st = nsvd_problem_status(*desc, *prob);

@@ -34,17 +34,38 @@ static inline NsvdBox nsvd_box_of(const nsvd_model_desc& d) {
 // implements: others.py:23-24 divides by the UNCLAMPED sqrt p (equal to the clamped one only from 1e-5 up), takes every
 // derivative by central differences (eps > 0; with eps <= 0 the reference's own einsum fails) and main's problems.py
 // asserts against the Gaussian sampler; no box mask is defined for the periodic problems.
+// Input dimensions above NSVD_SMALL_D (= NSVD_FD_MAXD, fd_math.h) take the direction-loop epilogue and the table pointer
+// of ABI 5, up to NSVD_MAX_D, in the finite-difference mode only.
+#define NSVD_SMALL_D 4
+#define NSVD_MAX_D 12
 static inline int nsvd_problem_status(const nsvd_model_desc& d, const nsvd_problem& p) {
-    if (p.potential < NSVD_POT_HYDROGEN || p.potential > NSVD_POT_SIN_OF_COS) return NSVD_EINVAL;
+    if ((p.potential < NSVD_POT_HYDROGEN || p.potential > NSVD_POT_SIN_OF_COS) && p.potential != NSVD_POT_MOLECULE)
+        return NSVD_EINVAL;
     if (p.use_importance < NSVD_IMP_NONE || p.use_importance > NSVD_IMP_UNIFORM) return NSVD_EINVAL;
     if (p.operator_kind < NSVD_OP_SCHROEDINGER || p.operator_kind > NSVD_OP_FOKKER_PLANCK) return NSVD_EINVAL;
+    if (p.n_particles < 0 || p.n_nuclei < 0 || p.pot_table_len < 0) return NSVD_EINVAL;
+    const int np = p.n_particles > 0 ? p.n_particles : 1;
+    if (p.potential == NSVD_POT_MOLECULE) {
+        if (p.operator_kind == NSVD_OP_FOKKER_PLANCK) return NSVD_EINVAL;
+        if (p.n_nuclei < 1 || d.D % np != 0) return NSVD_EINVAL;
+        const int sd = d.D / np;
+        if (sd != 2 && sd != 3) return NSVD_EINVAL;
+        if (!p.pot_table || p.pot_table_len != p.n_nuclei * (sd + 1)) return NSVD_EINVAL;
+    } else if (d.D % np != 0) {
+        return NSVD_EINVAL;
+    }
+    if (d.D > NSVD_SMALL_D && (p.potential == NSVD_POT_COSINE || p.potential == NSVD_POT_SIN_OF_COS) &&
+        (!p.pot_table || p.pot_table_len != d.D))
+        return NSVD_EINVAL;
+    if (d.D > NSVD_MAX_D) return NSVD_EUNSUPPORTED;
+    if (d.D > NSVD_SMALL_D && !(p.eps > 0.f)) return NSVD_EUNSUPPORTED;
     if (p.operator_kind != NSVD_OP_FOKKER_PLANCK) return p.potential == NSVD_POT_SIN_OF_COS ? NSVD_EINVAL : 0;
     if (p.potential != NSVD_POT_SIN_OF_COS || !(p.eps > 0.f) || p.use_importance == NSVD_IMP_GAUSSIAN ||
         d.box_mask != NSVD_BOX_NONE)
         return NSVD_EUNSUPPORTED;
     if (p.use_importance == NSVD_IMP_UNIFORM) {
         if (!(p.sigma > 0.f)) return NSVD_EINVAL;
-        const double sqrt_p = exp(-0.5 * (double)d.D * log(2.0 * (double)p.sigma));
+        const double sqrt_p = exp(-0.5 * (double)(d.D / np) * log(2.0 * (double)p.sigma));
         if (sqrt_p < (double)NSVD_SQRT_P_CLAMP) return NSVD_EUNSUPPORTED;
     }
     return 0;
@@ -256,5 +277,33 @@ __device__ __forceinline__ void nsvd_sample_row(const NsvdSampler& s, int b, int
         sincosf(6.283185307179586f * u2, &sn, &cs);
         xr[2 * pr] = rad * cs;
         if (2 * pr + 1 < D) xr[2 * pr + 1] = rad * sn;
+    }
+}
+
+// Coordinates 4 blk .. 4 blk + 3 of sample b for 5 <= D <= NSVD_MAX_D: Philox block blk of the row (the block index in the
+// counter word that is a constant for D <= 4, whose streams nsvd_sample_row keeps: block 0 of this path is another
+// word too), the same two Box-Muller pairs per block. One Philox block and one logf / sincosf per pair; xr is indexed
+// by constants only, n = min(4, D - 4 blk) of its entries are meaningful.
+__device__ __forceinline__ void nsvd_sample_block_nd(const NsvdSampler& s, int b, int blk, int n, float* xr) {
+    unsigned r[4];
+    const unsigned long long off = s.offset + (s.offset_add ? *s.offset_add : 0ull);
+    nsvd_philox4x32_10((unsigned)b, (unsigned)off, (unsigned)(off >> 32), 0x6e737664u + (unsigned)(1 + blk),
+                       (unsigned)s.seed, (unsigned)(s.seed >> 32), r);
+    if (s.kind == NSVD_IMP_UNIFORM) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) xr[k] = s.sigma * (2.0f * (((float)(r[k] >> 9) + 0.5f) * (1.0f / 8388608.0f)) - 1.0f);
+        return;
+    }
+#pragma unroll
+    for (int pr = 0; pr < 2; ++pr) {
+        xr[2 * pr] = xr[2 * pr + 1] = 0.f;
+        if (2 * pr >= n) continue;
+        const float u1 = ((float)(r[2 * pr] >> 9) + 0.5f) * (1.0f / 8388608.0f);
+        const float u2 = ((float)(r[2 * pr + 1] >> 9) + 0.5f) * (1.0f / 8388608.0f);
+        const float rad = s.sigma * sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincosf(6.283185307179586f * u2, &sn, &cs);
+        xr[2 * pr] = rad * cs;
+        xr[2 * pr + 1] = rad * sn;
     }
 }

@@ -80,6 +80,7 @@ bool nsvd_fused_model_supported(const nsvd_model_desc& d, int B);
 int nsvd_fused_model_forward(const nsvd_model_desc& d, const nsvd_params& p, const float* x, int B, float c,
                              float* out, void* ws, int save, hipStream_t s);
 bool nsvd_fused_supported(const nsvd_model_desc& d, int B, bool exact = false);
+bool nsvd_fused_split_nd_supported(const nsvd_model_desc& d, int B);  // 5 <= D <= 12, stencil mode, explicit request
 size_t nsvd_fused_workspace_bytes(const nsvd_model_desc& d, int B);
 // Fourier features of x into the fused path's workspace (phi, and phiT_c when save != 0)
 int nsvd_fused_features(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,

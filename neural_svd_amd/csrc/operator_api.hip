@@ -40,7 +40,9 @@ struct GenericWs {
 
 // plain model evaluation (nsvd_model_forward / _backward) has no stencil: any input dimension up to 64
 constexpr int MODEL_MAX_D = 64;
-int validate(const nsvd_model_desc* d, int max_d = 4) {
+// the operator: NSVD_MAX_D input dimensions (above NSVD_SMALL_D in the finite-difference mode on the generic kernels only:
+// nsvd_problem_status)
+int validate(const nsvd_model_desc* d, int max_d = NSVD_MAX_D) {
     if (!d) return NSVD_EINVAL;
     if (d->L <= 0 || d->D <= 0 || d->m <= 0) return NSVD_EINVAL;
     if (d->nlayers < 1 || d->nlayers > NSVD_MAX_LAYERS) return NSVD_EINVAL;
@@ -102,6 +104,9 @@ GenericWs carve(const nsvd_model_desc& d, int B, void* base, int erows = 0) {
 // exact: the exact-Laplacian mode (prob->eps <= 0), whose D + 2 jet streams fit the MFMA path up to D = 3
 bool want_fused(const nsvd_model_desc& d, int B, int path, bool exact = false) {
     if (path == NSVD_PATH_GENERIC) return false;  // NSVD_PATH_FUSED and NSVD_PATH_FUSED_BF16X3 both need the MFMA path
+    // above the small stencil: the split form on explicit request only - NSVD_PATH_AUTO stays on the generic kernels
+    // until the two are measured against each other
+    if (d.D > NSVD_SMALL_D) return path == NSVD_PATH_FUSED && !exact && nsvd_fused_split_nd_supported(d, B);
     return nsvd_fused_supported(d, B, exact);
 }
 
@@ -227,11 +232,14 @@ extern "C" int nsvd_step_emits_planes(const nsvd_model_desc* desc, int B, int pa
 }
 
 extern "C" const char* nsvd_path_name_for(const nsvd_model_desc* desc, const nsvd_problem* prob, int B, int path) {
-    if (validate(desc) != 0 || B <= 0 || !prob) return "invalid";
+    // (more input dimensions than the stencil carries are nsvd_problem_status' to answer: "unsupported")
+    if (validate(desc, MODEL_MAX_D) != 0 || B <= 0 || !prob) return "invalid";
     const int st = validate_problem(desc, prob);
     if (st) return st == NSVD_EUNSUPPORTED ? "unsupported" : "invalid";
     const bool exact = !(prob->eps > 0.f);
     if (want_fused(*desc, B, path, exact)) return "fused_mfma";
+    // (above NSVD_SMALL_D an explicitly fused path has nothing to fall back to: the entry points return NSVD_EUNSUPPORTED)
+    if (desc->D > NSVD_SMALL_D && (path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3)) return "unsupported";
     return exact ? "unsupported" : "generic";
 }
 
@@ -245,7 +253,8 @@ extern "C" size_t nsvd_model_workspace_bytes(const nsvd_model_desc* desc, int B)
 extern "C" size_t nsvd_workspace_bytes(const nsvd_model_desc* desc, int B) {
     if (validate(desc) != 0 || B <= 0) return 0;
     const size_t gen = carve(*desc, B, nullptr).bytes;
-    const size_t fus = nsvd_fused_supported(*desc, B, true) ? nsvd_fused_workspace_bytes(*desc, B) : 0;
+    const size_t fus = (nsvd_fused_supported(*desc, B, true) || nsvd_fused_split_nd_supported(*desc, B))
+                           ? nsvd_fused_workspace_bytes(*desc, B) : 0;
     return gen > fus ? gen : fus;
 }
 
@@ -440,7 +449,7 @@ int backward_evd_impl(const nsvd_model_desc* desc, const nsvd_params* params, co
     // opt2: the step of any rule (nsvd_operator_backward_evd_opt_step) - instead of `opt`, never both
     // model_mode: the forward was nsvd_model_forward (plain model evaluation, any input dimension up to 64, no
     // Hamiltonian): Tf is whatever operator output the caller computed from f (the kernel-operator path)
-    int rc = validate(desc, model_mode ? MODEL_MAX_D : 4);
+    int rc = validate(desc, model_mode ? MODEL_MAX_D : NSVD_MAX_D);
     if (rc) return rc;
     if ((!prob && !model_mode) || !x || !f || !Tf || !ws || B <= 0) return NSVD_EINVAL;
     // direct mode (fused path): neither reduced moments nor partial sums - the backward kernel takes the moments it

@@ -924,6 +924,18 @@ bool nsvd_fused_supported(const nsvd_model_desc& d, int B, bool exact) {
     return fused_shape_ok(d, B);
 }
 
+// ---- Part B: the split-stencil form above the small stencil (5 <= D <= NSVD_MAX_D), finite-difference mode, float32
+// MFMA, on explicit request only (operator_api.hip: want_fused). The E = 3 split instance runs D direction groups -
+// one direction's two points plus the centre per workgroup - without the in-kernel last-arriver epilogue (its
+// NSVD_FD_MAXD arrays stay D <= 3): the raw head outputs go to the direction-loop epilogue kernel.
+bool nsvd_fused_split_nd_supported(const nsvd_model_desc& d, int B) {
+    if (d.D <= NSVD_SMALL_D || d.D > NSVD_MAX_D) return false;
+    // base_raw (L, (1 + 2 D) B) and the launch's D (B / 32) L workgroups: well inside 32-bit indices
+    if ((size_t)d.L * (1 + 2 * (size_t)d.D) * (size_t)B * sizeof(float) >= ((size_t)1 << 32)) return false;
+    if ((size_t)d.D * (size_t)(B / BS) * (size_t)d.L >= ((size_t)1 << 31)) return false;
+    return fused_shape_ok(d, B);
+}
+
 size_t nsvd_fused_workspace_bytes(const nsvd_model_desc& d, int B) { return carve_fused(d, B, nullptr).bytes; }
 
 FusedWsView nsvd_fused_ws_view(const nsvd_model_desc& d, int B, void* ws) {
@@ -946,6 +958,8 @@ int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsv
                        int B, float* f, float* Tf, void* ws, int save, hipStream_t s, int bf3, int raw) {
     // raw (NeuralEF): leave the raw head outputs in w.base_raw, f / Tf not written (float32 stencil forms only)
     if (raw && (bf3 || prob.eps <= 0.f)) return NSVD_EUNSUPPORTED;
+    // above three dimensions: the float32 split form of the finite-difference mode only (nsvd_fused_split_nd_supported)
+    if (d.D > 3 && (bf3 || raw || !(prob.eps > 0.f) || !nsvd_fused_split_nd_supported(d, B))) return NSVD_EUNSUPPORTED;
     const FusedWs w = carve_fused(d, B, ws);
     const int E = 1 + 2 * d.D, R = E * B, F = 2 * d.m;
     int rc = 0;
@@ -1037,7 +1051,9 @@ int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsv
     }
     // split-stencil form: D = 3 (7 stencil columns do not fit one workgroup's LDS image), and D = 2 when the plain grid
     // would leave at least half of the CUs without a workgroup (cfg1: 64 -> 128 workgroups of three column tiles)
-    if (d.D == 3 || (d.D == 2 && (B / BS) * d.L <= 128)) {
+    // (5 <= D <= 12: the same instance, D direction groups, ks = 1 and no tickets: the centre tile is recomputed D times,
+    // 3 D tiles against the 2 D + 1 needed, and nsvd_fd_epilogue takes its direction-loop kernel)
+    if (d.D >= 3 || (d.D == 2 && (B / BS) * d.L <= 128)) {
         a.split = d.D;
         a.base_raw = w.base_raw;
         a.ks = d.D == 2 ? fwd_kslices(d, B) : 1;

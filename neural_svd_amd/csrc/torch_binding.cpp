@@ -114,7 +114,8 @@ struct Problem {
     nsvd_problem q;
     Problem(int potential, double charge_or_k, double eps, double op_scale, double op_shift, double sigma,
             double scale_kinetic, double hard_mul_const, int use_importance, int operator_kind, double fp_scale,
-            std::vector<double> pot_coef) {
+            std::vector<double> pot_coef, int n_particles = 0, int n_nuclei = 0, double pot_const = 0.0,
+            c10::optional<at::Tensor> pot_table = c10::nullopt) {
         memset(&q, 0, sizeof(q));
         q.potential = potential;
         q.charge_or_k = (float)charge_or_k;
@@ -129,7 +130,19 @@ struct Problem {
         q.operator_kind = operator_kind;  // NSVD_OP_*
         q.fp_scale = (float)fp_scale;
         for (size_t i = 0; i < pot_coef.size(); ++i) q.pot_coef[i] = (float)pot_coef[i];
+        // ABI 5: the table travels by device pointer, kept alive here
+        q.n_particles = n_particles;
+        q.n_nuclei = n_nuclei;
+        q.pot_const = (float)pot_const;
+        if (pot_table) {
+            TORCH_CHECK(pot_table->is_cuda() && pot_table->scalar_type() == at::kFloat && pot_table->is_contiguous(),
+                        "pot_table must be a contiguous float32 tensor that lives on the GPU");
+            table = *pot_table;
+            q.pot_table = table.data_ptr<float>();
+            q.pot_table_len = (int32_t)table.numel();
+        }
     }
+    at::Tensor table;
 };
 
 void see_params(Dev& dv, const ParamSet& ps) {
@@ -386,7 +399,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     py::class_<ParamSet>(m, "ParamSet")
         .def(py::init<const Shape&, std::vector<at::Tensor>, std::vector<at::Tensor>, c10::optional<at::Tensor>,
                       c10::optional<at::Tensor>>());
-    py::class_<Problem>(m, "Problem").def(py::init<int, double, double, double, double, double, double, double, int, int, double, std::vector<double>>());
+    py::class_<Problem>(m, "Problem").def(py::init<int, double, double, double, double, double, double, double, int, int, double, std::vector<double>, int, int, double, c10::optional<at::Tensor>>(),
+             py::arg("potential"), py::arg("charge_or_k"), py::arg("eps"), py::arg("op_scale"), py::arg("op_shift"),
+             py::arg("sigma"), py::arg("scale_kinetic"), py::arg("hard_mul_const"), py::arg("use_importance"),
+             py::arg("operator_kind"), py::arg("fp_scale"), py::arg("pot_coef"), py::arg("n_particles") = 0,
+             py::arg("n_nuclei") = 0, py::arg("pot_const") = 0.0, py::arg("pot_table") = py::none());
     py::class_<Rmsprop>(m, "Rmsprop")
         .def(py::init<const ParamSet&, const ParamSet*, double, double, double, double, c10::optional<at::Tensor>>(),
              py::keep_alive<1, 2>(), py::keep_alive<1, 3>());

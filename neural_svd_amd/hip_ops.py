@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import (MASK_CUSTOM, MASK_JOINT, MASK_SEQUENTIAL, PATH_AUTO, PATH_FUSED, PATH_FUSED_BF16X3,  # noqa: F401
                    PATH_GENERIC,
-                   BOX_EXP, BOX_NONE, BOX_SQRT, IMP_GAUSSIAN, IMP_NONE, IMP_UNIFORM, POT_HARMONIC, POT_HYDROGEN, POT_ZERO, POT_COSINE, POT_H2_ION, POT_SIN_OF_COS, OP_SCHROEDINGER, OP_FOKKER_PLANCK,
+                   BOX_EXP, BOX_NONE, BOX_SQRT, IMP_GAUSSIAN, IMP_NONE, IMP_UNIFORM, POT_HARMONIC, POT_HYDROGEN, POT_ZERO, POT_COSINE, POT_H2_ION, POT_SIN_OF_COS, POT_MOLECULE, OP_SCHROEDINGER, OP_FOKKER_PLANCK,
                    ModelDesc, NsvdError, Params, Problem, check)
 
 
@@ -67,9 +67,16 @@ def _tb_params(shape: "ModelShape", params: Params):
 def _tb_problem(prob: Problem):
     q = getattr(prob, "_tb", None)
     if q is None:
+        if prob.pot_table and getattr(prob, "_pot_table", None) is None:
+            # the binding takes the table as a tensor: a struct whose pointer was set by hand would silently become a
+            # null-table problem here - make_problem(pot_table=) is the way in for both bindings
+            raise NsvdError("Problem.pot_table was set directly: build the problem with make_problem(pot_table=tensor) "
+                            "so that the tensor binding receives the table too")
         q = prob._tb = _TB.Problem(prob.potential, prob.charge_or_k, prob.eps, prob.op_scale, prob.op_shift, prob.sigma,
                                    prob.scale_kinetic, prob.hard_mul_const, int(prob.use_importance),
-                                   int(prob.operator_kind), prob.fp_scale, [float(c) for c in prob.pot_coef])
+                                   int(prob.operator_kind), prob.fp_scale, [float(c) for c in prob.pot_coef],
+                                   int(prob.n_particles), int(prob.n_nuclei), float(prob.pot_const),
+                                   getattr(prob, "_pot_table", None))
     return q
 
 
@@ -165,11 +172,15 @@ class ModelShape:
 def make_problem(potential: int, charge_or_k: float, eps: float, op_scale: float, op_shift: float, sigma: float,
                  scale_kinetic: float = 1.0, hard_mul_const: float = 1.0, use_importance: bool = True,
                  importance_kind: Optional[int] = None, operator_kind: int = OP_SCHROEDINGER, fp_scale: float = 0.0,
-                 pot_coef: Sequence[float] = ()) -> Problem:
+                 pot_coef: Sequence[float] = (), n_particles: int = 0, pot_table: Optional[torch.Tensor] = None,
+                 n_nuclei: int = 0, pot_const: float = 0.0) -> Problem:
     """importance_kind (IMP_NONE / IMP_GAUSSIAN / IMP_UNIFORM) names the density when given; otherwise use_importance
     chooses between none and the Gaussian. ``sigma`` is the sampling scale of either density. ``pot_coef``: cs of
     POT_COSINE / POT_SIN_OF_COS (one per input dimension) or (R,) of POT_H2_ION; ``operator_kind`` OP_FOKKER_PLANCK
-    (with POT_SIN_OF_COS) applies fp_scale (Lap f + grad V . grad f + f Lap V) instead of the Hamiltonian."""
+    (with POT_SIN_OF_COS) applies fp_scale (Lap f + grad V . grad f + f Lap V) instead of the Hamiltonian.
+    ABI 5: ``n_particles`` electrons share the D coordinates (0 is read as 1); ``pot_table`` is a float32 DEVICE tensor,
+    kept alive by the returned object - cs[0..D) of POT_COSINE / POT_SIN_OF_COS above 4 input dimensions, or the
+    ``n_nuclei`` rows (R_0, .., R_{d-1}, Z) of POT_MOLECULE, whose nuclear repulsion energy is ``pot_const``."""
     p = Problem()
     p.potential = int(potential)
     p.charge_or_k = float(charge_or_k)
@@ -190,6 +201,13 @@ def make_problem(potential: int, charge_or_k: float, eps: float, op_scale: float
     p.fp_scale = float(fp_scale)
     for i, c in enumerate(pot_coef):
         p.pot_coef[i] = float(c)
+    p.n_particles = int(n_particles)
+    p.n_nuclei = int(n_nuclei)
+    p.pot_const = float(pot_const)
+    if pot_table is not None:
+        p.pot_table = _ptr(pot_table, "pot_table")
+        p.pot_table_len = int(pot_table.numel())
+        p._pot_table = pot_table  # the struct holds a raw address: pin the tensor to it
     return p
 
 

@@ -7,7 +7,10 @@ OperatorWrapper, get_problem, the Gaussian sampler / importance and the analytic
     OperatorWrapper                                     examples/__init__.py:1-9
     cosine_potential / hydrogen_mol_ion_potential       examples/operator/pde/schrodinger/potentials.py:11-17,30-31
     NegativeLinearFokkerPlanck / sin_of_cos_potential   examples/operator/pde/others.py:6-34
-    get_problem                                         examples/operator/pde/problems.py:23-130 (all but quantum_chemistry)
+    nuclear_energy / nuclear_potential / electronic_potential / local_potential_energy   potentials.py:35-57
+    Molecule                                            examples/operator/pde/schrodinger/molecule.py
+    get_problem                                         examples/operator/pde/problems.py:23-130 (ndim 5 / 10 and
+                                                        quantum_chemistry under args.high_dim_stencil)
     get_dataloader                                      examples/operator/pde/main_pde.py:89-130 (gaussian sampler)
     Hydrogen2D / HarmonicOscillator .get_eigvals        examples/operator/pde/schrodinger/ground_truths.py:78-90,120-132
     InfiniteWell2D.get_eigvals                          examples/operator/pde/schrodinger/ground_truths.py:40-58
@@ -74,6 +77,108 @@ def sin_of_cos_potential(xs, cs):
     return torch.sin((torch.cos(xs) * _coefs(cs, xs)).sum(-1))
 
 
+# ---- quantum chemistry (potentials.py:35-57): rs is (batch, n_electrons, ndim), mol carries coords (n_nuclei, ndim) and
+# charges (n_nuclei,). The HIP kernels evaluate the same sum in their epilogue (fd_math.h: nsvd_molecule_potential).
+def nuclear_energy(mol):
+    """sum_{a<b} Z_a Z_b / |R_a - R_b|: the nuclear repulsion energy, a constant of the molecule"""
+    coords, charges = mol.coords, mol.charges
+    coulombs = charges[:, None] * charges / (coords[:, None] - coords).norm(dim=-1)
+    return coulombs.triu(1).sum()
+
+
+def nuclear_potential(rs, mol):
+    """-sum_i sum_a Z_a / |r_i - R_a|"""
+    dists = (rs[:, :, None] - mol.coords).norm(dim=-1)
+    return -(mol.charges / dists).sum(dim=(-1, -2))
+
+
+def electronic_potential(rs):
+    """sum_{i<j} 1 / |r_i - r_j|"""
+    i, j = np.triu_indices(rs.shape[-2], k=1)
+    dists = (rs[:, :, None] - rs[:, None, :])[:, i, j].norm(dim=-1)
+    return (1 / dists).sum(dim=-1)
+
+
+def local_potential_energy(rs, mol):
+    return nuclear_energy(mol) + nuclear_potential(rs, mol) + electronic_potential(rs)
+
+
+ANGSTROM = 1 / 0.52917721092  # bohr per angstrom, the reference's constant (molecule.py)
+
+# The package's own table of small systems, from public data: atoms at the origin, H2+ with its nuclei at
+# x = +-0.52918 angstrom (2 bohr apart), bond lengths H2 0.742 and LiH 1.595 angstrom.
+_SYSTEMS = {
+    "H": dict(coords=[[0.0, 0.0, 0.0]], charges=[1], charge=0, spin=1, unit="angstrom"),
+    "He": dict(coords=[[0.0, 0.0, 0.0]], charges=[2], charge=0, spin=0, unit="angstrom"),
+    "Li": dict(coords=[[0.0, 0.0, 0.0]], charges=[3], charge=0, spin=1, unit="angstrom"),
+    "Be": dict(coords=[[0.0, 0.0, 0.0]], charges=[4], charge=0, spin=0, unit="angstrom"),
+    "B": dict(coords=[[0.0, 0.0, 0.0]], charges=[5], charge=0, spin=1, unit="angstrom"),
+    "H2+": dict(coords=[[-0.52918, 0.0, 0.0], [0.52918, 0.0, 0.0]], charges=[1, 1], charge=1, spin=1,
+                unit="angstrom"),
+    "H2": dict(coords=[[0.0, 0.0, 0.0], [0.742, 0.0, 0.0]], charges=[1, 1], charge=0, spin=0, unit="angstrom"),
+    "LiH": dict(coords=[[0.0, 0.0, 0.0], [1.595, 0.0, 0.0]], charges=[3, 1], charge=0, spin=0, unit="angstrom"),
+}
+
+
+def _load_systems(path):
+    try:
+        import tomllib as _toml
+        with open(path, "rb") as fh:
+            return _toml.load(fh)
+    except ModuleNotFoundError:
+        pass
+    try:
+        import toml as _toml
+    except ModuleNotFoundError:
+        raise NsvdError(f"Molecule.from_name: reading {path} needs tomllib (Python 3.11) or the toml package; neither "
+                        f"is importable - pass `systems` as a dict instead") from None
+    return _toml.load(path)
+
+
+class Molecule(torch.nn.Module):
+    """A molecule: nuclear coordinates (rows, atomic units after the unit conversion) and charges, its total charge and
+    spin (molecule.py). ``coords`` / ``charges`` are buffers, float32 when built from Python numbers."""
+
+    all_names = set(_SYSTEMS.keys())
+
+    def __init__(self, coords, charges, charge, spin, unit="bohr", data=None):
+        assert len(coords) == len(charges)
+        super().__init__()
+        unit_multiplier = {"bohr": 1.0, "angstrom": ANGSTROM}[unit]
+        self.register_buffer("coords", unit_multiplier * torch.as_tensor(coords))
+        self.register_buffer("charges", 1.0 * torch.as_tensor(charges))
+        self.charge = charge
+        self.spin = spin
+        self.data = data or {}
+
+    def __len__(self):
+        return len(self.charges)
+
+    def __iter__(self):
+        yield from zip(self.coords, self.charges)
+
+    def __repr__(self):
+        return (f"Molecule(coords=\n{self.coords.cpu().numpy()},\n  charges={self.charges.cpu().numpy()},\n"
+                f"  charge={self.charge}, spin={self.spin}\n)")
+
+    @classmethod
+    def from_name(cls, name, systems=None, **kwargs):
+        """``systems``: a dict name -> {coords, charges, charge, spin, unit}, or the path of a TOML file holding one
+        (read with tomllib / toml when importable); default: this package's own small table (Molecule.all_names)."""
+        import copy
+        import os
+        if systems is None:
+            systems = _SYSTEMS
+        elif isinstance(systems, (str, os.PathLike)):
+            systems = _load_systems(systems)
+        if name not in systems:
+            raise KeyError(f"Molecule.from_name: no system {name!r} (known: {sorted(systems)})")
+        system = copy.deepcopy(dict(systems[name]))
+        system.update(kwargs)
+        coords = system.pop("coords")
+        return cls(coords, **system)
+
+
 def _potential_kind(ftn):
     """-> (NSVD_POT_*, charge_or_k, pot_coef) of a potential function of this module (or a partial of one)"""
     base, kw = ftn, {}
@@ -89,20 +194,29 @@ def _potential_kind(ftn):
         if "cs" not in kw:
             raise NsvdError(f"{base.__name__}: bind the coefficients, partial({base.__name__}, cs=[...])")
         cs = tuple(float(c) for c in kw["cs"])
-        if len(cs) > _MAX_STENCIL_DIM:
-            raise NotImplementedError(f"{base.__name__} with {len(cs)} coefficients: {_TOO_MANY_DIMS}")
+        if len(cs) > _MAX_HIGH_DIM:
+            raise NotImplementedError(f"{base.__name__} with {len(cs)} coefficients: {_TOO_MANY_HIGH_DIMS}")
         return (H.POT_COSINE if base is cosine_potential else H.POT_SIN_OF_COS), 0.0, cs
     if base is hydrogen_mol_ion_potential:
         if "R" not in kw:
             raise NsvdError("hydrogen_mol_ion_potential: bind the half-distance, partial(..., R=..., charge=...)")
         return H.POT_H2_ION, float(kw.get("charge", 2.0)), (float(kw["R"]),)
+    if base is local_potential_energy:
+        if "mol" not in kw:
+            raise NsvdError("local_potential_energy: bind the molecule, partial(local_potential_energy, mol=...)")
+        return H.POT_MOLECULE, 0.0, ()
     raise NsvdError("HIP path supports hydrogen_potential, harmonic_oscillator_potential, infinite_well_potential, "
-                    "cosine_potential, hydrogen_mol_ion_potential and (Fokker-Planck) sin_of_cos_potential only")
+                    "cosine_potential, hydrogen_mol_ion_potential, local_potential_energy and (Fokker-Planck) "
+                    "sin_of_cos_potential only")
 
 
 _MAX_STENCIL_DIM = 4  # NSVD_FD_MAXD (csrc/fd_math.h); the fused MFMA kernels take D <= 3
 _TOO_MANY_DIMS = ("the finite-difference stencil of the HIP kernels carries at most 4 input dimensions (NSVD_FD_MAXD; "
                   "the fused MFMA kernels 3) - ndim 5 and 10 are not built")
+
+
+_MAX_HIGH_DIM = 12  # NSVD_MAX_D (csrc/nsvd_common.h): the direction-loop stencil, finite-difference mode, generic kernels
+_TOO_MANY_HIGH_DIMS = "the finite-difference stencil of the HIP kernels carries at most 12 input dimensions (NSVD_MAX_D)"
 
 
 class ProblemConfigError(AssertionError, NotImplementedError):
@@ -119,6 +233,7 @@ class NegativeHamiltonian:
         self.scale_kinetic = scale_kinetic
         self.laplacian_eps = laplacian_eps
         self.n_particles = n_particles
+        self.mol = local_potential_ftn.keywords["mol"] if self.potential_kind == H.POT_MOLECULE else None
         # laplacian_eps <= 0: exact Laplacian (reference diff_ops.py:7,54-61) - forward-mode jets on the MFMA path
 
     def __call__(self, f, xs, importance=None, threshold=1e5):
@@ -285,13 +400,31 @@ def fused_problem_of(operator, importance, model) -> H.Problem:
     ham = operator.operator
     kind = H.IMP_NONE if importance is None else \
         (H.IMP_UNIFORM if isinstance(importance, UniformImportance) else H.IMP_GAUSSIAN)
-    if kind == H.IMP_UNIFORM and importance.ndim != model.shape.D:
-        # the kernel's exponent is the model's input dimension; the reference's is args.ndim (equal: n_particles is 1)
+    D = model.shape.D
+    n_particles = int(getattr(ham, "n_particles", 1) or 1)
+    if D % n_particles:
+        raise NsvdError(f"fused operator kernel: {n_particles} particles on a model of input dimension {D}")
+    if kind == H.IMP_UNIFORM and importance.ndim != D // n_particles:
+        # the kernel's exponent is the space dimension D / n_particles, as the reference's args.ndim (main_pde.py:118)
         raise NsvdError(f"fused operator kernel: UniformImportance(ndim={importance.ndim}) on a model of input "
-                        f"dimension {model.shape.D}")
-    if len(ham.potential_coef) != (1 if ham.potential_kind == H.POT_H2_ION else model.shape.D) and ham.potential_coef:
+                        f"dimension {D} with {n_particles} particle(s)")
+    if len(ham.potential_coef) != (1 if ham.potential_kind == H.POT_H2_ION else D) and ham.potential_coef:
         raise NsvdError(f"fused operator kernel: {len(ham.potential_coef)} potential coefficients on a model of input "
-                        f"dimension {model.shape.D}")
+                        f"dimension {D}")
+    # ABI 5: tables longer than pot_coef (cs above 4 dimensions, the molecule's nuclei) travel as a device tensor
+    extra, coef = {}, ham.potential_coef
+    device = model.base.ws[0].device
+    if ham.potential_kind == H.POT_MOLECULE:
+        mol = ham.mol
+        sd = D // n_particles
+        if tuple(mol.coords.shape) != (len(mol.charges), sd):
+            raise NsvdError(f"fused operator kernel: molecule coordinates {tuple(mol.coords.shape)} with "
+                            f"{n_particles} particles on a model of input dimension {D}")
+        table = torch.cat([mol.coords.float(), mol.charges.float().view(-1, 1)], dim=1).contiguous().to(device)
+        extra = dict(pot_table=table, n_nuclei=len(mol.charges), pot_const=float(nuclear_energy(mol)))
+    elif len(coef) > _MAX_STENCIL_DIM:
+        extra = dict(pot_table=torch.tensor(coef, dtype=torch.float32, device=device))
+        coef = ()
     fp = operator.fokker_planck
     if fp and kind == H.IMP_GAUSSIAN:
         raise NsvdError("fused operator kernel: the Fokker-Planck operator with the Gaussian density goes through "
@@ -300,7 +433,8 @@ def fused_problem_of(operator, importance, model) -> H.Problem:
                           importance.sigma if importance is not None else 1.0, ham.scale_kinetic,
                           float(model.hard_mul_const), importance_kind=kind,
                           operator_kind=H.OP_FOKKER_PLANCK if fp else H.OP_SCHROEDINGER,
-                          fp_scale=float(ham.scale) if fp else 0.0, pot_coef=ham.potential_coef)
+                          fp_scale=float(ham.scale) if fp else 0.0, pot_coef=coef,
+                          n_particles=n_particles if n_particles > 1 else 0, **extra)
 
 
 # ----------------------------------------------------------------------------------- ground truths
@@ -384,12 +518,25 @@ def _periodic_asserts(args, name):
              f"{name}: needs --use_fourier_feature and --fourier_deterministic (integer harmonics)")
     _require(args.sampling_mode != "gaussian", f"{name}: not with the Gaussian sampler")
     _require(args.ndim in (1, 2, 5, 10), f"{name}: ndim 1, 2, 5 or 10")
-    if args.ndim > 2:
+    if args.ndim > 2 and not getattr(args, "high_dim_stencil", False):
         raise ProblemConfigError(f"{name} with ndim {args.ndim}: {_TOO_MANY_DIMS}")
+    if args.ndim > 2:
+        _require(args.laplacian_eps > 0, f"{name} with ndim {args.ndim}: the direction-loop stencil needs laplacian_eps "
+                                         f"> 0 (no exact-Laplacian mode above 4 input dimensions)")
+
+
+# cs and first eigenvalue of the 5-D and 10-D pair (problems.py:62-69, 106-111)
+_COSINE_5D_CS = (0.162944737278636, 0.181158387415124, 0.025397363258701, 0.182675171227804, 0.126471849245082)
+_COSINE_10D_CS = _COSINE_5D_CS + (0.019508080999882, 0.055699643773410, 0.109376303840997, 0.191501367086860,
+                                  0.192977707039855)
+_COSINE_HIGH_EIG = {5: 0.054018930536326, 10: 0.098087448866409}
+_FP_CS = {1: [1.0], 2: [1.0, 1.0], 5: [1.0, 0.8, 0.6, 0.4, 0.2], 10: [0.1, 0.3, 0.2, 0.5, 0.2, 0.1, 0.3, 0.4, 0.2, 0.2]}
 
 
 def get_problem(args, device=None):
-    """problems.py:23-130 without its quantum_chemistry branch. The cosine and Fokker-Planck branches of the reference
+    """problems.py:23-130. ndim 5 / 10 of the periodic pair and the quantum_chemistry branch (args.mol_name, ndim 2 or
+    3, n_particles * ndim <= 12) are accepted when ``args.high_dim_stencil`` is true and refused as before without it.
+    The cosine and Fokker-Planck branches of the reference
     read two names its own parser (main_pde.py) never defines; here ``args.use_gaussian_sampling`` is read as
     ``args.sampling_mode == "gaussian"`` and ``args.scale_operator`` as ``getattr(args, "scale_operator", 1.0)``.
     Refusals raise ProblemConfigError (an AssertionError, as the reference's asserts, and a NotImplementedError)."""
@@ -397,7 +544,7 @@ def get_problem(args, device=None):
     args.n_particles = 1
     if args.problem == "fp":
         _periodic_asserts(args, "problem fp")
-        cs = {1: [1.0], 2: [1.0, 1.0]}[args.ndim]
+        cs = _FP_CS[args.ndim]
         gt = np.array([0.0] + (args.neigs - 1) * [0.0])
         inner = NegativeLinearFokkerPlanck(local_potential_ftn=partial(sin_of_cos_potential, cs=cs),
                                            scale=getattr(args, "scale_operator", 1.0),
@@ -406,6 +553,7 @@ def get_problem(args, device=None):
         return op, args.operator_scale * gt + args.operator_shift
     if args.problem != "sch":
         raise NotImplementedError(f"problem {args.problem}: 'sch' and 'fp' are on the HIP path")
+    scale_kinetic = 1.0
     if args.potential_type == "hydrogen":
         pot = partial(hydrogen_potential, charge=args.charge)
         if args.ndim == 2:
@@ -423,6 +571,9 @@ def get_problem(args, device=None):
         _periodic_asserts(args, "potential_type cosine")
         if args.ndim == 1:
             cs = [1.0]
+        elif args.ndim > 2:
+            cs = list(_COSINE_5D_CS if args.ndim == 5 else _COSINE_10D_CS)
+            gt = np.array([_COSINE_HIGH_EIG[args.ndim]] + (args.neigs - 1) * [0.0])
         else:
             _require(args.neigs <= 25, "potential_type cosine: 25 eigenvalues are tabulated for ndim 2")
             cs = list(_COSINE_2D_CS)
@@ -431,10 +582,26 @@ def get_problem(args, device=None):
     elif args.potential_type == "hydrogen_mol_ion":
         # (each nucleus gets 2 * args.charge, as problems.py:77 passes it)
         pot = partial(hydrogen_mol_ion_potential, R=args.hydrogen_mol_ion_R, charge=2 * args.charge)
+    elif args.potential_type == "quantum_chemistry" and getattr(args, "high_dim_stencil", False):
+        assert args.ndim in [2, 3]  # as the reference (problems.py:80)
+        mol = Molecule.from_name(args.mol_name, systems=getattr(args, "mol_systems", None))
+        if device is not None:
+            mol = mol.to(device)
+        if args.ndim == 2:
+            mol.coords = mol.coords[:, :2]
+        pot = partial(local_potential_energy, mol=mol)
+        args.n_particles = int((mol.charges.sum() - mol.charge).type(torch.int).item())
+        scale_kinetic = 0.5
+        d = args.n_particles * args.ndim
+        _require(args.n_particles >= 1, f"quantum_chemistry {args.mol_name}: no electrons")
+        _require(d <= _MAX_HIGH_DIM, f"quantum_chemistry {args.mol_name} at ndim {args.ndim}: {d} input dimensions - "
+                                     f"{_TOO_MANY_HIGH_DIMS}")
+        _require(d <= _MAX_STENCIL_DIM or args.laplacian_eps > 0,
+                 f"quantum_chemistry with {d} input dimensions needs laplacian_eps > 0")
     else:
         raise NotImplementedError(f"potential_type {args.potential_type}: not in scope of the HIP path")
-    ham = NegativeHamiltonian(local_potential_ftn=pot, scale_kinetic=1.0, laplacian_eps=args.laplacian_eps,
-                              n_particles=1)
+    ham = NegativeHamiltonian(local_potential_ftn=pot, scale_kinetic=scale_kinetic, laplacian_eps=args.laplacian_eps,
+                              n_particles=args.n_particles)
     op = OperatorWrapper(ham, scale=args.operator_scale, shift=args.operator_shift)
     return op, (args.operator_scale * gt + args.operator_shift if gt is not None else None)
 
