@@ -515,7 +515,10 @@ int nsvd_operator_backward_evd_opt_step(const nsvd_model_desc* desc, const nsvd_
 /* compute_spectrum_evd accumulation for one chunk (methods/spectrum.py:56-75):
  *   w = sqrt(p_train(x)) / sqrt(p_val), phi = nan_to_num(w f), Tphi = nan_to_num(w Tf),
  *   Tphi rows with x ~ 0 zeroed, cov += phi^T phi, quad += phi^T Tphi   (cov, quad: (L, L)).
- * p_val = uniform on [-lim, lim]^D (main_pde.py:129-130). */
+ * p_val = uniform on [-lim, lim]^D (main_pde.py:129-130).
+ * use_importance (all three entry points): NSVD_IMP_NONE (p_train = 1) or NSVD_IMP_GAUSSIAN (the N(0, sigma^2 I) pdf,
+ * evaluated in the kernel). NSVD_IMP_UNIFORM returns NSVD_EUNSUPPORTED - that density is a constant: weight the rows
+ * by sqrt(p_train) and pass NSVD_IMP_NONE - and any other value NSVD_EINVAL; nothing is launched. L <= 64. */
 int nsvd_spectrum_accumulate(const float* f, const float* Tf, const float* x, int B, int L, int D,
                              float sigma, int use_importance, float lim, float* cov, float* quad,
                              void* stream);

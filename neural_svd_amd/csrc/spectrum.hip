@@ -69,6 +69,10 @@ static int spectrum_accumulate_impl(const float* f, const float* Tf, const float
                                     int use_importance, float lim, Acc* cov, Acc* quad, void* stream, int pad = 0) {
     if (!f || !Tf || !x || !cov || !quad || B <= 0 || L <= 0 || D <= 0 || pad < 0 || pad > 1) return NSVD_EINVAL;
     if (L > SMAXL) return NSVD_EUNSUPPORTED;
+    // the kernel evaluates the Gaussian density only: the uniform one is a constant the caller weights the rows by
+    // (trainer.spectrum, spectrum.compute_spectrum_evd) - not silently the Gaussian
+    if (use_importance == NSVD_IMP_UNIFORM) return NSVD_EUNSUPPORTED;
+    if (use_importance != NSVD_IMP_NONE && use_importance != NSVD_IMP_GAUSSIAN) return NSVD_EINVAL;
     // importance_val is built as a float32 tensor in the reference (main_pde.py:130)
     const float pval = (float)(1.0 / pow(2.0 * (double)lim, (double)D));
     const float inv_sqrt_val = 1.f / sqrtf(pval);

@@ -1239,12 +1239,14 @@ def test_head_sharded_backward_at_the_multi_gpu_rank_shape(world, rank):
 
 
 @pytest.mark.parametrize("W,B,L,kind", [(8, 512, 36, "joint"), (8, 4096, 55, "seq"), (3, 96, 5, "custom"), (4, 1280, 7, "seq"),
-                                        (8, 64, 8, "joint"), (2, 64, 8, "seq")])
+                                        (8, 64, 8, "joint"), (2, 64, 8, "seq"),
+                                        (8, 320, 64, "joint"), (3, 200, 96, "custom"), (8, 192, 128, "seq")])
 def test_gather_head_blocks_with_uneven_head_counts(W, B, L, kind):
     """nsvd_evd_gather_head_blocks: rank w's block of 2 B ceil(L / W) floats begins with its packed f (B, n_w) | Tf (B,
     n_w), n_w = L // W + (w < L % W) (the scripts' --neigs 36 / 55 on 8 ranks: 5 / 4 and 7 / 6 heads); the tail of a
     short block is poisoned with NaN and must never be read. f, Tf bit for bit the concatenation, the partial
-    moments bit for bit those of nsvd_evd_partial on them."""
+    moments bit for bit those of nsvd_evd_partial on them. At L = 64, 96, 128 nsvd_evd_partial cuts each chunk's block
+    over 4 / 4 / 8 workgroups (evd_partial_cuts) while the gather kernel never cuts: the same bits across cuts."""
     from neural_svd_amd.parallel import head_block, head_range
     g = torch.Generator().manual_seed(W * B + L)
     Lb = head_block(L, W)
