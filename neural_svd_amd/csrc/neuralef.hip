@@ -199,10 +199,14 @@ __global__ void __launch_bounds__(256) nef_align_kernel(NefLossArgs a) {
         // coeff_h (methods/neuralef.py:43-50): triu(G_h, diagonal) unbiased; biased: triu(Q_o) / (diag(Q_o) + 1e-5) by
         // row with Q_o the OTHER half's phi^T Tphi
         const float* G = a.gram + (size_t)(a.unbiased ? hh : 1 - hh) * LL;
+        // biased with the diagonal kept, chunked: coeff_ii = Q_ii / (Q_ii + 1e-5) is 1 to 1e-5 / Q_ii, and 2 align's own
+        // head term cancels 4 variance down to that remainder (all of d loss / d phi at L = 1, or once the off-diagonal
+        // of Q has gone): `coef` then holds coeff - I with the remainder formed directly, the identity's part added below
+        const bool own = !a.unbiased && a.diagonal == 0 && a.chunked;
         for (int t = threadIdx.x; t < LL; t += blockDim.x) {
             const int i = t / L, j = t - i * L;
             float v = (j - i >= a.diagonal) ? G[t] : 0.f;
-            if (!a.unbiased) v = v / (G[i * L + i] + 1e-5f);
+            if (!a.unbiased) v = (own && i == j) ? -1e-5f / (G[t] + 1e-5f) : v / (G[i * L + i] + 1e-5f);
             coef[t] = v;
         }
         const float* Tp = a.Tph[hh] + (size_t)r0 * L;
@@ -214,11 +218,13 @@ __global__ void __launch_bounds__(256) nef_align_kernel(NefLossArgs a) {
             const int k = t / L, m = t - k * L;
             float s = 0.f;
             for (int i = 0; i < L; ++i) s = fmaf(Ts[k * L + i], coef[i * L + m], s);
-            const float al = s / Bh;
+            const float al = own ? (s + Ts[t]) / Bh : s / Bh;
             const float pv = P[t];
             if (a.chunked) {
                 const float var = -Ts[t] / Bf;
-                a.dphi[(size_t)(r0 + (hh ? a.Bh[0] : 0)) * L + t] = 4.f * var + 2.f * al;
+                // own: 4 var + 2 al = 2 s / B_h + Tphi (2 / B_h - 4 / B), the bracket from the integers (0 at even B)
+                a.dphi[(size_t)(r0 + (hh ? a.Bh[0] : 0)) * L + t] =
+                    own ? 2.f * (s / Bh) + Ts[t] * ((float)(2 * a.B - 4 * a.Bh[hh]) / (Bh * Bf)) : 4.f * var + 2.f * al;
                 lsum += pv * var + 0.5f * (pv * al);
             } else {
                 a.dph[hh][(size_t)r0 * L + t] = 2.f * al;

@@ -35,7 +35,7 @@ def update_running(running, norms, momentum=MOMENTUM):
     return [rb, ru, init]
 
 
-def operator_forward(x, p: O.Params, prob: O.Problem, running=None, normalize=True, training=True):
+def operator_forward(x, p: O.Params, prob: O.Problem, running=None, normalize=True, training=True, momentum=MOMENTUM):
     """Tphi, phi of operator(BatchL2NormalizedFunctions(model), x, importance) (normalize=False: batchnorm_mode 'none').
     Returns a dict with phi, Tphi, the batch norms, the updated running norms and what the backward needs."""
     B, D = x.shape
@@ -43,7 +43,7 @@ def operator_forward(x, p: O.Params, prob: O.Problem, running=None, normalize=Tr
     us = wave_outputs(x, p, prob)
     if normalize and training:
         norms = [u.norm(dim=0, keepdim=True) / math.sqrt(B) for u in us]
-        running = update_running(running, norms)
+        running = update_running(running, norms, momentum)
     elif normalize:
         norms = [running[0]] * len(us)
     else:
@@ -101,9 +101,9 @@ def param_grads(x, p: O.Params, prob: O.Problem, du0):
     return O.operator_backward(dataclasses.replace(c, sp0=one, spc0=one), p, prob, du0)
 
 
-def train_step(x, p: O.Params, prob: O.Problem, running, unbiased, normalize=True, diagonal=1):
+def train_step(x, p: O.Params, prob: O.Problem, running, unbiased, normalize=True, diagonal=1, momentum=MOMENTUM):
     """one compute_loss_operator + backward; returns (fwd dict, loss, grads in Params.trainable() order)"""
-    fwd = operator_forward(x, p, prob, running, normalize)
+    fwd = operator_forward(x, p, prob, running, normalize, momentum=momentum)
     loss, dphi, _, _ = loss_and_dphi(fwd["phi"], fwd["Tphi"], unbiased, diagonal)
     if normalize:
         grads = param_grads(x, p, prob, norm_backward(dphi, fwd))

@@ -60,10 +60,10 @@ def test_loss_kernel(L, B):
 # ------------------------------------------------------------------------------------------------ full shapes
 def build_model(p: O.Params, hidden, fourier_scale=1.0):
     from neural_svd_amd.models import ExponentialMask, GaussianFourierFeatureTransform, ParallelMLP, WaveFunctions
-    L, m = p.ws[0].shape[0], p.fourier_B.shape[1]
-    fm = GaussianFourierFeatureTransform(2, mapping_size=m, scale=fourier_scale)
+    L, (D, m) = p.ws[0].shape[0], p.fourier_B.shape
+    fm = GaussianFourierFeatureTransform(D, mapping_size=m, scale=fourier_scale)
     fm._B.data = p.fourier_B.float().clone()
-    base = ParallelMLP(2, list(hidden), 1, L, "softplus", bias=True, feature_map=fm)
+    base = ParallelMLP(D, list(hidden), 1, L, "softplus", bias=True, feature_map=fm)
     for w, w0 in zip(base.ws, p.ws):
         w.data = w0.float().clone()
     for b, b0 in zip(base.bs, p.bs):
