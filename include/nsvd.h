@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define NSVD_ABI_VERSION 5
+#define NSVD_ABI_VERSION 6
 #define NSVD_MAX_LAYERS 8
 
 #define NSVD_EINVAL (-10001)
@@ -550,6 +550,22 @@ int nsvd_kernel_apply(const float* K, size_t ldk, int N, const long long* rows, 
                       int B2, const float* f, int L, float scale, float* out, void* ws, size_t ws_bytes,
                       void* stream);
 
+/* ---- next row: matrix-free radial kernel operator on coordinate batches (ABI 6) -------------------------------
+ * out[i][l] = scale * sum_j k(|x_i - y_j|) f[j][l]: the (Kf, f) producer of the same consumer contract
+ * (methods/nestedlora.py:230-252; x = x1, y = x2, f = model(x2), scale = 1 / B2) for a kernel given by a formula on
+ * coordinates drawn fresh every step - the definition oracle/nsvd_oracle.py:gaussian_kernel_apply restates in float64.
+ * NSVD_RBF_GAUSSIAN: k = exp(-d^2 / (2 ell^2)); NSVD_RBF_EXPONENTIAL: k = exp(-d / ell); d = |x_i - y_j| from direct
+ * differences (translation invariant). x: (B1, D), y: (B2, D), f: (B2, L), out: (B1, L), float32 row-major; x == y is
+ * allowed, out must not alias an input. Any B1, B2, L >= 1; 1 <= D <= 64 (NSVD_EUNSUPPORTED above); ell > 0. The
+ * (B1, B2) kernel matrix is never stored; partial sums over slices of the reference rows are reduced in slice order
+ * (no atomics: bit-reproducible). The workspace (256-byte aligned) holds padded copies of y and f^T and the partial
+ * tiles; its size is 0 for shapes outside these ranges. */
+#define NSVD_RBF_GAUSSIAN 0
+#define NSVD_RBF_EXPONENTIAL 1
+size_t nsvd_rbf_apply_workspace_bytes(int B1, int B2, int D, int L);
+int nsvd_rbf_apply(const float* x, int B1, const float* y, int B2, int D, const float* f, int L, int kind, float ell,
+                   float scale, float* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- next row: the CDK (two-tower) NestedLoRA loss ------------------------------------------------------
  * NestedLoRALossFunctionForCDK (methods/nestedlora.py:273-332) as called by NestedLoRAForCDK.compute_loss
  * (methods/nestedlora.py:366-378; examples/cdk/sketchy/main_sketchy.py:188).
@@ -847,7 +863,7 @@ int nsvd_retrieval_eval(const float* zq, long ldq, const float* zg, long ldg, in
  * DOMINANT kernel of the next nsvd_operator_forward call made by this host thread (the fused MFMA
  * forward kernel, or the layer-0 GEMM on the generic path), on that call's stream - or, whichever
  * comes first, around the first contraction (X W1^T) of the next nsvd_tower_forward / the gathered-row
- * contraction of the next nsvd_kernel_apply. One-shot; pass NULLs to clear. Per-thread state; the
+ * contraction of the next nsvd_kernel_apply / the main kernel of the next nsvd_rbf_apply. One-shot; pass NULLs to clear. Per-thread state; the
  * compute entry points themselves stay stateless. */
 int nsvd_profile_next_forward(void* ev_start, void* ev_stop);
 

@@ -10,7 +10,7 @@ import os
 from typing import Optional
 
 NSVD_MAX_LAYERS = 8
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 EINVAL = -10001
 EUNSUPPORTED = -10002
@@ -177,6 +177,8 @@ SIGNATURES = {
     "nsvd_model_workspace_bytes": (_Z, [C.POINTER(ModelDesc), _I]),
     "nsvd_kernel_apply_workspace_bytes": (_Z, [_I, _I, _I]),
     "nsvd_kernel_apply": (_I, [_P, _Z, _I, _P, _I, _P, _I, _P, _I, _F, _P, _P, _Z, _P]),
+    "nsvd_rbf_apply_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "nsvd_rbf_apply": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _F, _F, _P, _P, _Z, _P]),
     "nsvd_cdk_workspace_bytes": (_Z, [_I, _I, _I]),
     "nsvd_cdk_loss_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "nsvd_cdk_loss_backward": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),

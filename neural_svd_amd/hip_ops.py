@@ -801,6 +801,48 @@ def kernel_apply(K: torch.Tensor, N: int, rows: torch.Tensor, cols: torch.Tensor
     return out
 
 
+RBF_GAUSSIAN, RBF_EXPONENTIAL = 0, 1  # NSVD_RBF_* (include/nsvd.h)
+
+
+def rbf_apply_workspace(B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
+    n = _lib.load().nsvd_rbf_apply_workspace_bytes(int(B1), int(B2), int(D), int(L))
+    if n == 0:
+        raise NsvdError(f"nsvd_rbf_apply_workspace_bytes: unsupported shape B1={B1} B2={B2} D={D} L={L} "
+                        "(row counts and L >= 1, 1 <= D <= 64)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def rbf_apply(x: torch.Tensor, y: torch.Tensor, f: torch.Tensor, kind: int, ell: float, scale: float,
+              ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i] = scale * sum_j k(|x_i - y_j|) f[j] without the (B1, B2) kernel matrix (nsvd_rbf_apply). kind:
+    RBF_GAUSSIAN k = exp(-d^2 / (2 ell^2)), RBF_EXPONENTIAL k = exp(-d / ell). x: (B1, D), y: (B2, D), f: (B2, L)
+    contiguous float32 on the GPU; x may be y. Returns (B1, L)."""
+    for t, n in ((x, "x"), (y, "y"), (f, "f")):
+        if t.dim() != 2:
+            raise NsvdError(f"rbf_apply: {n} must be 2-D")
+    B1, D = x.shape
+    B2, L = f.shape
+    if tuple(y.shape) != (B2, D):
+        raise NsvdError("rbf_apply: y must be (len(f), D) with x's D")
+    xp, yp, fp = _ptr(x, "x"), _ptr(y, "y"), _ptr(f, "f")
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty((B1, L), dtype=torch.float32, device=f.device)
+    elif tuple(out.shape) != (B1, L):
+        raise NsvdError("rbf_apply: out must be (len(x), L)")
+    op = _ptr(out, "out")
+    if ws is None:
+        # (an unsupported shape has no workspace: the entry point itself refuses it, with its own code)
+        ws = torch.empty(max(lib.nsvd_rbf_apply_workspace_bytes(B1, B2, D, L), 256), dtype=torch.uint8, device=f.device)
+    if torch_binding() is not None:
+        _TB.rbf_apply(x, y, f, int(kind), float(ell), float(scale), out, ws)
+        return out
+    rc = lib.nsvd_rbf_apply(xp, B1, yp, B2, D, fp, L, int(kind), float(ell), float(scale), op, ws.data_ptr(),
+                            ws.numel(), _stream())
+    check(rc, "nsvd_rbf_apply")
+    return out
+
+
 def cdk_workspace(B: int, L: int, set_first_mode_const: bool, device) -> torch.Tensor:
     n = _lib.load().nsvd_cdk_workspace_bytes(int(B), int(L), int(bool(set_first_mode_const)))
     return torch.empty(max(n, 256), dtype=torch.uint8, device=device)
@@ -1210,7 +1252,7 @@ def cdk_step(desc: "_lib.CdkStepDesc", x: torch.Tensor, y: torch.Tensor, towers:
 for _name in ("fourier_features", "operator_forward", "operator_features", "operator_sample_features",
               "operator_sample_features_dev", "rmsprop_ema_step_dev", "opt_step_dev",
               "operator_backward", "model_forward", "model_backward", "evd_moments", "evd_loss_grad", "evd_loss_fused",
-              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_opt_step", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "cdk_loss_forward",
+              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_opt_step", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "rbf_apply", "cdk_loss_forward",
               "cdk_loss_backward", "rmsprop_ema_step", "opt_step", "spectrum_accumulate", "row_normalize",
               "row_normalize_backward", "tower_forward", "tower_backward", "cdk_step", "to_bf16", "gemm_bf16"):
     globals()[_name] = _on_tensor_device(globals()[_name])

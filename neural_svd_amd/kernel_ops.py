@@ -11,9 +11,22 @@ contract's own ``self.model(x2)`` call works on an index batch),
 
 with the (B x B) . (B x L) contraction done by ``nsvd_kernel_apply`` on the fp32 MFMA (gathered rows of K, the batch
 scattered into the index space). No gradient flows through Kf (the EVD loss function returns none for it).
+
+``RadialKernelOperator`` is the matrix-free one: a radial kernel k(|x - y|) (Gaussian or exponential) on COORDINATE
+batches drawn fresh every step,
+
+    f = model(x),        Kf(x_i) = (1 / B2) sum_j k(|x_i - x_ref_j|) model(x_ref)_j
+
+- the definition oracle/nsvd_oracle.py:gaussian_kernel_apply restates and tests/golden/kernel_loss.npz pins - through
+``nsvd_rbf_apply``, which never stores the (B, B2) kernel matrix. Under the Gaussian measure N(0, sigma^2 I) the
+Gaussian kernel's Mercer spectrum is known in closed form (``gaussian_kernel_eigvals`` / ``_eigenfunctions``), and
+``kernel_spectrum`` evaluates the Rayleigh quotients of any functions against it on a sample.
 """
 from __future__ import annotations
 
+import math
+
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -81,6 +94,141 @@ def synthetic_psd_kernel(N: int = 10000, rank: int = 256, dim: int = 16, seed: i
     return DenseKernelOperator(K, z.to(device))
 
 
+class RadialKernelOperator:
+    """k(x, y) = exp(-|x - y|^2 / (2 ell^2)) (kind H.RBF_GAUSSIAN) or exp(-|x - y| / ell) (H.RBF_EXPONENTIAL) on
+    `dim`-dimensional coordinates; training batches are sigma * randn(B, dim). Serves NestedLoRA.compute_loss_kernel
+    and NeuralEigenfunctions.compute_loss_kernel in both split_batch modes: the models take coordinates as they are."""
+
+    def __init__(self, kind: int, ell: float, dim: int, sigma: float = 1.0, device="cuda:0"):
+        if kind not in (H.RBF_GAUSSIAN, H.RBF_EXPONENTIAL):
+            raise ValueError("RadialKernelOperator: kind must be H.RBF_GAUSSIAN or H.RBF_EXPONENTIAL")
+        if not ell > 0 or not sigma > 0:
+            raise ValueError("RadialKernelOperator: ell and sigma must be positive")
+        if not 1 <= int(dim) <= 64:
+            raise H.NsvdError("RadialKernelOperator: unsupported input dimension (nsvd_rbf_apply takes 1 <= D <= 64)")
+        self.kind, self.ell, self.dim, self.sigma = int(kind), float(ell), int(dim), float(sigma)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise H.NsvdError("RadialKernelOperator: the operator lives on the GPU (no CPU path)")
+
+    def apply(self, x: torch.Tensor, x_ref: torch.Tensor, f_ref: torch.Tensor, ws=None, out=None) -> torch.Tensor:
+        """Kf = (1 / B2) k(x, x_ref) @ f_ref, (B, L) float32; no gradient."""
+        with torch.no_grad():
+            return H.rbf_apply(x, x_ref, f_ref, self.kind, self.ell, 1.0 / x_ref.shape[0], ws=ws, out=out)
+
+    def get_approx_kernel_op(self, x_ref: torch.Tensor):
+        """x_ref: (B2, dim) reference coordinates -> op(model, x, importance=None) -> (Kf, f)."""
+        if not x_ref.is_cuda:
+            raise H.NsvdError("RadialKernelOperator: x_ref must live on the GPU (no CPU path)")
+        y = x_ref.detach().float().contiguous()
+
+        def op(model, x, importance=None):
+            if importance is not None:
+                raise NotImplementedError("RadialKernelOperator: importance-weighted kernel operators are not built")
+            if not x.is_cuda:
+                raise H.NsvdError("RadialKernelOperator: x must live on the GPU (no CPU path)")
+            f = model(x)
+            same = x is x_ref or (x.data_ptr() == x_ref.data_ptr() and x.shape == x_ref.shape and
+                                  x.stride() == x_ref.stride() and x.dtype == x_ref.dtype)
+            with torch.no_grad():
+                f_ref = f.detach() if same else model(x_ref).detach()
+                Kf = self.apply(x.detach().float().contiguous(), y, f_ref.float().contiguous())
+            return Kf, f
+        return op
+
+    def sample(self, batch_size: int, generator=None) -> torch.Tensor:
+        return self.sigma * torch.randn(batch_size, self.dim, device=self.device, generator=generator)
+
+
+def _gaussian_kernel_constants(sigma: float, ell: float):
+    a, b = 1.0 / (4.0 * sigma * sigma), 1.0 / (2.0 * ell * ell)
+    c = math.sqrt(a * a + 2.0 * a * b)
+    return a, b, c, a + b + c
+
+
+def gaussian_kernel_modes(sigma: float, ell: float, dim: int, neigs: int):
+    """The first `neigs` Mercer modes of k = exp(-|x - y|^2 / (2 ell^2)) under N(0, sigma^2 I_dim): eigenvalues
+    (descending, float64) and their multi-indices (neigs, dim). Per dimension lambda_k = sqrt(2a / A) (b / A)^k with
+    a = 1 / (4 sigma^2), b = 1 / (2 ell^2), c = sqrt(a^2 + 2ab), A = a + b + c; a mode's eigenvalue is the product over
+    dimensions, so modes come by total degree n (eigenvalue lambda_0^dim (b / A)^n), lexicographic within a degree."""
+    a, b, c, A = _gaussian_kernel_constants(sigma, ell)
+    lam0, ratio = math.sqrt(2.0 * a / A), b / A
+
+    def compositions(n, d):
+        if d == 1:
+            yield (n,)
+            return
+        for k in range(n, -1, -1):
+            for rest in compositions(n - k, d - 1):
+                yield (k,) + rest
+
+    idx, n = [], 0
+    while len(idx) < neigs:
+        for comp in compositions(n, dim):
+            idx.append(comp)
+            if len(idx) == neigs:
+                break
+        n += 1
+    idx = np.asarray(idx, dtype=np.int64).reshape(neigs, dim)
+    vals = np.array([np.prod([lam0 * ratio ** int(k) for k in row]) for row in idx], dtype=np.float64)
+    return vals, idx
+
+
+def gaussian_kernel_eigvals(sigma: float, ell: float, dim: int, neigs: int) -> np.ndarray:
+    return gaussian_kernel_modes(sigma, ell, dim, neigs)[0]
+
+
+def gaussian_kernel_eigenfunctions(x: torch.Tensor, sigma: float, ell: float, neigs: int) -> torch.Tensor:
+    """The (unnormalised) eigenfunctions of the same modes at x (n, dim), in float64 on x's device:
+    prod_d exp(-(c - a) x_d^2) H_k(sqrt(2c) x_d) with the physicists' Hermite polynomials. (n, neigs)."""
+    a, b, c, A = _gaussian_kernel_constants(sigma, ell)
+    x = x.double()
+    _, idx = gaussian_kernel_modes(sigma, ell, x.shape[1], neigs)
+    kmax = int(idx.max())
+    z = math.sqrt(2.0 * c) * x
+    herm = [torch.ones_like(z), 2.0 * z]
+    for k in range(1, kmax):
+        herm.append(2.0 * z * herm[k] - 2.0 * k * herm[k - 1])
+    env = torch.exp(-(c - a) * (x * x).sum(dim=1))
+    cols = []
+    for row in idx:
+        v = env.clone()
+        for d, k in enumerate(row):
+            v = v * herm[int(k)][:, d]
+        cols.append(v)
+    return torch.stack(cols, dim=1)
+
+
+@torch.no_grad()
+def kernel_spectrum(op: RadialKernelOperator, fn, x_eval: torch.Tensor, chunk: int = 4096):
+    """Rayleigh quotients of the columns of Phi = fn(x_eval) under the operator's kernel and the EMPIRICAL measure of
+    x_eval (n, dim): cov = Phi^T Phi / n, quad = Phi^T (K Phi) / n with K Phi = (1 / n) k(x_eval, x_eval) Phi from
+    nsvd_rbf_apply against the whole evaluation set, `chunk` rows at a time; products and sums in float64
+    (nsvd_spectrum_accumulate_f64, unweighted). Returns dict(eigvals = diag(quad) / diag(cov), norms = diag(cov), cov,
+    quad) as float64 numpy arrays. fn maps (m, dim) float32 GPU coordinates to (m, L) values, L <= 64."""
+    if not x_eval.is_cuda:
+        raise H.NsvdError("kernel_spectrum: x_eval must live on the GPU (no CPU path)")
+    x_eval = x_eval.float().contiguous()
+    n = x_eval.shape[0]
+    phi = torch.cat([fn(x_eval[i:i + chunk]).float() for i in range(0, n, chunk)]).contiguous()
+    L = phi.shape[1]
+    cov = torch.zeros((L, L), dtype=torch.float64, device=x_eval.device)
+    quad = torch.zeros_like(cov)
+    # the accumulation kernel's weight is 1 / sqrt(p_val) of the uniform box [-lim, lim]^D: lim = 1/2 makes it 1; it
+    # also drops the operator rows of samples AT the origin (a rule of the PDE problems): it is given a constant
+    # coordinate column instead of x_eval
+    ones = torch.ones((min(chunk, n), 1), dtype=torch.float32, device=x_eval.device)
+    ws = None
+    for i in range(0, n, chunk):
+        xc, pc = x_eval[i:i + chunk], phi[i:i + chunk]
+        if ws is None or len(xc) != min(chunk, n):
+            ws = H.rbf_apply_workspace(len(xc), n, op.dim, L, x_eval.device)
+        Kphi = op.apply(xc, x_eval, phi, ws=ws)
+        H.spectrum_accumulate(pc, Kphi, ones[:len(xc)], 1.0, False, 0.5, cov, quad)
+    cov64, quad64 = (cov / n).cpu().numpy(), (quad / n).cpu().numpy()
+    return dict(eigvals=np.diag(quad64) / np.diag(cov64), norms=np.diag(cov64).copy(), cov=cov64, quad=quad64)
+
+
 class FusedKernelTrainer:
     """The kernel-operator training step (NestedLoRA.compute_loss_kernel with split_batch = False on a
     DenseKernelOperator, then loss.backward(); RMSprop (+ cosine schedule); EMA - reference methods/nestedlora.py:230-252
@@ -95,18 +243,25 @@ class FusedKernelTrainer:
     Every rank draws the same index batch (equal generator seeds), evaluates its heads on it, and applies K to ITS
     columns of f only (Kf[:, l] = K[x][:, x] f[:, l] / B needs no other head): the MFMA work of the step is split W
     ways. One all-gather of the packed (2, B, L / W) block [f | Kf] per step (any L >= W: the first L % W ranks own one head more) (2 B L floats in total: 4 MB at cfg4) is
-    the only exchange; moments, loss gradient and backward of the local heads are then local."""
+    the only exchange; moments, loss gradient and backward of the local heads are then local.
 
-    def __init__(self, op: DenseKernelOperator, L: int, m: int, hidden=(128, 128), batch_size: int = 8192,
+    With a RadialKernelOperator the batch is a COORDINATE batch (drawn as sigma * randn, or given): the model is
+    evaluated on it directly and Kf = k(x, x) f / B comes from nsvd_rbf_apply in place of nsvd_kernel_apply; everything
+    after Kf is the same sequence. Single GPU only (comm raises NotImplementedError)."""
+
+    def __init__(self, op, L: int, m: int, hidden=(128, 128), batch_size: int = 8192,
                  sequential: bool = False, step: int = 1, lr: float = 1e-4, rmsprop_decay: float = 0.99,
                  rmsprop_eps: float = 1e-8, ema_decay: float = 0.0, num_iters: int = 0, fourier_scale: float = 0.05,
                  hard_mul_const: float = 1.0, seed: int = 0, index_seed: int = 1, comm=None):
         from .nested_lowrank import nesting_masks
         from .trainer import FlatParams, reference_init
         self.op = op
-        dev = op.K.device
+        self.radial = isinstance(op, RadialKernelOperator)
+        if self.radial and comm is not None:
+            raise NotImplementedError("FusedKernelTrainer: sharded runs (comm) are not built for RadialKernelOperator")
+        dev = op.device if self.radial else op.K.device
         self.device = dev
-        D = op.points.shape[1]
+        D = op.dim if self.radial else op.points.shape[1]
         self.comm = comm if comm is not None and comm.multi else None
         world = self.comm.world if self.comm is not None else 1
         rank = self.comm.rank if self.comm is not None else 0
@@ -137,8 +292,11 @@ class FusedKernelTrainer:
         self.lr, self.alpha, self.eps, self.ema_decay, self.num_iters = lr, rmsprop_decay, rmsprop_eps, ema_decay, num_iters
         self.c = float(hard_mul_const)
         self.ws = H.model_workspace(self.shape, self.B, dev)
-        self.ka_ws = torch.empty(H._lib.load().nsvd_kernel_apply_workspace_bytes(int(op.N), self.B, Ll),
-                                 dtype=torch.uint8, device=dev)
+        if self.radial:
+            self.ka_ws = H.rbf_apply_workspace(self.B, self.B, D, Ll, dev)
+        else:
+            self.ka_ws = torch.empty(H._lib.load().nsvd_kernel_apply_workspace_bytes(int(op.N), self.B, Ll),
+                                     dtype=torch.uint8, device=dev)
         # this rank's outputs packed [f | Kf] so that one all-gather moves both
         # (the all-gather block, as long as the largest rank's, begins with it: nsvd_evd_gather_head_blocks)
         self._blk = torch.zeros(2 * self.B * Lb, dtype=torch.float32, device=dev)
@@ -158,15 +316,24 @@ class FusedKernelTrainer:
         self.t = 0
 
     def step(self, idx: torch.Tensor = None) -> torch.Tensor:
-        """one optimiser step on the index batch idx (or a fresh draw; sharded runs: the SAME batch on every rank);
+        """one optimiser step on the index batch idx (or a fresh draw; sharded runs: the SAME batch on every rank) -
+        with a RadialKernelOperator: on the (B, D) coordinate batch given in its place, or a fresh draw;
         returns the device loss triple (no sync)"""
         from .trainer import cosine_lr
-        if idx is None:
-            idx = self.op.sample_indices(self.B, self.gen)
-        idx = idx.to(torch.int64).contiguous()
-        x = self.op.points.index_select(0, idx)
-        H.model_forward(self.shape, self._params, x, self.c, self.ws, save_for_backward=True, out=self.f_loc)
-        H.kernel_apply(self.op.K, self.op.N, idx, idx, self.f_loc, 1.0 / self.B, ws=self.ka_ws, out=self.Kf_loc)
+        if self.radial:
+            x = self.op.sample(self.B, self.gen) if idx is None else idx
+            if not x.is_cuda or tuple(x.shape) != (self.B, self.op.dim):
+                raise H.NsvdError(f"FusedKernelTrainer.step: a ({self.B}, {self.op.dim}) coordinate batch on the GPU")
+            x = x.float().contiguous()
+            H.model_forward(self.shape, self._params, x, self.c, self.ws, save_for_backward=True, out=self.f_loc)
+            H.rbf_apply(x, x, self.f_loc, self.op.kind, self.op.ell, 1.0 / self.B, ws=self.ka_ws, out=self.Kf_loc)
+        else:
+            if idx is None:
+                idx = self.op.sample_indices(self.B, self.gen)
+            idx = idx.to(torch.int64).contiguous()
+            x = self.op.points.index_select(0, idx)
+            H.model_forward(self.shape, self._params, x, self.c, self.ws, save_for_backward=True, out=self.f_loc)
+            H.kernel_apply(self.op.K, self.op.N, idx, idx, self.f_loc, 1.0 / self.B, ws=self.ka_ws, out=self.Kf_loc)
         if self.comm is not None:
             if self.probe is not None:
                 with self.probe.span("f_Kf_all_gather_wait"):

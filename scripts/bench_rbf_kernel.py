@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Time nsvd_rbf_apply (the matrix-free radial kernel operator) against what a user can compose from library calls.
+
+    python scripts/bench_rbf_kernel.py [--b 8192 --d 16 --l 64 --n 10000 --ell 4 --reps 30 --inner 10]
+
+Three routes at B1 = B2 = --b, D = --d, L = --l, timed with device events, ALTERNATING in one loop after a warm-up call
+each, --inner calls per timed window, medians over --reps windows:
+  * `rbf_apply`: hip_ops.rbf_apply (transpose / pad pass, main kernel, slice reduction), workspace and output reused;
+  * `library`: the float32 library composition torch.cdist -> exp -> matmul on the same GPU (the yardstick: it stores
+    the (B, B) kernel matrix);
+  * `kernel_apply`: nsvd_kernel_apply on a stored N = --n dense operator with the same batch and L (what the
+    interface had before).
+The main kernel alone is bracketed once with nsvd_profile_next_forward. Share of the fp32 MFMA peak (155 TFLOP/s, dense
+v_mfma_f32_32x32x2_f32): the issue's model counts 2 B^2 L for the contraction plus 2 B^2 D for distances on the matrix
+pipe (10.7 GFLOP at the defaults); this kernel takes the distances by direct differences on the VALU, so the MFMA work
+it executes is the contraction alone (8.6 GFLOP) - both fractions are reported, named.
+Before timing, rbf_apply is compared with the library composition (max-normalised difference).
+Writes profiles/rbf_apply_bench.json. The numbers are reported as they come out."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from neural_svd_amd import hip_ops as H  # noqa: E402
+from neural_svd_amd.kernel_ops import synthetic_psd_kernel  # noqa: E402
+
+MFMA_F32_PEAK = 155e12
+
+
+def median_ms_alternating(fns, reps, inner):
+    for fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(reps):
+        for fn, ts in zip(fns, times):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(inner):
+                fn()
+            b.record()
+            b.synchronize()
+            ts.append(float(a.elapsed_time(b)) / inner)
+    return [dict(median_ms=float(np.median(ts)), min_ms=float(np.min(ts)), max_ms=float(np.max(ts))) for ts in times]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--b", type=int, default=8192)
+    ap.add_argument("--d", type=int, default=16)
+    ap.add_argument("--l", type=int, default=64)
+    ap.add_argument("--n", type=int, default=10000)
+    ap.add_argument("--ell", type=float, default=4.0)
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rbf_apply_bench.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_rbf_kernel.py needs a GPU: a CPU run measures nothing")
+    dev = "cuda:0"
+    B, D, L = a.b, a.d, a.l
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(B, D, device=dev, generator=g)
+    f = torch.randn(B, L, device=dev, generator=g)
+    ws = H.rbf_apply_workspace(B, B, D, L, dev)
+    out = torch.empty(B, L, device=dev)
+    scale, ell = 1.0 / B, a.ell
+
+    def rbf():
+        H.rbf_apply(x, x, f, H.RBF_GAUSSIAN, ell, scale, ws=ws, out=out)
+
+    def library():
+        return torch.exp(torch.cdist(x, x) ** 2 * (-1.0 / (2.0 * ell * ell))) @ f * scale
+
+    op = synthetic_psd_kernel(a.n, 256, D, 0, dev)
+    idx = op.sample_indices(B, g)
+    ka_ws = torch.empty(H._lib.load().nsvd_kernel_apply_workspace_bytes(op.N, B, L), dtype=torch.uint8, device=dev)
+    ka_out = torch.empty(B, L, device=dev)
+
+    def dense():
+        H.kernel_apply(op.K, op.N, idx, idx, f, scale, ws=ka_ws, out=ka_out)
+
+    rbf()
+    ref = library()
+    agree = float((out - ref).abs().max() / ref.abs().max())
+    t_rbf, t_lib, t_dense = median_ms_alternating([rbf, library, dense], a.reps, a.inner)
+    # the main kernel alone (events recorded by the library around its launch)
+    ks = []
+    for _ in range(5):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        H.profile_next_forward(e0, e1)
+        rbf()
+        torch.cuda.synchronize()
+        ks.append(float(e0.elapsed_time(e1)))
+    k_ms = float(np.median(ks))
+    flop_contraction, flop_dist = 2.0 * B * B * L, 2.0 * B * B * D
+    rec = dict(B1=B, B2=B, D=D, L=L, ell=ell, N_dense=a.n, reps=a.reps, calls_per_window=a.inner,
+               rbf_apply=t_rbf, library_cdist_exp_matmul=t_lib, kernel_apply_dense=t_dense,
+               rbf_main_kernel_ms=k_ms,
+               speedup_vs_library=t_lib["median_ms"] / t_rbf["median_ms"],
+               ratio_to_dense_kernel_apply=t_rbf["median_ms"] / t_dense["median_ms"],
+               gflop_model_contraction_plus_mfma_distances=(flop_contraction + flop_dist) / 1e9,
+               mfma_peak_fraction_on_model_flop_main_kernel=(flop_contraction + flop_dist) / MFMA_F32_PEAK / (k_ms * 1e-3),
+               mfma_peak_fraction_on_model_flop_whole_call=(flop_contraction + flop_dist) / MFMA_F32_PEAK /
+               (t_rbf["median_ms"] * 1e-3),
+               gflop_mfma_executed_contraction_only=flop_contraction / 1e9,
+               mfma_peak_fraction_executed_main_kernel=flop_contraction / MFMA_F32_PEAK / (k_ms * 1e-3),
+               max_normalised_difference_to_library=agree, device=torch.cuda.get_device_name(0))
+    print(json.dumps(rec))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    json.dump(rec, open(a.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
