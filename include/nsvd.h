@@ -566,6 +566,42 @@ size_t nsvd_rbf_apply_workspace_bytes(int B1, int B2, int D, int L);
 int nsvd_rbf_apply(const float* x, int B1, const float* y, int B2, int D, const float* f, int L, int kind, float ell,
                    float scale, float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- next row: the dense side of the Nystrom baseline (methods/nystrom.py:8-47) -------------------------------------
+ * The reference's Nystrom.evd forms the n x n Gram matrix and calls a host eigh on it; here the top L <= 64 eigenpairs of
+ * G = k(xs, xs) / n come from block subspace iteration with Rayleigh-Ritz on a basis V (n, m), m <= 80, with
+ * W = G V from nsvd_rbf_apply (neural_svd_amd/nystrom.py drives the loop). These are the three pieces beside that
+ * product. NEW SYMBOLS ONLY: no existing entry point, struct or constant changes, so NSVD_ABI_VERSION stays 6.
+ *
+ * nsvd_tsgram_f64: XtX = X^T X and XtY = X^T Y, (m, m) float64 row-major, of X, Y (n, m) float32 with row strides
+ *   ldx, ldy >= m (in floats). Either output may be NULL (Y may then be NULL too). Products and sums in float64; the
+ *   rows are split over workgroups and the partial matrices reduced in slice order by a second launch (no atomics:
+ *   bit-reproducible). 1 <= m <= 80 (NSVD_EUNSUPPORTED above), any n >= 1. Workspace 256-byte aligned; its size is 0
+ *   for shapes outside these ranges.
+ * nsvd_ritz_step_f64: one workgroup, float64, everything (m, m) contiguous row-major:
+ *       eigh((A + A^T) / 2) = Q diag(theta) Q^T, theta descending, ties by ascending index (cyclic Jacobi in a fixed
+ *       round-robin ordering, at most 30 sweeps, until |off-diagonal|_F <= 1e-15 |A|_F);
+ *       M = Q^T S Q;  resid_k = sqrt(max(M_kk - theta_k^2 (2 - q_k^T C q_k), 0));  R = chol(M) (upper);  T = Q R^-1.
+ *   With S = W^T W, A = V^T W and C = V^T V: (theta_k, V q_k) are the Ritz pairs, resid_k = |W q_k - theta_k V q_k|, and
+ *   W T is an orthonormal basis of span(W) whose leading columns are the Ritz directions in order. C == NULL stands for
+ *   C = I (resid_k = sqrt(max(M_kk - theta_k^2, 0))): exact for an orthonormal V, but a V stored in float32 is
+ *   orthonormal to ~1e-8 only, and the square root turns that into a floor of ~1e-4 theta_k under the residuals -
+ *   pass the Gram matrix of the stored V to have them to ~1e-8.
+ *   A == NULL: orthonormalisation only (Q = I, theta = resid = 0, T = chol(S)^-T). theta, resid, Q may be NULL.
+ *   *status (device int, zeroed by the caller) has NSVD_RITZ_* bits OR-ed in, so that one read can cover several
+ *   calls. On a non-positive (or non-finite) pivot T is zero from that column on and nothing non-finite is stored in T.
+ *   Every loop of the kernel has a trip count bounded by m or a constant.
+ * nsvd_ts_rotate: out (n, k) = X (n, m) T[:, :k], T float64 with row stride ldt >= k, accumulation in float64, one
+ *   rounding to float32; 1 <= k <= m <= 80; out must not alias X. */
+#define NSVD_RITZ_BAD_PIVOT 1 /* a Cholesky pivot was not positive: S is numerically rank deficient */
+#define NSVD_RITZ_SWEEP_CAP 2 /* the Jacobi sweep cap was reached before the off-diagonal threshold */
+size_t nsvd_tsgram_f64_workspace_bytes(int n, int m);
+int nsvd_tsgram_f64(const float* X, long ldx, const float* Y, long ldy, int n, int m, double* XtX, double* XtY, void* ws,
+                    size_t ws_bytes, void* stream);
+int nsvd_ritz_step_f64(const double* S, const double* A, const double* C, int m, double* theta, double* resid,
+                       double* Q, double* T, int* status, void* stream);
+int nsvd_ts_rotate(const float* X, long ldx, int n, int m, const double* T, int ldt, int k, float* out, long ldo,
+                   void* stream);
+
 /* ---- next row: the CDK (two-tower) NestedLoRA loss ------------------------------------------------------
  * NestedLoRALossFunctionForCDK (methods/nestedlora.py:273-332) as called by NestedLoRAForCDK.compute_loss
  * (methods/nestedlora.py:366-378; examples/cdk/sketchy/main_sketchy.py:188).

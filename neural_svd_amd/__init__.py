@@ -5,7 +5,7 @@ this package is the host-side mirror of the reference's Python interface for tha
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib", "SketchyRetrieval", "evaluate_truncations"]
+__all__ = ["_lib", "SketchyRetrieval", "evaluate_truncations", "Nystrom", "run_nystrom"]
 
 
 def __getattr__(name):
@@ -14,4 +14,7 @@ def __getattr__(name):
     if name in ("SketchyRetrieval", "evaluate_truncations"):
         from . import retrieval
         return getattr(retrieval, name)
+    if name in ("Nystrom", "run_nystrom"):  # the Nystrom baseline (nystrom.py), the same way
+        from . import nystrom
+        return getattr(nystrom, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

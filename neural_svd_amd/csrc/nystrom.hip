@@ -1,0 +1,466 @@
+// The small dense work of a block eigensolver on a tall-skinny basis: what the Nystrom baseline (reference
+// methods/nystrom.py:8-47 - Nystrom, Nystrom.evd, run_nystrom - which forms the n x n Gram matrix and calls a host
+// eigh on it) needs beside the matrix-free product of rbf_apply.hip to find the top L <= 64 eigenpairs of
+// G = k(xs, xs) / n by block subspace iteration with Rayleigh-Ritz (neural_svd_amd/nystrom.py):
+//   nsvd_tsgram_f64     XtX = X^T X, XtY = X^T Y of two (n, m) float32 blocks, products and sums in float64
+//   nsvd_ritz_step_f64  the m x m solve of one iteration in ONE workgroup, float64, matrices in LDS:
+//                       eigh(sym(A)) = Q diag(theta) Q^T (cyclic Jacobi, round-robin parallel ordering),
+//                       M = Q^T S Q, residuals sqrt(max(M_kk - theta_k^2 (2 - q_k^T C q_k), 0)), R = chol(M),
+//                       T = Q R^-1
+//   nsvd_ts_rotate      out = X T[:, :k] in float64, rounded once to float32
+// m <= 80 throughout (64 pairs + 16 columns of oversampling). Every device loop has a trip count bounded by an argument
+// or a constant; nothing waits on a data-dependent flag. No atomics: the row slices of the Gram are reduced in slice
+// order by a second launch, so every result is bit-reproducible.
+#include "nsvd_kernels.h"
+
+namespace {
+
+constexpr int NY_MAXM = 80;     // block width limit
+constexpr int NY_THREADS = 256;
+constexpr int NY_CB = 5;        // column blocks of 16: 5 * 16 = NY_MAXM
+constexpr int TS_ROWS = 32;     // rows of X (and Y) per LDS chunk of the Gram kernel
+constexpr int TS_MAX_SLICES = 128, TS_SLICE_ROWS = 64;
+constexpr int RZ_SWEEPS = 30;   // Jacobi sweep cap (float64, m <= 80: 6-10 sweeps in practice)
+constexpr int RO_ROWS = 32;     // rows of X per workgroup of the rotation kernel
+
+int ts_slices(int n) {
+    const int s = nsvd_cdiv(n, TS_SLICE_ROWS);
+    return s < 1 ? 1 : (s > TS_MAX_SLICES ? TS_MAX_SLICES : s);
+}
+
+// part[slice][0] = X_slice^T X_slice, part[slice][1] = X_slice^T Y_slice (each (m, m)). Thread (ti, tj) = (t / 16, t % 16)
+// owns the outputs (ti + 16 a, tj + 16 b), a, b < 5: per row of the chunk five reads of x (two addresses per half
+// wave: broadcast), five of y (16 consecutive floats) and 25 float64 FMAs per product.
+template <bool XX, bool XY>
+__global__ void __launch_bounds__(NY_THREADS) tsgram_partial_kernel(const float* __restrict__ X, size_t ldx,
+                                                                    const float* __restrict__ Y, size_t ldy, int n, int m,
+                                                                    int S, double* __restrict__ part) {
+    __shared__ float xs[TS_ROWS][NY_MAXM];
+    __shared__ float ys[XY ? TS_ROWS : 1][NY_MAXM];
+    const int t = threadIdx.x, ti = t >> 4, tj = t & 15, slice = blockIdx.x;
+    const int r0 = (int)((long)n * slice / S), r1 = (int)((long)n * (slice + 1) / S);
+    double axx[NY_CB][NY_CB], axy[NY_CB][NY_CB];
+#pragma unroll
+    for (int a = 0; a < NY_CB; ++a)
+#pragma unroll
+        for (int b = 0; b < NY_CB; ++b) axx[a][b] = axy[a][b] = 0.0;
+    for (int rb = r0; rb < r1; rb += TS_ROWS) {
+        const int rows = min(TS_ROWS, r1 - rb);
+        __syncthreads();
+        for (int e = t; e < TS_ROWS * NY_MAXM; e += NY_THREADS) {
+            const int r = e / NY_MAXM, c = e - r * NY_MAXM;
+            const bool in = r < rows && c < m;
+            xs[r][c] = in ? X[(size_t)(rb + r) * ldx + c] : 0.f;
+            if (XY) ys[r][c] = in ? Y[(size_t)(rb + r) * ldy + c] : 0.f;
+        }
+        __syncthreads();
+        for (int r = 0; r < rows; ++r) {
+            double xa[NY_CB], xb[NY_CB], yb[NY_CB];
+#pragma unroll
+            for (int a = 0; a < NY_CB; ++a) {
+                xa[a] = (double)xs[r][ti + 16 * a];
+                if (XX) xb[a] = (double)xs[r][tj + 16 * a];
+                if (XY) yb[a] = (double)ys[r][tj + 16 * a];
+            }
+#pragma unroll
+            for (int a = 0; a < NY_CB; ++a)
+#pragma unroll
+                for (int b = 0; b < NY_CB; ++b) {
+                    if (XX) axx[a][b] = fma(xa[a], xb[b], axx[a][b]);
+                    if (XY) axy[a][b] = fma(xa[a], yb[b], axy[a][b]);
+                }
+        }
+    }
+    double* pxx = part + (size_t)slice * 2 * m * m;
+    double* pxy = pxx + (size_t)m * m;
+#pragma unroll
+    for (int a = 0; a < NY_CB; ++a)
+#pragma unroll
+        for (int b = 0; b < NY_CB; ++b) {
+            const int i = ti + 16 * a, j = tj + 16 * b;
+            if (i < m && j < m) {
+                if (XX) pxx[i * m + j] = axx[a][b];
+                if (XY) pxy[i * m + j] = axy[a][b];
+            }
+        }
+}
+
+// out[e] = sum over slices in slice order; blockIdx.y: 0 = XtX, 1 = XtY (a null output is skipped)
+__global__ void __launch_bounds__(NY_THREADS) tsgram_reduce_kernel(const double* __restrict__ part, int m, int S,
+                                                                   double* __restrict__ XtX, double* __restrict__ XtY) {
+    double* out = blockIdx.y == 0 ? XtX : XtY;
+    const int e = blockIdx.x * NY_THREADS + threadIdx.x, mm = m * m;
+    if (!out || e >= mm) return;
+    const double* p = part + (size_t)blockIdx.y * mm + e;
+    double s = 0.0;
+    for (int sl = 0; sl < S; ++sl) s += p[(size_t)sl * 2 * mm];
+    out[e] = s;
+}
+
+// out[rows of this workgroup][c < k] = sum_kk X[row][kk] T[kk][c]. T's first k columns wait in LDS as float64 (rows of
+// NY_MAXM, zero beyond k); thread (tr, tc) = (t / 16, t % 16) owns rows tr, tr + 16 and columns tc + 16 b.
+__global__ void __launch_bounds__(NY_THREADS) ts_rotate_kernel(const float* __restrict__ X, size_t ldx, int n, int m,
+                                                               const double* __restrict__ T, int ldt, int k,
+                                                               float* __restrict__ out, size_t ldo) {
+    __shared__ double Ts[NY_MAXM][NY_MAXM];
+    __shared__ float xs[RO_ROWS][NY_MAXM + 1];
+    const int t = threadIdx.x, tr = t >> 4, tc = t & 15;
+    const long rb = (long)blockIdx.x * RO_ROWS;
+    for (int e = t; e < m * NY_MAXM; e += NY_THREADS) {
+        const int kk = e / NY_MAXM, c = e - kk * NY_MAXM;
+        Ts[kk][c] = c < k ? T[(size_t)kk * ldt + c] : 0.0;
+    }
+    for (int e = t; e < RO_ROWS * m; e += NY_THREADS) {
+        const int r = e / m, c = e - r * m;
+        xs[r][c] = rb + r < n ? X[(size_t)(rb + r) * ldx + c] : 0.f;
+    }
+    __syncthreads();
+    double acc[2][NY_CB];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < NY_CB; ++b) acc[a][b] = 0.0;
+    for (int kk = 0; kk < m; ++kk) {
+        const double x0 = (double)xs[tr][kk], x1 = (double)xs[tr + 16][kk];
+#pragma unroll
+        for (int b = 0; b < NY_CB; ++b) {
+            const double tv = Ts[kk][tc + 16 * b];
+            acc[0][b] = fma(x0, tv, acc[0][b]);
+            acc[1][b] = fma(x1, tv, acc[1][b]);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const long row = rb + tr + 16 * a;
+#pragma unroll
+        for (int b = 0; b < NY_CB; ++b) {
+            const int c = tc + 16 * b;
+            if (row < n && c < k) out[(size_t)row * ldo + c] = (float)acc[a][b];
+        }
+    }
+}
+
+// ---- the m x m solve ------------------------------------------------------------------------------------------------
+struct RitzLds {
+    double *B0, *B1, *B2;  // three (m, ld) matrices, ld = m | 1 (odd: a column walk touches every bank pair once)
+    double *th, *ths;      // (m) eigenvalues as found / sorted; th is reused for the Cholesky diagonal
+    double *cc, *ss;       // (mp / 2) rotations of a round
+    double* red;           // (8) block reductions
+    int *pp, *qq, *perm;   // (mp / 2) pairs of a round, (m) sorted position -> column
+};
+
+__host__ __device__ inline size_t ritz_lds_doubles(int m) {
+    const int ld = m | 1, mp = (m + 1) & ~1;
+    return (size_t)3 * m * ld + 2 * m + mp + 8;
+}
+__host__ __device__ inline size_t ritz_lds_bytes(int m) {
+    const int mp = (m + 1) & ~1;
+    return ritz_lds_doubles(m) * sizeof(double) + (size_t)(mp + m) * sizeof(int);
+}
+
+// sums of two values over the workgroup, the same result in every thread, in a fixed order
+__device__ __forceinline__ void ritz_block_sum2(double& a, double& b, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        b += __shfl_xor(b, o, 64);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = a;
+        red[4 + (threadIdx.x >> 6)] = b;
+    }
+    __syncthreads();
+    a = (red[0] + red[1]) + (red[2] + red[3]);
+    b = (red[4] + red[5]) + (red[6] + red[7]);
+}
+
+__global__ void __launch_bounds__(NY_THREADS) ritz_step_kernel(const double* __restrict__ S, const double* __restrict__ A,
+                                                               const double* __restrict__ C, int m,
+                                                               double* __restrict__ theta,
+                                                               double* __restrict__ resid, double* __restrict__ Q,
+                                                               double* __restrict__ T, int* __restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int t = threadIdx.x, ld = m | 1, mp = (m + 1) & ~1, np = mp >> 1, mm = m * m;
+    RitzLds w;
+    w.B0 = sm;
+    w.B1 = w.B0 + m * ld;
+    w.B2 = w.B1 + m * ld;
+    w.th = w.B2 + m * ld;
+    w.ths = w.th + m;
+    w.cc = w.ths + m;
+    w.ss = w.cc + np;
+    w.red = w.ss + np;
+    w.pp = (int*)(w.red + 8);
+    w.qq = w.pp + np;
+    w.perm = w.qq + np;
+    int bits = 0;
+
+    if (A) {
+        // B0 = sym(A), B1 = I
+        for (int e = t; e < mm; e += NY_THREADS) {
+            const int i = e / m, j = e - i * m;
+            w.B0[i * ld + j] = 0.5 * (A[i * m + j] + A[j * m + i]);
+            w.B1[i * ld + j] = i == j ? 1.0 : 0.0;
+        }
+        bool converged = false;
+        for (int sweep = 0; sweep <= RZ_SWEEPS; ++sweep) {
+            __syncthreads();
+            double off = 0.0, fro = 0.0;
+            for (int e = t; e < mm; e += NY_THREADS) {
+                const int i = e / m, j = e - i * m;
+                const double v = w.B0[i * ld + j];
+                fro = fma(v, v, fro);
+                if (i != j) off = fma(v, v, off);
+            }
+            ritz_block_sum2(off, fro, w.red);
+            if (off <= 1e-30 * fro) {  // |off-diagonal|_F <= 1e-15 |A|_F (false for NaN: runs to the cap)
+                converged = true;
+                break;
+            }
+            if (sweep == RZ_SWEEPS) break;
+            // one sweep: mp - 1 rounds of the round-robin tournament, np disjoint pairs each (index m is the bye of an odd m)
+            for (int r = 0; r < mp - 1; ++r) {
+                if (t < np) {
+                    const int a = t == 0 ? mp - 1 : (r + t) % (mp - 1);
+                    const int b = t == 0 ? r : (r - t + mp - 1) % (mp - 1);
+                    const int p = min(a, b), q = max(a, b);
+                    double c = 1.0, s = 0.0;
+                    if (q < m) {
+                        const double apq = w.B0[p * ld + q];
+                        if (apq != 0.0) {
+                            const double zeta = (w.B0[q * ld + q] - w.B0[p * ld + p]) / (2.0 * apq);
+                            const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                            c = 1.0 / sqrt(1.0 + tt * tt);
+                            s = tt * c;
+                        }
+                    }
+                    w.pp[t] = q < m ? p : -1;
+                    w.qq[t] = q;
+                    w.cc[t] = c;
+                    w.ss[t] = s;
+                }
+                __syncthreads();
+                // columns p, q of A and of the eigenvector matrix: A <- A J, Q <- Q J
+                for (int e = t; e < np * m; e += NY_THREADS) {
+                    const int pr = e / m, i = e - pr * m, p = w.pp[pr], q = w.qq[pr];
+                    if (p < 0) continue;
+                    const double c = w.cc[pr], s = w.ss[pr];
+                    const double ap = w.B0[i * ld + p], aq = w.B0[i * ld + q];
+                    w.B0[i * ld + p] = c * ap - s * aq;
+                    w.B0[i * ld + q] = s * ap + c * aq;
+                    const double vp = w.B1[i * ld + p], vq = w.B1[i * ld + q];
+                    w.B1[i * ld + p] = c * vp - s * vq;
+                    w.B1[i * ld + q] = s * vp + c * vq;
+                }
+                __syncthreads();
+                // rows p, q of A: A <- J^T A; the annihilated pair is set to zero exactly
+                for (int e = t; e < np * m; e += NY_THREADS) {
+                    const int pr = e / m, j = e - pr * m, p = w.pp[pr], q = w.qq[pr];
+                    if (p < 0) continue;
+                    const double c = w.cc[pr], s = w.ss[pr];
+                    const double ap = w.B0[p * ld + j], aq = w.B0[q * ld + j];
+                    w.B0[p * ld + j] = j == q ? 0.0 : c * ap - s * aq;
+                    w.B0[q * ld + j] = j == p ? 0.0 : s * ap + c * aq;
+                }
+                __syncthreads();
+            }
+        }
+        if (!converged) bits |= NSVD_RITZ_SWEEP_CAP;
+        __syncthreads();
+        if (t < m) {
+            w.th[t] = w.B0[t * ld + t];
+            w.perm[t] = t;
+        }
+        __syncthreads();
+        // descending, ties by ascending index
+        if (t < m) {
+            const double v = w.th[t];
+            int rank = 0;
+            for (int j = 0; j < m; ++j) {
+                const double u = w.th[j];
+                rank += (u > v || (u == v && j < t)) ? 1 : 0;
+            }
+            if (!(v != v)) w.perm[rank] = t;  // (a NaN leaves the identity entry: indices stay in range)
+        }
+        __syncthreads();
+        if (t < m) {
+            const int src = min(max(w.perm[t], 0), m - 1);
+            w.perm[t] = src;
+            w.ths[t] = w.th[src];
+            if (theta) theta[t] = w.ths[t];
+        }
+        __syncthreads();
+        // B0 = the eigenvectors in sorted order (A itself is no longer needed)
+        for (int e = t; e < mm; e += NY_THREADS) {
+            const int i = e / m, j = e - i * m;
+            const double v = w.B1[i * ld + w.perm[j]];
+            w.B0[i * ld + j] = v;
+            if (Q) Q[e] = v;
+        }
+    } else {
+        for (int e = t; e < mm; e += NY_THREADS) {
+            const int i = e / m, j = e - i * m;
+            w.B0[i * ld + j] = i == j ? 1.0 : 0.0;
+            if (Q) Q[e] = i == j ? 1.0 : 0.0;
+        }
+        if (t < m) {
+            w.ths[t] = 0.0;
+            if (theta) theta[t] = 0.0;
+        }
+    }
+    // dk = q_k^T (C - I) q_k, C = V^T V of the basis as it is STORED (float32: orthonormal to ~1e-8 only). The residual
+    // |W q - theta V q|^2 = M_kk - theta^2 (1 - dk); without dk the difference M_kk - theta^2 carries theta^2 dk, and
+    // its square root a floor of theta sqrt(|dk|) ~ 1e-4 theta under every residual. Thread k keeps dk.
+    double dk = 0.0;
+    if (A && C) {
+        __syncthreads();
+        for (int e = t; e < mm; e += NY_THREADS) {
+            const int i = e / m, j = e - i * m;
+            w.B2[i * ld + j] = C[e] - (i == j ? 1.0 : 0.0);
+        }
+        __syncthreads();
+        for (int e = t; e < mm; e += NY_THREADS) {
+            const int i = e / m, j = e - i * m;
+            double s = 0.0;
+            for (int k = 0; k < m; ++k) s = fma(w.B2[i * ld + k], w.B0[k * ld + j], s);
+            w.B1[i * ld + j] = s;
+        }
+        __syncthreads();
+        if (t < m)
+            for (int i = 0; i < m; ++i) dk = fma(w.B0[i * ld + t], w.B1[i * ld + t], dk);
+        __syncthreads();
+    }
+    // B2 = S; with a rotation: B1 = S Q, then B2 = M = Q^T (S Q)
+    for (int e = t; e < mm; e += NY_THREADS) {
+        const int i = e / m, j = e - i * m;
+        w.B2[i * ld + j] = S[e];
+    }
+    __syncthreads();
+    if (A) {
+        for (int e = t; e < mm; e += NY_THREADS) {
+            const int i = e / m, j = e - i * m;
+            double s = 0.0;
+            for (int k = 0; k < m; ++k) s = fma(w.B2[i * ld + k], w.B0[k * ld + j], s);
+            w.B1[i * ld + j] = s;
+        }
+        __syncthreads();
+        for (int e = t; e < mm; e += NY_THREADS) {
+            const int i = e / m, j = e - i * m;
+            double s = 0.0;
+            for (int k = 0; k < m; ++k) s = fma(w.B0[k * ld + i], w.B1[k * ld + j], s);
+            w.B2[i * ld + j] = s;
+        }
+        __syncthreads();
+    }
+    if (resid && t < m) {
+        const double d = w.B2[t * ld + t] - w.ths[t] * w.ths[t] * (1.0 - dk);
+        resid[t] = A && d > 0.0 ? sqrt(d) : 0.0;
+    }
+    // R = chol(M), upper, in the upper triangle of B2 (its diagonal stays M's; R_jj goes to th)
+    int bad = m;
+    for (int j = 0; j < m; ++j) {
+        const double d = w.B2[j * ld + j];  // the same LDS word in every thread: the branch is uniform
+        if (!(d > 0.0) || !(d < 1.7e308)) {
+            bad = j;
+            break;
+        }
+        const double rj = sqrt(d), inv = 1.0 / rj;
+        if (t == 0) w.th[j] = rj;
+        for (int c = j + 1 + t; c < m; c += NY_THREADS) w.B2[j * ld + c] *= inv;
+        __syncthreads();
+        const int rem = m - j - 1;
+        for (int e = t; e < rem * rem; e += NY_THREADS) {
+            const int i = j + 1 + e / rem, c = j + 1 + e % rem;
+            if (c >= i) w.B2[i * ld + c] = fma(-w.B2[j * ld + i], w.B2[j * ld + c], w.B2[i * ld + c]);
+        }
+        __syncthreads();
+    }
+    if (bad < m) bits |= NSVD_RITZ_BAD_PIVOT;
+    __syncthreads();
+    // T = Q R^-1 by forward substitution along each row of Q, in place in B0 (one thread per row)
+    if (t < m) {
+        double* row = w.B0 + t * ld;
+        for (int j = 0; j < m; ++j) {
+            if (j >= bad) {
+                row[j] = 0.0;
+                continue;
+            }
+            double s = row[j];
+            for (int k = 0; k < j; ++k) s = fma(-row[k], w.B2[k * ld + j], s);
+            row[j] = s / w.th[j];
+        }
+    }
+    __syncthreads();
+    int nonfinite = 0;
+    for (int e = t; e < mm; e += NY_THREADS) {
+        const int i = e / m, j = e - i * m;
+        double v = w.B0[i * ld + j];
+        if (!(fabs(v) < 1.7e308)) {  // (overflow behind a tiny positive pivot, or NaN)
+            v = 0.0;
+            nonfinite = 1;
+        }
+        T[e] = v;
+    }
+    if (__syncthreads_or(nonfinite)) bits |= NSVD_RITZ_BAD_PIVOT;
+    if (t == 0 && bits) *status = *status | bits;
+}
+
+void ritz_set_lds_limit() {
+    static const bool done = [] {
+        (void)hipFuncSetAttribute((const void*)ritz_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)ritz_lds_bytes(NY_MAXM));
+        return true;
+    }();
+    (void)done;
+}
+
+}  // namespace
+
+extern "C" size_t nsvd_tsgram_f64_workspace_bytes(int n, int m) {
+    if (n <= 0 || m <= 0 || m > NY_MAXM) return 0;
+    return nsvd_align((size_t)ts_slices(n) * 2 * m * m * sizeof(double));
+}
+
+extern "C" int nsvd_tsgram_f64(const float* X, long ldx, const float* Y, long ldy, int n, int m, double* XtX,
+                               double* XtY, void* ws, size_t ws_bytes, void* stream) {
+    if (!X || !ws || n <= 0 || m <= 0 || ldx < m) return NSVD_EINVAL;
+    if (!XtX && !XtY) return NSVD_EINVAL;
+    if (XtY && (!Y || ldy < m)) return NSVD_EINVAL;
+    if (m > NY_MAXM) return NSVD_EUNSUPPORTED;
+    if (ws_bytes < nsvd_tsgram_f64_workspace_bytes(n, m) || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
+    const int S = ts_slices(n);
+    hipStream_t s = (hipStream_t)stream;
+    double* part = (double*)ws;
+    if (XtX && XtY)
+        tsgram_partial_kernel<true, true><<<S, NY_THREADS, 0, s>>>(X, (size_t)ldx, Y, (size_t)ldy, n, m, S, part);
+    else if (XtX)
+        tsgram_partial_kernel<true, false><<<S, NY_THREADS, 0, s>>>(X, (size_t)ldx, nullptr, 0, n, m, S, part);
+    else
+        tsgram_partial_kernel<false, true><<<S, NY_THREADS, 0, s>>>(X, (size_t)ldx, Y, (size_t)ldy, n, m, S, part);
+    NSVD_CHECK_LAUNCH();
+    tsgram_reduce_kernel<<<dim3(nsvd_cdiv(m * m, NY_THREADS), 2), NY_THREADS, 0, s>>>(part, m, S, XtX, XtY);
+    NSVD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nsvd_ritz_step_f64(const double* S, const double* A, const double* C, int m, double* theta,
+                                  double* resid, double* Q, double* T, int* status, void* stream) {
+    if (!S || !T || !status || m <= 0) return NSVD_EINVAL;
+    if (m > NY_MAXM) return NSVD_EUNSUPPORTED;
+    ritz_set_lds_limit();
+    ritz_step_kernel<<<1, NY_THREADS, ritz_lds_bytes(m), (hipStream_t)stream>>>(S, A, C, m, theta, resid, Q,
+                                                                                T, status);
+    NSVD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nsvd_ts_rotate(const float* X, long ldx, int n, int m, const double* T, int ldt, int k, float* out,
+                              long ldo, void* stream) {
+    if (!X || !T || !out || n <= 0 || m <= 0 || k <= 0 || k > m || ldx < m || ldt < k || ldo < k) return NSVD_EINVAL;
+    if (m > NY_MAXM) return NSVD_EUNSUPPORTED;
+    ts_rotate_kernel<<<nsvd_cdiv(n, RO_ROWS), NY_THREADS, 0, (hipStream_t)stream>>>(X, (size_t)ldx, n, m, T, ldt, k, out,
+                                                                                  (size_t)ldo);
+    NSVD_CHECK_LAUNCH();
+    return 0;
+}

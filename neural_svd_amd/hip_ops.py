@@ -843,6 +843,112 @@ def rbf_apply(x: torch.Tensor, y: torch.Tensor, f: torch.Tensor, kind: int, ell:
     return out
 
 
+# ---- the dense side of the Nystrom baseline (csrc/nystrom.hip; the loop is neural_svd_amd/nystrom.py) ---------------
+RITZ_BAD_PIVOT, RITZ_SWEEP_CAP = 1, 2  # NSVD_RITZ_* (include/nsvd.h)
+NYSTROM_MAX_BLOCK = 80
+
+
+def _rows_ptr(t: torch.Tensor, name: str) -> Tuple[int, int]:
+    """(pointer, row stride) of a 2-D float32 GPU tensor whose rows are contiguous (a column slice of a wider one may
+    come in as it is)"""
+    if not t.is_cuda:
+        raise NsvdError(f"{name} must live on the GPU (got {t.device}); neural_svd_amd has no CPU path")
+    if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise NsvdError(f"{name} must be a 2-D float32 tensor with unit column stride and non-overlapping rows")
+    return t.data_ptr(), t.stride(0)
+
+
+def tsgram_workspace(n: int, m: int, device) -> torch.Tensor:
+    b = _lib.load().nsvd_tsgram_f64_workspace_bytes(int(n), int(m))
+    if b == 0:
+        raise NsvdError(f"nsvd_tsgram_f64_workspace_bytes: unsupported shape n={n} m={m} (n >= 1, 1 <= m <= 80)")
+    return torch.empty(b, dtype=torch.uint8, device=device)
+
+
+def tsgram_f64(X: torch.Tensor, Y: Optional[torch.Tensor] = None, xtx: bool = True, ws: Optional[torch.Tensor] = None,
+               out_xtx: Optional[torch.Tensor] = None, out_xty: Optional[torch.Tensor] = None):
+    """(X^T X, X^T Y) as (m, m) float64 from (n, m) float32 blocks (nsvd_tsgram_f64): products and sums in float64, no
+    atomics, bit-reproducible. Y None: only X^T X (the second value is None); xtx False: only X^T Y."""
+    xp, ldx = _rows_ptr(X, "X")
+    n, m = X.shape
+    yp, ldy = None, 0
+    if Y is not None:
+        if tuple(Y.shape) != (n, m):
+            raise NsvdError("tsgram_f64: Y must have X's shape")
+        yp, ldy = _rows_ptr(Y, "Y")
+    elif not xtx:
+        raise NsvdError("tsgram_f64: nothing to compute")
+    lib = _lib.load()
+    if xtx and out_xtx is None:
+        out_xtx = torch.empty((m, m), dtype=torch.float64, device=X.device)
+    if Y is not None and out_xty is None:
+        out_xty = torch.empty((m, m), dtype=torch.float64, device=X.device)
+    for o, name in ((out_xtx, "out_xtx"), (out_xty, "out_xty")):
+        if o is not None and tuple(o.shape) != (m, m):
+            raise NsvdError(f"tsgram_f64: {name} must be (m, m)")
+    if ws is None:
+        ws = torch.empty(max(lib.nsvd_tsgram_f64_workspace_bytes(n, m), 256), dtype=torch.uint8, device=X.device)
+    rc = lib.nsvd_tsgram_f64(xp, ldx, yp, ldy, n, m, _ptr(out_xtx if xtx else None, "out_xtx", torch.float64),
+                             _ptr(out_xty, "out_xty", torch.float64), ws.data_ptr(), ws.numel(), _stream())
+    check(rc, "nsvd_tsgram_f64")
+    return (out_xtx if xtx else None), out_xty
+
+
+def ritz_step_f64(S: torch.Tensor, A: Optional[torch.Tensor], status: torch.Tensor,
+                  theta: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
+                  Q: Optional[torch.Tensor] = None, T: Optional[torch.Tensor] = None,
+                  C: Optional[torch.Tensor] = None):
+    """The m x m solve of one subspace iteration (nsvd_ritz_step_f64), float64: eigh(sym(A)) = Q diag(theta) Q^T with
+    theta descending, M = Q^T S Q, resid_k = sqrt(max(M_kk - theta_k^2 (2 - q_k^T C q_k), 0)) (C None: C = I),
+    T = Q chol(M)^-1. A None: Q = I, T = chol(S)^-T. status: (1,) int32, RITZ_* bits are OR-ed in (zero it first).
+    Returns (theta, resid, Q, T)."""
+    if S.dim() != 2 or S.shape[0] != S.shape[1]:
+        raise NsvdError("ritz_step_f64: S must be (m, m)")
+    m = S.shape[0]
+    dev = S.device
+    for o, name in ((A, "A"), (C, "C")):
+        if o is not None and tuple(o.shape) != (m, m):
+            raise NsvdError(f"ritz_step_f64: {name} must be (m, m)")
+    theta = torch.empty(m, dtype=torch.float64, device=dev) if theta is None else theta
+    resid = torch.empty(m, dtype=torch.float64, device=dev) if resid is None else resid
+    Q = torch.empty((m, m), dtype=torch.float64, device=dev) if Q is None else Q
+    T = torch.empty((m, m), dtype=torch.float64, device=dev) if T is None else T
+    if theta.numel() != m or resid.numel() != m or tuple(Q.shape) != (m, m) or tuple(T.shape) != (m, m):
+        raise NsvdError("ritz_step_f64: theta, resid (m); Q, T (m, m)")
+    if status.numel() < 1:
+        raise NsvdError("ritz_step_f64: status must hold one int32")
+    f64 = torch.float64
+    rc = _lib.load().nsvd_ritz_step_f64(_ptr(S, "S", f64), _ptr(A, "A", f64), _ptr(C, "C", f64), m,
+                                        _ptr(theta, "theta", f64),
+                                        _ptr(resid, "resid", f64), _ptr(Q, "Q", f64), _ptr(T, "T", f64),
+                                        _ptr(status, "status", torch.int32), _stream())
+    check(rc, "nsvd_ritz_step_f64")
+    return theta, resid, Q, T
+
+
+def ts_rotate(X: torch.Tensor, T: torch.Tensor, k: Optional[int] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out (n, k) = X (n, m) @ T[:, :k] with T (m, m) float64, accumulated in float64 and rounded once to float32
+    (nsvd_ts_rotate). out must not alias X."""
+    xp, ldx = _rows_ptr(X, "X")
+    n, m = X.shape
+    if T.dim() != 2 or T.shape[0] != m or T.stride(1) != 1:
+        raise NsvdError("ts_rotate: T must be (m, >= k) float64 with unit column stride")
+    k = T.shape[1] if k is None else int(k)
+    if out is None:
+        out = torch.empty((n, max(k, 0)), dtype=torch.float32, device=X.device)
+    elif tuple(out.shape) != (n, k):
+        raise NsvdError("ts_rotate: out must be (n, k)")
+    op, ldo = _rows_ptr(out, "out")
+    if out.data_ptr() == X.data_ptr():
+        raise NsvdError("ts_rotate: out must not alias X")
+    if T.dtype != torch.float64 or not T.is_cuda:
+        raise NsvdError("ts_rotate: T must be a float64 GPU tensor")
+    rc = _lib.load().nsvd_ts_rotate(xp, ldx, n, m, T.data_ptr(), T.stride(0), k, op, ldo, _stream())
+    check(rc, "nsvd_ts_rotate")
+    return out
+
+
 def cdk_workspace(B: int, L: int, set_first_mode_const: bool, device) -> torch.Tensor:
     n = _lib.load().nsvd_cdk_workspace_bytes(int(B), int(L), int(bool(set_first_mode_const)))
     return torch.empty(max(n, 256), dtype=torch.uint8, device=device)
@@ -1252,7 +1358,7 @@ def cdk_step(desc: "_lib.CdkStepDesc", x: torch.Tensor, y: torch.Tensor, towers:
 for _name in ("fourier_features", "operator_forward", "operator_features", "operator_sample_features",
               "operator_sample_features_dev", "rmsprop_ema_step_dev", "opt_step_dev",
               "operator_backward", "model_forward", "model_backward", "evd_moments", "evd_loss_grad", "evd_loss_fused",
-              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_opt_step", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "rbf_apply", "cdk_loss_forward",
+              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_opt_step", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "rbf_apply", "tsgram_f64", "ritz_step_f64", "ts_rotate", "cdk_loss_forward",
               "cdk_loss_backward", "rmsprop_ema_step", "opt_step", "spectrum_accumulate", "row_normalize",
               "row_normalize_backward", "tower_forward", "tower_backward", "cdk_step", "to_bf16", "gemm_bf16"):
     globals()[_name] = _on_tensor_device(globals()[_name])

@@ -5,6 +5,10 @@ fresh every step, and the Rayleigh quotients of the learned functions on a held-
 compared with the closed-form Mercer eigenvalues (gaussian_kernel_eigvals).
 
     python scripts/train_rbf_kernel.py [--steps 20000 --dim 2 --sigma 1 --ell 1.5 --L 10 --B 8192]
+    python scripts/train_rbf_kernel.py --kind exponential --ell 2 --nystrom 8192
+
+--nystrom N adds the Nystrom baseline (neural_svd_amd.Nystrom, matrix-free) on an N-point sample as a comparison
+column: the only one the exponential kind has, since its spectrum has no closed form.
 
 Prints steps/s and the relative errors; writes the record to profiles/rbf_kernel_train.json. The quotients are taken
 under the EMPIRICAL measure of --n-eval samples: their own float64 sampling gap to lambda_k is reported beside them
@@ -39,12 +43,16 @@ def main():
     ap.add_argument("--fourier-scale", type=float, default=0.3)
     ap.add_argument("--n-eval", type=int, default=16384)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--kind", choices=("gaussian", "exponential"), default="gaussian")
+    ap.add_argument("--nystrom", type=int, default=0, metavar="N",
+                    help="also print the Nystrom eigenvalues of an N-point sample (0: off)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rbf_kernel_train.json"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("train_rbf_kernel.py needs a GPU (neural_svd_amd has no CPU path)")
     dev = "cuda:0"
-    op = RadialKernelOperator(H.RBF_GAUSSIAN, a.ell, a.dim, a.sigma, dev)
+    gaussian = a.kind == "gaussian"
+    op = RadialKernelOperator(H.RBF_GAUSSIAN if gaussian else H.RBF_EXPONENTIAL, a.ell, a.dim, a.sigma, dev)
     fk = FusedKernelTrainer(op, L=a.L, m=a.m, hidden=(128, 128), batch_size=a.B, sequential=True, lr=a.lr,
                             rmsprop_decay=0.999, rmsprop_eps=1e-10, num_iters=a.steps, fourier_scale=a.fourier_scale,
                             seed=a.seed, index_seed=a.seed + 1)
@@ -66,18 +74,33 @@ def main():
         return H.model_forward(fk.shape, fk._params, xe.contiguous(), fk.c, ws)
 
     got = kernel_spectrum(op, learned, x_eval, chunk)
-    lam = gaussian_kernel_eigvals(a.sigma, a.ell, a.dim, a.L)
-    exact = kernel_spectrum(op, lambda xe: gaussian_kernel_eigenfunctions(xe, a.sigma, a.ell, a.L), x_eval, chunk)
-    rel = np.abs(got["eigvals"] - lam) / lam
-    gap = np.abs(exact["eigvals"] - lam) / lam
-    rec = dict(dim=a.dim, sigma=a.sigma, ell=a.ell, L=a.L, B=a.B, steps=a.steps, lr=a.lr, fourier_scale=a.fourier_scale,
-               seconds=round(dt, 2), steps_per_s=round((a.steps - 10) / dt, 1), loss=[float(v) for v in loss.cpu()],
-               eig_closed_form=[float(v) for v in lam], rayleigh_learned=[float(v) for v in got["eigvals"]],
-               rel_err=[float(v) for v in rel], rel_err_mean=float(rel.mean()), rel_err_max=float(rel.max()),
-               sampling_gap_of_the_analytic_eigenfunctions=[float(v) for v in gap], n_eval=a.n_eval,
-               device=torch.cuda.get_device_name(0))
+    rec = dict(kind=a.kind, dim=a.dim, sigma=a.sigma, ell=a.ell, L=a.L, B=a.B, steps=a.steps, lr=a.lr,
+               fourier_scale=a.fourier_scale, seconds=round(dt, 2), steps_per_s=round((a.steps - 10) / dt, 1),
+               loss=[float(v) for v in loss.cpu()], rayleigh_learned=[float(v) for v in got["eigvals"]],
+               n_eval=a.n_eval, device=torch.cuda.get_device_name(0))
     print(f"steps/s {rec['steps_per_s']}")
-    print("relative error of the Rayleigh quotients: " + " ".join(f"{v:.2e}" for v in rel))
+    columns = [("learned", got["eigvals"])]
+    if gaussian:  # the closed form exists for the Gaussian kind only
+        lam = gaussian_kernel_eigvals(a.sigma, a.ell, a.dim, a.L)
+        exact = kernel_spectrum(op, lambda xe: gaussian_kernel_eigenfunctions(xe, a.sigma, a.ell, a.L), x_eval, chunk)
+        rel = np.abs(got["eigvals"] - lam) / lam
+        gap = np.abs(exact["eigvals"] - lam) / lam
+        rec.update(eig_closed_form=[float(v) for v in lam], rel_err=[float(v) for v in rel],
+                   rel_err_mean=float(rel.mean()), rel_err_max=float(rel.max()),
+                   sampling_gap_of_the_analytic_eigenfunctions=[float(v) for v in gap])
+        columns.append(("closed form", lam))
+        print("relative error of the Rayleigh quotients: " + " ".join(f"{v:.2e}" for v in rel))
+    if a.nystrom:
+        from neural_svd_amd import Nystrom
+        ny = Nystrom(op, op.sample(a.nystrom, torch.Generator(device=dev).manual_seed(a.seed + 2000)), a.L)
+        ny_vals = ny.eigvals.double().cpu().numpy()
+        rec.update(nystrom_n=a.nystrom, nystrom_eigvals=[float(v) for v in ny_vals], nystrom_iterations=ny.iterations,
+                   nystrom_converged=bool(ny.converged), nystrom_seconds=round(ny.training_time, 4),
+                   rel_to_nystrom=[float(v) for v in np.abs(got["eigvals"] - ny_vals) / ny_vals])
+        columns.append((f"Nystrom n={a.nystrom}", ny_vals))
+    print("  k  " + "  ".join(f"{name:>16}" for name, _ in columns))
+    for k in range(a.L):
+        print(f"{k:3d}  " + "  ".join(f"{float(v[k]):16.8e}" for _, v in columns))
     print(json.dumps(rec))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     json.dump(rec, open(a.out, "w"), indent=1)
