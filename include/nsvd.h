@@ -566,6 +566,35 @@ size_t nsvd_rbf_apply_workspace_bytes(int B1, int B2, int D, int L);
 int nsvd_rbf_apply(const float* x, int B1, const float* y, int B2, int D, const float* f, int L, int kind, float ell,
                    float scale, float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- next row: matrix-free dot-product kernel operator on coordinate batches ----------------------------------------
+ * out[i][l] = scale * sum_j k(x_i, y_j) f[j][l] for a kernel of the inner product x.y - the other family kernel
+ * eigenfunction work is run on (polynomial and neural-network Gaussian-process kernels) - on the same consumer contract
+ * and with the conventions of nsvd_rbf_apply: x: (B1, D), y: (B2, D), f: (B2, L), out: (B1, L), float32 row-major;
+ * x == y is allowed, out must not alias an input. Any B1, B2, L >= 1; 1 <= D <= 64 (NSVD_EUNSUPPORTED above, workspace
+ * size 0). x.y is formed on the fp32 MFMA (an inner product has no cancellation to protect), the map is applied in
+ * registers and the (B1, B2) kernel matrix is never stored; partial sums over slices of the reference rows are reduced
+ * in slice order (no atomics: bit-reproducible). The workspace is 256-byte aligned. NSVD_EINVAL: a null pointer, a
+ * non-positive size, an unknown kind, (polynomial kind) a degree outside 1..8 or a non-finite gamma or coef0, a short
+ * or misaligned workspace. A refused call writes nothing. NEW SYMBOLS ONLY: NSVD_ABI_VERSION stays 6.
+ * Numerical rules (restated in float64 by tests/_dot_oracle.py):
+ * - NSVD_DOT_POLYNOMIAL: the integer power is taken by multiplication (no pow, exp or log); the result is whatever
+ *   float32 gives for finite inputs.
+ * - NSVD_DOT_ARCCOS1: cos t is clamped to [-1, 1]; the bracket sin t + (pi - t) cos t (non-negative in exact
+ *   arithmetic, ~(pi - t)^3 / 3 near antiparallel rows) is clamped at 0 from below; a row of zero norm on either side
+ *   gives exactly 0, never a NaN. The kind is well conditioned at both ends: at t -> 0 the bracket is
+ *   pi (1 - t^2 / 2), so the ~4e-4 that float32 leaves in t on the diagonal costs 1e-7.
+ * - The ORDER-0 arc-cosine kernel (1 - t / pi) is deliberately NOT offered, and is not a one-line addition: on the
+ *   diagonal it turns that 4e-4 in t into a 1e-4 error of the kernel value, and repairing it needs the angle from direct
+ *   differences of normalised rows - the radial kernel's VALU cost again. */
+#define NSVD_DOT_POLYNOMIAL 0   /* k = (gamma * x.y + coef0)^degree, integer degree in 1..8 */
+#define NSVD_DOT_ARCCOS1    1   /* k = |x||y| / pi * (sin t + (pi - t) cos t), cos t = x.y / (|x||y|): Cho & Saul's
+                                   order-1 arc-cosine kernel = 2 E_w[relu(w.x) relu(w.y)], w ~ N(0, I): the NNGP kernel
+                                   of one ReLU layer. gamma, coef0, degree ignored. */
+size_t nsvd_dot_apply_workspace_bytes(int B1, int B2, int D, int L);
+int nsvd_dot_apply(const float* x, int B1, const float* y, int B2, int D, const float* f, int L, int kind,
+                   float gamma, float coef0, int degree, float scale, float* out, void* ws, size_t ws_bytes,
+                   void* stream);
+
 /* ---- next row: the dense side of the Nystrom baseline (methods/nystrom.py:8-47) -------------------------------------
  * The reference's Nystrom.evd forms the n x n Gram matrix and calls a host eigh on it; here the top L <= 64 eigenpairs of
  * G = k(xs, xs) / n come from block subspace iteration with Rayleigh-Ritz on a basis V (n, m), m <= 80, with

@@ -5,7 +5,7 @@ this package is the host-side mirror of the reference's Python interface for tha
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib", "SketchyRetrieval", "evaluate_truncations", "Nystrom", "run_nystrom"]
+__all__ = ["_lib", "SketchyRetrieval", "evaluate_truncations", "Nystrom", "run_nystrom", "DotKernelOperator"]
 
 
 def __getattr__(name):
@@ -17,4 +17,7 @@ def __getattr__(name):
     if name in ("Nystrom", "run_nystrom"):  # the Nystrom baseline (nystrom.py), the same way
         from . import nystrom
         return getattr(nystrom, name)
+    if name == "DotKernelOperator":  # the dot-product kernel operator (kernel_ops.py), the same way
+        from . import kernel_ops
+        return kernel_ops.DotKernelOperator
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -335,6 +335,21 @@ void rbf_apply(const at::Tensor& x, const at::Tensor& y, const at::Tensor& f, in
              "nsvd_rbf_apply");
 }
 
+// matrix-free dot-product kernel operator (nsvd_dot_apply): the same tensors as rbf_apply
+void dot_apply(const at::Tensor& x, const at::Tensor& y, const at::Tensor& f, int64_t kind, double gamma, double coef0,
+               int64_t degree, double scale, at::Tensor out, at::Tensor ws) {
+    Dev dv;
+    TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && f.dim() == 2 && out.dim() == 2 && y.size(1) == x.size(1) &&
+                    f.size(0) == y.size(0) && out.size(0) == x.size(0) && out.size(1) == f.size(1),
+                "dot_apply: x (B1, D), y (B2, D), f (B2, L), out (B1, L)");
+    float *xp = f32(dv, x, "x"), *yp = f32(dv, y, "y"), *fp = f32(dv, f, "f"), *op = f32(dv, out, "out");
+    void* wp = bytes(dv, ws, "ws");
+    check_rc(nsvd_dot_apply(xp, (int)x.size(0), yp, (int)y.size(0), (int)x.size(1), fp, (int)f.size(1), (int)kind,
+                            (float)gamma, (float)coef0, (int)degree, (float)scale, op, wp,
+                            (size_t)ws.numel() * ws.element_size(), dv.stream()),
+             "nsvd_dot_apply");
+}
+
 // retrieval metrics (nsvd_retrieval_eval): zq / zg may be column windows (unit column stride); outputs as passed
 void retrieval_eval(const at::Tensor& zq, const at::Tensor& zg, const at::Tensor& q_cls, const at::Tensor& g_cls,
                     c10::optional<at::Tensor> n_relevant_items, int64_t metric, int64_t K,
@@ -404,7 +419,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                         "nsvd_evd_moments", "nsvd_evd_loss_grad", "nsvd_operator_backward_evd_step",
                                         "nsvd_operator_backward_evd_step_next", "nsvd_rmsprop_ema_step", "nsvd_opt_step",
                                         "nsvd_spectrum_accumulate", "nsvd_rbf_apply",
-                                        "nsvd_rbf_apply_workspace_bytes", "nsvd_retrieval_eval",
+                                        "nsvd_rbf_apply_workspace_bytes", "nsvd_dot_apply",
+                                        "nsvd_dot_apply_workspace_bytes", "nsvd_retrieval_eval",
                                         "nsvd_retrieval_workspace_bytes", "nsvd_retrieval_max_gallery",
                                         "nsvd_retrieval_max_k", "nsvd_retrieval_max_d"};
     });
@@ -436,6 +452,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rbf_apply", &rbf_apply);
     m.def("rbf_apply_workspace_bytes",
           [](int B1, int B2, int D, int L) { return (int64_t)nsvd_rbf_apply_workspace_bytes(B1, B2, D, L); });
+    m.def("dot_apply", &dot_apply);
+    m.def("dot_apply_workspace_bytes",
+          [](int B1, int B2, int D, int L) { return (int64_t)nsvd_dot_apply_workspace_bytes(B1, B2, D, L); });
     m.def("retrieval_eval", &retrieval_eval);
     m.def("retrieval_workspace_bytes",
           [](int Nq, int Ng, int d, int K) { return (int64_t)nsvd_retrieval_workspace_bytes(Nq, Ng, d, K); });

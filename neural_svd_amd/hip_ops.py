@@ -843,6 +843,49 @@ def rbf_apply(x: torch.Tensor, y: torch.Tensor, f: torch.Tensor, kind: int, ell:
     return out
 
 
+DOT_POLYNOMIAL, DOT_ARCCOS1 = 0, 1  # NSVD_DOT_* (include/nsvd.h)
+
+
+def dot_apply_workspace(B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
+    n = _lib.load().nsvd_dot_apply_workspace_bytes(int(B1), int(B2), int(D), int(L))
+    if n == 0:
+        raise NsvdError(f"nsvd_dot_apply_workspace_bytes: unsupported shape B1={B1} B2={B2} D={D} L={L} "
+                        "(row counts and L >= 1, 1 <= D <= 64)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def dot_apply(x: torch.Tensor, y: torch.Tensor, f: torch.Tensor, kind: int, gamma: float, coef0: float, degree: int,
+              scale: float, ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i] = scale * sum_j k(x_i, y_j) f[j] without the (B1, B2) kernel matrix (nsvd_dot_apply). kind:
+    DOT_POLYNOMIAL k = (gamma x.y + coef0)^degree (integer degree 1..8), DOT_ARCCOS1 k = |x||y| / pi (sin t +
+    (pi - t) cos t) with cos t = x.y / (|x||y|) (gamma, coef0, degree ignored). x: (B1, D), y: (B2, D), f: (B2, L)
+    contiguous float32 on the GPU; x may be y. Returns (B1, L)."""
+    for t, n in ((x, "x"), (y, "y"), (f, "f")):
+        if t.dim() != 2:
+            raise NsvdError(f"dot_apply: {n} must be 2-D")
+    B1, D = x.shape
+    B2, L = f.shape
+    if tuple(y.shape) != (B2, D):
+        raise NsvdError("dot_apply: y must be (len(f), D) with x's D")
+    xp, yp, fp = _ptr(x, "x"), _ptr(y, "y"), _ptr(f, "f")
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty((B1, L), dtype=torch.float32, device=f.device)
+    elif tuple(out.shape) != (B1, L):
+        raise NsvdError("dot_apply: out must be (len(x), L)")
+    op = _ptr(out, "out")
+    if ws is None:
+        # (an unsupported shape has no workspace: the entry point itself refuses it, with its own code)
+        ws = torch.empty(max(lib.nsvd_dot_apply_workspace_bytes(B1, B2, D, L), 256), dtype=torch.uint8, device=f.device)
+    if torch_binding() is not None:
+        _TB.dot_apply(x, y, f, int(kind), float(gamma), float(coef0), int(degree), float(scale), out, ws)
+        return out
+    rc = lib.nsvd_dot_apply(xp, B1, yp, B2, D, fp, L, int(kind), float(gamma), float(coef0), int(degree), float(scale),
+                            op, ws.data_ptr(), ws.numel(), _stream())
+    check(rc, "nsvd_dot_apply")
+    return out
+
+
 # ---- the dense side of the Nystrom baseline (csrc/nystrom.hip; the loop is neural_svd_amd/nystrom.py) ---------------
 RITZ_BAD_PIVOT, RITZ_SWEEP_CAP = 1, 2  # NSVD_RITZ_* (include/nsvd.h)
 NYSTROM_MAX_BLOCK = 80
@@ -1358,7 +1401,7 @@ def cdk_step(desc: "_lib.CdkStepDesc", x: torch.Tensor, y: torch.Tensor, towers:
 for _name in ("fourier_features", "operator_forward", "operator_features", "operator_sample_features",
               "operator_sample_features_dev", "rmsprop_ema_step_dev", "opt_step_dev",
               "operator_backward", "model_forward", "model_backward", "evd_moments", "evd_loss_grad", "evd_loss_fused",
-              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_opt_step", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "rbf_apply", "tsgram_f64", "ritz_step_f64", "ts_rotate", "cdk_loss_forward",
+              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_opt_step", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "rbf_apply", "dot_apply", "tsgram_f64", "ritz_step_f64", "ts_rotate", "cdk_loss_forward",
               "cdk_loss_backward", "rmsprop_ema_step", "opt_step", "spectrum_accumulate", "row_normalize",
               "row_normalize_backward", "tower_forward", "tower_backward", "cdk_step", "to_bf16", "gemm_bf16"):
     globals()[_name] = _on_tensor_device(globals()[_name])

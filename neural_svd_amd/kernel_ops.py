@@ -94,39 +94,48 @@ def synthetic_psd_kernel(N: int = 10000, rank: int = 256, dim: int = 16, seed: i
     return DenseKernelOperator(K, z.to(device))
 
 
-class RadialKernelOperator:
-    """k(x, y) = exp(-|x - y|^2 / (2 ell^2)) (kind H.RBF_GAUSSIAN) or exp(-|x - y| / ell) (H.RBF_EXPONENTIAL) on
-    `dim`-dimensional coordinates; training batches are sigma * randn(B, dim). Serves NestedLoRA.compute_loss_kernel
-    and NeuralEigenfunctions.compute_loss_kernel in both split_batch modes: the models take coordinates as they are."""
+class MatrixFreeKernelOperator:
+    """What ``kernel_spectrum``, ``FusedKernelTrainer`` and ``nystrom.Nystrom`` need of a matrix-free operator on
+    `dim`-dimensional coordinates (attributes ``dim``, ``sigma``, ``device``): a subclass supplies
 
-    def __init__(self, kind: int, ell: float, dim: int, sigma: float = 1.0, device="cuda:0"):
-        if kind not in (H.RBF_GAUSSIAN, H.RBF_EXPONENTIAL):
-            raise ValueError("RadialKernelOperator: kind must be H.RBF_GAUSSIAN or H.RBF_EXPONENTIAL")
-        if not ell > 0 or not sigma > 0:
-            raise ValueError("RadialKernelOperator: ell and sigma must be positive")
+        workspace(B1, B2, L, device=None)             the workspace of one product of that shape (on `device`;
+                                                      None: the operator's own)
+        apply_raw(x, y, f, scale, ws=None, out=None)  out = scale * k(x, y) @ f, one C-ABI call, no gradient
+
+    and inherits ``apply`` (scale = 1 / B2), the consumer contract ``get_approx_kernel_op`` and ``sample``."""
+
+    def _init_common(self, dim: int, sigma: float, device, entry: str):
+        name = type(self).__name__
         if not 1 <= int(dim) <= 64:
-            raise H.NsvdError("RadialKernelOperator: unsupported input dimension (nsvd_rbf_apply takes 1 <= D <= 64)")
-        self.kind, self.ell, self.dim, self.sigma = int(kind), float(ell), int(dim), float(sigma)
+            raise H.NsvdError(f"{name}: unsupported input dimension ({entry} takes 1 <= D <= 64)")
+        self.dim, self.sigma = int(dim), float(sigma)
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise H.NsvdError("RadialKernelOperator: the operator lives on the GPU (no CPU path)")
+            raise H.NsvdError(f"{name}: the operator lives on the GPU (no CPU path)")
+
+    def workspace(self, B1: int, B2: int, L: int, device=None) -> torch.Tensor:
+        raise NotImplementedError
+
+    def apply_raw(self, x, y, f, scale, ws=None, out=None) -> torch.Tensor:
+        raise NotImplementedError
 
     def apply(self, x: torch.Tensor, x_ref: torch.Tensor, f_ref: torch.Tensor, ws=None, out=None) -> torch.Tensor:
         """Kf = (1 / B2) k(x, x_ref) @ f_ref, (B, L) float32; no gradient."""
         with torch.no_grad():
-            return H.rbf_apply(x, x_ref, f_ref, self.kind, self.ell, 1.0 / x_ref.shape[0], ws=ws, out=out)
+            return self.apply_raw(x, x_ref, f_ref, 1.0 / x_ref.shape[0], ws=ws, out=out)
 
     def get_approx_kernel_op(self, x_ref: torch.Tensor):
         """x_ref: (B2, dim) reference coordinates -> op(model, x, importance=None) -> (Kf, f)."""
+        name = type(self).__name__
         if not x_ref.is_cuda:
-            raise H.NsvdError("RadialKernelOperator: x_ref must live on the GPU (no CPU path)")
+            raise H.NsvdError(f"{name}: x_ref must live on the GPU (no CPU path)")
         y = x_ref.detach().float().contiguous()
 
         def op(model, x, importance=None):
             if importance is not None:
-                raise NotImplementedError("RadialKernelOperator: importance-weighted kernel operators are not built")
+                raise NotImplementedError(f"{name}: importance-weighted kernel operators are not built")
             if not x.is_cuda:
-                raise H.NsvdError("RadialKernelOperator: x must live on the GPU (no CPU path)")
+                raise H.NsvdError(f"{name}: x must live on the GPU (no CPU path)")
             f = model(x)
             same = x is x_ref or (x.data_ptr() == x_ref.data_ptr() and x.shape == x_ref.shape and
                                   x.stride() == x_ref.stride() and x.dtype == x_ref.dtype)
@@ -138,6 +147,59 @@ class RadialKernelOperator:
 
     def sample(self, batch_size: int, generator=None) -> torch.Tensor:
         return self.sigma * torch.randn(batch_size, self.dim, device=self.device, generator=generator)
+
+
+class RadialKernelOperator(MatrixFreeKernelOperator):
+    """k(x, y) = exp(-|x - y|^2 / (2 ell^2)) (kind H.RBF_GAUSSIAN) or exp(-|x - y| / ell) (H.RBF_EXPONENTIAL) on
+    `dim`-dimensional coordinates; training batches are sigma * randn(B, dim). Serves NestedLoRA.compute_loss_kernel
+    and NeuralEigenfunctions.compute_loss_kernel in both split_batch modes: the models take coordinates as they are."""
+
+    def __init__(self, kind: int, ell: float, dim: int, sigma: float = 1.0, device="cuda:0"):
+        if kind not in (H.RBF_GAUSSIAN, H.RBF_EXPONENTIAL):
+            raise ValueError("RadialKernelOperator: kind must be H.RBF_GAUSSIAN or H.RBF_EXPONENTIAL")
+        if not ell > 0 or not sigma > 0:
+            raise ValueError("RadialKernelOperator: ell and sigma must be positive")
+        self.kind, self.ell = int(kind), float(ell)
+        self._init_common(dim, sigma, device, "nsvd_rbf_apply")
+
+    def workspace(self, B1: int, B2: int, L: int, device=None) -> torch.Tensor:
+        return H.rbf_apply_workspace(B1, B2, self.dim, L, self.device if device is None else device)
+
+    def apply_raw(self, x, y, f, scale, ws=None, out=None) -> torch.Tensor:
+        return H.rbf_apply(x, y, f, self.kind, self.ell, scale, ws=ws, out=out)
+
+
+class DotKernelOperator(MatrixFreeKernelOperator):
+    """A kernel of the inner product on `dim`-dimensional coordinates (nsvd_dot_apply: x.y on the fp32 MFMA, the
+    (B, B2) matrix never stored): kind H.DOT_POLYNOMIAL k = (gamma x.y + coef0)^degree with an integer degree in 1..8, or
+    H.DOT_ARCCOS1 k = |x||y| / pi (sin t + (pi - t) cos t), cos t = x.y / (|x||y|) - Cho & Saul's order-1 arc-cosine
+    kernel, the NNGP kernel of one ReLU layer (gamma, coef0, degree unused). Training batches are sigma * randn(B, dim);
+    the same contract and callers as RadialKernelOperator. Polynomial kind: gamma <= 0 or coef0 < 0 are refused (not PSD
+    in general).
+    A polynomial kernel has FINITE rank C(dim + degree, degree) (see nystrom.Nystrom's note on ``oversample``)."""
+
+    def __init__(self, kind: int, dim: int, *, gamma: float = 1.0, coef0: float = 1.0, degree: int = 2,
+                 sigma: float = 1.0, device="cuda:0"):
+        if kind not in (H.DOT_POLYNOMIAL, H.DOT_ARCCOS1):
+            raise ValueError("DotKernelOperator: kind must be H.DOT_POLYNOMIAL or H.DOT_ARCCOS1")
+        if kind == H.DOT_POLYNOMIAL:  # (the arc-cosine kind ignores the three, as the C entry point does)
+            if not (gamma > 0 and math.isfinite(gamma)) or not (coef0 >= 0 and math.isfinite(coef0)):
+                raise ValueError("DotKernelOperator: gamma must be positive and coef0 non-negative (and finite): "
+                                 "the kernel is not positive semi-definite otherwise")
+            if int(degree) != degree or not 1 <= int(degree) <= 8:
+                raise ValueError("DotKernelOperator: degree must be an integer in 1..8")
+        else:
+            gamma, coef0, degree = 1.0, 1.0, 2
+        if not sigma > 0:
+            raise ValueError("DotKernelOperator: sigma must be positive")
+        self.kind, self.gamma, self.coef0, self.degree = int(kind), float(gamma), float(coef0), int(degree)
+        self._init_common(dim, sigma, device, "nsvd_dot_apply")
+
+    def workspace(self, B1: int, B2: int, L: int, device=None) -> torch.Tensor:
+        return H.dot_apply_workspace(B1, B2, self.dim, L, self.device if device is None else device)
+
+    def apply_raw(self, x, y, f, scale, ws=None, out=None) -> torch.Tensor:
+        return H.dot_apply(x, y, f, self.kind, self.gamma, self.coef0, self.degree, scale, ws=ws, out=out)
 
 
 def _gaussian_kernel_constants(sigma: float, ell: float):
@@ -200,10 +262,10 @@ def gaussian_kernel_eigenfunctions(x: torch.Tensor, sigma: float, ell: float, ne
 
 
 @torch.no_grad()
-def kernel_spectrum(op: RadialKernelOperator, fn, x_eval: torch.Tensor, chunk: int = 4096):
+def kernel_spectrum(op: MatrixFreeKernelOperator, fn, x_eval: torch.Tensor, chunk: int = 4096):
     """Rayleigh quotients of the columns of Phi = fn(x_eval) under the operator's kernel and the EMPIRICAL measure of
     x_eval (n, dim): cov = Phi^T Phi / n, quad = Phi^T (K Phi) / n with K Phi = (1 / n) k(x_eval, x_eval) Phi from
-    nsvd_rbf_apply against the whole evaluation set, `chunk` rows at a time; products and sums in float64
+    op.apply_raw (nsvd_rbf_apply / nsvd_dot_apply) against the whole evaluation set, `chunk` rows at a time; products and sums in float64
     (nsvd_spectrum_accumulate_f64, unweighted). Returns dict(eigvals = diag(quad) / diag(cov), norms = diag(cov), cov,
     quad) as float64 numpy arrays. fn maps (m, dim) float32 GPU coordinates to (m, L) values, L <= 64."""
     if not x_eval.is_cuda:
@@ -222,7 +284,7 @@ def kernel_spectrum(op: RadialKernelOperator, fn, x_eval: torch.Tensor, chunk: i
     for i in range(0, n, chunk):
         xc, pc = x_eval[i:i + chunk], phi[i:i + chunk]
         if ws is None or len(xc) != min(chunk, n):
-            ws = H.rbf_apply_workspace(len(xc), n, op.dim, L, x_eval.device)
+            ws = op.workspace(len(xc), n, L, x_eval.device)
         Kphi = op.apply(xc, x_eval, phi, ws=ws)
         H.spectrum_accumulate(pc, Kphi, ones[:len(xc)], 1.0, False, 0.5, cov, quad)
     cov64, quad64 = (cov / n).cpu().numpy(), (quad / n).cpu().numpy()
@@ -245,8 +307,9 @@ class FusedKernelTrainer:
     ways. One all-gather of the packed (2, B, L / W) block [f | Kf] per step (any L >= W: the first L % W ranks own one head more) (2 B L floats in total: 4 MB at cfg4) is
     the only exchange; moments, loss gradient and backward of the local heads are then local.
 
-    With a RadialKernelOperator the batch is a COORDINATE batch (drawn as sigma * randn, or given): the model is
-    evaluated on it directly and Kf = k(x, x) f / B comes from nsvd_rbf_apply in place of nsvd_kernel_apply; everything
+    With a RadialKernelOperator or a DotKernelOperator the batch is a COORDINATE batch (drawn as sigma * randn, or given):
+    the model is evaluated on it directly and Kf = k(x, x) f / B comes from the operator's apply_raw (nsvd_rbf_apply /
+    nsvd_dot_apply) in place of nsvd_kernel_apply; everything
     after Kf is the same sequence. Single GPU only (comm raises NotImplementedError)."""
 
     def __init__(self, op, L: int, m: int, hidden=(128, 128), batch_size: int = 8192,
@@ -256,12 +319,13 @@ class FusedKernelTrainer:
         from .nested_lowrank import nesting_masks
         from .trainer import FlatParams, reference_init
         self.op = op
-        self.radial = isinstance(op, RadialKernelOperator)
-        if self.radial and comm is not None:
-            raise NotImplementedError("FusedKernelTrainer: sharded runs (comm) are not built for RadialKernelOperator")
-        dev = op.device if self.radial else op.K.device
+        self.coords = isinstance(op, MatrixFreeKernelOperator)  # coordinate batches (radial or dot-product kernel)
+        if self.coords and comm is not None:
+            raise NotImplementedError("FusedKernelTrainer: sharded runs (comm) are not built for "
+                                      + type(op).__name__)
+        dev = op.device if self.coords else op.K.device
         self.device = dev
-        D = op.dim if self.radial else op.points.shape[1]
+        D = op.dim if self.coords else op.points.shape[1]
         self.comm = comm if comm is not None and comm.multi else None
         world = self.comm.world if self.comm is not None else 1
         rank = self.comm.rank if self.comm is not None else 0
@@ -292,8 +356,8 @@ class FusedKernelTrainer:
         self.lr, self.alpha, self.eps, self.ema_decay, self.num_iters = lr, rmsprop_decay, rmsprop_eps, ema_decay, num_iters
         self.c = float(hard_mul_const)
         self.ws = H.model_workspace(self.shape, self.B, dev)
-        if self.radial:
-            self.ka_ws = H.rbf_apply_workspace(self.B, self.B, D, Ll, dev)
+        if self.coords:
+            self.ka_ws = op.workspace(self.B, self.B, Ll, dev)
         else:
             self.ka_ws = torch.empty(H._lib.load().nsvd_kernel_apply_workspace_bytes(int(op.N), self.B, Ll),
                                      dtype=torch.uint8, device=dev)
@@ -320,13 +384,13 @@ class FusedKernelTrainer:
         with a RadialKernelOperator: on the (B, D) coordinate batch given in its place, or a fresh draw;
         returns the device loss triple (no sync)"""
         from .trainer import cosine_lr
-        if self.radial:
+        if self.coords:
             x = self.op.sample(self.B, self.gen) if idx is None else idx
             if not x.is_cuda or tuple(x.shape) != (self.B, self.op.dim):
                 raise H.NsvdError(f"FusedKernelTrainer.step: a ({self.B}, {self.op.dim}) coordinate batch on the GPU")
             x = x.float().contiguous()
             H.model_forward(self.shape, self._params, x, self.c, self.ws, save_for_backward=True, out=self.f_loc)
-            H.rbf_apply(x, x, self.f_loc, self.op.kind, self.op.ell, 1.0 / self.B, ws=self.ka_ws, out=self.Kf_loc)
+            self.op.apply_raw(x, x, self.f_loc, 1.0 / self.B, ws=self.ka_ws, out=self.Kf_loc)
         else:
             if idx is None:
                 idx = self.op.sample_indices(self.B, self.gen)

@@ -5,7 +5,8 @@ the matrix has to fit. Only the top ``dim`` <= 64 eigenpairs of G = k(xs, xs) / 
 block subspace iteration with Rayleigh-Ritz on a basis V of m = min(n, dim + oversample) <= 80 columns:
 
     V0 = randn(n, m) (seeded device generator), orthonormalised by steps 2-4 with Q = I; then per iteration
-    1. W = G V             ``RadialKernelOperator``: H.rbf_apply(xs, xs, V, kind, ell, 1 / n) - G is never stored;
+    1. W = G V             a matrix-free operator (``RadialKernelOperator``: H.rbf_apply(xs, xs, V, kind, ell, 1 / n);
+                           ``DotKernelOperator``: H.dot_apply likewise), through its apply_raw - G is never stored;
                            any other callable kernel(a, b): emp_kernel @ V / n, a library matmul (not the hot path: the
                            reference's own route around the same solver, and the yardstick of the GPU tests)
     2. S = W^T W, A = V^T W, C = V^T V          (m, m) float64                       H.tsgram_f64
@@ -31,7 +32,7 @@ import numpy as np
 import torch
 
 from . import hip_ops as H
-from .kernel_ops import RadialKernelOperator
+from .kernel_ops import MatrixFreeKernelOperator
 
 MAX_DIM = 64
 
@@ -99,10 +100,17 @@ class _Solve:
 
 
 class Nystrom:
-    """only for fixed kernels (the reference's words). kernel: a ``RadialKernelOperator`` (matrix-free) or any callable
-    kernel(a, b) -> (len(a), len(b)) matrix on the device; xs: (n, dim_x) on the GPU; dim <= 64 eigenpairs.
+    """only for fixed kernels (the reference's words). kernel: a ``RadialKernelOperator`` or ``DotKernelOperator``
+    (matrix-free) or any callable kernel(a, b) -> (len(a), len(b)) matrix on the device; xs: (n, dim_x) on the GPU;
+    dim <= 64 eigenpairs.
     Attributes: eigvals (dim,) float32 descending eigenvalues of k(xs, xs) / n, eigvecs (n, dim) unit columns,
-    training_time; and iterations, residuals (relative: |G v - theta v| / theta_0, length dim), converged."""
+    training_time; and iterations, residuals (relative: |G v - theta v| / theta_0, length dim), converged.
+
+    oversample: the basis has m = min(n, dim + oversample) columns. A Gram matrix of FINITE RANK r - a polynomial kernel
+    (gamma x.y + coef0)^degree on D coordinates has r = C(D + degree, degree), e.g. 10 at (3, 2) and 20 at (3, 3) - must
+    be given m <= r: with dim + oversample above the rank, W = G V has rank r < m, W^T W is rank deficient and the small
+    solve reports a non-positive Cholesky pivot (``NsvdError`` names it). Lower ``oversample`` (or ``dim``) so that
+    m <= r; the solver is not changed to hide it."""
 
     def __init__(self, kernel, xs, dim, emp_kernel=None, *, oversample=8, tol=1e-5, max_iters=200, check_every=4,
                  seed=0):
@@ -125,7 +133,7 @@ class Nystrom:
             raise H.NsvdError(f"Nystrom: dim must be in 1..{MAX_DIM}")
         if dim > xs.shape[0]:
             raise H.NsvdError(f"Nystrom: dim = {dim} exceeds the number of points {xs.shape[0]}")
-        if isinstance(kernel, RadialKernelOperator) and xs.shape[1] != kernel.dim:
+        if isinstance(kernel, MatrixFreeKernelOperator) and xs.shape[1] != kernel.dim:
             raise H.NsvdError(f"Nystrom: xs must be (n, {kernel.dim}) for this operator")
         return xs.detach().float().contiguous()
 
@@ -133,12 +141,12 @@ class Nystrom:
     @torch.no_grad()
     def _solve(xs, kernel, dim, emp_kernel, oversample, tol, max_iters, check_every, seed):
         n = xs.shape[0]
-        if isinstance(kernel, RadialKernelOperator) and emp_kernel is None:
+        if isinstance(kernel, MatrixFreeKernelOperator) and emp_kernel is None:
             m = min(n, dim + int(oversample))
-            ws = H.rbf_apply_workspace(n, n, kernel.dim, m, xs.device)
+            ws = kernel.workspace(n, n, m, xs.device)
 
             def apply(V, W):
-                H.rbf_apply(xs, xs, V, kernel.kind, kernel.ell, 1.0 / n, ws=ws, out=W)
+                kernel.apply_raw(xs, xs, V, 1.0 / n, ws=ws, out=W)
         else:
             if emp_kernel is None:
                 assert kernel is not None, "If emp_kernel is not provided, kernel must be provided"
@@ -154,12 +162,11 @@ class Nystrom:
 
     def __call__(self, xnew):
         # projection via Nystrom approximation: kernel(xnew, xs) @ eigvecs / eigvals / sqrt(n)
-        if isinstance(self.kernel, RadialKernelOperator):
+        if isinstance(self.kernel, MatrixFreeKernelOperator):
             if not xnew.is_cuda:
                 raise H.NsvdError("Nystrom: xnew must live on the GPU (no CPU path)")
             with torch.no_grad():
-                kv = H.rbf_apply(xnew.detach().float().contiguous(), self.xs, self.eigvecs, self.kernel.kind,
-                                 self.kernel.ell, 1.0)
+                kv = self.kernel.apply_raw(xnew.detach().float().contiguous(), self.xs, self.eigvecs, 1.0)
         else:
             kv = self.kernel(xnew, self.xs) @ self.eigvecs
         return kv / self.eigvals / math.sqrt(self.xs.shape[0])

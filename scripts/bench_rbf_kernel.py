@@ -15,7 +15,15 @@ v_mfma_f32_32x32x2_f32): the issue's model counts 2 B^2 L for the contraction pl
 pipe (10.7 GFLOP at the defaults); this kernel takes the distances by direct differences on the VALU, so the MFMA work
 it executes is the contraction alone (8.6 GFLOP) - both fractions are reported, named.
 Before timing, rbf_apply is compared with the library composition (max-normalised difference).
-Writes profiles/rbf_apply_bench.json. The numbers are reported as they come out."""
+Writes profiles/rbf_apply_bench.json. The numbers are reported as they come out.
+
+    python scripts/bench_rbf_kernel.py --dot [--b 8192 --dot-d 16,64 --l 64 --degree 2]
+
+times the dot-product kinds instead (nsvd_dot_apply): at each D of --dot-d, in ONE alternating loop with the same
+window scheme, `dot_apply` polynomial (gamma = 1 / D, coef0 = 1, --degree) and arc-cosine, the float32 library
+composition of each (x @ x.T, the map, @ f: it stores the (B, B) matrix) and `rbf_apply` (Gaussian, ell = sqrt(D)) on
+the same shape; the main kernels alone bracketed with nsvd_profile_next_forward. The MFMA work nsvd_dot_apply executes
+is BOTH contractions, 2 B^2 L + 2 B^2 Dp with Dp = D rounded up to 8. Writes profiles/dot_apply_bench.json."""
 import argparse
 import json
 import os
@@ -50,8 +58,90 @@ def median_ms_alternating(fns, reps, inner):
     return [dict(median_ms=float(np.median(ts)), min_ms=float(np.min(ts)), max_ms=float(np.max(ts))) for ts in times]
 
 
+def main_kernel_ms(fn, n=5):
+    """the main kernel alone (events recorded by the library around its launch), median of n"""
+    ks = []
+    for _ in range(n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        H.profile_next_forward(e0, e1)
+        fn()
+        torch.cuda.synchronize()
+        ks.append(float(e0.elapsed_time(e1)))
+    return float(np.median(ks))
+
+
+def bench_dot(a, dev):
+    B, L = a.b, a.l
+    scale = 1.0 / B
+    recs = []
+    for D in [int(v) for v in a.dot_d.split(",")]:
+        g = torch.Generator(device=dev).manual_seed(0)
+        x = torch.randn(B, D, device=dev, generator=g)
+        f = torch.randn(B, L, device=dev, generator=g)
+        gamma, coef0, degree, ell = 1.0 / D, 1.0, a.degree, float(D) ** 0.5
+        ws, out = H.dot_apply_workspace(B, B, D, L, dev), torch.empty(B, L, device=dev)
+        rws, rout = H.rbf_apply_workspace(B, B, D, L, dev), torch.empty(B, L, device=dev)
+
+        def poly():
+            H.dot_apply(x, x, f, H.DOT_POLYNOMIAL, gamma, coef0, degree, scale, ws=ws, out=out)
+
+        def arccos():
+            H.dot_apply(x, x, f, H.DOT_ARCCOS1, 1.0, 1.0, 2, scale, ws=ws, out=out)
+
+        def lib_poly():
+            return ((gamma * (x @ x.T) + coef0) ** degree) @ f * scale
+
+        def lib_arccos():
+            n = x.norm(dim=1)
+            p = n[:, None] * n[None, :]
+            c = ((x @ x.T) / p).clamp(-1.0, 1.0)
+            t = torch.acos(c)
+            return (p * (torch.sin(t) + (torch.pi - t) * c).clamp(min=0.0)) @ f * (scale / torch.pi)
+
+        def rbf():
+            H.rbf_apply(x, x, f, H.RBF_GAUSSIAN, ell, scale, ws=rws, out=rout)
+
+        poly()
+        ref = lib_poly()
+        agree_p = float((out - ref).abs().max() / ref.abs().max())
+        arccos()
+        ref = lib_arccos()
+        agree_a = float((out - ref).abs().max() / ref.abs().max())
+        del ref
+        t_p, t_a, t_lp, t_la, t_r = median_ms_alternating([poly, arccos, lib_poly, lib_arccos, rbf], a.reps, a.inner)
+        k_p, k_a, k_r = main_kernel_ms(poly), main_kernel_ms(arccos), main_kernel_ms(rbf)
+        Dp = (D + 7) // 8 * 8
+        flop = 2.0 * B * B * L + 2.0 * B * B * Dp
+        recs.append(dict(B1=B, B2=B, D=D, Dp=Dp, L=L, degree=degree, gamma=gamma, coef0=coef0, rbf_ell=ell,
+                         dot_apply_polynomial=t_p, dot_apply_arccos1=t_a, library_polynomial=t_lp,
+                         library_arccos1=t_la, rbf_apply_gaussian=t_r,
+                         dot_main_kernel_ms_polynomial=k_p, dot_main_kernel_ms_arccos1=k_a, rbf_main_kernel_ms=k_r,
+                         gflop_mfma_executed_both_contractions=flop / 1e9,
+                         mfma_peak_fraction_executed_main_kernel_polynomial=flop / MFMA_F32_PEAK / (k_p * 1e-3),
+                         mfma_peak_fraction_executed_main_kernel_arccos1=flop / MFMA_F32_PEAK / (k_a * 1e-3),
+                         rbf_mfma_peak_fraction_executed_main_kernel=2.0 * B * B * L / MFMA_F32_PEAK / (k_r * 1e-3),
+                         speedup_vs_library_polynomial=t_lp["median_ms"] / t_p["median_ms"],
+                         speedup_vs_library_arccos1=t_la["median_ms"] / t_a["median_ms"],
+                         ratio_to_rbf_apply_polynomial=t_p["median_ms"] / t_r["median_ms"],
+                         ratio_to_rbf_apply_arccos1=t_a["median_ms"] / t_r["median_ms"],
+                         max_normalised_difference_to_library_polynomial=agree_p,
+                         max_normalised_difference_to_library_arccos1=agree_a))
+        print(json.dumps(recs[-1]))
+    rec = dict(reps=a.reps, calls_per_window=a.inner, mfma_f32_peak_flops=MFMA_F32_PEAK,
+               device=torch.cuda.get_device_name(0), shapes=recs)
+    out_path = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "dot_apply_bench.json")
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    json.dump(rec, open(out_path, "w"), indent=1)
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "rbf_apply_bench.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dot", action="store_true", help="time the dot-product kinds (nsvd_dot_apply) instead")
+    ap.add_argument("--dot-d", default="16,64", help="--dot: the input dimensions, comma separated")
+    ap.add_argument("--degree", type=int, default=2, help="--dot: the polynomial kind's degree")
     ap.add_argument("--b", type=int, default=8192)
     ap.add_argument("--d", type=int, default=16)
     ap.add_argument("--l", type=int, default=64)
@@ -59,11 +149,13 @@ def main():
     ap.add_argument("--ell", type=float, default=4.0)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--inner", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rbf_apply_bench.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_rbf_kernel.py needs a GPU: a CPU run measures nothing")
     dev = "cuda:0"
+    if a.dot:
+        return bench_dot(a, dev)
     B, D, L = a.b, a.d, a.l
     g = torch.Generator(device=dev).manual_seed(0)
     x = torch.randn(B, D, device=dev, generator=g)
@@ -90,15 +182,7 @@ def main():
     ref = library()
     agree = float((out - ref).abs().max() / ref.abs().max())
     t_rbf, t_lib, t_dense = median_ms_alternating([rbf, library, dense], a.reps, a.inner)
-    # the main kernel alone (events recorded by the library around its launch)
-    ks = []
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        H.profile_next_forward(e0, e1)
-        rbf()
-        torch.cuda.synchronize()
-        ks.append(float(e0.elapsed_time(e1)))
-    k_ms = float(np.median(ks))
+    k_ms = main_kernel_ms(rbf)
     flop_contraction, flop_dist = 2.0 * B * B * L, 2.0 * B * B * D
     rec = dict(B1=B, B2=B, D=D, L=L, ell=ell, N_dense=a.n, reps=a.reps, calls_per_window=a.inner,
                rbf_apply=t_rbf, library_cdist_exp_matmul=t_lib, kernel_apply_dense=t_dense,

@@ -6,9 +6,14 @@ compared with the closed-form Mercer eigenvalues (gaussian_kernel_eigvals).
 
     python scripts/train_rbf_kernel.py [--steps 20000 --dim 2 --sigma 1 --ell 1.5 --L 10 --B 8192]
     python scripts/train_rbf_kernel.py --kind exponential --ell 2 --nystrom 8192
+    python scripts/train_rbf_kernel.py --kind arccos1 --dim 3 --nystrom 8192
+    python scripts/train_rbf_kernel.py --kind polynomial --gamma 0.5 --coef0 1 --degree 3 --dim 3 --nystrom 8192
 
+--kind polynomial / arccos1 train on a DotKernelOperator instead (k = (gamma x.y + coef0)^degree, or Cho & Saul's order-1
+arc-cosine kernel; --ell unused) and write profiles/dot_kernel_train.json by default.
 --nystrom N adds the Nystrom baseline (neural_svd_amd.Nystrom, matrix-free) on an N-point sample as a comparison
-column: the only one the exponential kind has, since its spectrum has no closed form.
+column: the only one the exponential and the two dot-product kinds have, since their spectra have no closed form here.
+(A polynomial kernel has rank C(dim + degree, degree): keep L + 8 at or below it, see Nystrom's note on oversample.)
 
 Prints steps/s and the relative errors; writes the record to profiles/rbf_kernel_train.json. The quotients are taken
 under the EMPIRICAL measure of --n-eval samples: their own float64 sampling gap to lambda_k is reported beside them
@@ -26,8 +31,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from neural_svd_amd import hip_ops as H  # noqa: E402
-from neural_svd_amd.kernel_ops import (FusedKernelTrainer, RadialKernelOperator, gaussian_kernel_eigenfunctions,  # noqa: E402
-                                       gaussian_kernel_eigvals, kernel_spectrum)
+from neural_svd_amd.kernel_ops import (DotKernelOperator, FusedKernelTrainer, RadialKernelOperator,  # noqa: E402
+                                       gaussian_kernel_eigenfunctions, gaussian_kernel_eigvals, kernel_spectrum)
 
 
 def main():
@@ -43,16 +48,36 @@ def main():
     ap.add_argument("--fourier-scale", type=float, default=0.3)
     ap.add_argument("--n-eval", type=int, default=16384)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--kind", choices=("gaussian", "exponential"), default="gaussian")
+    ap.add_argument("--kind", choices=("gaussian", "exponential", "polynomial", "arccos1"), default="gaussian")
+    ap.add_argument("--gamma", type=float, default=1.0, help="polynomial kind: k = (gamma x.y + coef0)^degree")
+    ap.add_argument("--coef0", type=float, default=1.0)
+    ap.add_argument("--degree", type=int, default=2)
     ap.add_argument("--nystrom", type=int, default=0, metavar="N",
                     help="also print the Nystrom eigenvalues of an N-point sample (0: off)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rbf_kernel_train.json"))
+    ap.add_argument("--out", default=None,
+                    help="default: profiles/rbf_kernel_train.json (radial kinds) or profiles/dot_kernel_train.json")
     a = ap.parse_args()
+    dot = a.kind in ("polynomial", "arccos1")
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "dot_kernel_train.json" if dot else "rbf_kernel_train.json")
     if not torch.cuda.is_available():
         raise SystemExit("train_rbf_kernel.py needs a GPU (neural_svd_amd has no CPU path)")
     dev = "cuda:0"
     gaussian = a.kind == "gaussian"
-    op = RadialKernelOperator(H.RBF_GAUSSIAN if gaussian else H.RBF_EXPONENTIAL, a.ell, a.dim, a.sigma, dev)
+    if a.kind == "polynomial":
+        import math
+        rank = math.comb(a.dim + a.degree, a.degree)
+        need = a.L + 8 if a.nystrom else a.L
+        if rank < need:
+            raise SystemExit(f"train_rbf_kernel.py: (gamma x.y + coef0)^{a.degree} on {a.dim} coordinates has rank "
+                             f"C({a.dim + a.degree}, {a.degree}) = {rank}, below " +
+                             (f"L + 8 = {need} (the Nystrom basis, see Nystrom's note on oversample)" if a.nystrom
+                              else f"L = {need}") + ": raise --dim or --degree, or lower --L")
+    if dot:
+        op = DotKernelOperator(H.DOT_POLYNOMIAL if a.kind == "polynomial" else H.DOT_ARCCOS1, a.dim, gamma=a.gamma,
+                               coef0=a.coef0, degree=a.degree, sigma=a.sigma, device=dev)
+    else:
+        op = RadialKernelOperator(H.RBF_GAUSSIAN if gaussian else H.RBF_EXPONENTIAL, a.ell, a.dim, a.sigma, dev)
     fk = FusedKernelTrainer(op, L=a.L, m=a.m, hidden=(128, 128), batch_size=a.B, sequential=True, lr=a.lr,
                             rmsprop_decay=0.999, rmsprop_eps=1e-10, num_iters=a.steps, fourier_scale=a.fourier_scale,
                             seed=a.seed, index_seed=a.seed + 1)
@@ -74,7 +99,8 @@ def main():
         return H.model_forward(fk.shape, fk._params, xe.contiguous(), fk.c, ws)
 
     got = kernel_spectrum(op, learned, x_eval, chunk)
-    rec = dict(kind=a.kind, dim=a.dim, sigma=a.sigma, ell=a.ell, L=a.L, B=a.B, steps=a.steps, lr=a.lr,
+    params = dict(gamma=a.gamma, coef0=a.coef0, degree=a.degree) if a.kind == "polynomial" else {} if dot else dict(ell=a.ell)
+    rec = dict(kind=a.kind, dim=a.dim, sigma=a.sigma, **params, L=a.L, B=a.B, steps=a.steps, lr=a.lr,
                fourier_scale=a.fourier_scale, seconds=round(dt, 2), steps_per_s=round((a.steps - 10) / dt, 1),
                loss=[float(v) for v in loss.cpu()], rayleigh_learned=[float(v) for v in got["eigvals"]],
                n_eval=a.n_eval, device=torch.cuda.get_device_name(0))
