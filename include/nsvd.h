@@ -631,6 +631,44 @@ int nsvd_ritz_step_f64(const double* S, const double* A, const double* C, int m,
 int nsvd_ts_rotate(const float* X, long ldx, int n, int m, const double* T, int ldt, int k, float* out, long ldo,
                    void* stream);
 
+/* ---- next row: SpIN on the matrix-free kernel operators (methods/spin.py) ----------------------------------------------
+ * The two pieces of SpIN's step that are its own; the moments come from nsvd_tsgram_f64, the term-1 cotangents
+ * dphi = Kphi gpi / B1, dKphi = phi gpi / B1 (Covariance.backward, spin.py:76-100) from nsvd_ts_rotate, and the parameter
+ * gradients of both from nsvd_model_backward (dKphi first through one more matrix-free product with the arguments
+ * swapped: the kernels are symmetric). NEW SYMBOLS ONLY: NSVD_ABI_VERSION stays 6.
+ *
+ * nsvd_spin_solve (spin.py:33-38 spin_step, :41-59 SpINFunction.forward, :139-148 of _compute_loss): one workgroup,
+ *   float64, everything (L, L) contiguous row-major, 2 <= L <= 64 (NSVD_EUNSUPPORTED above):
+ *       sigma = sigma_scale * sigma_raw, pi = pi_scale * pi_raw  (the raw Gram matrices X^T X, X^T Y of nsvd_tsgram_f64)
+ *       sigma_avg <- (1 - decay) sigma_avg + decay sigma          (float32 state, IN PLACE; zeros at the start, no bias
+ *                                                                  correction; the solve uses the unrounded value)
+ *       chol = cholesky(sigma_avg + 1e-3 I) (lower, float32 out), Ci = chol^-1, Lambda = Ci pi Ci^T
+ *       loss_eigvals[0] = trace(Lambda), loss_eigvals[1 .. L] = diag(Lambda)
+ *       gsigma = Ci^T triu(Lambda diag(diag Ci)), gpi_scaled = gpi_scale * (-Ci^T diag(diag Ci))   (float64 out)
+ *   *status (device int, zeroed by the caller) has NSVD_RITZ_BAD_PIVOT OR-ed in on a non-positive or non-finite pivot
+ *   or any non-finite result: chol, loss_eigvals, gsigma and gpi_scaled are then all zero and a non-finite element of
+ *   sigma_avg is left as it was - nothing non-finite is stored. Every loop has a trip count bounded by L.
+ *
+ * nsvd_spin_jac_step (spin.py:15-30 jac_model_params, :155-167 of _compute_loss): for the plain model (no exponential
+ *   or box mask: NSVD_EUNSUPPORTED; D <= 64, L <= 64, 1 .. NSVD_MAX_LAYERS layers of any width, B1 >= 2)
+ *       j_new[a, c] = (2 / B1) sum_b phi[b, a] d model_c(x_b) / d p;   J <- (1 - decay) J + decay j_new;
+ *       grads += sum_a gsigma[a, c] J[a, c]                            (ADDED: the caller zeroes or pre-fills grads)
+ *   The reference's j_avg.<name> tensors (L, L, *p.shape) are zero outside head c's slice of index [a, c]; the state J
+ *   keeps that slice alone: J[a], a < L, is one parameter set [W_0 | .. | W_n | b_0 | .. | b_n] (the nsvd_params layouts,
+ *   contiguous, no padding) of nsvd_spin_state_floats floats, J[a][..][c][..] = j_avg[a, c, c, ..]. x (B1, D), phi (B1, L)
+ *   = model(x) with the same hard_mul_const, gsigma (L, L) float64. Activations and unit-seed deltas are recomputed from
+ *   x into `ws` (nsvd_spin_jac_workspace_bytes, 256-byte aligned; 0 for an unsupported description): no workspace of a
+ *   model forward is needed. The contraction over b runs on v_mfma_f32_32x32x2_f32; sums over a are taken in ascending
+ *   order (registers, then a fixed-order second launch): no atomics, bit-reproducible. */
+int nsvd_spin_solve(const double* sigma_raw, double sigma_scale, const double* pi_raw, double pi_scale, int L,
+                    double decay, double gpi_scale, float* sigma_avg, float* chol, double* loss_eigvals, double* gsigma,
+                    double* gpi_scaled, int* status, void* stream);
+size_t nsvd_spin_state_floats(const nsvd_model_desc* desc);
+size_t nsvd_spin_jac_workspace_bytes(const nsvd_model_desc* desc, int B1);
+int nsvd_spin_jac_step(const nsvd_model_desc* desc, const nsvd_params* params, const float* x, int B1, const float* phi,
+                       float hard_mul_const, const double* gsigma, double decay, float* J, const nsvd_params* grads,
+                       void* ws, size_t ws_bytes, void* stream);
+
 /* ---- next row: the CDK (two-tower) NestedLoRA loss ------------------------------------------------------
  * NestedLoRALossFunctionForCDK (methods/nestedlora.py:273-332) as called by NestedLoRAForCDK.compute_loss
  * (methods/nestedlora.py:366-378; examples/cdk/sketchy/main_sketchy.py:188).

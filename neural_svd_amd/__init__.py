@@ -5,7 +5,8 @@ this package is the host-side mirror of the reference's Python interface for tha
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib", "SketchyRetrieval", "evaluate_truncations", "Nystrom", "run_nystrom", "DotKernelOperator"]
+__all__ = ["_lib", "SketchyRetrieval", "evaluate_truncations", "Nystrom", "run_nystrom", "DotKernelOperator",
+           "SpIN", "SpinKernelTrainer"]
 
 
 def __getattr__(name):
@@ -20,4 +21,7 @@ def __getattr__(name):
     if name == "DotKernelOperator":  # the dot-product kernel operator (kernel_ops.py), the same way
         from . import kernel_ops
         return kernel_ops.DotKernelOperator
+    if name in ("SpIN", "SpinKernelTrainer"):  # SpIN on the kernel-operator path (spin.py), the same way
+        from . import spin
+        return getattr(spin, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

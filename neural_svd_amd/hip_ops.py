@@ -992,6 +992,74 @@ def ts_rotate(X: torch.Tensor, T: torch.Tensor, k: Optional[int] = None,
     return out
 
 
+# ---- SpIN on the kernel-operator path (csrc/spin.hip; the step is neural_svd_amd/spin.py) -----------------------------
+SPIN_MAX_L = 64
+
+
+@_on_tensor_device
+def spin_solve(sigma_raw: torch.Tensor, sigma_scale: float, pi_raw: torch.Tensor, pi_scale: float, decay: float,
+               gpi_scale: float, sigma_avg: torch.Tensor, chol: torch.Tensor, loss_eigvals: torch.Tensor,
+               gsigma: torch.Tensor, gpi_scaled: torch.Tensor, status: torch.Tensor) -> None:
+    """Steps 2-5 of SpIN's loss in one workgroup, float64 (nsvd_spin_solve): sigma_avg (L, L) float32 is updated IN
+    PLACE with sigma_scale * sigma_raw, chol (L, L) float32 = cholesky(sigma_avg + 1e-3 I); loss_eigvals (1 + L) =
+    [trace | diag] of Lambda = chol^-1 (pi_scale pi_raw) chol^-T, gsigma and gpi_scaled = gpi_scale * gpi (L, L), all
+    float64. status: (1,) int32, RITZ_BAD_PIVOT is OR-ed in on failure (every output is then zero)."""
+    L = sigma_avg.shape[0]
+    f64 = torch.float64
+    for o, name in ((sigma_raw, "sigma_raw"), (pi_raw, "pi_raw"), (sigma_avg, "sigma_avg"), (chol, "chol"),
+                    (gsigma, "gsigma"), (gpi_scaled, "gpi_scaled")):
+        if tuple(o.shape) != (L, L):
+            raise NsvdError(f"spin_solve: {name} must be ({L}, {L})")
+    if loss_eigvals.numel() != L + 1 or status.numel() < 1:
+        raise NsvdError("spin_solve: loss_eigvals must hold 1 + L float64 values and status one int32")
+    rc = _lib.load().nsvd_spin_solve(_ptr(sigma_raw, "sigma_raw", f64), float(sigma_scale), _ptr(pi_raw, "pi_raw", f64),
+                                     float(pi_scale), L, float(decay), float(gpi_scale), _ptr(sigma_avg, "sigma_avg"),
+                                     _ptr(chol, "chol"), _ptr(loss_eigvals, "loss_eigvals", f64),
+                                     _ptr(gsigma, "gsigma", f64), _ptr(gpi_scaled, "gpi_scaled", f64),
+                                     _ptr(status, "status", torch.int32), _stream())
+    check(rc, "nsvd_spin_solve")
+
+
+def spin_state_floats(shape: ModelShape) -> int:
+    """floats of ONE parameter set of SpIN's compact Jacobian state ([W_0 | .. | b_0 | ..], no padding); J is (L, this)"""
+    d = shape.desc()
+    n = int(_lib.load().nsvd_spin_state_floats(C.byref(d)))
+    if n == 0:
+        raise NsvdError("nsvd_spin_state_floats: unsupported model (no exponential / box mask, D <= 64, L <= 64)")
+    return n
+
+
+def spin_jac_workspace(shape: ModelShape, B1: int, device) -> torch.Tensor:
+    d = shape.desc()
+    n = int(_lib.load().nsvd_spin_jac_workspace_bytes(C.byref(d), int(B1)))
+    if n == 0:
+        raise NsvdError("nsvd_spin_jac_workspace_bytes: unsupported model or batch (no exponential / box mask, D <= 64, "
+                        "L <= 64, B1 >= 2)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+@_on_tensor_device
+def spin_jac_step(shape: ModelShape, params: Params, x: torch.Tensor, phi: torch.Tensor, hard_mul_const: float,
+                  gsigma: torch.Tensor, decay: float, J: torch.Tensor, grads: Params,
+                  ws: Optional[torch.Tensor] = None) -> None:
+    """SpIN's second gradient term (nsvd_spin_jac_step): J (L, spin_state_floats) <- (1 - decay) J + decay j_new IN
+    PLACE, j_new[a, c] = (2 / B1) sum_b phi[b, a] d model_c(x_b) / d p, and grads += sum_a gsigma[a, c] J[a, c]."""
+    B1 = x.shape[0]
+    if tuple(x.shape) != (B1, shape.D) or tuple(phi.shape) != (B1, shape.L):
+        raise NsvdError(f"spin_jac_step: x must be (B1, {shape.D}) and phi (B1, {shape.L})")
+    if tuple(gsigma.shape) != (shape.L, shape.L):
+        raise NsvdError(f"spin_jac_step: gsigma must be ({shape.L}, {shape.L})")
+    if J.numel() != shape.L * spin_state_floats(shape):
+        raise NsvdError("spin_jac_step: J must hold L * spin_state_floats(shape) floats")
+    if ws is None:
+        ws = spin_jac_workspace(shape, B1, x.device)
+    d = shape.desc()
+    rc = _lib.load().nsvd_spin_jac_step(C.byref(d), C.byref(params), _ptr(x, "x"), B1, _ptr(phi, "phi"),
+                                        float(hard_mul_const), _ptr(gsigma, "gsigma", torch.float64), float(decay),
+                                        _ptr(J, "J"), C.byref(grads), ws.data_ptr(), ws.numel(), _stream())
+    check(rc, "nsvd_spin_jac_step")
+
+
 def cdk_workspace(B: int, L: int, set_first_mode_const: bool, device) -> torch.Tensor:
     n = _lib.load().nsvd_cdk_workspace_bytes(int(B), int(L), int(bool(set_first_mode_const)))
     return torch.empty(max(n, 256), dtype=torch.uint8, device=device)

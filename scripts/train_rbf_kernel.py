@@ -11,6 +11,8 @@ compared with the closed-form Mercer eigenvalues (gaussian_kernel_eigvals).
 
 --kind polynomial / arccos1 train on a DotKernelOperator instead (k = (gamma x.y + coef0)^degree, or Cho & Saul's order-1
 arc-cosine kernel; --ell unused) and write profiles/dot_kernel_train.json by default.
+--spin adds a SpIN column (neural_svd_amd.spin.SpinKernelTrainer: the same model, batch size and step count trained with
+SpIN's loss; --spin-decay is its moving-average rate) with its own steps/s.
 --nystrom N adds the Nystrom baseline (neural_svd_amd.Nystrom, matrix-free) on an N-point sample as a comparison
 column: the only one the exponential and the two dot-product kinds have, since their spectra have no closed form here.
 (A polynomial kernel has rank C(dim + degree, degree): keep L + 8 at or below it, see Nystrom's note on oversample.)
@@ -54,6 +56,9 @@ def main():
     ap.add_argument("--degree", type=int, default=2)
     ap.add_argument("--nystrom", type=int, default=0, metavar="N",
                     help="also print the Nystrom eigenvalues of an N-point sample (0: off)")
+    ap.add_argument("--spin", action="store_true", help="also train SpIN on the same operator and print its column")
+    ap.add_argument("--spin-decay", type=float, default=0.01)
+    ap.add_argument("--spin-lr", type=float, default=None, help="default: --lr")
     ap.add_argument("--out", default=None,
                     help="default: profiles/rbf_kernel_train.json (radial kinds) or profiles/dot_kernel_train.json")
     a = ap.parse_args()
@@ -116,6 +121,30 @@ def main():
                    sampling_gap_of_the_analytic_eigenfunctions=[float(v) for v in gap])
         columns.append(("closed form", lam))
         print("relative error of the Rayleigh quotients: " + " ".join(f"{v:.2e}" for v in rel))
+    if a.spin:
+        from neural_svd_amd.spin import SpinKernelTrainer
+        sp = SpinKernelTrainer(op, L=a.L, m=a.m, hidden=(128, 128), batch_size=a.B, decay=a.spin_decay,
+                               lr=a.lr if a.spin_lr is None else a.spin_lr, rmsprop_decay=0.999, rmsprop_eps=1e-10,
+                               num_iters=a.steps, fourier_scale=a.fourier_scale, seed=a.seed, index_seed=a.seed + 1)
+        for _ in range(10):
+            sp.step()
+        sp.check()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps - 10):
+            sp.step()
+        torch.cuda.synchronize()
+        dts = time.perf_counter() - t0
+        sp.check()
+        # Rayleigh quotients of the orthonormalised functions chol^-1 model(x), as for the other columns
+        sp_vals = kernel_spectrum(op, sp.forward, x_eval, chunk)["eigvals"]
+        rec.update(spin_decay=a.spin_decay, spin_steps_per_s=round((a.steps - 10) / dts, 1),
+                   spin_rayleigh=[float(v) for v in sp_vals], spin_loss=float(sp.loss[0]),
+                   spin_eigvals_running=[float(v) for v in sp.loss[1:].cpu()])
+        if gaussian:
+            rec.update(spin_rel_err=[float(v) for v in np.abs(sp_vals - lam) / lam])
+        print(f"SpIN steps/s {rec['spin_steps_per_s']}")
+        columns.append(("SpIN", sp_vals))
     if a.nystrom:
         from neural_svd_amd import Nystrom
         ny = Nystrom(op, op.sample(a.nystrom, torch.Generator(device=dev).manual_seed(a.seed + 2000)), a.L)
