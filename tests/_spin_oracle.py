@@ -82,6 +82,27 @@ def jacobian_contraction_einsum(x, phi, fB, ws, bs, c=1.0):
     return [2.0 * j / B1 for j in jw] + [2.0 * j / B1 for j in jb]
 
 
+def jacobian_contraction_abs(x, phi, fB, ws, bs, c=1.0):
+    """A[a, c, ...] = (2 / B1) sum_b |phi[b, a]| |delta_i^c(x_b)| |a_{i-1}^c(x_b)|: jacobian_contraction_einsum with every
+    factor of the sum over the samples replaced by its absolute value (the deltas and activations themselves are the
+    signed ones), so every element bounds the sum of the absolute terms of the same element of j_new - the scale a
+    float32 rounding error of that element is relative to, however much the signed terms cancel."""
+    B1, L, n = x.shape[0], ws[0].shape[0], len(ws)
+    _, ins, zs = model_forward(x, fB, ws, bs, c, keep=True)
+    aw, ab = [None] * n, [None] * n
+    delta = torch.full((L, 1, B1), float(c), dtype=x.dtype)
+    pa = phi.abs()
+    for i in range(n - 1, -1, -1):
+        if i == 0:
+            aw[i] = torch.einsum("ba,chb,bk->achk", pa, delta.abs(), ins[0].abs())
+        else:
+            aw[i] = torch.einsum("ba,chb,ckb->achk", pa, delta.abs(), ins[i].abs())
+        ab[i] = torch.einsum("ba,chb->ach", pa, delta.abs())[..., None]
+        if i > 0:
+            delta = torch.einsum("chp,chb->cpb", ws[i], delta) * softplus_grad(zs[i - 1])
+    return [2.0 * j / B1 for j in aw] + [2.0 * j / B1 for j in ab]
+
+
 def spin_solve(sigma_avg, pi):
     """steps 3-5: chol, Ci, Lambda, eigvals, loss, gsigma, gpi"""
     L = sigma_avg.shape[0]
@@ -164,6 +185,19 @@ def gaussian_kernel(ell):
     def k(a, b):
         return torch.exp(-torch.cdist(a, b) ** 2 / (2.0 * ell ** 2))
     return k
+
+
+# ---- what the GPU test modules share ---------------------------------------------------------------------------------
+def pack_tensors(H, shape, tensors, fB=None):
+    """hip_ops.pack_params of [ws.. | bs..]; H = neural_svd_amd.hip_ops, passed in: this module needs no GPU"""
+    n = len(shape.dims)
+    return H.pack_params(shape, tensors[:n], tensors[n:], fB, None)
+
+
+def solve_ref(state64, sigma, pi, decay):
+    """the moving average of sigma in float64 and spin_solve on it"""
+    s = (1.0 - decay) * state64 + decay * sigma
+    return s, spin_solve(s, pi)
 
 
 # ---- what the golden script and the tests share: sampling of large tensors and the error measure ------------------

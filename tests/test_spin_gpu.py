@@ -33,9 +33,7 @@ def golden():
 
 
 # ---- 1. the small solve ---------------------------------------------------------------------------------------------
-def _solve_ref(state64, sigma, pi, decay):
-    s = (1.0 - decay) * state64 + decay * sigma
-    return s, S.spin_solve(s, pi)
+_solve_ref = S.solve_ref
 
 
 @pytest.mark.parametrize("decay", [0.01, 1.0])
@@ -102,9 +100,7 @@ JAC_SHAPES = [(2, 8, (16, 16), 3, 1), (5, 8, (16, 24), 33, 3), (4, 64, (128, 128
               (16, 64, (128, 128), 96, 64), (64, 8, (16,), 40, 4), (3, 8, (16, 16, 16), 25, 2)]
 
 
-def _pack(H, shape, tensors, fB=None):
-    n = len(shape.dims)
-    return H.pack_params(shape, tensors[:n], tensors[n:], fB, None)
+_pack = S.pack_tensors
 
 
 @pytest.mark.parametrize("L,m,hidden,B1,D", JAC_SHAPES)
@@ -276,11 +272,14 @@ def test_compute_loss_kernel_matches_the_oracle_on_other_operators(golden, kind,
 
 # ---- 5. the trainer -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("split", [False, True])
-@pytest.mark.parametrize("L,m,hidden,B", [(4, 8, (16, 16), 25), (5, 64, (128, 128), 64)])
+@pytest.mark.parametrize("L,m,hidden,B", [(4, 8, (16, 16), 25), (5, 64, (128, 128), 64), (10, 96, (136, 40), 130),
+                                          (9, 8, (260,), 33)])
 def test_trainer_is_the_class_path_plus_opt_step(L, m, hidden, B, split):
     """three steps of SpinKernelTrainer = three steps of SpIN.compute_loss_kernel + backward + nsvd_opt_step on the same
     batches, bit for bit (the two gradient terms are added in the other order: a two-term float sum commutes); two
-    trainer runs give equal bits; kernel_spectrum runs on the orthonormalised functions"""
+    trainer runs give equal bits; kernel_spectrum runs on the orthonormalised functions. The last two shapes: the
+    trainer's reused Jacobian workspace against the class path's fresh one at more than one column tile (2 m = 192,
+    kin = 260) and short blocks of a (L = 10: 5 + 5, L = 9: 5 + 4); B = 33 with split_batch: halves of 17 and 16 rows"""
     from neural_svd_amd import hip_ops as H
     from neural_svd_amd.kernel_ops import RadialKernelOperator, kernel_spectrum
     from neural_svd_amd.spin import SpinKernelTrainer

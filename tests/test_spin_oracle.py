@@ -58,6 +58,25 @@ def test_batched_contraction_is_the_per_sample_loop(golden):
         assert S.rel_err(b, a) <= 1e-12
 
 
+def test_abs_contraction_bounds_the_contraction(golden):
+    """jacobian_contraction_abs, the scale of the GPU tests' per-slice error metric: |j_new| <= A element by element
+    (equal where no term changes sign: the last layer's bias, whose delta is the constant hard_mul_const, times |phi|)"""
+    fB, ws, bs, xs = S.load_case(golden, "a")
+    fB, ws, bs, x = fB.double(), [w.double() for w in ws], [b.double() for b in bs], xs[0].double()
+    phi = S.model_forward(x, fB, ws, bs, 0.7)
+    J = S.jacobian_contraction_einsum(x, phi, fB, ws, bs, 0.7)
+    A = S.jacobian_contraction_abs(x, phi, fB, ws, bs, 0.7)
+    assert len(J) == len(A) == 2 * len(ws)
+    for j, a in zip(J, A):
+        assert tuple(j.shape) == tuple(a.shape)
+        assert bool((a > 0).all()) and bool((j.abs() <= a * (1 + 1e-12)).all())
+    # the signed sum does cancel somewhere: the bound is not the contraction itself
+    assert any(bool((j.abs() < 0.5 * a).any()) for j, a in zip(J, A))
+    want = 2.0 * 0.7 * phi.abs().mean(0)  # A of the last bias: (2 / B1) sum_b |phi[b, a]| c for every head
+    L = phi.shape[1]
+    assert S.rel_err(A[-1].reshape(L, L), want[:, None].expand(L, L)) <= 1e-12
+
+
 def _build_spin(name, fB, ws, bs):
     from neural_svd_amd.models import GaussianFourierFeatureTransform, ParallelMLP, WaveFunctions
     from neural_svd_amd.spin import SpIN
