@@ -566,6 +566,25 @@ size_t nsvd_rbf_apply_workspace_bytes(int B1, int B2, int D, int L);
 int nsvd_rbf_apply(const float* x, int B1, const float* y, int B2, int D, const float* f, int L, int kind, float ell,
                    float scale, float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- next row: two-sided matrix-free radial kernel operator: both halves of a kernel SVD step ------------------------
+ * out_x[i][l] = scale_g * sum_j k(|x_i - y_j|) g[j][l]   (B1, L)   "K g"
+ * out_y[j][l] = scale_f * sum_i k(|x_i - y_j|) f[i][l]   (B2, L)   "K^T f"
+ * - the (Tg, Tadjf) producer of NestedLoRALossFunctionSVD(f, Tg, g, Tadjf) (methods/nestedlora.py:100-156; f = f(x),
+ * g = g(y), scale_g = 1 / B2, scale_f = 1 / B1) for a cross-domain kernel k(x, y) with x and y drawn from different
+ * measures; restated in float64 by tests/_pair_oracle.py. Kinds, distances, the exponent constant, ranges, error codes
+ * and the workspace rules are nsvd_rbf_apply's: x: (B1, D), y: (B2, D), g: (B2, L), f: (B1, L), float32 row-major; x may
+ * be y and f may be g; the outputs must not alias an input or each other. Every kernel value is evaluated once per 64
+ * heads and feeds both contractions; what crosses workgroups goes through partial copies in the workspace (at most 32 of
+ * either output, whatever the shape) that a second launch adds in a fixed order: no atomics, bit-reproducible. No
+ * allocation, no synchronisation; a refused call writes nothing. NEW SYMBOLS ONLY: NSVD_ABI_VERSION stays 6.
+ * nsvd_rbf_apply_pair_partition (host only) reports how a call of that shape splits the work: row_groups runs of x tiles
+ * (= partial copies of out_y) and col_slices runs of y rows (= partial copies of out_x). */
+size_t nsvd_rbf_apply_pair_workspace_bytes(int B1, int B2, int D, int L);
+int nsvd_rbf_apply_pair_partition(int B1, int B2, int D, int L, int* row_groups, int* col_slices);
+int nsvd_rbf_apply_pair(const float* x, int B1, const float* y, int B2, int D, const float* g, const float* f, int L,
+                        int kind, float ell, float scale_g, float scale_f, float* out_x, float* out_y, void* ws,
+                        size_t ws_bytes, void* stream);
+
 /* ---- next row: matrix-free dot-product kernel operator on coordinate batches ----------------------------------------
  * out[i][l] = scale * sum_j k(x_i, y_j) f[j][l] for a kernel of the inner product x.y - the other family kernel
  * eigenfunction work is run on (polynomial and neural-network Gaussian-process kernels) - on the same consumer contract

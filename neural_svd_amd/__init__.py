@@ -6,7 +6,8 @@ this package is the host-side mirror of the reference's Python interface for tha
 from . import _lib  # noqa: F401
 
 __all__ = ["_lib", "SketchyRetrieval", "evaluate_truncations", "Nystrom", "run_nystrom", "DotKernelOperator",
-           "SpIN", "SpinKernelTrainer"]
+           "SpIN", "SpinKernelTrainer", "PairedFunctions", "KernelSvdTrainer", "gaussian_cross_singular_values",
+           "gaussian_cross_modes", "kernel_singular_values"]
 
 
 def __getattr__(name):
@@ -24,4 +25,10 @@ def __getattr__(name):
     if name in ("SpIN", "SpinKernelTrainer"):  # SpIN on the kernel-operator path (spin.py), the same way
         from . import spin
         return getattr(spin, name)
+    if name in ("PairedFunctions", "KernelSvdTrainer"):  # the kernel SVD path (kernel_svd.py), the same way
+        from . import kernel_svd
+        return getattr(kernel_svd, name)
+    if name in ("gaussian_cross_singular_values", "gaussian_cross_modes", "kernel_singular_values"):
+        from . import kernel_ops
+        return getattr(kernel_ops, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

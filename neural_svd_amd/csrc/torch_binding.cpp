@@ -335,6 +335,25 @@ void rbf_apply(const at::Tensor& x, const at::Tensor& y, const at::Tensor& f, in
              "nsvd_rbf_apply");
 }
 
+// two-sided radial kernel operator (nsvd_rbf_apply_pair): x (B1, D), y (B2, D), g (B2, L), f (B1, L) ->
+// out_x (B1, L) = K g, out_y (B2, L) = K^T f; x may be y and f may be g
+void rbf_apply_pair(const at::Tensor& x, const at::Tensor& y, const at::Tensor& g, const at::Tensor& f, int64_t kind,
+                    double ell, double scale_g, double scale_f, at::Tensor out_x, at::Tensor out_y, at::Tensor ws) {
+    Dev dv;
+    TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && g.dim() == 2 && f.dim() == 2 && out_x.dim() == 2 && out_y.dim() == 2 &&
+                    y.size(1) == x.size(1) && g.size(0) == y.size(0) && f.size(0) == x.size(0) &&
+                    f.size(1) == g.size(1) && out_x.size(0) == x.size(0) && out_x.size(1) == g.size(1) &&
+                    out_y.size(0) == y.size(0) && out_y.size(1) == g.size(1),
+                "rbf_apply_pair: x (B1, D), y (B2, D), g (B2, L), f (B1, L), out_x (B1, L), out_y (B2, L)");
+    float *xp = f32(dv, x, "x"), *yp = f32(dv, y, "y"), *gp = f32(dv, g, "g"), *fp = f32(dv, f, "f");
+    float *ox = f32(dv, out_x, "out_x"), *oy = f32(dv, out_y, "out_y");
+    void* wp = bytes(dv, ws, "ws");
+    check_rc(nsvd_rbf_apply_pair(xp, (int)x.size(0), yp, (int)y.size(0), (int)x.size(1), gp, fp, (int)g.size(1), (int)kind,
+                                 (float)ell, (float)scale_g, (float)scale_f, ox, oy, wp,
+                                 (size_t)ws.numel() * ws.element_size(), dv.stream()),
+             "nsvd_rbf_apply_pair");
+}
+
 // matrix-free dot-product kernel operator (nsvd_dot_apply): the same tensors as rbf_apply
 void dot_apply(const at::Tensor& x, const at::Tensor& y, const at::Tensor& f, int64_t kind, double gamma, double coef0,
                int64_t degree, double scale, at::Tensor out, at::Tensor ws) {
@@ -419,7 +438,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                         "nsvd_evd_moments", "nsvd_evd_loss_grad", "nsvd_operator_backward_evd_step",
                                         "nsvd_operator_backward_evd_step_next", "nsvd_rmsprop_ema_step", "nsvd_opt_step",
                                         "nsvd_spectrum_accumulate", "nsvd_rbf_apply",
-                                        "nsvd_rbf_apply_workspace_bytes", "nsvd_dot_apply",
+                                        "nsvd_rbf_apply_workspace_bytes", "nsvd_rbf_apply_pair",
+                                        "nsvd_rbf_apply_pair_workspace_bytes", "nsvd_rbf_apply_pair_partition",
+                                        "nsvd_dot_apply",
                                         "nsvd_dot_apply_workspace_bytes", "nsvd_retrieval_eval",
                                         "nsvd_retrieval_workspace_bytes", "nsvd_retrieval_max_gallery",
                                         "nsvd_retrieval_max_k", "nsvd_retrieval_max_d"};
@@ -452,6 +473,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rbf_apply", &rbf_apply);
     m.def("rbf_apply_workspace_bytes",
           [](int B1, int B2, int D, int L) { return (int64_t)nsvd_rbf_apply_workspace_bytes(B1, B2, D, L); });
+    m.def("rbf_apply_pair", &rbf_apply_pair);
+    m.def("rbf_apply_pair_workspace_bytes",
+          [](int B1, int B2, int D, int L) { return (int64_t)nsvd_rbf_apply_pair_workspace_bytes(B1, B2, D, L); });
+    m.def("rbf_apply_pair_partition", [](int B1, int B2, int D, int L) {
+        int rg = 0, cs = 0;
+        check_rc(nsvd_rbf_apply_pair_partition(B1, B2, D, L, &rg, &cs), "nsvd_rbf_apply_pair_partition");
+        return std::vector<int>{rg, cs};
+    });
     m.def("dot_apply", &dot_apply);
     m.def("dot_apply_workspace_bytes",
           [](int B1, int B2, int D, int L) { return (int64_t)nsvd_dot_apply_workspace_bytes(B1, B2, D, L); });

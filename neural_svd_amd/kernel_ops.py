@@ -102,7 +102,12 @@ class MatrixFreeKernelOperator:
                                                       None: the operator's own)
         apply_raw(x, y, f, scale, ws=None, out=None)  out = scale * k(x, y) @ f, one C-ABI call, no gradient
 
-    and inherits ``apply`` (scale = 1 / B2), the consumer contract ``get_approx_kernel_op`` and ``sample``."""
+    and inherits ``apply`` (scale = 1 / B2), the consumer contract ``get_approx_kernel_op`` and ``sample``.
+
+    The two-sided product of a kernel SVD step (``kernel_svd``) - out_x = scale_g k(x, y) g and
+    out_y = scale_f k(x, y)^T f - is ``apply_pair_raw`` with ``workspace_pair``: here two ``apply_raw`` calls with the
+    arguments swapped (k(y, x) = k(x, y)^T for every kernel this class serves), which a subclass may replace by one
+    call; ``get_approx_kernel_svd_op`` is its consumer contract."""
 
     def _init_common(self, dim: int, sigma: float, device, entry: str):
         name = type(self).__name__
@@ -148,6 +153,38 @@ class MatrixFreeKernelOperator:
     def sample(self, batch_size: int, generator=None) -> torch.Tensor:
         return self.sigma * torch.randn(batch_size, self.dim, device=self.device, generator=generator)
 
+    def workspace_pair(self, B1: int, B2: int, L: int, device=None) -> torch.Tensor:
+        """the workspace of one apply_pair_raw of that shape: here the larger of the two products' (used in turn; the
+        two sizes are compared on the meta device, one buffer is allocated)"""
+        a, b = self.workspace(B1, B2, L, "meta").numel(), self.workspace(B2, B1, L, "meta").numel()
+        return self.workspace(B1, B2, L, device) if a >= b else self.workspace(B2, B1, L, device)
+
+    def apply_pair_raw(self, x, y, g, f, scale_g, scale_f, ws=None, out_x=None, out_y=None):
+        """(out_x, out_y) = (scale_g * k(x, y) @ g, scale_f * k(x, y)^T @ f): (B1, L) and (B2, L), no gradient.
+        x: (B1, dim), y: (B2, dim), g: (B2, L), f: (B1, L)."""
+        out_x = self.apply_raw(x, y, g, scale_g, ws=ws, out=out_x)
+        out_y = self.apply_raw(y, x, f, scale_f, ws=ws, out=out_y)
+        return out_x, out_y
+
+    def get_approx_kernel_svd_op(self):
+        """-> svd_op(model_f, model_g, x, y, importance=None) -> (Tg, f, Tadjf, g), the arguments of
+        NestedLoRALossFunctionSVD: f = model_f(x) and g = model_g(y) differentiable,
+        Tg = k(x, y) g / B2 and Tadjf = k(x, y)^T f / B1 without gradient (one apply_pair_raw)."""
+        name = type(self).__name__
+
+        def svd_op(model_f, model_g, x, y, importance=None):
+            if importance is not None:
+                raise NotImplementedError(f"{name}: importance-weighted kernel operators are not built")
+            if not x.is_cuda or not y.is_cuda:
+                raise H.NsvdError(f"{name}: x and y must live on the GPU (no CPU path)")
+            f, g = model_f(x), model_g(y)
+            with torch.no_grad():
+                Tg, Tadjf = self.apply_pair_raw(x.detach().float().contiguous(), y.detach().float().contiguous(),
+                                                g.detach().float().contiguous(), f.detach().float().contiguous(),
+                                                1.0 / y.shape[0], 1.0 / x.shape[0])
+            return Tg, f, Tadjf, g
+        return svd_op
+
 
 class RadialKernelOperator(MatrixFreeKernelOperator):
     """k(x, y) = exp(-|x - y|^2 / (2 ell^2)) (kind H.RBF_GAUSSIAN) or exp(-|x - y| / ell) (H.RBF_EXPONENTIAL) on
@@ -167,6 +204,17 @@ class RadialKernelOperator(MatrixFreeKernelOperator):
 
     def apply_raw(self, x, y, f, scale, ws=None, out=None) -> torch.Tensor:
         return H.rbf_apply(x, y, f, self.kind, self.ell, scale, ws=ws, out=out)
+
+    def workspace_pair(self, B1: int, B2: int, L: int, device=None) -> torch.Tensor:
+        """nsvd_rbf_apply_pair_workspace_bytes. With B1p, B2p, Lp = B1, B2, L rounded up to 64, Dp = dim rounded up to 4
+        and (RG, CG) = hip_ops.rbf_apply_pair_partition(B1, B2, dim, L), both at most 32:
+        4 * (B2p Dp + Lp (B1p + B2p) + CG B1p Lp + RG B2p Lp) bytes, each term rounded up to 256 - the partial copies
+        dominate: 100 MiB at B1 = B2 = 8192, L = 64 (RG, CG = 32, 16), about 0.8 GiB at 65 536 rows a side."""
+        return H.rbf_apply_pair_workspace(B1, B2, self.dim, L, self.device if device is None else device)
+
+    def apply_pair_raw(self, x, y, g, f, scale_g, scale_f, ws=None, out_x=None, out_y=None):
+        """one nsvd_rbf_apply_pair call: every kernel value evaluated once for both products"""
+        return H.rbf_apply_pair(x, y, g, f, self.kind, self.ell, scale_g, scale_f, ws=ws, out_x=out_x, out_y=out_y)
 
 
 class DotKernelOperator(MatrixFreeKernelOperator):
@@ -208,6 +256,26 @@ def _gaussian_kernel_constants(sigma: float, ell: float):
     return a, b, c, a + b + c
 
 
+def _mode_indices(dim: int, n: int) -> np.ndarray:
+    """the first n multi-indices (n, dim) by total degree, lexicographic within a degree"""
+    def compositions(k, d):
+        if d == 1:
+            yield (k,)
+            return
+        for j in range(k, -1, -1):
+            for rest in compositions(k - j, d - 1):
+                yield (j,) + rest
+
+    idx, deg = [], 0
+    while len(idx) < n:
+        for comp in compositions(deg, dim):
+            idx.append(comp)
+            if len(idx) == n:
+                break
+        deg += 1
+    return np.asarray(idx, dtype=np.int64).reshape(n, dim)
+
+
 def gaussian_kernel_modes(sigma: float, ell: float, dim: int, neigs: int):
     """The first `neigs` Mercer modes of k = exp(-|x - y|^2 / (2 ell^2)) under N(0, sigma^2 I_dim): eigenvalues
     (descending, float64) and their multi-indices (neigs, dim). Per dimension lambda_k = sqrt(2a / A) (b / A)^k with
@@ -215,23 +283,7 @@ def gaussian_kernel_modes(sigma: float, ell: float, dim: int, neigs: int):
     dimensions, so modes come by total degree n (eigenvalue lambda_0^dim (b / A)^n), lexicographic within a degree."""
     a, b, c, A = _gaussian_kernel_constants(sigma, ell)
     lam0, ratio = math.sqrt(2.0 * a / A), b / A
-
-    def compositions(n, d):
-        if d == 1:
-            yield (n,)
-            return
-        for k in range(n, -1, -1):
-            for rest in compositions(n - k, d - 1):
-                yield (k,) + rest
-
-    idx, n = [], 0
-    while len(idx) < neigs:
-        for comp in compositions(n, dim):
-            idx.append(comp)
-            if len(idx) == neigs:
-                break
-        n += 1
-    idx = np.asarray(idx, dtype=np.int64).reshape(neigs, dim)
+    idx = _mode_indices(dim, neigs)
     vals = np.array([np.prod([lam0 * ratio ** int(k) for k in row]) for row in idx], dtype=np.float64)
     return vals, idx
 
@@ -259,6 +311,67 @@ def gaussian_kernel_eigenfunctions(x: torch.Tensor, sigma: float, ell: float, ne
             v = v * herm[int(k)][:, d]
         cols.append(v)
     return torch.stack(cols, dim=1)
+
+
+def gaussian_cross_modes(sigma_x: float, sigma_y: float, ell: float, dim: int, n: int):
+    """The first `n` singular values (descending, float64) of k = exp(-|x - y|^2 / (2 ell^2)) as an operator from
+    L2(N(0, sigma_y^2 I_dim)) to L2(N(0, sigma_x^2 I_dim)), (Kg)(x) = E_y[k(x, y) g(y)], and their multi-indices
+    (n, dim). Per dimension s_k = s_0 rho^k with a = 1 / (4 sigma_x^2) + 1 / (2 ell^2),
+    b = 1 / (4 sigma_y^2) + 1 / (2 ell^2), c = 1 / (2 ell^2), t = c / sqrt(a b), r = sqrt(1 - t^2), rho = t / (1 + r),
+    s_0 = (2 pi sigma_x^2)^(-1/4) (2 pi sigma_y^2)^(-1/4) (a b)^(-1/4) sqrt(pi / (1 + r)) (Mehler's formula after
+    rescaling both sides); a mode's value is the product over dimensions, ordered as gaussian_kernel_modes orders them.
+    With sigma_x == sigma_y these are gaussian_kernel_eigvals."""
+    c = 1.0 / (2.0 * ell * ell)
+    a, b = 1.0 / (4.0 * sigma_x * sigma_x) + c, 1.0 / (4.0 * sigma_y * sigma_y) + c
+    t = c / math.sqrt(a * b)
+    r = math.sqrt(1.0 - t * t)
+    rho = t / (1.0 + r)
+    s0 = ((2.0 * math.pi * sigma_x * sigma_x) ** -0.25 * (2.0 * math.pi * sigma_y * sigma_y) ** -0.25 *
+          (a * b) ** -0.25 * math.sqrt(math.pi / (1.0 + r)))
+    idx = _mode_indices(dim, n)
+    vals = np.array([np.prod([s0 * rho ** int(k) for k in row]) for row in idx], dtype=np.float64)
+    return vals, idx
+
+
+def gaussian_cross_singular_values(sigma_x: float, sigma_y: float, ell: float, dim: int, n: int) -> np.ndarray:
+    return gaussian_cross_modes(sigma_x, sigma_y, ell, dim, n)[0]
+
+
+@torch.no_grad()
+def kernel_singular_values(op: MatrixFreeKernelOperator, fn_f, fn_g, x_eval: torch.Tensor, y_eval: torch.Tensor,
+                           chunk: int = 4096):
+    """Singular-value quotients of the column pairs of F = fn_f(x_eval) (nx, L) and G = fn_g(y_eval) (ny, L) under the
+    operator's kernel and the EMPIRICAL measures of the two samples: cross = F^T (K G) / nx with
+    K G = (1 / ny) k(x_eval, y_eval) G from op.apply_raw, `chunk` rows of x_eval at a time, cov_f = F^T F / nx,
+    cov_g = G^T G / ny; products and sums in float64 (nsvd_spectrum_accumulate_f64, used as kernel_spectrum uses it).
+    Returns dict(svals = diag(cross) / sqrt(diag(cov_f) diag(cov_g)), norms_f, norms_g, cross, cov_f, cov_g) as float64
+    numpy arrays. L <= 64."""
+    if not x_eval.is_cuda or not y_eval.is_cuda:
+        raise H.NsvdError("kernel_singular_values: x_eval and y_eval must live on the GPU (no CPU path)")
+    x_eval, y_eval = x_eval.float().contiguous(), y_eval.float().contiguous()
+    nx, ny, dev = x_eval.shape[0], y_eval.shape[0], x_eval.device
+    F = torch.cat([fn_f(x_eval[i:i + chunk]).float() for i in range(0, nx, chunk)]).contiguous()
+    G = torch.cat([fn_g(y_eval[i:i + chunk]).float() for i in range(0, ny, chunk)]).contiguous()
+    L = F.shape[1]
+    if G.shape[1] != L:
+        raise H.NsvdError("kernel_singular_values: fn_f and fn_g must return the same number of columns")
+    cov_f = torch.zeros((L, L), dtype=torch.float64, device=dev)
+    cross, cov_g, unused = torch.zeros_like(cov_f), torch.zeros_like(cov_f), torch.zeros_like(cov_f)
+    # (the constant coordinate column and lim = 1/2: kernel_spectrum's note on the accumulation kernel's weight)
+    ones = torch.ones((min(chunk, max(nx, ny)), 1), dtype=torch.float32, device=dev)
+    ws = None
+    for i in range(0, nx, chunk):
+        xc, fc = x_eval[i:i + chunk], F[i:i + chunk]
+        if ws is None or len(xc) != min(chunk, nx):
+            ws = op.workspace(len(xc), ny, L, dev)
+        KG = op.apply(xc, y_eval, G, ws=ws)
+        H.spectrum_accumulate(fc, KG, ones[:len(xc)], 1.0, False, 0.5, cov_f, cross)
+    for i in range(0, ny, chunk):
+        gc = G[i:i + chunk]
+        H.spectrum_accumulate(gc, gc, ones[:len(gc)], 1.0, False, 0.5, cov_g, unused)
+    cf, cg, cr = (cov_f / nx).cpu().numpy(), (cov_g / ny).cpu().numpy(), (cross / nx).cpu().numpy()
+    nf, ng = np.diag(cf).copy(), np.diag(cg).copy()
+    return dict(svals=np.diag(cr) / np.sqrt(nf * ng), norms_f=nf, norms_g=ng, cross=cr, cov_f=cf, cov_g=cg)
 
 
 @torch.no_grad()

@@ -1,0 +1,171 @@
+"""Kernel SVD: the singular functions of a cross-domain kernel k(x, y), x ~ p_x, y ~ p_y, learned with two models.
+
+The SVD form of the nested low-rank loss (``NestedLoRALossFunctionSVD(f, Tg, g, Tadjf)``, reference
+methods/nestedlora.py:114-164, which has no caller there) needs ``Tg = K g`` together with ``Tadjf = K^T f``; a
+``MatrixFreeKernelOperator`` produces the two with ``apply_pair_raw`` (``RadialKernelOperator``: one
+``nsvd_rbf_apply_pair`` call, every kernel value evaluated once; any other: two ``apply_raw`` calls).
+
+- ``PairedFunctions(f_model, g_model)``: the model of a NestedLoRA method that learns a pair;
+- ``NestedLoRA.compute_loss_kernel_svd(svd_op, x, y)`` (defined here, bound in nested_lowrank.py): the class path,
+  differentiable through both models;
+- ``KernelSvdTrainer``: the same step as a fixed sequence of C-ABI calls on two flat parameter buffers.
+
+For the Gaussian kernel between two Gaussian measures the singular values are known in closed form
+(``kernel_ops.gaussian_cross_singular_values``); ``kernel_ops.kernel_singular_values`` evaluates the quotients of any
+pair of function families on samples."""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import hip_ops as H
+from ._lib import NsvdError
+from .kernel_ops import MatrixFreeKernelOperator
+
+
+class PairedFunctions(nn.Module):
+    """The two function families of a kernel SVD: ``.f`` takes x (the left singular functions), ``.g`` takes y."""
+
+    def __init__(self, f_model: nn.Module, g_model: nn.Module):
+        super().__init__()
+        self.f, self.g = f_model, g_model
+
+    def forward(self, x, y):
+        return self.f(x), self.g(y)
+
+
+def compute_loss_kernel_svd(method, svd_op, x, y, importance=None):
+    """NestedLoRA.compute_loss_kernel_svd: ``svd_op(model_f, model_g, x, y, importance) -> (Tg, f, Tadjf, g)``
+    (``op.get_approx_kernel_svd_op()``) on the method's PairedFunctions, then the SVD loss on the HIP kernels.
+    Returns (loss, dict(f, g, Tg, Tadjf, eigvals=None)); loss.backward() reaches both models."""
+    if not isinstance(method.model, PairedFunctions):
+        raise NsvdError("compute_loss_kernel_svd: the method's model must be a PairedFunctions(f_model, g_model)")
+    if method.sort_indices is not None:
+        raise NsvdError("compute_loss_kernel_svd: register_eigvals (sorted heads) is not built for a pair of models")
+    if not callable(svd_op):
+        raise NsvdError("compute_loss_kernel_svd: svd_op must be callable as svd_op(model_f, model_g, x, y, importance)")
+    if x.dim() != 2 or y.dim() != 2 or x.shape[0] != y.shape[0]:
+        raise NsvdError(f"compute_loss_kernel_svd: x {tuple(x.shape)} and y {tuple(y.shape)} must be two 2-D batches of "
+                        "the same number of rows (NestedLoRALossFunctionSVD on the HIP kernels takes B1 == B2)")
+    Tg, f, Tadjf, g = svd_op(method.model.f, method.model.g, x, y, importance=importance)
+    L = method.neigs
+    for t, n in ((f, "f"), (g, "g"), (Tg, "Tg"), (Tadjf, "Tadjf")):
+        if t.dim() != 2 or tuple(t.shape) != (x.shape[0], L):
+            raise NsvdError(f"compute_loss_kernel_svd: svd_op returned {n} {tuple(t.shape)}: expected "
+                            f"({x.shape[0]}, {L})")
+    f, g = f.float().contiguous(), g.float().contiguous()
+    loss = method._compute_loss(f, Tg.detach().float().contiguous(), g, Tadjf.detach().float().contiguous(), evd=False)
+    return loss, dict(f=f, g=g, Tg=Tg, Tadjf=Tadjf, eigvals=None)
+
+
+class KernelSvdTrainer:
+    """The kernel SVD training step (NestedLoRA.compute_loss_kernel_svd on a PairedFunctions, loss.backward(), one
+    optimiser over both models) as a fixed sequence of C-ABI calls on two flat parameter buffers: two
+    nsvd_model_forward (f on x, g on y, written into the halves of X = [f; g]) -> op.apply_pair_raw into the halves of
+    TX = [Tg; Tadjf] -> nsvd_evd_moments + nsvd_evd_loss_grad on (X, TX) (the identity in NestedLoRALossFunctionSVD's
+    docstring: d loss / d X = [d loss / d f; d loss / d g]) -> two nsvd_model_backward -> two nsvd_opt_step. No torch
+    autograd, no torch.optim; torch draws the two batches. The SpinKernelTrainer pattern and its constraints: 128-wide
+    hidden layers, 2 m % 128 == 0, batch % 32 == 0; single GPU.
+
+    x ~ N(0, sigma_x^2 I), y ~ N(0, sigma_y^2 I) (defaults: the operator's sigma for both). The g model is seeded with
+    seed + 1. ``loss`` = nsvd_evd_loss_grad's triple on (X, TX) after a step: loss[0] is the SVD loss - its operator
+    term -2 mean over the 2 B rows of sum_l v_l X TX is -2 mean_b sum_l v_l f Tg because
+    sum_b f_b . Tg_b = f^T K g / B = sum_b g_b . Tadjf_b."""
+
+    def __init__(self, op, L: int, m: int, hidden=(128, 128), batch_size: int = 8192, sigma_x: float = None,
+                 sigma_y: float = None, sequential: bool = False, step: int = 1, lr: float = 1e-4,
+                 optimizer: str = "rmsprop", rmsprop_decay: float = 0.99, rmsprop_eps: float = 1e-8,
+                 momentum: float = 0.0, num_iters: int = 0, fourier_scale: float = 0.05, hard_mul_const: float = 1.0,
+                 seed: int = 0, index_seed: int = 1):
+        from .nested_lowrank import nesting_masks
+        from .trainer import FlatParams, reference_init
+        if not isinstance(op, MatrixFreeKernelOperator):
+            raise NotImplementedError("KernelSvdTrainer: a MatrixFreeKernelOperator (radial or dot-product kernel)")
+        self.op, self.device = op, op.device
+        dev = self.device
+        self.B = int(batch_size)
+        D = op.dim
+        if any(h != 128 for h in hidden) or self.B % 32 != 0 or (2 * int(m)) % 128 != 0:
+            raise NsvdError("KernelSvdTrainer needs the MFMA model kernels: 128-wide hidden layers, batch % 32 == 0, "
+                            "2 m % 128 == 0 (nsvd_model_backward)")
+        self.shape = H.ModelShape(L=int(L), D=D, m=int(m), hidden=tuple(hidden), has_exp_mask=False)
+        self.sigma_x = float(op.sigma if sigma_x is None else sigma_x)
+        self.sigma_y = float(op.sigma if sigma_y is None else sigma_y)
+        if not (self.sigma_x > 0 and self.sigma_y > 0):
+            raise ValueError("KernelSvdTrainer: sigma_x and sigma_y must be positive")
+        self.c = float(hard_mul_const)
+        self.lr, self.num_iters = float(lr), int(num_iters)
+        self.cfg = H.opt_config(optimizer, lr, alpha=rmsprop_decay, eps=rmsprop_eps, momentum=momentum)
+        uses_sq, uses_mom = H.opt_uses(self.cfg)
+        self.Pf = FlatParams(self.shape, dev, with_state=True, with_mom=uses_mom)
+        self.Pg = FlatParams(self.shape, dev, with_state=True, with_mom=uses_mom)
+        self._sq = (self.Pf.sq, self.Pg.sq) if uses_sq else (None, None)
+        for P, s in ((self.Pf, seed), (self.Pg, seed + 1)):
+            fB0, ws0, bs0, _ = reference_init(self.shape, fourier_scale, None, s)
+            P.load(fB0, ws0, bs0, None)
+        self._params = (self.Pf.pack(self.Pf.flat, True), self.Pg.pack(self.Pg.flat, True))
+        self._grads = (self.Pf.pack(self.Pf.grad, False), self.Pg.pack(self.Pg.grad, False))
+        self.vector_mask, self.matrix_mask, self.mask_kind = nesting_masks(int(L), bool(sequential), step)
+        cust = self.mask_kind == H.MASK_CUSTOM
+        self.v = self.vector_mask.to(dev).float().contiguous() if cust else None
+        self.M = self.matrix_mask.to(dev).float().contiguous() if cust else None
+        B = self.B
+        self.model_ws = (H.model_workspace(self.shape, B, dev), H.model_workspace(self.shape, B, dev))
+        self.pair_ws = op.workspace_pair(B, B, int(L), dev)
+        self.X = torch.empty((2 * B, L), dtype=torch.float32, device=dev)
+        self.TX = torch.empty_like(self.X)
+        self.dX = torch.empty_like(self.X)
+        self.moments = torch.empty(2 * L * L + 1, dtype=torch.float32, device=dev)
+        self.loss = torch.zeros(3, dtype=torch.float32, device=dev)
+        self.scratch = H.evd_scratch(2 * B, int(L), dev)
+        self.gen = torch.Generator(device=dev).manual_seed(index_seed)
+        self.t = 0
+
+    def sample(self):
+        D = self.op.dim
+        x = self.sigma_x * torch.randn(self.B, D, device=self.device, generator=self.gen)
+        y = self.sigma_y * torch.randn(self.B, D, device=self.device, generator=self.gen)
+        return x, y
+
+    def step(self, x: torch.Tensor = None, y: torch.Tensor = None) -> torch.Tensor:
+        """one optimiser step on the (B, D) coordinate batches x and y (or a fresh draw of both); returns ``loss``
+        (no sync)"""
+        from .trainer import cosine_lr
+        if (x is None) != (y is None):
+            raise NsvdError("KernelSvdTrainer.step: give both x and y, or neither")
+        if x is None:
+            x, y = self.sample()
+        B, D = self.B, self.op.dim
+        for t, n in ((x, "x"), (y, "y")):
+            if not t.is_cuda or tuple(t.shape) != (B, D):
+                raise NsvdError(f"KernelSvdTrainer.step: {n} must be a ({B}, {D}) coordinate batch on the GPU")
+        x, y = x.float().contiguous(), y.float().contiguous()
+        f, g = self.X[:B], self.X[B:]
+        H.model_forward(self.shape, self._params[0], x, self.c, self.model_ws[0], save_for_backward=True, out=f)
+        H.model_forward(self.shape, self._params[1], y, self.c, self.model_ws[1], save_for_backward=True, out=g)
+        self.op.apply_pair_raw(x, y, g, f, 1.0 / B, 1.0 / B, ws=self.pair_ws, out_x=self.TX[:B], out_y=self.TX[B:])
+        H.evd_moments(self.X, self.TX, self.mask_kind, self.v, self.moments, self.scratch)
+        H.evd_loss_grad(self.X, self.TX, self.mask_kind, self.v, self.M, self.moments, 1.0, True, loss=self.loss,
+                        df=self.dX)
+        H.model_backward(self.shape, self._params[0], x, self.dX[:B], self._grads[0], self.model_ws[0])
+        H.model_backward(self.shape, self._params[1], y, self.dX[B:], self._grads[1], self.model_ws[1])
+        lr = cosine_lr(self.lr, self.t, self.num_iters) if self.num_iters > 0 else self.lr
+        for P, sq in zip((self.Pf, self.Pg), self._sq):
+            H.opt_step(self.cfg, P.flat, P.grad, sq, P.mom, None, self.t, lr=lr)
+        self.t += 1
+        return self.loss
+
+    def _eval(self, which: int, z: torch.Tensor) -> torch.Tensor:
+        if not z.is_cuda:
+            raise NsvdError("KernelSvdTrainer: coordinates must live on the GPU (no CPU path)")
+        z = z.float().contiguous()
+        return H.model_forward(self.shape, self._params[which], z, self.c,
+                               H.model_workspace(self.shape, z.shape[0], z.device))
+
+    def f(self, x: torch.Tensor) -> torch.Tensor:
+        """the left functions at x (n, D): (n, L)"""
+        return self._eval(0, x)
+
+    def g(self, y: torch.Tensor) -> torch.Tensor:
+        """the right functions at y (n, D): (n, L)"""
+        return self._eval(1, y)

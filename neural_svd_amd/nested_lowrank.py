@@ -303,6 +303,14 @@ class NestedLoRA(nn.Module):
         loss = self._compute_loss(f, Kf.contiguous(), f1, f2, evd=True)
         return loss, dict(f=f, Tf=Kf, eigvals=None)
 
+    def compute_loss_kernel_svd(self, svd_op, x, y, importance=None):
+        """The SVD form on a cross-domain kernel k(x, y): this method's model is a kernel_svd.PairedFunctions,
+        ``svd_op(model_f, model_g, x, y, importance) -> (Tg, f, Tadjf, g)`` comes from
+        ``MatrixFreeKernelOperator.get_approx_kernel_svd_op()``; the loss is ``_compute_loss(f, Tg, g, Tadjf,
+        evd=False)``. Returns (loss, dict(f, g, Tg, Tadjf, eigvals=None)). (kernel_svd.compute_loss_kernel_svd)"""
+        from .kernel_svd import compute_loss_kernel_svd
+        return compute_loss_kernel_svd(self, svd_op, x, y, importance)
+
     def apply_operator(self, operator, x, importance=None):
         """Tf, f = operator(self, x, importance).
         This package's OperatorWrapper (finite-difference / exact Hamiltonian with Gaussian or no importance): ONE fused

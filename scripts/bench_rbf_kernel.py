@@ -23,7 +23,14 @@ times the dot-product kinds instead (nsvd_dot_apply): at each D of --dot-d, in O
 window scheme, `dot_apply` polynomial (gamma = 1 / D, coef0 = 1, --degree) and arc-cosine, the float32 library
 composition of each (x @ x.T, the map, @ f: it stores the (B, B) matrix) and `rbf_apply` (Gaussian, ell = sqrt(D)) on
 the same shape; the main kernels alone bracketed with nsvd_profile_next_forward. The MFMA work nsvd_dot_apply executes
-is BOTH contractions, 2 B^2 L + 2 B^2 Dp with Dp = D rounded up to 8. Writes profiles/dot_apply_bench.json."""
+is BOTH contractions, 2 B^2 L + 2 B^2 Dp with Dp = D rounded up to 8. Writes profiles/dot_apply_bench.json.
+
+    python scripts/bench_rbf_kernel.py --pair [--b 8192 --pair-d 2,16,64 --l 64]
+
+times the two-sided call (nsvd_rbf_apply_pair: K g and K^T f, every kernel value evaluated once) against TWO
+nsvd_rbf_apply calls with swapped arguments (what the interface had before), both kinds, at each D of --pair-d, in ONE
+alternating loop with the same window scheme; x ~ N(0, I), y ~ N(0, I / 4), ell = sqrt(D). The MFMA work either route
+executes is 4 B^2 L. Writes profiles/rbf_apply_pair_bench.json."""
 import argparse
 import json
 import os
@@ -134,6 +141,50 @@ def bench_dot(a, dev):
     json.dump(rec, open(out_path, "w"), indent=1)
 
 
+def bench_pair(a, dev):
+    B, L = a.b, a.l
+    scale = 1.0 / B
+    recs = []
+    for D in [int(v) for v in a.pair_d.split(",")]:
+        gen = torch.Generator(device=dev).manual_seed(0)
+        x = torch.randn(B, D, device=dev, generator=gen)
+        y = 0.5 * torch.randn(B, D, device=dev, generator=gen)
+        g = torch.randn(B, L, device=dev, generator=gen)
+        f = torch.randn(B, L, device=dev, generator=gen)
+        ell = float(D) ** 0.5
+        pws = H.rbf_apply_pair_workspace(B, B, D, L, dev)
+        rws = H.rbf_apply_workspace(B, B, D, L, dev)
+        px, py, rx, ry = (torch.empty(B, L, device=dev) for _ in range(4))
+        flop = 4.0 * B * B * L
+        for name, kind in (("gaussian", H.RBF_GAUSSIAN), ("exponential", H.RBF_EXPONENTIAL)):
+            def pair():
+                H.rbf_apply_pair(x, y, g, f, kind, ell, scale, scale, ws=pws, out_x=px, out_y=py)
+
+            def two_calls():
+                H.rbf_apply(x, y, g, kind, ell, scale, ws=rws, out=rx)
+                H.rbf_apply(y, x, f, kind, ell, scale, ws=rws, out=ry)
+
+            pair()
+            two_calls()
+            agree = max(float((px - rx).abs().max() / rx.abs().max()), float((py - ry).abs().max() / ry.abs().max()))
+            t_p, t_2 = median_ms_alternating([pair, two_calls], a.reps, a.inner)
+            k_p = main_kernel_ms(pair)
+            recs.append(dict(B1=B, B2=B, D=D, L=L, kind=name, ell=ell, partition=list(H.rbf_apply_pair_partition(B, B, D, L)),
+                             workspace_mib=pws.numel() / 2 ** 20, rbf_apply_pair=t_p, two_rbf_apply_calls=t_2,
+                             pair_main_kernel_ms=k_p, speedup_over_two_calls=t_2["median_ms"] / t_p["median_ms"],
+                             gflop_mfma_executed_both_contractions=flop / 1e9,
+                             mfma_peak_fraction_executed_pair_whole_call=flop / MFMA_F32_PEAK / (t_p["median_ms"] * 1e-3),
+                             mfma_peak_fraction_executed_pair_main_kernel=flop / MFMA_F32_PEAK / (k_p * 1e-3),
+                             mfma_peak_fraction_executed_two_calls=flop / MFMA_F32_PEAK / (t_2["median_ms"] * 1e-3),
+                             max_normalised_difference_between_routes=agree))
+            print(json.dumps(recs[-1]))
+    rec = dict(reps=a.reps, calls_per_window=a.inner, mfma_f32_peak_flops=MFMA_F32_PEAK,
+               device=torch.cuda.get_device_name(0), shapes=recs)
+    out_path = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "rbf_apply_pair_bench.json")
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    json.dump(rec, open(out_path, "w"), indent=1)
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "rbf_apply_bench.json")
 
 
@@ -142,6 +193,8 @@ def main():
     ap.add_argument("--dot", action="store_true", help="time the dot-product kinds (nsvd_dot_apply) instead")
     ap.add_argument("--dot-d", default="16,64", help="--dot: the input dimensions, comma separated")
     ap.add_argument("--degree", type=int, default=2, help="--dot: the polynomial kind's degree")
+    ap.add_argument("--pair", action="store_true", help="time nsvd_rbf_apply_pair against two nsvd_rbf_apply calls")
+    ap.add_argument("--pair-d", default="2,16,64", help="--pair: the input dimensions, comma separated")
     ap.add_argument("--b", type=int, default=8192)
     ap.add_argument("--d", type=int, default=16)
     ap.add_argument("--l", type=int, default=64)
@@ -156,6 +209,8 @@ def main():
     dev = "cuda:0"
     if a.dot:
         return bench_dot(a, dev)
+    if a.pair:
+        return bench_pair(a, dev)
     B, D, L = a.b, a.d, a.l
     g = torch.Generator(device=dev).manual_seed(0)
     x = torch.randn(B, D, device=dev, generator=g)
