@@ -614,6 +614,25 @@ int nsvd_dot_apply(const float* x, int B1, const float* y, int B2, int D, const 
                    float gamma, float coef0, int degree, float scale, float* out, void* ws, size_t ws_bytes,
                    void* stream);
 
+/* ---- next row: two-sided matrix-free dot-product kernel operator: both halves of a kernel SVD step -------------------
+ * out_x[i][l] = scale_g * sum_j k(x_i, y_j) g[j][l]   (B1, L)   "K g"
+ * out_y[j][l] = scale_f * sum_i k(x_i, y_j) f[i][l]   (B2, L)   "K^T f"
+ * - nsvd_rbf_apply_pair for the kernels of the inner product. Kinds, numerical rules (the power by multiplication, the
+ * clamps, a row of zero norm on either side gives exactly 0), ranges (1 <= D <= 64, any B1, B2, L >= 1) and error codes
+ * are nsvd_dot_apply's; operand shapes (x: (B1, D), y: (B2, D), g: (B2, L), f: (B1, L), float32 row-major), aliasing
+ * rules (x may be y and f may be g; an output that overlaps an input or the other output is NSVD_EINVAL) and the
+ * partition query are nsvd_rbf_apply_pair's. Every x_i . y_j is formed once per 64 heads on the fp32 MFMA, mapped once
+ * in registers and feeds both contractions; rows that only pad a tile are forced to 0 on BOTH sides, so a kernel value
+ * that overflows (coef0^degree) reaches the rows it belongs to and no other. Partial copies in the workspace (at most 32
+ * of either output, whatever the shape) are added in a fixed order by a second launch: no atomics, bit-reproducible.
+ * No allocation, no synchronisation; a refused call writes nothing. Restated in float64 by tests/_dot_pair_oracle.py.
+ * NEW SYMBOLS ONLY: NSVD_ABI_VERSION stays 6. */
+size_t nsvd_dot_apply_pair_workspace_bytes(int B1, int B2, int D, int L);
+int nsvd_dot_apply_pair_partition(int B1, int B2, int D, int L, int* row_groups, int* col_slices);
+int nsvd_dot_apply_pair(const float* x, int B1, const float* y, int B2, int D, const float* g, const float* f, int L,
+                        int kind, float gamma, float coef0, int degree, float scale_g, float scale_f, float* out_x,
+                        float* out_y, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- next row: the dense side of the Nystrom baseline (methods/nystrom.py:8-47) -------------------------------------
  * The reference's Nystrom.evd forms the n x n Gram matrix and calls a host eigh on it; here the top L <= 64 eigenpairs of
  * G = k(xs, xs) / n come from block subspace iteration with Rayleigh-Ritz on a basis V (n, m), m <= 80, with

@@ -184,6 +184,9 @@ SIGNATURES = {
     "nsvd_rbf_apply_pair": (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _F, _F, _F, _P, _P, _P, _Z, _P]),
     "nsvd_dot_apply_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "nsvd_dot_apply": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _F, _F, _I, _F, _P, _P, _Z, _P]),
+    "nsvd_dot_apply_pair_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "nsvd_dot_apply_pair_partition": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nsvd_dot_apply_pair": (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _F, _F, _I, _F, _F, _P, _P, _P, _Z, _P]),
     "nsvd_tsgram_f64_workspace_bytes": (_Z, [_I, _I]),
     "nsvd_tsgram_f64": (_I, [_P, C.c_long, _P, C.c_long, _I, _I, _P, _P, _P, _Z, _P]),
     "nsvd_ritz_step_f64": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),

@@ -25,15 +25,13 @@
 // (they are rewritten between the two barriers of a chunk, when no wave can be reading them).
 #include <float.h>
 #include "nsvd_kernels.h"
+#include "pair_split.h"
 #include "tile_nt.h"
 
 namespace {
 
 constexpr int T = NSVD_TNT_T, KC = NSVD_TNT_KC, LDT = NSVD_TNT_LDT;
 constexpr int PAIR_MAX_D = 64;       // the model kernels' own input limit
-constexpr int PAIR_SLICE = 4;        // y chunks per slice (K^T f accumulator tiles per wave)
-constexpr int PAIR_MAX_GROUPS = 32;  // partial copies of either output
-constexpr int PAIR_FILL = 512;       // workgroups wanted: two per CU
 constexpr int PAIR_TILE = T * LDT;   // one 64 x 64 LDS tile with padded rows
 
 struct PairWs {
@@ -45,22 +43,6 @@ struct PairWs {
     int B1p, B2p, Dp, Lp, RG, CG;
     size_t bytes;
 };
-
-// RG row groups of x tiles, CG column groups of slices: split whichever side has more work per group until the grid
-// fills the chip or both sides are at one item per group / PAIR_MAX_GROUPS
-void pair_split(int xtiles, int slices, int ltiles, int* RG, int* CG) {
-    int rg = 1, cg = 1;
-    const int rmax = xtiles < PAIR_MAX_GROUPS ? xtiles : PAIR_MAX_GROUPS;
-    const int cmax = slices < PAIR_MAX_GROUPS ? slices : PAIR_MAX_GROUPS;
-    while ((long)ltiles * rg * cg < PAIR_FILL) {
-        const bool can_r = 2 * rg <= rmax, can_c = 2 * cg <= cmax;
-        if (!can_r && !can_c) break;
-        if (can_r && (!can_c || (long)xtiles * cg >= (long)slices * rg)) rg *= 2;
-        else cg *= 2;
-    }
-    *RG = rg;
-    *CG = cg;
-}
 
 PairWs carve(void* base, int B1, int B2, int D, int L) {
     PairWs w;

@@ -369,6 +369,25 @@ void dot_apply(const at::Tensor& x, const at::Tensor& y, const at::Tensor& f, in
              "nsvd_dot_apply");
 }
 
+// two-sided dot-product kernel operator (nsvd_dot_apply_pair): the same tensors as rbf_apply_pair
+void dot_apply_pair(const at::Tensor& x, const at::Tensor& y, const at::Tensor& g, const at::Tensor& f, int64_t kind,
+                    double gamma, double coef0, int64_t degree, double scale_g, double scale_f, at::Tensor out_x,
+                    at::Tensor out_y, at::Tensor ws) {
+    Dev dv;
+    TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && g.dim() == 2 && f.dim() == 2 && out_x.dim() == 2 && out_y.dim() == 2 &&
+                    y.size(1) == x.size(1) && g.size(0) == y.size(0) && f.size(0) == x.size(0) &&
+                    f.size(1) == g.size(1) && out_x.size(0) == x.size(0) && out_x.size(1) == g.size(1) &&
+                    out_y.size(0) == y.size(0) && out_y.size(1) == g.size(1),
+                "dot_apply_pair: x (B1, D), y (B2, D), g (B2, L), f (B1, L), out_x (B1, L), out_y (B2, L)");
+    float *xp = f32(dv, x, "x"), *yp = f32(dv, y, "y"), *gp = f32(dv, g, "g"), *fp = f32(dv, f, "f");
+    float *ox = f32(dv, out_x, "out_x"), *oy = f32(dv, out_y, "out_y");
+    void* wp = bytes(dv, ws, "ws");
+    check_rc(nsvd_dot_apply_pair(xp, (int)x.size(0), yp, (int)y.size(0), (int)x.size(1), gp, fp, (int)g.size(1), (int)kind,
+                                 (float)gamma, (float)coef0, (int)degree, (float)scale_g, (float)scale_f, ox, oy, wp,
+                                 (size_t)ws.numel() * ws.element_size(), dv.stream()),
+             "nsvd_dot_apply_pair");
+}
+
 // retrieval metrics (nsvd_retrieval_eval): zq / zg may be column windows (unit column stride); outputs as passed
 void retrieval_eval(const at::Tensor& zq, const at::Tensor& zg, const at::Tensor& q_cls, const at::Tensor& g_cls,
                     c10::optional<at::Tensor> n_relevant_items, int64_t metric, int64_t K,
@@ -441,7 +460,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                         "nsvd_rbf_apply_workspace_bytes", "nsvd_rbf_apply_pair",
                                         "nsvd_rbf_apply_pair_workspace_bytes", "nsvd_rbf_apply_pair_partition",
                                         "nsvd_dot_apply",
-                                        "nsvd_dot_apply_workspace_bytes", "nsvd_retrieval_eval",
+                                        "nsvd_dot_apply_workspace_bytes", "nsvd_dot_apply_pair",
+                                        "nsvd_dot_apply_pair_workspace_bytes", "nsvd_dot_apply_pair_partition",
+                                        "nsvd_retrieval_eval",
                                         "nsvd_retrieval_workspace_bytes", "nsvd_retrieval_max_gallery",
                                         "nsvd_retrieval_max_k", "nsvd_retrieval_max_d"};
     });
@@ -484,6 +505,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("dot_apply", &dot_apply);
     m.def("dot_apply_workspace_bytes",
           [](int B1, int B2, int D, int L) { return (int64_t)nsvd_dot_apply_workspace_bytes(B1, B2, D, L); });
+    m.def("dot_apply_pair", &dot_apply_pair);
+    m.def("dot_apply_pair_workspace_bytes",
+          [](int B1, int B2, int D, int L) { return (int64_t)nsvd_dot_apply_pair_workspace_bytes(B1, B2, D, L); });
+    m.def("dot_apply_pair_partition", [](int B1, int B2, int D, int L) {
+        int rg = 0, cs = 0;
+        check_rc(nsvd_dot_apply_pair_partition(B1, B2, D, L, &rg, &cs), "nsvd_dot_apply_pair_partition");
+        return std::vector<int>{rg, cs};
+    });
     m.def("retrieval_eval", &retrieval_eval);
     m.def("retrieval_workspace_bytes",
           [](int Nq, int Ng, int d, int K) { return (int64_t)nsvd_retrieval_workspace_bytes(Nq, Ng, d, K); });

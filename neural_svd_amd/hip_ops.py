@@ -943,6 +943,64 @@ def dot_apply(x: torch.Tensor, y: torch.Tensor, f: torch.Tensor, kind: int, gamm
     return out
 
 
+def dot_apply_pair_workspace(B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
+    n = _lib.load().nsvd_dot_apply_pair_workspace_bytes(int(B1), int(B2), int(D), int(L))
+    if n == 0:
+        raise NsvdError(f"nsvd_dot_apply_pair_workspace_bytes: unsupported shape B1={B1} B2={B2} D={D} L={L} "
+                        "(row counts and L >= 1, 1 <= D <= 64)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def dot_apply_pair_partition(B1: int, B2: int, D: int, L: int) -> Tuple[int, int]:
+    """(row groups, column slices) of an nsvd_dot_apply_pair call of that shape: the runs of x tiles and of y rows that
+    workgroups own = the partial copies of out_y and of out_x that the call reduces. Host only."""
+    rg, cs = C.c_int(0), C.c_int(0)
+    check(_lib.load().nsvd_dot_apply_pair_partition(int(B1), int(B2), int(D), int(L), C.byref(rg), C.byref(cs)),
+          "nsvd_dot_apply_pair_partition")
+    return rg.value, cs.value
+
+
+def dot_apply_pair(x: torch.Tensor, y: torch.Tensor, g: torch.Tensor, f: torch.Tensor, kind: int, gamma: float,
+                   coef0: float, degree: int, scale_g: float, scale_f: float, ws: Optional[torch.Tensor] = None,
+                   out_x: Optional[torch.Tensor] = None, out_y: Optional[torch.Tensor] = None):
+    """Both halves of a kernel SVD step in one pass (nsvd_dot_apply_pair), every x_i . y_j formed and mapped once:
+    out_x[i] = scale_g * sum_j k(x_i, y_j) g[j] ("K g", (B1, L)) and out_y[j] = scale_f * sum_i k(x_i, y_j) f[i]
+    ("K^T f", (B2, L)). kind, gamma, coef0, degree as dot_apply. x: (B1, D), y: (B2, D), g: (B2, L), f: (B1, L)
+    contiguous float32 on the GPU; x may be y and f may be g. Returns (out_x, out_y)."""
+    for t, n in ((x, "x"), (y, "y"), (g, "g"), (f, "f")):
+        if t.dim() != 2:
+            raise NsvdError(f"dot_apply_pair: {n} must be 2-D")
+    B1, D = x.shape
+    B2, L = g.shape
+    if tuple(y.shape) != (B2, D):
+        raise NsvdError("dot_apply_pair: y must be (len(g), D) with x's D")
+    if tuple(f.shape) != (B1, L):
+        raise NsvdError("dot_apply_pair: f must be (len(x), L) with g's L")
+    xp, yp, gp, fp = _ptr(x, "x"), _ptr(y, "y"), _ptr(g, "g"), _ptr(f, "f")
+    lib = _lib.load()
+    if out_x is None:
+        out_x = torch.empty((B1, L), dtype=torch.float32, device=g.device)
+    elif tuple(out_x.shape) != (B1, L):
+        raise NsvdError("dot_apply_pair: out_x must be (len(x), L)")
+    if out_y is None:
+        out_y = torch.empty((B2, L), dtype=torch.float32, device=g.device)
+    elif tuple(out_y.shape) != (B2, L):
+        raise NsvdError("dot_apply_pair: out_y must be (len(y), L)")
+    ox, oy = _ptr(out_x, "out_x"), _ptr(out_y, "out_y")
+    if ws is None:
+        # (an unsupported shape has no workspace: the entry point itself refuses it, with its own code)
+        ws = torch.empty(max(lib.nsvd_dot_apply_pair_workspace_bytes(B1, B2, D, L), 256), dtype=torch.uint8,
+                         device=g.device)
+    if torch_binding() is not None:
+        _TB.dot_apply_pair(x, y, g, f, int(kind), float(gamma), float(coef0), int(degree), float(scale_g),
+                           float(scale_f), out_x, out_y, ws)
+        return out_x, out_y
+    rc = lib.nsvd_dot_apply_pair(xp, B1, yp, B2, D, gp, fp, L, int(kind), float(gamma), float(coef0), int(degree),
+                                 float(scale_g), float(scale_f), ox, oy, ws.data_ptr(), ws.numel(), _stream())
+    check(rc, "nsvd_dot_apply_pair")
+    return out_x, out_y
+
+
 # ---- the dense side of the Nystrom baseline (csrc/nystrom.hip; the loop is neural_svd_amd/nystrom.py) ---------------
 RITZ_BAD_PIVOT, RITZ_SWEEP_CAP = 1, 2  # NSVD_RITZ_* (include/nsvd.h)
 NYSTROM_MAX_BLOCK = 80
@@ -1526,7 +1584,7 @@ def cdk_step(desc: "_lib.CdkStepDesc", x: torch.Tensor, y: torch.Tensor, towers:
 for _name in ("fourier_features", "operator_forward", "operator_features", "operator_sample_features",
               "operator_sample_features_dev", "rmsprop_ema_step_dev", "opt_step_dev",
               "operator_backward", "model_forward", "model_backward", "evd_moments", "evd_loss_grad", "evd_loss_fused",
-              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_opt_step", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "rbf_apply", "dot_apply", "tsgram_f64", "ritz_step_f64", "ts_rotate", "cdk_loss_forward",
+              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_opt_step", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "rbf_apply", "dot_apply", "dot_apply_pair", "tsgram_f64", "ritz_step_f64", "ts_rotate", "cdk_loss_forward",
               "cdk_loss_backward", "rmsprop_ema_step", "opt_step", "spectrum_accumulate", "row_normalize",
               "row_normalize_backward", "tower_forward", "tower_backward", "cdk_step", "to_bf16", "gemm_bf16"):
     globals()[_name] = _on_tensor_device(globals()[_name])

@@ -224,7 +224,8 @@ class DotKernelOperator(MatrixFreeKernelOperator):
     kernel, the NNGP kernel of one ReLU layer (gamma, coef0, degree unused). Training batches are sigma * randn(B, dim);
     the same contract and callers as RadialKernelOperator. Polynomial kind: gamma <= 0 or coef0 < 0 are refused (not PSD
     in general).
-    A polynomial kernel has FINITE rank C(dim + degree, degree) (see nystrom.Nystrom's note on ``oversample``)."""
+    A polynomial kernel has FINITE rank C(dim + degree, degree) (see nystrom.Nystrom's note on ``oversample``).
+    The two-sided product of a kernel SVD step is one nsvd_dot_apply_pair call (``apply_pair_raw``)."""
 
     def __init__(self, kind: int, dim: int, *, gamma: float = 1.0, coef0: float = 1.0, degree: int = 2,
                  sigma: float = 1.0, device="cuda:0"):
@@ -248,6 +249,20 @@ class DotKernelOperator(MatrixFreeKernelOperator):
 
     def apply_raw(self, x, y, f, scale, ws=None, out=None) -> torch.Tensor:
         return H.dot_apply(x, y, f, self.kind, self.gamma, self.coef0, self.degree, scale, ws=ws, out=out)
+
+    def workspace_pair(self, B1: int, B2: int, L: int, device=None) -> torch.Tensor:
+        """nsvd_dot_apply_pair_workspace_bytes. With B1p, B2p, Lp = B1, B2, L rounded up to 64, Dp = dim rounded up to 8
+        and (RG, CG) = hip_ops.dot_apply_pair_partition(B1, B2, dim, L), both at most 32:
+        4 * (B1p Dp + B1p + B2p Dp + B2p + Lp (B2p + B1p) + CG B1p Lp + RG B2p Lp) bytes, each term rounded up to 256
+        (padded x, |x|, padded y, |y|, g^T, f^T and the partial copies, which dominate: 100 MiB at B1 = B2 = 8192,
+        L = 64 with RG, CG = 32, 16)."""
+        return H.dot_apply_pair_workspace(B1, B2, self.dim, L, self.device if device is None else device)
+
+    def apply_pair_raw(self, x, y, g, f, scale_g, scale_f, ws=None, out_x=None, out_y=None):
+        """one nsvd_dot_apply_pair call at every dim and kind: every x_i . y_j formed and mapped once for both products
+        (the two-call route stays reachable as MatrixFreeKernelOperator.apply_pair_raw(op, ...))"""
+        return H.dot_apply_pair(x, y, g, f, self.kind, self.gamma, self.coef0, self.degree, scale_g, scale_f, ws=ws,
+                                out_x=out_x, out_y=out_y)
 
 
 def _gaussian_kernel_constants(sigma: float, ell: float):
@@ -335,6 +350,57 @@ def gaussian_cross_modes(sigma_x: float, sigma_y: float, ell: float, dim: int, n
 
 def gaussian_cross_singular_values(sigma_x: float, sigma_y: float, ell: float, dim: int, n: int) -> np.ndarray:
     return gaussian_cross_modes(sigma_x, sigma_y, ell, dim, n)[0]
+
+
+def _multi_indices_up_to(dim: int, degree: int) -> np.ndarray:
+    """every multi-index of `dim` entries with |alpha| <= degree, by total degree"""
+    n = math.comb(dim + degree, degree)
+    return _mode_indices(dim, n)
+
+
+def polynomial_cross_singular_values(sigma_x: float, sigma_y: float, gamma: float, coef0: float, degree: int, dim: int,
+                                     n: int) -> np.ndarray:
+    """The first `n` singular values (descending, float64; zeros beyond the rank) of k = (gamma x.y + coef0)^degree as
+    an operator from L2(N(0, sigma_y^2 I_dim)) to L2(N(0, sigma_x^2 I_dim)), (Kg)(x) = E_y[k(x, y) g(y)]. The kernel
+    has finite rank: k = sum over |alpha| <= degree of w_alpha x^alpha y^alpha with
+    w_alpha = C(degree, |alpha|) coef0^(degree - |alpha|) gamma^|alpha| |alpha|! / alpha! (binomial, then multinomial
+    theorem), so K = Phi_x diag(w) Phi_y^* on the monomials. With the moment matrices
+    M_x[alpha, beta] = E[x^(alpha + beta)] = prod_d E[x_d^(alpha_d + beta_d)] (E[t^a] = sigma^a (a - 1)!! for even a, 0
+    for odd a) and M_y likewise, M = R^T R, the non-zero singular values of K are those of R_x diag(w) R_y^T.
+    Exact up to float64 rounding; numpy only."""
+    degree, dim, n = int(degree), int(dim), int(n)
+    if degree < 1 or dim < 1 or n < 1:
+        raise ValueError("polynomial_cross_singular_values: degree, dim and n must be positive")
+    if not (sigma_x > 0 and sigma_y > 0):
+        raise ValueError("polynomial_cross_singular_values: sigma_x and sigma_y must be positive")
+    idx = _multi_indices_up_to(dim, degree)
+    tot = idx.sum(axis=1)
+    w = np.array([math.comb(degree, int(t)) * float(coef0) ** (degree - int(t)) * float(gamma) ** int(t) *
+                  math.factorial(int(t)) / np.prod([math.factorial(int(a)) for a in row])
+                  for row, t in zip(idx, tot)], dtype=np.float64)
+
+    def moment(sigma, a):  # E[t^a], t ~ N(0, sigma^2)
+        if a % 2:
+            return 0.0
+        return float(sigma) ** a * float(np.prod(np.arange(a - 1, 0, -2, dtype=np.float64)))
+
+    def root(sigma):
+        """R with M = R^T R, from the eigendecomposition (M is PSD and badly scaled: eigh keeps its small modes)"""
+        m1 = np.array([moment(sigma, a) for a in range(2 * degree + 1)], dtype=np.float64)
+        s = idx[:, None, :] + idx[None, :, :]
+        M = np.prod(m1[s], axis=2)
+        # scale to a unit diagonal first: the monomials' norms span sigma^(2 degree) (2 degree - 1)!!
+        d = np.sqrt(np.diag(M))
+        lam, V = np.linalg.eigh(M / d[:, None] / d[None, :])
+        return (np.sqrt(np.clip(lam, 0.0, None))[:, None] * V.T) * d[None, :]
+    A = root(sigma_x) @ (w[:, None] * root(sigma_y).T)
+    sv = np.linalg.svd(A, compute_uv=False)
+    out = np.zeros(n, dtype=np.float64)
+    m = min(n, len(sv))
+    out[:m] = sv[:m]
+    # values that are rounding noise of a rank-deficient product (coef0 = 0 drops every |alpha| < degree) are zeros
+    out[out < 64 * np.finfo(np.float64).eps * max(out[0], np.finfo(np.float64).tiny)] = 0.0
+    return out
 
 
 @torch.no_grad()

@@ -3,7 +3,8 @@
 The SVD form of the nested low-rank loss (``NestedLoRALossFunctionSVD(f, Tg, g, Tadjf)``, reference
 methods/nestedlora.py:114-164, which has no caller there) needs ``Tg = K g`` together with ``Tadjf = K^T f``; a
 ``MatrixFreeKernelOperator`` produces the two with ``apply_pair_raw`` (``RadialKernelOperator``: one
-``nsvd_rbf_apply_pair`` call, every kernel value evaluated once; any other: two ``apply_raw`` calls).
+``nsvd_rbf_apply_pair`` call, ``DotKernelOperator``: one ``nsvd_dot_apply_pair`` call, every kernel value evaluated
+once; the base class: two ``apply_raw`` calls).
 
 - ``PairedFunctions(f_model, g_model)``: the model of a NestedLoRA method that learns a pair;
 - ``NestedLoRA.compute_loss_kernel_svd(svd_op, x, y)`` (defined here, bound in nested_lowrank.py): the class path,
@@ -11,7 +12,8 @@ methods/nestedlora.py:114-164, which has no caller there) needs ``Tg = K g`` tog
 - ``KernelSvdTrainer``: the same step as a fixed sequence of C-ABI calls on two flat parameter buffers.
 
 For the Gaussian kernel between two Gaussian measures the singular values are known in closed form
-(``kernel_ops.gaussian_cross_singular_values``); ``kernel_ops.kernel_singular_values`` evaluates the quotients of any
+(``kernel_ops.gaussian_cross_singular_values``), and so are those of the polynomial kernel
+(``kernel_ops.polynomial_cross_singular_values``); ``kernel_ops.kernel_singular_values`` evaluates the quotients of any
 pair of function families on samples."""
 from __future__ import annotations
 

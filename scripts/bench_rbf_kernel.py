@@ -30,7 +30,15 @@ is BOTH contractions, 2 B^2 L + 2 B^2 Dp with Dp = D rounded up to 8. Writes pro
 times the two-sided call (nsvd_rbf_apply_pair: K g and K^T f, every kernel value evaluated once) against TWO
 nsvd_rbf_apply calls with swapped arguments (what the interface had before), both kinds, at each D of --pair-d, in ONE
 alternating loop with the same window scheme; x ~ N(0, I), y ~ N(0, I / 4), ell = sqrt(D). The MFMA work either route
-executes is 4 B^2 L. Writes profiles/rbf_apply_pair_bench.json."""
+executes is 4 B^2 L. Writes profiles/rbf_apply_pair_bench.json.
+
+    python scripts/bench_rbf_kernel.py --dot --pair [--b 8192 --pair-d 2,16,64 --l 64 --degree 2]
+
+does the same for the dot-product kinds: nsvd_dot_apply_pair (every x_i . y_j formed and mapped once) against TWO
+nsvd_dot_apply calls with swapped arguments, polynomial (gamma = 1 / D, coef0 = 1, --degree) and arc-cosine, at each D
+of --pair-d. Per wave and 64-row chunk the two calls issue 2 (Dp / 2 + 32) MFMAs and the fused call Dp / 2 + 64
+(Dp = D rounded up to 8); the record carries that ratio beside the measured one, and the spread (min, max) of the 30
+windows beside each median. Writes profiles/dot_apply_pair_bench.json."""
 import argparse
 import json
 import os
@@ -185,6 +193,54 @@ def bench_pair(a, dev):
     json.dump(rec, open(out_path, "w"), indent=1)
 
 
+def bench_dot_pair(a, dev):
+    B, L = a.b, a.l
+    scale = 1.0 / B
+    recs = []
+    for D in [int(v) for v in a.pair_d.split(",")]:
+        gen = torch.Generator(device=dev).manual_seed(0)
+        x = torch.randn(B, D, device=dev, generator=gen)
+        y = 0.5 * torch.randn(B, D, device=dev, generator=gen)
+        g = torch.randn(B, L, device=dev, generator=gen)
+        f = torch.randn(B, L, device=dev, generator=gen)
+        gamma, coef0, degree = 1.0 / D, 1.0, a.degree
+        pws = H.dot_apply_pair_workspace(B, B, D, L, dev)
+        dws = H.dot_apply_workspace(B, B, D, L, dev)
+        px, py, rx, ry = (torch.empty(B, L, device=dev) for _ in range(4))
+        Dp = (D + 7) // 8 * 8
+        model = 2.0 * (Dp / 2 + 32) / (Dp / 2 + 64)
+        for name, kind in (("polynomial", H.DOT_POLYNOMIAL), ("arccos1", H.DOT_ARCCOS1)):
+            def pair():
+                H.dot_apply_pair(x, y, g, f, kind, gamma, coef0, degree, scale, scale, ws=pws, out_x=px, out_y=py)
+
+            def two_calls():
+                H.dot_apply(x, y, g, kind, gamma, coef0, degree, scale, ws=dws, out=rx)
+                H.dot_apply(y, x, f, kind, gamma, coef0, degree, scale, ws=dws, out=ry)
+
+            pair()
+            two_calls()
+            agree = max(float((px - rx).abs().max() / rx.abs().max()), float((py - ry).abs().max() / ry.abs().max()))
+            t_p, t_2 = median_ms_alternating([pair, two_calls], a.reps, a.inner)
+            k_p = main_kernel_ms(pair)
+            flop_pair = 4.0 * B * B * L + 2.0 * B * B * Dp
+            speedup = t_2["median_ms"] / t_p["median_ms"]
+            recs.append(dict(B1=B, B2=B, D=D, Dp=Dp, L=L, kind=name, degree=degree, gamma=gamma, coef0=coef0,
+                             partition=list(H.dot_apply_pair_partition(B, B, D, L)),
+                             workspace_mib=pws.numel() / 2 ** 20, dot_apply_pair=t_p, two_dot_apply_calls=t_2,
+                             pair_main_kernel_ms=k_p, speedup_over_two_calls=speedup,
+                             mfma_instruction_count_model_ratio=model, model_held=bool(speedup >= model),
+                             gflop_mfma_executed_pair=flop_pair / 1e9,
+                             mfma_peak_fraction_executed_pair_whole_call=flop_pair / MFMA_F32_PEAK / (t_p["median_ms"] * 1e-3),
+                             mfma_peak_fraction_executed_pair_main_kernel=flop_pair / MFMA_F32_PEAK / (k_p * 1e-3),
+                             max_normalised_difference_between_routes=agree))
+            print(json.dumps(recs[-1]))
+    rec = dict(reps=a.reps, calls_per_window=a.inner, mfma_f32_peak_flops=MFMA_F32_PEAK,
+               device=torch.cuda.get_device_name(0), shapes=recs)
+    out_path = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "dot_apply_pair_bench.json")
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    json.dump(rec, open(out_path, "w"), indent=1)
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "rbf_apply_bench.json")
 
 
@@ -193,7 +249,8 @@ def main():
     ap.add_argument("--dot", action="store_true", help="time the dot-product kinds (nsvd_dot_apply) instead")
     ap.add_argument("--dot-d", default="16,64", help="--dot: the input dimensions, comma separated")
     ap.add_argument("--degree", type=int, default=2, help="--dot: the polynomial kind's degree")
-    ap.add_argument("--pair", action="store_true", help="time nsvd_rbf_apply_pair against two nsvd_rbf_apply calls")
+    ap.add_argument("--pair", action="store_true", help="time nsvd_rbf_apply_pair against two nsvd_rbf_apply calls (with --dot: nsvd_dot_apply_pair against two "
+                    "nsvd_dot_apply calls)")
     ap.add_argument("--pair-d", default="2,16,64", help="--pair: the input dimensions, comma separated")
     ap.add_argument("--b", type=int, default=8192)
     ap.add_argument("--d", type=int, default=16)
@@ -207,6 +264,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_rbf_kernel.py needs a GPU: a CPU run measures nothing")
     dev = "cuda:0"
+    if a.dot and a.pair:
+        return bench_dot_pair(a, dev)
     if a.dot:
         return bench_dot(a, dev)
     if a.pair:

@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
-"""Learn the singular functions of a cross-domain Gaussian kernel with two models (neural_svd_amd.KernelSvdTrainer).
+"""Learn the singular functions of a cross-domain kernel with two models (neural_svd_amd.KernelSvdTrainer).
 
     python scripts/train_kernel_svd.py [--steps 20000 --dim 2 --sigma-x 1 --sigma-y 0.5 --ell 1.5 --L 10 --B 8192]
+    python scripts/train_kernel_svd.py --kind polynomial --dim 3 --degree 2 --L 10 [--gamma 1 --coef0 1]
+    python scripts/train_kernel_svd.py --kind arccos1 --dim 3
+
+--kind gaussian (the default, described below) | exponential (--ell) | polynomial (--gamma --coef0 --degree:
+k = (gamma x.y + coef0)^degree) | arccos1 (the order-1 arc-cosine kernel). The radial kinds run on nsvd_rbf_apply_pair,
+the dot-product kinds on nsvd_dot_apply_pair; the two-call comparison trainer uses two nsvd_rbf_apply / nsvd_dot_apply
+calls. The truth column comes from a closed form where one exists - gaussian: gaussian_cross_singular_values,
+polynomial: polynomial_cross_singular_values (finite rank: zeros beyond it, where the relative error is not defined) -
+and the other kinds print the learned quotients only. The default output file is profiles/kernel_svd_train.json for the
+Gaussian kind and profiles/kernel_svd_train_<kind>.json for the others.
 
 k(x, y) = exp(-|x - y|^2 / (2 ell^2)) as an operator from L2(N(0, sigma_y^2 I)) to L2(N(0, sigma_x^2 I)): x and y are
 drawn fresh every step from the two measures, f takes x and g takes y, and one step is two model evaluations, one
@@ -26,15 +36,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from neural_svd_amd import hip_ops as H  # noqa: E402
-from neural_svd_amd.kernel_ops import (MatrixFreeKernelOperator, RadialKernelOperator,  # noqa: E402
-                                       gaussian_cross_singular_values, kernel_singular_values)
+from neural_svd_amd.kernel_ops import (DotKernelOperator, MatrixFreeKernelOperator, RadialKernelOperator,  # noqa: E402
+                                       gaussian_cross_singular_values, kernel_singular_values,
+                                       polynomial_cross_singular_values)
 from neural_svd_amd.kernel_svd import KernelSvdTrainer  # noqa: E402
 
 
-class TwoCallRadialOperator(RadialKernelOperator):
-    """the same operator with the base class's two-sided product: two nsvd_rbf_apply calls"""
-    workspace_pair = MatrixFreeKernelOperator.workspace_pair
-    apply_pair_raw = MatrixFreeKernelOperator.apply_pair_raw
+def two_call(op_class):
+    """the same operator class with the base class's two-sided product: two apply_raw calls with swapped arguments"""
+    return type("TwoCall" + op_class.__name__, (op_class,),
+                dict(workspace_pair=MatrixFreeKernelOperator.workspace_pair,
+                     apply_pair_raw=MatrixFreeKernelOperator.apply_pair_raw))
 
 
 def timed_steps(trainer, n):
@@ -55,7 +67,11 @@ def main():
     ap.add_argument("--dim", type=int, default=2)
     ap.add_argument("--sigma-x", type=float, default=1.0)
     ap.add_argument("--sigma-y", type=float, default=0.5)
-    ap.add_argument("--ell", type=float, default=1.5)
+    ap.add_argument("--kind", default="gaussian", choices=("gaussian", "exponential", "polynomial", "arccos1"))
+    ap.add_argument("--ell", type=float, default=1.5, help="radial kinds: the length scale")
+    ap.add_argument("--gamma", type=float, default=1.0, help="polynomial kind")
+    ap.add_argument("--coef0", type=float, default=1.0, help="polynomial kind")
+    ap.add_argument("--degree", type=int, default=2, help="polynomial kind")
     ap.add_argument("--L", type=int, default=10)
     ap.add_argument("--B", type=int, default=8192)
     ap.add_argument("--m", type=int, default=64)
@@ -63,41 +79,70 @@ def main():
     ap.add_argument("--fourier-scale", type=float, default=0.3)
     ap.add_argument("--n-eval", type=int, default=16384)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kernel_svd_train.json"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("train_kernel_svd.py needs a GPU (neural_svd_amd has no CPU path)")
     dev = "cuda:0"
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles",
+                             "kernel_svd_train.json" if a.kind == "gaussian" else f"kernel_svd_train_{a.kind}.json")
+    radial = a.kind in ("gaussian", "exponential")
+    base_class = RadialKernelOperator if radial else DotKernelOperator
+
+    def make_op(op_class):
+        if radial:
+            return op_class(H.RBF_GAUSSIAN if a.kind == "gaussian" else H.RBF_EXPONENTIAL, a.ell, a.dim, a.sigma_x, dev)
+        return op_class(H.DOT_POLYNOMIAL if a.kind == "polynomial" else H.DOT_ARCCOS1, a.dim, gamma=a.gamma,
+                        coef0=a.coef0, degree=a.degree, sigma=a.sigma_x, device=dev)
 
     def trainer(op_class, steps):
-        op = op_class(H.RBF_GAUSSIAN, a.ell, a.dim, a.sigma_x, dev)
+        op = make_op(op_class)
         return op, KernelSvdTrainer(op, L=a.L, m=a.m, hidden=(128, 128), batch_size=a.B, sigma_x=a.sigma_x,
                                     sigma_y=a.sigma_y, sequential=True, lr=a.lr, rmsprop_decay=0.999, rmsprop_eps=1e-10,
                                     num_iters=steps, fourier_scale=a.fourier_scale, seed=a.seed, index_seed=a.seed + 1)
-    op, kt = trainer(RadialKernelOperator, a.steps)
+    op, kt = trainer(base_class, a.steps)
     dt, loss = timed_steps(kt, a.steps)
-    _, kt2 = trainer(TwoCallRadialOperator, a.base_steps)
+    _, kt2 = trainer(two_call(base_class), a.base_steps)
     dt2, _ = timed_steps(kt2, a.base_steps)
     gen = torch.Generator(device=dev).manual_seed(a.seed + 1000)
     x_eval = a.sigma_x * torch.randn(a.n_eval, a.dim, device=dev, generator=gen)
     y_eval = a.sigma_y * torch.randn(a.n_eval, a.dim, device=dev, generator=gen)
     got = kernel_singular_values(op, kt.f, kt.g, x_eval, y_eval)
-    s = gaussian_cross_singular_values(a.sigma_x, a.sigma_y, a.ell, a.dim, a.L)
-    rel = np.abs(got["svals"] - s) / s
-    rec = dict(kind="gaussian", dim=a.dim, sigma_x=a.sigma_x, sigma_y=a.sigma_y, ell=a.ell, L=a.L, B=a.B, steps=a.steps,
+    if a.kind == "gaussian":
+        s = gaussian_cross_singular_values(a.sigma_x, a.sigma_y, a.ell, a.dim, a.L)
+    elif a.kind == "polynomial":
+        s = polynomial_cross_singular_values(a.sigma_x, a.sigma_y, a.gamma, a.coef0, a.degree, a.dim, a.L)
+    else:
+        s = None  # no closed form: quotients only
+    rec = dict(kind=a.kind, dim=a.dim, sigma_x=a.sigma_x, sigma_y=a.sigma_y, L=a.L, B=a.B, steps=a.steps,
                lr=a.lr, fourier_scale=a.fourier_scale, seconds=round(dt, 2),
                steps_per_s=round((a.steps - 10) / dt, 1),
                two_call_base_path_steps=a.base_steps, two_call_base_path_steps_per_s=round((a.base_steps - 10) / dt2, 1),
                loss=[float(v) for v in loss.cpu()], singular_learned=[float(v) for v in got["svals"]],
-               singular_closed_form=[float(v) for v in s], rel_err=[float(v) for v in rel],
-               rel_err_leading_three=[float(v) for v in rel[:3]], rel_err_mean=float(rel.mean()),
-               rel_err_max=float(rel.max()), norms_f=[float(v) for v in got["norms_f"]],
-               norms_g=[float(v) for v in got["norms_g"]], n_eval=a.n_eval, device=torch.cuda.get_device_name(0))
-    print(f"steps/s {rec['steps_per_s']} (two nsvd_rbf_apply calls in place of nsvd_rbf_apply_pair: "
+               norms_f=[float(v) for v in got["norms_f"]], norms_g=[float(v) for v in got["norms_g"]],
+               n_eval=a.n_eval, device=torch.cuda.get_device_name(0))
+    if radial:
+        rec.update(ell=a.ell)
+    elif a.kind == "polynomial":
+        rec.update(gamma=a.gamma, coef0=a.coef0, degree=a.degree)
+    names = ("nsvd_rbf_apply", "nsvd_rbf_apply_pair") if radial else ("nsvd_dot_apply", "nsvd_dot_apply_pair")
+    print(f"steps/s {rec['steps_per_s']} (two {names[0]} calls in place of {names[1]}: "
           f"{rec['two_call_base_path_steps_per_s']})")
-    print("  k           learned       closed form   rel err")
-    for k in range(a.L):
-        print(f"{k:3d}  {got['svals'][k]:16.8e}  {s[k]:16.8e}  {rel[k]:.2e}")
+    if s is not None:
+        nz = s > 0  # (a polynomial kernel has finite rank: no relative error beyond it)
+        rel = np.full(a.L, np.nan)
+        rel[nz] = np.abs(got["svals"][nz] - s[nz]) / s[nz]
+        rec.update(singular_closed_form=[float(v) for v in s], rel_err=[None if np.isnan(v) else float(v) for v in rel],
+                   rel_err_leading_three=[float(v) for v in rel[:3][nz[:3]]], rel_err_mean=float(rel[nz].mean()),
+                   rel_err_max=float(rel[nz].max()), rank_within_L=int(nz.sum()))
+        print("  k           learned       closed form   rel err")
+        for k in range(a.L):
+            print(f"{k:3d}  {got['svals'][k]:16.8e}  {s[k]:16.8e}  " + (f"{rel[k]:.2e}" if nz[k] else "-"))
+    else:
+        print("  k           learned   (no closed form for this kind)")
+        for k in range(a.L):
+            print(f"{k:3d}  {got['svals'][k]:16.8e}")
     print(json.dumps(rec))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     json.dump(rec, open(a.out, "w"), indent=1)
