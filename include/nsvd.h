@@ -97,6 +97,12 @@ extern "C" {
                                   * accumulated in float32 (f and Tf as close to float64 as the fp32 MFMA's). The
                                   * backward is NSVD_PATH_FUSED's; a fused training step on this path also leaves
                                   * the planes of the updated weights for the next forward (nsvd_step_emits_planes) */
+#define NSVD_PATH_GENERIC_EXACT 4 /* opt-in, never picked by AUTO: the exact Laplacian (prob->eps <= 0) on the generic
+                                   * kernels - any model validate() accepts, 1 <= D <= 12, every potential, mask and
+                                   * importance of the Schroedinger kind. The layers carry D + 2 forward-mode jet streams
+                                   * per sample (value, D first derivatives, Laplacian) where the stencil carries 2 D + 1.
+                                   * eps > 0 on this path is NSVD_EUNSUPPORTED, as is the Fokker-Planck kind, NeuralEF's
+                                   * forward and head-parallel sharding (l_offset / L_total) */
 
 /* Shape of WaveFunctions(ParallelMLP(GaussianFourierFeatureTransform)):
  * examples/operator/pde/__init__.py:19-55, examples/models/mlp.py:167-221, examples/utils.py:90-143 */
@@ -130,7 +136,8 @@ typedef struct nsvd_problem {
     float charge_or_k;               /* Z (hydrogen) or k (oscillator)                 */
     float scale_kinetic;             /* problems.py:26 (1.0)                           */
     float eps;                       /* --laplacian_eps: > 0 central differences; <= 0 the exact Laplacian
-                                      * (diff_ops.py:7,54-61) by forward-mode jets, MFMA path only */
+                                      * (diff_ops.py:7,54-61) by forward-mode jets: the MFMA path (D <= 3), or
+                                      * NSVD_PATH_GENERIC_EXACT on explicit request (any model, D <= 12) */
     float op_scale;                  /* --operator_scale                               */
     float op_shift;                  /* --operator_shift                               */
     float sigma;                     /* --sampling_scale of the Gaussian sampler       */
@@ -169,8 +176,11 @@ const char* nsvd_path_name(const nsvd_model_desc* desc, int B, int path);
  * cosine / sin-of-cos problem whose pot_table is NULL or not D long, and for a NSVD_POT_MOLECULE problem with
  * n_nuclei < 1, D not a multiple of n_particles, d = D / n_particles not 2 or 3, pot_table_len != n_nuclei (d + 1), a
  * NULL table, or inside the Fokker-Planck kind.
- * The exact-Laplacian mode (prob->eps <= 0) exists on the MFMA path only (D <= 3, as the
- * stencil mode: its 3-D form runs one direction per workgroup); "unsupported" when it has no path; "invalid" for a
+ * The exact-Laplacian mode (prob->eps <= 0) exists on the MFMA path (D <= 3, as the
+ * stencil mode: its 3-D form runs one direction per workgroup) and, on explicit request, on the generic kernels:
+ * NSVD_PATH_GENERIC_EXACT answers "generic_exact" for eps <= 0 with the Schroedinger kind at any 1 <= D <= 12 and
+ * "unsupported" for eps > 0. Every other path value answers as before: "unsupported" when the mode has no path there
+ * (NSVD_PATH_AUTO never picks the generic jets); "invalid" for a
  * potential, importance, operator kind or box mask value this library does not know (and for NSVD_POT_SIN_OF_COS
  * outside the Fokker-Planck kind). Every path implements every box mask, potential and importance; entry points that do
  * not (NeuralEF) return NSVD_EUNSUPPORTED. The Fokker-Planck kind is "unsupported" with eps <= 0, Gaussian importance,
@@ -186,6 +196,18 @@ size_t nsvd_workspace_bytes(const nsvd_model_desc* desc, int B);
  * phiT: (2m, ldr) feature-major, sample-contiguous; ldr >= E*B. nstencil = 1 (centre only) or E. */
 int nsvd_fourier_features(const float* x, const float* fourier_B, float* phiT, int B, int D, int m,
                           float eps, int nstencil, int ldr, void* stream);
+
+/* NEW SYMBOLS ONLY (ABI stays 6). The two kernels of NSVD_PATH_GENERIC_EXACT that are its own (the layers are the generic
+ * GEMM's), callable alone. Jet layout: D + 2 column blocks of B samples - block 0 the value, block 1 + d the derivative
+ * along x_d, block D + 1 the Laplacian (VectorizedLaplacian.exact_laplacian, diff_ops.py:54-61, in forward mode).
+ * nsvd_fourier_features_jets: phiT (2m, ldr) feature-major, ldr >= (D + 2) B: for phi = [sin | cos](x . B_j) the
+ * derivative along d is [cos | -sin](x . B_j) B_dj and the Laplacian -|B_j|^2 [sin | cos](x . B_j). Any D >= 1.
+ * nsvd_softplus_jets_inplace: z (rows, (D + 2) B), the jet of a hidden layer's pre-activations, becomes the jet of its
+ * activations: with s = sigmoid(z0), a = softplus(z0), t_d <- s t_d, l <- s l + s (1 - s) sum_d t_d^2 (the sum over the
+ * incoming t_d; torch's softplus threshold 20: s = 1, s (1 - s) = 0 above it). */
+int nsvd_fourier_features_jets(const float* x, const float* fourier_B, float* phiT, int B, int D, int m, int ldr,
+                               void* stream);
+int nsvd_softplus_jets_inplace(float* z, long long rows, int B, int D, void* stream);
 
 /* bit for nsvd_operator_forward's save_for_backward argument: the Fourier features of x are already in
  * the workspace (put there by nsvd_operator_features, typically on another stream while the previous

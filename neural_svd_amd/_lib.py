@@ -22,6 +22,7 @@ BOX_NONE, BOX_SQRT, BOX_EXP = 0, 1, 2
 IMP_NONE, IMP_GAUSSIAN, IMP_UNIFORM = 0, 1, 2
 MASK_CUSTOM, MASK_SEQUENTIAL, MASK_JOINT = 0, 1, 2
 PATH_AUTO, PATH_GENERIC, PATH_FUSED, PATH_FUSED_BF16X3 = 0, 1, 2, 3
+PATH_GENERIC_EXACT = 4  # opt-in: the exact Laplacian (eps <= 0) on the generic kernels, never picked by PATH_AUTO
 NORMALIZE_L2_BALL, NORMALIZE_L2_SPHERE = 0, 1
 OPT_RMSPROP, OPT_SGD, OPT_ADAM = 0, 1, 2
 FEATURES_READY = 0x100
@@ -123,6 +124,8 @@ SIGNATURES = {
     "nsvd_path_name_for": (C.c_char_p, [C.POINTER(ModelDesc), C.POINTER(Problem), _I, _I]),
     "nsvd_workspace_bytes": (_Z, [C.POINTER(ModelDesc), _I]),
     "nsvd_fourier_features": (_I, [_P, _P, _P, _I, _I, _I, _F, _I, _I, _P]),
+    "nsvd_fourier_features_jets": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "nsvd_softplus_jets_inplace": (_I, [_P, C.c_longlong, _I, _I, _P]),
     "nsvd_operator_forward": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem), _P, _I, _P, _P,
                                    _P, _Z, _I, _I, _P]),
     "nsvd_operator_features": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem), _P, _I, _P, _Z, _I,

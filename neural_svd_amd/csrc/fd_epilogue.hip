@@ -99,6 +99,88 @@ __global__ void __launch_bounds__(256) fd_epilogue_nd_kernel(const float* __rest
     }
 }
 
+// ---- exact-Laplacian mode on the generic jets (NSVD_PATH_GENERIC_EXACT): `base` is (L, ldr) with row block 0 the head's
+// value, blocks 1 .. D its derivatives along each axis, block D + 1 its Laplacian -------------------------------------
+// D <= NSVD_FD_MAXD: one thread per (sample, head) gathers the jet and calls nsvd_fd_exact (the fused kernels' product rule)
+__global__ void __launch_bounds__(256) fd_exact_kernel(const float* __restrict__ base, int ldr,
+                                                       const float* __restrict__ x, const float* __restrict__ scales,
+                                                       nsvd_problem prob, float log_norm, int B, int D, int L,
+                                                       float* __restrict__ f, float* __restrict__ Tf,
+                                                       float* __restrict__ jac, float* __restrict__ dsc, NsvdBox box) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= B * L) return;
+    const int b = idx / L, l = idx - b * L;
+    const float* bcol = base + (size_t)l * ldr + b;
+    float xc[NSVD_FD_MAXD], db[NSVD_FD_MAXD];
+#pragma unroll
+    for (int d = 0; d < NSVD_FD_MAXD; ++d) {
+        xc[d] = d < D ? x[(size_t)b * D + d] : 0.f;
+        db[d] = d < D ? bcol[(size_t)(1 + d) * B] : 0.f;
+    }
+    const NsvdFdOut o = nsvd_fd_exact(bcol[0], db, bcol[(size_t)(D + 1) * B], xc, D, scales != nullptr,
+                                      scales ? scales[l] : 0.f, prob, log_norm, box);
+    f[idx] = o.f;
+    Tf[idx] = o.Tf;
+    if (jac) jac[idx] = o.jac;
+    if (dsc) dsc[idx] = o.dsc;
+}
+
+// 5 <= D <= NSVD_MAX_D: the direction-loop form (fd_math.h: nsvd_fd_exact_nd), built like fd_epilogue_nd_kernel - ND_ROWS
+// samples per workgroup, the lane is the sample, wave g takes the heads l = g (mod 4). Wave 0 fills the per-direction
+// table of its 64 rows in LDS (x_d and the box factors by prefix / suffix products: sequential in d, once per row) and
+// the two row sums the heads share; the outputs leave through the LDS tile as runs of ND_HEADS floats per row.
+template <bool TRIG>
+__global__ void __launch_bounds__(256) fd_exact_nd_kernel(const float* __restrict__ base, int ldr,
+                                                          const float* __restrict__ x, const float* __restrict__ scales,
+                                                          nsvd_problem prob, float log_norm, int B, int D, int L,
+                                                          float* __restrict__ f, float* __restrict__ Tf,
+                                                          float* __restrict__ jac, float* __restrict__ dsc, NsvdBox box) {
+    __shared__ float tile[4][ND_ROWS][ND_HEADS + 1];
+    __shared__ float dirs[NSVD_MAX_D * NSVD_FDX_DIR_FIELDS][ND_ROWS];
+    __shared__ float rowsum[2][ND_ROWS];
+    const int bl = threadIdx.x & (ND_ROWS - 1), g = threadIdx.x >> 6;
+    const int b0 = blockIdx.x * ND_ROWS, b = b0 + bl;
+    const bool bok = b < B;
+    const float* xr = x + (size_t)(bok ? b : 0) * D;
+    NsvdFdRowNd w;
+    if (bok) {
+        w = nsvd_fd_row_nd<TRIG>(xr, D, prob, log_norm, box);
+        if (g == 0) {
+            const NsvdFdExactRowNd e = nsvd_fd_exact_dirs_nd(xr, D, box, &dirs[0][bl], ND_ROWS);
+            rowsum[0][bl] = e.xG;
+            rowsum[1][bl] = e.lM;
+        }
+    }
+    __syncthreads();
+    NsvdFdExactRowNd e;
+    e.xG = rowsum[0][bl];
+    e.lM = rowsum[1][bl];
+    for (int l0 = 0; l0 < L; l0 += ND_HEADS) {
+        for (int lh = g; lh < ND_HEADS; lh += 4) {
+            const int l = l0 + lh;
+            if (!bok || l >= L) continue;
+            const NsvdFdOut o = nsvd_fd_exact_nd(w, e, base + (size_t)l * ldr + b, (size_t)B, D, scales != nullptr,
+                                                 scales ? scales[l] : 0.f, prob, box, &dirs[0][bl], ND_ROWS);
+            tile[0][bl][lh] = o.f;
+            tile[1][bl][lh] = o.Tf;
+            tile[2][bl][lh] = o.jac;
+            tile[3][bl][lh] = o.dsc;
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < ND_ROWS * ND_HEADS; i += 256) {
+            const int r = i / ND_HEADS, h = i - r * ND_HEADS;
+            if (b0 + r < B && l0 + h < L) {
+                const size_t o = (size_t)(b0 + r) * L + l0 + h;
+                f[o] = tile[0][r][h];
+                Tf[o] = tile[1][r][h];
+                if (jac) jac[o] = tile[2][r][h];
+                if (dsc) dsc[o] = tile[3][r][h];
+            }
+        }
+        __syncthreads();
+    }
+}
+
 __global__ void __launch_bounds__(256) head_backward_kernel(const float* __restrict__ df,
                                                             const float* __restrict__ jac, int B, int L,
                                                             float* __restrict__ dzT) {
@@ -174,6 +256,24 @@ int nsvd_fd_epilogue(const float* base, int ldr, const float* x, const float* sc
     }
     hipLaunchKernelGGL(trig ? fd_epilogue_kernel<true> : fd_epilogue_kernel<false>, dim3(nsvd_cdiv(B * L, 256)),
                        dim3(256), 0, s, base, ldr, x, scales, prob, log_norm, B, D, L, f, Tf, jac, dsc, evenodd, box);
+    NSVD_CHECK_LAUNCH();
+    return 0;
+}
+
+int nsvd_fd_epilogue_exact(const float* base, int ldr, const float* x, const float* scales, const nsvd_problem& prob,
+                           int B, int D, int L, float* f, float* Tf, float* jac, float* dsc, hipStream_t s, NsvdBox box) {
+    if (D < 1 || D > NSVD_MAX_D || ldr < (D + 2) * B || prob.operator_kind != NSVD_OP_SCHROEDINGER)
+        return NSVD_EUNSUPPORTED;
+    const float log_norm = nsvd_importance_log_norm(D, prob);
+    if (D > NSVD_FD_MAXD) {
+        const bool trig = prob.potential == NSVD_POT_COSINE;
+        hipLaunchKernelGGL(trig ? fd_exact_nd_kernel<true> : fd_exact_nd_kernel<false>, dim3(nsvd_cdiv(B, ND_ROWS)),
+                           dim3(256), 0, s, base, ldr, x, scales, prob, log_norm, B, D, L, f, Tf, jac, dsc, box);
+        NSVD_CHECK_LAUNCH();
+        return 0;
+    }
+    hipLaunchKernelGGL(fd_exact_kernel, dim3(nsvd_cdiv(B * L, 256)), dim3(256), 0, s, base, ldr, x, scales, prob,
+                       log_norm, B, D, L, f, Tf, jac, dsc, box);
     NSVD_CHECK_LAUNCH();
     return 0;
 }

@@ -616,6 +616,115 @@ __device__ __forceinline__ NsvdFdOut nsvd_fd_exact(float base, const float* dbas
     return o;
 }
 
+// ---- the same product rule for 5 <= D <= NSVD_MAX_D (NSVD_PATH_GENERIC_EXACT): a loop over directions ----------------
+// nsvd_fd_exact's expressions with the head's jet read from MEMORY - base = bcol[0], d base / d x_d = bcol[(1 + d) bs],
+// Lap base = bcol[(D + 1) bs] (bs = B in the (L, (D + 2) B) layout of the generic jets) - and no per-thread array indexed
+// by a run-time d. What the L heads of a row share comes from nsvd_fd_row_nd (|x|, sqrt p, V, the box mask at the centre)
+// and, per direction, from a table of NSVD_FDX_DIR_FIELDS floats that ONE thread per row fills (nsvd_fd_exact_dirs_nd):
+// field k of direction d at dir[(d NSVD_FDX_DIR_FIELDS + k) es], as nsvd_fd_dir_nd's. The box factors
+// G_d = m'(x_d) prod_{j != d} m(x_j) take a prefix product on the way up and a suffix product on the way down instead of
+// the j != d inner loop; x . G and Lap M, which no head changes, are summed on the way down.
+#define NSVD_FDX_DIR_FIELDS 3
+enum { NSVD_XDIR_X = 0, NSVD_XDIR_G, NSVD_XDIR_M2 };
+struct NsvdFdExactRowNd {
+    float xG, lM;  // x . G, Lap M (0 without a box mask)
+};
+// m'(t), m''(t) inside the box (0 at and beyond the wall): nsvd_fd_exact's closed forms
+__device__ __forceinline__ void nsvd_box_m12(float t, const NsvdBox& box, float* m1, float* m2) {
+    const float a = box.lim - t, b = box.lim + t;
+    *m1 = *m2 = 0.f;
+    if (a > 0.f && b > 0.f) {
+        if (box.mode == NSVD_BOX_SQRT) {
+            const float A = fmaf(box.lim, box.lim, a * b), sA = sqrtf(A);
+            *m1 = -t / (box.lim * sA);
+            *m2 = -2.f * box.lim / (A * sA);
+        } else {
+            const float ea = expf(-a), eb = expf(-b);
+            *m1 = -(ea - eb);
+            *m2 = -(ea + eb);
+        }
+    }
+}
+__device__ __forceinline__ NsvdFdExactRowNd nsvd_fd_exact_dirs_nd(const float* xr, int D, const NsvdBox& box, float* dir,
+                                                                  size_t es) {
+    float pre = 1.f;  // prod_{j < d} m(x_j)
+    for (int d = 0; d < D; ++d) {
+        float* q = dir + (size_t)d * NSVD_FDX_DIR_FIELDS * es;
+        const float xd = xr[d];
+        q[NSVD_XDIR_X * es] = xd;
+        if (box.mode) {
+            float m1, m2;
+            nsvd_box_m12(xd, box, &m1, &m2);
+            q[NSVD_XDIR_G * es] = pre * m1;
+            q[NSVD_XDIR_M2 * es] = pre * m2;
+            pre *= nsvd_box_m1(box.lim - xd, box.lim + xd, box);
+        }
+    }
+    NsvdFdExactRowNd o;
+    o.xG = o.lM = 0.f;
+    if (box.mode) {
+        float suf = 1.f;  // prod_{j > d} m(x_j)
+        for (int d = D - 1; d >= 0; --d) {
+            float* q = dir + (size_t)d * NSVD_FDX_DIR_FIELDS * es;
+            const float xd = q[NSVD_XDIR_X * es];
+            const float G = q[NSVD_XDIR_G * es] * suf;
+            q[NSVD_XDIR_G * es] = G;
+            o.xG = fmaf(G, xd, o.xG);
+            o.lM = fmaf(q[NSVD_XDIR_M2 * es], suf, o.lM);
+            suf *= nsvd_box_m1(box.lim - xd, box.lim + xd, box);
+        }
+    }
+    return o;
+}
+__device__ __forceinline__ NsvdFdOut nsvd_fd_exact_nd(const NsvdFdRowNd& w, const NsvdFdExactRowNd& e, const float* bcol,
+                                                      size_t bs, int D, bool has_mask, float s_l,
+                                                      const nsvd_problem& prob, const NsvdBox& box, const float* dir,
+                                                      size_t es) {
+    const float r2 = w.r2, r0 = w.r0, sp = w.sp0;
+    const float base = bcol[0], lbase = bcol[(size_t)(D + 1) * bs];
+    const float c = prob.hard_mul_const;
+    float lsp_f = 0.f, dsp_f = 0.f;  // Lap sqrt p / sqrt p, and grad sqrt p = dsp_f * x * sqrt p
+    if (prob.use_importance == NSVD_IMP_GAUSSIAN) {
+        const float is2 = 1.f / (2.f * prob.sigma * prob.sigma);
+        dsp_f = -is2;
+        lsp_f = -(float)D * is2 + r2 * is2 * is2;
+    }
+    float mk = 1.f, lmk_f = 0.f, dmk_f = 0.f;  // mask, Lap mask / mask, grad mask = dmk_f * x * mask
+    if (has_mask) {
+        mk = expf(-r0 / s_l);
+        dmk_f = -1.f / (r0 * s_l);
+        lmk_f = 1.f / (s_l * s_l) - (float)(D - 1) / (r0 * s_l);
+    }
+    const float u = c * sp * mk;
+    const float gu = dsp_f + dmk_f;
+    float dot = 0.f, gdot = 0.f;  // x . grad base, G . grad base
+    for (int d = 0; d < D; ++d) {
+        const float* q = dir + (size_t)d * NSVD_FDX_DIR_FIELDS * es;
+        const float db = bcol[(size_t)(1 + d) * bs];
+        dot = fmaf(q[NSVD_XDIR_X * es], db, dot);
+        if (box.mode) gdot = fmaf(q[NSVD_XDIR_G * es], db, gdot);
+    }
+    const float lu = lsp_f + 2.f * dsp_f * dmk_f * r2 + lmk_f;
+    const float M = w.M0;
+    float g = u * base;
+    float lap = u * (lbase + 2.f * gu * dot + base * lu);
+    if (box.mode) {
+        g = u * M * base;
+        lap = u * (M * lbase + 2.f * (M * gu * dot + gdot) + base * (M * lu + 2.f * gu * e.xG + e.lM));
+    }
+    const float spc = prob.use_importance ? fmaxf(sp, NSVD_SQRT_P_CLAMP) : 1.f;
+    lap = lap / spc;
+    const float fs = g / spc;
+    const float H = -prob.scale_kinetic * lap + w.V * fs;
+    NsvdFdOut o;
+    o.f = fs;
+    o.Tf = prob.op_scale * (-H) + prob.op_shift * fs;
+    const float wt = (sp / spc) * c;
+    o.jac = wt * (mk * M);
+    o.dsc = has_mask ? wt * base * (mk * M) * r0 / (s_l * s_l) : 0.f;
+    return o;
+}
+
 // ---- NeuralEF (neuralef.hip): every stencil point divided by its own batch norm (methods/utils.py:48-56) ----------------
 // Even / odd parts of rho_+- = w(x_+-) / w(x0) - 1 along direction d: ev = rho_+ + rho_-, od = rho_+ - rho_-, with
 // w = sqrt p (qs = d log sqrt p / d |x|^2, 0 without importance) times the mask (has_mask) - nsvd_fd_evenodd's arithmetic

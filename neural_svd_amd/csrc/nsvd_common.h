@@ -35,10 +35,11 @@ static inline NsvdBox nsvd_box_of(const nsvd_model_desc& d) {
 // derivative by central differences (eps > 0; with eps <= 0 the reference's own einsum fails) and main's problems.py
 // asserts against the Gaussian sampler; no box mask is defined for the periodic problems.
 // Input dimensions above NSVD_SMALL_D (= NSVD_FD_MAXD, fd_math.h) take the direction-loop epilogue and the table pointer
-// of ABI 5, up to NSVD_MAX_D, in the finite-difference mode only.
+// of ABI 5, up to NSVD_MAX_D, in the finite-difference mode only - except on NSVD_PATH_GENERIC_EXACT (`path`), whose jet
+// epilogue carries the exact mode up to NSVD_MAX_D; every other path value keeps the refusal.
 #define NSVD_SMALL_D 4
 #define NSVD_MAX_D 12
-static inline int nsvd_problem_status(const nsvd_model_desc& d, const nsvd_problem& p) {
+static inline int nsvd_problem_status(const nsvd_model_desc& d, const nsvd_problem& p, int path = NSVD_PATH_AUTO) {
     if ((p.potential < NSVD_POT_HYDROGEN || p.potential > NSVD_POT_SIN_OF_COS) && p.potential != NSVD_POT_MOLECULE)
         return NSVD_EINVAL;
     if (p.use_importance < NSVD_IMP_NONE || p.use_importance > NSVD_IMP_UNIFORM) return NSVD_EINVAL;
@@ -58,7 +59,7 @@ static inline int nsvd_problem_status(const nsvd_model_desc& d, const nsvd_probl
         (!p.pot_table || p.pot_table_len != d.D))
         return NSVD_EINVAL;
     if (d.D > NSVD_MAX_D) return NSVD_EUNSUPPORTED;
-    if (d.D > NSVD_SMALL_D && !(p.eps > 0.f)) return NSVD_EUNSUPPORTED;
+    if (d.D > NSVD_SMALL_D && !(p.eps > 0.f) && path != NSVD_PATH_GENERIC_EXACT) return NSVD_EUNSUPPORTED;
     if (p.operator_kind != NSVD_OP_FOKKER_PLANCK) return p.potential == NSVD_POT_SIN_OF_COS ? NSVD_EINVAL : 0;
     if (p.potential != NSVD_POT_SIN_OF_COS || !(p.eps > 0.f) || p.use_importance == NSVD_IMP_GAUSSIAN ||
         d.box_mask != NSVD_BOX_NONE)

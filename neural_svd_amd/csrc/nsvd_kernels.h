@@ -61,6 +61,16 @@ int nsvd_rowsum(const float* in, float* out, int rows, int n, long ld, hipStream
 int nsvd_fd_epilogue(const float* base, int ldr, const float* x, const float* scales, const nsvd_problem& prob,
                      int B, int D, int L, float* f, float* Tf, float* jac, float* dsc, hipStream_t s, int evenodd = 0,
                      NsvdBox box = NsvdBox{0, 0.f});
+// The exact-Laplacian counterpart (NSVD_PATH_GENERIC_EXACT): base (L, ldr) holds each head's jet in D + 2 row blocks of B
+// samples - value, d / d x_0 .. d / d x_{D-1}, Laplacian; the product rule with sqrt p, the masks and the potential
+// (fd_math.h: nsvd_fd_exact up to D = 4, nsvd_fd_exact_nd above). Same outputs, so nsvd_head_backward is unchanged.
+int nsvd_fd_epilogue_exact(const float* base, int ldr, const float* x, const float* scales, const nsvd_problem& prob,
+                           int B, int D, int L, float* f, float* Tf, float* jac, float* dsc, hipStream_t s,
+                           NsvdBox box = NsvdBox{0, 0.f});
+
+// (the jets' own kernels, generic_jets.hip, are declared in include/nsvd.h: nsvd_fourier_features_jets,
+// nsvd_softplus_jets_inplace)
+
 // dzT[l][b] = df[b][l] * jac[b][l]; dscales[l] = sum_b df[b][l] * dsc[b][l] (when dscales != null)
 int nsvd_head_backward(const float* df, const float* jac, const float* dsc, int B, int L, float* dzT,
                        float* dscales, hipStream_t s);

@@ -57,10 +57,21 @@ int validate(const nsvd_model_desc* d, int max_d = NSVD_MAX_D) {
 
 // every operator path implements every potential and importance below; anything else is refused, never ignored
 // (the Fokker-Planck kind only inside nsvd_problem_status' conditions: NSVD_EUNSUPPORTED outside them)
-int validate_problem(const nsvd_model_desc* d, const nsvd_problem* p) {
+// path: NSVD_PATH_GENERIC_EXACT lifts the exact mode's limit of NSVD_SMALL_D input dimensions (nsvd_problem_status)
+int validate_problem(const nsvd_model_desc* d, const nsvd_problem* p, int path = NSVD_PATH_AUTO) {
     if (!p) return NSVD_EINVAL;
-    return nsvd_problem_status(*d, *p);
+    return nsvd_problem_status(*d, *p, path);
 }
+
+// NSVD_PATH_GENERIC_EXACT: the exact Laplacian on the generic kernels, D + 2 jet blocks per sample instead of the 1 + 2 D
+// stencil blocks. Explicit request only; with eps > 0 it cannot be honoured (the Fokker-Planck kind has no exact mode at
+// all: nsvd_problem_status refuses it with eps <= 0 on every path).
+bool generic_exact(int path) { return path == NSVD_PATH_GENERIC_EXACT; }
+int generic_exact_status(const nsvd_problem& p) {
+    return (p.eps > 0.f || p.operator_kind != NSVD_OP_SCHROEDINGER) ? NSVD_EUNSUPPORTED : 0;
+}
+// stencil blocks of the generic layout for `path` (carve's erows; 0 = the 1 + 2 D of the stencil mode)
+int generic_erows(const nsvd_model_desc& d, int path) { return generic_exact(path) ? d.D + 2 : 0; }
 
 NsvdSampler make_sampler(const nsvd_problem& prob, unsigned long long seed, unsigned long long offset) {
     NsvdSampler smp;
@@ -103,7 +114,8 @@ GenericWs carve(const nsvd_model_desc& d, int B, void* base, int erows = 0) {
 
 // exact: the exact-Laplacian mode (prob->eps <= 0), whose D + 2 jet streams fit the MFMA path up to D = 3
 bool want_fused(const nsvd_model_desc& d, int B, int path, bool exact = false) {
-    if (path == NSVD_PATH_GENERIC) return false;  // NSVD_PATH_FUSED and NSVD_PATH_FUSED_BF16X3 both need the MFMA path
+    // (NSVD_PATH_FUSED and NSVD_PATH_FUSED_BF16X3 both need the MFMA path)
+    if (path == NSVD_PATH_GENERIC || path == NSVD_PATH_GENERIC_EXACT) return false;
     // above the small stencil: the split form on explicit request only - NSVD_PATH_AUTO stays on the generic kernels
     // until the two are measured against each other
     if (d.D > NSVD_SMALL_D) return path == NSVD_PATH_FUSED && !exact && nsvd_fused_split_nd_supported(d, B);
@@ -120,15 +132,17 @@ int check_params(const nsvd_model_desc& d, const nsvd_params* p, bool need_fouri
 }
 
 // Fourier map + every ParallelMLP layer for the first `nst` stencil blocks (nst = E: all rows, 1: centre only)
+// jets: the nst = D + 2 blocks are the forward-mode jet of the exact mode (generic_jets.hip) instead of the stencil
 int generic_mlp(const nsvd_model_desc& d, const nsvd_params& p, const float* x, int B, float eps, int nst,
-                const GenericWs& w, hipStream_t s, bool features_ready = false) {
+                const GenericWs& w, hipStream_t s, bool features_ready = false, bool jets = false) {
     const int R = w.R, F = 2 * d.m;
     int rc = 0;
     // all stencil rows: the shifted row blocks in EVEN / ODD form - features, pre-activations and head
     // outputs of block 1 + 2 d / 2 + 2 d are the even / odd perturbations along d; centre rows only (nst = 1): plain
-    const bool eo = nst > 1;
+    const bool eo = nst > 1 && !jets;
     if (!features_ready)
-        rc = eo ? nsvd_fourier_features_evenodd(x, p.fourier_B, w.phiT, B, d.D, d.m, eps, R, s)
+        rc = jets ? nsvd_fourier_features_jets(x, p.fourier_B, w.phiT, B, d.D, d.m, R, s) :
+             eo ? nsvd_fourier_features_evenodd(x, p.fourier_B, w.phiT, B, d.D, d.m, eps, R, s)
                 : nsvd_fourier_features(x, p.fourier_B, w.phiT, B, d.D, d.m, eps, nst, R, s);
     if (rc) return rc;
     int kin = F;
@@ -140,13 +154,14 @@ int generic_mlp(const nsvd_model_desc& d, const nsvd_params& p, const float* x, 
         g.B = (i == 0) ? w.phiT : w.z[i - 1]; g.sBk = R; g.sBn = 1; g.bB = (i == 0) ? 0 : (long)kin * R;
         g.C = w.z[i]; g.sCm = R; g.bC = (long)d.dims[i] * R;
         g.bias = p.b[i]; g.bBias = d.dims[i];
-        g.eo_cols = eo ? B : 0;
+        g.eo_cols = (eo || jets) ? B : 0;  // (jets too: a linear layer maps every stream by itself, the bias joins block 0)
         rc = nsvd_gemm_generic(g, s);
         if (rc) return rc;
         // hidden layers: pre-activations -> activations in place (what the next layer, the weight gradient and the data
         // gradient's sigmoid factor read); the last layer's output stays as it is
         if (i + 1 < d.nlayers) {
-            rc = nsvd_softplus_inplace(w.z[i], (long)d.L * d.dims[i], B, nst, s);
+            rc = jets ? nsvd_softplus_jets_inplace(w.z[i], (long long)d.L * d.dims[i], B, d.D, s)
+                      : nsvd_softplus_inplace(w.z[i], (long)d.L * d.dims[i], B, nst, s);
             if (rc) return rc;
         }
         kin = d.dims[i];
@@ -155,16 +170,18 @@ int generic_mlp(const nsvd_model_desc& d, const nsvd_params& p, const float* x, 
 }
 
 int generic_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x, int B,
-                    float* f, float* Tf, void* ws, hipStream_t s, bool features_ready = false) {
-    const GenericWs w = carve(d, B, ws);
-    const int E = 1 + 2 * d.D, R = E * B;
+                    float* f, float* Tf, void* ws, hipStream_t s, bool features_ready = false, bool exact = false) {
+    const GenericWs w = carve(d, B, ws, exact ? d.D + 2 : 0);
+    const int E = exact ? d.D + 2 : 1 + 2 * d.D, R = E * B;
     // (bench.py's event bracket: the WHOLE forward - features, every layer, the finite-difference epilogue - as the fused
     // forward kernel is one launch doing all of it)
     nsvd_prof_begin(s);
-    int rc = generic_mlp(d, p, x, B, prob.eps, E, w, s, features_ready);
+    int rc = generic_mlp(d, p, x, B, prob.eps, E, w, s, features_ready, exact);
     if (rc) return rc;
-    rc = nsvd_fd_epilogue(w.z[d.nlayers - 1], R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L, f, Tf,
-                          w.jac, w.dsc, s, 1, nsvd_box_of(d));
+    rc = exact ? nsvd_fd_epilogue_exact(w.z[d.nlayers - 1], R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L,
+                                        f, Tf, w.jac, w.dsc, s, nsvd_box_of(d))
+               : nsvd_fd_epilogue(w.z[d.nlayers - 1], R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L, f, Tf,
+                                  w.jac, w.dsc, s, 1, nsvd_box_of(d));
     nsvd_prof_end(s);
     return rc;
 }
@@ -221,6 +238,7 @@ extern "C" int nsvd_abi_version(void) { return NSVD_ABI_VERSION; }
 
 extern "C" const char* nsvd_path_name(const nsvd_model_desc* desc, int B, int path) {
     if (validate(desc) != 0 || B <= 0) return "invalid";
+    if (generic_exact(path)) return "generic_exact";
     return want_fused(*desc, B, path) ? "fused_mfma" : "generic";
 }
 
@@ -234,8 +252,9 @@ extern "C" int nsvd_step_emits_planes(const nsvd_model_desc* desc, int B, int pa
 extern "C" const char* nsvd_path_name_for(const nsvd_model_desc* desc, const nsvd_problem* prob, int B, int path) {
     // (more input dimensions than the stencil carries are nsvd_problem_status' to answer: "unsupported")
     if (validate(desc, MODEL_MAX_D) != 0 || B <= 0 || !prob) return "invalid";
-    const int st = validate_problem(desc, prob);
+    const int st = validate_problem(desc, prob, path);
     if (st) return st == NSVD_EUNSUPPORTED ? "unsupported" : "invalid";
+    if (generic_exact(path)) return generic_exact_status(*prob) ? "unsupported" : "generic_exact";
     const bool exact = !(prob->eps > 0.f);
     if (want_fused(*desc, B, path, exact)) return "fused_mfma";
     // (above NSVD_SMALL_D an explicitly fused path has nothing to fall back to: the entry points return NSVD_EUNSUPPORTED)
@@ -264,23 +283,26 @@ extern "C" int nsvd_operator_forward(const nsvd_model_desc* desc, const nsvd_par
     int rc = validate(desc);
     if (rc) return rc;
     if (!prob || !x || !f || !Tf || !ws || B <= 0) return NSVD_EINVAL;
-    rc = validate_problem(desc, prob);
+    rc = validate_problem(desc, prob, path);
     if (rc) return rc;
+    const bool gexact = generic_exact(path);
+    if (gexact && (rc = generic_exact_status(*prob)) != 0) return rc;
     rc = check_params(*desc, params, true);
     if (rc) return rc;
     if (ws_bytes < nsvd_workspace_bytes(desc, B)) return NSVD_EINVAL;
     if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
     const bool fused = want_fused(*desc, B, path, !(prob->eps > 0.f));
     if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
-    // eps <= 0 selects the exact Laplacian (reference diff_ops.py:7): forward-mode jets, MFMA path only
-    if (!(prob->eps > 0.f) && !fused) return NSVD_EUNSUPPORTED;
+    // eps <= 0 selects the exact Laplacian (reference diff_ops.py:7): forward-mode jets, on the MFMA path or - on
+    // explicit request only - on the generic kernels
+    if (!(prob->eps > 0.f) && !fused && !gexact) return NSVD_EUNSUPPORTED;
     const bool ready = (save_for_backward & NSVD_FEATURES_READY) != 0;
     const bool planes = (save_for_backward & NSVD_W_PLANES_READY) != 0 && path == NSVD_PATH_FUSED_BF16X3;
     if (fused)
         return nsvd_fused_forward(*desc, *params, *prob, x, B, f, Tf, ws,
                                   (save_for_backward & 1) | (ready ? 2 : 0) | (planes ? 4 : 0), (hipStream_t)stream,
                                   path == NSVD_PATH_FUSED_BF16X3);
-    return generic_forward(*desc, *params, *prob, x, B, f, Tf, ws, (hipStream_t)stream, ready);
+    return generic_forward(*desc, *params, *prob, x, B, f, Tf, ws, (hipStream_t)stream, ready, gexact);
 }
 
 // NeuralEF (neuralef.hip): the operator forward up to the raw head outputs - (L, ldr) rows e B + b in the even / odd
@@ -290,6 +312,7 @@ int nsvd_operator_forward_raw(const nsvd_model_desc& d, const nsvd_params& p, co
     const bool fused = want_fused(d, B, path, !(prob.eps > 0.f));
     if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
     if (path == NSVD_PATH_FUSED_BF16X3 || !(prob.eps > 0.f)) return NSVD_EUNSUPPORTED;
+    if (generic_exact(path)) return NSVD_EUNSUPPORTED;  // (no NeuralEF on the generic jets, and no stencil on that path)
     // the per-point batch norms know neither the box mask nor the uniform density
     if (d.box_mask != NSVD_BOX_NONE || prob.use_importance > NSVD_IMP_GAUSSIAN) return NSVD_EUNSUPPORTED;
     const int R = (1 + 2 * d.D) * B;
@@ -323,6 +346,11 @@ extern "C" int nsvd_operator_features(const nsvd_model_desc* desc, const nsvd_pa
     const bool fused = want_fused(*desc, B, path, !(prob->eps > 0.f));
     if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
     if (fused) return nsvd_fused_features(*desc, *params, *prob, x, B, ws, save_for_backward & 1, (hipStream_t)stream);
+    if (generic_exact(path)) {  // the jet features, in the layout generic_forward(exact) reads
+        if (const int st = generic_exact_status(*prob)) return st;
+        const GenericWs w = carve(*desc, B, ws, desc->D + 2);
+        return nsvd_fourier_features_jets(x, params->fourier_B, w.phiT, B, desc->D, desc->m, w.R, stream);
+    }
     if (!(prob->eps > 0.f)) return NSVD_EUNSUPPORTED;
     const GenericWs w = carve(*desc, B, ws);
     const int E = 1 + 2 * desc->D;
@@ -337,8 +365,10 @@ int sample_features_impl(const nsvd_model_desc* desc, const nsvd_params* params,
     int rc = validate(desc);
     if (rc) return rc;
     if (!prob || !x || !ws || !params || !params->fourier_B || B <= 0) return NSVD_EINVAL;
-    rc = validate_problem(desc, prob);
+    rc = validate_problem(desc, prob, path);
     if (rc) return rc;
+    const bool gexact = generic_exact(path);
+    if (gexact && (rc = generic_exact_status(*prob)) != 0) return rc;
     if (ws_bytes < nsvd_workspace_bytes(desc, B)) return NSVD_EINVAL;
     if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
     const bool fused = want_fused(*desc, B, path, !(prob->eps > 0.f));
@@ -347,9 +377,13 @@ int sample_features_impl(const nsvd_model_desc* desc, const nsvd_params* params,
     smp.offset_add = state ? (const unsigned long long*)&state->step : nullptr;
     hipStream_t s = (hipStream_t)stream;
     if (fused) return nsvd_fused_features(*desc, *params, *prob, x, B, ws, save_for_backward & 1, s, &smp, x);
-    if (!(prob->eps > 0.f)) return NSVD_EUNSUPPORTED;
+    if (!(prob->eps > 0.f) && !gexact) return NSVD_EUNSUPPORTED;
     rc = nsvd_sample_launch(smp, x, B, desc->D, s);
     if (rc) return rc;
+    if (gexact) {
+        const GenericWs w = carve(*desc, B, ws, desc->D + 2);
+        return nsvd_fourier_features_jets(x, params->fourier_B, w.phiT, B, desc->D, desc->m, w.R, stream);
+    }
     const GenericWs w = carve(*desc, B, ws);
     const int E = 1 + 2 * desc->D;
     return nsvd_fourier_features_evenodd(x, params->fourier_B, w.phiT, B, desc->D, desc->m, prob->eps, E * B,
@@ -434,7 +468,8 @@ extern "C" int nsvd_operator_backward(const nsvd_model_desc* desc, const nsvd_pa
     const bool fused = want_fused(*desc, B, path, !(prob->eps > 0.f));
     if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
     if (fused) return nsvd_fused_backward(*desc, *params, *prob, x, B, df, *grads, ws, (hipStream_t)stream);
-    return generic_backward(*desc, *params, x, B, df, *grads, ws, (hipStream_t)stream);
+    if (generic_exact(path) && generic_exact_status(*prob)) return NSVD_EUNSUPPORTED;
+    return generic_backward(*desc, *params, x, B, df, *grads, ws, (hipStream_t)stream, generic_erows(*desc, path));
 }
 
 namespace {
@@ -556,7 +591,9 @@ int backward_evd_impl(const nsvd_model_desc* desc, const nsvd_params* params, co
     // generic path: finish the loss with the stand-alone kernels, then the layer-by-layer backward
     if (direct) return NSVD_EINVAL;  // needs the partial moments (evd_scratch) or the reduced ones
     if (L_total != desc->L) return NSVD_EUNSUPPORTED;  // head-parallel sharding needs the fused kernels
-    const GenericWs w = carve(*desc, B, ws);
+    if (generic_exact(path) && generic_exact_status(*prob)) return NSVD_EUNSUPPORTED;
+    const int erows = generic_erows(*desc, path);  // (the workspace of the forward call: jet blocks or stencil blocks)
+    const GenericWs w = carve(*desc, B, ws, erows);
     if (!moments_reduced) {
         rc = nsvd_evd_reduce_partials(evd_scratch, B, L, moments, s);
         if (rc) return rc;
@@ -564,7 +601,7 @@ int backward_evd_impl(const nsvd_model_desc* desc, const nsvd_params* params, co
     rc = nsvd_evd_loss_grad(f, Tf, B, L, mask_kind, v, M, moments, grad_scale, loss, w.df, stream);
     if (rc) return rc;
     if (!grads) return NSVD_EINVAL;  // the generic path needs somewhere to put the gradients
-    rc = generic_backward(*desc, *params, x, B, w.df, *grads, ws, s);
+    rc = generic_backward(*desc, *params, x, B, w.df, *grads, ws, s, erows);
     if (rc || !take_step) return rc;
     if (st.rule != NSVD_RULE_RMSPROP) {
         // the other rules: one stand-alone launch per tensor (scalars from the device-resident schedule when there is

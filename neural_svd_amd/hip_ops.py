@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import (MASK_CUSTOM, MASK_JOINT, MASK_SEQUENTIAL, PATH_AUTO, PATH_FUSED, PATH_FUSED_BF16X3,  # noqa: F401
-                   PATH_GENERIC,
+                   PATH_GENERIC, PATH_GENERIC_EXACT,
                    BOX_EXP, BOX_NONE, BOX_SQRT, IMP_GAUSSIAN, IMP_NONE, IMP_UNIFORM, POT_HARMONIC, POT_HYDROGEN, POT_ZERO, POT_COSINE, POT_H2_ION, POT_SIN_OF_COS, POT_MOLECULE, OP_SCHROEDINGER, OP_FOKKER_PLANCK,
                    ModelDesc, NsvdError, Params, Problem, check)
 
@@ -250,7 +250,8 @@ def workspace_bytes(shape: ModelShape, B: int) -> int:
 
 
 def path_name(shape: ModelShape, B: int, path: int = PATH_AUTO, prob: Optional[Problem] = None) -> str:
-    """"fused_mfma" / "generic" (/ "unsupported": exact-Laplacian mode on a shape the MFMA path does not take)."""
+    """"fused_mfma" / "generic" / "generic_exact" (PATH_GENERIC_EXACT with eps <= 0) (/ "unsupported": e.g. the
+    exact-Laplacian mode on a shape the MFMA path does not take, under any path value but PATH_GENERIC_EXACT)."""
     d = shape.desc()
     if prob is not None:
         return _lib.load().nsvd_path_name_for(C.byref(d), C.byref(prob), int(B), int(path)).decode()
@@ -277,6 +278,33 @@ def fourier_features(x: torch.Tensor, fourier_B: torch.Tensor, eps: float, nsten
                                            int(nstencil), R, _stream())
     check(rc, "nsvd_fourier_features")
     return out
+
+
+@_on_tensor_device
+def fourier_features_jets(x: torch.Tensor, fourier_B: torch.Tensor) -> torch.Tensor:
+    """The jet of the Fourier map as PATH_GENERIC_EXACT lays it out: (2m, (D + 2) B) - block 0 [sin | cos](x B), block
+    1 + d the derivative along x_d, block D + 1 the Laplacian (nsvd_fourier_features_jets)."""
+    B, D = x.shape
+    m = fourier_B.shape[1]
+    if tuple(fourier_B.shape) != (D, m):
+        raise NsvdError(f"fourier_B must be ({D}, m), got {tuple(fourier_B.shape)}")
+    R = (D + 2) * B
+    out = torch.empty((2 * m, R), dtype=torch.float32, device=x.device)
+    rc = _lib.load().nsvd_fourier_features_jets(_ptr(x, "x"), _ptr(fourier_B, "fourier_B"), _ptr(out), B, D, m, R,
+                                                _stream())
+    check(rc, "nsvd_fourier_features_jets")
+    return out
+
+
+@_on_tensor_device
+def softplus_jets_inplace(z: torch.Tensor, B: int, D: int) -> torch.Tensor:
+    """z (rows, (D + 2) B), the jet of a hidden layer's pre-activations, becomes the jet of its activations in place
+    (nsvd_softplus_jets_inplace); returns z."""
+    if z.dim() != 2 or z.shape[1] != (D + 2) * B:
+        raise NsvdError(f"z must be (rows, {(D + 2) * B}), got {tuple(z.shape)}")
+    rc = _lib.load().nsvd_softplus_jets_inplace(_ptr(z, "z"), z.shape[0], int(B), int(D), _stream())
+    check(rc, "nsvd_softplus_jets_inplace")
+    return z
 
 
 def operator_forward(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor, ws: torch.Tensor,

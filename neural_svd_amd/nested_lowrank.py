@@ -359,5 +359,8 @@ def get_evd_method(args, method_name, model):
                                     unbiased=args.loss.neuralef.unbiased, sort=args.sort)
     if method_name != "neuralsvd":
         raise NotImplementedError(f"{method_name}: only 'neuralsvd' (NestedLoRA) and 'neuralef' are built on this path")
+    # opt-in (args.generic_exact_laplacian with laplacian_eps <= 0): the exact Laplacian on the generic kernels, for
+    # models and input dimensions the MFMA jets do not take - never chosen otherwise (PATH_AUTO refuses those shapes)
+    exact = getattr(args, "generic_exact_laplacian", False) and not float(getattr(args, "laplacian_eps", 1.0)) > 0
     return NestedLoRA(model=model, neigs=args.neigs, step=args.loss.neuralsvd.step, sort=args.sort,
-                      sequential=args.loss.neuralsvd.sequential)
+                      sequential=args.loss.neuralsvd.sequential, path=H.PATH_GENERIC_EXACT if exact else H.PATH_AUTO)

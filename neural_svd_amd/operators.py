@@ -234,7 +234,8 @@ class NegativeHamiltonian:
         self.laplacian_eps = laplacian_eps
         self.n_particles = n_particles
         self.mol = local_potential_ftn.keywords["mol"] if self.potential_kind == H.POT_MOLECULE else None
-        # laplacian_eps <= 0: exact Laplacian (reference diff_ops.py:7,54-61) - forward-mode jets on the MFMA path
+        # laplacian_eps <= 0: exact Laplacian (reference diff_ops.py:7,54-61) - forward-mode jets on the MFMA path, or
+        # on the generic kernels for a method built with path=PATH_GENERIC_EXACT (args.generic_exact_laplacian)
 
     def __call__(self, f, xs, importance=None, threshold=1e5):
         return OperatorWrapper(self)(f, xs, importance)
@@ -520,7 +521,7 @@ def _periodic_asserts(args, name):
     _require(args.ndim in (1, 2, 5, 10), f"{name}: ndim 1, 2, 5 or 10")
     if args.ndim > 2 and not getattr(args, "high_dim_stencil", False):
         raise ProblemConfigError(f"{name} with ndim {args.ndim}: {_TOO_MANY_DIMS}")
-    if args.ndim > 2:
+    if args.ndim > 2 and not (getattr(args, "generic_exact_laplacian", False) and name != "problem fp"):
         _require(args.laplacian_eps > 0, f"{name} with ndim {args.ndim}: the direction-loop stencil needs laplacian_eps "
                                          f"> 0 (no exact-Laplacian mode above 4 input dimensions)")
 
@@ -536,6 +537,9 @@ _FP_CS = {1: [1.0], 2: [1.0, 1.0], 5: [1.0, 0.8, 0.6, 0.4, 0.2], 10: [0.1, 0.3, 
 def get_problem(args, device=None):
     """problems.py:23-130. ndim 5 / 10 of the periodic pair and the quantum_chemistry branch (args.mol_name, ndim 2 or
     3, n_particles * ndim <= 12) are accepted when ``args.high_dim_stencil`` is true and refused as before without it.
+    ``args.generic_exact_laplacian`` (opt-in, read with getattr) lifts the ``laplacian_eps > 0`` requirement of those
+    Schroedinger problems: get_evd_method then builds the method on PATH_GENERIC_EXACT, whose jets carry the exact
+    Laplacian up to 12 input dimensions (the Fokker-Planck problem has no exact mode and keeps the requirement).
     The cosine and Fokker-Planck branches of the reference
     read two names its own parser (main_pde.py) never defines; here ``args.use_gaussian_sampling`` is read as
     ``args.sampling_mode == "gaussian"`` and ``args.scale_operator`` as ``getattr(args, "scale_operator", 1.0)``.
@@ -596,8 +600,9 @@ def get_problem(args, device=None):
         _require(args.n_particles >= 1, f"quantum_chemistry {args.mol_name}: no electrons")
         _require(d <= _MAX_HIGH_DIM, f"quantum_chemistry {args.mol_name} at ndim {args.ndim}: {d} input dimensions - "
                                      f"{_TOO_MANY_HIGH_DIMS}")
-        _require(d <= _MAX_STENCIL_DIM or args.laplacian_eps > 0,
-                 f"quantum_chemistry with {d} input dimensions needs laplacian_eps > 0")
+        _require(d <= _MAX_STENCIL_DIM or args.laplacian_eps > 0 or getattr(args, "generic_exact_laplacian", False),
+                 f"quantum_chemistry with {d} input dimensions needs laplacian_eps > 0 (or args.generic_exact_laplacian: "
+                 f"the exact Laplacian on the generic kernels)")
     else:
         raise NotImplementedError(f"potential_type {args.potential_type}: not in scope of the HIP path")
     ham = NegativeHamiltonian(local_potential_ftn=pot, scale_kinetic=scale_kinetic, laplacian_eps=args.laplacian_eps,

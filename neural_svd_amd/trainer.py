@@ -188,6 +188,10 @@ class FusedTrainer:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.path = path
+        if path == H.PATH_GENERIC_EXACT and comm is not None and comm.multi:
+            raise NotImplementedError("FusedTrainer(path=PATH_GENERIC_EXACT) with a communicator: the exact Laplacian on "
+                                      "the generic kernels is built for single-process steps only (no sample- or "
+                                      "head-sharded step on this path)")
         self.comm = comm  # parallel.Communicator or None
         world = comm.world if comm is not None else 1
         rank = comm.rank if comm is not None else 0

@@ -48,13 +48,17 @@ def main():
     ap.add_argument("--problem", default="sch", choices=("sch", "fp"), help="fp: the linear Fokker-Planck operator")
     ap.add_argument("--hidden", default="128,128,128")
     ap.add_argument("--val-points", type=int, default=65536, help="ndim > 2: points of the sampled evaluation")
+    ap.add_argument("--exact", action="store_true",
+                    help="laplacian_eps 0: the exact Laplacian on the generic kernels' forward-mode jets "
+                         "(args.generic_exact_laplacian -> PATH_GENERIC_EXACT) instead of the eps = 0.01 stencil")
     ap.add_argument("--out", default=None)
     o = ap.parse_args()
     high = o.ndim > 2
     dev = "cuda:0"
     pi = float(np.pi)
     a = argparse.Namespace(
-        problem=o.problem, potential_type="cosine", charge=1.0, ndim=o.ndim, n_particles=1, neigs=o.neigs, laplacian_eps=0.01,
+        problem=o.problem, potential_type="cosine", charge=1.0, ndim=o.ndim, n_particles=1, neigs=o.neigs,
+        laplacian_eps=0.0 if o.exact else 0.01,
         operator_scale=1.0, operator_shift=o.operator_shift, sampling_mode="uniform", sampling_scale=pi,
         batch_size=o.batch_size, lim=pi, val_eps=pi / 100.0, use_fourier_feature=True,
         fourier_mapping_size=o.fourier_mapping_size, fourier_scale=1.0, fourier_deterministic=True,
@@ -62,7 +66,7 @@ def main():
         exp_mask_init_scale=1.0, hard_mul_const=1.0, apply_boundary=0, boundary_mode="dir_box_sqrt", sort=0,
         optimizer="rmsprop", lr=1e-4, rmsprop_decay=0.999, momentum=0.0, adam_eps=1e-7, num_iters=o.steps,
         ema_decay=0.995, use_lr_scheduler=True, print_freq=10 ** 9, eval_freq=o.eval_freq or o.steps, log_dir=None,
-        fused_loop=not o.plain_loop, high_dim_stencil=high)
+        fused_loop=not o.plain_loop, high_dim_stencil=high, generic_exact_laplacian=o.exact)
     a.loss = argparse.Namespace(name="neuralsvd", neuralsvd=argparse.Namespace(step=1, sequential=o.sequential))
     torch.manual_seed(o.seed)
     operator, gt = get_problem(a, dev)

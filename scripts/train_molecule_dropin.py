@@ -42,19 +42,22 @@ def main():
     ap.add_argument("--val-points", type=int, default=65536)
     ap.add_argument("--sequential", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--exact", action="store_true",
+                    help="laplacian_eps 0: the exact Laplacian on the generic kernels' forward-mode jets "
+                         "(args.generic_exact_laplacian -> PATH_GENERIC_EXACT) instead of the eps = 0.01 stencil")
     ap.add_argument("--out", default=None)
     o = ap.parse_args()
     dev = "cuda:0"
     a = argparse.Namespace(
         problem="sch", potential_type="quantum_chemistry", mol_name=o.mol_name, charge=1.0, ndim=o.ndim, n_particles=1,
-        neigs=o.neigs, laplacian_eps=0.01, operator_scale=1.0, operator_shift=o.operator_shift,
+        neigs=o.neigs, laplacian_eps=0.0 if o.exact else 0.01, operator_scale=1.0, operator_shift=o.operator_shift,
         sampling_mode="gaussian", sampling_scale=o.sampling_scale, batch_size=o.batch_size, lim=o.lim, val_eps=0.5,
         use_fourier_feature=True, fourier_mapping_size=o.fourier_mapping_size, fourier_scale=0.1,
         fourier_deterministic=False, fourier_append_raw=False, mlp_hidden_dims=o.hidden, parallel=1,
         nonlinearity="softplus", apply_exp_mask=1, exp_mask_init_scale=4.0, hard_mul_const=1.0, apply_boundary=0,
         boundary_mode="dir_box_sqrt", sort=0, optimizer="rmsprop", lr=1e-4, rmsprop_decay=0.999, momentum=0.0,
         adam_eps=1e-7, num_iters=o.steps, ema_decay=0.995, use_lr_scheduler=True, print_freq=10 ** 9,
-        eval_freq=10 ** 9, log_dir=None, fused_loop=True, high_dim_stencil=True)
+        eval_freq=10 ** 9, log_dir=None, fused_loop=True, high_dim_stencil=True, generic_exact_laplacian=o.exact)
     a.loss = argparse.Namespace(name="neuralsvd", neuralsvd=argparse.Namespace(step=1, sequential=o.sequential))
     torch.manual_seed(o.seed)
     operator, _ = get_problem(a, dev)
