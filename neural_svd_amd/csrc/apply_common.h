@@ -1,0 +1,255 @@
+// What the matrix-free kernel products share (rbf_apply.hip, dot_apply.hip, rbf_apply_pair.hip, dot_apply_pair.hip;
+// the arena, the slice rule and the tile store also serve kernel_apply.hip): the padding rule and the workspace arena,
+// the prep kernel (pad coordinates, row norms, transposes), the reduce kernels, the maps of the kernel kinds and the
+// pieces of tile_nt.h's layout that every main kernel repeats. Everything has internal linkage: each file gets its own.
+#pragma once
+#include <float.h>
+#include <math.h>
+#include <initializer_list>
+#include "nsvd_kernels.h"
+#include "tile_nt.h"
+
+constexpr int APPLY_MAX_D = 64;  // the model kernels' own input limit
+
+// ---- host: shapes, workspace -----------------------------------------------------------------------------------------
+struct ApplyPad {
+    int B1p, B2p, Dp, Lp;
+};
+
+// rows and heads to whole 64 x 64 tiles, D to the file's granule (4: float4 reads of a row, 8: one b128 per MFMA group)
+static inline ApplyPad apply_pad(int B1, int B2, int D, int L, int granule) {
+    return {nsvd_cdiv(B1, NSVD_TNT_T) * NSVD_TNT_T, nsvd_cdiv(B2, NSVD_TNT_KC) * NSVD_TNT_KC,
+            nsvd_cdiv(D, granule) * granule, nsvd_cdiv(L, NSVD_TNT_T) * NSVD_TNT_T};
+}
+
+// blocks of floats carved from a workspace one after the other, each starting on nsvd_align's boundary
+struct ApplyArena {
+    char* base;
+    size_t off = 0;
+    explicit ApplyArena(void* p) : base((char*)p) {}
+    float* take(size_t n) {
+        float* r = (float*)(base + off);
+        off += nsvd_align(n * sizeof(float));
+        return r;
+    }
+};
+
+// slices of the contraction range of a one-sided product: enough workgroups for two per CU, at least 8 chunks per slice
+static inline int apply_slices(long tiles, int chunks) {
+    int S = 1;
+    while (tiles * S < 512 && chunks / (2 * S) >= 8) S *= 2;
+    return S;
+}
+
+static inline bool apply_shape_ok(int B1, int B2, int D, int L) { return B1 > 0 && B2 > 0 && L > 0 && D > 0; }
+
+static inline bool apply_args_ok(std::initializer_list<const void*> ptrs, int B1, int B2, int D, int L) {
+    for (const void* p : ptrs)
+        if (!p) return false;
+    return apply_shape_ok(B1, B2, D, L);
+}
+
+static inline bool apply_ws_ok(const void* ws, size_t ws_bytes, size_t need) {
+    return ws_bytes >= need && ((uintptr_t)ws & 255) == 0;
+}
+
+// do the float arrays at a (na elements) and b (nb elements) share a byte?
+static inline bool apply_overlap(const float* a, size_t na, const float* b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb * sizeof(float) && pb < pa + na * sizeof(float);
+}
+
+// nsvd_*_apply_pair_partition: carve is the file's own
+template <class Carve>
+static inline int apply_pair_partition(Carve carve, int B1, int B2, int D, int L, int* row_groups, int* col_slices) {
+    if (!apply_args_ok({row_groups, col_slices}, B1, B2, D, L)) return NSVD_EINVAL;
+    if (D > APPLY_MAX_D) return NSVD_EUNSUPPORTED;
+    const auto w = carve(nullptr, B1, B2, D, L);
+    *row_groups = w.RG;
+    *col_slices = w.CG;
+    return 0;
+}
+
+// the exponent's constant of the radial kinds, log2 e / (2 ell^2) (Gaussian) or log2 e / ell (exponential), in double
+// and kept finite: a tiny ell gives exp2(-0 * FLT_MAX) = 1 on the diagonal and 0 elsewhere
+static inline float apply_radial_cexp(int kind, float ell) {
+    const double le = 1.4426950408889634;
+    double cd = kind == NSVD_RBF_GAUSSIAN ? le / (2.0 * (double)ell * (double)ell) : le / (double)ell;
+    if (!(cd < (double)FLT_MAX)) cd = (double)FLT_MAX;
+    return (float)cd;
+}
+
+// raise the dynamic-LDS limit of a file's main-kernel instances; true, to initialise the static that makes it happen once
+static inline bool apply_set_lds_limit(std::initializer_list<const void*> kernels, size_t bytes) {
+    for (const void* k : kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    return true;
+}
+
+// ---- prep ------------------------------------------------------------------------------------------------------------
+// One side of a product: `rows` coordinate rows c (rows, D) and a matrix m (rows, L) that is contracted over them.
+// cP = c zero padded to (ld, Dp), cN = the row norms (0 for padded rows), mT = m^T zero padded to (Lp, ld).
+// c == nullptr: no coordinates to pad; cN == nullptr: no norms. ld == 0: no such side.
+struct ApplyPrepSide {
+    const float* c;
+    float* cP;
+    float* cN;
+    const float* m;
+    float* mT;
+    int rows, ld;
+};
+
+struct ApplyPrep {
+    ApplyPrepSide s[2];
+    int D, Dp, L, Lp;
+    int rooted;  // norms as |c| (1) or |c|^2 (0)
+};
+
+// grid: (s[0].ld / 64 + s[1].ld / 64, Lp / 64 + 1). The first s[0].ld / 64 columns of blocks serve side 0, the others
+// side 1; the last row of blocks pads the coordinates and writes the norms (fmaf over d ascending), the others
+// transpose through a 64 x 64 LDS tile.
+// (the kernels of this header are templates so that a file's code object holds only the ones it launches)
+template <int = 0>
+static __global__ void __launch_bounds__(256) apply_prep_kernel(ApplyPrep p) {
+    __shared__ float tile[64][65];
+    const int t = threadIdx.x;
+    const int nb0 = p.s[0].ld / 64;
+    const bool is0 = (int)blockIdx.x < nb0;
+    const ApplyPrepSide sd = is0 ? p.s[0] : p.s[1];
+    const int j0 = (is0 ? (int)blockIdx.x : (int)blockIdx.x - nb0) * 64;
+    if ((int)blockIdx.y == p.Lp / 64) {
+        if (!sd.c) return;
+        for (int e = t; e < 64 * p.Dp; e += 256) {
+            const int j = j0 + e / p.Dp, d = e % p.Dp;
+            sd.cP[(size_t)j * p.Dp + d] = (j < sd.rows && d < p.D) ? sd.c[(size_t)j * p.D + d] : 0.f;
+        }
+        if (sd.cN && t < 64) {
+            const int j = j0 + t;
+            float s = 0.f;
+            if (j < sd.rows)
+                for (int d = 0; d < p.D; ++d) {
+                    const float v = sd.c[(size_t)j * p.D + d];
+                    s = fmaf(v, v, s);
+                }
+            sd.cN[j] = p.rooted ? __builtin_sqrtf(s) : s;
+        }
+        return;
+    }
+    const int l0 = blockIdx.y * 64;
+    for (int e = t; e < 4096; e += 256) {
+        const int jj = e >> 6, ll = e & 63;  // consecutive threads: consecutive heads of one row
+        tile[jj][ll] = (j0 + jj < sd.rows && l0 + ll < p.L) ? sd.m[(size_t)(j0 + jj) * p.L + l0 + ll] : 0.f;
+    }
+    __syncthreads();
+    for (int e = t; e < 4096; e += 256) {
+        const int ll = e >> 6, jj = e & 63;
+        sd.mT[(size_t)(l0 + ll) * sd.ld + j0 + jj] = tile[jj][ll];
+    }
+}
+
+template <int = 0>
+static inline void apply_prep_launch(const ApplyPrep& p, hipStream_t s) {
+    apply_prep_kernel<><<<dim3(p.s[0].ld / 64 + p.s[1].ld / 64, p.Lp / 64 + 1), 256, 0, s>>>(p);
+}
+
+// ---- reduce ----------------------------------------------------------------------------------------------------------
+// out[i] = scale * (sum of the n partial copies of a (Bp, Lp) matrix at element i of its (B, L) corner), in copy order:
+// no atomics, bit-reproducible
+__device__ __forceinline__ void apply_reduce_one(const float* __restrict__ part, int n, int Bp, int Lp, int L, size_t i,
+                                                 float scale, float* __restrict__ out) {
+    const size_t b = i / L, l = i - b * L;
+    float s = 0.f;
+    for (int c = 0; c < n; ++c) s += part[((size_t)c * Bp + b) * Lp + l];
+    out[i] = scale * s;
+}
+
+template <int = 0>
+static __global__ void __launch_bounds__(256) apply_reduce_kernel(const float* __restrict__ part, int S, int B1p, int Lp,
+                                                                  int B1, int L, float scale, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (size_t)B1 * L) apply_reduce_one(part, S, B1p, Lp, L, i, scale, out);
+}
+
+// both outputs of a two-sided product in one launch: out_x from the CG copies partX, then out_y from the RG copies partY
+template <int = 0>
+static __global__ void __launch_bounds__(256)
+apply_pair_reduce_kernel(const float* __restrict__ partX, int CG, int B1p, const float* __restrict__ partY, int RG, int B2p,
+                         int Lp, int B1, int B2, int L, float scale_g, float scale_f, float* __restrict__ out_x,
+                         float* __restrict__ out_y) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t nx = (size_t)B1 * L, ny = (size_t)B2 * L;
+    if (i < nx)
+        apply_reduce_one(partX, CG, B1p, Lp, L, i, scale_g, out_x);
+    else if (i - nx < ny)
+        apply_reduce_one(partY, RG, B2p, Lp, L, i - nx, scale_f, out_y);
+}
+
+// ---- device: the pieces of a main kernel -----------------------------------------------------------------------------
+// Workgroup barrier that orders LDS only: __syncthreads() would also wait for the global loads in flight (the staging
+// loads that every main kernel issues just before it), and an asm barrier with a memory clobber makes the compiler give
+// up the scalar loads of y (rbf_apply.hip, rbf_apply_pair.hip).
+__device__ __forceinline__ void apply_lds_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// 32 MFMAs of one wave on LDS buffer `b` (A chunk then B chunk, rows of LDT floats): tile_nt.h's read pattern
+__device__ __forceinline__ void apply_chunk_mfma(const float* __restrict__ b, int ra, int rb, int kq, nsvd_f32x16& a0,
+                                                 nsvd_f32x16& a1, nsvd_f32x16& a2, nsvd_f32x16& a3) {
+    constexpr int T = NSVD_TNT_T, KC = NSVD_TNT_KC, LDT = NSVD_TNT_LDT;
+    const float* la = b + ra * LDT + kq;
+    const float* lb = b + T * LDT + rb * LDT + kq;
+    float4 av = *(const float4*)la, bv = *(const float4*)lb;
+#pragma unroll
+    for (int s = 0; s < KC / 8; ++s) {
+        float4 an = av, bn = bv;
+        if (s + 1 < KC / 8) {
+            an = *(const float4*)(la + (s + 1) * 8);
+            bn = *(const float4*)(lb + (s + 1) * 8);
+        }
+        a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, a0, 0, 0, 0);
+        a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, a1, 0, 0, 0);
+        a2 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, a2, 0, 0, 0);
+        a3 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, a3, 0, 0, 0);
+        av = an;
+        bv = bn;
+    }
+}
+
+// the radial kinds from a squared distance: ONE v_exp_f32 per pair (cexp: apply_radial_cexp)
+template <int KIND>
+__device__ __forceinline__ float apply_radial(float d2, float cexp) {
+    const float r = KIND == NSVD_RBF_GAUSSIAN ? d2 : __builtin_sqrtf(d2);
+    return __builtin_amdgcn_exp2f(-(r * cexp));
+}
+
+// (gamma s + coef0)^degree, the power by multiplication: one wave-uniform loop over the degree, 16 independent products
+// inside
+__device__ __forceinline__ nsvd_f32x16 apply_poly(const nsvd_f32x16& sv, float gamma, float coef0, int degree) {
+    nsvd_f32x16 u, pw;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) u[r] = fmaf(gamma, sv[r], coef0);
+    pw = u;
+    for (int d = 1; d < degree; ++d) pw *= u;
+    return pw;
+}
+
+// the arc-cosine map of s = x.y. nx = |x_i| of this lane's row, ny = |y_j|.
+__device__ __forceinline__ float apply_arccos1(float s, float nx, float ny) {
+    const float p = nx * ny;
+    float c = s / p;
+    c = fminf(fmaxf(c, -1.f), 1.f);
+    // sin t and pi - t = acos(-c) from the SAME c (the bracket is stationary at t = 0), neither through t near pi
+    const float sn = __builtin_sqrtf((1.f - c) * (1.f + c));
+    const float br = fmaxf(fmaf(acosf(-c), c, sn), 0.f);
+    const float k = p * (br * 0.318309886183790671538f);
+    return p > 0.f ? k : 0.f;  // a zero row on either side (also c = NaN from 0 / 0)
+}
+
+// Partial-tile store: element r (value v) of a wave's 32 x 32 accumulator, MFMA 32x32 layout, to rows row0.., column
+// col of a matrix with Lp columns. The kernel keeps the unrolled loop over r = 0 .. 15 and reads acc[r] itself: handed
+// the whole accumulator, the compiler keeps the sum of the four chains a vector and rebuilds the main kernel around it.
+__device__ __forceinline__ void apply_store_acc(float* out, int Lp, int row0, int col, int lane, int r, float v) {
+    const int row = row0 + (r >> 2) * 8 + (lane >> 5) * 4 + (r & 3);
+    out[(size_t)row * Lp + col] = v;
+}

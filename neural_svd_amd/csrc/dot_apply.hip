@@ -5,26 +5,23 @@
 // - the sibling of rbf_apply.hip for kernels of the inner product. An inner product has no cancellation to protect
 // (rbf_apply.hip forms distances by direct differences on the VALU for that reason), so x.y goes on the matrix pipe: two
 // contractions back to back, like an attention forward. A workgroup owns 64 rows of x and 64 heads, walks its slice of
-// the reference rows in chunks of 64 (rbf_apply.hip's shape, slice rule and reduce kernel), and per chunk
+// the reference rows in chunks of 64 (rbf_apply.hip's shape; slice rule, prep and reduce kernels: apply_common.h), and
+// per chunk
 //   1. forms S^T = Y_chunk X_tile^T (64 x 64 x Dp) on v_mfma_f32_32x32x2_f32: the y chunk is staged in LDS (two
 //      buffers, its global loads two chunks ahead in registers), the x operand of a wave (32 rows, this lane's half of
 //      every 8 coordinates) is loop invariant and lives in registers, loaded once per workgroup;
-//   2. applies the map to the accumulators in registers. S^T, not S: a lane then owns ONE row i of x (one |x_i|, held
-//      in a register) and 4 runs of 4 consecutive reference rows j, which are 4 ds_write_b128 into the A operand of
-//      the second contraction - S would leave it 16 ds_write_b32;
+//   2. applies the map (apply_poly, apply_arccos1) to the accumulators in registers. S^T, not S: a lane then owns ONE
+//      row i of x (one |x_i|, held in a register) and 4 runs of 4 consecutive reference rows j, which are 4
+//      ds_write_b128 into the A operand of the second contraction - S would leave it 16 ds_write_b32;
 //   3. accumulates against the matching chunk of f^T exactly as rbf_apply.hip does (tile_nt.h's LDS layout and MFMA
-//      read pattern, f^T one chunk ahead in registers, one LDS-only barrier per chunk).
+//      read pattern in apply_chunk_mfma, f^T one chunk ahead in registers, one apply_lds_barrier per chunk).
 // D is padded to a multiple of 8 (one ds_read_b128 per lane feeds 4 MFMAs of k = 2) and the first contraction issues
 // Dp / 2 MFMAs per wave and chunk: 4 at D <= 8, 32 at D = 64, beside the 32 of the second.
-#include <float.h>
-#include <math.h>
-#include "nsvd_kernels.h"
-#include "tile_nt.h"
+#include "apply_common.h"
 
 namespace {
 
 constexpr int T = NSVD_TNT_T, KC = NSVD_TNT_KC, LDT = NSVD_TNT_LDT;
-constexpr int DOT_MAX_D = 64;  // the model kernels' own input limit
 
 struct DotWs {
     float* yP;    // (B2p, Dp) reference coordinates, zero padded
@@ -36,101 +33,23 @@ struct DotWs {
 };
 
 DotWs carve(void* base, int B1, int B2, int D, int L) {
+    const ApplyPad pd = apply_pad(B1, B2, D, L, 8);
     DotWs w;
-    w.B1p = nsvd_cdiv(B1, T) * T;
-    w.B2p = nsvd_cdiv(B2, KC) * KC;
-    w.Dp = nsvd_cdiv(D, 8) * 8;
-    w.Lp = nsvd_cdiv(L, T) * T;
-    // rbf_apply.hip's slice rule: enough workgroups for two per CU, at least 8 chunks per slice
-    const long tiles = (long)(w.B1p / T) * (w.Lp / T);
-    const int chunks = w.B2p / KC;
-    int S = 1;
-    while (tiles * S < 512 && chunks / (2 * S) >= 8) S *= 2;
-    w.S = S;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t n) { float* r = (float*)(p + off); off += nsvd_align(n * sizeof(float)); return r; };
-    w.yP = take((size_t)w.B2p * w.Dp);
-    w.yN = take((size_t)w.B2p);
-    w.fT = take((size_t)w.Lp * w.B2p);
-    w.part = take((size_t)S * w.B1p * w.Lp);
-    w.bytes = off;
+    w.B1p = pd.B1p, w.B2p = pd.B2p, w.Dp = pd.Dp, w.Lp = pd.Lp;
+    w.S = apply_slices((long)(w.B1p / T) * (w.Lp / T), w.B2p / KC);
+    ApplyArena a(base);
+    w.yP = a.take((size_t)w.B2p * w.Dp);
+    w.yN = a.take((size_t)w.B2p);
+    w.fT = a.take((size_t)w.Lp * w.B2p);
+    w.part = a.take((size_t)w.S * w.B1p * w.Lp);
+    w.bytes = a.off;
     return w;
-}
-
-// yP = y zero padded to (B2p, Dp), yN = |y_j|^2; fT = f^T zero padded to (Lp, B2p) through a 64 x 64 LDS tile.
-// grid: (B2p / 64, Lp / 64 + 1); the last y-row of blocks pads y and writes the norms.
-__global__ void __launch_bounds__(256) dot_prep_kernel(const float* __restrict__ y, const float* __restrict__ f, int B2,
-                                                       int D, int L, DotWs w) {
-    __shared__ float tile[64][65];
-    const int t = threadIdx.x, j0 = blockIdx.x * 64;
-    if ((int)blockIdx.y == w.Lp / 64) {
-        for (int e = t; e < 64 * w.Dp; e += 256) {
-            const int j = j0 + e / w.Dp, d = e % w.Dp;
-            w.yP[(size_t)j * w.Dp + d] = (j < B2 && d < D) ? y[(size_t)j * D + d] : 0.f;
-        }
-        if (t < 64) {
-            const int j = j0 + t;
-            float s = 0.f;
-            if (j < B2)
-                for (int d = 0; d < D; ++d) {
-                    const float v = y[(size_t)j * D + d];
-                    s = fmaf(v, v, s);
-                }
-            w.yN[j] = s;
-        }
-        return;
-    }
-    const int l0 = blockIdx.y * 64;
-    for (int e = t; e < 4096; e += 256) {
-        const int jj = e >> 6, ll = e & 63;  // consecutive threads: consecutive heads of one reference row
-        tile[jj][ll] = (j0 + jj < B2 && l0 + ll < L) ? f[(size_t)(j0 + jj) * L + l0 + ll] : 0.f;
-    }
-    __syncthreads();
-    for (int e = t; e < 4096; e += 256) {
-        const int ll = e >> 6, jj = e & 63;
-        w.fT[(size_t)(l0 + ll) * w.B2p + j0 + jj] = tile[jj][ll];
-    }
-}
-
-// 32 MFMAs of one wave on LDS buffer `b` (A chunk then B chunk, rows of LDT floats): tile_nt.h's read pattern
-__device__ __forceinline__ void dot_chunk_mfma(const float* __restrict__ b, int ra, int rb, int kq, nsvd_f32x16& a0,
-                                               nsvd_f32x16& a1, nsvd_f32x16& a2, nsvd_f32x16& a3) {
-    const float* la = b + ra * LDT + kq;
-    const float* lb = b + T * LDT + rb * LDT + kq;
-    float4 av = *(const float4*)la, bv = *(const float4*)lb;
-#pragma unroll
-    for (int s = 0; s < KC / 8; ++s) {
-        float4 an = av, bn = bv;
-        if (s + 1 < KC / 8) {
-            an = *(const float4*)(la + (s + 1) * 8);
-            bn = *(const float4*)(lb + (s + 1) * 8);
-        }
-        a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, a1, 0, 0, 0);
-        a2 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, a2, 0, 0, 0);
-        a3 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, a3, 0, 0, 0);
-        av = an;
-        bv = bn;
-    }
 }
 
 struct DotMap {
     float gamma, coef0;
     int degree;
 };
-
-// the arc-cosine map of s = x.y. nx = |x_i| of this lane's row, ny = |y_j|.
-__device__ __forceinline__ float dot_arccos1(float s, float nx, float ny) {
-    const float p = nx * ny;
-    float c = s / p;
-    c = fminf(fmaxf(c, -1.f), 1.f);
-    // sin t and pi - t = acos(-c) from the SAME c (the bracket is stationary at t = 0), neither through t near pi
-    const float sn = __builtin_sqrtf((1.f - c) * (1.f + c));
-    const float br = fmaxf(fmaf(acosf(-c), c, sn), 0.f);
-    const float k = p * (br * 0.318309886183790671538f);
-    return p > 0.f ? k : 0.f;  // a zero row on either side (also c = NaN from 0 / 0)
-}
 
 // the ds_read_b128 of the y operand for step s of the first contraction, and its 4 MFMAs on two chains
 #define DOT_S_STEP(s)                                                                          \
@@ -227,22 +146,17 @@ __global__ void __launch_bounds__(256, 2) dot_main_kernel(const float* __restric
         // sv[r] = x_i . y_j, i = ib + (lane & 31), j = jb + 8 (r >> 2) + 4 (lane >> 5) + (r & 3)
         float kv[16];
         if (KIND == NSVD_DOT_POLYNOMIAL) {
-            // the power by multiplication: one wave-uniform loop over the degree, 16 independent products inside
-            nsvd_f32x16 u, pw;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) u[r] = fmaf(mp.gamma, sv[r], mp.coef0);
-            pw = u;
-            for (int d = 1; d < mp.degree; ++d) pw *= u;
+            const nsvd_f32x16 pw = apply_poly(sv, mp.gamma, mp.coef0, mp.degree);
 #pragma unroll
             for (int r = 0; r < 16; ++r) kv[r] = pw[r];
         } else {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const float4 ny = *(const float4*)(yb + 64 * yld + jb + 8 * g + kq);
-                kv[4 * g] = dot_arccos1(sv[4 * g], nx, ny.x);
-                kv[4 * g + 1] = dot_arccos1(sv[4 * g + 1], nx, ny.y);
-                kv[4 * g + 2] = dot_arccos1(sv[4 * g + 2], nx, ny.z);
-                kv[4 * g + 3] = dot_arccos1(sv[4 * g + 3], nx, ny.w);
+                kv[4 * g] = apply_arccos1(sv[4 * g], nx, ny.x);
+                kv[4 * g + 1] = apply_arccos1(sv[4 * g + 1], nx, ny.y);
+                kv[4 * g + 2] = apply_arccos1(sv[4 * g + 2], nx, ny.z);
+                kv[4 * g + 3] = apply_arccos1(sv[4 * g + 3], nx, ny.w);
             }
         }
         if (c == chunks - 1) {
@@ -270,67 +184,49 @@ __global__ void __launch_bounds__(256, 2) dot_main_kernel(const float* __restric
         // the y buffer written here was last read in the first contraction of chunk c - 1: before the barrier of c - 1
         DOT_Y_PUT(par ^ 1)
         DOT_Y_LOAD(min(c + 2, c1 - 1))
-        // one barrier per chunk, ordering LDS only (rbf_apply.hip): __syncthreads() would wait for the loads just issued
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-        dot_chunk_mfma(buf, ra, rb, kq, acc0, acc1, acc2, acc3);
+        // one barrier per chunk, ordering LDS only: the loads just issued stay in flight
+        apply_lds_barrier();
+        apply_chunk_mfma(buf, ra, rb, kq, acc0, acc1, acc2, acc3);
     }
     const nsvd_f32x16 acc = (acc0 + acc1) + (acc2 + acc3);
     float* out = w.part + (size_t)slice * w.B1p * w.Lp;
-    const int col = tl * T + (wv >> 1) * 32 + (lane & 31);
+    const int row0 = tb * T + (wv & 1) * 32, col = tl * T + (wv >> 1) * 32 + (lane & 31);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = tb * T + (wv & 1) * 32 + (r >> 2) * 8 + (lane >> 5) * 4 + (r & 3);
-        out[(size_t)row * w.Lp + col] = acc[r];
-    }
+    for (int r = 0; r < 16; ++r) apply_store_acc(out, w.Lp, row0, col, lane, r, acc[r]);
 }
 #undef DOT_S_STEP
 #undef DOT_X_LOAD
 #undef DOT_Y_LOAD
 #undef DOT_Y_PUT
 
-__global__ void __launch_bounds__(256) dot_reduce_kernel(DotWs w, int B1, int L, float scale, float* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)B1 * L) return;
-    const size_t b = i / L, l = i - b * L;
-    float s = 0.f;
-    for (int sl = 0; sl < w.S; ++sl) s += w.part[((size_t)sl * w.B1p + b) * w.Lp + l];
-    out[i] = scale * s;
-}
-
 size_t dot_lds_bytes(int Dp) { return (size_t)(NSVD_TNT_FLOATS + 2 * (64 * (Dp + 4) + 64)) * sizeof(float); }
-
-void dot_set_lds_limit() {
-    static const bool done = [] {
-        const int b = (int)dot_lds_bytes(DOT_MAX_D);
-        (void)hipFuncSetAttribute((const void*)dot_main_kernel<NSVD_DOT_POLYNOMIAL>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-        (void)hipFuncSetAttribute((const void*)dot_main_kernel<NSVD_DOT_ARCCOS1>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-        return true;
-    }();
-    (void)done;
-}
 
 }  // namespace
 
 extern "C" size_t nsvd_dot_apply_workspace_bytes(int B1, int B2, int D, int L) {
-    if (B1 <= 0 || B2 <= 0 || L <= 0 || D <= 0 || D > DOT_MAX_D) return 0;
+    if (!apply_shape_ok(B1, B2, D, L) || D > APPLY_MAX_D) return 0;
     return carve(nullptr, B1, B2, D, L).bytes;
 }
 
 extern "C" int nsvd_dot_apply(const float* x, int B1, const float* y, int B2, int D, const float* f, int L, int kind,
                               float gamma, float coef0, int degree, float scale, float* out, void* ws, size_t ws_bytes,
                               void* stream) {
-    if (!x || !y || !f || !out || !ws || B1 <= 0 || B2 <= 0 || L <= 0 || D <= 0) return NSVD_EINVAL;
+    if (!apply_args_ok({x, y, f, out, ws}, B1, B2, D, L)) return NSVD_EINVAL;
     if (kind != NSVD_DOT_POLYNOMIAL && kind != NSVD_DOT_ARCCOS1) return NSVD_EINVAL;
     if (kind == NSVD_DOT_POLYNOMIAL && (degree < 1 || degree > 8 || !isfinite(gamma) || !isfinite(coef0))) return NSVD_EINVAL;
-    if (D > DOT_MAX_D) return NSVD_EUNSUPPORTED;
+    if (D > APPLY_MAX_D) return NSVD_EUNSUPPORTED;
     const DotWs w = carve(ws, B1, B2, D, L);
-    if (ws_bytes < w.bytes || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
+    if (!apply_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    dot_prep_kernel<<<dim3(w.B2p / 64, w.Lp / 64 + 1), 256, 0, s>>>(y, f, B2, D, L, w);
+    ApplyPrep pr = {};
+    pr.s[0] = {y, w.yP, w.yN, f, w.fT, B2, w.B2p};  // (|y|^2: the main kernel takes the root at staging)
+    pr.D = D, pr.Dp = w.Dp, pr.L = L, pr.Lp = w.Lp;
+    apply_prep_launch(pr, s);
     NSVD_CHECK_LAUNCH();
-    dot_set_lds_limit();
+    static const bool lds_limit_set = apply_set_lds_limit({(const void*)dot_main_kernel<NSVD_DOT_POLYNOMIAL>,
+                                                           (const void*)dot_main_kernel<NSVD_DOT_ARCCOS1>},
+                                                          dot_lds_bytes(APPLY_MAX_D));
+    (void)lds_limit_set;
     const dim3 grid(w.B1p / T, w.Lp / T, w.S);
     const DotMap mp = {gamma, coef0, degree};
     nsvd_prof_begin(s);
@@ -341,7 +237,7 @@ extern "C" int nsvd_dot_apply(const float* x, int B1, const float* y, int B2, in
     nsvd_prof_end(s);
     NSVD_CHECK_LAUNCH();
     const size_t n = (size_t)B1 * L;
-    dot_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(w, B1, L, scale, out);
+    apply_reduce_kernel<><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(w.part, w.S, w.B1p, w.Lp, B1, L, scale, out);
     NSVD_CHECK_LAUNCH();
     return 0;
 }

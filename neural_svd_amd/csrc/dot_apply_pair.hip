@@ -1,11 +1,12 @@
 // Two-sided matrix-free dot-product kernel operator on coordinate batches - both halves of a kernel SVD step in one pass:
 //     out_x[i][l] = scale_g * sum_j k(x_i, y_j) g[j][l]        (B1, L)   "K g"
 //     out_y[j][l] = scale_f * sum_i k(x_i, y_j) f[i][l]        (B2, L)   "K^T f"
-// with the kinds and numerical rules of dot_apply.hip (polynomial by multiplication, order-1 arc-cosine with its clamps).
+// with the kinds and numerical rules of dot_apply.hip (polynomial by multiplication, order-1 arc-cosine with its clamps:
+// apply_poly and apply_arccos1 of apply_common.h).
 // Two nsvd_dot_apply calls with swapped arguments form every x_i . y_j twice on the matrix pipe and run the map twice;
 // here each kernel value is formed ONCE per 64-head tile and feeds both contractions.
 //
-// The workgroup, its runs, the partial copies and the reduce kernel are rbf_apply_pair.hip's: a workgroup (row group,
+// The workgroup, its runs and the partial copies are rbf_apply_pair.hip's (prep and reduce kernels: apply_common.h): a workgroup (row group,
 // head tile, column group) owns a run of 64-row x tiles and a run of slices of at most four 64-row y chunks; per slice
 // it walks its x tiles, the K^T f accumulators of the slice's chunks (4 x 16 registers) staying in registers over the
 // run. The kernel values are dot_apply.hip's: per (x tile, chunk) a step
@@ -24,16 +25,12 @@
 // y chunk = 57.5 KB at D <= 8, 77.5 KB at D = 48 (two workgroups per CU), 85.5 KB at D = 64 (one). 174 / 191 VGPRs, no
 // scratch - by three rules the source keeps: staging loads are unconditional, lane offsets of global
 // addresses are opaque to the compiler (dpair_opaque), and a chain's first MFMA takes an inline zero.
-#include <float.h>
-#include <math.h>
-#include "nsvd_kernels.h"
+#include "apply_common.h"
 #include "pair_split.h"
-#include "tile_nt.h"
 
 namespace {
 
 constexpr int T = NSVD_TNT_T, KC = NSVD_TNT_KC, LDT = NSVD_TNT_LDT;
-constexpr int DPAIR_MAX_D = 64;       // the model kernels' own input limit
 constexpr int DPAIR_TILE = T * LDT;   // one 64 x 64 LDS tile with padded rows
 
 struct DPairWs {
@@ -50,97 +47,27 @@ struct DPairWs {
 };
 
 DPairWs carve(void* base, int B1, int B2, int D, int L) {
+    const ApplyPad pd = apply_pad(B1, B2, D, L, 8);
     DPairWs w;
-    w.B1p = nsvd_cdiv(B1, T) * T;
-    w.B2p = nsvd_cdiv(B2, KC) * KC;
-    w.Dp = nsvd_cdiv(D, 8) * 8;
-    w.Lp = nsvd_cdiv(L, T) * T;
+    w.B1p = pd.B1p, w.B2p = pd.B2p, w.Dp = pd.Dp, w.Lp = pd.Lp;
     pair_split(w.B1p / T, nsvd_cdiv(w.B2p / KC, PAIR_SLICE), w.Lp / T, &w.RG, &w.CG);
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t n) { float* r = (float*)(p + off); off += nsvd_align(n * sizeof(float)); return r; };
-    w.xP = take((size_t)w.B1p * w.Dp);
-    w.xN = take((size_t)w.B1p);
-    w.yP = take((size_t)w.B2p * w.Dp);
-    w.yN = take((size_t)w.B2p);
-    w.gT = take((size_t)w.Lp * w.B2p);
-    w.fT = take((size_t)w.Lp * w.B1p);
-    w.partX = take((size_t)w.CG * w.B1p * w.Lp);
-    w.partY = take((size_t)w.RG * w.B2p * w.Lp);
-    w.bytes = off;
+    ApplyArena a(base);
+    w.xP = a.take((size_t)w.B1p * w.Dp);
+    w.xN = a.take((size_t)w.B1p);
+    w.yP = a.take((size_t)w.B2p * w.Dp);
+    w.yN = a.take((size_t)w.B2p);
+    w.gT = a.take((size_t)w.Lp * w.B2p);
+    w.fT = a.take((size_t)w.Lp * w.B1p);
+    w.partX = a.take((size_t)w.CG * w.B1p * w.Lp);
+    w.partY = a.take((size_t)w.RG * w.B2p * w.Lp);
+    w.bytes = a.off;
     return w;
-}
-
-// xP, yP = x, y zero padded to Dp columns and whole tiles, xN, yN = the row norms; gT = g^T (Lp, B2p) and fT = f^T
-// (Lp, B1p), zero padded, through a 64 x 64 LDS tile. grid: (B2p / 64 + B1p / 64, Lp / 64 + 1): the first B2p / 64
-// columns of blocks serve y and g, the others x and f; the last row of blocks pads the coordinates.
-__global__ void __launch_bounds__(256) dot_pair_prep_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                            const float* __restrict__ g, const float* __restrict__ f,
-                                                            int B1, int B2, int D, int L, DPairWs w) {
-    __shared__ float tile[64][65];
-    const int t = threadIdx.x;
-    const int nb2 = w.B2p / 64;
-    const bool is_g = (int)blockIdx.x < nb2;
-    const int j0 = (is_g ? (int)blockIdx.x : (int)blockIdx.x - nb2) * 64;
-    const int rows = is_g ? B2 : B1;
-    if ((int)blockIdx.y == w.Lp / 64) {
-        const float* src = is_g ? y : x;
-        float* dst = is_g ? w.yP : w.xP;
-        float* nrm = is_g ? w.yN : w.xN;
-        for (int e = t; e < 64 * w.Dp; e += 256) {
-            const int j = j0 + e / w.Dp, d = e % w.Dp;
-            dst[(size_t)j * w.Dp + d] = (j < rows && d < D) ? src[(size_t)j * D + d] : 0.f;
-        }
-        if (t < 64) {
-            const int j = j0 + t;
-            float s = 0.f;
-            if (j < rows)
-                for (int d = 0; d < D; ++d) {
-                    const float v = src[(size_t)j * D + d];
-                    s = fmaf(v, v, s);
-                }
-            nrm[j] = __builtin_sqrtf(s);
-        }
-        return;
-    }
-    const float* src = is_g ? g : f;
-    float* dst = is_g ? w.gT : w.fT;
-    const int ld = is_g ? w.B2p : w.B1p;
-    const int l0 = blockIdx.y * 64;
-    for (int e = t; e < 4096; e += 256) {
-        const int jj = e >> 6, ll = e & 63;  // consecutive threads: consecutive heads of one row
-        tile[jj][ll] = (j0 + jj < rows && l0 + ll < L) ? src[(size_t)(j0 + jj) * L + l0 + ll] : 0.f;
-    }
-    __syncthreads();
-    for (int e = t; e < 4096; e += 256) {
-        const int ll = e >> 6, jj = e & 63;
-        dst[(size_t)(l0 + ll) * ld + j0 + jj] = tile[jj][ll];
-    }
-}
-
-// workgroup barrier that orders LDS only (rbf_apply.hip: __syncthreads() would wait for the global loads in flight)
-__device__ __forceinline__ void dpair_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
 struct DPairMap {
     float gamma, coef0;
     int degree;
 };
-
-// the arc-cosine map of s = x.y (dot_apply.hip's). nx = |x_i| of this lane's row, ny = |y_j|.
-__device__ __forceinline__ float dpair_arccos1(float s, float nx, float ny) {
-    const float p = nx * ny;
-    float c = s / p;
-    c = fminf(fmaxf(c, -1.f), 1.f);
-    // sin t and pi - t = acos(-c) from the SAME c (the bracket is stationary at t = 0), neither through t near pi
-    const float sn = __builtin_sqrtf((1.f - c) * (1.f + c));
-    const float br = fmaxf(fmaf(acosf(-c), c, sn), 0.f);
-    const float k = p * (br * 0.318309886183790671538f);
-    return p > 0.f ? k : 0.f;  // a zero row on either side (also c = NaN from 0 / 0)
-}
 
 // The value, opaque to the compiler: what is computed from it is computed where it is used. Every step of this kernel
 // is inlined four times with loop-invariant operands, and the compiler otherwise forms each lane's 64-bit addresses and
@@ -229,12 +156,7 @@ __device__ __forceinline__ void dpair_step(const DPairLane& p, float* __restrict
     // sv[r] = x_i . y_j, i = rb, j = jb + 8 (r >> 2) + 4 (lane >> 5) + (r & 3)
     float kv[16];
     if (KIND == NSVD_DOT_POLYNOMIAL) {
-        // the power by multiplication: one wave-uniform loop over the degree, 16 independent products inside
-        nsvd_f32x16 u, pw;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) u[r] = fmaf(mp.gamma, sv[r], mp.coef0);
-        pw = u;
-        for (int d = 1; d < mp.degree; ++d) pw *= u;
+        const nsvd_f32x16 pw = apply_poly(sv, mp.gamma, mp.coef0, mp.degree);
 #pragma unroll
         for (int r = 0; r < 16; ++r) kv[r] = pw[r];
     } else {
@@ -242,10 +164,10 @@ __device__ __forceinline__ void dpair_step(const DPairLane& p, float* __restrict
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const float4 ny = *(const float4*)(ys + 64 * p.xld + jb + 8 * g + p.kq);
-            kv[4 * g] = dpair_arccos1(sv[4 * g], nx, ny.x);
-            kv[4 * g + 1] = dpair_arccos1(sv[4 * g + 1], nx, ny.y);
-            kv[4 * g + 2] = dpair_arccos1(sv[4 * g + 2], nx, ny.z);
-            kv[4 * g + 3] = dpair_arccos1(sv[4 * g + 3], nx, ny.w);
+            kv[4 * g] = apply_arccos1(sv[4 * g], nx, ny.x);
+            kv[4 * g + 1] = apply_arccos1(sv[4 * g + 1], nx, ny.y);
+            kv[4 * g + 2] = apply_arccos1(sv[4 * g + 2], nx, ny.z);
+            kv[4 * g + 3] = apply_arccos1(sv[4 * g + 3], nx, ny.w);
         }
     }
     if (xvalid < T || yvalid < KC) {
@@ -265,7 +187,7 @@ __device__ __forceinline__ void dpair_step(const DPairLane& p, float* __restrict
     dpair_load<KIND>(p, ynext, ynnext, yb0, yb1, yb2, yb3, ynb);
     // every wave is done with the previous step's kernel chunk, g^T chunk and f^T tile, and with this step's x tile and
     // y chunk
-    dpair_barrier();
+    apply_lds_barrier();
     float* la = ks + p.rb * LDT + jb + p.kq;
 #pragma unroll
     for (int g = 0; g < 4; ++g)
@@ -299,7 +221,7 @@ __device__ __forceinline__ void dpair_step(const DPairLane& p, float* __restrict
         dpair_load<KIND>(p, xnext, xnnext, x0, x1, x2, x3, xn);
         dpair_put<KIND>(p, xs, x0, x1, x2, x3, xn);
     }
-    dpair_barrier();
+    apply_lds_barrier();
     // K g: rows = x rows (b128 along y), columns = heads of g^T;  K^T f: rows = y rows (b32 down the x rows of the same
     // copy), columns = heads of f^T. MFMA e of group s contracts k = 8 s + e (lanes 0-31) and 8 s + 4 + e (lanes 32-63).
     const float* pa = ks + p.ra * LDT + p.kq;
@@ -436,86 +358,47 @@ __global__ void __launch_bounds__(256, 2) dot_pair_main_kernel(int B1, int B2, D
     }
 }
 
-// out_x = scale_g * sum over column groups, out_y = scale_f * sum over row groups, in group order
-__global__ void __launch_bounds__(256) dot_pair_reduce_kernel(DPairWs w, int B1, int B2, int L, float scale_g,
-                                                              float scale_f, float* __restrict__ out_x,
-                                                              float* __restrict__ out_y) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t nx = (size_t)B1 * L, ny = (size_t)B2 * L;
-    if (i < nx) {
-        const size_t b = i / L, l = i - b * L;
-        float s = 0.f;
-        for (int c = 0; c < w.CG; ++c) s += w.partX[((size_t)c * w.B1p + b) * w.Lp + l];
-        out_x[i] = scale_g * s;
-        return;
-    }
-    i -= nx;
-    if (i >= ny) return;
-    const size_t b = i / L, l = i - b * L;
-    float s = 0.f;
-    for (int r = 0; r < w.RG; ++r) s += w.partY[((size_t)r * w.B2p + b) * w.Lp + l];
-    out_y[i] = scale_f * s;
-}
-
 size_t dpair_lds_bytes(int Dp) { return (size_t)(3 * DPAIR_TILE + 2 * (64 * (Dp + 4) + 64)) * sizeof(float); }
-
-void dpair_set_lds_limit() {
-    static const bool done = [] {
-        const int b = (int)dpair_lds_bytes(DPAIR_MAX_D);
-        (void)hipFuncSetAttribute((const void*)dot_pair_main_kernel<NSVD_DOT_POLYNOMIAL>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, b);
-        (void)hipFuncSetAttribute((const void*)dot_pair_main_kernel<NSVD_DOT_ARCCOS1>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, b);
-        return true;
-    }();
-    (void)done;
-}
-
-bool dpair_shape_ok(int B1, int B2, int D, int L) { return B1 > 0 && B2 > 0 && L > 0 && D > 0 && D <= DPAIR_MAX_D; }
-
-// do the (B, L) float matrices at a and b share a byte?
-bool dpair_overlap(const float* a, size_t na, const float* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb * sizeof(float) && pb < pa + na * sizeof(float);
-}
 
 }  // namespace
 
 extern "C" size_t nsvd_dot_apply_pair_workspace_bytes(int B1, int B2, int D, int L) {
-    if (!dpair_shape_ok(B1, B2, D, L)) return 0;
+    if (!apply_shape_ok(B1, B2, D, L) || D > APPLY_MAX_D) return 0;
     return carve(nullptr, B1, B2, D, L).bytes;
 }
 
 extern "C" int nsvd_dot_apply_pair_partition(int B1, int B2, int D, int L, int* row_groups, int* col_slices) {
-    if (!row_groups || !col_slices || B1 <= 0 || B2 <= 0 || L <= 0 || D <= 0) return NSVD_EINVAL;
-    if (D > DPAIR_MAX_D) return NSVD_EUNSUPPORTED;
-    const DPairWs w = carve(nullptr, B1, B2, D, L);
-    *row_groups = w.RG;
-    *col_slices = w.CG;
-    return 0;
+    return apply_pair_partition(carve, B1, B2, D, L, row_groups, col_slices);
 }
 
 extern "C" int nsvd_dot_apply_pair(const float* x, int B1, const float* y, int B2, int D, const float* g, const float* f,
                                    int L, int kind, float gamma, float coef0, int degree, float scale_g, float scale_f,
                                    float* out_x, float* out_y, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !y || !g || !f || !out_x || !out_y || !ws || B1 <= 0 || B2 <= 0 || L <= 0 || D <= 0) return NSVD_EINVAL;
+    if (!apply_args_ok({x, y, g, f, out_x, out_y, ws}, B1, B2, D, L)) return NSVD_EINVAL;
     if (kind != NSVD_DOT_POLYNOMIAL && kind != NSVD_DOT_ARCCOS1) return NSVD_EINVAL;
     if (kind == NSVD_DOT_POLYNOMIAL && (degree < 1 || degree > 8 || !isfinite(gamma) || !isfinite(coef0))) return NSVD_EINVAL;
     const size_t nox = (size_t)B1 * L, noy = (size_t)B2 * L;
-    if (dpair_overlap(out_x, nox, out_y, noy)) return NSVD_EINVAL;
+    if (apply_overlap(out_x, nox, out_y, noy)) return NSVD_EINVAL;
     for (float* o : {out_x, out_y}) {  // the outputs alias nothing
         const size_t no = o == out_x ? nox : noy;
-        if (dpair_overlap(o, no, x, (size_t)B1 * D) || dpair_overlap(o, no, y, (size_t)B2 * D) ||
-            dpair_overlap(o, no, g, noy) || dpair_overlap(o, no, f, nox))
+        if (apply_overlap(o, no, x, (size_t)B1 * D) || apply_overlap(o, no, y, (size_t)B2 * D) ||
+            apply_overlap(o, no, g, noy) || apply_overlap(o, no, f, nox))
             return NSVD_EINVAL;
     }
-    if (D > DPAIR_MAX_D) return NSVD_EUNSUPPORTED;
+    if (D > APPLY_MAX_D) return NSVD_EUNSUPPORTED;
     const DPairWs w = carve(ws, B1, B2, D, L);
-    if (ws_bytes < w.bytes || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
+    if (!apply_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    dot_pair_prep_kernel<<<dim3(w.B2p / 64 + w.B1p / 64, w.Lp / 64 + 1), 256, 0, s>>>(x, y, g, f, B1, B2, D, L, w);
+    ApplyPrep pr = {};
+    pr.s[0] = {y, w.yP, w.yN, g, w.gT, B2, w.B2p};
+    pr.s[1] = {x, w.xP, w.xN, f, w.fT, B1, w.B1p};
+    pr.D = D, pr.Dp = w.Dp, pr.L = L, pr.Lp = w.Lp, pr.rooted = 1;
+    apply_prep_launch(pr, s);
     NSVD_CHECK_LAUNCH();
-    dpair_set_lds_limit();
+    static const bool lds_limit_set = apply_set_lds_limit({(const void*)dot_pair_main_kernel<NSVD_DOT_POLYNOMIAL>,
+                                                           (const void*)dot_pair_main_kernel<NSVD_DOT_ARCCOS1>},
+                                                          dpair_lds_bytes(APPLY_MAX_D));
+    (void)lds_limit_set;
     const dim3 grid(w.RG, w.Lp / T, w.CG);
     const DPairMap mp = {gamma, coef0, degree};
     nsvd_prof_begin(s);
@@ -526,7 +409,8 @@ extern "C" int nsvd_dot_apply_pair(const float* x, int B1, const float* y, int B
     nsvd_prof_end(s);
     NSVD_CHECK_LAUNCH();
     const size_t n = (size_t)(B1 + (size_t)B2) * L;
-    dot_pair_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(w, B1, B2, L, scale_g, scale_f, out_x, out_y);
+    apply_pair_reduce_kernel<><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(
+        w.partX, w.CG, w.B1p, w.partY, w.RG, w.B2p, w.Lp, B1, B2, L, scale_g, scale_f, out_x, out_y);
     NSVD_CHECK_LAUNCH();
     return 0;
 }

@@ -10,8 +10,7 @@
 // partial tiles reduced in slice order; the scatter adds duplicates in batch order (ka_scatter_blocks_kernel: no
 // atomics), so the result is bit-reproducible whatever the indices.
 #include <string.h>
-#include "nsvd_kernels.h"
-#include "tile_nt.h"
+#include "apply_common.h"
 #include "tile128_dma.h"
 
 namespace {
@@ -44,16 +43,13 @@ KaWs carve(void* base, int N, int B1, int L) {
         const int tiles = (w.B1p / 128) * (w.Lp / T), chunks32 = w.Np / 32;
         while (tiles * S < 512 && chunks32 / (2 * S) >= 16) S *= 2;
     } else {
-        const int tiles = (w.B1p / T) * (w.Lp / T), chunks = w.Np / KC;
-        while (tiles * S < 512 && chunks / (2 * S) >= 8) S *= 2;  // enough blocks for two per CU, >= 8 chunks per slice
+        S = apply_slices((long)(w.B1p / T) * (w.Lp / T), w.Np / KC);
     }
     w.S = S;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t n) { float* r = (float*)(p + off); off += nsvd_align(n * sizeof(float)); return r; };
-    w.ST = take((size_t)w.Lp * w.Np);
-    w.part = take((size_t)S * w.B1p * w.Lp);
-    w.bytes = off;
+    ApplyArena a(base);
+    w.ST = a.take((size_t)w.Lp * w.Np);
+    w.part = a.take((size_t)S * w.B1p * w.Lp);
+    w.bytes = a.off;
     return w;
 }
 
@@ -183,12 +179,9 @@ __global__ void __launch_bounds__(256, 2) ka_gemm_kernel(const float* __restrict
                              w.Np, c1 - c0, lds, acc, unused);
     const int lane = t & 63, wv = t >> 6;
     float* out = w.part + (size_t)slice * w.B1p * w.Lp;
-    const int col = tl * T + (wv >> 1) * 32 + (lane & 31);
+    const int row0 = tb * T + (wv & 1) * 32, col = tl * T + (wv >> 1) * 32 + (lane & 31);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = tb * T + (wv & 1) * 32 + (r >> 2) * 8 + (lane >> 5) * 4 + (r & 3);
-        out[(size_t)row * w.Lp + col] = acc[r];
-    }
+    for (int r = 0; r < 16; ++r) apply_store_acc(out, w.Lp, row0, col, lane, r, acc[r]);
 }
 
 // the same contraction on 128 x 64 tiles with both operands by LDS-DMA (tile128_dma.h, gathered A rows): no staging

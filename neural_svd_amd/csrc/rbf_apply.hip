@@ -12,20 +12,19 @@
 //      their coordinates are read through the scalar cache and cost no LDS bandwidth;
 //   2. applies the exponential as ONE v_exp_f32 per pair (exp2 with log2 e / (2 ell^2), or log2 e / ell, folded in);
 //   3. writes the chunk into LDS as the A operand in tile_nt.h's layout (rows of 64 + 4 floats: conflict-free b128);
-//   4. accumulates against the matching chunk of f^T (K-contiguous after rbf_prep_kernel's transpose, staged like
+//   4. accumulates against the matching chunk of f^T (K-contiguous after apply_prep_kernel's transpose, staged like
 //      tile_nt.h's B operand) on v_mfma_f32_32x32x2_f32, four accumulation chains as in tile_nt.h.
 // tile_nt.h's routine itself stages BOTH operands from global memory, which is exactly what must not happen to the
 // kernel matrix; its LDS layout, wave-to-tile map and MFMA read pattern are kept so that the two stay comparable.
 // The reference rows are split into slices so that the grid fills the chip at small B1; partial tiles are reduced in
-// slice order by rbf_reduce_kernel: no atomics, bit-reproducible.
-#include <float.h>
-#include "nsvd_kernels.h"
-#include "tile_nt.h"
+// slice order by apply_reduce_kernel: no atomics, bit-reproducible. What this file shares with dot_apply.hip and the two
+// *_apply_pair.hip (padding and arena, slice rule, prep and reduce kernels, LDS-only barrier, chunk MFMAs, the radial
+// map) is apply_common.h's.
+#include "apply_common.h"
 
 namespace {
 
 constexpr int T = NSVD_TNT_T, KC = NSVD_TNT_KC, LDT = NSVD_TNT_LDT;
-constexpr int RBF_MAX_D = 64;  // the model kernels' own input limit
 
 struct RbfWs {
     float* yP;    // (B2p, Dp) reference coordinates, zero padded (padded coordinates add 0 to every distance)
@@ -36,72 +35,16 @@ struct RbfWs {
 };
 
 RbfWs carve(void* base, int B1, int B2, int D, int L) {
+    const ApplyPad pd = apply_pad(B1, B2, D, L, 4);
     RbfWs w;
-    w.B1p = nsvd_cdiv(B1, T) * T;
-    w.B2p = nsvd_cdiv(B2, KC) * KC;
-    w.Dp = nsvd_cdiv(D, 4) * 4;
-    w.Lp = nsvd_cdiv(L, T) * T;
-    // enough workgroups for two per CU, at least 8 chunks per slice (the rule of kernel_apply.hip)
-    const long tiles = (long)(w.B1p / T) * (w.Lp / T);
-    const int chunks = w.B2p / KC;
-    int S = 1;
-    while (tiles * S < 512 && chunks / (2 * S) >= 8) S *= 2;
-    w.S = S;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t n) { float* r = (float*)(p + off); off += nsvd_align(n * sizeof(float)); return r; };
-    w.yP = take((size_t)w.B2p * w.Dp);
-    w.fT = take((size_t)w.Lp * w.B2p);
-    w.part = take((size_t)S * w.B1p * w.Lp);
-    w.bytes = off;
+    w.B1p = pd.B1p, w.B2p = pd.B2p, w.Dp = pd.Dp, w.Lp = pd.Lp;
+    w.S = apply_slices((long)(w.B1p / T) * (w.Lp / T), w.B2p / KC);
+    ApplyArena a(base);
+    w.yP = a.take((size_t)w.B2p * w.Dp);
+    w.fT = a.take((size_t)w.Lp * w.B2p);
+    w.part = a.take((size_t)w.S * w.B1p * w.Lp);
+    w.bytes = a.off;
     return w;
-}
-
-// yP = y zero padded to (B2p, Dp); fT = f^T zero padded to (Lp, B2p) through a 64 x 64 LDS tile.
-// grid: (B2p / 64, Lp / 64 + 1); the last y-row of blocks pads y.
-__global__ void __launch_bounds__(256) rbf_prep_kernel(const float* __restrict__ y, const float* __restrict__ f, int B2,
-                                                       int D, int L, RbfWs w) {
-    __shared__ float tile[64][65];
-    const int t = threadIdx.x, j0 = blockIdx.x * 64;
-    if ((int)blockIdx.y == w.Lp / 64) {
-        for (int e = t; e < 64 * w.Dp; e += 256) {
-            const int j = j0 + e / w.Dp, d = e % w.Dp;
-            w.yP[(size_t)j * w.Dp + d] = (j < B2 && d < D) ? y[(size_t)j * D + d] : 0.f;
-        }
-        return;
-    }
-    const int l0 = blockIdx.y * 64;
-    for (int e = t; e < 4096; e += 256) {
-        const int jj = e >> 6, ll = e & 63;  // consecutive threads: consecutive heads of one reference row
-        tile[jj][ll] = (j0 + jj < B2 && l0 + ll < L) ? f[(size_t)(j0 + jj) * L + l0 + ll] : 0.f;
-    }
-    __syncthreads();
-    for (int e = t; e < 4096; e += 256) {
-        const int ll = e >> 6, jj = e & 63;
-        w.fT[(size_t)(l0 + ll) * w.B2p + j0 + jj] = tile[jj][ll];
-    }
-}
-
-// 32 MFMAs of one wave on LDS buffer `b` (A chunk then B chunk, rows of LDT floats): tile_nt.h's read pattern
-__device__ __forceinline__ void rbf_chunk_mfma(const float* __restrict__ b, int ra, int rb, int kq, nsvd_f32x16& a0,
-                                               nsvd_f32x16& a1, nsvd_f32x16& a2, nsvd_f32x16& a3) {
-    const float* la = b + ra * LDT + kq;
-    const float* lb = b + T * LDT + rb * LDT + kq;
-    float4 av = *(const float4*)la, bv = *(const float4*)lb;
-#pragma unroll
-    for (int s = 0; s < KC / 8; ++s) {
-        float4 an = av, bn = bv;
-        if (s + 1 < KC / 8) {
-            an = *(const float4*)(la + (s + 1) * 8);
-            bn = *(const float4*)(lb + (s + 1) * 8);
-        }
-        a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, a1, 0, 0, 0);
-        a2 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, a2, 0, 0, 0);
-        a3 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, a3, 0, 0, 0);
-        av = an;
-        bv = bn;
-    }
 }
 
 // tile (tb, tl) x slice. LDS: two buffers of [A chunk | B chunk] (NSVD_TNT_FLOATS), then the x tile (64, Dp + 4).
@@ -155,10 +98,7 @@ __global__ void __launch_bounds__(256, 2) rbf_main_kernel(const float* __restric
         }
         float kv[16];
 #pragma unroll
-        for (int jj = 0; jj < 16; ++jj) {
-            const float r = KIND == NSVD_RBF_GAUSSIAN ? d2[jj] : __builtin_sqrtf(d2[jj]);
-            kv[jj] = __builtin_amdgcn_exp2f(-(r * cexp));
-        }
+        for (int jj = 0; jj < 16; ++jj) kv[jj] = apply_radial<KIND>(d2[jj], cexp);
         float* la = buf + lane * LDT + 16 * wv;
 #pragma unroll
         for (int i = 0; i < 4; ++i) *(float4*)(la + 4 * i) = make_float4(kv[4 * i], kv[4 * i + 1], kv[4 * i + 2], kv[4 * i + 3]);
@@ -174,77 +114,55 @@ __global__ void __launch_bounds__(256, 2) rbf_main_kernel(const float* __restric
         fb2 = *(const float4*)(fc + 2 * fr);
         fb3 = *(const float4*)(fc + 3 * fr);
         // one barrier per chunk: the buffer written next is the one every wave finished reading before THIS barrier
-        // (a workgroup barrier that orders LDS only: __syncthreads() would wait for the global loads just issued, and an
-        // asm barrier with a memory clobber makes the compiler give up the scalar loads of y)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-        rbf_chunk_mfma(buf, ra, rb, kq, acc0, acc1, acc2, acc3);
+        // (LDS only: the global loads just issued stay in flight)
+        apply_lds_barrier();
+        apply_chunk_mfma(buf, ra, rb, kq, acc0, acc1, acc2, acc3);
     }
     const nsvd_f32x16 acc = (acc0 + acc1) + (acc2 + acc3);
     float* out = w.part + (size_t)slice * w.B1p * w.Lp;
-    const int col = tl * T + (wv >> 1) * 32 + (lane & 31);
+    const int row0 = tb * T + (wv & 1) * 32, col = tl * T + (wv >> 1) * 32 + (lane & 31);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = tb * T + (wv & 1) * 32 + (r >> 2) * 8 + (lane >> 5) * 4 + (r & 3);
-        out[(size_t)row * w.Lp + col] = acc[r];
-    }
-}
-
-__global__ void __launch_bounds__(256) rbf_reduce_kernel(RbfWs w, int B1, int L, float scale, float* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)B1 * L) return;
-    const size_t b = i / L, l = i - b * L;
-    float s = 0.f;
-    for (int sl = 0; sl < w.S; ++sl) s += w.part[((size_t)sl * w.B1p + b) * w.Lp + l];
-    out[i] = scale * s;
+    for (int r = 0; r < 16; ++r) apply_store_acc(out, w.Lp, row0, col, lane, r, acc[r]);
 }
 
 size_t rbf_lds_bytes(int Dp) { return (size_t)(NSVD_TNT_FLOATS + 64 * (Dp + 4)) * sizeof(float); }
 
-void rbf_set_lds_limit() {
-    static const bool done = [] {
-        const int b = (int)rbf_lds_bytes(RBF_MAX_D);
-        (void)hipFuncSetAttribute((const void*)rbf_main_kernel<NSVD_RBF_GAUSSIAN>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-        (void)hipFuncSetAttribute((const void*)rbf_main_kernel<NSVD_RBF_EXPONENTIAL>, hipFuncAttributeMaxDynamicSharedMemorySize, b);
-        return true;
-    }();
-    (void)done;
-}
-
 }  // namespace
 
 extern "C" size_t nsvd_rbf_apply_workspace_bytes(int B1, int B2, int D, int L) {
-    if (B1 <= 0 || B2 <= 0 || L <= 0 || D <= 0 || D > RBF_MAX_D) return 0;
+    if (!apply_shape_ok(B1, B2, D, L) || D > APPLY_MAX_D) return 0;
     return carve(nullptr, B1, B2, D, L).bytes;
 }
 
 extern "C" int nsvd_rbf_apply(const float* x, int B1, const float* y, int B2, int D, const float* f, int L, int kind,
                               float ell, float scale, float* out, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !y || !f || !out || !ws || B1 <= 0 || B2 <= 0 || L <= 0 || D <= 0) return NSVD_EINVAL;
+    if (!apply_args_ok({x, y, f, out, ws}, B1, B2, D, L)) return NSVD_EINVAL;
     if (kind != NSVD_RBF_GAUSSIAN && kind != NSVD_RBF_EXPONENTIAL) return NSVD_EINVAL;
     if (!(ell > 0.f)) return NSVD_EINVAL;  // (also NaN)
-    if (D > RBF_MAX_D) return NSVD_EUNSUPPORTED;
+    if (D > APPLY_MAX_D) return NSVD_EUNSUPPORTED;
     const RbfWs w = carve(ws, B1, B2, D, L);
-    if (ws_bytes < w.bytes || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
-    // the exponent's constant in double, kept finite: a tiny ell gives exp2(-0 * FLT_MAX) = 1 on the diagonal and 0 elsewhere
-    const double le = 1.4426950408889634;
-    double cd = kind == NSVD_RBF_GAUSSIAN ? le / (2.0 * (double)ell * (double)ell) : le / (double)ell;
-    if (!(cd < (double)FLT_MAX)) cd = (double)FLT_MAX;
+    if (!apply_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
+    const float cexp = apply_radial_cexp(kind, ell);
     hipStream_t s = (hipStream_t)stream;
-    rbf_prep_kernel<<<dim3(w.B2p / 64, w.Lp / 64 + 1), 256, 0, s>>>(y, f, B2, D, L, w);
+    ApplyPrep pr = {};
+    pr.s[0] = {y, w.yP, nullptr, f, w.fT, B2, w.B2p};
+    pr.D = D, pr.Dp = w.Dp, pr.L = L, pr.Lp = w.Lp;
+    apply_prep_launch(pr, s);
     NSVD_CHECK_LAUNCH();
-    rbf_set_lds_limit();
+    static const bool lds_limit_set = apply_set_lds_limit({(const void*)rbf_main_kernel<NSVD_RBF_GAUSSIAN>,
+                                                           (const void*)rbf_main_kernel<NSVD_RBF_EXPONENTIAL>},
+                                                          rbf_lds_bytes(APPLY_MAX_D));
+    (void)lds_limit_set;
     const dim3 grid(w.B1p / T, w.Lp / T, w.S);
     nsvd_prof_begin(s);
     if (kind == NSVD_RBF_GAUSSIAN)
-        rbf_main_kernel<NSVD_RBF_GAUSSIAN><<<grid, 256, rbf_lds_bytes(w.Dp), s>>>(x, B1, D, w, (float)cd);
+        rbf_main_kernel<NSVD_RBF_GAUSSIAN><<<grid, 256, rbf_lds_bytes(w.Dp), s>>>(x, B1, D, w, cexp);
     else
-        rbf_main_kernel<NSVD_RBF_EXPONENTIAL><<<grid, 256, rbf_lds_bytes(w.Dp), s>>>(x, B1, D, w, (float)cd);
+        rbf_main_kernel<NSVD_RBF_EXPONENTIAL><<<grid, 256, rbf_lds_bytes(w.Dp), s>>>(x, B1, D, w, cexp);
     nsvd_prof_end(s);
     NSVD_CHECK_LAUNCH();
     const size_t n = (size_t)B1 * L;
-    rbf_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(w, B1, L, scale, out);
+    apply_reduce_kernel<><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(w.part, w.S, w.B1p, w.Lp, B1, L, scale, out);
     NSVD_CHECK_LAUNCH();
     return 0;
 }

@@ -18,20 +18,17 @@
 //      in registers over the whole run of x tiles.
 // K g tiles are flushed per x tile into the partial copy of the workgroup's column group (added to what the SAME thread
 // stored for its previous slice: memory only this workgroup touches), K^T f tiles once per slice into the partial copy of
-// its row group. rbf_pair_reduce_kernel adds the copies in group order: no atomics, bit-reproducible, at most
+// its row group. apply_pair_reduce_kernel (apply_common.h) adds the copies in group order: no atomics, bit-reproducible, at most
 // PAIR_MAX_GROUPS copies of either output whatever the shape.
 // LDS is single-buffered (kernel chunk, g^T chunk, f^T tile, x tile: 68 KB at D = 64) so that two workgroups share a CU
 // and one's distances run under the other's MFMAs; two LDS-only barriers per chunk, none for the x tile or the f^T tile
 // (they are rewritten between the two barriers of a chunk, when no wave can be reading them).
-#include <float.h>
-#include "nsvd_kernels.h"
+#include "apply_common.h"
 #include "pair_split.h"
-#include "tile_nt.h"
 
 namespace {
 
 constexpr int T = NSVD_TNT_T, KC = NSVD_TNT_KC, LDT = NSVD_TNT_LDT;
-constexpr int PAIR_MAX_D = 64;       // the model kernels' own input limit
 constexpr int PAIR_TILE = T * LDT;   // one 64 x 64 LDS tile with padded rows
 
 struct PairWs {
@@ -45,64 +42,18 @@ struct PairWs {
 };
 
 PairWs carve(void* base, int B1, int B2, int D, int L) {
+    const ApplyPad pd = apply_pad(B1, B2, D, L, 4);
     PairWs w;
-    w.B1p = nsvd_cdiv(B1, T) * T;
-    w.B2p = nsvd_cdiv(B2, KC) * KC;
-    w.Dp = nsvd_cdiv(D, 4) * 4;
-    w.Lp = nsvd_cdiv(L, T) * T;
+    w.B1p = pd.B1p, w.B2p = pd.B2p, w.Dp = pd.Dp, w.Lp = pd.Lp;
     pair_split(w.B1p / T, nsvd_cdiv(w.B2p / KC, PAIR_SLICE), w.Lp / T, &w.RG, &w.CG);
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t n) { float* r = (float*)(p + off); off += nsvd_align(n * sizeof(float)); return r; };
-    w.yP = take((size_t)w.B2p * w.Dp);
-    w.gT = take((size_t)w.Lp * w.B2p);
-    w.fT = take((size_t)w.Lp * w.B1p);
-    w.partX = take((size_t)w.CG * w.B1p * w.Lp);
-    w.partY = take((size_t)w.RG * w.B2p * w.Lp);
-    w.bytes = off;
+    ApplyArena a(base);
+    w.yP = a.take((size_t)w.B2p * w.Dp);
+    w.gT = a.take((size_t)w.Lp * w.B2p);
+    w.fT = a.take((size_t)w.Lp * w.B1p);
+    w.partX = a.take((size_t)w.CG * w.B1p * w.Lp);
+    w.partY = a.take((size_t)w.RG * w.B2p * w.Lp);
+    w.bytes = a.off;
     return w;
-}
-
-// yP = y zero padded; gT = g^T (Lp, B2p) and fT = f^T (Lp, B1p), zero padded, through a 64 x 64 LDS tile.
-// grid: (B2p / 64 + B1p / 64, Lp / 64 + 1): the first B2p / 64 columns of blocks transpose g (their last row pads y),
-// the others transpose f.
-__global__ void __launch_bounds__(256) rbf_pair_prep_kernel(const float* __restrict__ y, const float* __restrict__ g,
-                                                            const float* __restrict__ f, int B1, int B2, int D, int L,
-                                                            PairWs w) {
-    __shared__ float tile[64][65];
-    const int t = threadIdx.x;
-    const int nb2 = w.B2p / 64;
-    const bool is_g = (int)blockIdx.x < nb2;
-    const int j0 = (is_g ? (int)blockIdx.x : (int)blockIdx.x - nb2) * 64;
-    if ((int)blockIdx.y == w.Lp / 64) {
-        if (!is_g) return;
-        for (int e = t; e < 64 * w.Dp; e += 256) {
-            const int j = j0 + e / w.Dp, d = e % w.Dp;
-            w.yP[(size_t)j * w.Dp + d] = (j < B2 && d < D) ? y[(size_t)j * D + d] : 0.f;
-        }
-        return;
-    }
-    const float* src = is_g ? g : f;
-    float* dst = is_g ? w.gT : w.fT;
-    const int rows = is_g ? B2 : B1, ld = is_g ? w.B2p : w.B1p;
-    const int l0 = blockIdx.y * 64;
-    for (int e = t; e < 4096; e += 256) {
-        const int jj = e >> 6, ll = e & 63;  // consecutive threads: consecutive heads of one row
-        tile[jj][ll] = (j0 + jj < rows && l0 + ll < L) ? src[(size_t)(j0 + jj) * L + l0 + ll] : 0.f;
-    }
-    __syncthreads();
-    for (int e = t; e < 4096; e += 256) {
-        const int ll = e >> 6, jj = e & 63;
-        dst[(size_t)(l0 + ll) * ld + j0 + jj] = tile[jj][ll];
-    }
-}
-
-// workgroup barrier that orders LDS only (rbf_apply.hip: __syncthreads() would wait for the global loads in flight, an
-// asm barrier with a memory clobber makes the compiler give up the scalar loads of y)
-__device__ __forceinline__ void pair_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
 struct PairLane {
@@ -141,12 +92,9 @@ __device__ __forceinline__ void pair_step(const PairLane& p, float* __restrict__
     }
     float kv[16];
 #pragma unroll
-    for (int jj = 0; jj < 16; ++jj) {
-        const float r = KIND == NSVD_RBF_GAUSSIAN ? d2[jj] : __builtin_sqrtf(d2[jj]);
-        kv[jj] = __builtin_amdgcn_exp2f(-(r * cexp));
-    }
+    for (int jj = 0; jj < 16; ++jj) kv[jj] = apply_radial<KIND>(d2[jj], cexp);
     // every wave is done with the previous step's kernel chunk, g^T chunk and f^T tile, and with this step's x tile
-    pair_barrier();
+    apply_lds_barrier();
     float* la = ks + p.lane * LDT + 16 * p.wv;
 #pragma unroll
     for (int i = 0; i < 4; ++i) *(float4*)(la + 4 * i) = make_float4(kv[4 * i], kv[4 * i + 1], kv[4 * i + 2], kv[4 * i + 3]);
@@ -173,7 +121,7 @@ __device__ __forceinline__ void pair_step(const PairLane& p, float* __restrict__
             xs[i * p.xld + d] = (r < B1 && d < D) ? x[(size_t)r * D + d] : 0.f;
         }
     }
-    pair_barrier();
+    apply_lds_barrier();
     // K g: rows = x rows (b128 along y), columns = heads of g^T;  K^T f: rows = y rows (b32 down the x rows of the same
     // copy), columns = heads of f^T. MFMA e of group s contracts k = 8 s + e (lanes 0-31) and 8 s + 4 + e (lanes 32-63).
     const float* pa = ks + p.ra * LDT + p.kq;
@@ -283,86 +231,51 @@ __global__ void __launch_bounds__(256, 2) rbf_pair_main_kernel(const float* __re
     }
 }
 
-// out_x = scale_g * sum over column groups, out_y = scale_f * sum over row groups, in group order
-__global__ void __launch_bounds__(256) rbf_pair_reduce_kernel(PairWs w, int B1, int B2, int L, float scale_g,
-                                                              float scale_f, float* __restrict__ out_x,
-                                                              float* __restrict__ out_y) {
-    size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t nx = (size_t)B1 * L, ny = (size_t)B2 * L;
-    if (i < nx) {
-        const size_t b = i / L, l = i - b * L;
-        float s = 0.f;
-        for (int c = 0; c < w.CG; ++c) s += w.partX[((size_t)c * w.B1p + b) * w.Lp + l];
-        out_x[i] = scale_g * s;
-        return;
-    }
-    i -= nx;
-    if (i >= ny) return;
-    const size_t b = i / L, l = i - b * L;
-    float s = 0.f;
-    for (int r = 0; r < w.RG; ++r) s += w.partY[((size_t)r * w.B2p + b) * w.Lp + l];
-    out_y[i] = scale_f * s;
-}
-
 size_t pair_lds_bytes(int Dp) { return (size_t)(3 * PAIR_TILE + 64 * (Dp + 4)) * sizeof(float); }
-
-void pair_set_lds_limit() {
-    static const bool done = [] {
-        const int b = (int)pair_lds_bytes(PAIR_MAX_D);
-        (void)hipFuncSetAttribute((const void*)rbf_pair_main_kernel<NSVD_RBF_GAUSSIAN>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, b);
-        (void)hipFuncSetAttribute((const void*)rbf_pair_main_kernel<NSVD_RBF_EXPONENTIAL>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, b);
-        return true;
-    }();
-    (void)done;
-}
-
-bool pair_shape_ok(int B1, int B2, int D, int L) { return B1 > 0 && B2 > 0 && L > 0 && D > 0 && D <= PAIR_MAX_D; }
 
 }  // namespace
 
 extern "C" size_t nsvd_rbf_apply_pair_workspace_bytes(int B1, int B2, int D, int L) {
-    if (!pair_shape_ok(B1, B2, D, L)) return 0;
+    if (!apply_shape_ok(B1, B2, D, L) || D > APPLY_MAX_D) return 0;
     return carve(nullptr, B1, B2, D, L).bytes;
 }
 
 extern "C" int nsvd_rbf_apply_pair_partition(int B1, int B2, int D, int L, int* row_groups, int* col_slices) {
-    if (!row_groups || !col_slices || B1 <= 0 || B2 <= 0 || L <= 0 || D <= 0) return NSVD_EINVAL;
-    if (D > PAIR_MAX_D) return NSVD_EUNSUPPORTED;
-    const PairWs w = carve(nullptr, B1, B2, D, L);
-    *row_groups = w.RG;
-    *col_slices = w.CG;
-    return 0;
+    return apply_pair_partition(carve, B1, B2, D, L, row_groups, col_slices);
 }
 
 extern "C" int nsvd_rbf_apply_pair(const float* x, int B1, const float* y, int B2, int D, const float* g, const float* f,
                                    int L, int kind, float ell, float scale_g, float scale_f, float* out_x, float* out_y,
                                    void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !y || !g || !f || !out_x || !out_y || !ws || B1 <= 0 || B2 <= 0 || L <= 0 || D <= 0) return NSVD_EINVAL;
+    if (!apply_args_ok({x, y, g, f, out_x, out_y, ws}, B1, B2, D, L)) return NSVD_EINVAL;
     if (kind != NSVD_RBF_GAUSSIAN && kind != NSVD_RBF_EXPONENTIAL) return NSVD_EINVAL;
     if (!(ell > 0.f)) return NSVD_EINVAL;  // (also NaN)
-    if (D > PAIR_MAX_D) return NSVD_EUNSUPPORTED;
+    if (D > APPLY_MAX_D) return NSVD_EUNSUPPORTED;
     const PairWs w = carve(ws, B1, B2, D, L);
-    if (ws_bytes < w.bytes || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
-    // the exponent's constant in double, kept finite (rbf_apply.hip's)
-    const double le = 1.4426950408889634;
-    double cd = kind == NSVD_RBF_GAUSSIAN ? le / (2.0 * (double)ell * (double)ell) : le / (double)ell;
-    if (!(cd < (double)FLT_MAX)) cd = (double)FLT_MAX;
+    if (!apply_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
+    const float cexp = apply_radial_cexp(kind, ell);
     hipStream_t s = (hipStream_t)stream;
-    rbf_pair_prep_kernel<<<dim3(w.B2p / 64 + w.B1p / 64, w.Lp / 64 + 1), 256, 0, s>>>(y, g, f, B1, B2, D, L, w);
+    ApplyPrep pr = {};
+    pr.s[0] = {y, w.yP, nullptr, g, w.gT, B2, w.B2p};
+    pr.s[1] = {nullptr, nullptr, nullptr, f, w.fT, B1, w.B1p};  // (the main kernel stages x itself)
+    pr.D = D, pr.Dp = w.Dp, pr.L = L, pr.Lp = w.Lp;
+    apply_prep_launch(pr, s);
     NSVD_CHECK_LAUNCH();
-    pair_set_lds_limit();
+    static const bool lds_limit_set = apply_set_lds_limit({(const void*)rbf_pair_main_kernel<NSVD_RBF_GAUSSIAN>,
+                                                           (const void*)rbf_pair_main_kernel<NSVD_RBF_EXPONENTIAL>},
+                                                          pair_lds_bytes(APPLY_MAX_D));
+    (void)lds_limit_set;
     const dim3 grid(w.RG, w.Lp / T, w.CG);
     nsvd_prof_begin(s);
     if (kind == NSVD_RBF_GAUSSIAN)
-        rbf_pair_main_kernel<NSVD_RBF_GAUSSIAN><<<grid, 256, pair_lds_bytes(w.Dp), s>>>(x, B1, D, w, (float)cd);
+        rbf_pair_main_kernel<NSVD_RBF_GAUSSIAN><<<grid, 256, pair_lds_bytes(w.Dp), s>>>(x, B1, D, w, cexp);
     else
-        rbf_pair_main_kernel<NSVD_RBF_EXPONENTIAL><<<grid, 256, pair_lds_bytes(w.Dp), s>>>(x, B1, D, w, (float)cd);
+        rbf_pair_main_kernel<NSVD_RBF_EXPONENTIAL><<<grid, 256, pair_lds_bytes(w.Dp), s>>>(x, B1, D, w, cexp);
     nsvd_prof_end(s);
     NSVD_CHECK_LAUNCH();
     const size_t n = (size_t)(B1 + (size_t)B2) * L;
-    rbf_pair_reduce_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(w, B1, B2, L, scale_g, scale_f, out_x, out_y);
+    apply_pair_reduce_kernel<><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(
+        w.partX, w.CG, w.B1p, w.partY, w.RG, w.B2p, w.Lp, B1, B2, L, scale_g, scale_f, out_x, out_y);
     NSVD_CHECK_LAUNCH();
     return 0;
 }

@@ -321,70 +321,89 @@ void spectrum_accumulate(const at::Tensor& f, const at::Tensor& Tf, const at::Te
              "nsvd_spectrum_accumulate");
 }
 
-// matrix-free radial kernel operator (nsvd_rbf_apply): x (B1, D), y (B2, D), f (B2, L) -> out (B1, L); x may be y
-void rbf_apply(const at::Tensor& x, const at::Tensor& y, const at::Tensor& f, int64_t kind, double ell, double scale,
-               at::Tensor out, at::Tensor ws) {
-    Dev dv;
+// ---- matrix-free kernel products: x (B1, D), y (B2, D), contiguous float32; x may be y -------------------------------
+// the checked shapes and pointers of a one-sided call: f (B2, L) -> out (B1, L)
+struct ApplyArgs {
+    float *x, *y, *f, *out;
+    void* ws;
+    size_t ws_bytes;
+    int B1, B2, D, L;
+};
+
+ApplyArgs apply_args(Dev& dv, const char* name, const at::Tensor& x, const at::Tensor& y, const at::Tensor& f,
+                     at::Tensor& out, at::Tensor& ws) {
     TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && f.dim() == 2 && out.dim() == 2 && y.size(1) == x.size(1) &&
                     f.size(0) == y.size(0) && out.size(0) == x.size(0) && out.size(1) == f.size(1),
-                "rbf_apply: x (B1, D), y (B2, D), f (B2, L), out (B1, L)");
-    float *xp = f32(dv, x, "x"), *yp = f32(dv, y, "y"), *fp = f32(dv, f, "f"), *op = f32(dv, out, "out");
-    void* wp = bytes(dv, ws, "ws");
-    check_rc(nsvd_rbf_apply(xp, (int)x.size(0), yp, (int)y.size(0), (int)x.size(1), fp, (int)f.size(1), (int)kind,
-                            (float)ell, (float)scale, op, wp, (size_t)ws.numel() * ws.element_size(), dv.stream()),
-             "nsvd_rbf_apply");
+                name, ": x (B1, D), y (B2, D), f (B2, L), out (B1, L)");
+    ApplyArgs a;
+    a.x = f32(dv, x, "x"), a.y = f32(dv, y, "y"), a.f = f32(dv, f, "f"), a.out = f32(dv, out, "out");
+    a.ws = bytes(dv, ws, "ws");
+    a.ws_bytes = (size_t)ws.numel() * ws.element_size();
+    a.B1 = (int)x.size(0), a.B2 = (int)y.size(0), a.D = (int)x.size(1), a.L = (int)f.size(1);
+    return a;
 }
 
-// two-sided radial kernel operator (nsvd_rbf_apply_pair): x (B1, D), y (B2, D), g (B2, L), f (B1, L) ->
-// out_x (B1, L) = K g, out_y (B2, L) = K^T f; x may be y and f may be g
-void rbf_apply_pair(const at::Tensor& x, const at::Tensor& y, const at::Tensor& g, const at::Tensor& f, int64_t kind,
-                    double ell, double scale_g, double scale_f, at::Tensor out_x, at::Tensor out_y, at::Tensor ws) {
-    Dev dv;
+// ... of a two-sided call: g (B2, L), f (B1, L) -> out_x (B1, L) = K g, out_y (B2, L) = K^T f; f may be g
+struct ApplyPairArgs {
+    float *x, *y, *g, *f, *out_x, *out_y;
+    void* ws;
+    size_t ws_bytes;
+    int B1, B2, D, L;
+};
+
+ApplyPairArgs apply_pair_args(Dev& dv, const char* name, const at::Tensor& x, const at::Tensor& y, const at::Tensor& g,
+                              const at::Tensor& f, at::Tensor& out_x, at::Tensor& out_y, at::Tensor& ws) {
     TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && g.dim() == 2 && f.dim() == 2 && out_x.dim() == 2 && out_y.dim() == 2 &&
                     y.size(1) == x.size(1) && g.size(0) == y.size(0) && f.size(0) == x.size(0) &&
                     f.size(1) == g.size(1) && out_x.size(0) == x.size(0) && out_x.size(1) == g.size(1) &&
                     out_y.size(0) == y.size(0) && out_y.size(1) == g.size(1),
-                "rbf_apply_pair: x (B1, D), y (B2, D), g (B2, L), f (B1, L), out_x (B1, L), out_y (B2, L)");
-    float *xp = f32(dv, x, "x"), *yp = f32(dv, y, "y"), *gp = f32(dv, g, "g"), *fp = f32(dv, f, "f");
-    float *ox = f32(dv, out_x, "out_x"), *oy = f32(dv, out_y, "out_y");
-    void* wp = bytes(dv, ws, "ws");
-    check_rc(nsvd_rbf_apply_pair(xp, (int)x.size(0), yp, (int)y.size(0), (int)x.size(1), gp, fp, (int)g.size(1), (int)kind,
-                                 (float)ell, (float)scale_g, (float)scale_f, ox, oy, wp,
-                                 (size_t)ws.numel() * ws.element_size(), dv.stream()),
+                name, ": x (B1, D), y (B2, D), g (B2, L), f (B1, L), out_x (B1, L), out_y (B2, L)");
+    ApplyPairArgs a;
+    a.x = f32(dv, x, "x"), a.y = f32(dv, y, "y"), a.g = f32(dv, g, "g"), a.f = f32(dv, f, "f");
+    a.out_x = f32(dv, out_x, "out_x"), a.out_y = f32(dv, out_y, "out_y");
+    a.ws = bytes(dv, ws, "ws");
+    a.ws_bytes = (size_t)ws.numel() * ws.element_size();
+    a.B1 = (int)x.size(0), a.B2 = (int)y.size(0), a.D = (int)x.size(1), a.L = (int)g.size(1);
+    return a;
+}
+
+// radial kernels (nsvd_rbf_apply, nsvd_rbf_apply_pair)
+void rbf_apply(const at::Tensor& x, const at::Tensor& y, const at::Tensor& f, int64_t kind, double ell, double scale,
+               at::Tensor out, at::Tensor ws) {
+    Dev dv;
+    const ApplyArgs a = apply_args(dv, "rbf_apply", x, y, f, out, ws);
+    check_rc(nsvd_rbf_apply(a.x, a.B1, a.y, a.B2, a.D, a.f, a.L, (int)kind, (float)ell, (float)scale, a.out, a.ws,
+                            a.ws_bytes, dv.stream()),
+             "nsvd_rbf_apply");
+}
+
+void rbf_apply_pair(const at::Tensor& x, const at::Tensor& y, const at::Tensor& g, const at::Tensor& f, int64_t kind,
+                    double ell, double scale_g, double scale_f, at::Tensor out_x, at::Tensor out_y, at::Tensor ws) {
+    Dev dv;
+    const ApplyPairArgs a = apply_pair_args(dv, "rbf_apply_pair", x, y, g, f, out_x, out_y, ws);
+    check_rc(nsvd_rbf_apply_pair(a.x, a.B1, a.y, a.B2, a.D, a.g, a.f, a.L, (int)kind, (float)ell, (float)scale_g,
+                                 (float)scale_f, a.out_x, a.out_y, a.ws, a.ws_bytes, dv.stream()),
              "nsvd_rbf_apply_pair");
 }
 
-// matrix-free dot-product kernel operator (nsvd_dot_apply): the same tensors as rbf_apply
+// dot-product kernels (nsvd_dot_apply, nsvd_dot_apply_pair)
 void dot_apply(const at::Tensor& x, const at::Tensor& y, const at::Tensor& f, int64_t kind, double gamma, double coef0,
                int64_t degree, double scale, at::Tensor out, at::Tensor ws) {
     Dev dv;
-    TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && f.dim() == 2 && out.dim() == 2 && y.size(1) == x.size(1) &&
-                    f.size(0) == y.size(0) && out.size(0) == x.size(0) && out.size(1) == f.size(1),
-                "dot_apply: x (B1, D), y (B2, D), f (B2, L), out (B1, L)");
-    float *xp = f32(dv, x, "x"), *yp = f32(dv, y, "y"), *fp = f32(dv, f, "f"), *op = f32(dv, out, "out");
-    void* wp = bytes(dv, ws, "ws");
-    check_rc(nsvd_dot_apply(xp, (int)x.size(0), yp, (int)y.size(0), (int)x.size(1), fp, (int)f.size(1), (int)kind,
-                            (float)gamma, (float)coef0, (int)degree, (float)scale, op, wp,
-                            (size_t)ws.numel() * ws.element_size(), dv.stream()),
+    const ApplyArgs a = apply_args(dv, "dot_apply", x, y, f, out, ws);
+    check_rc(nsvd_dot_apply(a.x, a.B1, a.y, a.B2, a.D, a.f, a.L, (int)kind, (float)gamma, (float)coef0, (int)degree,
+                            (float)scale, a.out, a.ws, a.ws_bytes, dv.stream()),
              "nsvd_dot_apply");
 }
 
-// two-sided dot-product kernel operator (nsvd_dot_apply_pair): the same tensors as rbf_apply_pair
 void dot_apply_pair(const at::Tensor& x, const at::Tensor& y, const at::Tensor& g, const at::Tensor& f, int64_t kind,
                     double gamma, double coef0, int64_t degree, double scale_g, double scale_f, at::Tensor out_x,
                     at::Tensor out_y, at::Tensor ws) {
     Dev dv;
-    TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && g.dim() == 2 && f.dim() == 2 && out_x.dim() == 2 && out_y.dim() == 2 &&
-                    y.size(1) == x.size(1) && g.size(0) == y.size(0) && f.size(0) == x.size(0) &&
-                    f.size(1) == g.size(1) && out_x.size(0) == x.size(0) && out_x.size(1) == g.size(1) &&
-                    out_y.size(0) == y.size(0) && out_y.size(1) == g.size(1),
-                "dot_apply_pair: x (B1, D), y (B2, D), g (B2, L), f (B1, L), out_x (B1, L), out_y (B2, L)");
-    float *xp = f32(dv, x, "x"), *yp = f32(dv, y, "y"), *gp = f32(dv, g, "g"), *fp = f32(dv, f, "f");
-    float *ox = f32(dv, out_x, "out_x"), *oy = f32(dv, out_y, "out_y");
-    void* wp = bytes(dv, ws, "ws");
-    check_rc(nsvd_dot_apply_pair(xp, (int)x.size(0), yp, (int)y.size(0), (int)x.size(1), gp, fp, (int)g.size(1), (int)kind,
-                                 (float)gamma, (float)coef0, (int)degree, (float)scale_g, (float)scale_f, ox, oy, wp,
-                                 (size_t)ws.numel() * ws.element_size(), dv.stream()),
+    const ApplyPairArgs a = apply_pair_args(dv, "dot_apply_pair", x, y, g, f, out_x, out_y, ws);
+    check_rc(nsvd_dot_apply_pair(a.x, a.B1, a.y, a.B2, a.D, a.g, a.f, a.L, (int)kind, (float)gamma, (float)coef0,
+                                 (int)degree, (float)scale_g, (float)scale_f, a.out_x, a.out_y, a.ws, a.ws_bytes,
+                                 dv.stream()),
              "nsvd_dot_apply_pair");
 }
 

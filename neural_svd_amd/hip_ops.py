@@ -832,12 +832,97 @@ def kernel_apply(K: torch.Tensor, N: int, rows: torch.Tensor, cols: torch.Tensor
 RBF_GAUSSIAN, RBF_EXPONENTIAL = 0, 1  # NSVD_RBF_* (include/nsvd.h)
 
 
-def rbf_apply_workspace(B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
-    n = _lib.load().nsvd_rbf_apply_workspace_bytes(int(B1), int(B2), int(D), int(L))
+# ---- matrix-free kernel products (csrc/rbf_apply*.hip, dot_apply*.hip): one body per call shape ----------------------
+def _apply_workspace(name: str, B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
+    """workspace of entry point nsvd_<name>"""
+    n = getattr(_lib.load(), f"nsvd_{name}_workspace_bytes")(int(B1), int(B2), int(D), int(L))
     if n == 0:
-        raise NsvdError(f"nsvd_rbf_apply_workspace_bytes: unsupported shape B1={B1} B2={B2} D={D} L={L} "
+        raise NsvdError(f"nsvd_{name}_workspace_bytes: unsupported shape B1={B1} B2={B2} D={D} L={L} "
                         "(row counts and L >= 1, 1 <= D <= 64)")
     return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _apply_pair_partition(name: str, B1: int, B2: int, D: int, L: int) -> Tuple[int, int]:
+    rg, cs = C.c_int(0), C.c_int(0)
+    check(getattr(_lib.load(), f"nsvd_{name}_partition")(int(B1), int(B2), int(D), int(L), C.byref(rg), C.byref(cs)),
+          f"nsvd_{name}_partition")
+    return rg.value, cs.value
+
+
+def _apply_ws(lib, name: str, B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
+    # (an unsupported shape has no workspace: the entry point itself refuses it, with its own code)
+    n = getattr(lib, f"nsvd_{name}_workspace_bytes")(B1, B2, D, L)
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=device)
+
+
+_RBF_PARAMS, _DOT_PARAMS = (float,), (float, float, int)  # (ell) and (gamma, coef0, degree) as the entry points type them
+
+
+def _apply(name: str, x, y, f, kind: int, params: tuple, ptypes: tuple, scale: float, ws, out) -> torch.Tensor:
+    """the one-sided products: nsvd_<name>(x, y, f, kind, *params, scale) -> out"""
+    for t, n in ((x, "x"), (y, "y"), (f, "f")):
+        if t.dim() != 2:
+            raise NsvdError(f"{name}: {n} must be 2-D")
+    B1, D = x.shape
+    B2, L = f.shape
+    if tuple(y.shape) != (B2, D):
+        raise NsvdError(f"{name}: y must be (len(f), D) with x's D")
+    xp, yp, fp = _ptr(x, "x"), _ptr(y, "y"), _ptr(f, "f")
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty((B1, L), dtype=torch.float32, device=f.device)
+    elif tuple(out.shape) != (B1, L):
+        raise NsvdError(f"{name}: out must be (len(x), L)")
+    op = _ptr(out, "out")
+    if ws is None:
+        ws = _apply_ws(lib, name, B1, B2, D, L, f.device)
+    params = tuple(t(v) for t, v in zip(ptypes, params))
+    if torch_binding() is not None:
+        getattr(_TB, name)(x, y, f, int(kind), *params, float(scale), out, ws)
+        return out
+    rc = getattr(lib, f"nsvd_{name}")(xp, B1, yp, B2, D, fp, L, int(kind), *params, float(scale), op, ws.data_ptr(),
+                                      ws.numel(), _stream())
+    check(rc, f"nsvd_{name}")
+    return out
+
+
+def _apply_pair(name: str, x, y, g, f, kind: int, params: tuple, ptypes: tuple, scale_g: float, scale_f: float, ws,
+                out_x, out_y):
+    """the two-sided products: nsvd_<name>(x, y, g, f, kind, *params, scale_g, scale_f) -> (out_x, out_y)"""
+    for t, n in ((x, "x"), (y, "y"), (g, "g"), (f, "f")):
+        if t.dim() != 2:
+            raise NsvdError(f"{name}: {n} must be 2-D")
+    B1, D = x.shape
+    B2, L = g.shape
+    if tuple(y.shape) != (B2, D):
+        raise NsvdError(f"{name}: y must be (len(g), D) with x's D")
+    if tuple(f.shape) != (B1, L):
+        raise NsvdError(f"{name}: f must be (len(x), L) with g's L")
+    xp, yp, gp, fp = _ptr(x, "x"), _ptr(y, "y"), _ptr(g, "g"), _ptr(f, "f")
+    lib = _lib.load()
+    if out_x is None:
+        out_x = torch.empty((B1, L), dtype=torch.float32, device=g.device)
+    elif tuple(out_x.shape) != (B1, L):
+        raise NsvdError(f"{name}: out_x must be (len(x), L)")
+    if out_y is None:
+        out_y = torch.empty((B2, L), dtype=torch.float32, device=g.device)
+    elif tuple(out_y.shape) != (B2, L):
+        raise NsvdError(f"{name}: out_y must be (len(y), L)")
+    ox, oy = _ptr(out_x, "out_x"), _ptr(out_y, "out_y")
+    if ws is None:
+        ws = _apply_ws(lib, name, B1, B2, D, L, g.device)
+    params = tuple(t(v) for t, v in zip(ptypes, params))
+    if torch_binding() is not None:
+        getattr(_TB, name)(x, y, g, f, int(kind), *params, float(scale_g), float(scale_f), out_x, out_y, ws)
+        return out_x, out_y
+    rc = getattr(lib, f"nsvd_{name}")(xp, B1, yp, B2, D, gp, fp, L, int(kind), *params, float(scale_g), float(scale_f),
+                                      ox, oy, ws.data_ptr(), ws.numel(), _stream())
+    check(rc, f"nsvd_{name}")
+    return out_x, out_y
+
+
+def rbf_apply_workspace(B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
+    return _apply_workspace("rbf_apply", B1, B2, D, L, device)
 
 
 def rbf_apply(x: torch.Tensor, y: torch.Tensor, f: torch.Tensor, kind: int, ell: float, scale: float,
@@ -845,47 +930,17 @@ def rbf_apply(x: torch.Tensor, y: torch.Tensor, f: torch.Tensor, kind: int, ell:
     """out[i] = scale * sum_j k(|x_i - y_j|) f[j] without the (B1, B2) kernel matrix (nsvd_rbf_apply). kind:
     RBF_GAUSSIAN k = exp(-d^2 / (2 ell^2)), RBF_EXPONENTIAL k = exp(-d / ell). x: (B1, D), y: (B2, D), f: (B2, L)
     contiguous float32 on the GPU; x may be y. Returns (B1, L)."""
-    for t, n in ((x, "x"), (y, "y"), (f, "f")):
-        if t.dim() != 2:
-            raise NsvdError(f"rbf_apply: {n} must be 2-D")
-    B1, D = x.shape
-    B2, L = f.shape
-    if tuple(y.shape) != (B2, D):
-        raise NsvdError("rbf_apply: y must be (len(f), D) with x's D")
-    xp, yp, fp = _ptr(x, "x"), _ptr(y, "y"), _ptr(f, "f")
-    lib = _lib.load()
-    if out is None:
-        out = torch.empty((B1, L), dtype=torch.float32, device=f.device)
-    elif tuple(out.shape) != (B1, L):
-        raise NsvdError("rbf_apply: out must be (len(x), L)")
-    op = _ptr(out, "out")
-    if ws is None:
-        # (an unsupported shape has no workspace: the entry point itself refuses it, with its own code)
-        ws = torch.empty(max(lib.nsvd_rbf_apply_workspace_bytes(B1, B2, D, L), 256), dtype=torch.uint8, device=f.device)
-    if torch_binding() is not None:
-        _TB.rbf_apply(x, y, f, int(kind), float(ell), float(scale), out, ws)
-        return out
-    rc = lib.nsvd_rbf_apply(xp, B1, yp, B2, D, fp, L, int(kind), float(ell), float(scale), op, ws.data_ptr(),
-                            ws.numel(), _stream())
-    check(rc, "nsvd_rbf_apply")
-    return out
+    return _apply("rbf_apply", x, y, f, kind, (ell,), _RBF_PARAMS, scale, ws, out)
 
 
 def rbf_apply_pair_workspace(B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
-    n = _lib.load().nsvd_rbf_apply_pair_workspace_bytes(int(B1), int(B2), int(D), int(L))
-    if n == 0:
-        raise NsvdError(f"nsvd_rbf_apply_pair_workspace_bytes: unsupported shape B1={B1} B2={B2} D={D} L={L} "
-                        "(row counts and L >= 1, 1 <= D <= 64)")
-    return torch.empty(n, dtype=torch.uint8, device=device)
+    return _apply_workspace("rbf_apply_pair", B1, B2, D, L, device)
 
 
 def rbf_apply_pair_partition(B1: int, B2: int, D: int, L: int) -> Tuple[int, int]:
     """(row groups, column slices) of an nsvd_rbf_apply_pair call of that shape: the runs of x tiles and of y rows that
     workgroups own = the partial copies of out_y and of out_x that the call reduces. Host only."""
-    rg, cs = C.c_int(0), C.c_int(0)
-    check(_lib.load().nsvd_rbf_apply_pair_partition(int(B1), int(B2), int(D), int(L), C.byref(rg), C.byref(cs)),
-          "nsvd_rbf_apply_pair_partition")
-    return rg.value, cs.value
+    return _apply_pair_partition("rbf_apply_pair", B1, B2, D, L)
 
 
 def rbf_apply_pair(x: torch.Tensor, y: torch.Tensor, g: torch.Tensor, f: torch.Tensor, kind: int, ell: float,
@@ -895,48 +950,14 @@ def rbf_apply_pair(x: torch.Tensor, y: torch.Tensor, g: torch.Tensor, f: torch.T
     out_x[i] = scale_g * sum_j k(|x_i - y_j|) g[j] ("K g", (B1, L)) and out_y[j] = scale_f * sum_i k(|x_i - y_j|) f[i]
     ("K^T f", (B2, L)). kind and ell as rbf_apply. x: (B1, D), y: (B2, D), g: (B2, L), f: (B1, L) contiguous float32 on
     the GPU; x may be y and f may be g. Returns (out_x, out_y)."""
-    for t, n in ((x, "x"), (y, "y"), (g, "g"), (f, "f")):
-        if t.dim() != 2:
-            raise NsvdError(f"rbf_apply_pair: {n} must be 2-D")
-    B1, D = x.shape
-    B2, L = g.shape
-    if tuple(y.shape) != (B2, D):
-        raise NsvdError("rbf_apply_pair: y must be (len(g), D) with x's D")
-    if tuple(f.shape) != (B1, L):
-        raise NsvdError("rbf_apply_pair: f must be (len(x), L) with g's L")
-    xp, yp, gp, fp = _ptr(x, "x"), _ptr(y, "y"), _ptr(g, "g"), _ptr(f, "f")
-    lib = _lib.load()
-    if out_x is None:
-        out_x = torch.empty((B1, L), dtype=torch.float32, device=g.device)
-    elif tuple(out_x.shape) != (B1, L):
-        raise NsvdError("rbf_apply_pair: out_x must be (len(x), L)")
-    if out_y is None:
-        out_y = torch.empty((B2, L), dtype=torch.float32, device=g.device)
-    elif tuple(out_y.shape) != (B2, L):
-        raise NsvdError("rbf_apply_pair: out_y must be (len(y), L)")
-    ox, oy = _ptr(out_x, "out_x"), _ptr(out_y, "out_y")
-    if ws is None:
-        # (an unsupported shape has no workspace: the entry point itself refuses it, with its own code)
-        ws = torch.empty(max(lib.nsvd_rbf_apply_pair_workspace_bytes(B1, B2, D, L), 256), dtype=torch.uint8,
-                         device=g.device)
-    if torch_binding() is not None:
-        _TB.rbf_apply_pair(x, y, g, f, int(kind), float(ell), float(scale_g), float(scale_f), out_x, out_y, ws)
-        return out_x, out_y
-    rc = lib.nsvd_rbf_apply_pair(xp, B1, yp, B2, D, gp, fp, L, int(kind), float(ell), float(scale_g), float(scale_f),
-                                 ox, oy, ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_rbf_apply_pair")
-    return out_x, out_y
+    return _apply_pair("rbf_apply_pair", x, y, g, f, kind, (ell,), _RBF_PARAMS, scale_g, scale_f, ws, out_x, out_y)
 
 
 DOT_POLYNOMIAL, DOT_ARCCOS1 = 0, 1  # NSVD_DOT_* (include/nsvd.h)
 
 
 def dot_apply_workspace(B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
-    n = _lib.load().nsvd_dot_apply_workspace_bytes(int(B1), int(B2), int(D), int(L))
-    if n == 0:
-        raise NsvdError(f"nsvd_dot_apply_workspace_bytes: unsupported shape B1={B1} B2={B2} D={D} L={L} "
-                        "(row counts and L >= 1, 1 <= D <= 64)")
-    return torch.empty(n, dtype=torch.uint8, device=device)
+    return _apply_workspace("dot_apply", B1, B2, D, L, device)
 
 
 def dot_apply(x: torch.Tensor, y: torch.Tensor, f: torch.Tensor, kind: int, gamma: float, coef0: float, degree: int,
@@ -945,47 +966,17 @@ def dot_apply(x: torch.Tensor, y: torch.Tensor, f: torch.Tensor, kind: int, gamm
     DOT_POLYNOMIAL k = (gamma x.y + coef0)^degree (integer degree 1..8), DOT_ARCCOS1 k = |x||y| / pi (sin t +
     (pi - t) cos t) with cos t = x.y / (|x||y|) (gamma, coef0, degree ignored). x: (B1, D), y: (B2, D), f: (B2, L)
     contiguous float32 on the GPU; x may be y. Returns (B1, L)."""
-    for t, n in ((x, "x"), (y, "y"), (f, "f")):
-        if t.dim() != 2:
-            raise NsvdError(f"dot_apply: {n} must be 2-D")
-    B1, D = x.shape
-    B2, L = f.shape
-    if tuple(y.shape) != (B2, D):
-        raise NsvdError("dot_apply: y must be (len(f), D) with x's D")
-    xp, yp, fp = _ptr(x, "x"), _ptr(y, "y"), _ptr(f, "f")
-    lib = _lib.load()
-    if out is None:
-        out = torch.empty((B1, L), dtype=torch.float32, device=f.device)
-    elif tuple(out.shape) != (B1, L):
-        raise NsvdError("dot_apply: out must be (len(x), L)")
-    op = _ptr(out, "out")
-    if ws is None:
-        # (an unsupported shape has no workspace: the entry point itself refuses it, with its own code)
-        ws = torch.empty(max(lib.nsvd_dot_apply_workspace_bytes(B1, B2, D, L), 256), dtype=torch.uint8, device=f.device)
-    if torch_binding() is not None:
-        _TB.dot_apply(x, y, f, int(kind), float(gamma), float(coef0), int(degree), float(scale), out, ws)
-        return out
-    rc = lib.nsvd_dot_apply(xp, B1, yp, B2, D, fp, L, int(kind), float(gamma), float(coef0), int(degree), float(scale),
-                            op, ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_dot_apply")
-    return out
+    return _apply("dot_apply", x, y, f, kind, (gamma, coef0, degree), _DOT_PARAMS, scale, ws, out)
 
 
 def dot_apply_pair_workspace(B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
-    n = _lib.load().nsvd_dot_apply_pair_workspace_bytes(int(B1), int(B2), int(D), int(L))
-    if n == 0:
-        raise NsvdError(f"nsvd_dot_apply_pair_workspace_bytes: unsupported shape B1={B1} B2={B2} D={D} L={L} "
-                        "(row counts and L >= 1, 1 <= D <= 64)")
-    return torch.empty(n, dtype=torch.uint8, device=device)
+    return _apply_workspace("dot_apply_pair", B1, B2, D, L, device)
 
 
 def dot_apply_pair_partition(B1: int, B2: int, D: int, L: int) -> Tuple[int, int]:
     """(row groups, column slices) of an nsvd_dot_apply_pair call of that shape: the runs of x tiles and of y rows that
     workgroups own = the partial copies of out_y and of out_x that the call reduces. Host only."""
-    rg, cs = C.c_int(0), C.c_int(0)
-    check(_lib.load().nsvd_dot_apply_pair_partition(int(B1), int(B2), int(D), int(L), C.byref(rg), C.byref(cs)),
-          "nsvd_dot_apply_pair_partition")
-    return rg.value, cs.value
+    return _apply_pair_partition("dot_apply_pair", B1, B2, D, L)
 
 
 def dot_apply_pair(x: torch.Tensor, y: torch.Tensor, g: torch.Tensor, f: torch.Tensor, kind: int, gamma: float,
@@ -995,38 +986,8 @@ def dot_apply_pair(x: torch.Tensor, y: torch.Tensor, g: torch.Tensor, f: torch.T
     out_x[i] = scale_g * sum_j k(x_i, y_j) g[j] ("K g", (B1, L)) and out_y[j] = scale_f * sum_i k(x_i, y_j) f[i]
     ("K^T f", (B2, L)). kind, gamma, coef0, degree as dot_apply. x: (B1, D), y: (B2, D), g: (B2, L), f: (B1, L)
     contiguous float32 on the GPU; x may be y and f may be g. Returns (out_x, out_y)."""
-    for t, n in ((x, "x"), (y, "y"), (g, "g"), (f, "f")):
-        if t.dim() != 2:
-            raise NsvdError(f"dot_apply_pair: {n} must be 2-D")
-    B1, D = x.shape
-    B2, L = g.shape
-    if tuple(y.shape) != (B2, D):
-        raise NsvdError("dot_apply_pair: y must be (len(g), D) with x's D")
-    if tuple(f.shape) != (B1, L):
-        raise NsvdError("dot_apply_pair: f must be (len(x), L) with g's L")
-    xp, yp, gp, fp = _ptr(x, "x"), _ptr(y, "y"), _ptr(g, "g"), _ptr(f, "f")
-    lib = _lib.load()
-    if out_x is None:
-        out_x = torch.empty((B1, L), dtype=torch.float32, device=g.device)
-    elif tuple(out_x.shape) != (B1, L):
-        raise NsvdError("dot_apply_pair: out_x must be (len(x), L)")
-    if out_y is None:
-        out_y = torch.empty((B2, L), dtype=torch.float32, device=g.device)
-    elif tuple(out_y.shape) != (B2, L):
-        raise NsvdError("dot_apply_pair: out_y must be (len(y), L)")
-    ox, oy = _ptr(out_x, "out_x"), _ptr(out_y, "out_y")
-    if ws is None:
-        # (an unsupported shape has no workspace: the entry point itself refuses it, with its own code)
-        ws = torch.empty(max(lib.nsvd_dot_apply_pair_workspace_bytes(B1, B2, D, L), 256), dtype=torch.uint8,
-                         device=g.device)
-    if torch_binding() is not None:
-        _TB.dot_apply_pair(x, y, g, f, int(kind), float(gamma), float(coef0), int(degree), float(scale_g),
-                           float(scale_f), out_x, out_y, ws)
-        return out_x, out_y
-    rc = lib.nsvd_dot_apply_pair(xp, B1, yp, B2, D, gp, fp, L, int(kind), float(gamma), float(coef0), int(degree),
-                                 float(scale_g), float(scale_f), ox, oy, ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_dot_apply_pair")
-    return out_x, out_y
+    return _apply_pair("dot_apply_pair", x, y, g, f, kind, (gamma, coef0, degree), _DOT_PARAMS, scale_g, scale_f, ws,
+                       out_x, out_y)
 
 
 # ---- the dense side of the Nystrom baseline (csrc/nystrom.hip; the loop is neural_svd_amd/nystrom.py) ---------------
