@@ -118,6 +118,11 @@ class Optimizer(C.Structure):
 
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against include/nsvd.h
 _P, _I, _F, _Z, _Dbl = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_double
+# what the seven EVD-backward entry points begin with: x, B, f, Tf, mask_kind, v, M, moments, moments_reduced,
+# evd_scratch, L_total, l_offset, grad_scale, loss, grads - behind desc, params and (the operator's six) prob
+_EVD_LOSS = [_P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _F, _P, C.POINTER(Params)]
+_EVD = [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem)] + _EVD_LOSS
+_NEXT = [C.c_uint64, C.c_uint64, _P, _P, _Z]  # next_seed, next_offset, x_next, ws_next, ws_next_bytes
 SIGNATURES = {
     "nsvd_abi_version": (_I, []),
     "nsvd_path_name": (C.c_char_p, [C.POINTER(ModelDesc), _I, _I]),
@@ -136,35 +141,22 @@ SIGNATURES = {
                                     C.POINTER(Params), _P, _Z, _I, _P]),
     "nsvd_model_forward": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), _P, _I, _F, _P, _P, _Z, _I, _P]),
     "nsvd_model_backward": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), _P, _I, _P, C.POINTER(Params), _P, _Z, _P]),
-    "nsvd_model_backward_evd_step": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), _P, _I, _P, _P, _I, _P, _P, _P, _I, _P,
-                                          _I, _I, _F, _P, C.POINTER(Params), C.POINTER(Rmsprop), _P, _Z, _P]),
+    "nsvd_model_backward_evd_step": (_I, [C.POINTER(ModelDesc), C.POINTER(Params)] + _EVD_LOSS +
+                                     [C.POINTER(Rmsprop), _P, _Z, _P]),
     "nsvd_evd_scratch_bytes": (_Z, [_I, _I]),
     "nsvd_evd_moments": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "nsvd_evd_loss_grad": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P]),
     "nsvd_evd_partial": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "nsvd_evd_gather_heads": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nsvd_evd_gather_head_blocks": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
-    "nsvd_operator_backward_evd": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem), _P, _I, _P, _P,
-                                        _I, _P, _P, _P, _I, _P, _I, _I, _F, _P, C.POINTER(Params), _P, _Z, _I, _P]),
-    "nsvd_operator_backward_evd_heads": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem), _P, _I, _P,
-                                              _P, _I, _P, _P, _P, _I, _P, _I, _I, _F, _P, C.POINTER(Params), _P, _Z,
-                                              _I, _I, _I, _P]),
+    "nsvd_operator_backward_evd": (_I, _EVD + [_P, _Z, _I, _P]),
+    "nsvd_operator_backward_evd_heads": (_I, _EVD + [_P, _Z, _I, _I, _I, _P]),
     "nsvd_backward_head_window_ok": (_I, [C.POINTER(ModelDesc), C.POINTER(Problem), _I, _I, _I]),
-    "nsvd_operator_backward_evd_step": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem), _P, _I, _P,
-                                             _P, _I, _P, _P, _P, _I, _P, _I, _I, _F, _P, C.POINTER(Params),
-                                             C.POINTER(Rmsprop), _P, _Z, _I, _P]),
-    "nsvd_operator_backward_evd_step_window": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem), _P, _I,
-                                                    _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _F, _P, C.POINTER(Params),
-                                                    C.POINTER(Rmsprop), _P, _Z, _I, _I, _I, _I, _P, C.c_ulonglong,
-                                                    C.c_ulonglong, _P, _P, _Z, _P]),
-    "nsvd_operator_backward_evd_step_next": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem), _P, _I,
-                                                  _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _F, _P, C.POINTER(Params),
-                                                  C.POINTER(Rmsprop), _P, _Z, _I, C.c_uint64, C.c_uint64, _P, _P, _Z,
-                                                  _P]),
-    "nsvd_operator_backward_evd_opt_step": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), C.POINTER(Problem), _P, _I,
-                                                 _P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _F, _P, C.POINTER(Params),
-                                                 C.POINTER(Optimizer), _P, _Z, _I, C.c_uint64, C.c_uint64, _P, _P, _Z,
-                                                 _P]),
+    "nsvd_operator_backward_evd_step": (_I, _EVD + [C.POINTER(Rmsprop), _P, _Z, _I, _P]),
+    "nsvd_operator_backward_evd_step_window": (_I, _EVD + [C.POINTER(Rmsprop), _P, _Z, _I, _I, _I, _I, _P, C.c_ulonglong,
+                                                           C.c_ulonglong] + _NEXT[2:] + [_P]),
+    "nsvd_operator_backward_evd_step_next": (_I, _EVD + [C.POINTER(Rmsprop), _P, _Z, _I] + _NEXT + [_P]),
+    "nsvd_operator_backward_evd_opt_step": (_I, _EVD + [C.POINTER(Optimizer), _P, _Z, _I] + _NEXT + [_P]),
     "nsvd_evd_loss_fused": (_I, [_P, _P, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P]),
     "nsvd_rmsprop_ema_step": (_I, [_P, _P, _P, _P, _Z, _Dbl, _Dbl, _Dbl, _Dbl, _Dbl, _P]),
     "nsvd_step_state_init": (_I, [_P, _Dbl, _Dbl, C.c_uint64, _Dbl, _Dbl, _Dbl, C.c_uint64, _P]),

@@ -122,6 +122,19 @@ bool want_fused(const nsvd_model_desc& d, int B, int path, bool exact = false) {
     return nsvd_fused_supported(d, B, exact);
 }
 
+bool fused_requested(int path) { return path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3; }
+
+bool ws_ok(const void* ws, size_t ws_bytes, size_t need) { return ws_bytes >= need && ((uintptr_t)ws & 255) == 0; }
+
+// what every operator entry point ends its validation with: the workspace is big enough and 256-byte aligned, and an
+// explicitly fused path on a shape the MFMA kernels do not take is refused, never rerouted. *fused: which kernels run
+int resolve_path(const nsvd_model_desc& d, const nsvd_problem& prob, int B, const void* ws, size_t ws_bytes, int path,
+                 bool* fused) {
+    if (!ws_ok(ws, ws_bytes, nsvd_workspace_bytes(&d, B))) return NSVD_EINVAL;
+    *fused = want_fused(d, B, path, !(prob.eps > 0.f));
+    return fused_requested(path) && !*fused ? NSVD_EUNSUPPORTED : 0;
+}
+
 int check_params(const nsvd_model_desc& d, const nsvd_params* p, bool need_fourier) {
     if (!p) return NSVD_EINVAL;
     if (need_fourier && !p->fourier_B) return NSVD_EINVAL;
@@ -258,7 +271,7 @@ extern "C" const char* nsvd_path_name_for(const nsvd_model_desc* desc, const nsv
     const bool exact = !(prob->eps > 0.f);
     if (want_fused(*desc, B, path, exact)) return "fused_mfma";
     // (above NSVD_SMALL_D an explicitly fused path has nothing to fall back to: the entry points return NSVD_EUNSUPPORTED)
-    if (desc->D > NSVD_SMALL_D && (path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3)) return "unsupported";
+    if (desc->D > NSVD_SMALL_D && fused_requested(path)) return "unsupported";
     return exact ? "unsupported" : "generic";
 }
 
@@ -289,10 +302,9 @@ extern "C" int nsvd_operator_forward(const nsvd_model_desc* desc, const nsvd_par
     if (gexact && (rc = generic_exact_status(*prob)) != 0) return rc;
     rc = check_params(*desc, params, true);
     if (rc) return rc;
-    if (ws_bytes < nsvd_workspace_bytes(desc, B)) return NSVD_EINVAL;
-    if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
-    const bool fused = want_fused(*desc, B, path, !(prob->eps > 0.f));
-    if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
+    bool fused;
+    rc = resolve_path(*desc, *prob, B, ws, ws_bytes, path, &fused);
+    if (rc) return rc;
     // eps <= 0 selects the exact Laplacian (reference diff_ops.py:7): forward-mode jets, on the MFMA path or - on
     // explicit request only - on the generic kernels
     if (!(prob->eps > 0.f) && !fused && !gexact) return NSVD_EUNSUPPORTED;
@@ -310,7 +322,7 @@ extern "C" int nsvd_operator_forward(const nsvd_model_desc* desc, const nsvd_par
 int nsvd_operator_forward_raw(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
                               int B, void* ws, int path, hipStream_t s, NsvdRawOut* out) {
     const bool fused = want_fused(d, B, path, !(prob.eps > 0.f));
-    if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
+    if (fused_requested(path) && !fused) return NSVD_EUNSUPPORTED;
     if (path == NSVD_PATH_FUSED_BF16X3 || !(prob.eps > 0.f)) return NSVD_EUNSUPPORTED;
     if (generic_exact(path)) return NSVD_EUNSUPPORTED;  // (no NeuralEF on the generic jets, and no stencil on that path)
     // the per-point batch norms know neither the box mask nor the uniform density
@@ -341,10 +353,9 @@ extern "C" int nsvd_operator_features(const nsvd_model_desc* desc, const nsvd_pa
     int rc = validate(desc);
     if (rc) return rc;
     if (!prob || !x || !ws || !params || !params->fourier_B || B <= 0) return NSVD_EINVAL;
-    if (ws_bytes < nsvd_workspace_bytes(desc, B)) return NSVD_EINVAL;
-    if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
-    const bool fused = want_fused(*desc, B, path, !(prob->eps > 0.f));
-    if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
+    bool fused;
+    rc = resolve_path(*desc, *prob, B, ws, ws_bytes, path, &fused);
+    if (rc) return rc;
     if (fused) return nsvd_fused_features(*desc, *params, *prob, x, B, ws, save_for_backward & 1, (hipStream_t)stream);
     if (generic_exact(path)) {  // the jet features, in the layout generic_forward(exact) reads
         if (const int st = generic_exact_status(*prob)) return st;
@@ -369,10 +380,9 @@ int sample_features_impl(const nsvd_model_desc* desc, const nsvd_params* params,
     if (rc) return rc;
     const bool gexact = generic_exact(path);
     if (gexact && (rc = generic_exact_status(*prob)) != 0) return rc;
-    if (ws_bytes < nsvd_workspace_bytes(desc, B)) return NSVD_EINVAL;
-    if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
-    const bool fused = want_fused(*desc, B, path, !(prob->eps > 0.f));
-    if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
+    bool fused;
+    rc = resolve_path(*desc, *prob, B, ws, ws_bytes, path, &fused);
+    if (rc) return rc;
     NsvdSampler smp = make_sampler(*prob, seed, offset);
     smp.offset_add = state ? (const unsigned long long*)&state->step : nullptr;
     hipStream_t s = (hipStream_t)stream;
@@ -418,8 +428,7 @@ extern "C" int nsvd_model_forward(const nsvd_model_desc* desc, const nsvd_params
     if (!x || !out || !ws || B <= 0) return NSVD_EINVAL;
     rc = check_params(*desc, params, true);
     if (rc) return rc;
-    if (ws_bytes < nsvd_model_workspace_bytes(desc, B)) return NSVD_EINVAL;
-    if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
+    if (!ws_ok(ws, ws_bytes, nsvd_model_workspace_bytes(desc, B))) return NSVD_EINVAL;
     if (nsvd_fused_model_supported(*desc, B))  // 128-wide hidden layers: the E = 1 instance of the MFMA forward
         return nsvd_fused_model_forward(*desc, *params, x, B, hard_mul_const, out, ws, save_for_backward,
                                         (hipStream_t)stream);
@@ -443,8 +452,7 @@ extern "C" int nsvd_model_backward(const nsvd_model_desc* desc, const nsvd_param
     if (rc) return rc;
     rc = check_params(*desc, grads, false);
     if (rc) return rc;
-    if (ws_bytes < nsvd_model_workspace_bytes(desc, B)) return NSVD_EINVAL;
-    if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
+    if (!ws_ok(ws, ws_bytes, nsvd_model_workspace_bytes(desc, B))) return NSVD_EINVAL;
     if (nsvd_fused_model_supported(*desc, B)) {
         nsvd_problem unused;
         memset(&unused, 0, sizeof(unused));
@@ -463,210 +471,270 @@ extern "C" int nsvd_operator_backward(const nsvd_model_desc* desc, const nsvd_pa
     if (rc) return rc;
     rc = check_params(*desc, grads, false);
     if (rc) return rc;
-    if (ws_bytes < nsvd_workspace_bytes(desc, B)) return NSVD_EINVAL;
-    if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
-    const bool fused = want_fused(*desc, B, path, !(prob->eps > 0.f));
-    if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
+    bool fused;
+    rc = resolve_path(*desc, *prob, B, ws, ws_bytes, path, &fused);
+    if (rc) return rc;
     if (fused) return nsvd_fused_backward(*desc, *params, *prob, x, B, df, *grads, ws, (hipStream_t)stream);
     if (generic_exact(path) && generic_exact_status(*prob)) return NSVD_EUNSUPPORTED;
     return generic_backward(*desc, *params, x, B, df, *grads, ws, (hipStream_t)stream, generic_erows(*desc, path));
 }
 
 namespace {
-int backward_evd_impl(const nsvd_model_desc* desc, const nsvd_params* params, const nsvd_problem* prob,
-                      const float* x, int B, const float* f, const float* Tf, int mask_kind, const float* v,
-                      const float* M, float* moments, int moments_reduced, const void* evd_scratch, int L_total,
-                      int l_offset, float grad_scale, float* loss, const nsvd_params* grads,
-                      const nsvd_rmsprop* opt, void* ws, size_t ws_bytes, int path, void* stream, int l_begin = 0,
-                      int l_count = 0, const NsvdNextBatch* next = nullptr, bool model_mode = false,
-                      int window_of_step = 0, int not_last = 0, void* ev_after_chain = nullptr,
-                      const nsvd_optimizer* opt2 = nullptr) {
-    // opt2: the step of any rule (nsvd_operator_backward_evd_opt_step) - instead of `opt`, never both
+// What one call of the EVD-backward family asks for. evd_call fills what the seven entry points share from their common
+// arguments (everything else zero); each entry point then sets only the fields that make it different.
+struct EvdCall {
+    const nsvd_model_desc* desc;
+    const nsvd_params* params;
+    const nsvd_problem* prob;
+    const float* x;
+    int B;
+    const float *f, *Tf;  // the loss inputs: f .. loss
+    int mask_kind;
+    const float *v, *M;
+    float* moments;
+    int moments_reduced;
+    const void* evd_scratch;
+    int L_total, l_offset;
+    float grad_scale;
+    float* loss;
+    const nsvd_params* grads;
+    void* ws;
+    size_t ws_bytes;
+    int path;
+    void* stream;
     // model_mode: the forward was nsvd_model_forward (plain model evaluation, any input dimension up to 64, no
-    // Hamiltonian): Tf is whatever operator output the caller computed from f (the kernel-operator path)
-    int rc = validate(desc, model_mode ? MODEL_MAX_D : NSVD_MAX_D);
+    // Hamiltonian): prob is null and Tf is whatever operator output the caller computed from f (the kernel-operator path)
+    bool model_mode;
+    int l_begin, l_count;  // the head window (l_count = 0: every head)
+    NsvdNextBatch next;    // next.x set: the next batch rides in this call's chain launch (next_batch)
+    int window_of_step, not_last;  // nsvd_fused_backward_evd
+    void* ev_after_chain;
+    // the optimiser step, where the entry point takes one: its descriptor (one of the two, or neither) and the step the
+    // kernels take, which backward_evd converts it into
+    const nsvd_rmsprop* rmsprop;
+    const nsvd_optimizer* optimizer;
+    bool take_step;
+    NsvdOptStep opt;
+};
+
+EvdCall evd_call(const nsvd_model_desc* desc, const nsvd_params* params, const nsvd_problem* prob, const float* x, int B,
+                 const float* f, const float* Tf, int mask_kind, const float* v, const float* M, float* moments,
+                 int moments_reduced, const void* evd_scratch, int L_total, int l_offset, float grad_scale, float* loss,
+                 const nsvd_params* grads, void* ws, size_t ws_bytes, int path, void* stream) {
+    EvdCall c = EvdCall();
+    c.desc = desc; c.params = params; c.prob = prob;
+    c.x = x; c.B = B;
+    c.f = f; c.Tf = Tf; c.mask_kind = mask_kind; c.v = v; c.M = M;
+    c.moments = moments; c.moments_reduced = moments_reduced; c.evd_scratch = evd_scratch;
+    c.L_total = L_total; c.l_offset = l_offset; c.grad_scale = grad_scale; c.loss = loss;
+    c.grads = grads;
+    c.ws = ws; c.ws_bytes = ws_bytes; c.path = path; c.stream = stream;
+    return c;
+}
+
+// the next batch of a step (drawn by the sampler, written to x_next) and the OTHER workspace set its features go to
+int next_batch(EvdCall& c, unsigned long long seed, unsigned long long offset, float* x_next, void* ws_next,
+               size_t ws_next_bytes) {
+    if (!x_next || !ws_next || ws_next == c.ws || !c.desc) return NSVD_EINVAL;
+    if (!ws_ok(ws_next, ws_next_bytes, nsvd_workspace_bytes(c.desc, c.B))) return NSVD_EINVAL;
+    if (const int st = validate_problem(c.desc, c.prob)) return st;
+    c.next.smp = make_sampler(*c.prob, seed, offset);
+    c.next.x = x_next;
+    c.next.ws = ws_next;
+    c.next.eps = c.prob->eps;
+    return 0;
+}
+
+// nsvd_rmsprop -> the step the kernels take: RMSprop without momentum, its device-resident schedule in `state`
+int opt_step_from(const nsvd_model_desc& d, const nsvd_rmsprop& o, NsvdOptStep* st) {
+    int rc = check_params(d, &o.sq, false);
     if (rc) return rc;
-    if ((!prob && !model_mode) || !x || !f || !Tf || !ws || B <= 0) return NSVD_EINVAL;
-    // direct mode (fused path): neither reduced moments nor partial sums - the backward kernel takes the moments it
-    // needs from f itself; `moments` and `loss` are then not written
-    const bool direct = !moments_reduced && !evd_scratch;
-    if (!direct && !moments) return NSVD_EINVAL;
-    if (mask_kind < 0 || mask_kind > NSVD_MASK_JOINT) return NSVD_EINVAL;
-    if (mask_kind == NSVD_MASK_CUSTOM && (!v || !M)) return NSVD_EINVAL;
-    rc = check_params(*desc, params, true);
-    if (rc) return rc;
-    if (opt && opt2) return NSVD_EINVAL;
-    if (grads || !(opt || opt2)) {
-        rc = check_params(*desc, grads, false);
+    if (o.has_ema) {
+        rc = check_params(d, &o.ema, false);
         if (rc) return rc;
+        st->ema = &o.ema;
     }
-    NsvdOptStep st;
-    memset(&st, 0, sizeof(st));
-    if (opt) {
-        rc = check_params(*desc, &opt->sq, false);
+    st->sq = o.sq;
+    st->h = nsvd_make_hyper(o.lr, o.alpha, o.eps, o.has_ema ? o.ema_decay : 0.0, 1.0);
+    st->state = o.state;
+    if (st->state && ((uintptr_t)st->state & 7) != 0) return NSVD_EINVAL;
+    return 0;
+}
+
+// nsvd_optimizer -> the step the kernels take: any rule of opt_math.h
+int opt_step_from(const nsvd_model_desc& d, const nsvd_optimizer& o, NsvdOptStep* st) {
+    const nsvd_opt_config& c = o.cfg;
+    const int rule = nsvd_opt_rule(c.kind, c.momentum);
+    if (rule < 0) return NSVD_EINVAL;
+    int rc;
+    if (nsvd_rule_uses_sq(rule)) {
+        rc = check_params(d, &o.sq, false);
         if (rc) return rc;
-        if (opt->has_ema) {
-            rc = check_params(*desc, &opt->ema, false);
-            if (rc) return rc;
-            st.ema = &opt->ema;
-        }
-        st.sq = opt->sq;
-        st.h = nsvd_make_hyper(opt->lr, opt->alpha, opt->eps, opt->has_ema ? opt->ema_decay : 0.0, 1.0);
-        st.state = opt->state;
-        if (st.state && ((uintptr_t)st.state & 7) != 0) return NSVD_EINVAL;
-        st.emit_planes = !model_mode && path == NSVD_PATH_FUSED_BF16X3;
+        st->sq = o.sq;
     }
-    if (opt2) {
-        const nsvd_opt_config& c = opt2->cfg;
-        const int rule = nsvd_opt_rule(c.kind, c.momentum);
-        if (rule < 0) return NSVD_EINVAL;
-        if (nsvd_rule_uses_sq(rule)) {
-            rc = check_params(*desc, &opt2->sq, false);
-            if (rc) return rc;
-            st.sq = opt2->sq;
-        }
-        if (nsvd_rule_uses_mom(rule)) {
-            rc = check_params(*desc, &opt2->mom, false);
-            if (rc) return rc;
-            st.mom = &opt2->mom;
-        }
-        if (opt2->has_ema) {
-            rc = check_params(*desc, &opt2->ema, false);
-            if (rc) return rc;
-            st.ema = &opt2->ema;
-        }
-        if (opt2->state && ((uintptr_t)opt2->state & 7) != 0) return NSVD_EINVAL;
-        st.rule = rule;
-        if (rule == NSVD_RULE_RMSPROP) {
-            if (opt2->state) return NSVD_EUNSUPPORTED;  // (its device-resident schedule is nsvd_rmsprop::state)
-            st.h = nsvd_make_hyper(c.lr, c.alpha, c.eps, opt2->has_ema ? c.ema_decay : 0.0, 1.0);
-        } else {
-            st.oh = nsvd_make_opt_hyper(rule, c.lr, c.alpha, c.eps, c.momentum, c.beta1, c.beta2,
-                                        opt2->has_ema ? c.ema_decay : 0.0, 1.0, opt2->steps_taken);
-            st.ostate = opt2->state;
-        }
-        st.emit_planes = !model_mode && path == NSVD_PATH_FUSED_BF16X3;
-    }
-    const bool take_step = opt || opt2;
-    if (ws_bytes < (model_mode ? nsvd_model_workspace_bytes(desc, B) : nsvd_workspace_bytes(desc, B))) return NSVD_EINVAL;
-    if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const bool fused = model_mode ? nsvd_fused_model_supported(*desc, B) : want_fused(*desc, B, path, !(prob->eps > 0.f));
-    if (model_mode && !fused) return NSVD_EUNSUPPORTED;  // plain-model training steps exist on the MFMA kernels only
-    if ((path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3) && !fused) return NSVD_EUNSUPPORTED;
-    if (L_total <= 0) L_total = desc->L;
-    if (l_offset < 0 || l_offset + desc->L > L_total || L_total > 128) return NSVD_EINVAL;
-    const int L = L_total;  // f, Tf, moments and masks are indexed by GLOBAL head
-    const NsvdEvdChunking c = nsvd_evd_chunking(B);
-    if (fused) {
-        NsvdEvdIn in;
-        memset(&in, 0, sizeof(in));
-        in.f = f; in.Tf = Tf; in.v = v; in.M = M;
-        in.kind = mask_kind;
-        in.grad_scale = grad_scale;
-        in.loss = loss;
-        in.Lg = L_total;
-        in.l_off = l_offset;
-        if (direct) {
-            // (the loss scalars come from per-head partials of the chain kernel, added by the weight-gradient kernel)
-        } else if (moments_reduced) {
-            in.moments = moments;
-        } else {
-            in.part = (const float*)evd_scratch;
-            in.part_op = in.part + (size_t)(c.n1 + c.n2) * L * L;
-            in.moments_out = moments;
-        }
-        if (l_count < 0 || l_begin < 0 || l_begin + l_count > desc->L) return NSVD_EINVAL;
-        if (st.ostate) {  // the step's scalars, derived before the step's first kernel
-            rc = nsvd_opt_state_begin(st.ostate, stream);
-            if (rc) return rc;
-        }
-        return nsvd_fused_backward_evd(*desc, *params, B, in, grads, take_step ? &st : nullptr, ws, s, l_begin, l_count,
-                                       next, window_of_step, not_last, ev_after_chain);
-    }
-    if (window_of_step) return NSVD_EUNSUPPORTED;  // windows of a fused step exist on the fused kernels only
-    if (next) return NSVD_EUNSUPPORTED;  // guest feature workgroups exist on the fused kernels only
-    if (opt && opt->state) return NSVD_EUNSUPPORTED;  // the device-resident schedule is read by the fused kernels only
-    if (l_count > 0 && l_count != desc->L) return NSVD_EUNSUPPORTED;  // head windows need the fused kernels
-    // generic path: finish the loss with the stand-alone kernels, then the layer-by-layer backward
-    if (direct) return NSVD_EINVAL;  // needs the partial moments (evd_scratch) or the reduced ones
-    if (L_total != desc->L) return NSVD_EUNSUPPORTED;  // head-parallel sharding needs the fused kernels
-    if (generic_exact(path) && generic_exact_status(*prob)) return NSVD_EUNSUPPORTED;
-    const int erows = generic_erows(*desc, path);  // (the workspace of the forward call: jet blocks or stencil blocks)
-    const GenericWs w = carve(*desc, B, ws, erows);
-    if (!moments_reduced) {
-        rc = nsvd_evd_reduce_partials(evd_scratch, B, L, moments, s);
+    if (nsvd_rule_uses_mom(rule)) {
+        rc = check_params(d, &o.mom, false);
         if (rc) return rc;
+        st->mom = &o.mom;
     }
-    rc = nsvd_evd_loss_grad(f, Tf, B, L, mask_kind, v, M, moments, grad_scale, loss, w.df, stream);
-    if (rc) return rc;
-    if (!grads) return NSVD_EINVAL;  // the generic path needs somewhere to put the gradients
-    rc = generic_backward(*desc, *params, x, B, w.df, *grads, ws, s, erows);
-    if (rc || !take_step) return rc;
+    if (o.has_ema) {
+        rc = check_params(d, &o.ema, false);
+        if (rc) return rc;
+        st->ema = &o.ema;
+    }
+    if (o.state && ((uintptr_t)o.state & 7) != 0) return NSVD_EINVAL;
+    st->rule = rule;
+    if (rule == NSVD_RULE_RMSPROP) {
+        if (o.state) return NSVD_EUNSUPPORTED;  // (its device-resident schedule is nsvd_rmsprop::state)
+        st->h = nsvd_make_hyper(c.lr, c.alpha, c.eps, o.has_ema ? c.ema_decay : 0.0, 1.0);
+    } else {
+        st->oh = nsvd_make_opt_hyper(rule, c.lr, c.alpha, c.eps, c.momentum, c.beta1, c.beta2,
+                                     o.has_ema ? c.ema_decay : 0.0, 1.0, o.steps_taken);
+        st->ostate = o.state;
+    }
+    return 0;
+}
+
+// The trainable tensors of a model in the order of the optimiser table: W[i], b[i] per layer, then scales.
+struct ParamTensors {
+    int nlayers, count;
+    size_t n[NSVD_OPT_TABLE_MAX];  // elements of tensor k
+    explicit ParamTensors(const nsvd_model_desc& d)
+        : nlayers(d.nlayers), count(2 * d.nlayers + (d.has_exp_mask ? 1 : 0)) {
+        for (int i = 0; i < d.nlayers; ++i) {
+            const size_t hin = i == 0 ? 2 * (size_t)d.m : (size_t)d.dims[i - 1], hout = (size_t)d.dims[i];
+            n[2 * i] = (size_t)d.L * hout * hin;
+            n[2 * i + 1] = (size_t)d.L * hout;
+        }
+        n[2 * d.nlayers] = (size_t)d.L;
+    }
+    // tensor k of a set laid out like the parameters (params, grads, optimiser state; no set: null)
+    float* in(const nsvd_params* set, int k) const {
+        if (!set) return nullptr;
+        return k == 2 * nlayers ? set->scales : (k & 1) ? set->b[k / 2] : set->W[k / 2];
+    }
+};
+
+// the optimiser step of the generic path: stand-alone launches behind the layer-by-layer backward
+int generic_opt_step(const EvdCall& c, hipStream_t s) {
+    const NsvdOptStep& st = c.opt;
+    const ParamTensors t(*c.desc);
+    int rc = 0;
     if (st.rule != NSVD_RULE_RMSPROP) {
         // the other rules: one stand-alone launch per tensor (scalars from the device-resident schedule when there is
         // one: derived first, advanced by the last launch)
         if (st.ostate) {
-            rc = nsvd_opt_state_begin(st.ostate, stream);
+            rc = nsvd_opt_state_begin(st.ostate, c.stream);
             if (rc) return rc;
         }
-        const int F = 2 * desc->m;
-        const int last = 2 * desc->nlayers - 1 + (desc->has_exp_mask ? 1 : 0);
-        int k = 0;
-        auto one = [&](float* pp, const float* gg, float* qq, float* mm, float* ee, size_t n) {
-            const int r = nsvd_opt_launch(st.rule, pp, gg, qq, mm, ee, n, st.oh, s, st.ostate, k == last);
-            ++k;
-            return r;
-        };
-        for (int i = 0; i < desc->nlayers; ++i) {
-            const size_t hin = i == 0 ? (size_t)F : (size_t)desc->dims[i - 1], hout = (size_t)desc->dims[i];
-            rc = one(params->W[i], grads->W[i], st.sq.W[i], st.mom ? st.mom->W[i] : nullptr,
-                     st.ema ? st.ema->W[i] : nullptr, (size_t)desc->L * hout * hin);
-            if (rc) return rc;
-            rc = one(params->b[i], grads->b[i], st.sq.b[i], st.mom ? st.mom->b[i] : nullptr,
-                     st.ema ? st.ema->b[i] : nullptr, (size_t)desc->L * hout);
-            if (rc) return rc;
-        }
-        if (desc->has_exp_mask)
-            rc = one(params->scales, grads->scales, st.sq.scales, st.mom ? st.mom->scales : nullptr,
-                     st.ema ? st.ema->scales : nullptr, (size_t)desc->L);
+        for (int k = 0; k < t.count && !rc; ++k)
+            rc = nsvd_opt_launch(st.rule, t.in(c.params, k), t.in(c.grads, k), t.in(&st.sq, k), t.in(st.mom, k),
+                                 t.in(st.ema, k), t.n[k], st.oh, s, st.ostate, k == t.count - 1);
         return rc;
     }
     // generic path + fused-step request: ONE stand-alone optimiser launch over the table of tensors (unaligned tensors -
     // never with torch allocations -: one launch per tensor)
-    const int F = 2 * desc->m;
-    {
-        NsvdOptTable tab;
-        memset(&tab, 0, sizeof(tab));
-        int c = 0;
-        auto add = [&](float* pp, const float* gg, float* qq, float* ee, size_t n) {
-            tab.p[c] = pp; tab.g[c] = gg; tab.sq[c] = qq; tab.ema[c] = ee; tab.n[c] = n;
-            ++c;
-        };
-        for (int i = 0; i < desc->nlayers; ++i) {
-            const size_t hin = i == 0 ? (size_t)F : (size_t)desc->dims[i - 1], hout = (size_t)desc->dims[i];
-            add(params->W[i], grads->W[i], st.sq.W[i], st.ema ? st.ema->W[i] : nullptr, (size_t)desc->L * hout * hin);
-            add(params->b[i], grads->b[i], st.sq.b[i], st.ema ? st.ema->b[i] : nullptr, (size_t)desc->L * hout);
-        }
-        if (desc->has_exp_mask)
-            add(params->scales, grads->scales, st.sq.scales, st.ema ? st.ema->scales : nullptr, (size_t)desc->L);
-        tab.count = c;
-        rc = nsvd_rmsprop_table_launch(tab, st.h, s);
-        if (rc != NSVD_EUNSUPPORTED) return rc;  // (misaligned pointers: one launch per tensor below)
+    NsvdOptTable tab;
+    memset(&tab, 0, sizeof(tab));
+    for (int k = 0; k < t.count; ++k) {
+        tab.p[k] = t.in(c.params, k); tab.g[k] = t.in(c.grads, k); tab.sq[k] = t.in(&st.sq, k);
+        tab.ema[k] = t.in(st.ema, k); tab.n[k] = t.n[k];
     }
-    for (int i = 0; i < desc->nlayers; ++i) {
-        const size_t hin = i == 0 ? (size_t)F : (size_t)desc->dims[i - 1], hout = (size_t)desc->dims[i];
-        rc = nsvd_rmsprop_launch(params->W[i], grads->W[i], st.sq.W[i], st.ema ? st.ema->W[i] : nullptr,
-                                 (size_t)desc->L * hout * hin, st.h, s);
-        if (rc) return rc;
-        rc = nsvd_rmsprop_launch(params->b[i], grads->b[i], st.sq.b[i], st.ema ? st.ema->b[i] : nullptr,
-                                 (size_t)desc->L * hout, st.h, s);
-        if (rc) return rc;
-    }
-    if (desc->has_exp_mask)
-        rc = nsvd_rmsprop_launch(params->scales, grads->scales, st.sq.scales, st.ema ? st.ema->scales : nullptr,
-                                 (size_t)desc->L, st.h, s);
+    tab.count = t.count;
+    rc = nsvd_rmsprop_table_launch(tab, st.h, s);
+    if (rc != NSVD_EUNSUPPORTED) return rc;  // (misaligned pointers: one launch per tensor below)
+    rc = 0;
+    for (int k = 0; k < t.count && !rc; ++k)
+        rc = nsvd_rmsprop_launch(t.in(c.params, k), t.in(c.grads, k), t.in(&st.sq, k), t.in(st.ema, k), t.n[k], st.h, s);
     return rc;
+}
+
+// The conversion of the entry point's optimiser descriptor into c.opt stands between the checks of the inputs and those
+// of the workspace and the path, where its refusals always stood; everything behind it sees c.opt alone.
+int backward_evd(EvdCall& c) {
+    const nsvd_model_desc* desc = c.desc;
+    const int B = c.B;
+    int rc = validate(desc, c.model_mode ? MODEL_MAX_D : NSVD_MAX_D);
+    if (rc) return rc;
+    if ((!c.prob && !c.model_mode) || !c.x || !c.f || !c.Tf || !c.ws || B <= 0) return NSVD_EINVAL;
+    // direct mode (fused path): neither reduced moments nor partial sums - the backward kernel takes the moments it
+    // needs from f itself; `moments` and `loss` are then not written
+    const bool direct = !c.moments_reduced && !c.evd_scratch;
+    if (!direct && !c.moments) return NSVD_EINVAL;
+    if (c.mask_kind < 0 || c.mask_kind > NSVD_MASK_JOINT) return NSVD_EINVAL;
+    if (c.mask_kind == NSVD_MASK_CUSTOM && (!c.v || !c.M)) return NSVD_EINVAL;
+    rc = check_params(*desc, c.params, true);
+    if (rc) return rc;
+    c.take_step = c.rmsprop || c.optimizer;
+    if (c.grads || !c.take_step) {
+        rc = check_params(*desc, c.grads, false);
+        if (rc) return rc;
+    }
+    if (c.take_step) {
+        rc = c.rmsprop ? opt_step_from(*desc, *c.rmsprop, &c.opt) : opt_step_from(*desc, *c.optimizer, &c.opt);
+        if (rc) return rc;
+        c.opt.emit_planes = !c.model_mode && c.path == NSVD_PATH_FUSED_BF16X3;
+    }
+    hipStream_t s = (hipStream_t)c.stream;
+    bool fused;
+    if (c.model_mode) {
+        if (!ws_ok(c.ws, c.ws_bytes, nsvd_model_workspace_bytes(desc, B))) return NSVD_EINVAL;
+        fused = nsvd_fused_model_supported(*desc, B);
+        if (!fused) return NSVD_EUNSUPPORTED;  // plain-model training steps exist on the MFMA kernels only
+    } else {
+        rc = resolve_path(*desc, *c.prob, B, c.ws, c.ws_bytes, c.path, &fused);
+        if (rc) return rc;
+    }
+    const int L = c.L_total <= 0 ? desc->L : c.L_total;  // f, Tf, moments and masks are indexed by GLOBAL head
+    if (c.l_offset < 0 || c.l_offset + desc->L > L || L > 128) return NSVD_EINVAL;
+    const NsvdEvdChunking ch = nsvd_evd_chunking(B);
+    if (fused) {
+        NsvdEvdIn in;
+        memset(&in, 0, sizeof(in));
+        in.f = c.f; in.Tf = c.Tf; in.v = c.v; in.M = c.M;
+        in.kind = c.mask_kind;
+        in.grad_scale = c.grad_scale;
+        in.loss = c.loss;
+        in.Lg = L;
+        in.l_off = c.l_offset;
+        if (direct) {
+            // (the loss scalars come from per-head partials of the chain kernel, added by the weight-gradient kernel)
+        } else if (c.moments_reduced) {
+            in.moments = c.moments;
+        } else {
+            in.part = (const float*)c.evd_scratch;
+            in.part_op = in.part + (size_t)(ch.n1 + ch.n2) * L * L;
+            in.moments_out = c.moments;
+        }
+        if (c.l_count < 0 || c.l_begin < 0 || c.l_begin + c.l_count > desc->L) return NSVD_EINVAL;
+        if (c.opt.ostate) {  // the step's scalars, derived before the step's first kernel
+            rc = nsvd_opt_state_begin(c.opt.ostate, c.stream);
+            if (rc) return rc;
+        }
+        return nsvd_fused_backward_evd(*desc, *c.params, B, in, c.grads, c.take_step ? &c.opt : nullptr, c.ws, s,
+                                       c.l_begin, c.l_count, c.next.x ? &c.next : nullptr, c.window_of_step,
+                                       c.not_last, c.ev_after_chain);
+    }
+    if (c.window_of_step) return NSVD_EUNSUPPORTED;  // windows of a fused step exist on the fused kernels only
+    if (c.next.x) return NSVD_EUNSUPPORTED;  // guest feature workgroups exist on the fused kernels only
+    if (c.opt.state) return NSVD_EUNSUPPORTED;  // the device-resident schedule is read by the fused kernels only
+    if (c.l_count > 0 && c.l_count != desc->L) return NSVD_EUNSUPPORTED;  // head windows need the fused kernels
+    // generic path: finish the loss with the stand-alone kernels, then the layer-by-layer backward
+    if (direct) return NSVD_EINVAL;  // needs the partial moments (evd_scratch) or the reduced ones
+    if (L != desc->L) return NSVD_EUNSUPPORTED;  // head-parallel sharding needs the fused kernels
+    if (generic_exact(c.path) && generic_exact_status(*c.prob)) return NSVD_EUNSUPPORTED;
+    const int erows = generic_erows(*desc, c.path);  // (the workspace of the forward call: jet blocks or stencil blocks)
+    const GenericWs w = carve(*desc, B, c.ws, erows);
+    if (!c.moments_reduced) {
+        rc = nsvd_evd_reduce_partials(c.evd_scratch, B, L, c.moments, s);
+        if (rc) return rc;
+    }
+    rc = nsvd_evd_loss_grad(c.f, c.Tf, B, L, c.mask_kind, c.v, c.M, c.moments, c.grad_scale, c.loss, w.df, c.stream);
+    if (rc) return rc;
+    if (!c.grads) return NSVD_EINVAL;  // the generic path needs somewhere to put the gradients
+    rc = generic_backward(*desc, *c.params, c.x, B, w.df, *c.grads, c.ws, s, erows);
+    if (rc || !c.take_step) return rc;
+    return generic_opt_step(c, s);
 }
 }  // namespace
 
@@ -678,9 +746,9 @@ extern "C" int nsvd_operator_backward_evd(const nsvd_model_desc* desc, const nsv
                                           const nsvd_params* grads, void* ws, size_t ws_bytes, int path,
                                           void* stream) {
     if (!grads) return NSVD_EINVAL;
-    return backward_evd_impl(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced,
-                             evd_scratch, L_total, l_offset, grad_scale, loss, grads, nullptr, ws, ws_bytes, path,
-                             stream);
+    EvdCall c = evd_call(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch,
+                         L_total, l_offset, grad_scale, loss, grads, ws, ws_bytes, path, stream);
+    return backward_evd(c);
 }
 
 extern "C" int nsvd_operator_backward_evd_heads(const nsvd_model_desc* desc, const nsvd_params* params,
@@ -691,9 +759,11 @@ extern "C" int nsvd_operator_backward_evd_heads(const nsvd_model_desc* desc, con
                                                 const nsvd_params* grads, void* ws, size_t ws_bytes, int path,
                                                 int l_begin, int l_count, void* stream) {
     if (!grads || l_count <= 0) return NSVD_EINVAL;
-    return backward_evd_impl(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced,
-                             evd_scratch, L_total, l_offset, grad_scale, loss, grads, nullptr, ws, ws_bytes, path,
-                             stream, l_begin, l_count);
+    EvdCall c = evd_call(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch,
+                         L_total, l_offset, grad_scale, loss, grads, ws, ws_bytes, path, stream);
+    c.l_begin = l_begin;
+    c.l_count = l_count;
+    return backward_evd(c);
 }
 
 extern "C" int nsvd_backward_head_window_ok(const nsvd_model_desc* desc, const nsvd_problem* prob, int B, int path,
@@ -711,9 +781,10 @@ extern "C" int nsvd_operator_backward_evd_step(const nsvd_model_desc* desc, cons
                                                const nsvd_params* grads, const nsvd_rmsprop* opt, void* ws,
                                                size_t ws_bytes, int path, void* stream) {
     if (!opt) return NSVD_EINVAL;
-    return backward_evd_impl(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced,
-                             evd_scratch, L_total, l_offset, grad_scale, loss, grads, opt, ws, ws_bytes, path,
-                             stream);
+    EvdCall c = evd_call(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch,
+                         L_total, l_offset, grad_scale, loss, grads, ws, ws_bytes, path, stream);
+    c.rmsprop = opt;
+    return backward_evd(c);
 }
 
 extern "C" int nsvd_operator_backward_evd_step_window(const nsvd_model_desc* desc, const nsvd_params* params,
@@ -728,22 +799,18 @@ extern "C" int nsvd_operator_backward_evd_step_window(const nsvd_model_desc* des
                                                       float* x_next, void* ws_next, size_t ws_next_bytes,
                                                       void* stream) {
     if (!opt || !prob || l_count <= 0) return NSVD_EINVAL;
-    NsvdNextBatch nb;
-    if (x_next) {  // the next batch rides in THIS window's chain launch (pass it to one window of the step only)
-        if (!ws_next || ws_next == ws) return NSVD_EINVAL;
-        if (ws_next_bytes < nsvd_workspace_bytes(desc, B) || ((uintptr_t)ws_next & 255) != 0) return NSVD_EINVAL;
-        if (!desc) return NSVD_EINVAL;
-        if (const int st = validate_problem(desc, prob)) return st;
-        memset(&nb, 0, sizeof(nb));
-        nb.smp = make_sampler(*prob, next_seed, next_offset);
-        nb.x = x_next;
-        nb.ws = ws_next;
-        nb.eps = prob->eps;
-    }
-    return backward_evd_impl(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced,
-                             evd_scratch, L_total, l_offset, grad_scale, loss, grads, opt, ws, ws_bytes, path,
-                             stream, l_begin, l_count, x_next ? &nb : nullptr, false, 1, last_window ? 0 : 1,
-                             ev_after_chain);
+    EvdCall c = evd_call(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch,
+                         L_total, l_offset, grad_scale, loss, grads, ws, ws_bytes, path, stream);
+    // the next batch rides in THIS window's chain launch (pass it to one window of the step only)
+    if (x_next)
+        if (const int rc = next_batch(c, next_seed, next_offset, x_next, ws_next, ws_next_bytes)) return rc;
+    c.l_begin = l_begin;
+    c.l_count = l_count;
+    c.window_of_step = 1;
+    c.not_last = last_window ? 0 : 1;
+    c.ev_after_chain = ev_after_chain;
+    c.rmsprop = opt;
+    return backward_evd(c);
 }
 
 extern "C" int nsvd_operator_backward_evd_step_next(const nsvd_model_desc* desc, const nsvd_params* params,
@@ -755,19 +822,12 @@ extern "C" int nsvd_operator_backward_evd_step_next(const nsvd_model_desc* desc,
                                                     size_t ws_bytes, int path, unsigned long long next_seed,
                                                     unsigned long long next_offset, float* x_next, void* ws_next,
                                                     size_t ws_next_bytes, void* stream) {
-    if (!opt || !prob || !x_next || !ws_next || ws_next == ws) return NSVD_EINVAL;
-    if (ws_next_bytes < nsvd_workspace_bytes(desc, B) || ((uintptr_t)ws_next & 255) != 0) return NSVD_EINVAL;
-    if (!desc) return NSVD_EINVAL;
-    if (const int st = validate_problem(desc, prob)) return st;
-    NsvdNextBatch nb;
-    memset(&nb, 0, sizeof(nb));
-    nb.smp = make_sampler(*prob, next_seed, next_offset);
-    nb.x = x_next;
-    nb.ws = ws_next;
-    nb.eps = prob->eps;
-    return backward_evd_impl(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced,
-                             evd_scratch, L_total, l_offset, grad_scale, loss, grads, opt, ws, ws_bytes, path,
-                             stream, 0, 0, &nb);
+    if (!opt || !prob) return NSVD_EINVAL;
+    EvdCall c = evd_call(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch,
+                         L_total, l_offset, grad_scale, loss, grads, ws, ws_bytes, path, stream);
+    if (const int rc = next_batch(c, next_seed, next_offset, x_next, ws_next, ws_next_bytes)) return rc;  // (mandatory)
+    c.rmsprop = opt;
+    return backward_evd(c);
 }
 
 extern "C" int nsvd_model_backward_evd_step(const nsvd_model_desc* desc, const nsvd_params* params, const float* x,
@@ -777,9 +837,11 @@ extern "C" int nsvd_model_backward_evd_step(const nsvd_model_desc* desc, const n
                                             float* loss, const nsvd_params* grads, const nsvd_rmsprop* opt, void* ws,
                                             size_t ws_bytes, void* stream) {
     if (!opt && !grads) return NSVD_EINVAL;
-    return backward_evd_impl(desc, params, nullptr, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch,
-                             L_total, l_offset, grad_scale, loss, grads, opt, ws, ws_bytes, NSVD_PATH_AUTO, stream, 0, 0,
-                             nullptr, true);
+    EvdCall c = evd_call(desc, params, nullptr, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch,
+                         L_total, l_offset, grad_scale, loss, grads, ws, ws_bytes, NSVD_PATH_AUTO, stream);
+    c.model_mode = true;
+    c.rmsprop = opt;
+    return backward_evd(c);
 }
 
 extern "C" int nsvd_operator_backward_evd_opt_step(const nsvd_model_desc* desc, const nsvd_params* params,
@@ -793,18 +855,10 @@ extern "C" int nsvd_operator_backward_evd_opt_step(const nsvd_model_desc* desc, 
                                                    size_t ws_next_bytes, void* stream) {
     if (!opt || !prob) return NSVD_EINVAL;
     if (nsvd_opt_rule(opt->cfg.kind, opt->cfg.momentum) < 0) return NSVD_EINVAL;
-    NsvdNextBatch nb;
-    if (x_next) {
-        if (!ws_next || ws_next == ws || !desc) return NSVD_EINVAL;
-        if (ws_next_bytes < nsvd_workspace_bytes(desc, B) || ((uintptr_t)ws_next & 255) != 0) return NSVD_EINVAL;
-        if (const int st = validate_problem(desc, prob)) return st;
-        memset(&nb, 0, sizeof(nb));
-        nb.smp = make_sampler(*prob, next_seed, next_offset);
-        nb.x = x_next;
-        nb.ws = ws_next;
-        nb.eps = prob->eps;
-    }
-    return backward_evd_impl(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced,
-                             evd_scratch, L_total, l_offset, grad_scale, loss, grads, nullptr, ws, ws_bytes, path,
-                             stream, 0, 0, x_next ? &nb : nullptr, false, 0, 0, nullptr, opt);
+    EvdCall c = evd_call(desc, params, prob, x, B, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch,
+                         L_total, l_offset, grad_scale, loss, grads, ws, ws_bytes, path, stream);
+    if (x_next)
+        if (const int rc = next_batch(c, next_seed, next_offset, x_next, ws_next, ws_next_bytes)) return rc;
+    c.optimizer = opt;
+    return backward_evd(c);
 }

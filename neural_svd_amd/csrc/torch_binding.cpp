@@ -261,21 +261,21 @@ void operator_backward_evd_step(const Shape& s, const ParamSet& params, const Pr
     void* wp = bytes(dv, ws, "ws");
     const size_t wn = (size_t)ws.numel() * ws.element_size();
     const nsvd_params* gp = grads ? &grads->p : nullptr;
+    // (the two entry points begin alike, desc .. path; tail: what follows path)
+    auto call = [&](auto entry, auto... tail) {
+        return entry(&s.d, &params.p, &prob.q, xp, B, fp, tp, (int)mask_kind, vp, Mp, mp, moments_reduced ? 1 : 0, scr, Lt,
+                     (int)l_offset, (float)grad_scale, lp, gp, &opt.o, wp, wn, (int)path, tail...);
+    };
     if (x_next.has_value()) {
         TORCH_CHECK(ws_next.has_value(), "ws_next required with x_next");
         float* xn = f32(dv, *x_next, "x_next");
         void* wnp = bytes(dv, *ws_next, "ws_next");
-        check_rc(nsvd_operator_backward_evd_step_next(&s.d, &params.p, &prob.q, xp, B, fp, tp, (int)mask_kind, vp, Mp, mp,
-                                                      moments_reduced ? 1 : 0, scr, Lt, (int)l_offset, (float)grad_scale,
-                                                      lp, gp, &opt.o, wp, wn, (int)path, next_seed, next_offset, xn, wnp,
-                                                      (size_t)ws_next->numel() * ws_next->element_size(), dv.stream()),
+        const size_t wnn = (size_t)ws_next->numel() * ws_next->element_size();
+        check_rc(call(nsvd_operator_backward_evd_step_next, next_seed, next_offset, xn, wnp, wnn, dv.stream()),
                  "nsvd_operator_backward_evd_step_next");
         return;
     }
-    check_rc(nsvd_operator_backward_evd_step(&s.d, &params.p, &prob.q, xp, B, fp, tp, (int)mask_kind, vp, Mp, mp,
-                                             moments_reduced ? 1 : 0, scr, Lt, (int)l_offset, (float)grad_scale, lp, gp,
-                                             &opt.o, wp, wn, (int)path, dv.stream()),
-             "nsvd_operator_backward_evd_step");
+    check_rc(call(nsvd_operator_backward_evd_step, dv.stream()), "nsvd_operator_backward_evd_step");
 }
 
 // torch.optim.RMSprop step + torch_ema update: examples/utils.py:50-57, examples/operator/__init__.py:69-73

@@ -531,6 +531,34 @@ def evd_gather_head_blocks(gathered: torch.Tensor, L: int, f: torch.Tensor, Tf: 
     check(rc, "nsvd_evd_gather_head_blocks")
 
 
+def _evd_check(complaint: str, shape: ModelShape, x: torch.Tensor, f: torch.Tensor, Tf: torch.Tensor,
+               moments: Optional[torch.Tensor]) -> None:
+    """The shape check the EVD-backward wrappers share: Tf like f, L_total >= shape.L, 2 L_total^2 + 1 moments;
+    `complaint` names the caller (who checks what is its own behind this, with the same words)."""
+    B, L_total = x.shape[0], f.shape[1]
+    if tuple(Tf.shape) != (B, L_total) or L_total < shape.L or \
+            (moments is not None and moments.numel() != 2 * L_total * L_total + 1):
+        raise NsvdError(complaint)
+
+
+def _evd_args(shape: ModelShape, params: Params, prob: Optional[Problem], x, f, Tf, mask_kind, v, M, moments,
+              moments_reduced, evd_scratch, l_offset, grad_scale, loss, grads: Optional[Params]) -> tuple:
+    """The arguments every EVD-backward entry point begins with (include/nsvd.h): desc, params, prob (the model's own
+    entry point, prob None, has none), x .. loss, grads."""
+    d = shape.desc()
+    return (C.byref(d), C.byref(params)) + ((C.byref(prob),) if prob is not None else ()) + (
+        _ptr(x, "x"), x.shape[0], _ptr(f, "f"), _ptr(Tf, "Tf"), int(mask_kind), _ptr(v, "v"), _ptr(M, "M"),
+        _ptr(moments, "moments"), int(bool(moments_reduced)),
+        evd_scratch.data_ptr() if evd_scratch is not None else None, int(f.shape[1]), int(l_offset), float(grad_scale),
+        _ptr(loss, "loss"), C.byref(grads) if grads is not None else None)
+
+
+def _next_args(next_seed: int, next_offset: int, x_next: Optional[torch.Tensor], ws_next: Optional[torch.Tensor]) -> tuple:
+    """next_seed, next_offset, x_next, ws_next, ws_next_bytes of the entry points a next batch can ride in"""
+    return (int(next_seed) & (2 ** 64 - 1), int(next_offset) & (2 ** 64 - 1), _ptr(x_next, "x_next"),
+            ws_next.data_ptr() if ws_next is not None else None, ws_next.numel() if ws_next is not None else 0)
+
+
 def operator_backward_evd(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor, f: torch.Tensor,
                           Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor], M: Optional[torch.Tensor],
                           moments: torch.Tensor, moments_reduced: bool, evd_scratch: Optional[torch.Tensor],
@@ -538,18 +566,10 @@ def operator_backward_evd(shape: ModelShape, params: Params, prob: Problem, x: t
                           path: int = PATH_AUTO, l_offset: int = 0) -> None:
     """loss gradient + operator backward in one call (d loss / d f is never materialised).
     f, Tf: (B, L_total) with L_total >= shape.L; this model owns heads [l_offset, l_offset + shape.L)."""
-    B = x.shape[0]
-    L_total = f.shape[1]
-    if tuple(Tf.shape) != (B, L_total) or L_total < shape.L or \
-            (moments is not None and moments.numel() != 2 * L_total * L_total + 1):
-        raise NsvdError("operator_backward_evd: f/Tf must be (B, L_total), moments 2*L_total^2+1")
-    d = shape.desc()
+    _evd_check("operator_backward_evd: f/Tf must be (B, L_total), moments 2*L_total^2+1", shape, x, f, Tf, moments)
     rc = _lib.load().nsvd_operator_backward_evd(
-        C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(f, "f"), _ptr(Tf, "Tf"), int(mask_kind),
-        _ptr(v, "v"), _ptr(M, "M"), _ptr(moments, "moments"), int(bool(moments_reduced)),
-        evd_scratch.data_ptr() if evd_scratch is not None else None, int(L_total), int(l_offset),
-        float(grad_scale), _ptr(loss, "loss"),
-        C.byref(grads), ws.data_ptr(), ws.numel(), int(path), _stream())
+        *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                   grad_scale, loss, grads), ws.data_ptr(), ws.numel(), int(path), _stream())
     check(rc, "nsvd_operator_backward_evd")
 
 
@@ -565,30 +585,21 @@ def operator_backward_evd_heads(shape: ModelShape, params: Params, prob: Problem
                                 ws: torch.Tensor, l_begin: int, l_count: int, grad_scale: float = 1.0,
                                 path: int = PATH_AUTO, l_offset: int = 0) -> None:
     """operator_backward_evd for the heads [l_begin, l_begin + l_count) only (the other gradients are untouched)."""
-    B = x.shape[0]
-    L_total = f.shape[1]
-    if tuple(Tf.shape) != (B, L_total) or L_total < shape.L or \
-            (moments is not None and moments.numel() != 2 * L_total * L_total + 1):
-        raise NsvdError("operator_backward_evd_heads: f/Tf must be (B, L_total), moments 2*L_total^2+1")
-    d = shape.desc()
+    _evd_check("operator_backward_evd_heads: f/Tf must be (B, L_total), moments 2*L_total^2+1", shape, x, f, Tf, moments)
     rc = _lib.load().nsvd_operator_backward_evd_heads(
-        C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(f, "f"), _ptr(Tf, "Tf"), int(mask_kind),
-        _ptr(v, "v"), _ptr(M, "M"), _ptr(moments, "moments"), int(bool(moments_reduced)),
-        evd_scratch.data_ptr() if evd_scratch is not None else None, int(L_total), int(l_offset),
-        float(grad_scale), _ptr(loss, "loss"), C.byref(grads), ws.data_ptr(), ws.numel(), int(path), int(l_begin),
-        int(l_count), _stream())
+        *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                   grad_scale, loss, grads), ws.data_ptr(), ws.numel(), int(path), int(l_begin), int(l_count), _stream())
     check(rc, "nsvd_operator_backward_evd_heads")
 
 
-class StepState:
-    """The device-resident schedule state (include/nsvd.h: nsvd_step_state): step counter, CosineAnnealingLR /
-    RMSprop / torch_ema constants and the scheduled values of the step being taken, in DEVICE memory - what lets a
-    captured training step replay along the schedule (examples/operator/__init__.py:69-73)."""
+class _DeviceSchedule:
+    """What StepState and OptState share: the device buffer of the library's struct (host mirror `_mirror`), and the
+    library's `_entry`_init (through the subclass' `_init`) / `_entry`_begin on it."""
+    _mirror: type = None
+    _entry: str = ""
 
-    def __init__(self, device, lr0: float, T_max: int, alpha: float, eps: float, ema_decay: float, eta_min: float = 0.0,
-                 step: int = 0):
-        self.buf = torch.zeros(C.sizeof(_lib.StepState) // 8, dtype=torch.int64, device=device)
-        self.args = (float(lr0), float(eta_min), int(T_max), float(alpha), float(eps), float(ema_decay))
+    def __init__(self, device, step: int):
+        self.buf = torch.zeros(C.sizeof(self._mirror) // 8, dtype=torch.int64, device=device)
         self.reset(step)
 
     @property
@@ -596,20 +607,33 @@ class StepState:
         return self.buf.data_ptr()
 
     def reset(self, step: int) -> None:
-        lr0, eta_min, T_max, alpha, eps, ema_decay = self.args
         with torch.cuda.device(self.buf.device):
-            check(_lib.load().nsvd_step_state_init(self.ptr, lr0, eta_min, T_max, alpha, eps, ema_decay, int(step),
-                                                   _stream()), "nsvd_step_state_init")
+            check(self._init(_lib.load(), int(step)), self._entry + "_init")
 
     def begin(self) -> None:
         """cur <- the scheduled values of step `step` (loop bodies whose first backward kernel does not do it)"""
         with torch.cuda.device(self.buf.device):
-            check(_lib.load().nsvd_step_state_begin(self.ptr, _stream()), "nsvd_step_state_begin")
+            check(getattr(_lib.load(), self._entry + "_begin")(self.ptr, _stream()), self._entry + "_begin")
 
-    def read(self) -> "_lib.StepState":
-        """host copy (synchronises)"""
-        raw = self.buf.cpu().numpy().tobytes()
-        return _lib.StepState.from_buffer_copy(raw)
+    def read(self):
+        """host copy, as the `_lib` mirror of the struct (synchronises)"""
+        return self._mirror.from_buffer_copy(self.buf.cpu().numpy().tobytes())
+
+
+class StepState(_DeviceSchedule):
+    """The device-resident schedule state (include/nsvd.h: nsvd_step_state): step counter, CosineAnnealingLR /
+    RMSprop / torch_ema constants and the scheduled values of the step being taken, in DEVICE memory - what lets a
+    captured training step replay along the schedule (examples/operator/__init__.py:69-73)."""
+    _mirror, _entry = _lib.StepState, "nsvd_step_state"
+
+    def __init__(self, device, lr0: float, T_max: int, alpha: float, eps: float, ema_decay: float, eta_min: float = 0.0,
+                 step: int = 0):
+        self.args = (float(lr0), float(eta_min), int(T_max), float(alpha), float(eps), float(ema_decay))
+        super().__init__(device, step)
+
+    def _init(self, lib, step: int) -> int:
+        lr0, eta_min, T_max, alpha, eps, ema_decay = self.args
+        return lib.nsvd_step_state_init(self.ptr, lr0, eta_min, T_max, alpha, eps, ema_decay, step, _stream())
 
 
 def rmsprop_state(sq: Params, ema: Optional[Params], lr: float, alpha: float, eps: float,
@@ -633,6 +657,16 @@ def _tb_rmsprop(shape: ModelShape, opt: "_lib.Rmsprop"):
                        opt.eps, opt.ema_decay, state.buf if state is not None else None)
 
 
+def _tb_evd_step(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                 grad_scale, loss, grads, opt, ws, path, x_next, ws_next, next_seed, next_offset) -> None:
+    """operator_backward_evd_step / _step_next through the tensor-level binding (one entry point there: x_next or None)"""
+    _TB.operator_backward_evd_step(_tb_shape(shape), _tb_params(shape, params), _tb_problem(prob), x, f, Tf,
+                                   int(mask_kind), v, M, moments, bool(moments_reduced), evd_scratch, int(l_offset),
+                                   float(grad_scale), loss, _tb_params(shape, grads) if grads is not None else None,
+                                   _tb_rmsprop(shape, opt), ws, int(path), x_next, ws_next,
+                                   int(next_seed) & (2 ** 64 - 1), int(next_offset) & (2 ** 64 - 1))
+
+
 def operator_backward_evd_step(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor, f: torch.Tensor,
                                Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor],
                                M: Optional[torch.Tensor], moments: torch.Tensor, moments_reduced: bool,
@@ -640,24 +674,14 @@ def operator_backward_evd_step(shape: ModelShape, params: Params, prob: Problem,
                                opt: "_lib.Rmsprop", ws: torch.Tensor, grad_scale: float = 1.0,
                                path: int = PATH_AUTO, l_offset: int = 0) -> None:
     """operator_backward_evd + RMSprop/EMA step inside the weight-gradient kernel; params are updated in place."""
-    B = x.shape[0]
-    L_total = f.shape[1]
-    if tuple(Tf.shape) != (B, L_total) or L_total < shape.L or \
-            (moments is not None and moments.numel() != 2 * L_total * L_total + 1):
-        raise NsvdError("operator_backward_evd_step: f/Tf must be (B, L_total), moments 2*L_total^2+1")
+    _evd_check("operator_backward_evd_step: f/Tf must be (B, L_total), moments 2*L_total^2+1", shape, x, f, Tf, moments)
     if torch_binding() is not None:
-        _TB.operator_backward_evd_step(_tb_shape(shape), _tb_params(shape, params), _tb_problem(prob), x, f, Tf,
-                                       int(mask_kind), v, M, moments, bool(moments_reduced), evd_scratch, int(l_offset),
-                                       float(grad_scale), loss, _tb_params(shape, grads) if grads is not None else None,
-                                       _tb_rmsprop(shape, opt), ws, int(path), None, None, 0, 0)
+        _tb_evd_step(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                     grad_scale, loss, grads, opt, ws, path, None, None, 0, 0)
         return
-    d = shape.desc()
     rc = _lib.load().nsvd_operator_backward_evd_step(
-        C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(f, "f"), _ptr(Tf, "Tf"), int(mask_kind),
-        _ptr(v, "v"), _ptr(M, "M"), _ptr(moments, "moments"), int(bool(moments_reduced)),
-        evd_scratch.data_ptr() if evd_scratch is not None else None, int(L_total), int(l_offset),
-        float(grad_scale), _ptr(loss, "loss"), C.byref(grads) if grads is not None else None, C.byref(opt),
-        ws.data_ptr(), ws.numel(), int(path), _stream())
+        *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                   grad_scale, loss, grads), C.byref(opt), ws.data_ptr(), ws.numel(), int(path), _stream())
     check(rc, "nsvd_operator_backward_evd_step")
 
 
@@ -673,22 +697,15 @@ def operator_backward_evd_step_window(shape: ModelShape, params: Params, prob: P
     """operator_backward_evd_step for the heads [l_begin, l_begin + l_count) of ONE fused step taken as several head
     windows (nsvd_operator_backward_evd_step_window: include/nsvd.h). Launches on the CURRENT stream; ev_after_chain is
     recorded between the window's two launches."""
-    B = x.shape[0]
-    L_total = f.shape[1]
     ev = None
     if ev_after_chain is not None:
         if ev_after_chain.cuda_event == 0:  # torch creates the hipEvent lazily, at the first record
             ev_after_chain.record()
         ev = ev_after_chain.cuda_event
-    d = shape.desc()
     rc = _lib.load().nsvd_operator_backward_evd_step_window(
-        C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(f, "f"), _ptr(Tf, "Tf"), int(mask_kind),
-        _ptr(v, "v"), _ptr(M, "M"), _ptr(moments, "moments"), int(bool(moments_reduced)),
-        evd_scratch.data_ptr() if evd_scratch is not None else None, int(L_total), int(l_offset),
-        float(grad_scale), _ptr(loss, "loss"), None, C.byref(opt), ws.data_ptr(), ws.numel(), int(path),
-        int(l_begin), int(l_count), int(bool(last_window)), ev, int(next_seed) & (2 ** 64 - 1),
-        int(next_offset) & (2 ** 64 - 1), _ptr(x_next, "x_next"), ws_next.data_ptr() if ws_next is not None else None,
-        ws_next.numel() if ws_next is not None else 0, _stream())
+        *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                   grad_scale, loss, None), C.byref(opt), ws.data_ptr(), ws.numel(), int(path), int(l_begin),
+        int(l_count), int(bool(last_window)), ev, *_next_args(next_seed, next_offset, x_next, ws_next), _stream())
     check(rc, "nsvd_operator_backward_evd_step_window")
 
 
@@ -700,26 +717,18 @@ def operator_backward_evd_step_next(shape: ModelShape, params: Params, prob: Pro
                                     x_next: torch.Tensor, ws_next: torch.Tensor, grad_scale: float = 1.0,
                                     path: int = PATH_AUTO, l_offset: int = 0) -> None:
     """operator_backward_evd_step + operator_sample_features(next batch) in the same launches (MFMA path only)."""
-    B = x.shape[0]
-    L_total = f.shape[1]
-    if tuple(Tf.shape) != (B, L_total) or L_total < shape.L or tuple(x_next.shape) != tuple(x.shape) or \
-            (moments is not None and moments.numel() != 2 * L_total * L_total + 1):
-        raise NsvdError("operator_backward_evd_step_next: f/Tf (B, L_total), moments 2*L_total^2+1, x_next like x")
+    complaint = "operator_backward_evd_step_next: f/Tf (B, L_total), moments 2*L_total^2+1, x_next like x"
+    _evd_check(complaint, shape, x, f, Tf, moments)
+    if tuple(x_next.shape) != tuple(x.shape):
+        raise NsvdError(complaint)
     if torch_binding() is not None:
-        _TB.operator_backward_evd_step(_tb_shape(shape), _tb_params(shape, params), _tb_problem(prob), x, f, Tf,
-                                       int(mask_kind), v, M, moments, bool(moments_reduced), evd_scratch, int(l_offset),
-                                       float(grad_scale), loss, _tb_params(shape, grads) if grads is not None else None,
-                                       _tb_rmsprop(shape, opt), ws, int(path), x_next, ws_next,
-                                       int(next_seed) & (2 ** 64 - 1), int(next_offset) & (2 ** 64 - 1))
+        _tb_evd_step(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                     grad_scale, loss, grads, opt, ws, path, x_next, ws_next, next_seed, next_offset)
         return
-    d = shape.desc()
     rc = _lib.load().nsvd_operator_backward_evd_step_next(
-        C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(f, "f"), _ptr(Tf, "Tf"), int(mask_kind),
-        _ptr(v, "v"), _ptr(M, "M"), _ptr(moments, "moments"), int(bool(moments_reduced)),
-        evd_scratch.data_ptr() if evd_scratch is not None else None, int(L_total), int(l_offset),
-        float(grad_scale), _ptr(loss, "loss"), C.byref(grads) if grads is not None else None, C.byref(opt),
-        ws.data_ptr(), ws.numel(), int(path), int(next_seed) & (2 ** 64 - 1), int(next_offset) & (2 ** 64 - 1),
-        _ptr(x_next, "x_next"), ws_next.data_ptr(), ws_next.numel(), _stream())
+        *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                   grad_scale, loss, grads), C.byref(opt), ws.data_ptr(), ws.numel(), int(path),
+        *_next_args(next_seed, next_offset, x_next, ws_next), _stream())
     check(rc, "nsvd_operator_backward_evd_step_next")
 
 
@@ -757,21 +766,14 @@ def operator_backward_evd_opt_step(shape: ModelShape, params: Params, prob: Prob
                                    x_next: Optional[torch.Tensor] = None, ws_next: Optional[torch.Tensor] = None) -> None:
     """operator_backward_evd_step for any optimiser rule (nsvd_operator_backward_evd_opt_step); with x_next / ws_next
     the next batch's draw and features ride along as in operator_backward_evd_step_next (MFMA path only)."""
-    B = x.shape[0]
-    L_total = f.shape[1]
-    if tuple(Tf.shape) != (B, L_total) or L_total < shape.L or \
-            (moments is not None and moments.numel() != 2 * L_total * L_total + 1) or \
-            (x_next is not None and (ws_next is None or tuple(x_next.shape) != tuple(x.shape))):
-        raise NsvdError("operator_backward_evd_opt_step: f/Tf (B, L_total), moments 2*L_total^2+1, x_next like x")
-    d = shape.desc()
+    complaint = "operator_backward_evd_opt_step: f/Tf (B, L_total), moments 2*L_total^2+1, x_next like x"
+    _evd_check(complaint, shape, x, f, Tf, moments)
+    if x_next is not None and (ws_next is None or tuple(x_next.shape) != tuple(x.shape)):
+        raise NsvdError(complaint)
     rc = _lib.load().nsvd_operator_backward_evd_opt_step(
-        C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(f, "f"), _ptr(Tf, "Tf"), int(mask_kind),
-        _ptr(v, "v"), _ptr(M, "M"), _ptr(moments, "moments"), int(bool(moments_reduced)),
-        evd_scratch.data_ptr() if evd_scratch is not None else None, int(L_total), int(l_offset),
-        float(grad_scale), _ptr(loss, "loss"), C.byref(grads) if grads is not None else None, C.byref(opt),
-        ws.data_ptr(), ws.numel(), int(path), int(next_seed) & (2 ** 64 - 1), int(next_offset) & (2 ** 64 - 1),
-        _ptr(x_next, "x_next"), ws_next.data_ptr() if ws_next is not None else None,
-        ws_next.numel() if ws_next is not None else 0, _stream())
+        *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                   grad_scale, loss, grads), C.byref(opt), ws.data_ptr(), ws.numel(), int(path),
+        *_next_args(next_seed, next_offset, x_next, ws_next), _stream())
     check(rc, "nsvd_operator_backward_evd_opt_step")
 
 
@@ -786,13 +788,10 @@ def model_backward_evd_step(shape: ModelShape, params: Params, x: torch.Tensor, 
     B, L = f.shape
     if tuple(Tf.shape) != (B, L) or L < l_offset + shape.L or x.shape[0] != B or moments.numel() != 2 * L * L + 1:
         raise NsvdError("model_backward_evd_step: f, Tf (B, L_total); moments 2 L_total^2 + 1")
-    d = shape.desc()
     rc = _lib.load().nsvd_model_backward_evd_step(
-        C.byref(d), C.byref(params), _ptr(x, "x"), B, _ptr(f, "f"), _ptr(Tf, "Tf"), int(mask_kind), _ptr(v, "v"),
-        _ptr(M, "M"), _ptr(moments, "moments"), int(bool(moments_reduced)),
-        evd_scratch.data_ptr() if evd_scratch is not None else None, int(L), int(l_offset), float(grad_scale),
-        _ptr(loss, "loss"), C.byref(grads) if grads is not None else None, C.byref(opt) if opt is not None else None,
-        ws.data_ptr(), ws.numel(), _stream())
+        *_evd_args(shape, params, None, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                   grad_scale, loss, grads), C.byref(opt) if opt is not None else None, ws.data_ptr(), ws.numel(),
+        _stream())
     check(rc, "nsvd_model_backward_evd_step")
 
 
@@ -1279,32 +1278,17 @@ def opt_step(cfg: _lib.OptConfig, p: torch.Tensor, grad: torch.Tensor, sq: Optio
     check(rc, "nsvd_opt_step")
 
 
-class OptState:
+class OptState(_DeviceSchedule):
     """The device-resident schedule of any optimiser rule (include/nsvd.h: nsvd_opt_state): what StepState is for
     RMSprop without momentum, plus Adam's bias corrections and SGD's first-step flag."""
+    _mirror, _entry = _lib.OptState, "nsvd_opt_state"
 
     def __init__(self, device, cfg: _lib.OptConfig, T_max: int, eta_min: float = 0.0, step: int = 0):
-        self.buf = torch.zeros(C.sizeof(_lib.OptState) // 8, dtype=torch.int64, device=device)
         self.cfg, self.T_max, self.eta_min = cfg, int(T_max), float(eta_min)
-        self.reset(step)
+        super().__init__(device, step)
 
-    @property
-    def ptr(self) -> int:
-        return self.buf.data_ptr()
-
-    def reset(self, step: int) -> None:
-        with torch.cuda.device(self.buf.device):
-            check(_lib.load().nsvd_opt_state_init(self.ptr, C.byref(self.cfg), self.eta_min, self.T_max, int(step),
-                                                  _stream()), "nsvd_opt_state_init")
-
-    def begin(self) -> None:
-        """cur <- the scheduled values of step `step` (first launch of a loop body)"""
-        with torch.cuda.device(self.buf.device):
-            check(_lib.load().nsvd_opt_state_begin(self.ptr, _stream()), "nsvd_opt_state_begin")
-
-    def read(self) -> "_lib.OptState":
-        """host copy (synchronises)"""
-        return _lib.OptState.from_buffer_copy(self.buf.cpu().numpy().tobytes())
+    def _init(self, lib, step: int) -> int:
+        return lib.nsvd_opt_state_init(self.ptr, C.byref(self.cfg), self.eta_min, self.T_max, step, _stream())
 
 
 def opt_step_dev(p: torch.Tensor, grad: torch.Tensor, sq: Optional[torch.Tensor], mom: Optional[torch.Tensor],

@@ -417,18 +417,20 @@ class FusedTrainer:
             self._partials_ready = False  # left by after_gather (heads sharded), for this f, Tf
         else:
             H.evd_partial(self.f_g, self.Tf_g, self.mask_kind, v, self.scratch)
-        x = self._x_cur
+        # what every entry point of the EVD-backward family begins with (hip_ops: shape .. loss)
+        call = (self.shape, self._params, self.problem, self._x_cur, self.f_g, self.Tf_g, self.mask_kind, v, M, moments,
+                reduced, scratch, loss)
         if self.fused_step and take_step:
             t_before = self.t
             lr, decay = self._advance_schedule()
             # (device schedule: lr / decay are read on the device, the host values only keep the counters in step)
             if self._other_rule:
-                self._backward_other_rule(x, v, M, moments, reduced, scratch, loss, lr, decay, t_before)
+                self._backward_other_rule(call, lr, decay, t_before)
                 return
             opt = H.rmsprop_state(self._sq_params, self._ema_params, lr, self.alpha, self.eps, decay, self.state)
             if self._two_windows():
                 ride = self.guest_features and self._own_batch and not self._next_ready
-                self._backward_two_windows(x, v, M, moments, reduced, scratch, loss, opt, ride,
+                self._backward_two_windows(call, opt, ride,
                                            self.batches_drawn - (t_before if self.state is not None else 0))
                 if ride:
                     self.batches_drawn += 1
@@ -439,39 +441,32 @@ class FusedTrainer:
                     (not self.multi or not self.overlap):
                 # the next batch rides in this backward's first launch (hp with overlap prepares it under its
                 # all-gather instead: parallel.hp_step -> prefetch)
-                H.operator_backward_evd_step_next(self.shape, self._params, self.problem, x, self.f_g, self.Tf_g,
-                                                  self.mask_kind, v, M, moments, reduced, scratch, loss, None, opt,
-                                                  self.ws, self.sample_key,
+                H.operator_backward_evd_step_next(*call, None, opt, self.ws, self.sample_key,
                                                   self.batches_drawn - (t_before if self.state is not None else 0),
                                                   self._x_other, self._ws_other, 1.0, self.path, l_offset=self.l_off)
                 self.batches_drawn += 1
                 self._next_ready = True
                 self._note_planes(self._ws_other)
                 return
-            H.operator_backward_evd_step(self.shape, self._params, self.problem, x, self.f_g, self.Tf_g,
-                                         self.mask_kind, v, M, moments, reduced, scratch, loss,
-                                         self._grads if self.keep_grads else None, opt, self.ws, 1.0, self.path,
+            H.operator_backward_evd_step(*call, self._grads if self.keep_grads else None, opt, self.ws, 1.0, self.path,
                                          l_offset=self.l_off)
             self._note_planes(self.ws)
             return
-        H.operator_backward_evd(self.shape, self._params, self.problem, x, self.f_g, self.Tf_g, self.mask_kind, v, M,
-                                moments, reduced, scratch, loss, self._grads, self.ws, 1.0, self.path,
-                                l_offset=self.l_off)
+        H.operator_backward_evd(*call, self._grads, self.ws, 1.0, self.path, l_offset=self.l_off)
         if take_step and (not self.multi or self.hp):  # no exchange between backward and optimiser
             self.begin_apply()
             self.apply(0, self.P.numel, 1.0)
 
-    def _backward_other_rule(self, x, v, M, moments, reduced, scratch, loss, lr, decay, t_before) -> None:
-        """the fused step of any rule but RMSprop without momentum (nsvd_operator_backward_evd_opt_step)"""
+    def _backward_other_rule(self, call, lr, decay, t_before) -> None:
+        """the fused step of any rule but RMSprop without momentum (nsvd_operator_backward_evd_opt_step); call: the
+        leading arguments backward() bound"""
         if self._opt_desc is None:
             self._opt_desc = H.optimizer_state(self._cfg, self._sq_params if self._uses_sq else None, self._mom_params,
                                                self._ema_params, state=self.state)
         opt = self._opt_desc
         opt.cfg.lr, opt.cfg.ema_decay, opt.steps_taken = float(lr), float(decay), int(t_before)
         ride = self.guest_features and self._own_batch and not self._next_ready
-        H.operator_backward_evd_opt_step(self.shape, self._params, self.problem, x, self.f_g, self.Tf_g, self.mask_kind,
-                                         v, M, moments, reduced, scratch, loss,
-                                         self._grads if self.keep_grads else None, opt, self.ws, 1.0, self.path,
+        H.operator_backward_evd_opt_step(*call, self._grads if self.keep_grads else None, opt, self.ws, 1.0, self.path,
                                          l_offset=self.l_off, next_seed=self.sample_key,
                                          next_offset=self.batches_drawn - (t_before if self.state is not None else 0),
                                          x_next=self._x_other if ride else None,
@@ -496,21 +491,18 @@ class FusedTrainer:
             self._ev_done1 = torch.cuda.Event()
         return True
 
-    def _backward_two_windows(self, x, v, M, moments, reduced, scratch, loss, opt, ride, next_offset) -> None:
+    def _backward_two_windows(self, call, opt, ride, next_offset) -> None:
         half = self.shape.L // 2
         cur = torch.cuda.current_stream(self.device)
         kw = dict(grad_scale=1.0, path=self.path, l_offset=self.l_off)
         # window 0 on the current stream (the next batch rides in its chain launch); the event sits between its launches
-        H.operator_backward_evd_step_window(self.shape, self._params, self.problem, x, self.f_g, self.Tf_g,
-                                            self.mask_kind, v, M, moments, reduced, scratch, loss, opt, self.ws, 0, half,
-                                            False, self._ev_chain0, self.sample_key, next_offset,
-                                            self._x_other if ride else None, self._ws_other if ride else None, **kw)
+        H.operator_backward_evd_step_window(*call, opt, self.ws, 0, half, False, self._ev_chain0, self.sample_key,
+                                            next_offset, self._x_other if ride else None,
+                                            self._ws_other if ride else None, **kw)
         # window 1 (the LAST: schedule advance, loss) on the side stream, behind window 0's chain
         self._side_stream.wait_event(self._ev_chain0)
         with torch.cuda.stream(self._side_stream):
-            H.operator_backward_evd_step_window(self.shape, self._params, self.problem, x, self.f_g, self.Tf_g,
-                                                self.mask_kind, v, M, moments, reduced, scratch, loss, opt, self.ws,
-                                                half, self.shape.L - half, True, None, **kw)
+            H.operator_backward_evd_step_window(*call, opt, self.ws, half, self.shape.L - half, True, None, **kw)
             self._ev_done1.record(self._side_stream)
         cur.wait_event(self._ev_done1)
 
@@ -542,10 +534,10 @@ class FusedTrainer:
             return
         assert reduced_moments is self._moments
         v, M = self._masks()
+        call = (self.shape, self._params, self.problem, self._x_cur, self.f_g, self.Tf_g, self.mask_kind, v, M,
+                self._moments, True, self.scratch, self._loss)
         for k, (l0, lc) in enumerate(self._windows):
-            H.operator_backward_evd_heads(self.shape, self._params, self.problem, self._x_cur, self.f_g, self.Tf_g,
-                                          self.mask_kind, v, M, self._moments, True, self.scratch, self._loss,
-                                          self._grads, self.ws, l0, lc, 1.0, self.path, l_offset=self.l_off)
+            H.operator_backward_evd_heads(*call, self._grads, self.ws, l0, lc, 1.0, self.path, l_offset=self.l_off)
             yield self._stage_buckets[k]
         yield self._stage_buckets[-1]
 
