@@ -691,6 +691,45 @@ int nsvd_ritz_step_f64(const double* S, const double* A, const double* C, int m,
 int nsvd_ts_rotate(const float* X, long ldx, int n, int m, const double* T, int ldt, int k, float* out, long ldo,
                    void* stream);
 
+/* ---- next row: the dense side of the truncated-SVD baseline of the kernel SVD operators ------------------------------
+ * The top L <= 64 singular triplets of the empirical cross operator C = k(xs, ys) / sqrt(n_x n_y) come from a two-sided
+ * block iteration on bases U (n_x, m), V (n_y, m), m <= 80, with P = C V and R = C^T U from ONE nsvd_rbf_apply_pair /
+ * nsvd_dot_apply_pair call (neural_svd_amd/nystrom_svd.py drives the loop; nsvd_ts_rotate applies Tu and Tv). These are
+ * the two pieces beside that product. NEW SYMBOLS ONLY: NSVD_ABI_VERSION stays 6.
+ *
+ * nsvd_tsgram3_f64: XtX = X^T X, XtY = X^T Y and YtY = Y^T Y, (m, m) float64 row-major, of X, Y (n, m) float32 with row
+ *   strides ldx, ldy >= m (in floats), in one pass: each row tile of X and Y is staged once and feeds all three
+ *   accumulations. All three outputs are required; X may be Y. Otherwise nsvd_tsgram_f64's conventions: products and
+ *   sums in float64, rows split over workgroups by the same rule, partial matrices reduced in slice order by a second
+ *   launch (no atomics: bit-reproducible), 1 <= m <= 80 (NSVD_EUNSUPPORTED above), any n >= 1, workspace 256-byte
+ *   aligned, its size 0 for shapes outside these ranges.
+ * nsvd_svd_ritz_step_f64: one workgroup, float64, everything (m, m) contiguous row-major. With
+ *   Sp = P^T P, PtU = P^T U, Cu = U^T U, Sr = R^T R, RtV = R^T V, Cv = V^T V (two nsvd_tsgram3_f64 calls):
+ *       Hl = PtU^T, Hr = RtV (both U^T C V up to the float32 rounding of P and R);
+ *       H = (Hl + Hr) / 2 = A diag(sigma) B^T, sigma descending and >= 0, ties by ascending index (one-sided Jacobi on
+ *       the columns of H in a fixed round-robin ordering: a pair is rotated when |g_p . g_q| > 1e-15 |g_p| |g_q|, a sweep
+ *       without a rotation ends the loop, at most 40 sweeps; sigma_k = |g_k|, a_k = g_k / sigma_k - never through
+ *       eigh(H^T H), which would square the trailing singular values into the rounding of the leading ones);
+ *       Mp = B^T Sp B, Mr = A^T Sr A;
+ *       resid_l_k = sqrt(max(Mp_kk - 2 sigma_k (A^T Hl B)_kk + sigma_k^2 (A^T Cu A)_kk, 0)) = |P b_k - sigma_k U a_k|,
+ *       resid_r_k = sqrt(max(Mr_kk - 2 sigma_k (A^T Hr B)_kk + sigma_k^2 (B^T Cv B)_kk, 0)) = |R a_k - sigma_k V b_k|
+ *       - identities for ANY U, A, B: the short form Mp_kk - sigma_k^2 assumes an orthonormal U and H = U^T P exactly, and
+ *       with a float32 U and an H that averages two float32-derived matrices its square root stalls at 1e-4 sigma_0;
+ *       Tu = B chol(Mp)^-1, Tv = A chol(Mr)^-1 (upper Cholesky factors): P Tu and R Tv are orthonormal bases of span(P)
+ *       and span(R) whose leading columns are the Ritz directions in order.
+ *   Cu / Cv NULL stand for the identity (the same bits as passing it). sigma, resid_l, resid_r, A, B may be NULL; Tu, Tv
+ *   and status are required. *status (device int, zeroed by the caller) has NSVD_RITZ_* bits OR-ed in. On a
+ *   non-positive (or non-finite) pivot that T is zero from the column on (NSVD_RITZ_BAD_PIVOT); sigma_k = 0 gives a zero
+ *   column of A, never a division, and surfaces as a bad pivot of Mr. Nothing non-finite is ever stored. m > 80 is
+ *   NSVD_EUNSUPPORTED; a NULL required pointer or m <= 0 is NSVD_EINVAL; a refused call writes nothing. Every loop of
+ *   the kernel has a trip count bounded by m or a constant. Restated in float64 numpy by tests/_ksvd_oracle.py. */
+size_t nsvd_tsgram3_f64_workspace_bytes(int n, int m);
+int nsvd_tsgram3_f64(const float* X, long ldx, const float* Y, long ldy, int n, int m, double* XtX, double* XtY,
+                     double* YtY, void* ws, size_t ws_bytes, void* stream);
+int nsvd_svd_ritz_step_f64(const double* PtU, const double* RtV, const double* Sp, const double* Sr, const double* Cu,
+                           const double* Cv, int m, double* sigma, double* resid_l, double* resid_r, double* A, double* B,
+                           double* Tu, double* Tv, int* status, void* stream);
+
 /* ---- next row: SpIN on the matrix-free kernel operators (methods/spin.py) ----------------------------------------------
  * The two pieces of SpIN's step that are its own; the moments come from nsvd_tsgram_f64, the term-1 cotangents
  * dphi = Kphi gpi / B1, dKphi = phi gpi / B1 (Covariance.backward, spin.py:76-100) from nsvd_ts_rotate, and the parameter

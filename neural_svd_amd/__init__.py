@@ -5,7 +5,7 @@ this package is the host-side mirror of the reference's Python interface for tha
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib", "SketchyRetrieval", "evaluate_truncations", "Nystrom", "run_nystrom", "DotKernelOperator",
+__all__ = ["_lib", "SketchyRetrieval", "evaluate_truncations", "Nystrom", "run_nystrom", "NystromSVD", "DotKernelOperator",
            "SpIN", "SpinKernelTrainer", "PairedFunctions", "KernelSvdTrainer", "gaussian_cross_singular_values",
            "gaussian_cross_modes", "kernel_singular_values"]
 
@@ -19,6 +19,9 @@ def __getattr__(name):
     if name in ("Nystrom", "run_nystrom"):  # the Nystrom baseline (nystrom.py), the same way
         from . import nystrom
         return getattr(nystrom, name)
+    if name == "NystromSVD":  # the truncated-SVD baseline of the kernel SVD operators (nystrom_svd.py), the same way
+        from . import nystrom_svd
+        return nystrom_svd.NystromSVD
     if name == "DotKernelOperator":  # the dot-product kernel operator (kernel_ops.py), the same way
         from . import kernel_ops
         return kernel_ops.DotKernelOperator

@@ -186,6 +186,9 @@ SIGNATURES = {
     "nsvd_tsgram_f64": (_I, [_P, C.c_long, _P, C.c_long, _I, _I, _P, _P, _P, _Z, _P]),
     "nsvd_ritz_step_f64": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "nsvd_ts_rotate": (_I, [_P, C.c_long, _I, _I, _P, _I, _I, _P, C.c_long, _P]),
+    "nsvd_tsgram3_f64_workspace_bytes": (_Z, [_I, _I]),
+    "nsvd_tsgram3_f64": (_I, [_P, C.c_long, _P, C.c_long, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "nsvd_svd_ritz_step_f64": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nsvd_spin_solve": (_I, [_P, _Dbl, _P, _Dbl, _I, _Dbl, _Dbl, _P, _P, _P, _P, _P, _P, _P]),
     "nsvd_spin_state_floats": (_Z, [C.POINTER(ModelDesc)]),
     "nsvd_spin_jac_workspace_bytes": (_Z, [C.POINTER(ModelDesc), _I]),

@@ -1095,6 +1095,78 @@ def ts_rotate(X: torch.Tensor, T: torch.Tensor, k: Optional[int] = None,
     return out
 
 
+# ---- the dense side of the truncated-SVD baseline (csrc/nystrom_svd.hip; the loop is neural_svd_amd/nystrom_svd.py) ---
+def tsgram3_workspace(n: int, m: int, device) -> torch.Tensor:
+    b = _lib.load().nsvd_tsgram3_f64_workspace_bytes(int(n), int(m))
+    if b == 0:
+        raise NsvdError(f"nsvd_tsgram3_f64_workspace_bytes: unsupported shape n={n} m={m} (n >= 1, 1 <= m <= 80)")
+    return torch.empty(b, dtype=torch.uint8, device=device)
+
+
+def tsgram3_f64(X: torch.Tensor, Y: torch.Tensor, ws: Optional[torch.Tensor] = None,
+                out_xtx: Optional[torch.Tensor] = None, out_xty: Optional[torch.Tensor] = None,
+                out_yty: Optional[torch.Tensor] = None):
+    """(X^T X, X^T Y, Y^T Y) as (m, m) float64 from (n, m) float32 blocks in one pass (nsvd_tsgram3_f64): each row tile
+    of X and Y is staged once for all three; products and sums in float64, no atomics, bit-reproducible. X may be Y."""
+    xp, ldx = _rows_ptr(X, "X")
+    n, m = X.shape
+    if tuple(Y.shape) != (n, m):
+        raise NsvdError("tsgram3_f64: Y must have X's shape")
+    yp, ldy = _rows_ptr(Y, "Y")
+    lib = _lib.load()
+    outs = []
+    for o, name in ((out_xtx, "out_xtx"), (out_xty, "out_xty"), (out_yty, "out_yty")):
+        if o is None:
+            o = torch.empty((m, m), dtype=torch.float64, device=X.device)
+        elif tuple(o.shape) != (m, m):
+            raise NsvdError(f"tsgram3_f64: {name} must be (m, m)")
+        outs.append(o)
+    if ws is None:
+        ws = torch.empty(max(lib.nsvd_tsgram3_f64_workspace_bytes(n, m), 256), dtype=torch.uint8, device=X.device)
+    f64 = torch.float64
+    rc = lib.nsvd_tsgram3_f64(xp, ldx, yp, ldy, n, m, _ptr(outs[0], "out_xtx", f64), _ptr(outs[1], "out_xty", f64),
+                              _ptr(outs[2], "out_yty", f64), ws.data_ptr(), ws.numel(), _stream())
+    check(rc, "nsvd_tsgram3_f64")
+    return outs[0], outs[1], outs[2]
+
+
+def svd_ritz_step_f64(PtU: torch.Tensor, RtV: torch.Tensor, Sp: torch.Tensor, Sr: torch.Tensor, status: torch.Tensor,
+                      Cu: Optional[torch.Tensor] = None, Cv: Optional[torch.Tensor] = None,
+                      sigma: Optional[torch.Tensor] = None, resid_l: Optional[torch.Tensor] = None,
+                      resid_r: Optional[torch.Tensor] = None, A: Optional[torch.Tensor] = None,
+                      B: Optional[torch.Tensor] = None, Tu: Optional[torch.Tensor] = None,
+                      Tv: Optional[torch.Tensor] = None):
+    """The m x m solve of one two-sided block iteration (nsvd_svd_ritz_step_f64), float64: with Hl = PtU^T, Hr = RtV,
+    (Hl + Hr) / 2 = A diag(sigma) B^T (sigma descending), Mp = B^T Sp B, Mr = A^T Sr A,
+    resid_l_k = sqrt(max(Mp_kk - 2 sigma_k (A^T Hl B)_kk + sigma_k^2 (A^T Cu A)_kk, 0)),
+    resid_r_k = sqrt(max(Mr_kk - 2 sigma_k (A^T Hr B)_kk + sigma_k^2 (B^T Cv B)_kk, 0)) (Cu / Cv None: the identity),
+    Tu = B chol(Mp)^-1, Tv = A chol(Mr)^-1. status: (1,) int32, RITZ_* bits are OR-ed in (zero it first).
+    Returns (sigma, resid_l, resid_r, A, B, Tu, Tv)."""
+    if PtU.dim() != 2 or PtU.shape[0] != PtU.shape[1]:
+        raise NsvdError("svd_ritz_step_f64: PtU must be (m, m)")
+    m = PtU.shape[0]
+    dev = PtU.device
+    for o, name in ((RtV, "RtV"), (Sp, "Sp"), (Sr, "Sr"), (Cu, "Cu"), (Cv, "Cv")):
+        if o is not None and tuple(o.shape) != (m, m):
+            raise NsvdError(f"svd_ritz_step_f64: {name} must be (m, m)")
+    f64 = torch.float64
+    sigma, resid_l, resid_r = (torch.empty(m, dtype=f64, device=dev) if o is None else o
+                               for o in (sigma, resid_l, resid_r))
+    A, B, Tu, Tv = (torch.empty((m, m), dtype=f64, device=dev) if o is None else o for o in (A, B, Tu, Tv))
+    if any(o.numel() != m for o in (sigma, resid_l, resid_r)) or any(tuple(o.shape) != (m, m) for o in (A, B, Tu, Tv)):
+        raise NsvdError("svd_ritz_step_f64: sigma, resid_l, resid_r (m); A, B, Tu, Tv (m, m)")
+    if status.numel() < 1:
+        raise NsvdError("svd_ritz_step_f64: status must hold one int32")
+    rc = _lib.load().nsvd_svd_ritz_step_f64(_ptr(PtU, "PtU", f64), _ptr(RtV, "RtV", f64), _ptr(Sp, "Sp", f64),
+                                            _ptr(Sr, "Sr", f64), _ptr(Cu, "Cu", f64), _ptr(Cv, "Cv", f64), m,
+                                            _ptr(sigma, "sigma", f64), _ptr(resid_l, "resid_l", f64),
+                                            _ptr(resid_r, "resid_r", f64), _ptr(A, "A", f64), _ptr(B, "B", f64),
+                                            _ptr(Tu, "Tu", f64), _ptr(Tv, "Tv", f64),
+                                            _ptr(status, "status", torch.int32), _stream())
+    check(rc, "nsvd_svd_ritz_step_f64")
+    return sigma, resid_l, resid_r, A, B, Tu, Tv
+
+
 # ---- SpIN on the kernel-operator path (csrc/spin.hip; the step is neural_svd_amd/spin.py) -----------------------------
 SPIN_MAX_L = 64
 
@@ -1557,7 +1629,7 @@ def cdk_step(desc: "_lib.CdkStepDesc", x: torch.Tensor, y: torch.Tensor, towers:
 for _name in ("fourier_features", "operator_forward", "operator_features", "operator_sample_features",
               "operator_sample_features_dev", "rmsprop_ema_step_dev", "opt_step_dev",
               "operator_backward", "model_forward", "model_backward", "evd_moments", "evd_loss_grad", "evd_loss_fused",
-              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_opt_step", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "rbf_apply", "dot_apply", "dot_apply_pair", "tsgram_f64", "ritz_step_f64", "ts_rotate", "cdk_loss_forward",
+              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_opt_step", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "rbf_apply", "dot_apply", "dot_apply_pair", "tsgram_f64", "ritz_step_f64", "ts_rotate", "tsgram3_f64", "svd_ritz_step_f64", "cdk_loss_forward",
               "cdk_loss_backward", "rmsprop_ema_step", "opt_step", "spectrum_accumulate", "row_normalize",
               "row_normalize_backward", "tower_forward", "tower_backward", "cdk_step", "to_bf16", "gemm_bf16"):
     globals()[_name] = _on_tensor_device(globals()[_name])

@@ -4,6 +4,13 @@
     python scripts/train_kernel_svd.py [--steps 20000 --dim 2 --sigma-x 1 --sigma-y 0.5 --ell 1.5 --L 10 --B 8192]
     python scripts/train_kernel_svd.py --kind polynomial --dim 3 --degree 2 --L 10 [--gamma 1 --coef0 1]
     python scripts/train_kernel_svd.py --kind arccos1 --dim 3
+    python scripts/train_kernel_svd.py --kind exponential --baseline 8192
+
+--baseline N: draw N points a side from the two measures, run the matrix-free truncated SVD of their cross Gram
+(neural_svd_amd.NystromSVD: the singular values of k(xs, ys) / N) and print its singular values as a comparison column -
+the only one for the exponential and arccos1 kinds, an extra one beside the closed form otherwise - with the relative
+error of the learned quotients against it; the record gains baseline_n, baseline_svals, baseline_iterations,
+baseline_seconds, rel_err_vs_baseline. Without the flag the output and the record are as before.
 
 --kind gaussian (the default, described below) | exponential (--ell) | polynomial (--gamma --coef0 --degree:
 k = (gamma x.y + coef0)^degree) | arccos1 (the order-1 arc-cosine kernel). The radial kinds run on nsvd_rbf_apply_pair,
@@ -25,6 +32,7 @@ kernel_ops.kernel_singular_values on --n-eval held-out samples a side beside the
 reported as they come out."""
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -40,6 +48,7 @@ from neural_svd_amd.kernel_ops import (DotKernelOperator, MatrixFreeKernelOperat
                                        gaussian_cross_singular_values, kernel_singular_values,
                                        polynomial_cross_singular_values)
 from neural_svd_amd.kernel_svd import KernelSvdTrainer  # noqa: E402
+from neural_svd_amd.nystrom_svd import NystromSVD  # noqa: E402
 
 
 def two_call(op_class):
@@ -79,6 +88,8 @@ def main():
     ap.add_argument("--fourier-scale", type=float, default=0.3)
     ap.add_argument("--n-eval", type=int, default=16384)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--baseline", type=int, default=None, metavar="N",
+                    help="comparison column: NystromSVD on N fresh points a side")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -129,6 +140,24 @@ def main():
     names = ("nsvd_rbf_apply", "nsvd_rbf_apply_pair") if radial else ("nsvd_dot_apply", "nsvd_dot_apply_pair")
     print(f"steps/s {rec['steps_per_s']} (two {names[0]} calls in place of {names[1]}: "
           f"{rec['two_call_base_path_steps_per_s']})")
+    base = None
+    if a.baseline is not None:
+        # a polynomial kernel has finite rank: the block may not be wider than it (NystromSVD's note on oversample)
+        rank = math.comb(a.dim + a.degree, a.degree) if a.kind == "polynomial" else a.baseline
+        bdim = min(a.L, rank, a.baseline)
+        gen_b = torch.Generator(device=dev).manual_seed(a.seed + 2000)
+        xs_b = a.sigma_x * torch.randn(a.baseline, a.dim, device=dev, generator=gen_b)
+        ys_b = a.sigma_y * torch.randn(a.baseline, a.dim, device=dev, generator=gen_b)
+        sol = NystromSVD(op, xs_b, ys_b, bdim, oversample=min(8, rank - bdim), seed=a.seed)
+        base = np.full(a.L, np.nan)
+        base[:bdim] = sol.svals.double().cpu().numpy()
+        ok = np.isfinite(base) & (base > 0)
+        rel_b = np.full(a.L, np.nan)
+        rel_b[ok] = np.abs(got["svals"][ok] - base[ok]) / base[ok]
+        rec.update(baseline_n=a.baseline, baseline_svals=[None if np.isnan(v) else float(v) for v in base],
+                   baseline_iterations=sol.iterations, baseline_seconds=round(sol.training_time, 4),
+                   baseline_converged=bool(sol.converged),
+                   rel_err_vs_baseline=[None if np.isnan(v) else float(v) for v in rel_b])
     if s is not None:
         nz = s > 0  # (a polynomial kernel has finite rank: no relative error beyond it)
         rel = np.full(a.L, np.nan)
@@ -136,13 +165,27 @@ def main():
         rec.update(singular_closed_form=[float(v) for v in s], rel_err=[None if np.isnan(v) else float(v) for v in rel],
                    rel_err_leading_three=[float(v) for v in rel[:3][nz[:3]]], rel_err_mean=float(rel[nz].mean()),
                    rel_err_max=float(rel[nz].max()), rank_within_L=int(nz.sum()))
+    def err(v):
+        return "-       " if np.isnan(v) else f"{v:.2e}"
+    if s is not None and base is not None:
+        print(f"  k           learned       closed form   rel err   baseline n={a.baseline}   rel err")
+        for k in range(a.L):
+            print(f"{k:3d}  {got['svals'][k]:16.8e}  {s[k]:16.8e}  {err(rel[k])}  {base[k]:16.8e}  {err(rel_b[k])}")
+    elif s is not None:
         print("  k           learned       closed form   rel err")
         for k in range(a.L):
             print(f"{k:3d}  {got['svals'][k]:16.8e}  {s[k]:16.8e}  " + (f"{rel[k]:.2e}" if nz[k] else "-"))
+    elif base is not None:
+        print(f"  k           learned   baseline n={a.baseline}   rel err   (no closed form for this kind)")
+        for k in range(a.L):
+            print(f"{k:3d}  {got['svals'][k]:16.8e}  {base[k]:16.8e}  {err(rel_b[k])}")
     else:
         print("  k           learned   (no closed form for this kind)")
         for k in range(a.L):
             print(f"{k:3d}  {got['svals'][k]:16.8e}")
+    if base is not None:
+        print(f"baseline: NystromSVD on {a.baseline} points a side, {rec['baseline_iterations']} iterations, "
+              f"{rec['baseline_seconds']} s, converged {rec['baseline_converged']}")
     print(json.dumps(rec))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     json.dump(rec, open(a.out, "w"), indent=1)
