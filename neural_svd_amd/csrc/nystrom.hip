@@ -2,7 +2,8 @@
 // methods/nystrom.py:8-47 - Nystrom, Nystrom.evd, run_nystrom - which forms the n x n Gram matrix and calls a host
 // eigh on it) needs beside the matrix-free product of rbf_apply.hip to find the top L <= 64 eigenpairs of
 // G = k(xs, xs) / n by block subspace iteration with Rayleigh-Ritz (neural_svd_amd/nystrom.py):
-//   nsvd_tsgram_f64     XtX = X^T X, XtY = X^T Y of two (n, m) float32 blocks, products and sums in float64
+//   nsvd_tsgram_f64     XtX = X^T X, XtY = X^T Y of two (n, m) float32 blocks, products and sums in float64 (the
+//                       kernels and the body of the entry point are ts_dense.h's, shared with nystrom_svd.hip)
 //   nsvd_ritz_step_f64  the m x m solve of one iteration in ONE workgroup, float64, matrices in LDS:
 //                       eigh(sym(A)) = Q diag(theta) Q^T (cyclic Jacobi, round-robin parallel ordering),
 //                       M = Q^T S Q, residuals sqrt(max(M_kk - theta_k^2 (2 - q_k^T C q_k), 0)), R = chol(M),
@@ -11,91 +12,12 @@
 // m <= 80 throughout (64 pairs + 16 columns of oversampling). Every device loop has a trip count bounded by an argument
 // or a constant; nothing waits on a data-dependent flag. No atomics: the row slices of the Gram are reduced in slice
 // order by a second launch, so every result is bit-reproducible.
-#include "nsvd_kernels.h"
+#include "ts_dense.h"
 
 namespace {
 
-constexpr int NY_MAXM = 80;     // block width limit
-constexpr int NY_THREADS = 256;
-constexpr int NY_CB = 5;        // column blocks of 16: 5 * 16 = NY_MAXM
-constexpr int TS_ROWS = 32;     // rows of X (and Y) per LDS chunk of the Gram kernel
-constexpr int TS_MAX_SLICES = 128, TS_SLICE_ROWS = 64;
 constexpr int RZ_SWEEPS = 30;   // Jacobi sweep cap (float64, m <= 80: 6-10 sweeps in practice)
 constexpr int RO_ROWS = 32;     // rows of X per workgroup of the rotation kernel
-
-int ts_slices(int n) {
-    const int s = nsvd_cdiv(n, TS_SLICE_ROWS);
-    return s < 1 ? 1 : (s > TS_MAX_SLICES ? TS_MAX_SLICES : s);
-}
-
-// part[slice][0] = X_slice^T X_slice, part[slice][1] = X_slice^T Y_slice (each (m, m)). Thread (ti, tj) = (t / 16, t % 16)
-// owns the outputs (ti + 16 a, tj + 16 b), a, b < 5: per row of the chunk five reads of x (two addresses per half
-// wave: broadcast), five of y (16 consecutive floats) and 25 float64 FMAs per product.
-template <bool XX, bool XY>
-__global__ void __launch_bounds__(NY_THREADS) tsgram_partial_kernel(const float* __restrict__ X, size_t ldx,
-                                                                    const float* __restrict__ Y, size_t ldy, int n, int m,
-                                                                    int S, double* __restrict__ part) {
-    __shared__ float xs[TS_ROWS][NY_MAXM];
-    __shared__ float ys[XY ? TS_ROWS : 1][NY_MAXM];
-    const int t = threadIdx.x, ti = t >> 4, tj = t & 15, slice = blockIdx.x;
-    const int r0 = (int)((long)n * slice / S), r1 = (int)((long)n * (slice + 1) / S);
-    double axx[NY_CB][NY_CB], axy[NY_CB][NY_CB];
-#pragma unroll
-    for (int a = 0; a < NY_CB; ++a)
-#pragma unroll
-        for (int b = 0; b < NY_CB; ++b) axx[a][b] = axy[a][b] = 0.0;
-    for (int rb = r0; rb < r1; rb += TS_ROWS) {
-        const int rows = min(TS_ROWS, r1 - rb);
-        __syncthreads();
-        for (int e = t; e < TS_ROWS * NY_MAXM; e += NY_THREADS) {
-            const int r = e / NY_MAXM, c = e - r * NY_MAXM;
-            const bool in = r < rows && c < m;
-            xs[r][c] = in ? X[(size_t)(rb + r) * ldx + c] : 0.f;
-            if (XY) ys[r][c] = in ? Y[(size_t)(rb + r) * ldy + c] : 0.f;
-        }
-        __syncthreads();
-        for (int r = 0; r < rows; ++r) {
-            double xa[NY_CB], xb[NY_CB], yb[NY_CB];
-#pragma unroll
-            for (int a = 0; a < NY_CB; ++a) {
-                xa[a] = (double)xs[r][ti + 16 * a];
-                if (XX) xb[a] = (double)xs[r][tj + 16 * a];
-                if (XY) yb[a] = (double)ys[r][tj + 16 * a];
-            }
-#pragma unroll
-            for (int a = 0; a < NY_CB; ++a)
-#pragma unroll
-                for (int b = 0; b < NY_CB; ++b) {
-                    if (XX) axx[a][b] = fma(xa[a], xb[b], axx[a][b]);
-                    if (XY) axy[a][b] = fma(xa[a], yb[b], axy[a][b]);
-                }
-        }
-    }
-    double* pxx = part + (size_t)slice * 2 * m * m;
-    double* pxy = pxx + (size_t)m * m;
-#pragma unroll
-    for (int a = 0; a < NY_CB; ++a)
-#pragma unroll
-        for (int b = 0; b < NY_CB; ++b) {
-            const int i = ti + 16 * a, j = tj + 16 * b;
-            if (i < m && j < m) {
-                if (XX) pxx[i * m + j] = axx[a][b];
-                if (XY) pxy[i * m + j] = axy[a][b];
-            }
-        }
-}
-
-// out[e] = sum over slices in slice order; blockIdx.y: 0 = XtX, 1 = XtY (a null output is skipped)
-__global__ void __launch_bounds__(NY_THREADS) tsgram_reduce_kernel(const double* __restrict__ part, int m, int S,
-                                                                   double* __restrict__ XtX, double* __restrict__ XtY) {
-    double* out = blockIdx.y == 0 ? XtX : XtY;
-    const int e = blockIdx.x * NY_THREADS + threadIdx.x, mm = m * m;
-    if (!out || e >= mm) return;
-    const double* p = part + (size_t)blockIdx.y * mm + e;
-    double s = 0.0;
-    for (int sl = 0; sl < S; ++sl) s += p[(size_t)sl * 2 * mm];
-    out[e] = s;
-}
 
 // out[rows of this workgroup][c < k] = sum_kk X[row][kk] T[kk][c]. T's first k columns wait in LDS as float64 (rows of
 // NY_MAXM, zero beyond k); thread (tr, tc) = (t / 16, t % 16) owns rows tr, tr + 16 and columns tc + 16 b.
@@ -417,31 +339,12 @@ void ritz_set_lds_limit() {
 
 }  // namespace
 
-extern "C" size_t nsvd_tsgram_f64_workspace_bytes(int n, int m) {
-    if (n <= 0 || m <= 0 || m > NY_MAXM) return 0;
-    return nsvd_align((size_t)ts_slices(n) * 2 * m * m * sizeof(double));
-}
+extern "C" size_t nsvd_tsgram_f64_workspace_bytes(int n, int m) { return ts_gram_workspace_bytes(n, m, 2); }
 
 extern "C" int nsvd_tsgram_f64(const float* X, long ldx, const float* Y, long ldy, int n, int m, double* XtX,
                                double* XtY, void* ws, size_t ws_bytes, void* stream) {
-    if (!X || !ws || n <= 0 || m <= 0 || ldx < m) return NSVD_EINVAL;
     if (!XtX && !XtY) return NSVD_EINVAL;
-    if (XtY && (!Y || ldy < m)) return NSVD_EINVAL;
-    if (m > NY_MAXM) return NSVD_EUNSUPPORTED;
-    if (ws_bytes < nsvd_tsgram_f64_workspace_bytes(n, m) || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
-    const int S = ts_slices(n);
-    hipStream_t s = (hipStream_t)stream;
-    double* part = (double*)ws;
-    if (XtX && XtY)
-        tsgram_partial_kernel<true, true><<<S, NY_THREADS, 0, s>>>(X, (size_t)ldx, Y, (size_t)ldy, n, m, S, part);
-    else if (XtX)
-        tsgram_partial_kernel<true, false><<<S, NY_THREADS, 0, s>>>(X, (size_t)ldx, nullptr, 0, n, m, S, part);
-    else
-        tsgram_partial_kernel<false, true><<<S, NY_THREADS, 0, s>>>(X, (size_t)ldx, Y, (size_t)ldy, n, m, S, part);
-    NSVD_CHECK_LAUNCH();
-    tsgram_reduce_kernel<<<dim3(nsvd_cdiv(m * m, NY_THREADS), 2), NY_THREADS, 0, s>>>(part, m, S, XtX, XtY);
-    NSVD_CHECK_LAUNCH();
-    return 0;
+    return ts_gram<false>(X, ldx, Y, ldy, n, m, XtX, XtY, nullptr, ws, ws_bytes, stream);
 }
 
 extern "C" int nsvd_ritz_step_f64(const double* S, const double* A, const double* C, int m, double* theta,

@@ -3,102 +3,21 @@
 // products of rbf_apply_pair.hip / dot_apply_pair.hip, which return P = C V and R = C^T U in one pass:
 //   nsvd_tsgram3_f64         XtX = X^T X, XtY = X^T Y, YtY = Y^T Y of two (n, m) float32 blocks in ONE pass: each row tile
 //                            of X and Y is staged once and feeds all three float64 accumulations (nystrom.hip's
-//                            nsvd_tsgram_f64 needs two calls = four launches for the same three matrices)
+//                            nsvd_tsgram_f64 needs two calls = four launches for the same three matrices). The kernels
+//                            are ts_dense.h's: the <true, true, true> instance of nsvd_tsgram_f64's, three slots a slice
 //   nsvd_svd_ritz_step_f64   the m x m solve of one iteration in ONE workgroup, float64, matrices in LDS:
 //                            H = (PtU^T + RtV) / 2 = A diag(sigma) B^T (one-sided Jacobi on the columns of H, round-robin
 //                            parallel ordering), Mp = B^T Sp B, Mr = A^T Sr A, the two residuals in their full
 //                            three-term form, Tu = B chol(Mp)^-1, Tv = A chol(Mr)^-1
-// m <= 80 throughout, as in nystrom.hip (whose nsvd_ts_rotate applies Tu and Tv). Every device loop has a trip count
-// bounded by an argument or a constant; nothing waits on a data-dependent flag. No atomics: the row slices of the Gram
-// are reduced in slice order by a second launch, so every result is bit-reproducible.
-#include "nsvd_kernels.h"
+// m <= 80 throughout (ts_dense.h's limits, shared with nystrom.hip, whose nsvd_ts_rotate applies Tu and Tv). Every
+// device loop has a trip count bounded by an argument or a constant; nothing waits on a data-dependent flag. No atomics:
+// the row slices of the Gram are reduced in slice order by a second launch, so every result is bit-reproducible.
+#include "ts_dense.h"
 
 namespace {
 
-constexpr int NY_MAXM = 80;     // block width limit (nystrom.hip)
-constexpr int NY_THREADS = 256;
-constexpr int NY_CB = 5;        // column blocks of 16: 5 * 16 = NY_MAXM
-constexpr int TS_ROWS = 32;     // rows of X and Y per LDS chunk of the Gram kernel
-constexpr int TS_MAX_SLICES = 128, TS_SLICE_ROWS = 64;  // nsvd_tsgram_f64's split rule
 constexpr int SV_MAX_THREADS = 512, SV_WIDE_M = 32;  // the small step runs 512 threads above m = 32, 256 up to it
 constexpr int SV_SWEEPS = 40;   // one-sided Jacobi sweep cap (float64, m <= 80: at most 19 sweeps on graded spectra)
-
-int ts_slices(int n) {
-    const int s = nsvd_cdiv(n, TS_SLICE_ROWS);
-    return s < 1 ? 1 : (s > TS_MAX_SLICES ? TS_MAX_SLICES : s);
-}
-
-// part[slice][0 | 1 | 2] = X_s^T X_s | X_s^T Y_s | Y_s^T Y_s (each (m, m)). Thread (ti, tj) = (t / 16, t % 16) owns the
-// outputs (ti + 16 a, tj + 16 b), a, b < 5, of all three: per row of the chunk ten reads of x and ten of y (the ti side
-// two addresses per half wave: broadcast; the tj side 16 consecutive floats) and 75 float64 FMAs.
-__global__ void __launch_bounds__(NY_THREADS) tsgram3_partial_kernel(const float* __restrict__ X, size_t ldx,
-                                                                     const float* __restrict__ Y, size_t ldy, int n, int m,
-                                                                     int S, double* __restrict__ part) {
-    __shared__ float xs[TS_ROWS][NY_MAXM];
-    __shared__ float ys[TS_ROWS][NY_MAXM];
-    const int t = threadIdx.x, ti = t >> 4, tj = t & 15, slice = blockIdx.x;
-    const int r0 = (int)((long)n * slice / S), r1 = (int)((long)n * (slice + 1) / S);
-    double axx[NY_CB][NY_CB], axy[NY_CB][NY_CB], ayy[NY_CB][NY_CB];
-#pragma unroll
-    for (int a = 0; a < NY_CB; ++a)
-#pragma unroll
-        for (int b = 0; b < NY_CB; ++b) axx[a][b] = axy[a][b] = ayy[a][b] = 0.0;
-    for (int rb = r0; rb < r1; rb += TS_ROWS) {
-        const int rows = min(TS_ROWS, r1 - rb);
-        __syncthreads();
-        for (int e = t; e < TS_ROWS * NY_MAXM; e += NY_THREADS) {
-            const int r = e / NY_MAXM, c = e - r * NY_MAXM;
-            const bool in = r < rows && c < m;
-            xs[r][c] = in ? X[(size_t)(rb + r) * ldx + c] : 0.f;
-            ys[r][c] = in ? Y[(size_t)(rb + r) * ldy + c] : 0.f;
-        }
-        __syncthreads();
-        for (int r = 0; r < rows; ++r) {
-            double xa[NY_CB], xb[NY_CB], ya[NY_CB], yb[NY_CB];
-#pragma unroll
-            for (int a = 0; a < NY_CB; ++a) {
-                xa[a] = (double)xs[r][ti + 16 * a];
-                xb[a] = (double)xs[r][tj + 16 * a];
-                ya[a] = (double)ys[r][ti + 16 * a];
-                yb[a] = (double)ys[r][tj + 16 * a];
-            }
-#pragma unroll
-            for (int a = 0; a < NY_CB; ++a)
-#pragma unroll
-                for (int b = 0; b < NY_CB; ++b) {
-                    axx[a][b] = fma(xa[a], xb[b], axx[a][b]);
-                    axy[a][b] = fma(xa[a], yb[b], axy[a][b]);
-                    ayy[a][b] = fma(ya[a], yb[b], ayy[a][b]);
-                }
-        }
-    }
-    const size_t mm = (size_t)m * m;
-    double* p = part + (size_t)slice * 3 * mm;
-#pragma unroll
-    for (int a = 0; a < NY_CB; ++a)
-#pragma unroll
-        for (int b = 0; b < NY_CB; ++b) {
-            const int i = ti + 16 * a, j = tj + 16 * b;
-            if (i < m && j < m) {
-                p[i * m + j] = axx[a][b];
-                p[mm + i * m + j] = axy[a][b];
-                p[2 * mm + i * m + j] = ayy[a][b];
-            }
-        }
-}
-
-// out[e] = sum over slices in slice order; blockIdx.y: 0 = XtX, 1 = XtY, 2 = YtY
-__global__ void __launch_bounds__(NY_THREADS) tsgram3_reduce_kernel(const double* __restrict__ part, int m, int S,
-                                                                    double* __restrict__ XtX, double* __restrict__ XtY,
-                                                                    double* __restrict__ YtY) {
-    double* out = blockIdx.y == 0 ? XtX : (blockIdx.y == 1 ? XtY : YtY);
-    const int e = blockIdx.x * NY_THREADS + threadIdx.x, mm = m * m;
-    if (e >= mm) return;
-    const double* p = part + (size_t)blockIdx.y * mm + e;
-    double s = 0.0;
-    for (int sl = 0; sl < S; ++sl) s += p[(size_t)sl * 3 * mm];
-    out[e] = s;
-}
 
 // ---- the m x m solve ------------------------------------------------------------------------------------------------
 // LDS: three (m, ld) float64 matrices, ld = m | 1 (odd: a column walk touches every bank pair once) - 155 KB of the
@@ -448,24 +367,12 @@ void svd_ritz_set_lds_limit() {
 
 }  // namespace
 
-extern "C" size_t nsvd_tsgram3_f64_workspace_bytes(int n, int m) {
-    if (n <= 0 || m <= 0 || m > NY_MAXM) return 0;
-    return nsvd_align((size_t)ts_slices(n) * 3 * m * m * sizeof(double));
-}
+extern "C" size_t nsvd_tsgram3_f64_workspace_bytes(int n, int m) { return ts_gram_workspace_bytes(n, m, 3); }
 
 extern "C" int nsvd_tsgram3_f64(const float* X, long ldx, const float* Y, long ldy, int n, int m, double* XtX,
                                 double* XtY, double* YtY, void* ws, size_t ws_bytes, void* stream) {
-    if (!X || !Y || !XtX || !XtY || !YtY || !ws || n <= 0 || m <= 0 || ldx < m || ldy < m) return NSVD_EINVAL;
-    if (m > NY_MAXM) return NSVD_EUNSUPPORTED;
-    if (ws_bytes < nsvd_tsgram3_f64_workspace_bytes(n, m) || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
-    const int S = ts_slices(n);
-    hipStream_t s = (hipStream_t)stream;
-    double* part = (double*)ws;
-    tsgram3_partial_kernel<<<S, NY_THREADS, 0, s>>>(X, (size_t)ldx, Y, (size_t)ldy, n, m, S, part);
-    NSVD_CHECK_LAUNCH();
-    tsgram3_reduce_kernel<<<dim3(nsvd_cdiv(m * m, NY_THREADS), 3), NY_THREADS, 0, s>>>(part, m, S, XtX, XtY, YtY);
-    NSVD_CHECK_LAUNCH();
-    return 0;
+    if (!XtX || !XtY || !YtY) return NSVD_EINVAL;
+    return ts_gram<true>(X, ldx, Y, ldy, n, m, XtX, XtY, YtY, ws, ws_bytes, stream);
 }
 
 extern "C" int nsvd_svd_ritz_step_f64(const double* PtU, const double* RtV, const double* Sp, const double* Sr,

@@ -1004,40 +1004,52 @@ def _rows_ptr(t: torch.Tensor, name: str) -> Tuple[int, int]:
     return t.data_ptr(), t.stride(0)
 
 
-def tsgram_workspace(n: int, m: int, device) -> torch.Tensor:
-    b = _lib.load().nsvd_tsgram_f64_workspace_bytes(int(n), int(m))
+def _gram_workspace(fn: str, n: int, m: int, device) -> torch.Tensor:
+    b = getattr(_lib.load(), fn + "_workspace_bytes")(int(n), int(m))
     if b == 0:
-        raise NsvdError(f"nsvd_tsgram_f64_workspace_bytes: unsupported shape n={n} m={m} (n >= 1, 1 <= m <= 80)")
+        raise NsvdError(f"{fn}_workspace_bytes: unsupported shape n={n} m={m} (n >= 1, 1 <= m <= 80)")
     return torch.empty(b, dtype=torch.uint8, device=device)
+
+
+def _gram(fn: str, X: torch.Tensor, Y: Optional[torch.Tensor], outs, use, ws: Optional[torch.Tensor]):
+    """What tsgram_f64 and tsgram3_f64 share. fn: the C function; outs: the caller's out_xtx, out_xty(, out_yty), each
+    allocated when None (those with Y only when Y is given) and checked; use: which of them the call is handed.
+    Returns them, None where use is False."""
+    name, f64 = fn[len("nsvd_"):], torch.float64
+    xp, ldx = _rows_ptr(X, "X")
+    n, m = X.shape
+    yp, ldy = None, 0
+    if Y is not None:
+        if tuple(Y.shape) != (n, m):
+            raise NsvdError(f"{name}: Y must have X's shape")
+        yp, ldy = _rows_ptr(Y, "Y")
+    elif not use[0]:
+        raise NsvdError(f"{name}: nothing to compute")
+    lib = _lib.load()
+    names = ("out_xtx", "out_xty", "out_yty")
+    outs = [torch.empty((m, m), dtype=f64, device=X.device) if o is None and u and (i == 0 or Y is not None) else o
+            for i, (o, u) in enumerate(zip(outs, use))]
+    for o, nm in zip(outs, names):
+        if o is not None and tuple(o.shape) != (m, m):
+            raise NsvdError(f"{name}: {nm} must be (m, m)")
+    if ws is None:
+        ws = torch.empty(max(getattr(lib, fn + "_workspace_bytes")(n, m), 256), dtype=torch.uint8, device=X.device)
+    outs = [o if u else None for o, u in zip(outs, use)]
+    rc = getattr(lib, fn)(xp, ldx, yp, ldy, n, m, *(_ptr(o, nm, f64) for o, nm in zip(outs, names)), ws.data_ptr(),
+                          ws.numel(), _stream())
+    check(rc, fn)
+    return outs
+
+
+def tsgram_workspace(n: int, m: int, device) -> torch.Tensor:
+    return _gram_workspace("nsvd_tsgram_f64", n, m, device)
 
 
 def tsgram_f64(X: torch.Tensor, Y: Optional[torch.Tensor] = None, xtx: bool = True, ws: Optional[torch.Tensor] = None,
                out_xtx: Optional[torch.Tensor] = None, out_xty: Optional[torch.Tensor] = None):
     """(X^T X, X^T Y) as (m, m) float64 from (n, m) float32 blocks (nsvd_tsgram_f64): products and sums in float64, no
     atomics, bit-reproducible. Y None: only X^T X (the second value is None); xtx False: only X^T Y."""
-    xp, ldx = _rows_ptr(X, "X")
-    n, m = X.shape
-    yp, ldy = None, 0
-    if Y is not None:
-        if tuple(Y.shape) != (n, m):
-            raise NsvdError("tsgram_f64: Y must have X's shape")
-        yp, ldy = _rows_ptr(Y, "Y")
-    elif not xtx:
-        raise NsvdError("tsgram_f64: nothing to compute")
-    lib = _lib.load()
-    if xtx and out_xtx is None:
-        out_xtx = torch.empty((m, m), dtype=torch.float64, device=X.device)
-    if Y is not None and out_xty is None:
-        out_xty = torch.empty((m, m), dtype=torch.float64, device=X.device)
-    for o, name in ((out_xtx, "out_xtx"), (out_xty, "out_xty")):
-        if o is not None and tuple(o.shape) != (m, m):
-            raise NsvdError(f"tsgram_f64: {name} must be (m, m)")
-    if ws is None:
-        ws = torch.empty(max(lib.nsvd_tsgram_f64_workspace_bytes(n, m), 256), dtype=torch.uint8, device=X.device)
-    rc = lib.nsvd_tsgram_f64(xp, ldx, yp, ldy, n, m, _ptr(out_xtx if xtx else None, "out_xtx", torch.float64),
-                             _ptr(out_xty, "out_xty", torch.float64), ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_tsgram_f64")
-    return (out_xtx if xtx else None), out_xty
+    return tuple(_gram("nsvd_tsgram_f64", X, Y, (out_xtx, out_xty), (xtx, True), ws))
 
 
 def ritz_step_f64(S: torch.Tensor, A: Optional[torch.Tensor], status: torch.Tensor,
@@ -1097,10 +1109,7 @@ def ts_rotate(X: torch.Tensor, T: torch.Tensor, k: Optional[int] = None,
 
 # ---- the dense side of the truncated-SVD baseline (csrc/nystrom_svd.hip; the loop is neural_svd_amd/nystrom_svd.py) ---
 def tsgram3_workspace(n: int, m: int, device) -> torch.Tensor:
-    b = _lib.load().nsvd_tsgram3_f64_workspace_bytes(int(n), int(m))
-    if b == 0:
-        raise NsvdError(f"nsvd_tsgram3_f64_workspace_bytes: unsupported shape n={n} m={m} (n >= 1, 1 <= m <= 80)")
-    return torch.empty(b, dtype=torch.uint8, device=device)
+    return _gram_workspace("nsvd_tsgram3_f64", n, m, device)
 
 
 def tsgram3_f64(X: torch.Tensor, Y: torch.Tensor, ws: Optional[torch.Tensor] = None,
@@ -1108,26 +1117,7 @@ def tsgram3_f64(X: torch.Tensor, Y: torch.Tensor, ws: Optional[torch.Tensor] = N
                 out_yty: Optional[torch.Tensor] = None):
     """(X^T X, X^T Y, Y^T Y) as (m, m) float64 from (n, m) float32 blocks in one pass (nsvd_tsgram3_f64): each row tile
     of X and Y is staged once for all three; products and sums in float64, no atomics, bit-reproducible. X may be Y."""
-    xp, ldx = _rows_ptr(X, "X")
-    n, m = X.shape
-    if tuple(Y.shape) != (n, m):
-        raise NsvdError("tsgram3_f64: Y must have X's shape")
-    yp, ldy = _rows_ptr(Y, "Y")
-    lib = _lib.load()
-    outs = []
-    for o, name in ((out_xtx, "out_xtx"), (out_xty, "out_xty"), (out_yty, "out_yty")):
-        if o is None:
-            o = torch.empty((m, m), dtype=torch.float64, device=X.device)
-        elif tuple(o.shape) != (m, m):
-            raise NsvdError(f"tsgram3_f64: {name} must be (m, m)")
-        outs.append(o)
-    if ws is None:
-        ws = torch.empty(max(lib.nsvd_tsgram3_f64_workspace_bytes(n, m), 256), dtype=torch.uint8, device=X.device)
-    f64 = torch.float64
-    rc = lib.nsvd_tsgram3_f64(xp, ldx, yp, ldy, n, m, _ptr(outs[0], "out_xtx", f64), _ptr(outs[1], "out_xty", f64),
-                              _ptr(outs[2], "out_yty", f64), ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_tsgram3_f64")
-    return outs[0], outs[1], outs[2]
+    return tuple(_gram("nsvd_tsgram3_f64", X, Y, (out_xtx, out_xty, out_yty), (True, True, True), ws))
 
 
 def svd_ritz_step_f64(PtU: torch.Tensor, RtV: torch.Tensor, Sp: torch.Tensor, Sr: torch.Tensor, status: torch.Tensor,

@@ -37,6 +37,16 @@ from .kernel_ops import MatrixFreeKernelOperator
 MAX_DIM = 64
 
 
+def orthonormalize(X, status, ws=None, S=None, theta=None, resid=None, Q=None, T=None, out=None):
+    """X chol(X^T X)^-1: the (n, k) float32 block X with its columns orthonormalised among themselves (an upper
+    triangular correction; Gram and Cholesky in float64): H.tsgram_f64, H.ritz_step_f64 with A = None, H.ts_rotate.
+    status as for H.ritz_step_f64; ws, S (k, k), theta, resid (k), Q, T (k, k) and out (n, k) are the caller's buffers,
+    allocated where None."""
+    S = H.tsgram_f64(X, None, ws=ws, out_xtx=S)[0]
+    T = H.ritz_step_f64(S, None, status, theta, resid, Q, T)[3]
+    return H.ts_rotate(X, T, X.shape[1], out=out)
+
+
 class _Solve:
     """eigvals (dim,) / eigvecs (n, dim) float32 on the device, iterations, relative residuals (dim,), converged"""
 
@@ -58,10 +68,7 @@ class _Solve:
         small = torch.zeros(2 * m + 1, dtype=f64, device=device)
         theta, resid, status = small[:m], small[m:2 * m], small[2 * m:].view(torch.int32)
         ws = H.tsgram_workspace(n, m, device)
-        # V = V0 chol(V0^T V0)^-1
-        H.tsgram_f64(W, None, ws=ws, out_xtx=S)
-        H.ritz_step_f64(S, None, status, theta, resid, Q, T)
-        H.ts_rotate(W, T, m, out=V)
+        orthonormalize(W, status, ws, S, theta, resid, Q, T, out=V)  # V = V0 chol(V0^T V0)^-1
         H.tsgram_f64(V, None, ws=ws, out_xtx=C)
         self.iterations, self.converged = 0, False
         host = None

@@ -5,8 +5,8 @@ kernel between two samples (the reference has no such baseline; its methods/nyst
 A two-sided block iteration on bases U (n_x, m), V (n_y, m), m = min(n_x, n_y, dim + oversample) <= 80, float32 with
 orthonormal columns:
 
-    U0, V0 = randn (seeded device generator), each orthonormalised as ``Nystrom`` does (H.tsgram_f64, H.ritz_step_f64 with
-    A = None, H.ts_rotate); then per iteration
+    U0, V0 = randn (seeded device generator), each orthonormalised as ``Nystrom`` does (``nystrom.orthonormalize``:
+    H.tsgram_f64, H.ritz_step_f64 with A = None, H.ts_rotate); then per iteration
     1. (P, R) = (C V, C^T U)    ONE apply_pair_raw(xs, ys, g=V, f=U, 1 / sqrt(n_x n_y), ...) of a matrix-free operator
                                 (``RadialKernelOperator``, ``DotKernelOperator``: every kernel value evaluated once; the
                                 base class: two products) - C is never stored; any other callable kernel(a, b) or a
@@ -25,7 +25,7 @@ orthonormal columns:
 
 until max_{k < dim} max(rl_k, rr_k) <= tol * sigma_0 or ``max_iters``; then left = U_prev A[:, :dim],
 right = V_prev B[:, :dim], svals = sigma[:dim], and left and right are orthonormalised once more among themselves
-(H.tsgram_f64, H.ritz_step_f64 with A = None, H.ts_rotate on the dim stored columns: chol(Mp) in float64 leaves U = P Tu
+(``nystrom.orthonormalize`` on the dim stored columns: chol(Mp) in float64 leaves U = P Tu
 orthonormal to eps64 cond(P)^2 only, 1e-4 in the trailing columns of a dim = 56 block on a fast-decaying spectrum; the
 correction is upper triangular and of that size, so it reaches those columns alone). The host reads sigma | rl | rr | status in ONE small copy every
 ``check_every`` iterations; nothing else in the loop synchronises. A flat spectrum converges slowly, and the object says
@@ -41,6 +41,7 @@ import torch
 
 from . import hip_ops as H
 from .kernel_ops import MatrixFreeKernelOperator
+from .nystrom import orthonormalize
 
 MAX_DIM = 64
 
@@ -69,10 +70,7 @@ class _Solve:
         ws_u, ws_v = H.tsgram3_workspace(nx, m, device), H.tsgram3_workspace(ny, m, device)
         # U = U0 chol(U0^T U0)^-1, V = V0 chol(V0^T V0)^-1
         for X0, X, n in ((P, U, nx), (R, V, ny)):
-            ws0 = H.tsgram_workspace(n, m, device)
-            H.tsgram_f64(X0, None, ws=ws0, out_xtx=Sp)
-            H.ritz_step_f64(Sp, None, status, sigma, rl, A, Tu)
-            H.ts_rotate(X0, Tu, m, out=X)
+            orthonormalize(X0, status, H.tsgram_workspace(n, m, device), Sp, sigma, rl, A, Tu, out=X)
         self.iterations, self.converged = 0, False
         host = None
         for it in range(1, max_iters + 1):
@@ -102,13 +100,7 @@ class _Solve:
         # one more orthonormalisation among themselves: the float64 Cholesky of Mp leaves U = P Tu orthonormal to
         # eps64 cond(P)^2 only, and cond(P) reaches 1e6 when dim is large on a fast-decaying spectrum - 1e-4 in the
         # trailing columns. The correction is upper triangular and of that size: it touches those columns alone.
-        out = []
-        for X, Q, n in ((U, A, nx), (V, B, ny)):
-            X0 = H.ts_rotate(X, Q, dim)
-            N = H.tsgram_f64(X0, None, ws=H.tsgram_workspace(n, dim, device))[0]
-            T = H.ritz_step_f64(N, None, status)[3]
-            out.append(H.ts_rotate(X0, T, dim))
-        self.left, self.right = out
+        self.left, self.right = (orthonormalize(H.ts_rotate(X, Q, dim), status) for X, Q in ((U, A), (V, B)))
         if int(status[0]):
             raise H.NsvdError("NystromSVD: the final orthonormalisation met a non-positive Cholesky pivot")
         self.svals = sigma[:dim].to(f32)

@@ -6,7 +6,7 @@ Bounds of the solver tests follow the repository's convention max(floor, 4 x yar
 quantity from the reference's op sequence on the same GPU (a float32 Gram by torch ops, copied to the host, float32
 np.linalg.eigh) against the same float64 oracle. Both are printed by every test.
 
-Measured on an MI355X: the tables in the docstrings of the tests (the whole file: 72 tests in 3.5 s).
+Measured on an MI355X: the tables in the docstrings of the tests (the whole file: 77 tests in 3.5 s).
 """
 import os
 import warnings
@@ -21,6 +21,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TOL = 1e-5
 NS, MS = (1, 63, 64, 65, 1030, 4100), (1, 13, 64, 80)
+# the Gram kernels' slice count stops at 128 from n = 8192 on: 8200 rows go to 128 slices of 64 or 65 rows
+GRAM_SHAPES = [(n, m) for n in NS for m in MS] + [(8200, 13), (8200, 80)]
 
 
 def _rel(got, want):
@@ -35,11 +37,11 @@ def _block(n, m, seed, ld=None):
 
 
 # ---- nsvd_tsgram_f64 --------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("m", MS)
-@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("n,m", GRAM_SHAPES)
 def test_tsgram_against_float64(n, m):
     """X^T X and X^T Y against float64 torch on the same float32 inputs, rel <= 1e-13; Y strided (ld = m + 7); two calls
-    give the same bits. Measured: worst rel 6.6e-15 (n = 4100, m = 80); 2.6e-15 at n = 1030."""
+    give the same bits. Measured: worst rel 1.8e-14 (n = 8200, m = 80: the slice cap); 6.6e-15 at n = 4100, 2.6e-15 at
+    n = 1030."""
     from neural_svd_amd import hip_ops as H
     X, Y = _block(n, m, 1), _block(n, m, 2, ld=m + 7)
     assert Y.stride(0) == m + 7
@@ -93,12 +95,17 @@ def _run_ritz(S, A, C=None):
     return theta.cpu().numpy(), resid.cpu().numpy(), Q.cpu().numpy(), T.cpu().numpy(), int(status.item())
 
 
-@pytest.mark.parametrize("m", (1, 2, 13, 64, 80))
+@pytest.mark.parametrize("m", (1, 2, 13, 16, 17, 33, 64, 80))
 def test_ritz_step_against_numpy(m):
-    """theta to 1e-12 of theta_0; |Q^T Q - I| and |T^T S T - I| <= 1e-10; resid to 1e-9 of theta_0.
+    """theta to 1e-12 of theta_0; |Q^T Q - I| and |T^T S T - I| <= 1e-10; resid to 1e-9 of theta_0. m = 16 is the
+    last width whose m^2 elements take one pass of the 256 threads, 17 the first that takes two; 17 and 33 are odd (a
+    bye in every round of the tournament).
     Measured (theta / Q^T Q / T^T S T / resid; status 0 everywhere):
         m = 2    1.6e-16 / 2.2e-16 / 1.9e-16 / 6.3e-16
         m = 13   3.5e-15 / 4.0e-15 / 5.6e-16 / 1.2e-15
+        m = 16   2.3e-15 / 3.6e-15 / 6.7e-16 / 1.1e-15
+        m = 17   2.0e-15 / 2.9e-15 / 1.0e-15 / 7.4e-16
+        m = 33   5.1e-15 / 7.8e-15 / 3.1e-15 / 1.6e-15
         m = 64   1.4e-14 / 1.5e-14 / 7.9e-15 / 7.7e-15
         m = 80   1.5e-14 / 1.9e-14 / 2.3e-14 / 8.7e-15"""
     V, W, S, A = _ritz_inputs(m)
