@@ -768,6 +768,43 @@ int nsvd_spin_jac_step(const nsvd_model_desc* desc, const nsvd_params* params, c
                        float hard_mul_const, const double* gsigma, double decay, float* J, const nsvd_params* grads,
                        void* ws, size_t ws_bytes, void* stream);
 
+/* ---- next row: SpINx on the matrix-free kernel operators (methods/spinx.py) --------------------------------------------
+ * SpINx keeps SpIN's Cholesky whitening, drops the per-sample Jacobian contraction, differentiates straight through
+ * cholesky(sigma + 1e-3 I) of the BATCH sigma and adds one squared-residual loss per eigenfunction. Its loss is a
+ * function of four L x L moment matrices (nsvd_tsgram_f64 on all rows, nsvd_tsgram3_f64 on (P, K)); these are the two
+ * pieces beside them. NEW SYMBOLS ONLY: NSVD_ABI_VERSION stays 6.
+ *
+ * nsvd_spinx_solve (spinx.py:13-23 SpINxLossFunction.forward with its autograd backward, :92-99 SpINx._compute_loss):
+ *   one workgroup, float64, everything (L, L) contiguous row-major, 2 <= L <= 64 (NSVD_EUNSUPPORTED above). With
+ *       S = s_scale S_raw (all rows), Gpp = g_scale Gpp_raw = P^T P / B1, Gpk = g_scale Gpk_raw = P^T K / B1 (= pi),
+ *       Gkk = g_scale Gkk_raw = K^T K / B1 (S_raw and Gpp_raw may be one pointer), A = cholesky(S + 1e-3 I)^-1, rows a_l:
+ *       lambda_l = a_l^T Gpk a_l, qk_l = a_l^T Gkk a_l, qp_l = a_l^T Gpp a_l
+ *       losses = [sum_l trace_w_l lambda_l | qk_l - lambda_l^2 (2 - qp_l)]  (L + 1; the second part is
+ *                mean_b (K a_l - lambda_l P a_l)^2 because Gpk is pi itself; trace_w NULL = ones)
+ *       loss = sum_k w_k losses_k / L                                       (w: L + 1 float64 on the device)
+ *       out64 = [loss | losses (L + 1) | lambda (L)]                         (2 L + 2 float64)
+ *   and the reverse mode of loss, already scaled for the tall products (sigma_bar through the Cholesky factor):
+ *       T_s = (S_bar + S_bar^T) s_scale,  T_pp = (Gpp_bar + Gpp_bar^T) g_scale + T_s,  T_kp = Gpk_bar^T g_scale,
+ *       T_pk = Gpk_bar g_scale,  T_kk = (Gkk_bar + Gkk_bar^T) g_scale
+ *   so that dP = P T_pp + K T_kp, dK = P T_pk + K T_kk (two nsvd_ts_rotate2 calls) and, with split rows, dPhi = Phi T_s
+ *   on the rows that carry no K.
+ *   update_state != 0: sigma_avg <- (1 - decay) sigma_avg + decay S (float32 state, IN PLACE, no bias correction) and
+ *   chol = cholesky(sigma_avg + 1e-3 I) (lower, float32): a second factorisation, used only by SpINx.forward.
+ *   update_state == 0: neither state tensor is read or written (both may be NULL).
+ *   *status (device int, zeroed by the caller) has NSVD_RITZ_BAD_PIVOT OR-ed in on a non-positive or non-finite pivot
+ *   of either factorisation or any non-finite result: out64, the five T's and (with update_state) chol are then all
+ *   zero and a non-finite element of sigma_avg is left as it was - nothing non-finite is stored. Every loop has a trip
+ *   count bounded by L. The Grams are read from global memory; no workspace.
+ * nsvd_ts_rotate2: out (n, k) = X (n, m) T1[:, :k] + Y (n, m) T2[:, :k], X, Y float32 with row strides ldx, ldy >= m, T1, T2
+ *   float64 with row strides ldt1, ldt2 >= k; both products and their sum accumulate in float64, one rounding to float32;
+ *   1 <= k <= m <= 80; out must not alias X or Y (NSVD_EINVAL). */
+int nsvd_spinx_solve(const double* S_raw, double s_scale, const double* Gpp_raw, const double* Gpk_raw,
+                     const double* Gkk_raw, double g_scale, int L, const double* w, const double* trace_w, double decay,
+                     int update_state, float* sigma_avg, float* chol, double* out64, double* T_s, double* T_pp,
+                     double* T_kp, double* T_pk, double* T_kk, int* status, void* stream);
+int nsvd_ts_rotate2(const float* X, long ldx, const float* Y, long ldy, int n, int m, const double* T1, int ldt1,
+                    const double* T2, int ldt2, int k, float* out, long ldo, void* stream);
+
 /* ---- next row: the CDK (two-tower) NestedLoRA loss ------------------------------------------------------
  * NestedLoRALossFunctionForCDK (methods/nestedlora.py:273-332) as called by NestedLoRAForCDK.compute_loss
  * (methods/nestedlora.py:366-378; examples/cdk/sketchy/main_sketchy.py:188).

@@ -194,6 +194,8 @@ SIGNATURES = {
     "nsvd_spin_jac_workspace_bytes": (_Z, [C.POINTER(ModelDesc), _I]),
     "nsvd_spin_jac_step": (_I, [C.POINTER(ModelDesc), C.POINTER(Params), _P, _I, _P, _F, _P, _Dbl, _P,
                                 C.POINTER(Params), _P, _Z, _P]),
+    "nsvd_spinx_solve": (_I, [_P, _Dbl, _P, _P, _P, _Dbl, _I, _P, _P, _Dbl, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "nsvd_ts_rotate2": (_I, [_P, C.c_long, _P, C.c_long, _I, _I, _P, _I, _P, _I, _I, _P, C.c_long, _P]),
     "nsvd_cdk_workspace_bytes": (_Z, [_I, _I, _I]),
     "nsvd_cdk_loss_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "nsvd_cdk_loss_backward": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),

@@ -9,6 +9,7 @@
 //                       M = Q^T S Q, residuals sqrt(max(M_kk - theta_k^2 (2 - q_k^T C q_k), 0)), R = chol(M),
 //                       T = Q R^-1
 //   nsvd_ts_rotate      out = X T[:, :k] in float64, rounded once to float32
+//   nsvd_ts_rotate2     out = X T1[:, :k] + Y T2[:, :k], the sum in float64, rounded once (SpINx's cotangents)
 // m <= 80 throughout (64 pairs + 16 columns of oversampling). Every device loop has a trip count bounded by an argument
 // or a constant; nothing waits on a data-dependent flag. No atomics: the row slices of the Gram are reduced in slice
 // order by a second launch, so every result is bit-reproducible.
@@ -49,6 +50,58 @@ __global__ void __launch_bounds__(NY_THREADS) ts_rotate_kernel(const float* __re
             const double tv = Ts[kk][tc + 16 * b];
             acc[0][b] = fma(x0, tv, acc[0][b]);
             acc[1][b] = fma(x1, tv, acc[1][b]);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const long row = rb + tr + 16 * a;
+#pragma unroll
+        for (int b = 0; b < NY_CB; ++b) {
+            const int c = tc + 16 * b;
+            if (row < n && c < k) out[(size_t)row * ldo + c] = (float)acc[a][b];
+        }
+    }
+}
+
+// out = X T1[:, :k] + Y T2[:, :k]: the same tile and thread map; the two terms pass through the same LDS one after the
+// other and share the float64 accumulators, so the sum is rounded once.
+__global__ void __launch_bounds__(NY_THREADS) ts_rotate2_kernel(const float* __restrict__ X, size_t ldx,
+                                                                const float* __restrict__ Y, size_t ldy, int n, int m,
+                                                                const double* __restrict__ T1, int ldt1,
+                                                                const double* __restrict__ T2, int ldt2, int k,
+                                                                float* __restrict__ out, size_t ldo) {
+    __shared__ double Ts[NY_MAXM][NY_MAXM];
+    __shared__ float xs[RO_ROWS][NY_MAXM + 1];
+    const int t = threadIdx.x, tr = t >> 4, tc = t & 15;
+    const long rb = (long)blockIdx.x * RO_ROWS;
+    double acc[2][NY_CB];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < NY_CB; ++b) acc[a][b] = 0.0;
+    for (int term = 0; term < 2; ++term) {
+        const float* Z = term ? Y : X;
+        const size_t ldz = term ? ldy : ldx;
+        const double* T = term ? T2 : T1;
+        const int ldt = term ? ldt2 : ldt1;
+        __syncthreads();
+        for (int e = t; e < m * NY_MAXM; e += NY_THREADS) {
+            const int kk = e / NY_MAXM, c = e - kk * NY_MAXM;
+            Ts[kk][c] = c < k ? T[(size_t)kk * ldt + c] : 0.0;
+        }
+        for (int e = t; e < RO_ROWS * m; e += NY_THREADS) {
+            const int r = e / m, c = e - r * m;
+            xs[r][c] = rb + r < n ? Z[(size_t)(rb + r) * ldz + c] : 0.f;
+        }
+        __syncthreads();
+        for (int kk = 0; kk < m; ++kk) {
+            const double x0 = (double)xs[tr][kk], x1 = (double)xs[tr + 16][kk];
+#pragma unroll
+            for (int b = 0; b < NY_CB; ++b) {
+                const double tv = Ts[kk][tc + 16 * b];
+                acc[0][b] = fma(x0, tv, acc[0][b]);
+                acc[1][b] = fma(x1, tv, acc[1][b]);
+            }
         }
     }
 #pragma unroll
@@ -364,6 +417,19 @@ extern "C" int nsvd_ts_rotate(const float* X, long ldx, int n, int m, const doub
     if (m > NY_MAXM) return NSVD_EUNSUPPORTED;
     ts_rotate_kernel<<<nsvd_cdiv(n, RO_ROWS), NY_THREADS, 0, (hipStream_t)stream>>>(X, (size_t)ldx, n, m, T, ldt, k, out,
                                                                                   (size_t)ldo);
+    NSVD_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nsvd_ts_rotate2(const float* X, long ldx, const float* Y, long ldy, int n, int m, const double* T1,
+                               int ldt1, const double* T2, int ldt2, int k, float* out, long ldo, void* stream) {
+    if (!X || !Y || !T1 || !T2 || !out || n <= 0 || m <= 0 || k <= 0 || k > m || ldx < m || ldy < m || ldt1 < k ||
+        ldt2 < k || ldo < k)
+        return NSVD_EINVAL;
+    if (out == X || out == Y) return NSVD_EINVAL;
+    if (m > NY_MAXM) return NSVD_EUNSUPPORTED;
+    ts_rotate2_kernel<<<nsvd_cdiv(n, RO_ROWS), NY_THREADS, 0, (hipStream_t)stream>>>(
+        X, (size_t)ldx, Y, (size_t)ldy, n, m, T1, ldt1, T2, ldt2, k, out, (size_t)ldo);
     NSVD_CHECK_LAUNCH();
     return 0;
 }

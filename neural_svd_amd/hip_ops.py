@@ -1185,6 +1185,74 @@ def spin_solve(sigma_raw: torch.Tensor, sigma_scale: float, pi_raw: torch.Tensor
     check(rc, "nsvd_spin_solve")
 
 
+@_on_tensor_device
+def spinx_solve(S_raw: torch.Tensor, s_scale: float, Gpp_raw: torch.Tensor, Gpk_raw: torch.Tensor, Gkk_raw: torch.Tensor,
+                g_scale: float, w: torch.Tensor, trace_w: Optional[torch.Tensor], decay: float, update_state: bool,
+                sigma_avg: Optional[torch.Tensor], chol: Optional[torch.Tensor], out64: torch.Tensor, T_s: torch.Tensor,
+                T_pp: torch.Tensor, T_kp: torch.Tensor, T_pk: torch.Tensor, T_kk: torch.Tensor,
+                status: torch.Tensor) -> None:
+    """SpINx's loss and its reverse mode on the four raw (L, L) float64 Grams in one workgroup (nsvd_spinx_solve):
+    out64 (2 L + 2) = [loss | losses (L + 1) | eigvals (L)], the five (L, L) float64 matrices of the cotangent products
+    dP = P T_pp + K T_kp, dK = P T_pk + K T_kk, dPhi = Phi T_s; w (L + 1) float64 loss weights, trace_w (L) float64 or
+    None for ones. update_state: sigma_avg (L, L) float32 takes the moving average IN PLACE and chol its factor;
+    otherwise neither is touched. S_raw may be Gpp_raw. status: (1,) int32, RITZ_BAD_PIVOT is OR-ed in on failure (every
+    output is then zero)."""
+    if S_raw.dim() != 2:
+        raise NsvdError("spinx_solve: S_raw must be (L, L)")
+    L = S_raw.shape[0]
+    f64 = torch.float64
+    mats = [(S_raw, "S_raw"), (Gpp_raw, "Gpp_raw"), (Gpk_raw, "Gpk_raw"), (Gkk_raw, "Gkk_raw"), (T_s, "T_s"),
+            (T_pp, "T_pp"), (T_kp, "T_kp"), (T_pk, "T_pk"), (T_kk, "T_kk")]
+    if update_state:
+        if sigma_avg is None or chol is None:
+            raise NsvdError("spinx_solve: update_state needs sigma_avg and chol")
+        mats += [(sigma_avg, "sigma_avg"), (chol, "chol")]
+    for o, name in mats:
+        if tuple(o.shape) != (L, L):
+            raise NsvdError(f"spinx_solve: {name} must be ({L}, {L})")
+    if w.numel() != L + 1 or (trace_w is not None and trace_w.numel() != L):
+        raise NsvdError("spinx_solve: w must hold L + 1 and trace_w L float64 values")
+    if out64.numel() != 2 * L + 2 or status.numel() < 1:
+        raise NsvdError("spinx_solve: out64 must hold 2 L + 2 float64 values and status one int32")
+    rc = _lib.load().nsvd_spinx_solve(_ptr(S_raw, "S_raw", f64), float(s_scale), _ptr(Gpp_raw, "Gpp_raw", f64),
+                                      _ptr(Gpk_raw, "Gpk_raw", f64), _ptr(Gkk_raw, "Gkk_raw", f64), float(g_scale), L,
+                                      _ptr(w, "w", f64), _ptr(trace_w, "trace_w", f64), float(decay),
+                                      1 if update_state else 0,
+                                      _ptr(sigma_avg, "sigma_avg") if update_state else None,
+                                      _ptr(chol, "chol") if update_state else None, _ptr(out64, "out64", f64),
+                                      _ptr(T_s, "T_s", f64), _ptr(T_pp, "T_pp", f64), _ptr(T_kp, "T_kp", f64),
+                                      _ptr(T_pk, "T_pk", f64), _ptr(T_kk, "T_kk", f64),
+                                      _ptr(status, "status", torch.int32), _stream())
+    check(rc, "nsvd_spinx_solve")
+
+
+@_on_tensor_device
+def ts_rotate2(X: torch.Tensor, T1: torch.Tensor, Y: torch.Tensor, T2: torch.Tensor, k: Optional[int] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out (n, k) = X (n, m) @ T1[:, :k] + Y (n, m) @ T2[:, :k] with T1, T2 float64, everything accumulated in float64
+    and rounded once to float32 (nsvd_ts_rotate2). out must not alias X or Y."""
+    xp, ldx = _rows_ptr(X, "X")
+    yp, ldy = _rows_ptr(Y, "Y")
+    n, m = X.shape
+    if tuple(Y.shape) != (n, m):
+        raise NsvdError("ts_rotate2: X and Y must have one shape")
+    for T in (T1, T2):
+        if T.dim() != 2 or T.shape[0] != m or T.stride(1) != 1 or T.dtype != torch.float64 or not T.is_cuda:
+            raise NsvdError("ts_rotate2: T1, T2 must be (m, >= k) float64 GPU tensors with unit column stride")
+    k = min(T1.shape[1], T2.shape[1]) if k is None else int(k)
+    if out is None:
+        out = torch.empty((n, max(k, 0)), dtype=torch.float32, device=X.device)
+    elif tuple(out.shape) != (n, k):
+        raise NsvdError("ts_rotate2: out must be (n, k)")
+    op, ldo = _rows_ptr(out, "out")
+    if op in (xp, yp):
+        raise NsvdError("ts_rotate2: out must not alias X or Y")
+    rc = _lib.load().nsvd_ts_rotate2(xp, ldx, yp, ldy, n, m, T1.data_ptr(), T1.stride(0), T2.data_ptr(), T2.stride(0), k,
+                                     op, ldo, _stream())
+    check(rc, "nsvd_ts_rotate2")
+    return out
+
+
 def spin_state_floats(shape: ModelShape) -> int:
     """floats of ONE parameter set of SpIN's compact Jacobian state ([W_0 | .. | b_0 | ..], no padding); J is (L, this)"""
     d = shape.desc()

@@ -357,6 +357,11 @@ def get_evd_method(args, method_name, model):
         from .neuralef import NeuralEigenfunctions
         return NeuralEigenfunctions(model=model, neigs=args.neigs, batchnorm_mode=args.loss.neuralef.batchnorm_mode,
                                     unbiased=args.loss.neuralef.unbiased, sort=args.sort)
+    if method_name == "spinx":
+        raise NotImplementedError("spinx: built for the matrix-free kernel operators only - construct "
+                                  "neural_svd_amd.spinx.SpINx and call neural_svd_amd.spinx.SpINx.compute_loss_kernel "
+                                  "(or SpinxKernelTrainer); this factory serves the PDE operator path, where the loss "
+                                  "sends a gradient into Tphi that the HIP backward does not carry through the stencil")
     if method_name != "neuralsvd":
         raise NotImplementedError(f"{method_name}: only 'neuralsvd' (NestedLoRA) and 'neuralef' are built on this path")
     # opt-in (args.generic_exact_laplacian with laplacian_eps <= 0): the exact Laplacian on the generic kernels, for

@@ -13,6 +13,9 @@ compared with the closed-form Mercer eigenvalues (gaussian_kernel_eigvals).
 arc-cosine kernel; --ell unused) and write profiles/dot_kernel_train.json by default.
 --spin adds a SpIN column (neural_svd_amd.spin.SpinKernelTrainer: the same model, batch size and step count trained with
 SpIN's loss; --spin-decay is its moving-average rate) with its own steps/s.
+--spinx adds a SpINx column (neural_svd_amd.spinx.SpinxKernelTrainer, the same way; --spinx-decay its moving-average
+rate, --spinx-lr its learning rate, --spinx-weight-freq N re-weights the L + 1 losses by their NTK norms every N steps,
+0 = never) with its own steps/s (the weight updates are inside the timed loop).
 --nystrom N adds the Nystrom baseline (neural_svd_amd.Nystrom, matrix-free) on an N-point sample as a comparison
 column: the only one the exponential and the two dot-product kinds have, since their spectra have no closed form here.
 (A polynomial kernel has rank C(dim + degree, degree): keep L + 8 at or below it, see Nystrom's note on oversample.)
@@ -59,6 +62,11 @@ def main():
     ap.add_argument("--spin", action="store_true", help="also train SpIN on the same operator and print its column")
     ap.add_argument("--spin-decay", type=float, default=0.01)
     ap.add_argument("--spin-lr", type=float, default=None, help="default: --lr")
+    ap.add_argument("--spinx", action="store_true", help="also train SpINx on the same operator and print its column")
+    ap.add_argument("--spinx-decay", type=float, default=0.01)
+    ap.add_argument("--spinx-lr", type=float, default=None, help="default: --lr")
+    ap.add_argument("--spinx-weight-freq", type=int, default=0, metavar="N",
+                    help="SpINx: update the loss weights every N steps (0: never)")
     ap.add_argument("--out", default=None,
                     help="default: profiles/rbf_kernel_train.json (radial kinds) or profiles/dot_kernel_train.json")
     a = ap.parse_args()
@@ -145,6 +153,43 @@ def main():
             rec.update(spin_rel_err=[float(v) for v in np.abs(sp_vals - lam) / lam])
         print(f"SpIN steps/s {rec['spin_steps_per_s']}")
         columns.append(("SpIN", sp_vals))
+    if a.spinx:
+        from neural_svd_amd.spinx import SpinxKernelTrainer
+        sx = SpinxKernelTrainer(op, L=a.L, m=a.m, hidden=(128, 128), batch_size=a.B, decay=a.spinx_decay,
+                                lr=a.lr if a.spinx_lr is None else a.spinx_lr, rmsprop_decay=0.999, rmsprop_eps=1e-10,
+                                num_iters=a.steps, fourier_scale=a.fourier_scale, seed=a.seed, index_seed=a.seed + 1,
+                                trace_weights=[-1.0] * a.L)  # the loss is minimised: -1 = the reference's negated operator
+
+        def sx_steps(first, last):
+            for t in range(first, last):
+                if a.spinx_weight_freq > 0 and t > 0 and t % a.spinx_weight_freq == 0:
+                    sx.update_weights()
+                sx.step()
+
+        sx_steps(0, 10)
+        sx.check()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        sx_steps(10, a.steps)
+        torch.cuda.synchronize()
+        dtx = time.perf_counter() - t0
+        sx.check()
+        sx_vals = kernel_spectrum(op, sx.forward, x_eval, chunk)["eigvals"]
+        out64 = sx.loss.cpu()
+        rec.update(spinx_decay=a.spinx_decay, spinx_lr=a.lr if a.spinx_lr is None else a.spinx_lr,
+                   spinx_weight_freq=a.spinx_weight_freq, spinx_steps_per_s=round((a.steps - 10) / dtx, 1),
+                   spinx_rayleigh=[float(v) for v in sx_vals], spinx_loss=float(out64[0]),
+                   spinx_losses=[float(v) for v in out64[1:a.L + 2]],
+                   spinx_eigvals_batch=[float(v) for v in out64[a.L + 2:]],
+                   spinx_weights=[float(v) for v in sx.weights.cpu()])
+        if gaussian:
+            # (with equal trace weights nothing orders the L functions: each converges to an eigenfunction, in any
+            # order - the sorted quotients are the ones to hold against the spectrum)
+            rec.update(spinx_rel_err=[float(v) for v in np.abs(sx_vals - lam) / lam],
+                       spinx_rel_err_sorted=[float(v) for v in np.abs(np.sort(sx_vals)[::-1] - lam) / lam])
+            print("SpINx, sorted quotients, relative error: " + " ".join(f"{v:.2e}" for v in rec["spinx_rel_err_sorted"]))
+        print(f"SpINx steps/s {rec['spinx_steps_per_s']}")
+        columns.append(("SpINx", sx_vals))
     if a.nystrom:
         from neural_svd_amd import Nystrom
         ny = Nystrom(op, op.sample(a.nystrom, torch.Generator(device=dev).manual_seed(a.seed + 2000)), a.L)
