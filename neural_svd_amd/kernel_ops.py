@@ -562,12 +562,10 @@ class FusedKernelTrainer:
         """one optimiser step on the index batch idx (or a fresh draw; sharded runs: the SAME batch on every rank) -
         with a RadialKernelOperator: on the (B, D) coordinate batch given in its place, or a fresh draw;
         returns the device loss triple (no sync)"""
-        from .trainer import cosine_lr
+        from .trainer import coordinate_batch, cosine_lr
         if self.coords:
             x = self.op.sample(self.B, self.gen) if idx is None else idx
-            if not x.is_cuda or tuple(x.shape) != (self.B, self.op.dim):
-                raise H.NsvdError(f"FusedKernelTrainer.step: a ({self.B}, {self.op.dim}) coordinate batch on the GPU")
-            x = x.float().contiguous()
+            x = coordinate_batch(x, self.B, self.op.dim, "FusedKernelTrainer.step: the batch")
             H.model_forward(self.shape, self._params, x, self.c, self.ws, save_for_backward=True, out=self.f_loc)
             self.op.apply_raw(x, x, self.f_loc, 1.0 / self.B, ws=self.ka_ws, out=self.Kf_loc)
         else:

@@ -80,7 +80,7 @@ class KernelSvdTrainer:
                  momentum: float = 0.0, num_iters: int = 0, fourier_scale: float = 0.05, hard_mul_const: float = 1.0,
                  seed: int = 0, index_seed: int = 1):
         from .nested_lowrank import nesting_masks
-        from .trainer import FlatParams, reference_init
+        from .trainer import FlatModel
         if not isinstance(op, MatrixFreeKernelOperator):
             raise NotImplementedError("KernelSvdTrainer: a MatrixFreeKernelOperator (radial or dot-product kernel)")
         self.op, self.device = op, op.device
@@ -96,17 +96,10 @@ class KernelSvdTrainer:
         if not (self.sigma_x > 0 and self.sigma_y > 0):
             raise ValueError("KernelSvdTrainer: sigma_x and sigma_y must be positive")
         self.c = float(hard_mul_const)
-        self.lr, self.num_iters = float(lr), int(num_iters)
-        self.cfg = H.opt_config(optimizer, lr, alpha=rmsprop_decay, eps=rmsprop_eps, momentum=momentum)
-        uses_sq, uses_mom = H.opt_uses(self.cfg)
-        self.Pf = FlatParams(self.shape, dev, with_state=True, with_mom=uses_mom)
-        self.Pg = FlatParams(self.shape, dev, with_state=True, with_mom=uses_mom)
-        self._sq = (self.Pf.sq, self.Pg.sq) if uses_sq else (None, None)
-        for P, s in ((self.Pf, seed), (self.Pg, seed + 1)):
-            fB0, ws0, bs0, _ = reference_init(self.shape, fourier_scale, None, s)
-            P.load(fB0, ws0, bs0, None)
-        self._params = (self.Pf.pack(self.Pf.flat, True), self.Pg.pack(self.Pg.flat, True))
-        self._grads = (self.Pf.pack(self.Pf.grad, False), self.Pg.pack(self.Pg.grad, False))
+        # the f model on x, the g model on y: seeded apart, the same optimiser rule
+        self.models = tuple(FlatModel(self.shape, dev, s, fourier_scale, hard_mul_const, optimizer, lr, rmsprop_decay,
+                                      rmsprop_eps, momentum, num_iters) for s in (seed, seed + 1))
+        self.Pf, self.Pg = self.models[0].P, self.models[1].P
         self.vector_mask, self.matrix_mask, self.mask_kind = nesting_masks(int(L), bool(sequential), step)
         cust = self.mask_kind == H.MASK_CUSTOM
         self.v = self.vector_mask.to(dev).float().contiguous() if cust else None
@@ -132,42 +125,32 @@ class KernelSvdTrainer:
     def step(self, x: torch.Tensor = None, y: torch.Tensor = None) -> torch.Tensor:
         """one optimiser step on the (B, D) coordinate batches x and y (or a fresh draw of both); returns ``loss``
         (no sync)"""
-        from .trainer import cosine_lr
+        from .trainer import coordinate_batch
         if (x is None) != (y is None):
             raise NsvdError("KernelSvdTrainer.step: give both x and y, or neither")
         if x is None:
             x, y = self.sample()
-        B, D = self.B, self.op.dim
-        for t, n in ((x, "x"), (y, "y")):
-            if not t.is_cuda or tuple(t.shape) != (B, D):
-                raise NsvdError(f"KernelSvdTrainer.step: {n} must be a ({B}, {D}) coordinate batch on the GPU")
-        x, y = x.float().contiguous(), y.float().contiguous()
+        B, (mf, mg) = self.B, self.models
+        x = coordinate_batch(x, B, self.op.dim, "KernelSvdTrainer.step: x")
+        y = coordinate_batch(y, B, self.op.dim, "KernelSvdTrainer.step: y")
         f, g = self.X[:B], self.X[B:]
-        H.model_forward(self.shape, self._params[0], x, self.c, self.model_ws[0], save_for_backward=True, out=f)
-        H.model_forward(self.shape, self._params[1], y, self.c, self.model_ws[1], save_for_backward=True, out=g)
+        mf.forward(x, self.model_ws[0], out=f)
+        mg.forward(y, self.model_ws[1], out=g)
         self.op.apply_pair_raw(x, y, g, f, 1.0 / B, 1.0 / B, ws=self.pair_ws, out_x=self.TX[:B], out_y=self.TX[B:])
         H.evd_moments(self.X, self.TX, self.mask_kind, self.v, self.moments, self.scratch)
         H.evd_loss_grad(self.X, self.TX, self.mask_kind, self.v, self.M, self.moments, 1.0, True, loss=self.loss,
                         df=self.dX)
-        H.model_backward(self.shape, self._params[0], x, self.dX[:B], self._grads[0], self.model_ws[0])
-        H.model_backward(self.shape, self._params[1], y, self.dX[B:], self._grads[1], self.model_ws[1])
-        lr = cosine_lr(self.lr, self.t, self.num_iters) if self.num_iters > 0 else self.lr
-        for P, sq in zip((self.Pf, self.Pg), self._sq):
-            H.opt_step(self.cfg, P.flat, P.grad, sq, P.mom, None, self.t, lr=lr)
+        mf.backward(x, self.dX[:B], self.model_ws[0])
+        mg.backward(y, self.dX[B:], self.model_ws[1])
+        mf.opt_step(self.t)
+        mg.opt_step(self.t)
         self.t += 1
         return self.loss
 
-    def _eval(self, which: int, z: torch.Tensor) -> torch.Tensor:
-        if not z.is_cuda:
-            raise NsvdError("KernelSvdTrainer: coordinates must live on the GPU (no CPU path)")
-        z = z.float().contiguous()
-        return H.model_forward(self.shape, self._params[which], z, self.c,
-                               H.model_workspace(self.shape, z.shape[0], z.device))
-
     def f(self, x: torch.Tensor) -> torch.Tensor:
         """the left functions at x (n, D): (n, L)"""
-        return self._eval(0, x)
+        return self.models[0].evaluate(x)
 
     def g(self, y: torch.Tensor) -> torch.Tensor:
         """the right functions at y (n, D): (n, L)"""
-        return self._eval(1, y)
+        return self.models[1].evaluate(y)

@@ -38,7 +38,9 @@ import torch.nn as nn
 
 from . import hip_ops as H
 from ._lib import NsvdError
-from .kernel_ops import MatrixFreeKernelOperator
+from ._spin_step import (StepBuffers, WhitenedKernelTrainer, WhitenedMethod, check_op, check_x, forward_product,
+                         swapped_product_backward)
+from .trainer import PackedModel
 
 _PDE_REASON = ("SpIN.compute_loss_operator is not built: Covariance.backward (methods/spin.py:76-100) sends a gradient "
                "into Tphi; on the PDE path Tphi comes out of the 1 + 2D stencil and the HIP backward does not go through "
@@ -46,62 +48,48 @@ _PDE_REASON = ("SpIN.compute_loss_operator is not built: Covariance.backward (me
                "with a MatrixFreeKernelOperator")
 
 
-def _chunk_rows(B: int, split_batch: bool):
-    """(B1, B2): rows that carry Kphi / reference rows, as torch.chunk(x, 2) splits them"""
-    if not split_batch:
-        return B, B
-    B1 = (B + 1) // 2
-    if B - B1 < 1:
-        raise NsvdError("SpIN: split_batch needs at least 2 rows")
-    return B1, B - B1
+class _SpinWork(StepBuffers):
+    """+ SpIN's own: the raw moments, the solve's outputs, the Gram and Jacobian workspaces"""
 
-
-class _SpinWork:
-    """the device buffers of one step shape (B rows, split or not)"""
-
-    def __init__(self, L, B, B1, dev):
-        f32, f64 = torch.float32, torch.float64
+    def __init__(self, op, shape, B, split, dev):
+        super().__init__(op, shape, B, split, dev)
+        L, f64 = shape.L, torch.float64
         self.S = torch.empty((L, L), dtype=f64, device=dev)
         self.Pi = torch.empty((L, L), dtype=f64, device=dev)
-        self.le = torch.empty(L + 1, dtype=f64, device=dev)
+        self.le = self.loss = torch.empty(L + 1, dtype=f64, device=dev)
         self.gsigma = torch.empty((L, L), dtype=f64, device=dev)
         self.gpis = torch.empty((L, L), dtype=f64, device=dev)
         self.ws_all = H.tsgram_workspace(B, L, dev)
-        self.ws_1 = H.tsgram_workspace(B1, L, dev)
-        self.dK = torch.empty((B1, L), dtype=f32, device=dev)
+        self.ws_1 = H.tsgram_workspace(self.B1, L, dev)
+        self.jac_ws = H.spin_jac_workspace(shape, self.B1, dev)
 
 
-def _spin_solve_half(op, shape, params, c, x, split_batch, decay, sigma_avg, chol, status, model_ws, ka_ws, work,
-                     phi_all, Kphi):
-    """steps 1-5 of one step: fills phi_all (B, L), Kphi (B1, L) and the solve's outputs in `work`, updates sigma_avg and
-    chol in place"""
-    B = x.shape[0]
-    B1, B2 = _chunk_rows(B, split_batch)
-    H.model_forward(shape, params, x, c, model_ws, save_for_backward=True, out=phi_all)
-    if split_batch:
-        op.apply_raw(x[:B1], x[B1:], phi_all[B1:], 1.0 / B2, ws=ka_ws, out=Kphi)
-        H.tsgram_f64(phi_all, None, ws=work.ws_all, out_xtx=work.S)
-        H.tsgram_f64(phi_all[:B1], Kphi, xtx=False, ws=work.ws_1, out_xty=work.Pi)
+def _solve_half(model, x, w, decay, sigma_avg, chol):
+    """steps 1-5 of one step: fills w.phi_all (B, L), w.Kphi (B1, L) and the solve's outputs in w, updates sigma_avg
+    and chol in place"""
+    B1 = w.B1
+    forward_product(model, x, w)
+    if w.split:
+        H.tsgram_f64(w.phi_all, None, ws=w.ws_all, out_xtx=w.S)
+        H.tsgram_f64(w.phi_all[:B1], w.Kphi, xtx=False, ws=w.ws_1, out_xty=w.Pi)
     else:
-        op.apply_raw(x, x, phi_all, 1.0 / B2, ws=ka_ws, out=Kphi)
-        H.tsgram_f64(phi_all, Kphi, ws=work.ws_all, out_xtx=work.S, out_xty=work.Pi)
-    H.spin_solve(work.S, 1.0 / B, work.Pi, 1.0 / B1, decay, 1.0 / B1, sigma_avg, chol, work.le, work.gsigma, work.gpis,
-                 status)
+        H.tsgram_f64(w.phi_all, w.Kphi, ws=w.ws_all, out_xtx=w.S, out_xty=w.Pi)
+    H.spin_solve(w.S, 1.0 / w.B, w.Pi, 1.0 / B1, decay, 1.0 / B1, sigma_avg, chol, w.le, w.gsigma, w.gpis, w.status)
 
 
-def _spin_term1(op, shape, params, x, split_batch, grads, model_ws, ka_ws_back, work, phi_all, Kphi, dout):
+def _term1(model, x, w):
     """step 6: the cotangents of phi and Kphi, the swapped-argument product, one model backward (grads OVERWRITTEN)"""
-    B = x.shape[0]
-    B1, B2 = _chunk_rows(B, split_batch)
-    L = shape.L
-    H.ts_rotate(Kphi, work.gpis, L, out=dout[:B1])
-    H.ts_rotate(phi_all[:B1], work.gpis, L, out=work.dK)
-    if split_batch:
-        op.apply_raw(x[B1:], x[:B1], work.dK, 1.0 / B2, ws=ka_ws_back, out=dout[B1:])
-    else:
-        back = op.apply_raw(x, x, work.dK, 1.0 / B2, ws=ka_ws_back)
-        dout.add_(back)
-    H.model_backward(shape, params, x, dout, grads, model_ws)
+    B1 = w.B1
+    H.ts_rotate(w.Kphi, w.gpis, w.L, out=w.dout[:B1])
+    H.ts_rotate(w.phi_all[:B1], w.gpis, w.L, out=w.dK)
+    swapped_product_backward(model, x, w, False)
+
+
+def _term2(model, x, w, decay, j_avg):
+    """step 7: the moving average of the Jacobian contraction, ADDED to the gradient buffers"""
+    B1 = w.B1
+    H.spin_jac_step(model.shape, model.params, x[:B1], w.phi_all[:B1], model.c, w.gsigma, decay, j_avg, model.grads,
+                    ws=w.jac_ws)
 
 
 class _SpinLossFn(torch.autograd.Function):
@@ -112,79 +100,41 @@ class _SpinLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, spin, op, split_batch, *params):
         model = spin.model
-        shape, dev = model.shape, x.device
-        B = x.shape[0]
-        B1, B2 = _chunk_rows(B, split_batch)
-        L = shape.L
-        packed = model.packed_params()
-        work = _SpinWork(L, B, B1, dev)
-        model_ws = H.model_workspace(shape, B, dev)
-        ka_ws = op.workspace(B1, B2, L, dev)
-        phi_all = torch.empty((B, L), dtype=torch.float32, device=dev)
-        Kphi = torch.empty((B1, L), dtype=torch.float32, device=dev)
+        shape = model.shape
+        w = _SpinWork(op, shape, x.shape[0], split_batch, x.device)
         term2 = [torch.zeros_like(t.data) for t in model.trainable_tensors()]
         nl = len(shape.dims)
-        g2 = H.pack_params(shape, term2[:nl], term2[nl:], None, None)
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-        c = float(model.hard_mul_const)
-        _spin_solve_half(op, shape, packed, c, x, split_batch, float(spin.decay), spin.sigma_avg.data, spin.chol.data,
-                         status, model_ws, ka_ws, work, phi_all, Kphi)
-        H.spin_jac_step(shape, packed, x[:B1], phi_all[:B1], c, work.gsigma, float(spin.decay), spin.j_avg.data, g2)
-        if int(status.item()):
+        packed = PackedModel(shape, model.packed_params(), H.pack_params(shape, term2[:nl], term2[nl:], None, None),
+                             model.hard_mul_const)
+        _solve_half(packed, x, w, float(spin.decay), spin.sigma_avg.data, spin.chol.data)
+        _term2(packed, x, w, float(spin.decay), spin.j_avg.data)
+        if int(w.status.item()):
             raise NsvdError("SpIN: cholesky(sigma_avg + 1e-3 I) failed (non-positive or non-finite pivot); the step's "
                             "outputs are zero")
         spin._term2 = term2
-        ctx.op, ctx.model, ctx.split, ctx.work, ctx.model_ws = op, model, split_batch, work, model_ws
-        ctx.phi_all, ctx.Kphi = phi_all, Kphi
+        ctx.model, ctx.work = model, w
         ctx.save_for_backward(x)
-        le = work.le.to(torch.float32)
-        loss, eigvals, phi = le[0].clone(), le[1:].clone(), phi_all[:B1]
-        ctx.mark_non_differentiable(phi, Kphi, eigvals)
-        return loss, phi, Kphi, eigvals
+        le = w.le.to(torch.float32)
+        loss, eigvals, phi = le[0].clone(), le[1:].clone(), w.phi_all[:w.B1]
+        ctx.mark_non_differentiable(phi, w.Kphi, eigvals)
+        return loss, phi, w.Kphi, eigvals
 
     @staticmethod
     def backward(ctx, *grad_outputs):
         (x,) = ctx.saved_tensors
-        model, op = ctx.model, ctx.op
-        shape = model.shape
-        B = x.shape[0]
-        B1, B2 = _chunk_rows(B, ctx.split)
+        model = ctx.model
         grads = model.grad_buffers()
-        dout = torch.empty((B, shape.L), dtype=torch.float32, device=x.device)
-        _spin_term1(op, shape, model.packed_params(), x, ctx.split, grads.packed, ctx.model_ws,
-                    op.workspace(B2, B1, shape.L, x.device), ctx.work, ctx.phi_all, ctx.Kphi, dout)
+        _term1(PackedModel(model.shape, model.packed_params(), grads.packed, model.hard_mul_const), x,
+               ctx.work.with_backward())
         return (None, None, None, None) + tuple(grads.tensors)
 
 
-class SpIN(nn.Module):
+class SpIN(WhitenedMethod):
     def __init__(self, model, neigs, decay, use_vmap=True):
-        """
-        :param decay:
-            0.0 = the moving average is constant (less update)
-            1.0 = the moving average has no memory (more update)
-        use_vmap is accepted and ignored: the Jacobian contraction is one HIP kernel either way.
-        """
-        self.name = "spin"
-        super().__init__()
-        from .models import WaveFunctions
-        if not isinstance(model, WaveFunctions):
-            raise NotImplementedError("SpIN (HIP): model must be this package's WaveFunctions(ParallelMLP)")
-        if model.has_exp_mask or model.box is not None:
-            raise NotImplementedError("SpIN (HIP): models with an exponential or box mask are not built (the "
-                                      "kernel-operator models have none)")
-        if int(neigs) != model.base.num_copies:
-            raise ValueError(f"SpIN: neigs = {neigs} but the model has {model.base.num_copies} heads")
-        if not 2 <= int(neigs) <= H.SPIN_MAX_L:
-            # (the reference's own class fails at neigs = 1: spin_step receives a 0-D pi)
-            raise ValueError(f"SpIN: neigs must be in 2..{H.SPIN_MAX_L}")
-        if not 0.0 <= float(decay) <= 1.0:
-            raise ValueError("SpIN: decay must be in [0, 1]")
-        self.model = model
-        self.neigs = int(neigs)
-        self.decay = decay
+        """decay: WhitenedMethod's. use_vmap is accepted and ignored: the Jacobian contraction is one HIP kernel either
+        way."""
+        super().__init__("spin", "SpIN", model, neigs, decay)
         self.use_vmap = use_vmap
-        self.sigma_avg = nn.Parameter(torch.zeros(neigs, neigs), requires_grad=False)
-        self.chol = nn.Parameter(torch.zeros(neigs, neigs), requires_grad=False)
         # the compact state: row a = one parameter set [ws.. | bs..], j_avg[a][..][c][..] = reference j_avg[a, c, c, ..]
         n = sum(t.numel() for t in model.trainable_tensors())
         self.j_avg = nn.Parameter(torch.zeros(neigs, n), requires_grad=False)
@@ -241,19 +191,8 @@ class SpIN(nn.Module):
     def compute_loss_kernel(self, get_approx_kernel_op, x, importance, split_batch: bool, *args, **kwargs):
         """methods/spin.py:171-193 for ``get_approx_kernel_op`` = the bound method of a MatrixFreeKernelOperator.
         Returns (loss, dict(f, Tf, eigvals)); assigns term 2 to the model's .grad's, loss.backward() adds term 1."""
-        op = getattr(get_approx_kernel_op, "__self__", None)
-        if not isinstance(op, MatrixFreeKernelOperator) or \
-                getattr(get_approx_kernel_op, "__func__", None) is not MatrixFreeKernelOperator.get_approx_kernel_op:
-            raise NotImplementedError("SpIN.compute_loss_kernel (HIP): get_approx_kernel_op must be the bound method of a "
-                                      "MatrixFreeKernelOperator (the gradient into Kphi is taken through the operator's "
-                                      "own matrix-free product); foreign callables are not built")
-        if importance is not None:
-            raise NotImplementedError("SpIN.compute_loss_kernel (HIP): importance-weighted kernel operators are not built")
-        if not x.is_cuda:
-            raise NsvdError("SpIN: x must live on the GPU (no CPU path)")
-        x = x.detach().reshape(x.shape[0], -1).float().contiguous()
-        if x.shape[1] != op.dim:
-            raise NsvdError(f"SpIN: x must be (B, {op.dim}) for this operator")
+        op = check_op("SpIN.compute_loss_kernel", get_approx_kernel_op, importance)
+        x = check_x("SpIN", x, op)
         params = self.model.trainable_tensors()
         loss, phi, Kphi, eigvals = _SpinLossFn.apply(x, self, op, bool(split_batch), *params)
         for p, g in zip(params, self._term2):
@@ -265,12 +204,8 @@ class SpIN(nn.Module):
     def compute_loss_operator(self, operator, x, importance, *args, **kwargs):
         raise NotImplementedError(_PDE_REASON)
 
-    def forward(self, x):
-        # a wrapper to output orthonormalized eigenfunction (methods/spin.py:209-215)
-        return torch.linalg.solve_triangular(self.chol, self.model(x).T, upper=False).T
 
-
-class SpinKernelTrainer:
+class SpinKernelTrainer(WhitenedKernelTrainer):
     """SpIN's training step on a matrix-free kernel operator (SpIN.compute_loss_kernel, loss.backward(), optimiser -
     methods/spin.py:130-193 with the optimiser of examples/utils.py:48-72) as a fixed sequence of C-ABI calls on flat
     buffers: nsvd_model_forward on all of x -> Kphi (op.apply_raw) -> moments (nsvd_tsgram_f64) -> nsvd_spin_solve ->
@@ -281,82 +216,24 @@ class SpinKernelTrainer:
     ``loss`` = [trace(Lambda) | eigvals] float64 on the device after a step; ``status`` accumulates the solve's failure
     bit (``check()`` reads it and raises)."""
 
+    Work = _SpinWork
+    FAILED = "cholesky(sigma_avg + 1e-3 I) failed"
+
     def __init__(self, op, L: int, m: int, hidden=(128, 128), batch_size: int = 8192, decay: float = 0.01,
                  split_batch: bool = False, lr: float = 1e-4, optimizer: str = "rmsprop", rmsprop_decay: float = 0.99,
                  rmsprop_eps: float = 1e-10, momentum: float = 0.0, num_iters: int = 0, fourier_scale: float = 0.05,
                  hard_mul_const: float = 1.0, seed: int = 0, index_seed: int = 1):
-        from .trainer import FlatParams, reference_init
-        if not isinstance(op, MatrixFreeKernelOperator):
-            raise NotImplementedError("SpinKernelTrainer: a MatrixFreeKernelOperator (radial or dot-product kernel)")
-        if not 2 <= int(L) <= H.SPIN_MAX_L:
-            raise ValueError(f"SpinKernelTrainer: L must be in 2..{H.SPIN_MAX_L}")
-        self.op, self.device = op, op.device
-        dev = self.device
-        self.shape = H.ModelShape(L=int(L), D=op.dim, m=int(m), hidden=tuple(hidden), has_exp_mask=False)
-        self.B, self.split = int(batch_size), bool(split_batch)
-        self.B1, self.B2 = _chunk_rows(self.B, self.split)
-        self.decay, self.c = float(decay), float(hard_mul_const)
-        self.lr, self.num_iters = float(lr), int(num_iters)
-        self.cfg = H.opt_config(optimizer, lr, alpha=rmsprop_decay, eps=rmsprop_eps, momentum=momentum)
-        uses_sq, uses_mom = H.opt_uses(self.cfg)
-        self.P = FlatParams(self.shape, dev, with_state=True, with_mom=uses_mom)
-        self._sq = self.P.sq if uses_sq else None
-        fB0, ws0, bs0, _ = reference_init(self.shape, fourier_scale, None, seed)
-        self.P.load(fB0, ws0, bs0, None)
-        self._params = self.P.pack(self.P.flat, True)
-        self._grads = self.P.pack(self.P.grad, False)
-        self.sigma_avg = torch.zeros((L, L), dtype=torch.float32, device=dev)
-        self.chol = torch.zeros((L, L), dtype=torch.float32, device=dev)
-        self.j_avg = torch.zeros((L, H.spin_state_floats(self.shape)), dtype=torch.float32, device=dev)
-        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.work = _SpinWork(L, self.B, self.B1, dev)
-        self.loss = self.work.le
-        self.model_ws = H.model_workspace(self.shape, self.B, dev)
-        self.ka_ws = op.workspace(self.B1, self.B2, L, dev)
-        self.ka_ws_back = op.workspace(self.B2, self.B1, L, dev)
-        self.jac_ws = H.spin_jac_workspace(self.shape, self.B1, dev)
-        self.phi_all = torch.empty((self.B, L), dtype=torch.float32, device=dev)
-        self.Kphi = torch.empty((self.B1, L), dtype=torch.float32, device=dev)
-        self.dout = torch.empty((self.B, L), dtype=torch.float32, device=dev)
-        self.gen = torch.Generator(device=dev).manual_seed(index_seed)
-        self.t = 0
-
-    @property
-    def phi(self) -> torch.Tensor:
-        return self.phi_all[:self.B1]
+        super().__init__(op, (L, m, hidden), batch_size, decay, split_batch, index_seed, seed=seed,
+                         fourier_scale=fourier_scale, hard_mul_const=hard_mul_const, optimizer=optimizer, lr=lr,
+                         rmsprop_decay=rmsprop_decay, rmsprop_eps=rmsprop_eps, momentum=momentum, num_iters=num_iters)
+        self.j_avg = torch.zeros((L, H.spin_state_floats(self.shape)), dtype=torch.float32, device=self.device)
 
     def step(self, x: torch.Tensor = None) -> torch.Tensor:
         """one optimiser step on the (B, D) coordinate batch x (or a fresh draw); returns ``loss`` (no sync)"""
-        from .trainer import cosine_lr
-        x = self.op.sample(self.B, self.gen) if x is None else x
-        if not x.is_cuda or tuple(x.shape) != (self.B, self.op.dim):
-            raise NsvdError(f"SpinKernelTrainer.step: a ({self.B}, {self.op.dim}) coordinate batch on the GPU")
-        x = x.float().contiguous()
+        x = self._batch(x, "step")
         # (term 1 overwrites the gradient buffer, term 2 is added to it: the order of the two launches is swapped
         # against the class path, the sum is the same)
-        B1, w = self.B1, self.work
-        _spin_solve_half(self.op, self.shape, self._params, self.c, x, self.split, self.decay, self.sigma_avg, self.chol,
-                         self.status, self.model_ws, self.ka_ws, w, self.phi_all, self.Kphi)
-        _spin_term1(self.op, self.shape, self._params, x, self.split, self._grads, self.model_ws, self.ka_ws_back, w,
-                    self.phi_all, self.Kphi, self.dout)
-        H.spin_jac_step(self.shape, self._params, x[:B1], self.phi_all[:B1], self.c, w.gsigma, self.decay, self.j_avg, self._grads,
-                        ws=self.jac_ws)
-        lr = cosine_lr(self.lr, self.t, self.num_iters) if self.num_iters > 0 else self.lr
-        H.opt_step(self.cfg, self.P.flat, self.P.grad, self._sq, self.P.mom, None, self.t, lr=lr)
-        self.t += 1
-        return self.loss
-
-    def check(self) -> None:
-        """raise if any step since the last check failed its Cholesky factorisation (one small device read)"""
-        bits = int(self.status.item())
-        self.status.zero_()
-        if bits:
-            raise NsvdError("SpinKernelTrainer: cholesky(sigma_avg + 1e-3 I) failed in a step since the last check")
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """the orthonormalised eigenfunctions (SpIN.forward): chol^-1 applied to model(x)"""
-        x = x.float().contiguous()
-        f = H.model_forward(self.shape, self._params, x, self.c, H.model_workspace(self.shape, x.shape[0], x.device))
-        return torch.linalg.solve_triangular(self.chol, f.T, upper=False).T
-
-    __call__ = forward
+        _solve_half(self.model, x, self.work, self.decay, self.sigma_avg, self.chol)
+        _term1(self.model, x, self.work)
+        _term2(self.model, x, self.work, self.decay, self.j_avg)
+        return self._opt_step()

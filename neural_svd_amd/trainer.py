@@ -127,6 +127,59 @@ class FlatParams:
             self.mom.zero_()
 
 
+def coordinate_batch(x: torch.Tensor, B: int, D: int, who: str) -> torch.Tensor:
+    """the (B, D) coordinate batch of a kernel trainer's step as contiguous float32; anything else raises"""
+    if not x.is_cuda or tuple(x.shape) != (B, D):
+        raise H.NsvdError(f"{who} must be a ({B}, {D}) coordinate batch on the GPU")
+    return x.float().contiguous()
+
+
+class PackedModel:
+    """One ParallelMLP as the C ABI takes it (shape, packed parameters, packed gradient buffers or None,
+    hard_mul_const) and the two model calls on it: what a step of the kernel methods needs of a model, whether the
+    tensors are a module's (the class paths) or views of flat buffers (FlatModel)."""
+
+    def __init__(self, shape: H.ModelShape, params: H.Params, grads: Optional[H.Params], c: float):
+        self.shape, self.params, self.grads, self.c = shape, params, grads, float(c)
+
+    def forward(self, x, ws, out=None, save_for_backward: bool = True) -> torch.Tensor:
+        return H.model_forward(self.shape, self.params, x, self.c, ws, save_for_backward=save_for_backward, out=out)
+
+    def backward(self, x, dout, ws) -> None:
+        """the gradient buffers are OVERWRITTEN"""
+        H.model_backward(self.shape, self.params, x, dout, self.grads, ws)
+
+
+class FlatModel(PackedModel):
+    """One ParallelMLP on flat buffers together with its optimiser (the reference's get_optimizer,
+    examples/utils.py:48-72, + the cosine schedule when num_iters > 0): ``P`` with the reference's initial weights of
+    ``seed``, ``cfg`` and ``sq`` (P.sq, or None for a rule without square averages; P.mom exists for the rules with a
+    momentum buffer). No torch autograd, no torch.optim."""
+
+    def __init__(self, shape: H.ModelShape, device, seed, fourier_scale: float, hard_mul_const: float, optimizer: str,
+                 lr: float, rmsprop_decay: float, rmsprop_eps: float, momentum: float, num_iters: int):
+        self.lr, self.num_iters = float(lr), int(num_iters)
+        self.cfg = H.opt_config(optimizer, lr, alpha=rmsprop_decay, eps=rmsprop_eps, momentum=momentum)
+        uses_sq, uses_mom = H.opt_uses(self.cfg)
+        self.P = FlatParams(shape, device, with_state=True, with_mom=uses_mom)
+        self.sq = self.P.sq if uses_sq else None
+        fB0, ws0, bs0, _ = reference_init(shape, fourier_scale, None, seed)
+        self.P.load(fB0, ws0, bs0, None)
+        super().__init__(shape, self.P.pack(self.P.flat, True), self.P.pack(self.P.grad, False), hard_mul_const)
+
+    def opt_step(self, t: int) -> None:
+        """the optimiser step after t earlier ones, on P.grad"""
+        lr = cosine_lr(self.lr, t, self.num_iters) if self.num_iters > 0 else self.lr
+        H.opt_step(self.cfg, self.P.flat, self.P.grad, self.sq, self.P.mom, None, t, lr=lr)
+
+    def evaluate(self, x: torch.Tensor) -> torch.Tensor:
+        """model(x) for any number of rows (n, D): (n, L), on a workspace of its own"""
+        if not x.is_cuda:
+            raise H.NsvdError("FlatModel.evaluate: coordinates must live on the GPU (no CPU path)")
+        x = x.float().contiguous()
+        return self.forward(x, H.model_workspace(self.shape, x.shape[0], x.device), save_for_backward=False)
+
+
 class FusedTrainer:
     """The step as one object, and the HIP compute backend of parallel.dp_step / parallel.hp_step (every protocol
     method below enqueues kernels on the current stream of ``device`` and returns)."""

@@ -428,3 +428,61 @@ def test_trainer_is_the_class_path_plus_opt_step(L, m, hidden, B, split):
     x_eval = op.sample(64, torch.Generator(device=DEV).manual_seed(99))
     with torch.no_grad():
         assert torch.equal(spinx.forward(x_eval), tr.forward(x_eval))
+
+
+OPT_RULES = [("sgd", 0.9, 3), ("adam", 0.0, 0), ("rmsprop", 0.5, 3)]
+
+
+@pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("optimizer,momentum,num_iters", OPT_RULES)
+def test_trainer_optimizer_rules_are_the_class_path_plus_opt_step(optimizer, momentum, num_iters, split):
+    """the rules beside plain RMSprop (a momentum buffer, no square average, the cosine schedule), which all three kernel
+    trainers take from trainer.FlatModel: three steps of SpinxKernelTrainer = three steps of the class path +
+    nsvd_opt_step per tensor with its own state buffers and the scheduled rate, bit for bit (t = 3 = num_iters, where
+    the rate is zero, is not reached)"""
+    from neural_svd_amd import hip_ops as H
+    from neural_svd_amd.kernel_ops import RadialKernelOperator
+    from neural_svd_amd.spinx import SpinxKernelTrainer
+    from neural_svd_amd.trainer import cosine_lr
+    (L, m, hidden, B), D, decay, lr = (4, 8, (16, 16), 25), 2, 0.05, 1e-3
+    op = RadialKernelOperator(H.RBF_GAUSSIAN, X.ELL, D, device=DEV)
+    tr = SpinxKernelTrainer(op, L=L, m=m, hidden=hidden, batch_size=B, decay=decay, split_batch=split, lr=lr,
+                            optimizer=optimizer, rmsprop_decay=0.99, momentum=momentum, num_iters=num_iters,
+                            fourier_scale=X.FOURIER_SCALE, hard_mul_const=0.8, seed=3)
+    xs = [op.sample(B, torch.Generator(device=DEV).manual_seed(40 + i)) for i in range(3)]
+    init, fB = [t.clone() for t in tr.P.views(tr.P.flat)], tr.P.fourier_B.clone()
+    losses = [tr.step(x).clone() for x in xs]
+    tr.check()
+    n = len(hidden) + 1
+    spinx = _build(dict(L=L, D=D, m=m, hidden=hidden, decay=decay), fB, init[:n], init[n:], 0.8)
+    params = spinx.model.trainable_tensors()
+    cfg = H.opt_config(optimizer, lr, alpha=0.99, eps=1e-10, momentum=momentum)
+    uses_sq, uses_mom = H.opt_uses(cfg)
+    assert (tr.P.mom is not None) == uses_mom and uses_sq == (optimizer != "sgd")
+    sq = [torch.zeros_like(p.data).view(-1) if uses_sq else None for p in params]
+    mom = [torch.zeros_like(p.data).view(-1) if uses_mom else None for p in params]
+    for t, x in enumerate(xs):
+        spinx.zero_grad()
+        loss, _ = spinx.compute_loss_kernel(op.get_approx_kernel_op, x, None, split_batch=split)
+        loss.backward()
+        assert torch.equal(loss.detach(), losses[t][0].float())
+        for p, s, v in zip(params, sq, mom):
+            H.opt_step(cfg, p.data.view(-1), p.grad.contiguous().view(-1), s, v, None, t,
+                       lr=cosine_lr(lr, t, num_iters) if num_iters else None)
+    for p, got in zip(params, tr.P.views(tr.P.flat)):
+        assert torch.equal(p.data, got)
+    assert not any(torch.equal(a, b) for a, b in zip(init, tr.P.views(tr.P.flat)))
+    assert torch.equal(spinx.sigma_avg.data, tr.sigma_avg) and torch.equal(spinx.chol.data, tr.chol)
+
+
+def test_trainer_refuses_an_unknown_optimizer_and_a_decay_outside_the_unit_interval():
+    from neural_svd_amd import hip_ops as H
+    from neural_svd_amd._lib import NsvdError
+    from neural_svd_amd.kernel_ops import RadialKernelOperator
+    from neural_svd_amd.spinx import SpinxKernelTrainer
+    op = RadialKernelOperator(H.RBF_GAUSSIAN, X.ELL, 2, device=DEV)
+    with pytest.raises(NsvdError):
+        SpinxKernelTrainer(op, L=4, m=8, hidden=(16, 16), batch_size=25, optimizer="lbfgs")
+    for decay in (-0.01, 1.5):
+        with pytest.raises(ValueError, match="decay"):
+            SpinxKernelTrainer(op, L=4, m=8, hidden=(16, 16), batch_size=25, decay=decay)
