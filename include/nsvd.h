@@ -1070,6 +1070,32 @@ int nsvd_nef_loss(const float* phi, const float* Tphi, int B, const float* phi1,
 /* f[b, l] /= norm[l], Tf[b, l] /= norm[l] in place: BatchL2NormalizedFunctions in evaluation mode (utils.py:54-56). */
 int nsvd_nef_scale_heads(float* f, float* Tf, const float* norm, int B, int L, void* stream);
 
+/* ---- NeuralEF on a matrix-free kernel operator: the batch normalisation of a plain (B, L) block ---------------------
+ * nsvd_nef_rows_forward: BatchL2NormalizedFunctions.forward in training mode (methods/utils.py:48-68) on the raw head
+ * outputs u (B, L) of ONE model evaluation. The rows are one segment (B1 == B) or the two segments [0, B1) and [B1, B)
+ * (the two model calls of a split step, methods/neuralef.py:113-118), each with at least one row. Per segment h and
+ * head l: n_h[l] = ||u_h[:, l]|| / sqrt(B_h) (utils.py:51), phi = u / n_h (utils.py:56; phi may alias u), and stats
+ * (2 L) = n_1 | n_2 (one segment: n_1 twice). A zero norm is divided by, as in the reference.
+ * The running norms norm_biased / norm_unbiased (L each) take n_order <= 4 updates (utils.py:58-68), update k with the
+ * norm of segment order[k] (a HOST array, read before the call returns): biased m r + (1 - m) n, unbiased
+ * sqrt(m r^2 + (1 - m) n^2); *initialized == 0 makes the first one a copy, and a call with n_order > 0 sets it to 1
+ * (device int: no host read in a step). n_order == 0 touches neither the running norms nor *initialized (all three
+ * may then be NULL).
+ * The column sums of squares are float64: per block of rows, then over the blocks by every workgroup that needs them,
+ * each in a fixed order (no floating-point atomics: equal bits from run to run). 1 <= L <= 64, B <= 65536.
+ * ws: nsvd_nef_rows_workspace_bytes(B, L) bytes (0: unsupported shape), 256-byte aligned.
+ *
+ * nsvd_nef_rows_backward: the cotangent of u. g = dphi (+ dphi1 + dphi2 when BOTH are given: the three gradients
+ * NeuralEigenfunctionsLossFunction returns for phi1 = phi2 = phi, neuralef.py:61-62; each (B, L), added in float64),
+ * s_h[l] = mean over the rows of segment h of g phi (float64, the same two ordered passes), du = (g - phi s_h) / n_h
+ * formed in float64 and rounded once. du may alias dphi. stats == NULL (batchnorm_mode 'none'): du = g, phi unused. */
+size_t nsvd_nef_rows_workspace_bytes(int B, int L);
+int nsvd_nef_rows_forward(const float* u, int B, int B1, int L, float* phi, float* stats, float* norm_biased,
+                          float* norm_unbiased, int* initialized, float momentum, const int* order, int n_order,
+                          void* ws, size_t ws_bytes, void* stream);
+int nsvd_nef_rows_backward(const float* phi, const float* stats, int B, int B1, int L, const float* dphi,
+                           const float* dphi1, const float* dphi2, float* du, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Retrieval metrics of the CDK towers: examples/cdk/sketchy/retrieve.py ----------------------------------------
  * For each of the Nq queries the WHOLE gallery is ranked by descending key, ties by ASCENDING gallery index (a stable
  * sort; faiss leaves ties open, here the rule is part of the contract). Key s_ij: NSVD_RETR_INNER_PRODUCT x_i . y_j

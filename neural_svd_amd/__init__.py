@@ -6,7 +6,7 @@ this package is the host-side mirror of the reference's Python interface for tha
 from . import _lib  # noqa: F401
 
 __all__ = ["_lib", "SketchyRetrieval", "evaluate_truncations", "Nystrom", "run_nystrom", "NystromSVD", "DotKernelOperator",
-           "SpIN", "SpinKernelTrainer", "SpINx", "SpinxKernelTrainer", "PairedFunctions", "KernelSvdTrainer", "gaussian_cross_singular_values",
+           "SpIN", "SpinKernelTrainer", "SpINx", "SpinxKernelTrainer", "NefKernelTrainer", "PairedFunctions", "KernelSvdTrainer", "gaussian_cross_singular_values",
            "gaussian_cross_modes", "kernel_singular_values"]
 
 
@@ -31,6 +31,9 @@ def __getattr__(name):
     if name in ("SpINx", "SpinxKernelTrainer"):  # SpINx on the kernel-operator path (spinx.py), the same way
         from . import spinx
         return getattr(spinx, name)
+    if name == "NefKernelTrainer":  # NeuralEF on the kernel-operator path (neuralef.py), the same way
+        from . import neuralef
+        return neuralef.NefKernelTrainer
     if name in ("PairedFunctions", "KernelSvdTrainer"):  # the kernel SVD path (kernel_svd.py), the same way
         from . import kernel_svd
         return getattr(kernel_svd, name)

@@ -224,6 +224,9 @@ SIGNATURES = {
     "nsvd_nef_loss_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "nsvd_nef_loss": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "nsvd_nef_scale_heads": (_I, [_P, _P, _P, _I, _I, _P]),
+    "nsvd_nef_rows_workspace_bytes": (_Z, [_I, _I]),
+    "nsvd_nef_rows_forward": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, C.c_float, C.POINTER(C.c_int), _I, _P, _Z, _P]),
+    "nsvd_nef_rows_backward": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "nsvd_retrieval_max_gallery": (_I, []),
     "nsvd_retrieval_max_k": (_I, []),
     "nsvd_retrieval_max_d": (_I, []),

@@ -1,7 +1,8 @@
 """What SpIN (spin.py) and SpINx (spinx.py) share on the matrix-free kernel operators: the per-shape device buffers
 of a step, its two ends (model forward + Kphi; the swapped-argument product + model backward), the refusals of the
-two class paths with their common nn.Module base, and the base of the two trainers on flat buffers. Each method
-keeps its own moments, solve and cotangents."""
+two class paths with their common nn.Module base, and the base of the two trainers on flat buffers - whose
+method-independent part, KernelTrainer, is also the base of NeuralEF's trainer (neuralef.py). Each method keeps its own
+moments, solve and cotangents."""
 from __future__ import annotations
 
 import torch
@@ -135,34 +136,24 @@ class WhitenedMethod(nn.Module):
 
 
 # ---- the trainers on flat buffers -------------------------------------------------------------------------------------
-class WhitenedKernelTrainer:
-    """what SpinKernelTrainer and SpinxKernelTrainer share: one FlatModel, sigma_avg / chol, the buffers of the step
-    shape (``Work``, a StepBuffers subclass whose ``loss`` is what step() returns), the batch, check() and the
-    orthonormalised forward. model_kw: FlatModel's arguments after the device."""
-    Work = None
-    FAILED = ""  # what check() reports
+class KernelTrainer:
+    """what every method's trainer on a matrix-free kernel operator shares (SpIN, SpINx here, NeuralEF in neuralef.py):
+    the refusals, one FlatModel, the batch and the optimiser step; a subclass sets ``loss``, what step() returns.
+    dims = (L, m, hidden), L within MIN_L..MAX_L; model_kw: FlatModel's arguments after the device."""
+    MIN_L, MAX_L = 1, 64
 
-    def __init__(self, op, dims, batch_size: int, decay: float, split_batch: bool, index_seed: int, **model_kw):
+    def __init__(self, op, dims, batch_size: int, index_seed: int, **model_kw):
         who = type(self).__name__
         L, m, hidden = dims
         if not isinstance(op, MatrixFreeKernelOperator):
             raise NotImplementedError(f"{who}: a MatrixFreeKernelOperator (radial or dot-product kernel)")
-        if not 2 <= int(L) <= H.SPIN_MAX_L:
-            raise ValueError(f"{who}: L must be in 2..{H.SPIN_MAX_L}")
-        if not 0.0 <= float(decay) <= 1.0:
-            raise ValueError(f"{who}: decay must be in [0, 1]")
-        self.op, self.device, self.decay = op, op.device, float(decay)
-        dev = self.device
+        if not self.MIN_L <= int(L) <= self.MAX_L:
+            raise ValueError(f"{who}: L must be in {self.MIN_L}..{self.MAX_L}")
+        self.op, self.device, self.B = op, op.device, int(batch_size)
         self.shape = H.ModelShape(L=int(L), D=op.dim, m=int(m), hidden=tuple(hidden), has_exp_mask=False)
-        self.work = w = self.Work(op, self.shape, int(batch_size), bool(split_batch), dev)
-        self.model = FlatModel(self.shape, dev, **model_kw)
+        self.model = FlatModel(self.shape, self.device, **model_kw)
         self.P, self.c = self.model.P, self.model.c
-        self.sigma_avg = torch.zeros((L, L), dtype=torch.float32, device=dev)
-        self.chol = torch.zeros((L, L), dtype=torch.float32, device=dev)
-        w.with_backward()
-        self.B, self.B1, self.B2, self.split = w.B, w.B1, w.B2, w.split
-        self.status, self.loss, self.phi = w.status, w.loss, w.phi_all[:w.B1]
-        self.gen = torch.Generator(device=dev).manual_seed(index_seed)
+        self.gen = torch.Generator(device=self.device).manual_seed(index_seed)
         self.t = 0
 
     def _batch(self, x, what: str):
@@ -173,6 +164,26 @@ class WhitenedKernelTrainer:
         self.model.opt_step(self.t)
         self.t += 1
         return self.loss
+
+
+class WhitenedKernelTrainer(KernelTrainer):
+    """what SpinKernelTrainer and SpinxKernelTrainer add: sigma_avg / chol, the buffers of the step shape (``Work``, a
+    StepBuffers subclass whose ``loss`` is what step() returns), check() and the orthonormalised forward."""
+    MIN_L, MAX_L = 2, H.SPIN_MAX_L
+    Work = None
+    FAILED = ""  # what check() reports
+
+    def __init__(self, op, dims, batch_size: int, decay: float, split_batch: bool, index_seed: int, **model_kw):
+        super().__init__(op, dims, batch_size, index_seed, **model_kw)
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"{type(self).__name__}: decay must be in [0, 1]")
+        self.decay, dev, L = float(decay), self.device, self.shape.L
+        self.work = w = self.Work(op, self.shape, self.B, bool(split_batch), dev)
+        self.sigma_avg = torch.zeros((L, L), dtype=torch.float32, device=dev)
+        self.chol = torch.zeros((L, L), dtype=torch.float32, device=dev)
+        w.with_backward()
+        self.B1, self.B2, self.split = w.B1, w.B2, w.split
+        self.status, self.loss, self.phi = w.status, w.loss, w.phi_all[:w.B1]
 
     def check(self) -> None:
         """raise if any step since the last check failed a Cholesky factorisation (one small device read)"""

@@ -407,6 +407,51 @@ void dot_apply_pair(const at::Tensor& x, const at::Tensor& y, const at::Tensor& 
              "nsvd_dot_apply_pair");
 }
 
+// NeuralEF's batch normalisation of a (B, L) block and its reverse mode (nsvd_nef_rows_forward / _backward)
+void nef_rows_forward(const at::Tensor& u, int64_t B1, at::Tensor phi, at::Tensor stats,
+                      c10::optional<at::Tensor> norm_biased, c10::optional<at::Tensor> norm_unbiased,
+                      c10::optional<at::Tensor> initialized, double momentum, std::vector<int> order, at::Tensor ws) {
+    Dev dv;
+    TORCH_CHECK(u.dim() == 2 && phi.dim() == 2 && phi.size(0) == u.size(0) && phi.size(1) == u.size(1),
+                "nef_rows_forward: u and phi (B, L)");
+    const int B = (int)u.size(0), L = (int)u.size(1);
+    TORCH_CHECK(stats.numel() == 2 * (int64_t)L, "nef_rows_forward: stats must hold 2 L values");
+    TORCH_CHECK(order.size() <= 4, "nef_rows_forward: at most four running-norm updates");
+    TORCH_CHECK((!norm_biased.has_value() || norm_biased->numel() == L) &&
+                    (!norm_unbiased.has_value() || norm_unbiased->numel() == L),
+                "nef_rows_forward: the running norms hold L values");
+    float *up = f32(dv, u, "u"), *pp = f32(dv, phi, "phi"), *sp = f32(dv, stats, "stats");
+    float *nb = f32_opt(dv, norm_biased, "norm_biased"), *nu = f32_opt(dv, norm_unbiased, "norm_unbiased");
+    int* init = nullptr;
+    if (initialized.has_value()) {
+        dv.see(*initialized, "initialized");
+        TORCH_CHECK(initialized->scalar_type() == at::kInt && initialized->numel() == 1, "initialized must be one int32");
+        init = initialized->data_ptr<int>();
+    }
+    void* wp = bytes(dv, ws, "ws");
+    check_rc(nsvd_nef_rows_forward(up, B, (int)B1, L, pp, sp, nb, nu, init, (float)momentum, order.data(),
+                                   (int)order.size(), wp, (size_t)ws.numel() * ws.element_size(), dv.stream()),
+             "nsvd_nef_rows_forward");
+}
+
+void nef_rows_backward(c10::optional<at::Tensor> phi, c10::optional<at::Tensor> stats, int64_t B1, const at::Tensor& dphi,
+                       c10::optional<at::Tensor> dphi1, c10::optional<at::Tensor> dphi2, at::Tensor du, at::Tensor ws) {
+    Dev dv;
+    TORCH_CHECK(dphi.dim() == 2, "nef_rows_backward: dphi (B, L)");
+    const int B = (int)dphi.size(0), L = (int)dphi.size(1);
+    auto same = [&](const at::Tensor& t) { return t.dim() == 2 && t.size(0) == B && t.size(1) == L; };
+    TORCH_CHECK(same(du) && (!phi.has_value() || same(*phi)) && (!dphi1.has_value() || same(*dphi1)) &&
+                    (!dphi2.has_value() || same(*dphi2)),
+                "nef_rows_backward: phi, dphi1, dphi2 and du are (B, L) like dphi");
+    TORCH_CHECK(!stats.has_value() || stats->numel() == 2 * (int64_t)L, "nef_rows_backward: stats must hold 2 L values");
+    float *pp = f32_opt(dv, phi, "phi"), *sp = f32_opt(dv, stats, "stats"), *gp = f32(dv, dphi, "dphi");
+    float *g1 = f32_opt(dv, dphi1, "dphi1"), *g2 = f32_opt(dv, dphi2, "dphi2"), *dp = f32(dv, du, "du");
+    void* wp = bytes(dv, ws, "ws");
+    check_rc(nsvd_nef_rows_backward(pp, sp, B, (int)B1, L, gp, g1, g2, dp, wp, (size_t)ws.numel() * ws.element_size(),
+                                    dv.stream()),
+             "nsvd_nef_rows_backward");
+}
+
 // retrieval metrics (nsvd_retrieval_eval): zq / zg may be column windows (unit column stride); outputs as passed
 void retrieval_eval(const at::Tensor& zq, const at::Tensor& zg, const at::Tensor& q_cls, const at::Tensor& g_cls,
                     c10::optional<at::Tensor> n_relevant_items, int64_t metric, int64_t K,
@@ -481,7 +526,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                         "nsvd_dot_apply",
                                         "nsvd_dot_apply_workspace_bytes", "nsvd_dot_apply_pair",
                                         "nsvd_dot_apply_pair_workspace_bytes", "nsvd_dot_apply_pair_partition",
-                                        "nsvd_retrieval_eval",
+                                        "nsvd_nef_rows_forward", "nsvd_nef_rows_backward",
+                                        "nsvd_nef_rows_workspace_bytes", "nsvd_retrieval_eval",
                                         "nsvd_retrieval_workspace_bytes", "nsvd_retrieval_max_gallery",
                                         "nsvd_retrieval_max_k", "nsvd_retrieval_max_d"};
     });
@@ -532,6 +578,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         check_rc(nsvd_dot_apply_pair_partition(B1, B2, D, L, &rg, &cs), "nsvd_dot_apply_pair_partition");
         return std::vector<int>{rg, cs};
     });
+    m.def("nef_rows_forward", &nef_rows_forward);
+    m.def("nef_rows_backward", &nef_rows_backward);
+    m.def("nef_rows_workspace_bytes", [](int B, int L) { return (int64_t)nsvd_nef_rows_workspace_bytes(B, L); });
     m.def("retrieval_eval", &retrieval_eval);
     m.def("retrieval_workspace_bytes",
           [](int Nq, int Ng, int d, int K) { return (int64_t)nsvd_retrieval_workspace_bytes(Nq, Ng, d, K); });

@@ -1737,9 +1737,10 @@ def nef_operator_backward(shape: ModelShape, params: Params, prob: Problem, x: t
 
 @_on_tensor_device
 def nef_loss(phi: torch.Tensor, Tphi: torch.Tensor, phi1: torch.Tensor, Tphi1: torch.Tensor, phi2: torch.Tensor,
-             Tphi2: torch.Tensor, unbiased: bool, diagonal: int):
+             Tphi2: torch.Tensor, unbiased: bool, diagonal: int, out=None, scratch: Optional[torch.Tensor] = None):
     """NeuralEigenfunctionsLossFunction on the HIP kernels. Returns (loss (1,), dphi, dphi1, dphi2): with phi1 / phi2
-    the two chunks of phi, dphi holds the whole d loss / d phi and dphi1 = dphi2 = None."""
+    the two chunks of phi, dphi holds the whole d loss / d phi and dphi1 = dphi2 = None. out: that tuple as buffers to
+    write (a step that allocates nothing), scratch: nef_loss_scratch of the shape."""
     B, L = phi.shape
     B1, B2 = phi1.shape[0], phi2.shape[0]
     for n, t, rows in (("Tphi", Tphi, B), ("phi1", phi1, B1), ("Tphi1", Tphi1, B1), ("phi2", phi2, B2),
@@ -1753,16 +1754,118 @@ def nef_loss(phi: torch.Tensor, Tphi: torch.Tensor, phi1: torch.Tensor, Tphi1: t
     nbytes = lib.nsvd_nef_loss_workspace_bytes(B, B1, B2, L)
     if nbytes == 0:
         raise NsvdError(f"nsvd_nef_loss: unsupported shape B={B}, B1={B1}, B2={B2}, L={L} (L <= 64)")
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    dphi = torch.empty_like(phi)
-    d1 = None if chunked else torch.empty_like(phi1)
-    d2 = None if chunked else torch.empty_like(phi2)
+    if scratch is None:
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif scratch.numel() < nbytes:
+        raise NsvdError("nsvd_nef_loss: scratch is too small for this shape")
+    if out is None:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        dphi = torch.empty_like(phi)
+        d1 = None if chunked else torch.empty_like(phi1)
+        d2 = None if chunked else torch.empty_like(phi2)
+    else:
+        loss, dphi, d1, d2 = out
+        if tuple(dphi.shape) != (B, L) or (not chunked and (d1 is None or d2 is None or
+                                                          tuple(d1.shape) != (B1, L) or tuple(d2.shape) != (B2, L))):
+            raise NsvdError("nsvd_nef_loss: out must be (loss (1,), dphi (B, L), dphi1 (B1, L), dphi2 (B2, L))")
+        if chunked:
+            d1 = d2 = None
     rc = lib.nsvd_nef_loss(_ptr(phi, "phi"), _ptr(Tphi, "Tphi"), B, _ptr(phi1, "phi1"), _ptr(Tphi1, "Tphi1"), B1,
                            _ptr(phi2, "phi2"), _ptr(Tphi2, "Tphi2"), B2, L, int(bool(unbiased)), int(diagonal),
                            _ptr(loss), _ptr(dphi), _ptr(d1), _ptr(d2), scratch.data_ptr(), nbytes, _stream())
     check(rc, "nsvd_nef_loss")
     return loss, dphi, d1, d2
+
+
+def nef_loss_scratch(B: int, B1: int, B2: int, L: int, device) -> torch.Tensor:
+    nbytes = _lib.load().nsvd_nef_loss_workspace_bytes(int(B), int(B1), int(B2), int(L))
+    if nbytes == 0:
+        raise NsvdError(f"nsvd_nef_loss: unsupported shape B={B}, B1={B1}, B2={B2}, L={L} (L <= 64)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+NEF_MAX_L = 64  # heads nsvd_nef_loss and nsvd_nef_rows_* take
+
+
+def nef_rows_workspace(B: int, L: int, device) -> torch.Tensor:
+    """the workspace of nef_rows_forward / nef_rows_backward on a (B, L) block (either segmentation)"""
+    nbytes = _lib.load().nsvd_nef_rows_workspace_bytes(int(B), int(L))
+    if nbytes == 0:
+        raise NsvdError(f"nsvd_nef_rows: unsupported shape B={B}, L={L} (1 <= L <= {NEF_MAX_L}, B <= 65536)")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _nef_rows_shape(u: torch.Tensor, B1: Optional[int], name: str):
+    if u.dim() != 2:
+        raise NsvdError(f"{name} must be (B, L)")
+    B, L = u.shape
+    B1 = B if B1 is None else int(B1)
+    if not 1 <= B1 <= B:
+        raise NsvdError(f"nsvd_nef_rows: the first segment must hold 1..{B} rows (got {B1})")
+    return B, B1, L
+
+
+@_on_tensor_device
+def nef_rows_forward(u: torch.Tensor, B1: Optional[int], norm_biased: Optional[torch.Tensor],
+                     norm_unbiased: Optional[torch.Tensor], initialized: Optional[torch.Tensor], momentum: float,
+                     order=(0,), ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                     stats: Optional[torch.Tensor] = None):
+    """BatchL2NormalizedFunctions.forward in training mode on the raw head outputs u (B, L) (nsvd_nef_rows_forward):
+    the rows are one segment (B1 None or B) or the two segments [0, B1), [B1, B). Returns (phi = u / n_h by segment,
+    stats (2, L) = the batch norms n_1 | n_2); the running norms (L values each) take one update per entry of `order`
+    (segment indices, at most four; none: the three state tensors may be None) and `initialized` (int32, 1 value) is
+    set. out may be u."""
+    B, B1, L = _nef_rows_shape(u, B1, "u")
+    order = tuple(int(o) for o in order)
+    if len(order) > 4 or any(o not in ((0, 1) if B1 < B else (0,)) for o in order):
+        raise NsvdError("nsvd_nef_rows_forward: order holds at most four indices of existing segments")
+    if order and (norm_biased is None or norm_unbiased is None or initialized is None):
+        raise NsvdError("nsvd_nef_rows_forward: running-norm updates need norm_biased, norm_unbiased and initialized")
+    for n, t in (("norm_biased", norm_biased), ("norm_unbiased", norm_unbiased)):
+        if t is not None and t.numel() != L:
+            raise NsvdError(f"{n} must hold {L} values")
+    if out is None:
+        out = torch.empty_like(u)
+    elif tuple(out.shape) != (B, L):
+        raise NsvdError("nsvd_nef_rows_forward: out must be (B, L)")
+    if stats is None:
+        stats = torch.empty((2, L), dtype=torch.float32, device=u.device)
+    elif stats.numel() != 2 * L:
+        raise NsvdError("nsvd_nef_rows_forward: stats must hold 2 L values")
+    if ws is None:
+        ws = nef_rows_workspace(B, L, u.device)
+    rc = _lib.load().nsvd_nef_rows_forward(_ptr(u, "u"), B, B1, L, _ptr(out, "out"), _ptr(stats, "stats"),
+                                           _ptr(norm_biased, "norm_biased"), _ptr(norm_unbiased, "norm_unbiased"),
+                                           _ptr(initialized, "initialized", torch.int32), float(momentum),
+                                           (C.c_int * 4)(*(order + (0,) * (4 - len(order)))), len(order),
+                                           ws.data_ptr(), ws.numel(), _stream())
+    check(rc, "nsvd_nef_rows_forward")
+    return out, stats
+
+
+@_on_tensor_device
+def nef_rows_backward(phi: Optional[torch.Tensor], stats: Optional[torch.Tensor], B1: Optional[int],
+                      dphi: torch.Tensor, dphi1: Optional[torch.Tensor] = None, dphi2: Optional[torch.Tensor] = None,
+                      ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the cotangent of u (nsvd_nef_rows_backward): g = dphi (+ dphi1 + dphi2, each (B, L)), du = (g - phi s_h) / n_h
+    with s_h the segment's column means of g phi; stats None (batchnorm_mode 'none'): du = g. out may be dphi."""
+    B, B1, L = _nef_rows_shape(dphi, B1, "dphi")
+    if (dphi1 is None) != (dphi2 is None):
+        raise NsvdError("nsvd_nef_rows_backward: dphi1 and dphi2 come together")
+    for n, t in (("phi", phi), ("dphi1", dphi1), ("dphi2", dphi2), ("out", out)):
+        if t is not None and tuple(t.shape) != (B, L):
+            raise NsvdError(f"nsvd_nef_rows_backward: {n} must be {(B, L)}")
+    if stats is not None and (phi is None or stats.numel() != 2 * L):
+        raise NsvdError("nsvd_nef_rows_backward: stats (2 L values) comes with phi")
+    if out is None:
+        out = torch.empty_like(dphi)
+    if ws is None:
+        ws = nef_rows_workspace(B, L, dphi.device)
+    rc = _lib.load().nsvd_nef_rows_backward(_ptr(phi, "phi"), _ptr(stats, "stats"), B, B1, L, _ptr(dphi, "dphi"),
+                                            _ptr(dphi1, "dphi1"), _ptr(dphi2, "dphi2"), _ptr(out, "out"),
+                                            ws.data_ptr(), ws.numel(), _stream())
+    check(rc, "nsvd_nef_rows_backward")
+    return out
 
 
 @_on_tensor_device

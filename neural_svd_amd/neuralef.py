@@ -11,6 +11,10 @@ the raw head outputs, the per-stencil-point batch norms and running-norm updates
 folded into the even / odd stencil. Any other density or callable runs the reference's op sequence
 through ``BatchL2NormalizedFunctions.forward`` around the HIP model. The loss is the HIP kernel nsvd_nef_loss in
 every case. There is no CPU / eager fallback.
+
+    NefKernelTrainer(op, L, m, hidden, batch_size, split_batch, ...)   compute_loss_kernel's step on a matrix-free kernel
+                                                                       operator on flat buffers, no torch autograd
+                                                                       (nsvd_nef_rows_forward / _backward)
 """
 from __future__ import annotations
 
@@ -20,6 +24,7 @@ import torch.nn as nn
 
 from . import hip_ops as H
 from ._lib import NsvdError
+from ._spin_step import KernelTrainer
 
 
 def _flat(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -264,3 +269,109 @@ class NeuralEigenfunctions(nn.Module):
         prob = fused_problem_of(operator, importance, self.model)
         x = x.reshape(x.shape[0], -1).float().contiguous()
         return _OperatorFn.apply(x, self, operator, prob, *self.model.trainable_tensors())
+
+
+_BN_MODES = ("biased", "unbiased", "none")
+
+
+class NefKernelTrainer(KernelTrainer):
+    """NeuralEF's training step on a matrix-free kernel operator (NeuralEigenfunctions.compute_loss_kernel, loss.backward(),
+    optimiser - methods/neuralef.py:108-134 with the optimiser of examples/utils.py:48-72) as a fixed sequence of C-ABI
+    calls on flat buffers: nsvd_model_forward ONCE on all B rows -> nsvd_nef_rows_forward (the batch norms of the one or
+    two segments, phi = u / n in place, the running-norm updates; skipped for batchnorm_mode 'none') -> Kphi, one
+    matrix-free product (not split: op.apply_raw(x, x, phi, 1 / B); split: x1, x2 = chunk(x, 2) and ONE
+    op.apply_pair_raw(x1, x2, phi2, phi1, 1 / B2, 1 / B1) into the two row ranges of Kphi, every kernel value evaluated
+    once) -> nsvd_nef_loss (split: the chunked form; not split: phi1 = phi2 = phi as independent halves) ->
+    nsvd_nef_rows_backward (the three cotangents added, then back through u / n(u)) -> nsvd_model_backward ONCE ->
+    nsvd_opt_step. No torch autograd, no torch.optim; torch draws the batch. The loss sends no gradient into Kphi
+    (neuralef.py:61-62), so there is no swapped-argument product. Single GPU.
+
+    The running norms are updated in the order MatrixFreeKernelOperator.get_approx_kernel_op evaluates the model
+    (model(x) first, model(x_ref) only when x_ref is another batch): segment 0 once, or with split_batch segments
+    0, 1, 1, 0.
+
+    ``loss`` (1,), ``phi`` and ``Kphi`` (B, L), ``norm_biased`` / ``norm_unbiased`` (L) and ``initialized`` (int32)
+    live on the device; nothing is read back in a step."""
+
+    MIN_L, MAX_L = 1, H.NEF_MAX_L
+
+    def __init__(self, op, L: int, m: int, hidden=(128, 128), batch_size: int = 8192, split_batch: bool = False,
+                 unbiased: bool = False, include_diag: bool = False, batchnorm_mode: str = "unbiased",
+                 bn_momentum: float = 0.9, lr: float = 1e-4, optimizer: str = "rmsprop", rmsprop_decay: float = 0.99,
+                 rmsprop_eps: float = 1e-10, momentum: float = 0.0, num_iters: int = 0, fourier_scale: float = 0.05,
+                 hard_mul_const: float = 1.0, seed: int = 0, index_seed: int = 1):
+        if batchnorm_mode not in _BN_MODES:
+            raise ValueError(f"NefKernelTrainer: batchnorm_mode must be one of {_BN_MODES}")
+        if split_batch and int(batch_size) < 2:
+            raise ValueError("NefKernelTrainer: split_batch needs at least 2 rows")
+        super().__init__(op, (L, m, hidden), batch_size, index_seed, seed=seed, fourier_scale=fourier_scale,
+                         hard_mul_const=hard_mul_const, optimizer=optimizer, lr=lr, rmsprop_decay=rmsprop_decay,
+                         rmsprop_eps=rmsprop_eps, momentum=momentum, num_iters=num_iters)
+        B, dev, f32 = self.B, self.device, torch.float32
+        self.split, self.unbiased, self.diagonal = bool(split_batch), bool(unbiased), 0 if include_diag else 1
+        self.batchnorm_mode, self.bn_momentum = batchnorm_mode, float(bn_momentum)
+        self.B1 = (B + 1) // 2 if self.split else B  # as torch.chunk splits
+        self.B2 = B - self.B1 if self.split else B
+        self.order = (0, 1, 1, 0) if self.split else (0,)
+        self.model_ws = H.model_workspace(self.shape, B, dev)
+        self.ka_ws = op.workspace_pair(self.B1, self.B2, L, dev) if self.split else op.workspace(B, B, L, dev)
+        self.phi = torch.empty((B, L), dtype=f32, device=dev)
+        self.Kphi = torch.empty_like(self.phi)
+        self.dphi = torch.empty_like(self.phi)
+        # (not split: the loss returns three gradients for the one phi; nsvd_nef_rows_backward adds them)
+        self.dphi1, self.dphi2 = (None, None) if self.split else (torch.empty_like(self.phi), torch.empty_like(self.phi))
+        self.loss = torch.zeros(1, dtype=f32, device=dev)
+        self.loss_ws = H.nef_loss_scratch(B, self.B1, self.B2, L, dev)
+        self.rows_ws = H.nef_rows_workspace(B, L, dev)
+        self.stats = torch.ones((2, L), dtype=f32, device=dev) if batchnorm_mode != "none" else None
+        self.norm_biased = torch.ones(L, dtype=f32, device=dev)
+        self.norm_unbiased = torch.ones(L, dtype=f32, device=dev)
+        self.initialized = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def step(self, x: torch.Tensor = None) -> torch.Tensor:
+        """one optimiser step on the (B, D) coordinate batch x (or a fresh draw); returns ``loss`` (no sync)"""
+        x = self._batch(x, "step")
+        B1, phi, Kphi = self.B1, self.phi, self.Kphi
+        self.model.forward(x, self.model_ws, out=phi)
+        if self.stats is not None:
+            H.nef_rows_forward(phi, B1, self.norm_biased, self.norm_unbiased, self.initialized, self.bn_momentum,
+                               self.order, ws=self.rows_ws, out=phi, stats=self.stats)
+        if self.split:
+            self.op.apply_pair_raw(x[:B1], x[B1:], phi[B1:], phi[:B1], 1.0 / self.B2, 1.0 / B1, ws=self.ka_ws,
+                                   out_x=Kphi[:B1], out_y=Kphi[B1:])
+            halves = (phi[:B1], Kphi[:B1], phi[B1:], Kphi[B1:])
+        else:
+            self.op.apply_raw(x, x, phi, 1.0 / self.B2, ws=self.ka_ws, out=Kphi)
+            halves = (phi, Kphi, phi, Kphi)
+        H.nef_loss(phi, Kphi, *halves, self.unbiased, self.diagonal,
+                   out=(self.loss, self.dphi, self.dphi1, self.dphi2), scratch=self.loss_ws)
+        H.nef_rows_backward(phi, self.stats, B1, self.dphi, self.dphi1, self.dphi2, ws=self.rows_ws, out=self.dphi)
+        self.model.backward(x, self.dphi, self.model_ws)
+        return self._opt_step()
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """the evaluation-mode model (NeuralEigenfunctions.forward under eval()): model(x) / norm_biased with either
+        batchnorm_mode (utils.py:55 tests the mode string: DESIGN.md 3.9), model(x) itself with 'none'"""
+        u = self.model.evaluate(x)
+        return u if self.stats is None else u / self.norm_biased
+
+    __call__ = forward
+
+    @torch.no_grad()
+    def register_norm(self, data: torch.Tensor) -> None:
+        """BatchL2NormalizedFunctions.register_norm (utils.py:70-86): both running norms become the model's column
+        norms over ``data`` (n, D), evaluated in batches that are halved whenever one fails"""
+        if self.stats is None:
+            raise NsvdError("NefKernelTrainer.register_norm: batchnorm_mode 'none' keeps no norms")
+        batch_size = len(data)
+        while True:
+            try:
+                sq = sum(self.model.evaluate(data[i:i + batch_size]).norm(dim=0) ** 2
+                         for i in range(0, len(data), batch_size))
+                break
+            except Exception:  # noqa: BLE001 (the reference halves the batch on any failure, e.g. out of memory)
+                if batch_size <= 1:
+                    raise
+                batch_size = batch_size // 2
+        self.norm_biased.copy_(torch.sqrt(sq / len(data)))
+        self.norm_unbiased.copy_(self.norm_biased)

@@ -16,6 +16,9 @@ SpIN's loss; --spin-decay is its moving-average rate) with its own steps/s.
 --spinx adds a SpINx column (neural_svd_amd.spinx.SpinxKernelTrainer, the same way; --spinx-decay its moving-average
 rate, --spinx-lr its learning rate, --spinx-weight-freq N re-weights the L + 1 losses by their NTK norms every N steps,
 0 = never) with its own steps/s (the weight updates are inside the timed loop).
+--neuralef adds a NeuralEF column (neural_svd_amd.neuralef.NefKernelTrainer, the same way; --neuralef-unbiased makes
+it mu-EigenGame, --neuralef-lr is its learning rate) with its own steps/s; its functions come out in no fixed order, so
+the sorted quotients are the ones compared.
 --nystrom N adds the Nystrom baseline (neural_svd_amd.Nystrom, matrix-free) on an N-point sample as a comparison
 column: the only one the exponential and the two dot-product kinds have, since their spectra have no closed form here.
 (A polynomial kernel has rank C(dim + degree, degree): keep L + 8 at or below it, see Nystrom's note on oversample.)
@@ -67,6 +70,10 @@ def main():
     ap.add_argument("--spinx-lr", type=float, default=None, help="default: --lr")
     ap.add_argument("--spinx-weight-freq", type=int, default=0, metavar="N",
                     help="SpINx: update the loss weights every N steps (0: never)")
+    ap.add_argument("--neuralef", action="store_true",
+                    help="also train NeuralEF on the same operator and print its column")
+    ap.add_argument("--neuralef-unbiased", action="store_true", help="NeuralEF: the mu-EigenGame form")
+    ap.add_argument("--neuralef-lr", type=float, default=None, help="default: --lr")
     ap.add_argument("--out", default=None,
                     help="default: profiles/rbf_kernel_train.json (radial kinds) or profiles/dot_kernel_train.json")
     a = ap.parse_args()
@@ -190,6 +197,32 @@ def main():
             print("SpINx, sorted quotients, relative error: " + " ".join(f"{v:.2e}" for v in rec["spinx_rel_err_sorted"]))
         print(f"SpINx steps/s {rec['spinx_steps_per_s']}")
         columns.append(("SpINx", sx_vals))
+    if a.neuralef:
+        from neural_svd_amd.neuralef import NefKernelTrainer
+        nef_lr = a.lr if a.neuralef_lr is None else a.neuralef_lr
+        nf = NefKernelTrainer(op, L=a.L, m=a.m, hidden=(128, 128), batch_size=a.B, unbiased=a.neuralef_unbiased,
+                              lr=nef_lr, rmsprop_decay=0.999, rmsprop_eps=1e-10, num_iters=a.steps,
+                              fourier_scale=a.fourier_scale, seed=a.seed, index_seed=a.seed + 1)
+        for _ in range(10):
+            nf.step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps - 10):
+            nf.step()
+        torch.cuda.synchronize()
+        dtn = time.perf_counter() - t0
+        # Rayleigh quotients of the evaluation-mode functions model(x) / norm_biased, as for the other columns
+        nf_vals = kernel_spectrum(op, nf.forward, x_eval, chunk)["eigvals"]
+        rec.update(neuralef_unbiased=bool(a.neuralef_unbiased), neuralef_lr=nef_lr,
+                   neuralef_steps_per_s=round((a.steps - 10) / dtn, 1), neuralef_rayleigh=[float(v) for v in nf_vals],
+                   neuralef_loss=float(nf.loss[0]), neuralef_norm_biased=[float(v) for v in nf.norm_biased.cpu()])
+        if gaussian:
+            rec.update(neuralef_rel_err=[float(v) for v in np.abs(nf_vals - lam) / lam],
+                       neuralef_rel_err_sorted=[float(v) for v in np.abs(np.sort(nf_vals)[::-1] - lam) / lam])
+            print("NeuralEF, sorted quotients, relative error: " +
+                  " ".join(f"{v:.2e}" for v in rec["neuralef_rel_err_sorted"]))
+        print(f"NeuralEF steps/s {rec['neuralef_steps_per_s']}")
+        columns.append(("NeuralEF", np.sort(nf_vals)[::-1]))
     if a.nystrom:
         from neural_svd_amd import Nystrom
         ny = Nystrom(op, op.sample(a.nystrom, torch.Generator(device=dev).manual_seed(a.seed + 2000)), a.L)
