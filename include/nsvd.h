@@ -615,8 +615,9 @@ int nsvd_rbf_apply_pair(const float* x, int B1, const float* y, int B2, int D, c
  * size 0). x.y is formed on the fp32 MFMA (an inner product has no cancellation to protect), the map is applied in
  * registers and the (B1, B2) kernel matrix is never stored; partial sums over slices of the reference rows are reduced
  * in slice order (no atomics: bit-reproducible). The workspace is 256-byte aligned. NSVD_EINVAL: a null pointer, a
- * non-positive size, an unknown kind, (polynomial kind) a degree outside 1..8 or a non-finite gamma or coef0, a short
- * or misaligned workspace. A refused call writes nothing. NEW SYMBOLS ONLY: NSVD_ABI_VERSION stays 6.
+ * non-positive size, an unknown kind (2 is unassigned), (polynomial kind) a degree outside 1..8 or a non-finite gamma or
+ * coef0, (deep ReLU kinds) a depth outside 1..8, a gamma that is not finite and positive or a coef0 that is not finite
+ * and non-negative, a short or misaligned workspace. A refused call writes nothing. NEW SYMBOLS ONLY: NSVD_ABI_VERSION stays 6.
  * Numerical rules (restated in float64 by tests/_dot_oracle.py):
  * - NSVD_DOT_POLYNOMIAL: the integer power is taken by multiplication (no pow, exp or log); the result is whatever
  *   float32 gives for finite inputs.
@@ -626,11 +627,30 @@ int nsvd_rbf_apply_pair(const float* x, int B1, const float* y, int B2, int D, c
  *   pi (1 - t^2 / 2), so the ~4e-4 that float32 leaves in t on the diagonal costs 1e-7.
  * - The ORDER-0 arc-cosine kernel (1 - t / pi) is deliberately NOT offered, and is not a one-line addition: on the
  *   diagonal it turns that 4e-4 in t into a 1e-4 error of the kernel value, and repairing it needs the angle from direct
- *   differences of normalised rows - the radial kernel's VALU cost again. */
+ *   differences of normalised rows - the radial kernel's VALU cost again.
+ * - NSVD_DOT_RELU_NNGP, NSVD_DOT_RELU_NTK: the NNGP kernel S_depth and the neural tangent kernel T_depth of a ReLU
+ *   network `depth` layers deep, weight variance gamma > 0, bias variance coef0 >= 0. These kinds read gamma, coef0 and,
+ *   IN THE degree SLOT, depth (1..8). With A1(c) = (sin t + (pi - t) cos t) / pi and A0(c) = (pi - t) / pi, cos t = c
+ *   clamped to [-1, 1] (Cho & Saul's orders 1 and 0), S_0 = T_0 = x.y, q_0(v) = |v|^2, and for l = 1 .. depth
+ *       p = sqrt(q_{l-1}(x) q_{l-1}(y)),  c = S_{l-1} / p,  S_l = gamma p A1(c) + coef0,
+ *       T_l = S_l + gamma T_{l-1} A0(c),  q_l(v) = gamma q_{l-1}(v) + coef0  (= S_l(v, v): the diagonal in closed form).
+ *   Conventions: S_0 is x.y itself (no input-layer variance), and where p = 0 (a zero row at level 1; with coef0 = 0 at
+ *   every level) both A terms are taken as 0: S_l = T_l = coef0, never a NaN. gamma = 1, coef0 = 0, depth = 1 makes the
+ *   NNGP kind NSVD_DOT_ARCCOS1 (to rounding: p is one root of the product here). Per level the bracket is clamped at 0
+ *   and sin t, pi - t come from the same clamped c, as for NSVD_DOT_ARCCOS1. The NNGP kind is as well conditioned as
+ *   that kind. The NTK kind is NOT, by the argument of the paragraph above: A0 = acos(-c) / pi has an unbounded slope
+ *   at c = +-1, so an error delta of the float32 c becomes sqrt(2 delta) / pi in A0 - about 2e-4 per level where x_i
+ *   meets itself (c = 1 - 1.2e-7), on near-parallel pairs, and on every pair at D = 1. That is a property of forming c
+ *   from a float32 x.y, shared by a float32 composition from library calls, and it is left as it is: no special case
+ *   for x == y, no distance-based 1 - c. Away from c = +-1 both kinds meet the bound of the other kinds. */
 #define NSVD_DOT_POLYNOMIAL 0   /* k = (gamma * x.y + coef0)^degree, integer degree in 1..8 */
 #define NSVD_DOT_ARCCOS1    1   /* k = |x||y| / pi * (sin t + (pi - t) cos t), cos t = x.y / (|x||y|): Cho & Saul's
                                    order-1 arc-cosine kernel = 2 E_w[relu(w.x) relu(w.y)], w ~ N(0, I): the NNGP kernel
                                    of one ReLU layer. gamma, coef0, degree ignored. */
+/* (2 is unassigned: NSVD_EINVAL) */
+#define NSVD_DOT_RELU_NNGP  3   /* k = S_depth: the NNGP kernel of a ReLU network `depth` layers deep (gamma: weight
+                                   variance, coef0: bias variance, degree: the depth, 1..8) */
+#define NSVD_DOT_RELU_NTK   4   /* k = T_depth: the neural tangent kernel of the same network */
 size_t nsvd_dot_apply_workspace_bytes(int B1, int B2, int D, int L);
 int nsvd_dot_apply(const float* x, int B1, const float* y, int B2, int D, const float* f, int L, int kind,
                    float gamma, float coef0, int degree, float scale, float* out, void* ws, size_t ws_bytes,

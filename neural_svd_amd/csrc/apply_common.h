@@ -79,6 +79,20 @@ static inline float apply_radial_cexp(int kind, float ell) {
     return (float)cd;
 }
 
+// the deep ReLU kinds of the dot-product products (NNGP and NTK: apply_relu_deep)
+constexpr __host__ __device__ bool apply_is_relu(int kind) {
+    return kind == NSVD_DOT_RELU_NNGP || kind == NSVD_DOT_RELU_NTK;
+}
+
+// nsvd_dot_apply and nsvd_dot_apply_pair: is `kind` one they serve, with parameters in its range? (the arc-cosine kind
+// reads none of the three; the deep ReLU kinds read the depth from the degree slot)
+static inline bool apply_dot_kind_ok(int kind, float gamma, float coef0, int degree) {
+    if (kind == NSVD_DOT_POLYNOMIAL) return degree >= 1 && degree <= 8 && isfinite(gamma) && isfinite(coef0);
+    if (apply_is_relu(kind))
+        return degree >= 1 && degree <= 8 && isfinite(gamma) && gamma > 0.f && isfinite(coef0) && coef0 >= 0.f;
+    return kind == NSVD_DOT_ARCCOS1;
+}
+
 // raise the dynamic-LDS limit of a file's main-kernel instances; true, to initialise the static that makes it happen once
 static inline bool apply_set_lds_limit(std::initializer_list<const void*> kernels, size_t bytes) {
     for (const void* k : kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
@@ -244,6 +258,47 @@ __device__ __forceinline__ float apply_arccos1(float s, float nx, float ny) {
     const float br = fmaxf(fmaf(acosf(-c), c, sn), 0.f);
     const float k = p * (br * 0.318309886183790671538f);
     return p > 0.f ? k : 0.f;  // a zero row on either side (also c = NaN from 0 / 0)
+}
+
+// the deep ReLU kinds (NNGP: k = S_depth; NTK: k = T_depth, a second chain beside S) of a lane's 16 values s = x.y.
+// nx2 = |x_i|^2 of the lane's row, ny2 = the 16 |y_j|^2. Level l maps S_{l-1} to S_l = gamma p A1(c) + coef0 with
+// p = sqrt(q_{l-1}(x) q_{l-1}(y)), c = S_{l-1} / p, and T_l = S_l + gamma T_{l-1} A0(c). q_l(v) = gl |v|^2 + bl with the
+// wave-uniform gl = gamma^l, bl = gamma bl + coef0: one FMA per pair and level, nothing carried. p = 0 (a zero row at
+// level 1; at every level when coef0 = 0) gives S_l = T_l = coef0. sin t and pi - t come from the SAME clamped c, as in
+// apply_arccos1; with gamma = 1, coef0 = 0, depth = 1 the values are apply_arccos1's up to the rounding of p and of c
+// (p = sqrt(|x|^2 |y|^2) and a corrected reciprocal here, |x| |y| and a division there). A0 = acos(-c) / pi has an unbounded slope at c = +-1: the rounding of c there (the diagonal of a Gram,
+// near-parallel rows, every pair at D = 1) reaches the NTK value as sqrt(2 delta) / pi per level, and is left there.
+template <bool NTK>
+__device__ __forceinline__ void apply_relu_deep(const nsvd_f32x16& sv, float nx2, const float (&ny2)[16], float gamma,
+                                                float coef0, int depth, float (&kv)[16]) {
+    constexpr float inv_pi = 0.318309886183790671538f;
+    float S[16], Tn[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) S[r] = Tn[r] = sv[r];
+    float gl = 1.f, bl = 0.f;
+    for (int l = 0; l < depth; ++l) {
+        const float qx = fmaf(gl, nx2, bl);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            // ONE root: where x_i meets itself qx = qy and p = qx to the bit. c = S / p by the reciprocal and one
+            // correction step (S = p then gives c = 1 exactly, where A0 cannot afford the reciprocal's ulp)
+            const float p = __builtin_sqrtf(qx * fmaf(gl, ny2[r], bl));
+            const float rp = __builtin_amdgcn_rcpf(p);
+            float c = S[r] * rp;
+            c = fmaf(fmaf(-c, p, S[r]), rp, c);
+            c = fminf(fmaxf(c, -1.f), 1.f);  // (also c = NaN where p = 0)
+            const float sn = __builtin_sqrtf((1.f - c) * (1.f + c));
+            const float ac = acosf(-c);
+            const float br = fmaxf(fmaf(ac, c, sn), 0.f);
+            const float s1 = fmaf(gamma * p, br * inv_pi, coef0);
+            if (NTK) Tn[r] = p > 0.f ? fmaf(gamma * (ac * inv_pi), Tn[r], s1) : coef0;
+            S[r] = p > 0.f ? s1 : coef0;
+        }
+        bl = fmaf(gamma, bl, coef0);
+        gl *= gamma;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) kv[r] = NTK ? Tn[r] : S[r];
 }
 
 // Partial-tile store: element r (value v) of a wave's 32 x 32 accumulator, MFMA 32x32 layout, to rows row0.., column

@@ -2,6 +2,8 @@
 //     out[i][l] = scale * sum_j k(x_i, y_j) f[j][l],        i < B1, j < B2, l < L
 //     NSVD_DOT_POLYNOMIAL: k = (gamma x.y + coef0)^degree, integer degree 1..8, the power by multiplication
 //     NSVD_DOT_ARCCOS1:    k = |x||y| / pi (sin t + (pi - t) cos t), cos t = x.y / (|x||y|)   (Cho & Saul, order 1)
+//     NSVD_DOT_RELU_NNGP:  k = S_depth, NSVD_DOT_RELU_NTK: k = T_depth of a ReLU network `depth` layers deep (weight
+//                          variance gamma, bias variance coef0, depth in the degree slot): apply_relu_deep's recursion
 // - the sibling of rbf_apply.hip for kernels of the inner product. An inner product has no cancellation to protect
 // (rbf_apply.hip forms distances by direct differences on the VALU for that reason), so x.y goes on the matrix pipe: two
 // contractions back to back, like an attention forward. A workgroup owns 64 rows of x and 64 heads, walks its slice of
@@ -10,8 +12,8 @@
 //   1. forms S^T = Y_chunk X_tile^T (64 x 64 x Dp) on v_mfma_f32_32x32x2_f32: the y chunk is staged in LDS (two
 //      buffers, its global loads two chunks ahead in registers), the x operand of a wave (32 rows, this lane's half of
 //      every 8 coordinates) is loop invariant and lives in registers, loaded once per workgroup;
-//   2. applies the map (apply_poly, apply_arccos1) to the accumulators in registers. S^T, not S: a lane then owns ONE
-//      row i of x (one |x_i|, held in a register) and 4 runs of 4 consecutive reference rows j, which are 4
+//   2. applies the map (apply_poly, apply_arccos1, apply_relu_deep) to the accumulators in registers. S^T, not S: a lane
+//      then owns ONE row i of x (one |x_i|, held in a register) and 4 runs of 4 consecutive reference rows j, which are 4
 //      ds_write_b128 into the A operand of the second contraction - S would leave it 16 ds_write_b32;
 //   3. accumulates against the matching chunk of f^T exactly as rbf_apply.hip does (tile_nt.h's LDS layout and MFMA
 //      read pattern in apply_chunk_mfma, f^T one chunk ahead in registers, one apply_lds_barrier per chunk).
@@ -82,7 +84,7 @@ struct DotMap {
         if (t + 256 < nv) yb1 = yc_[256];                                                      \
         if (t + 512 < nv) yb2 = yc_[512];                                                      \
         if (t + 768 < nv) yb3 = yc_[768];                                                      \
-        if (KIND == NSVD_DOT_ARCCOS1 && t < KC) ynb = w.yN[(size_t)(cc) * KC + t];             \
+        if (KIND != NSVD_DOT_POLYNOMIAL && t < KC) ynb = w.yN[(size_t)(cc) * KC + t];          \
     }
 #define DOT_Y_PUT(b)                                                                           \
     {                                                                                          \
@@ -92,10 +94,11 @@ struct DotMap {
         if (t + 512 < nv) *(float4*)(yd_ + yo2) = yb2;                                         \
         if (t + 768 < nv) *(float4*)(yd_ + yo3) = yb3;                                         \
         if (KIND == NSVD_DOT_ARCCOS1 && t < KC) yd_[64 * yld + t] = __builtin_sqrtf(ynb);      \
+        if (apply_is_relu(KIND) && t < KC) yd_[64 * yld + t] = ynb;                            \
     }
 
 // tile (tb, tl) x slice. LDS: two buffers of [A chunk | B chunk] (NSVD_TNT_FLOATS), then two buffers of
-// [y chunk (64, Dp + 4) | |y_j| (64)].
+// [y chunk (64, Dp + 4) | |y_j| (64)] (the deep ReLU kinds: |y_j|^2).
 template <int KIND>
 __global__ void __launch_bounds__(256, 2) dot_main_kernel(const float* __restrict__ x, int B1, int B2, int D, DotWs w,
                                                           DotMap mp) {
@@ -116,6 +119,15 @@ __global__ void __launch_bounds__(256, 2) dot_main_kernel(const float* __restric
     DOT_X_LOAD(0) DOT_X_LOAD(1) DOT_X_LOAD(2) DOT_X_LOAD(3) DOT_X_LOAD(4) DOT_X_LOAD(5) DOT_X_LOAD(6) DOT_X_LOAD(7)
     nx2 += __shfl_xor(nx2, 32);  // the other half of every 8 coordinates
     const float nx = __builtin_sqrtf(nx2);
+    if (apply_is_relu(KIND)) {
+        // |x_i|^2 summed as the prep kernel sums |y_j|^2 (d ascending): equal rows give equal bits, and sqrt(q q) = q
+        nx2 = 0.f;
+        if (xrow < B1)
+            for (int d = 0; d < D; ++d) {
+                const float v = x[(size_t)xrow * D + d];
+                nx2 = fmaf(v, v, nx2);
+            }
+    }
     // LDS offsets of this thread's float4s of a y chunk
     const int Dq = Dp >> 2;
     const int yo0 = (t / Dq) * yld + (t % Dq) * 4, yo1 = ((t + 256) / Dq) * yld + ((t + 256) % Dq) * 4,
@@ -149,6 +161,14 @@ __global__ void __launch_bounds__(256, 2) dot_main_kernel(const float* __restric
             const nsvd_f32x16 pw = apply_poly(sv, mp.gamma, mp.coef0, mp.degree);
 #pragma unroll
             for (int r = 0; r < 16; ++r) kv[r] = pw[r];
+        } else if (apply_is_relu(KIND)) {
+            float ny2[16];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float4 ny = *(const float4*)(yb + 64 * yld + jb + 8 * g + kq);
+                ny2[4 * g] = ny.x, ny2[4 * g + 1] = ny.y, ny2[4 * g + 2] = ny.z, ny2[4 * g + 3] = ny.w;
+            }
+            apply_relu_deep<KIND == NSVD_DOT_RELU_NTK>(sv, nx2, ny2, mp.gamma, mp.coef0, mp.degree, kv);
         } else {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -160,7 +180,8 @@ __global__ void __launch_bounds__(256, 2) dot_main_kernel(const float* __restric
             }
         }
         if (c == chunks - 1) {
-            // padded reference rows: f^T is 0 there, but k (coef0^degree of a huge coef0) need not be finite
+            // padded reference rows: f^T is 0 there, but k (coef0^degree of a huge coef0) need not be finite (and the deep
+            // ReLU kinds give a padded zero row k = coef0-derived values: 0 * k is right only while k is finite)
             const int jg = c * KC + jb + kq;
 #pragma unroll
             for (int r = 0; r < 16; ++r)
@@ -212,8 +233,7 @@ extern "C" int nsvd_dot_apply(const float* x, int B1, const float* y, int B2, in
                               float gamma, float coef0, int degree, float scale, float* out, void* ws, size_t ws_bytes,
                               void* stream) {
     if (!apply_args_ok({x, y, f, out, ws}, B1, B2, D, L)) return NSVD_EINVAL;
-    if (kind != NSVD_DOT_POLYNOMIAL && kind != NSVD_DOT_ARCCOS1) return NSVD_EINVAL;
-    if (kind == NSVD_DOT_POLYNOMIAL && (degree < 1 || degree > 8 || !isfinite(gamma) || !isfinite(coef0))) return NSVD_EINVAL;
+    if (!apply_dot_kind_ok(kind, gamma, coef0, degree)) return NSVD_EINVAL;
     if (D > APPLY_MAX_D) return NSVD_EUNSUPPORTED;
     const DotWs w = carve(ws, B1, B2, D, L);
     if (!apply_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
@@ -224,7 +244,9 @@ extern "C" int nsvd_dot_apply(const float* x, int B1, const float* y, int B2, in
     apply_prep_launch(pr, s);
     NSVD_CHECK_LAUNCH();
     static const bool lds_limit_set = apply_set_lds_limit({(const void*)dot_main_kernel<NSVD_DOT_POLYNOMIAL>,
-                                                           (const void*)dot_main_kernel<NSVD_DOT_ARCCOS1>},
+                                                           (const void*)dot_main_kernel<NSVD_DOT_ARCCOS1>,
+                                                           (const void*)dot_main_kernel<NSVD_DOT_RELU_NNGP>,
+                                                           (const void*)dot_main_kernel<NSVD_DOT_RELU_NTK>},
                                                           dot_lds_bytes(APPLY_MAX_D));
     (void)lds_limit_set;
     const dim3 grid(w.B1p / T, w.Lp / T, w.S);
@@ -232,8 +254,12 @@ extern "C" int nsvd_dot_apply(const float* x, int B1, const float* y, int B2, in
     nsvd_prof_begin(s);
     if (kind == NSVD_DOT_POLYNOMIAL)
         dot_main_kernel<NSVD_DOT_POLYNOMIAL><<<grid, 256, dot_lds_bytes(w.Dp), s>>>(x, B1, B2, D, w, mp);
-    else
+    else if (kind == NSVD_DOT_ARCCOS1)
         dot_main_kernel<NSVD_DOT_ARCCOS1><<<grid, 256, dot_lds_bytes(w.Dp), s>>>(x, B1, B2, D, w, mp);
+    else if (kind == NSVD_DOT_RELU_NNGP)
+        dot_main_kernel<NSVD_DOT_RELU_NNGP><<<grid, 256, dot_lds_bytes(w.Dp), s>>>(x, B1, B2, D, w, mp);
+    else
+        dot_main_kernel<NSVD_DOT_RELU_NTK><<<grid, 256, dot_lds_bytes(w.Dp), s>>>(x, B1, B2, D, w, mp);
     nsvd_prof_end(s);
     NSVD_CHECK_LAUNCH();
     const size_t n = (size_t)B1 * L;

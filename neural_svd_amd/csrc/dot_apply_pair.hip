@@ -1,8 +1,8 @@
 // Two-sided matrix-free dot-product kernel operator on coordinate batches - both halves of a kernel SVD step in one pass:
 //     out_x[i][l] = scale_g * sum_j k(x_i, y_j) g[j][l]        (B1, L)   "K g"
 //     out_y[j][l] = scale_f * sum_i k(x_i, y_j) f[i][l]        (B2, L)   "K^T f"
-// with the kinds and numerical rules of dot_apply.hip (polynomial by multiplication, order-1 arc-cosine with its clamps:
-// apply_poly and apply_arccos1 of apply_common.h).
+// with the kinds and numerical rules of dot_apply.hip (polynomial by multiplication, order-1 arc-cosine with its clamps,
+// the deep ReLU NNGP and NTK recursions: apply_poly, apply_arccos1 and apply_relu_deep of apply_common.h).
 // Two nsvd_dot_apply calls with swapped arguments form every x_i . y_j twice on the matrix pipe and run the map twice;
 // here each kernel value is formed ONCE per 64-head tile and feeds both contractions.
 //
@@ -35,9 +35,9 @@ constexpr int DPAIR_TILE = T * LDT;   // one 64 x 64 LDS tile with padded rows
 
 struct DPairWs {
     float* xP;     // (B1p, Dp) x coordinates, zero padded
-    float* xN;     // (B1p) |x_i|, 0 for padded rows
+    float* xN;     // (B1p) |x_i| (the deep ReLU kinds: |x_i|^2), 0 for padded rows
     float* yP;     // (B2p, Dp) y coordinates, zero padded
-    float* yN;     // (B2p) |y_j|, 0 for padded rows
+    float* yN;     // (B2p) |y_j| (the deep ReLU kinds: |y_j|^2), 0 for padded rows
     float* gT;     // (Lp, B2p) g transposed, zero padded
     float* fT;     // (Lp, B1p) f transposed, zero padded
     float* partX;  // (CG, B1p, Lp) partial K g
@@ -105,7 +105,7 @@ __device__ __forceinline__ void dpair_load(const DPairLane& p, const float* __re
     b1 = *(const float4*)(s + dpair_opaque(p.bo1));
     b2 = *(const float4*)(s + dpair_opaque(p.bo2));
     b3 = *(const float4*)(s + dpair_opaque(p.bo3));
-    if (KIND == NSVD_DOT_ARCCOS1) nb = *(const float*)((const char*)nrm + dpair_opaque(p.bon));
+    if (KIND != NSVD_DOT_POLYNOMIAL) nb = *(const float*)((const char*)nrm + dpair_opaque(p.bon));
 }
 
 template <int KIND>
@@ -115,7 +115,7 @@ __device__ __forceinline__ void dpair_put(const DPairLane& p, float* __restrict_
     if (p.t + 256 < p.nv) *(float4*)(dst + p.so1) = b1;
     if (p.t + 512 < p.nv) *(float4*)(dst + p.so2) = b2;
     if (p.t + 768 < p.nv) *(float4*)(dst + p.so3) = b3;
-    if (KIND == NSVD_DOT_ARCCOS1 && p.t < 64) dst[64 * p.xld + p.t] = nb;
+    if (KIND != NSVD_DOT_POLYNOMIAL && p.t < 64) dst[64 * p.xld + p.t] = nb;
 }
 
 // One (x tile, chunk) step. ks: kernel chunk [x row][y row]; gs: g^T chunk [head][y row]; fs: f^T tile [head][x row];
@@ -159,6 +159,15 @@ __device__ __forceinline__ void dpair_step(const DPairLane& p, float* __restrict
         const nsvd_f32x16 pw = apply_poly(sv, mp.gamma, mp.coef0, mp.degree);
 #pragma unroll
         for (int r = 0; r < 16; ++r) kv[r] = pw[r];
+    } else if (apply_is_relu(KIND)) {
+        const float nx2 = xs[64 * p.xld + p.rb];  // (these kinds stage the SQUARED norms: the prep call's `rooted`)
+        float ny2[16];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 ny = *(const float4*)(ys + 64 * p.xld + jb + 8 * g + p.kq);
+            ny2[4 * g] = ny.x, ny2[4 * g + 1] = ny.y, ny2[4 * g + 2] = ny.z, ny2[4 * g + 3] = ny.w;
+        }
+        apply_relu_deep<KIND == NSVD_DOT_RELU_NTK>(sv, nx2, ny2, mp.gamma, mp.coef0, mp.degree, kv);
     } else {
         const float nx = xs[64 * p.xld + p.rb];
 #pragma unroll
@@ -172,6 +181,7 @@ __device__ __forceinline__ void dpair_step(const DPairLane& p, float* __restrict
     }
     if (xvalid < T || yvalid < KC) {
         // padded rows of EITHER side: f^T and g^T are 0 there, but k (coef0^degree of a huge coef0) need not be finite
+        // (the deep ReLU kinds: coef0-derived values there)
         const bool xpad = p.rb >= xvalid;
         // (rows left from this lane's first y row on, against constants: the 16 row numbers themselves are loop invariant,
         // and the compiler would carry them in 16 registers through the whole kernel)
@@ -375,8 +385,7 @@ extern "C" int nsvd_dot_apply_pair(const float* x, int B1, const float* y, int B
                                    int L, int kind, float gamma, float coef0, int degree, float scale_g, float scale_f,
                                    float* out_x, float* out_y, void* ws, size_t ws_bytes, void* stream) {
     if (!apply_args_ok({x, y, g, f, out_x, out_y, ws}, B1, B2, D, L)) return NSVD_EINVAL;
-    if (kind != NSVD_DOT_POLYNOMIAL && kind != NSVD_DOT_ARCCOS1) return NSVD_EINVAL;
-    if (kind == NSVD_DOT_POLYNOMIAL && (degree < 1 || degree > 8 || !isfinite(gamma) || !isfinite(coef0))) return NSVD_EINVAL;
+    if (!apply_dot_kind_ok(kind, gamma, coef0, degree)) return NSVD_EINVAL;
     const size_t nox = (size_t)B1 * L, noy = (size_t)B2 * L;
     if (apply_overlap(out_x, nox, out_y, noy)) return NSVD_EINVAL;
     for (float* o : {out_x, out_y}) {  // the outputs alias nothing
@@ -392,11 +401,13 @@ extern "C" int nsvd_dot_apply_pair(const float* x, int B1, const float* y, int B
     ApplyPrep pr = {};
     pr.s[0] = {y, w.yP, w.yN, g, w.gT, B2, w.B2p};
     pr.s[1] = {x, w.xP, w.xN, f, w.fT, B1, w.B1p};
-    pr.D = D, pr.Dp = w.Dp, pr.L = L, pr.Lp = w.Lp, pr.rooted = 1;
+    pr.D = D, pr.Dp = w.Dp, pr.L = L, pr.Lp = w.Lp, pr.rooted = apply_is_relu(kind) ? 0 : 1;  // (|.|; the deep ReLU kinds: |.|^2)
     apply_prep_launch(pr, s);
     NSVD_CHECK_LAUNCH();
     static const bool lds_limit_set = apply_set_lds_limit({(const void*)dot_pair_main_kernel<NSVD_DOT_POLYNOMIAL>,
-                                                           (const void*)dot_pair_main_kernel<NSVD_DOT_ARCCOS1>},
+                                                           (const void*)dot_pair_main_kernel<NSVD_DOT_ARCCOS1>,
+                                                           (const void*)dot_pair_main_kernel<NSVD_DOT_RELU_NNGP>,
+                                                           (const void*)dot_pair_main_kernel<NSVD_DOT_RELU_NTK>},
                                                           dpair_lds_bytes(APPLY_MAX_D));
     (void)lds_limit_set;
     const dim3 grid(w.RG, w.Lp / T, w.CG);
@@ -404,8 +415,12 @@ extern "C" int nsvd_dot_apply_pair(const float* x, int B1, const float* y, int B
     nsvd_prof_begin(s);
     if (kind == NSVD_DOT_POLYNOMIAL)
         dot_pair_main_kernel<NSVD_DOT_POLYNOMIAL><<<grid, 256, dpair_lds_bytes(w.Dp), s>>>(B1, B2, w, mp);
-    else
+    else if (kind == NSVD_DOT_ARCCOS1)
         dot_pair_main_kernel<NSVD_DOT_ARCCOS1><<<grid, 256, dpair_lds_bytes(w.Dp), s>>>(B1, B2, w, mp);
+    else if (kind == NSVD_DOT_RELU_NNGP)
+        dot_pair_main_kernel<NSVD_DOT_RELU_NNGP><<<grid, 256, dpair_lds_bytes(w.Dp), s>>>(B1, B2, w, mp);
+    else
+        dot_pair_main_kernel<NSVD_DOT_RELU_NTK><<<grid, 256, dpair_lds_bytes(w.Dp), s>>>(B1, B2, w, mp);
     nsvd_prof_end(s);
     NSVD_CHECK_LAUNCH();
     const size_t n = (size_t)(B1 + (size_t)B2) * L;

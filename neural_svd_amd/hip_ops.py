@@ -953,6 +953,7 @@ def rbf_apply_pair(x: torch.Tensor, y: torch.Tensor, g: torch.Tensor, f: torch.T
 
 
 DOT_POLYNOMIAL, DOT_ARCCOS1 = 0, 1  # NSVD_DOT_* (include/nsvd.h)
+DOT_RELU_NNGP, DOT_RELU_NTK = 3, 4   # (2 is unassigned)
 
 
 def dot_apply_workspace(B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
@@ -963,8 +964,11 @@ def dot_apply(x: torch.Tensor, y: torch.Tensor, f: torch.Tensor, kind: int, gamm
               scale: float, ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[i] = scale * sum_j k(x_i, y_j) f[j] without the (B1, B2) kernel matrix (nsvd_dot_apply). kind:
     DOT_POLYNOMIAL k = (gamma x.y + coef0)^degree (integer degree 1..8), DOT_ARCCOS1 k = |x||y| / pi (sin t +
-    (pi - t) cos t) with cos t = x.y / (|x||y|) (gamma, coef0, degree ignored). x: (B1, D), y: (B2, D), f: (B2, L)
-    contiguous float32 on the GPU; x may be y. Returns (B1, L)."""
+    (pi - t) cos t) with cos t = x.y / (|x||y|) (gamma, coef0, degree ignored), DOT_RELU_NNGP / DOT_RELU_NTK the NNGP
+    kernel S_depth / the neural tangent kernel T_depth of a ReLU network with weight variance gamma > 0, bias variance
+    coef0 >= 0 and depth 1..8 PASSED AS ``degree`` (the recursion: include/nsvd.h, kernel_ops.DotKernelOperator; the NTK
+    kind carries ~2e-4 per level where cos t = +-1 in float32: diagonals, near-parallel rows, D = 1).
+    x: (B1, D), y: (B2, D), f: (B2, L) contiguous float32 on the GPU; x may be y. Returns (B1, L)."""
     return _apply("dot_apply", x, y, f, kind, (gamma, coef0, degree), _DOT_PARAMS, scale, ws, out)
 
 
@@ -983,8 +987,9 @@ def dot_apply_pair(x: torch.Tensor, y: torch.Tensor, g: torch.Tensor, f: torch.T
                    out_x: Optional[torch.Tensor] = None, out_y: Optional[torch.Tensor] = None):
     """Both halves of a kernel SVD step in one pass (nsvd_dot_apply_pair), every x_i . y_j formed and mapped once:
     out_x[i] = scale_g * sum_j k(x_i, y_j) g[j] ("K g", (B1, L)) and out_y[j] = scale_f * sum_i k(x_i, y_j) f[i]
-    ("K^T f", (B2, L)). kind, gamma, coef0, degree as dot_apply. x: (B1, D), y: (B2, D), g: (B2, L), f: (B1, L)
-    contiguous float32 on the GPU; x may be y and f may be g. Returns (out_x, out_y)."""
+    ("K^T f", (B2, L)). kind, gamma, coef0, degree as dot_apply (the deep ReLU kinds: depth as ``degree``).
+    x: (B1, D), y: (B2, D), g: (B2, L), f: (B1, L) contiguous float32 on the GPU; x may be y and f may be g.
+    Returns (out_x, out_y)."""
     return _apply_pair("dot_apply_pair", x, y, g, f, kind, (gamma, coef0, degree), _DOT_PARAMS, scale_g, scale_f, ws,
                        out_x, out_y)
 

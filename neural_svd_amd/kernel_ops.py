@@ -217,6 +217,27 @@ class RadialKernelOperator(MatrixFreeKernelOperator):
         return H.rbf_apply_pair(x, y, g, f, self.kind, self.ell, scale_g, scale_f, ws=ws, out_x=out_x, out_y=out_y)
 
 
+def _is_relu_kind(kind) -> bool:
+    return kind in (H.DOT_RELU_NNGP, H.DOT_RELU_NTK)
+
+
+def relu_kernel_diagonal(kind: int, r2, gamma: float, coef0: float, depth: int) -> np.ndarray:
+    """k(x, x) of the deep ReLU kinds in closed form from r2 = |x|^2, float64 numpy: q_0 = r2,
+    q_l = gamma q_{l-1} + coef0; H.DOT_RELU_NNGP: q_depth, H.DOT_RELU_NTK: sum over l = 0 .. depth of
+    gamma^(depth - l) q_l (T_l(x, x) = q_l + gamma T_{l-1}(x, x): A1(1) = A0(1) = 1). A zero row needs no case of its
+    own: where the kernel takes both A terms as 0, T_{l-1} is 0 as well."""
+    if not _is_relu_kind(kind):
+        raise ValueError("relu_kernel_diagonal: kind must be H.DOT_RELU_NNGP or H.DOT_RELU_NTK")
+    if int(depth) != depth or not 1 <= int(depth) <= 8:
+        raise ValueError("relu_kernel_diagonal: depth must be an integer in 1..8")
+    q = np.asarray(r2, dtype=np.float64).copy()
+    t = q.copy()
+    for _ in range(int(depth)):
+        q = float(gamma) * q + float(coef0)
+        t = q + float(gamma) * t
+    return q if kind == H.DOT_RELU_NNGP else t
+
+
 class DotKernelOperator(MatrixFreeKernelOperator):
     """A kernel of the inner product on `dim`-dimensional coordinates (nsvd_dot_apply: x.y on the fp32 MFMA, the
     (B, B2) matrix never stored): kind H.DOT_POLYNOMIAL k = (gamma x.y + coef0)^degree with an integer degree in 1..8, or
@@ -225,30 +246,59 @@ class DotKernelOperator(MatrixFreeKernelOperator):
     the same contract and callers as RadialKernelOperator. Polynomial kind: gamma <= 0 or coef0 < 0 are refused (not PSD
     in general).
     A polynomial kernel has FINITE rank C(dim + degree, degree) (see nystrom.Nystrom's note on ``oversample``).
-    The two-sided product of a kernel SVD step is one nsvd_dot_apply_pair call (``apply_pair_raw``)."""
+    The two-sided product of a kernel SVD step is one nsvd_dot_apply_pair call (``apply_pair_raw``).
+
+    H.DOT_RELU_NNGP and H.DOT_RELU_NTK are the NNGP kernel and the neural tangent kernel of a ReLU network ``depth``
+    layers deep (an integer in 1..8, ``op.depth``; ``degree`` is ignored) with weight variance gamma > 0 and bias
+    variance coef0 >= 0. With A1(c) = (sin t + (pi - t) cos t) / pi and A0(c) = (pi - t) / pi, cos t = c clamped to
+    [-1, 1] (Cho & Saul's orders 1 and 0; A1 = 2 E[relu u relu v], A0 = 2 E[1{u>0} 1{v>0}] for unit Gaussians of
+    correlation c), S_0 = T_0 = x.y, q_0(x) = |x|^2, and for l = 1 .. depth
+
+        p = sqrt(q_{l-1}(x) q_{l-1}(y)),   c = S_{l-1} / p,   S_l = gamma p A1(c) + coef0,
+        T_l = S_l + gamma T_{l-1} A0(c),   q_l(x) = gamma q_{l-1}(x) + coef0   (= S_l(x, x)),
+
+    the NNGP kind is k = S_depth and the NTK kind k = T_depth (diagonals: ``relu_kernel_diagonal``). Two conventions:
+    S_0 is x.y itself (no variance on the input layer), and where p = 0 - a zero row at level 1, at every level when
+    coef0 = 0 - both A terms are taken as 0, so S_l = T_l = coef0. gamma = 1, coef0 = 0, depth = 1 makes the NNGP kind
+    H.DOT_ARCCOS1. Both are positive semi-definite. The NTK kind inherits A0's unbounded slope at c = +-1: float32
+    leaves about 2e-4 per level on the diagonal of a Gram, on near-parallel rows and on every pair at dim = 1
+    (include/nsvd.h); the NNGP kind is as well conditioned as H.DOT_ARCCOS1."""
 
     def __init__(self, kind: int, dim: int, *, gamma: float = 1.0, coef0: float = 1.0, degree: int = 2,
-                 sigma: float = 1.0, device="cuda:0"):
-        if kind not in (H.DOT_POLYNOMIAL, H.DOT_ARCCOS1):
-            raise ValueError("DotKernelOperator: kind must be H.DOT_POLYNOMIAL or H.DOT_ARCCOS1")
+                 depth: int = 1, sigma: float = 1.0, device="cuda:0"):
+        if kind not in (H.DOT_POLYNOMIAL, H.DOT_ARCCOS1, H.DOT_RELU_NNGP, H.DOT_RELU_NTK):
+            raise ValueError("DotKernelOperator: kind must be H.DOT_POLYNOMIAL, H.DOT_ARCCOS1, H.DOT_RELU_NNGP or "
+                             "H.DOT_RELU_NTK")
         if kind == H.DOT_POLYNOMIAL:  # (the arc-cosine kind ignores the three, as the C entry point does)
             if not (gamma > 0 and math.isfinite(gamma)) or not (coef0 >= 0 and math.isfinite(coef0)):
                 raise ValueError("DotKernelOperator: gamma must be positive and coef0 non-negative (and finite): "
                                  "the kernel is not positive semi-definite otherwise")
             if int(degree) != degree or not 1 <= int(degree) <= 8:
                 raise ValueError("DotKernelOperator: degree must be an integer in 1..8")
+            depth = 1
+        elif _is_relu_kind(kind):
+            if not (gamma > 0 and math.isfinite(gamma)) or not (coef0 >= 0 and math.isfinite(coef0)):
+                raise ValueError("DotKernelOperator: gamma (the weight variance) must be positive and coef0 (the bias "
+                                 "variance) non-negative, both finite")
+            if not isinstance(depth, (int, float, np.integer, np.floating)) or not math.isfinite(depth) or \
+                    int(depth) != depth or not 1 <= int(depth) <= 8:
+                raise ValueError("DotKernelOperator: depth must be an integer in 1..8")
+            degree = 2
         else:
-            gamma, coef0, degree = 1.0, 1.0, 2
+            gamma, coef0, degree, depth = 1.0, 1.0, 2, 1
         if not sigma > 0:
             raise ValueError("DotKernelOperator: sigma must be positive")
         self.kind, self.gamma, self.coef0, self.degree = int(kind), float(gamma), float(coef0), int(degree)
+        self.depth = int(depth)
+        # what the entry points take in their degree slot: the deep ReLU kinds read their depth there
+        self._slot = self.depth if _is_relu_kind(self.kind) else self.degree
         self._init_common(dim, sigma, device, "nsvd_dot_apply")
 
     def workspace(self, B1: int, B2: int, L: int, device=None) -> torch.Tensor:
         return H.dot_apply_workspace(B1, B2, self.dim, L, self.device if device is None else device)
 
     def apply_raw(self, x, y, f, scale, ws=None, out=None) -> torch.Tensor:
-        return H.dot_apply(x, y, f, self.kind, self.gamma, self.coef0, self.degree, scale, ws=ws, out=out)
+        return H.dot_apply(x, y, f, self.kind, self.gamma, self.coef0, self._slot, scale, ws=ws, out=out)
 
     def workspace_pair(self, B1: int, B2: int, L: int, device=None) -> torch.Tensor:
         """nsvd_dot_apply_pair_workspace_bytes. With B1p, B2p, Lp = B1, B2, L rounded up to 64, Dp = dim rounded up to 8
@@ -261,7 +311,7 @@ class DotKernelOperator(MatrixFreeKernelOperator):
     def apply_pair_raw(self, x, y, g, f, scale_g, scale_f, ws=None, out_x=None, out_y=None):
         """one nsvd_dot_apply_pair call at every dim and kind: every x_i . y_j formed and mapped once for both products
         (the two-call route stays reachable as MatrixFreeKernelOperator.apply_pair_raw(op, ...))"""
-        return H.dot_apply_pair(x, y, g, f, self.kind, self.gamma, self.coef0, self.degree, scale_g, scale_f, ws=ws,
+        return H.dot_apply_pair(x, y, g, f, self.kind, self.gamma, self.coef0, self._slot, scale_g, scale_f, ws=ws,
                                 out_x=out_x, out_y=out_y)
 
 

@@ -5,6 +5,7 @@
     python scripts/train_kernel_svd.py --kind polynomial --dim 3 --degree 2 --L 10 [--gamma 1 --coef0 1]
     python scripts/train_kernel_svd.py --kind arccos1 --dim 3
     python scripts/train_kernel_svd.py --kind exponential --baseline 8192
+    python scripts/train_kernel_svd.py --kind relu_nngp --depth 3 --gamma 2 --coef0 0.1 --dim 3 --baseline 8192
 
 --baseline N: draw N points a side from the two measures, run the matrix-free truncated SVD of their cross Gram
 (neural_svd_amd.NystromSVD: the singular values of k(xs, ys) / N) and print its singular values as a comparison column -
@@ -13,7 +14,9 @@ error of the learned quotients against it; the record gains baseline_n, baseline
 baseline_seconds, rel_err_vs_baseline. Without the flag the output and the record are as before.
 
 --kind gaussian (the default, described below) | exponential (--ell) | polynomial (--gamma --coef0 --degree:
-k = (gamma x.y + coef0)^degree) | arccos1 (the order-1 arc-cosine kernel). The radial kinds run on nsvd_rbf_apply_pair,
+k = (gamma x.y + coef0)^degree) | arccos1 (the order-1 arc-cosine kernel) | relu_nngp, relu_ntk (the NNGP kernel and the
+neural tangent kernel of a ReLU network --depth layers deep, weight variance --gamma, bias variance --coef0; --baseline
+is their comparison column). The radial kinds run on nsvd_rbf_apply_pair,
 the dot-product kinds on nsvd_dot_apply_pair; the two-call comparison trainer uses two nsvd_rbf_apply / nsvd_dot_apply
 calls. The truth column comes from a closed form where one exists - gaussian: gaussian_cross_singular_values,
 polynomial: polynomial_cross_singular_values (finite rank: zeros beyond it, where the relative error is not defined) -
@@ -76,11 +79,12 @@ def main():
     ap.add_argument("--dim", type=int, default=2)
     ap.add_argument("--sigma-x", type=float, default=1.0)
     ap.add_argument("--sigma-y", type=float, default=0.5)
-    ap.add_argument("--kind", default="gaussian", choices=("gaussian", "exponential", "polynomial", "arccos1"))
+    ap.add_argument("--kind", default="gaussian", choices=("gaussian", "exponential", "polynomial", "arccos1", "relu_nngp", "relu_ntk"))
     ap.add_argument("--ell", type=float, default=1.5, help="radial kinds: the length scale")
-    ap.add_argument("--gamma", type=float, default=1.0, help="polynomial kind")
-    ap.add_argument("--coef0", type=float, default=1.0, help="polynomial kind")
+    ap.add_argument("--gamma", type=float, default=1.0, help="polynomial kind; relu kinds: the weight variance")
+    ap.add_argument("--coef0", type=float, default=1.0, help="polynomial kind; relu kinds: the bias variance")
     ap.add_argument("--degree", type=int, default=2, help="polynomial kind")
+    ap.add_argument("--depth", type=int, default=1, help="relu kinds: the number of layers, 1..8")
     ap.add_argument("--L", type=int, default=10)
     ap.add_argument("--B", type=int, default=8192)
     ap.add_argument("--m", type=int, default=64)
@@ -104,8 +108,10 @@ def main():
     def make_op(op_class):
         if radial:
             return op_class(H.RBF_GAUSSIAN if a.kind == "gaussian" else H.RBF_EXPONENTIAL, a.ell, a.dim, a.sigma_x, dev)
-        return op_class(H.DOT_POLYNOMIAL if a.kind == "polynomial" else H.DOT_ARCCOS1, a.dim, gamma=a.gamma,
-                        coef0=a.coef0, degree=a.degree, sigma=a.sigma_x, device=dev)
+        hkind = dict(polynomial=H.DOT_POLYNOMIAL, arccos1=H.DOT_ARCCOS1, relu_nngp=H.DOT_RELU_NNGP,
+                     relu_ntk=H.DOT_RELU_NTK)[a.kind]
+        return op_class(hkind, a.dim, gamma=a.gamma, coef0=a.coef0, degree=a.degree, depth=a.depth, sigma=a.sigma_x,
+                        device=dev)
 
     def trainer(op_class, steps):
         op = make_op(op_class)
@@ -137,6 +143,8 @@ def main():
         rec.update(ell=a.ell)
     elif a.kind == "polynomial":
         rec.update(gamma=a.gamma, coef0=a.coef0, degree=a.degree)
+    elif a.kind in ("relu_nngp", "relu_ntk"):
+        rec.update(gamma=a.gamma, coef0=a.coef0, depth=a.depth)
     names = ("nsvd_rbf_apply", "nsvd_rbf_apply_pair") if radial else ("nsvd_dot_apply", "nsvd_dot_apply_pair")
     print(f"steps/s {rec['steps_per_s']} (two {names[0]} calls in place of {names[1]}: "
           f"{rec['two_call_base_path_steps_per_s']})")

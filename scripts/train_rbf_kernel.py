@@ -8,9 +8,13 @@ compared with the closed-form Mercer eigenvalues (gaussian_kernel_eigvals).
     python scripts/train_rbf_kernel.py --kind exponential --ell 2 --nystrom 8192
     python scripts/train_rbf_kernel.py --kind arccos1 --dim 3 --nystrom 8192
     python scripts/train_rbf_kernel.py --kind polynomial --gamma 0.5 --coef0 1 --degree 3 --dim 3 --nystrom 8192
+    python scripts/train_rbf_kernel.py --kind relu_ntk --depth 3 --gamma 2 --coef0 0.1 --dim 3 --nystrom 8192
 
 --kind polynomial / arccos1 train on a DotKernelOperator instead (k = (gamma x.y + coef0)^degree, or Cho & Saul's order-1
 arc-cosine kernel; --ell unused) and write profiles/dot_kernel_train.json by default.
+--kind relu_nngp / relu_ntk train on the NNGP kernel / the neural tangent kernel of a ReLU network --depth layers deep
+(1..8) with weight variance --gamma and bias variance --coef0 (DotKernelOperator's recursion) and write
+profiles/relu_kernel_train_<kind>.json by default; --nystrom is their comparison column.
 --spin adds a SpIN column (neural_svd_amd.spin.SpinKernelTrainer: the same model, batch size and step count trained with
 SpIN's loss; --spin-decay is its moving-average rate) with its own steps/s.
 --spinx adds a SpINx column (neural_svd_amd.spinx.SpinxKernelTrainer, the same way; --spinx-decay its moving-average
@@ -56,10 +60,12 @@ def main():
     ap.add_argument("--fourier-scale", type=float, default=0.3)
     ap.add_argument("--n-eval", type=int, default=16384)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--kind", choices=("gaussian", "exponential", "polynomial", "arccos1"), default="gaussian")
-    ap.add_argument("--gamma", type=float, default=1.0, help="polynomial kind: k = (gamma x.y + coef0)^degree")
-    ap.add_argument("--coef0", type=float, default=1.0)
+    ap.add_argument("--kind", choices=("gaussian", "exponential", "polynomial", "arccos1", "relu_nngp", "relu_ntk"),
+                    default="gaussian")
+    ap.add_argument("--gamma", type=float, default=1.0, help="polynomial kind: k = (gamma x.y + coef0)^degree; relu kinds: the weight variance")
+    ap.add_argument("--coef0", type=float, default=1.0, help="relu kinds: the bias variance")
     ap.add_argument("--degree", type=int, default=2)
+    ap.add_argument("--depth", type=int, default=1, help="relu kinds: the number of layers, 1..8")
     ap.add_argument("--nystrom", type=int, default=0, metavar="N",
                     help="also print the Nystrom eigenvalues of an N-point sample (0: off)")
     ap.add_argument("--spin", action="store_true", help="also train SpIN on the same operator and print its column")
@@ -77,9 +83,11 @@ def main():
     ap.add_argument("--out", default=None,
                     help="default: profiles/rbf_kernel_train.json (radial kinds) or profiles/dot_kernel_train.json")
     a = ap.parse_args()
-    dot = a.kind in ("polynomial", "arccos1")
+    relu = a.kind in ("relu_nngp", "relu_ntk")
+    dot = relu or a.kind in ("polynomial", "arccos1")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "dot_kernel_train.json" if dot else "rbf_kernel_train.json")
+        a.out = os.path.join(ROOT, "profiles", f"relu_kernel_train_{a.kind}.json" if relu else
+                             "dot_kernel_train.json" if dot else "rbf_kernel_train.json")
     if not torch.cuda.is_available():
         raise SystemExit("train_rbf_kernel.py needs a GPU (neural_svd_amd has no CPU path)")
     dev = "cuda:0"
@@ -94,8 +102,10 @@ def main():
                              (f"L + 8 = {need} (the Nystrom basis, see Nystrom's note on oversample)" if a.nystrom
                               else f"L = {need}") + ": raise --dim or --degree, or lower --L")
     if dot:
-        op = DotKernelOperator(H.DOT_POLYNOMIAL if a.kind == "polynomial" else H.DOT_ARCCOS1, a.dim, gamma=a.gamma,
-                               coef0=a.coef0, degree=a.degree, sigma=a.sigma, device=dev)
+        hkind = dict(polynomial=H.DOT_POLYNOMIAL, arccos1=H.DOT_ARCCOS1, relu_nngp=H.DOT_RELU_NNGP,
+                     relu_ntk=H.DOT_RELU_NTK)[a.kind]
+        op = DotKernelOperator(hkind, a.dim, gamma=a.gamma, coef0=a.coef0, degree=a.degree, depth=a.depth, sigma=a.sigma,
+                               device=dev)
     else:
         op = RadialKernelOperator(H.RBF_GAUSSIAN if gaussian else H.RBF_EXPONENTIAL, a.ell, a.dim, a.sigma, dev)
     fk = FusedKernelTrainer(op, L=a.L, m=a.m, hidden=(128, 128), batch_size=a.B, sequential=True, lr=a.lr,
@@ -119,7 +129,8 @@ def main():
         return H.model_forward(fk.shape, fk._params, xe.contiguous(), fk.c, ws)
 
     got = kernel_spectrum(op, learned, x_eval, chunk)
-    params = dict(gamma=a.gamma, coef0=a.coef0, degree=a.degree) if a.kind == "polynomial" else {} if dot else dict(ell=a.ell)
+    params = dict(gamma=a.gamma, coef0=a.coef0, degree=a.degree) if a.kind == "polynomial" else \
+        dict(gamma=a.gamma, coef0=a.coef0, depth=a.depth) if relu else {} if dot else dict(ell=a.ell)
     rec = dict(kind=a.kind, dim=a.dim, sigma=a.sigma, **params, L=a.L, B=a.B, steps=a.steps, lr=a.lr,
                fourier_scale=a.fourier_scale, seconds=round(dt, 2), steps_per_s=round((a.steps - 10) / dt, 1),
                loss=[float(v) for v in loss.cpu()], rayleigh_learned=[float(v) for v in got["eigvals"]],
