@@ -835,7 +835,8 @@ int nsvd_ts_rotate2(const float* X, long ldx, const float* Y, long ldy, int n, i
  *   rs_joint (B) = diag(f~ g~^T), rs_indep (B (B-1)) = off_diagonal(f~ g~^T) (methods/utils.py:16-22); either
  *   may be NULL (both NULL skips the (B, B) gram contraction).
  * v: (Lp), M: (Lp, Lp) nesting masks (methods/nestedlora.py:345-359), float32 on the device.
- * ws: nsvd_cdk_workspace_bytes(B, L, set_first_mode_const) bytes; keeps f~, g~ and M * lam for the backward.
+ * ws: nsvd_cdk_workspace_bytes(B, L, set_first_mode_const) bytes, 256-byte aligned (NSVD_EINVAL otherwise, in the forward
+ * and in the backward); keeps f~, g~ and M * lam for the backward.
  * Arithmetic is float32 on the fp32-input MFMA, independent of any autocast state of the caller. */
 size_t nsvd_cdk_workspace_bytes(int B, int L, int set_first_mode_const);
 int nsvd_cdk_loss_forward(const float* f, const float* g, const float* batch_weights, const float* v,

@@ -1,5 +1,5 @@
 // What the matrix-free kernel products share (rbf_apply.hip, dot_apply.hip, rbf_apply_pair.hip, dot_apply_pair.hip;
-// the arena, the slice rule and the tile store also serve kernel_apply.hip): the padding rule and the workspace arena,
+// the slice rule and the tile store also serve kernel_apply.hip): the padding rule,
 // the prep kernel (pad coordinates, row norms, transposes), the reduce kernels, the maps of the kernel kinds and the
 // pieces of tile_nt.h's layout that every main kernel repeats. Everything has internal linkage: each file gets its own.
 #pragma once
@@ -22,18 +22,6 @@ static inline ApplyPad apply_pad(int B1, int B2, int D, int L, int granule) {
             nsvd_cdiv(D, granule) * granule, nsvd_cdiv(L, NSVD_TNT_T) * NSVD_TNT_T};
 }
 
-// blocks of floats carved from a workspace one after the other, each starting on nsvd_align's boundary
-struct ApplyArena {
-    char* base;
-    size_t off = 0;
-    explicit ApplyArena(void* p) : base((char*)p) {}
-    float* take(size_t n) {
-        float* r = (float*)(base + off);
-        off += nsvd_align(n * sizeof(float));
-        return r;
-    }
-};
-
 // slices of the contraction range of a one-sided product: enough workgroups for two per CU, at least 8 chunks per slice
 static inline int apply_slices(long tiles, int chunks) {
     int S = 1;
@@ -47,10 +35,6 @@ static inline bool apply_args_ok(std::initializer_list<const void*> ptrs, int B1
     for (const void* p : ptrs)
         if (!p) return false;
     return apply_shape_ok(B1, B2, D, L);
-}
-
-static inline bool apply_ws_ok(const void* ws, size_t ws_bytes, size_t need) {
-    return ws_bytes >= need && ((uintptr_t)ws & 255) == 0;
 }
 
 // do the float arrays at a (na elements) and b (nb elements) share a byte?
@@ -91,12 +75,6 @@ static inline bool apply_dot_kind_ok(int kind, float gamma, float coef0, int deg
     if (apply_is_relu(kind))
         return degree >= 1 && degree <= 8 && isfinite(gamma) && gamma > 0.f && isfinite(coef0) && coef0 >= 0.f;
     return kind == NSVD_DOT_ARCCOS1;
-}
-
-// raise the dynamic-LDS limit of a file's main-kernel instances; true, to initialise the static that makes it happen once
-static inline bool apply_set_lds_limit(std::initializer_list<const void*> kernels, size_t bytes) {
-    for (const void* k : kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return true;
 }
 
 // ---- prep ------------------------------------------------------------------------------------------------------------

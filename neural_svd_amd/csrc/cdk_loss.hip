@@ -63,16 +63,14 @@ __host__ CdkWs carve(void* base, int B, int L, int first) {
     w.nmain = (w.R / TS) * (w.R / TS);
     w.nfin = w.nmain + (w.first ? nsvd_cdiv(w.LD, 256) : 0);
     w.nsplit = nsvd_cdiv(w.Bp / KC, SPLIT_CHUNKS);
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t n) { float* r = (float*)(p + off); off += nsvd_align(n * sizeof(float)); return r; };
+    NsvdArena a(base);
     const size_t feat = (size_t)w.Bp * w.LD, sq = (size_t)w.LD * w.LD;
-    w.ft = take(feat); w.gt = take(feat); w.fT = take(feat); w.gT = take(feat);
-    w.lam_f = take(sq * w.nsplit); w.lam_g = take(sq * w.nsplit);
-    w.lam0_f = take((size_t)NB0 * w.LD); w.lam0_g = take((size_t)NB0 * w.LD);
-    w.MlfT = take(sq); w.MlgT = take(sq);
-    w.part_op = take(w.nstage); w.part_met = take(w.nfin);
-    w.bytes = off;
+    w.ft = a.take(feat); w.gt = a.take(feat); w.fT = a.take(feat); w.gT = a.take(feat);
+    w.lam_f = a.take(sq * w.nsplit); w.lam_g = a.take(sq * w.nsplit);
+    w.lam0_f = a.take((size_t)NB0 * w.LD); w.lam0_g = a.take((size_t)NB0 * w.LD);
+    w.MlfT = a.take(sq); w.MlgT = a.take(sq);
+    w.part_op = a.take(w.nstage); w.part_met = a.take(w.nfin);
+    w.bytes = a.off;
     return w;
 }
 
@@ -359,17 +357,13 @@ __global__ void __launch_bounds__(256) cdk_backward_gemm_kernel(CdkWs w, const f
     }
 }
 
-// double-buffered 64-wide chunks: 68 KB, above the 64 KB default -> opt in once per process
-size_t gemm_lds_bytes() {
-    static const size_t bytes = [] {
-        const size_t b = TILE_FLOATS * sizeof(float);
-        (void)hipFuncSetAttribute((const void*)cdk_forward_gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)b);
-        (void)hipFuncSetAttribute((const void*)cdk_backward_gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)b);
-        return b;
-    }();
-    return bytes;
+// double-buffered 64-wide chunks: 68 KB, above the 64 KB default -> opt in (both kernels, once per device)
+constexpr size_t GEMM_LDS_BYTES = TILE_FLOATS * sizeof(float);
+static_assert(GEMM_LDS_BYTES <= NSVD_LDS_MAX, "LDS of gfx950");
+int gemm_lds_opt_in() {
+    static NsvdLdsOptIn st;
+    return nsvd_lds_opt_in(st, {(const void*)cdk_forward_gemm_kernel, (const void*)cdk_backward_gemm_kernel},
+                           GEMM_LDS_BYTES);
 }
 
 }  // namespace
@@ -386,15 +380,16 @@ int nsvd_cdk_loss_forward_parts(const float* f, const float* g, const float* bat
     if (!f || !g || !v || !M || !ws || !parts || B <= 0 || L <= 0) return NSVD_EINVAL;
     if (rs_indep && B < 2) return NSVD_EINVAL;
     const CdkWs w = carve(ws, B, L, set_first_mode_const);
-    if (ws_bytes < w.bytes) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
+    if (const int rc = gemm_lds_opt_in()) return rc;
     const int nr = w.R / T, nb = w.Bp / T;
     cdk_stage_kernel<<<dim3(w.Bp / TS, w.LD / TS), 256, 0, s>>>(f, g, batch_weights, v, B, L, w);
     NSVD_CHECK_LAUNCH();
     const int nbord = w.first ? NB0 * (w.LD / T) : 0;
     const int ngram = (rs_joint || rs_indep) ? nb * nb : 0;
     const int nlam = 2 * (nr * (nr + 1) / 2) * w.nsplit;
-    cdk_forward_gemm_kernel<<<nbord + ngram + nlam, 256, gemm_lds_bytes(), s>>>(w, B, nbord, ngram, rs_joint,
-                                                                                 rs_indep);
+    cdk_forward_gemm_kernel<<<nbord + ngram + nlam, 256, GEMM_LDS_BYTES, s>>>(w, B, nbord, ngram, rs_joint,
+                                                                              rs_indep);
     NSVD_CHECK_LAUNCH();
     cdk_finish_kernel<<<w.nfin, 256, 0, s>>>(w, M, B);
     NSVD_CHECK_LAUNCH();
@@ -421,9 +416,10 @@ extern "C" int nsvd_cdk_loss_backward(const float* v, int B, int L, int set_firs
                                       float* grad_f, float* grad_g, void* ws, size_t ws_bytes, void* stream) {
     if (!v || !ws || B <= 0 || L <= 0 || (!grad_f && !grad_g)) return NSVD_EINVAL;
     const CdkWs w = carve(ws, B, L, set_first_mode_const);
-    if (ws_bytes < w.bytes) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
+    if (const int rc = gemm_lds_opt_in()) return rc;
     const int both = grad_f && grad_g;
-    cdk_backward_gemm_kernel<<<dim3(w.Bp / T, w.R / T, both ? 2 : 1), 256, gemm_lds_bytes(), (hipStream_t)stream>>>(
+    cdk_backward_gemm_kernel<<<dim3(w.Bp / T, w.R / T, both ? 2 : 1), 256, GEMM_LDS_BYTES, (hipStream_t)stream>>>(
         w, v, B, L, grad_out, grad_f, grad_g, both ? -1 : (grad_g ? 1 : 0));
     NSVD_CHECK_LAUNCH();
     return 0;

@@ -183,23 +183,17 @@ struct StepWs {
 StepWs carve_step(const nsvd_cdk_step_desc& d, void* base) {
     StepWs w;
     memset(&w, 0, sizeof(w));
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* q = p + off;
-        off += nsvd_align(bytes);
-        return q;
-    };
+    NsvdArena a(base);
     w.tower_bytes = nsvd_tower_workspace_bytes(d.B, d.d0, d.d1, d.d2);
     w.cdk_bytes = nsvd_cdk_workspace_bytes(d.B, d.d2, d.set_first_mode_const);
-    for (int s = 0; s < 2; ++s) w.tower[s] = take(w.tower_bytes);
-    w.cdk = take(w.cdk_bytes);
-    const size_t bl = (size_t)d.B * d.d2 * sizeof(float);
+    for (int s = 0; s < 2; ++s) w.tower[s] = a.take_bytes(w.tower_bytes);
+    w.cdk = a.take_bytes(w.cdk_bytes);
+    const size_t bl = (size_t)d.B * d.d2;
     for (int s = 0; s < 2; ++s) {
-        w.z[s] = (float*)take(bl);
-        w.e[s] = (float*)take(bl);
-        w.ge[s] = (float*)take(bl);
-        w.dz[s] = (float*)take(bl);
+        w.z[s] = a.take(bl);
+        w.e[s] = a.take(bl);
+        w.ge[s] = a.take(bl);
+        w.dz[s] = a.take(bl);
     }
     const size_t n[NT] = {(size_t)d.d1 * d.d0, (size_t)d.d1, (size_t)d.d1, (size_t)d.d1,
                           (size_t)d.d2 * d.d1, (size_t)d.d2, (size_t)d.d2, (size_t)d.d2};
@@ -209,15 +203,15 @@ StepWs carve_step(const nsvd_cdk_step_desc& d, void* base) {
         w.gn[k] = n[k];
         g += (n[k] + 63) / 64 * 64;
     }
-    for (int s = 0; s < 2; ++s) w.grad[s] = (float*)take(g * sizeof(float));
+    for (int s = 0; s < 2; ++s) w.grad[s] = a.take(g);
     // mixed precision with the fused narrow end: the small tensors' squares come from the kernels that write those
     // gradients (one float per strip of columns: d1 / 64 + nsvd_narrow_sumsq_count(d2) per tower)
     w.nsmall = (d.gemm_bf16 != 0 && nsvd_narrow_supported(2, d.B, d.d2)) ? (d.d1 / 64 + nsvd_narrow_sumsq_count(d.d2)) : 0;
     w.npartial = SUMSQ_BLOCKS + 2 * (nsvd_tower_sumsq_count(d.d0, d.d1, d.d2, d.gemm_bf16 != 0) + w.nsmall);
-    w.partial = (float*)take((size_t)w.npartial * sizeof(float));
-    w.scal = (float*)take(256);
-    w.narrow = (float*)take(nsvd_narrow_scratch_floats(2, d.B, d.d2) * sizeof(float));
-    w.bytes = off;
+    w.partial = a.take((size_t)w.npartial);
+    w.scal = a.take(64);
+    w.narrow = a.take(nsvd_narrow_scratch_floats(2, d.B, d.d2));
+    w.bytes = a.off;
     return w;
 }
 
@@ -261,9 +255,8 @@ extern "C" int nsvd_cdk_step(const nsvd_cdk_step_desc* d, const float* x, const 
                              const float* M, float* loss, float* rs_joint, float* rs_indep, void* ws,
                              size_t ws_bytes, void* stream) {
     if (!desc_ok(d) || !x || !y || !towers || !momentum_bufs || !v || !M || !loss || !ws) return NSVD_EINVAL;
-    if (((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
     const StepWs w = carve_step(*d, ws);
-    if (ws_bytes < w.bytes) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int B = d->B, L = d->d2;
     const float r_up = sqrtf(d->mu);

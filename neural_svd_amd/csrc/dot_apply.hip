@@ -39,7 +39,7 @@ DotWs carve(void* base, int B1, int B2, int D, int L) {
     DotWs w;
     w.B1p = pd.B1p, w.B2p = pd.B2p, w.Dp = pd.Dp, w.Lp = pd.Lp;
     w.S = apply_slices((long)(w.B1p / T) * (w.Lp / T), w.B2p / KC);
-    ApplyArena a(base);
+    NsvdArena a(base);
     w.yP = a.take((size_t)w.B2p * w.Dp);
     w.yN = a.take((size_t)w.B2p);
     w.fT = a.take((size_t)w.Lp * w.B2p);
@@ -236,19 +236,20 @@ extern "C" int nsvd_dot_apply(const float* x, int B1, const float* y, int B2, in
     if (!apply_dot_kind_ok(kind, gamma, coef0, degree)) return NSVD_EINVAL;
     if (D > APPLY_MAX_D) return NSVD_EUNSUPPORTED;
     const DotWs w = carve(ws, B1, B2, D, L);
-    if (!apply_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     ApplyPrep pr = {};
     pr.s[0] = {y, w.yP, w.yN, f, w.fT, B2, w.B2p};  // (|y|^2: the main kernel takes the root at staging)
     pr.D = D, pr.Dp = w.Dp, pr.L = L, pr.Lp = w.Lp;
     apply_prep_launch(pr, s);
     NSVD_CHECK_LAUNCH();
-    static const bool lds_limit_set = apply_set_lds_limit({(const void*)dot_main_kernel<NSVD_DOT_POLYNOMIAL>,
-                                                           (const void*)dot_main_kernel<NSVD_DOT_ARCCOS1>,
-                                                           (const void*)dot_main_kernel<NSVD_DOT_RELU_NNGP>,
-                                                           (const void*)dot_main_kernel<NSVD_DOT_RELU_NTK>},
-                                                          dot_lds_bytes(APPLY_MAX_D));
-    (void)lds_limit_set;
+    static NsvdLdsOptIn lds_opt_in;
+    if (const int rc = nsvd_lds_opt_in(lds_opt_in, {(const void*)dot_main_kernel<NSVD_DOT_POLYNOMIAL>,
+                                                    (const void*)dot_main_kernel<NSVD_DOT_ARCCOS1>,
+                                                    (const void*)dot_main_kernel<NSVD_DOT_RELU_NNGP>,
+                                                    (const void*)dot_main_kernel<NSVD_DOT_RELU_NTK>},
+                                                   dot_lds_bytes(APPLY_MAX_D)))
+        return rc;
     const dim3 grid(w.B1p / T, w.Lp / T, w.S);
     const DotMap mp = {gamma, coef0, degree};
     nsvd_prof_begin(s);

@@ -51,7 +51,7 @@ DPairWs carve(void* base, int B1, int B2, int D, int L) {
     DPairWs w;
     w.B1p = pd.B1p, w.B2p = pd.B2p, w.Dp = pd.Dp, w.Lp = pd.Lp;
     pair_split(w.B1p / T, nsvd_cdiv(w.B2p / KC, PAIR_SLICE), w.Lp / T, &w.RG, &w.CG);
-    ApplyArena a(base);
+    NsvdArena a(base);
     w.xP = a.take((size_t)w.B1p * w.Dp);
     w.xN = a.take((size_t)w.B1p);
     w.yP = a.take((size_t)w.B2p * w.Dp);
@@ -396,7 +396,7 @@ extern "C" int nsvd_dot_apply_pair(const float* x, int B1, const float* y, int B
     }
     if (D > APPLY_MAX_D) return NSVD_EUNSUPPORTED;
     const DPairWs w = carve(ws, B1, B2, D, L);
-    if (!apply_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     ApplyPrep pr = {};
     pr.s[0] = {y, w.yP, w.yN, g, w.gT, B2, w.B2p};
@@ -404,12 +404,13 @@ extern "C" int nsvd_dot_apply_pair(const float* x, int B1, const float* y, int B
     pr.D = D, pr.Dp = w.Dp, pr.L = L, pr.Lp = w.Lp, pr.rooted = apply_is_relu(kind) ? 0 : 1;  // (|.|; the deep ReLU kinds: |.|^2)
     apply_prep_launch(pr, s);
     NSVD_CHECK_LAUNCH();
-    static const bool lds_limit_set = apply_set_lds_limit({(const void*)dot_pair_main_kernel<NSVD_DOT_POLYNOMIAL>,
-                                                           (const void*)dot_pair_main_kernel<NSVD_DOT_ARCCOS1>,
-                                                           (const void*)dot_pair_main_kernel<NSVD_DOT_RELU_NNGP>,
-                                                           (const void*)dot_pair_main_kernel<NSVD_DOT_RELU_NTK>},
-                                                          dpair_lds_bytes(APPLY_MAX_D));
-    (void)lds_limit_set;
+    static NsvdLdsOptIn lds_opt_in;
+    if (const int rc = nsvd_lds_opt_in(lds_opt_in, {(const void*)dot_pair_main_kernel<NSVD_DOT_POLYNOMIAL>,
+                                                    (const void*)dot_pair_main_kernel<NSVD_DOT_ARCCOS1>,
+                                                    (const void*)dot_pair_main_kernel<NSVD_DOT_RELU_NNGP>,
+                                                    (const void*)dot_pair_main_kernel<NSVD_DOT_RELU_NTK>},
+                                                   dpair_lds_bytes(APPLY_MAX_D)))
+        return rc;
     const dim3 grid(w.RG, w.Lp / T, w.CG);
     const DPairMap mp = {gamma, coef0, degree};
     nsvd_prof_begin(s);

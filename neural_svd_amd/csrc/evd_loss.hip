@@ -357,15 +357,17 @@ __global__ void __launch_bounds__(FUSED_THREADS) evd_fused_kernel(const float* _
 bool fused_ok(int B, int L) { return (size_t)B * L <= FUSED_MAX && L <= 64 && B >= 2; }
 
 size_t fused_lds(int B, int L) { return ((size_t)B * L + 2 * (size_t)L * L + 32) * sizeof(float); }
+constexpr size_t FUSED_LDS_MAX = ((size_t)FUSED_MAX + 2 * 64 * 64 + 32) * sizeof(float);  // fused_lds at fused_ok's limit
+constexpr size_t GRAD_LDS_MAX = ((size_t)MAXL * MAXL + (size_t)CH * MAXL) * sizeof(float);  // evd_loss_grad_kernel at MAXL
+static_assert(FUSED_LDS_MAX == 98432 && FUSED_LDS_MAX <= NSVD_LDS_MAX && GRAD_LDS_MAX <= NSVD_LDS_MAX, "LDS of gfx950");
 
 template <int STAGE>
 int launch_fused(const float* f, const float* Tf, int B, int L, int kind, const float* v, const float* M,
                  float grad_scale, float* moments, float* loss, float* df, hipStream_t s) {
     const size_t lds = fused_lds(B, L);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)evd_fused_kernel<STAGE>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return -(int)e;
+    if (lds > 48 * 1024) {  // raised to the admission limit of fused_ok
+        static NsvdLdsOptIn lds_opt_in;
+        if (const int e = nsvd_lds_opt_in(lds_opt_in, {(const void*)evd_fused_kernel<STAGE>}, FUSED_LDS_MAX)) return e;
     }
     hipLaunchKernelGGL(evd_fused_kernel<STAGE>, dim3(1), dim3(FUSED_THREADS), lds, s, f, Tf, B, L, kind, v, M,
                        grad_scale, moments, loss, df);
@@ -477,9 +479,8 @@ extern "C" int nsvd_evd_loss_grad(const float* f, const float* Tf, int B, int L,
     const int nch = df ? c.n1 + c.n2 : 1;
     const size_t lds = ((size_t)L * L + (size_t)CH * L) * sizeof(float);
     if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)evd_loss_grad_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return -(int)e;
+        static NsvdLdsOptIn lds_opt_in;
+        if (const int e = nsvd_lds_opt_in(lds_opt_in, {(const void*)evd_loss_grad_kernel}, GRAD_LDS_MAX)) return e;
     }
     hipLaunchKernelGGL(evd_loss_grad_kernel, dim3(nch), dim3(256), lds, (hipStream_t)stream, f, Tf, B, L, mask_kind,
                        v, M, moments, grad_scale, loss, df);

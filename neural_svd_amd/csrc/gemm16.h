@@ -379,13 +379,10 @@ inline int launch(const Args& a0, bool a_strided, bool b_strided, bool out_bf16,
         const int rcb = launch_b_inst<AS_, BS_, O_, F_>(a, s);                                                     \
         if (rcb) return rcb;                                                                                       \
     } else {                                                                                                       \
-        static bool attr_set = false;                                                                              \
-        if (!attr_set) {                                                                                           \
-            hipError_t e = hipFuncSetAttribute((const void*)gemm16_kernel<AS_, BS_, O_, F_>,                       \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);             \
-            if (e != hipSuccess) return -(int)e;                                                                   \
-            attr_set = true;                                                                                       \
-        }                                                                                                          \
+        static NsvdLdsOptIn lds_opt_in;                                                                            \
+        if (const int e =                                                                                          \
+                nsvd_lds_opt_in(lds_opt_in, {(const void*)gemm16_kernel<AS_, BS_, O_, F_>}, LDS_BYTES))            \
+            return e;                                                                                              \
         hipLaunchKernelGGL((gemm16_kernel<AS_, BS_, O_, F_>), grid, dim3(512), LDS_BYTES, s, a);                   \
     }
 #define G16_LAUNCH(AS_, BS_, O_)                                                                                   \

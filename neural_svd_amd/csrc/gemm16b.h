@@ -218,13 +218,9 @@ __global__ void __launch_bounds__(512, 4) gemm16b_kernel(Args a) {  // (4 waves 
 // launch the two-workgroups-per-CU form (arguments already validated and completed by launch(): tiles, wg0, nwg)
 template <bool AS_, bool BS_, bool O_, bool F_>
 inline int launch_b_inst(const Args& a, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm16b_kernel<AS_, BS_, O_, F_>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, B_LDS_BYTES);
-        if (e != hipSuccess) return -(int)e;
-        attr_set = true;
-    }
+    static NsvdLdsOptIn lds_opt_in;
+    if (const int e = nsvd_lds_opt_in(lds_opt_in, {(const void*)gemm16b_kernel<AS_, BS_, O_, F_>}, B_LDS_BYTES))
+        return e;
     hipLaunchKernelGGL((gemm16b_kernel<AS_, BS_, O_, F_>), dim3((unsigned)a.nwg), dim3(512), B_LDS_BYTES, s, a);
     return 0;
 }

@@ -46,7 +46,7 @@ KaWs carve(void* base, int N, int B1, int L) {
         S = apply_slices((long)(w.B1p / T) * (w.Lp / T), w.Np / KC);
     }
     w.S = S;
-    ApplyArena a(base);
+    NsvdArena a(base);
     w.ST = a.take((size_t)w.Lp * w.Np);
     w.part = a.take((size_t)S * w.B1p * w.Lp);
     w.bytes = a.off;
@@ -239,14 +239,9 @@ __global__ void __launch_bounds__(256) ka_reduce_kernel(KaWs w, const long long*
     out[i] = scale * s;
 }
 
-size_t ka_lds_bytes() {
-    static const size_t bytes = [] {
-        const size_t b = NSVD_TNT_FLOATS * sizeof(float);
-        (void)hipFuncSetAttribute((const void*)ka_gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-        return b;
-    }();
-    return bytes;
-}
+constexpr size_t KA_LDS_BYTES = NSVD_TNT_FLOATS * sizeof(float);
+constexpr size_t KA_DMA_LDS_BYTES = nsvd_pmlp::T128D_LDS_FLOATS * sizeof(float);
+static_assert(KA_LDS_BYTES <= NSVD_LDS_MAX && KA_DMA_LDS_BYTES <= NSVD_LDS_MAX, "LDS of gfx950");
 
 }  // namespace
 
@@ -262,8 +257,13 @@ extern "C" int nsvd_kernel_apply(const float* K, size_t ldk, int N, const long l
     const KaWs w = carve(ws, N, B1, L);
     // the tile routine reads whole 64-float chunks of a row: the leading dimension must cover the padded width
     if (ldk < (size_t)w.Np || (ldk & 3) != 0 || ((uintptr_t)K & 15) != 0) return NSVD_EINVAL;
-    if (ws_bytes < w.bytes || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
+    const bool dma = w.dma && (size_t)N * ldk * sizeof(float) < ((size_t)1 << 32);  // (32-bit row offsets)
+    static NsvdLdsOptIn lds_dma, lds_plain;
+    if (const int rc = dma ? nsvd_lds_opt_in(lds_dma, {(const void*)ka_gemm_dma_kernel}, KA_DMA_LDS_BYTES)
+                           : nsvd_lds_opt_in(lds_plain, {(const void*)ka_gemm_kernel}, KA_LDS_BYTES))
+        return rc;
     if (w.Np % KS_PB == 0 && w.Lp % 64 == 0) {  // (always: Np is a multiple of 64, Lp of 64)
         ka_scatter_blocks_kernel<<<dim3(w.Np / KS_PB, w.Lp / 64), 256, 0, s>>>(f, cols, B2, L, N, w.ST, w.Np);
         NSVD_CHECK_LAUNCH();
@@ -275,19 +275,13 @@ extern "C" int nsvd_kernel_apply(const float* K, size_t ldk, int N, const long l
         NSVD_CHECK_LAUNCH();
     }
     nsvd_prof_begin(s);  // bench.py --config cfg4 brackets the contraction (nsvd_profile_next_forward)
-    if (w.dma && (size_t)N * ldk * sizeof(float) < ((size_t)1 << 32)) {  // (32-bit row offsets)
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)ka_gemm_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)(nsvd_pmlp::T128D_LDS_FLOATS * sizeof(float)));
-            attr_set = true;
-        }
-        ka_gemm_dma_kernel<<<dim3(w.B1p / 128, w.Lp / T, w.S), 256, nsvd_pmlp::T128D_LDS_FLOATS * sizeof(float), s>>>(
+    if (dma) {
+        ka_gemm_dma_kernel<<<dim3(w.B1p / 128, w.Lp / T, w.S), 256, KA_DMA_LDS_BYTES, s>>>(
             K, (long)ldk, N, w.all_rows ? nullptr : rows, w.all_rows ? N : B1, w);
     } else {
-        ka_gemm_kernel<<<dim3(w.B1p / T, w.Lp / T, w.S), 256, ka_lds_bytes(), s>>>(K, (long)ldk, N,
-                                                                                    w.all_rows ? nullptr : rows,
-                                                                                    w.all_rows ? N : B1, w);
+        ka_gemm_kernel<<<dim3(w.B1p / T, w.Lp / T, w.S), 256, KA_LDS_BYTES, s>>>(K, (long)ldk, N,
+                                                                                  w.all_rows ? nullptr : rows,
+                                                                                  w.all_rows ? N : B1, w);
     }
     nsvd_prof_end(s);
     NSVD_CHECK_LAUNCH();

@@ -188,7 +188,7 @@ bool rows_shape_ok(int B, int L) { return L >= 1 && L <= NR_MAXL && B >= 1 && B 
 int rows_args(int B, int B1, int L, void* ws, size_t ws_bytes, NefRows* a) {
     if (!rows_shape_ok(B, L)) return NSVD_EUNSUPPORTED;
     if (B1 < 1 || B1 > B) return NSVD_EINVAL;
-    if (!ws || ws_bytes < nsvd_nef_rows_workspace_bytes(B, L) || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, nsvd_nef_rows_workspace_bytes(B, L))) return NSVD_EINVAL;
     a->B = B;
     a->L = L;
     a->Bh[0] = B1;

@@ -332,7 +332,7 @@ extern "C" int nsvd_nef_loss(const float* phi, const float* Tphi, int B, const f
     if (diagonal != 0 && diagonal != 1) return NSVD_EINVAL;
     NefLossArgs a = loss_args(phi, Tphi, B, phi1, Tphi1, B1, phi2, Tphi2, B2, L);
     if (!a.chunked && (!dphi1 || !dphi2)) return NSVD_EINVAL;
-    if (scratch_bytes < nsvd_nef_loss_workspace_bytes(B, B1, B2, L) || ((uintptr_t)scratch & 255) != 0) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(scratch, scratch_bytes, nsvd_nef_loss_workspace_bytes(B, B1, B2, L))) return NSVD_EINVAL;
     a.unbiased = unbiased ? 1 : 0;
     a.diagonal = diagonal;
     const size_t LL = (size_t)L * L;
@@ -370,7 +370,7 @@ extern "C" int nsvd_nef_operator_forward(const nsvd_model_desc* desc, const nsvd
     if (desc->D < 1 || desc->L <= 0) return NSVD_EINVAL;
     if (desc->D > NSVD_FD_MAXD) return NSVD_EUNSUPPORTED;  // (the per-point batch norms stop at the small stencil)
     if (desc->has_exp_mask && !params->scales) return NSVD_EINVAL;
-    if (ws_bytes < nsvd_workspace_bytes(desc, B) || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, nsvd_workspace_bytes(desc, B))) return NSVD_EINVAL;
     const int st = nsvd_problem_status(*desc, *prob);
     if (st) return st;
     // NeuralEF is built on the Schroedinger kind (every potential of nsvd_potential)
@@ -397,6 +397,8 @@ extern "C" int nsvd_nef_operator_backward(const nsvd_model_desc* desc, const nsv
                                           const float* h, const float* r, const float* stats, float* du0,
                                           const nsvd_params* grads, void* ws, size_t ws_bytes, int path, void* stream) {
     if (!desc || !dphi || !h || !r || !stats || !du0 || B <= 0 || desc->L <= 0) return NSVD_EINVAL;
+    // (nsvd_operator_backward judges the workspace again, behind this launch: a bad one is refused before anything runs)
+    if (!nsvd_ws_ok(ws, ws_bytes, nsvd_workspace_bytes(desc, B))) return NSVD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(nef_norm_bwd_kernel, dim3(desc->L), dim3(256), 0, s, dphi, h, r, stats, B, desc->L, du0);
     NSVD_CHECK_LAUNCH();

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <atomic>
+#include <initializer_list>
 #include "../../include/nsvd.h"
 
 #define NSVD_SOFTPLUS_THRESHOLD 20.0f  // torch.nn.Softplus default (reference mlp.py:84-85)
@@ -72,6 +74,50 @@ static inline int nsvd_problem_status(const nsvd_model_desc& d, const nsvd_probl
     return 0;
 }
 static inline size_t nsvd_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// ---- host: the three policies in front of every launch --------------------------------------------------------------
+// A caller's workspace (or scratch) is usable: there, large enough, and on the 256-byte boundary every carve assumes.
+static inline bool nsvd_ws_ok(const void* ws, size_t ws_bytes, size_t need) {
+    return ws && ws_bytes >= need && ((uintptr_t)ws & 255) == 0;
+}
+
+// Blocks carved from a workspace one after the other, each starting on nsvd_align's boundary. A null base measures:
+// `off` after the last block is the byte count of the layout.
+struct NsvdArena {
+    char* base;
+    size_t off = 0;
+    explicit NsvdArena(void* p) : base((char*)p) {}
+    void* take_bytes(size_t n) {
+        void* r = base + off;
+        off += nsvd_align(n);
+        return r;
+    }
+    float* take(size_t nfloats) { return (float*)take_bytes(nfloats * sizeof(float)); }
+};
+
+// The dynamic-LDS limit of a kernel above the 64 KB default is raised once per device and kernel. The call site owns the
+// state (a function-local static, one per kernel or per group of instances that share `bytes`); `bytes` is the most the
+// site ever launches with, not this call's. Bit d of the mask: raised on device d. Nothing here says whether the
+// attribute is per device (HIP's header is silent, CUDA's is), once per device is right under either reading. After the
+// first launch on a device a call costs one hipGetDevice and one atomic load; a device index of 64 or more opts in on
+// every call. Returns 0 or -(int)hipError.
+constexpr size_t NSVD_LDS_MAX = 160 * 1024;  // gfx950
+struct NsvdLdsOptIn {
+    std::atomic<uint64_t> devices{0};
+};
+static inline int nsvd_lds_opt_in(NsvdLdsOptIn& st, std::initializer_list<const void*> kernels, size_t bytes) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return -(int)e;
+    const uint64_t bit = (unsigned)dev < 64u ? (uint64_t)1 << dev : 0;
+    if (st.devices.load(std::memory_order_acquire) & bit) return 0;
+    for (const void* k : kernels) {
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return -(int)e;
+    }
+    st.devices.fetch_or(bit, std::memory_order_release);
+    return 0;
+}
 
 // softplus(z) = log(1 + e^z) with torch's threshold. Hardware exp2/log2 (v_exp_f32 / v_log_f32, ~1 ulp) plus the
 // first-order log1p correction: with u = fl(1 + t), d = u - 1 (exact), ln(1 + t) = ln(u) + (t - d) / u + ..., and

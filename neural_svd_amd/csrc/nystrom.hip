@@ -381,15 +381,6 @@ __global__ void __launch_bounds__(NY_THREADS) ritz_step_kernel(const double* __r
     if (t == 0 && bits) *status = *status | bits;
 }
 
-void ritz_set_lds_limit() {
-    static const bool done = [] {
-        (void)hipFuncSetAttribute((const void*)ritz_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)ritz_lds_bytes(NY_MAXM));
-        return true;
-    }();
-    (void)done;
-}
-
 }  // namespace
 
 extern "C" size_t nsvd_tsgram_f64_workspace_bytes(int n, int m) { return ts_gram_workspace_bytes(n, m, 2); }
@@ -404,7 +395,8 @@ extern "C" int nsvd_ritz_step_f64(const double* S, const double* A, const double
                                   double* resid, double* Q, double* T, int* status, void* stream) {
     if (!S || !T || !status || m <= 0) return NSVD_EINVAL;
     if (m > NY_MAXM) return NSVD_EUNSUPPORTED;
-    ritz_set_lds_limit();
+    static NsvdLdsOptIn lds_opt_in;
+    if (const int rc = nsvd_lds_opt_in(lds_opt_in, {(const void*)ritz_step_kernel}, ritz_lds_bytes(NY_MAXM))) return rc;
     ritz_step_kernel<<<1, NY_THREADS, ritz_lds_bytes(m), (hipStream_t)stream>>>(S, A, C, m, theta, resid, Q,
                                                                                 T, status);
     NSVD_CHECK_LAUNCH();

@@ -355,14 +355,11 @@ __global__ void __launch_bounds__(NT) svd_ritz_step_kernel(const double* __restr
     if (t == 0 && bits) *status = *status | bits;
 }
 
-void svd_ritz_set_lds_limit() {
-    static const bool done = [] {
-        // (the 256-thread instance serves m <= 32: 26 KB, inside the default limit)
-        (void)hipFuncSetAttribute((const void*)svd_ritz_step_kernel<SV_MAX_THREADS>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)svd_lds_bytes(NY_MAXM));
-        return true;
-    }();
-    (void)done;
+// (the 256-thread instance serves m <= 32: 26 KB, inside the default limit. A function of its own ahead of the entry
+// point: the instance named first in the file comes first in the code object, and the wide one did)
+int svd_ritz_lds_opt_in() {
+    static NsvdLdsOptIn st;
+    return nsvd_lds_opt_in(st, {(const void*)svd_ritz_step_kernel<SV_MAX_THREADS>}, svd_lds_bytes(NY_MAXM));
 }
 
 }  // namespace
@@ -381,7 +378,7 @@ extern "C" int nsvd_svd_ritz_step_f64(const double* PtU, const double* RtV, cons
                                       void* stream) {
     if (!PtU || !RtV || !Sp || !Sr || !Tu || !Tv || !status || m <= 0) return NSVD_EINVAL;
     if (m > NY_MAXM) return NSVD_EUNSUPPORTED;
-    svd_ritz_set_lds_limit();
+    if (const int rc = svd_ritz_lds_opt_in()) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (m > SV_WIDE_M)
         svd_ritz_step_kernel<SV_MAX_THREADS><<<1, SV_MAX_THREADS, svd_lds_bytes(m), s>>>(

@@ -90,25 +90,19 @@ GenericWs carve(const nsvd_model_desc& d, int B, void* base, int erows = 0) {
     memset(&w, 0, sizeof(w));
     const size_t E = erows > 0 ? (size_t)erows : 1 + 2 * (size_t)d.D, R = E * B, F = 2 * (size_t)d.m;
     w.R = (int)R;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t nfloats) {
-        float* q = (float*)(p + off);
-        off += nsvd_align(nfloats * sizeof(float));
-        return q;
-    };
-    w.phiT = take(F * R);
+    NsvdArena a(base);
+    w.phiT = a.take(F * R);
     int hmax = 1;
     for (int i = 0; i < d.nlayers; ++i) {
-        w.z[i] = take((size_t)d.L * d.dims[i] * R);
+        w.z[i] = a.take((size_t)d.L * d.dims[i] * R);
         if (d.dims[i] > hmax) hmax = d.dims[i];
     }
-    w.jac = take((size_t)B * d.L);
-    w.dsc = take((size_t)B * d.L);
-    w.dz[0] = take((size_t)d.L * hmax * B);
-    w.dz[1] = take((size_t)d.L * hmax * B);
-    w.df = take((size_t)B * d.L);
-    w.bytes = off;
+    w.jac = a.take((size_t)B * d.L);
+    w.dsc = a.take((size_t)B * d.L);
+    w.dz[0] = a.take((size_t)d.L * hmax * B);
+    w.dz[1] = a.take((size_t)d.L * hmax * B);
+    w.df = a.take((size_t)B * d.L);
+    w.bytes = a.off;
     return w;
 }
 
@@ -124,13 +118,11 @@ bool want_fused(const nsvd_model_desc& d, int B, int path, bool exact = false) {
 
 bool fused_requested(int path) { return path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3; }
 
-bool ws_ok(const void* ws, size_t ws_bytes, size_t need) { return ws_bytes >= need && ((uintptr_t)ws & 255) == 0; }
-
 // what every operator entry point ends its validation with: the workspace is big enough and 256-byte aligned, and an
 // explicitly fused path on a shape the MFMA kernels do not take is refused, never rerouted. *fused: which kernels run
 int resolve_path(const nsvd_model_desc& d, const nsvd_problem& prob, int B, const void* ws, size_t ws_bytes, int path,
                  bool* fused) {
-    if (!ws_ok(ws, ws_bytes, nsvd_workspace_bytes(&d, B))) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, nsvd_workspace_bytes(&d, B))) return NSVD_EINVAL;
     *fused = want_fused(d, B, path, !(prob.eps > 0.f));
     return fused_requested(path) && !*fused ? NSVD_EUNSUPPORTED : 0;
 }
@@ -428,7 +420,7 @@ extern "C" int nsvd_model_forward(const nsvd_model_desc* desc, const nsvd_params
     if (!x || !out || !ws || B <= 0) return NSVD_EINVAL;
     rc = check_params(*desc, params, true);
     if (rc) return rc;
-    if (!ws_ok(ws, ws_bytes, nsvd_model_workspace_bytes(desc, B))) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, nsvd_model_workspace_bytes(desc, B))) return NSVD_EINVAL;
     if (nsvd_fused_model_supported(*desc, B))  // 128-wide hidden layers: the E = 1 instance of the MFMA forward
         return nsvd_fused_model_forward(*desc, *params, x, B, hard_mul_const, out, ws, save_for_backward,
                                         (hipStream_t)stream);
@@ -452,7 +444,7 @@ extern "C" int nsvd_model_backward(const nsvd_model_desc* desc, const nsvd_param
     if (rc) return rc;
     rc = check_params(*desc, grads, false);
     if (rc) return rc;
-    if (!ws_ok(ws, ws_bytes, nsvd_model_workspace_bytes(desc, B))) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, nsvd_model_workspace_bytes(desc, B))) return NSVD_EINVAL;
     if (nsvd_fused_model_supported(*desc, B)) {
         nsvd_problem unused;
         memset(&unused, 0, sizeof(unused));
@@ -536,7 +528,7 @@ EvdCall evd_call(const nsvd_model_desc* desc, const nsvd_params* params, const n
 int next_batch(EvdCall& c, unsigned long long seed, unsigned long long offset, float* x_next, void* ws_next,
                size_t ws_next_bytes) {
     if (!x_next || !ws_next || ws_next == c.ws || !c.desc) return NSVD_EINVAL;
-    if (!ws_ok(ws_next, ws_next_bytes, nsvd_workspace_bytes(c.desc, c.B))) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws_next, ws_next_bytes, nsvd_workspace_bytes(c.desc, c.B))) return NSVD_EINVAL;
     if (const int st = validate_problem(c.desc, c.prob)) return st;
     c.next.smp = make_sampler(*c.prob, seed, offset);
     c.next.x = x_next;
@@ -678,7 +670,7 @@ int backward_evd(EvdCall& c) {
     hipStream_t s = (hipStream_t)c.stream;
     bool fused;
     if (c.model_mode) {
-        if (!ws_ok(c.ws, c.ws_bytes, nsvd_model_workspace_bytes(desc, B))) return NSVD_EINVAL;
+        if (!nsvd_ws_ok(c.ws, c.ws_bytes, nsvd_model_workspace_bytes(desc, B))) return NSVD_EINVAL;
         fused = nsvd_fused_model_supported(*desc, B);
         if (!fused) return NSVD_EUNSUPPORTED;  // plain-model training steps exist on the MFMA kernels only
     } else {

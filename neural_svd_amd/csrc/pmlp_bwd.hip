@@ -1194,13 +1194,8 @@ static int fused_backward_impl(const nsvd_model_desc& dfull, const nsvd_params& 
             sa.pob[i] = pl.ob[i];
         }
         sa.poscales = pl.oscales;
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute((const void*)pmlp_stream_bwd2_kernel,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)SB2_LDS_BYTES);
-            if (e != hipSuccess) return -(int)e;
-            attr_set = true;
-        }
+        static NsvdLdsOptIn lds_opt_in;
+        if (const int e = nsvd_lds_opt_in(lds_opt_in, {(const void*)pmlp_stream_bwd2_kernel}, SB2_LDS_BYTES)) return e;
         hipLaunchKernelGGL(pmlp_stream_bwd2_kernel, dim3(d.L * SS), dim3(512), SB2_LDS_BYTES, s, sa);
     } else if ((nh == 2 || nh == 3) && chain_only <= 128)
         hipLaunchKernelGGL(pmlp_fused_bwd_chain_kernel<true>, dim3(chain_grid), dim3(256), 0, s, a);

@@ -208,31 +208,25 @@ inline FusedWs carve_fused(const nsvd_model_desc& d, int B, void* base) {
     FusedWs w;
     memset(&w, 0, sizeof(w));
     const size_t F = 2 * (size_t)d.m;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t nfloats) {
-        float* q = (float*)(p + off);
-        off += nsvd_align(nfloats * sizeof(float));
-        return q;
-    };
-    w.phi = take(F * B);
-    w.sctab = take((size_t)3 * d.D * d.m);  // (D, 2, m) cos / sin of eps B_dj, then (D, m) cos - 1 (bf16x3 forward)
-    w.phiTc = take(F * B);
-    for (int i = 0; i < d.nlayers - 1; ++i) w.zsave[i] = take((size_t)d.L * HID * B);
-    w.jac = take((size_t)B * d.L);
-    w.dsc = take((size_t)B * d.L);
-    for (int i = 0; i < d.nlayers - 1; ++i) w.dz[i] = take((size_t)d.L * HID * B);
-    w.dbase = take((size_t)B * d.L);
-    w.dfsc = take((size_t)B * d.L);
+    NsvdArena a(base);
+    w.phi = a.take(F * B);
+    w.sctab = a.take((size_t)3 * d.D * d.m);  // (D, 2, m) cos / sin of eps B_dj, then (D, m) cos - 1 (bf16x3 forward)
+    w.phiTc = a.take(F * B);
+    for (int i = 0; i < d.nlayers - 1; ++i) w.zsave[i] = a.take((size_t)d.L * HID * B);
+    w.jac = a.take((size_t)B * d.L);
+    w.dsc = a.take((size_t)B * d.L);
+    for (int i = 0; i < d.nlayers - 1; ++i) w.dz[i] = a.take((size_t)d.L * HID * B);
+    w.dbase = a.take((size_t)B * d.L);
+    w.dfsc = a.take((size_t)B * d.L);
     const int S = wgrad_slices(d, B), SS = stream_bwd_slices(d, B);
-    w.gpart = (S > 1 || SS > 0) ? take((size_t)(S > SS ? S : SS) * part_layout(d).stride) : nullptr;
-    w.w0p = (unsigned short*)take(((size_t)3 * d.L * HID * F + 1) / 2);
-    w.whp = (unsigned short*)take(((size_t)(d.nlayers > 2 ? d.nlayers - 2 : 0) * 3 * d.L * HID * HID + 1) / 2);
-    w.base_raw = take((size_t)d.L * (1 + 2 * (size_t)d.D) * B);
-    w.loss_part = take(33 * (size_t)d.L);
-    w.kpart = fwd_kpart_floats(d, B) ? take(fwd_kpart_floats(d, B)) : nullptr;
-    w.tickets = w.kpart ? (unsigned*)take((size_t)d.L * (B / BS)) : nullptr;
-    w.bytes = off;
+    w.gpart = (S > 1 || SS > 0) ? a.take((size_t)(S > SS ? S : SS) * part_layout(d).stride) : nullptr;
+    w.w0p = (unsigned short*)a.take(((size_t)3 * d.L * HID * F + 1) / 2);
+    w.whp = (unsigned short*)a.take(((size_t)(d.nlayers > 2 ? d.nlayers - 2 : 0) * 3 * d.L * HID * HID + 1) / 2);
+    w.base_raw = a.take((size_t)d.L * (1 + 2 * (size_t)d.D) * B);
+    w.loss_part = a.take(33 * (size_t)d.L);
+    w.kpart = fwd_kpart_floats(d, B) ? a.take(fwd_kpart_floats(d, B)) : nullptr;
+    w.tickets = w.kpart ? (unsigned*)a.take((size_t)d.L * (B / BS)) : nullptr;
+    w.bytes = a.off;
     return w;
 }
 

@@ -886,13 +886,9 @@ size_t fwd_lds_bytes() {
 template <int E, int JET = 0, int BF3 = 0, int PL = 0, int KS = 0>
 int launch_fwd(const FwdArgs& a, hipStream_t s, int prof = 3) {  // prof: bit 0 / 1 = this launch opens / closes the bracket
     const size_t lds = fwd_lds_bytes<E, BF3>();
-    static bool attr_done = false;  // idempotent, racing threads set the same value
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)pmlp_fused_fwd_kernel<E, JET, BF3, PL, KS>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return -(int)e;
-        attr_done = true;
-    }
+    static NsvdLdsOptIn lds_opt_in;
+    if (const int rc = nsvd_lds_opt_in(lds_opt_in, {(const void*)pmlp_fused_fwd_kernel<E, JET, BF3, PL, KS>}, lds))
+        return rc;
     const int grid = (a.B / (PL ? E * BS : BS)) * a.L * (a.split > 0 ? a.split : 1) * (KS == 1 ? a.ks : 1);
     if (prof & 1) nsvd_prof_begin(s);
     hipLaunchKernelGGL((pmlp_fused_fwd_kernel<E, JET, BF3, PL, KS>), dim3(grid), dim3(256), lds, s, a);
@@ -1126,13 +1122,9 @@ int nsvd_fused_model_forward(const nsvd_model_desc& d, const nsvd_params& p, con
             pa.out = out; pa.jac = a.jac; pa.dsc = a.dsc;
             pa.z0 = a.zsave[0]; pa.z1 = a.zsave[1];
             pa.B = B; pa.L = d.L; pa.tpw = tpw;
-            static bool attr_set = false;
-            if (!attr_set) {
-                hipError_t er = hipFuncSetAttribute((const void*)pmlp_plain_stream_fwd_kernel,
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF_LDS_BYTES);
-                if (er != hipSuccess) return -(int)er;
-                attr_set = true;
-            }
+            static NsvdLdsOptIn lds_opt_in;
+            if (const int er = nsvd_lds_opt_in(lds_opt_in, {(const void*)pmlp_plain_stream_fwd_kernel}, PF_LDS_BYTES))
+                return er;
             nsvd_prof_begin(s);
             hipLaunchKernelGGL(pmlp_plain_stream_fwd_kernel, dim3((B / BS / tpw) * d.L), dim3(256), PF_LDS_BYTES, s, pa);
             nsvd_prof_end(s);

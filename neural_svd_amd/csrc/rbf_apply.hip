@@ -39,7 +39,7 @@ RbfWs carve(void* base, int B1, int B2, int D, int L) {
     RbfWs w;
     w.B1p = pd.B1p, w.B2p = pd.B2p, w.Dp = pd.Dp, w.Lp = pd.Lp;
     w.S = apply_slices((long)(w.B1p / T) * (w.Lp / T), w.B2p / KC);
-    ApplyArena a(base);
+    NsvdArena a(base);
     w.yP = a.take((size_t)w.B2p * w.Dp);
     w.fT = a.take((size_t)w.Lp * w.B2p);
     w.part = a.take((size_t)w.S * w.B1p * w.Lp);
@@ -141,7 +141,7 @@ extern "C" int nsvd_rbf_apply(const float* x, int B1, const float* y, int B2, in
     if (!(ell > 0.f)) return NSVD_EINVAL;  // (also NaN)
     if (D > APPLY_MAX_D) return NSVD_EUNSUPPORTED;
     const RbfWs w = carve(ws, B1, B2, D, L);
-    if (!apply_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
     const float cexp = apply_radial_cexp(kind, ell);
     hipStream_t s = (hipStream_t)stream;
     ApplyPrep pr = {};
@@ -149,10 +149,11 @@ extern "C" int nsvd_rbf_apply(const float* x, int B1, const float* y, int B2, in
     pr.D = D, pr.Dp = w.Dp, pr.L = L, pr.Lp = w.Lp;
     apply_prep_launch(pr, s);
     NSVD_CHECK_LAUNCH();
-    static const bool lds_limit_set = apply_set_lds_limit({(const void*)rbf_main_kernel<NSVD_RBF_GAUSSIAN>,
-                                                           (const void*)rbf_main_kernel<NSVD_RBF_EXPONENTIAL>},
-                                                          rbf_lds_bytes(APPLY_MAX_D));
-    (void)lds_limit_set;
+    static NsvdLdsOptIn lds_opt_in;
+    if (const int rc = nsvd_lds_opt_in(lds_opt_in, {(const void*)rbf_main_kernel<NSVD_RBF_GAUSSIAN>,
+                                                    (const void*)rbf_main_kernel<NSVD_RBF_EXPONENTIAL>},
+                                                   rbf_lds_bytes(APPLY_MAX_D)))
+        return rc;
     const dim3 grid(w.B1p / T, w.Lp / T, w.S);
     nsvd_prof_begin(s);
     if (kind == NSVD_RBF_GAUSSIAN)

@@ -318,20 +318,17 @@ extern "C" int nsvd_retrieval_eval(const float* zq, long ldq, const float* zg, l
     if (Nq == 0) return 0;
     if (!zq || !zg || !q_cls || !g_cls || !prec_at_k || !ws || ldq < d || ldg < d) return NSVD_EINVAL;
     if (avg_prec && !n_relevant_items) return NSVD_EINVAL;
-    if ((((uintptr_t)zq | (uintptr_t)zg) & 3) != 0 || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
-    if (ws_bytes < nsvd_retrieval_workspace_bytes(Nq, Ng, d, K)) return NSVD_EINVAL;
+    if ((((uintptr_t)zq | (uintptr_t)zg) & 3) != 0) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, nsvd_retrieval_workspace_bytes(Nq, Ng, d, K))) return NSVD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int Npad = rt_npad(Ng), rows = rt_chunk_rows(Nq, Npad);
     float* hn = (float*)ws;
     unsigned long long* comps = (unsigned long long*)((char*)ws + nsvd_align((size_t)Ng * sizeof(float)));
     const int TL = Npad < RT_TILE ? Npad : RT_TILE;
     const size_t lds = (size_t)TL * 8;
-    // (per device and idempotent: set on every call rather than once per process)
-    {
-        hipError_t e = hipFuncSetAttribute((const void*)retr_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           RT_TILE * 8);
-        if (e != hipSuccess) return -(int)e;
-    }
+    static_assert((size_t)RT_TILE * 8 <= NSVD_LDS_MAX, "LDS of gfx950");
+    static NsvdLdsOptIn lds_opt_in;
+    if (const int e = nsvd_lds_opt_in(lds_opt_in, {(const void*)retr_rank_kernel}, (size_t)RT_TILE * 8)) return e;
     if (metric == NSVD_RETR_EUCLIDEAN) {
         hipLaunchKernelGGL(retr_half_sqnorm_kernel, dim3(nsvd_cdiv(Ng, 4)), dim3(256), 0, s, zg, ldg, Ng, d, hn);
         NSVD_CHECK_LAUNCH();

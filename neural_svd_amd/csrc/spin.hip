@@ -167,15 +167,6 @@ __global__ void __launch_bounds__(SP_THREADS) spin_solve_kernel(const double* __
     }
 }
 
-void solve_set_lds_limit() {
-    static const bool done = [] {
-        (void)hipFuncSetAttribute((const void*)spin_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)solve_lds_bytes(SP_MAXL));
-        return true;
-    }();
-    (void)done;
-}
-
 // ---- the Jacobian contraction -----------------------------------------------------------------------------------------
 struct SpinLayer {
     const float* act;    // a_{i-1}: (L, kin, R), or the Fourier features (kin, R) shared by the heads (act_stride 0)
@@ -390,18 +381,12 @@ SpinWs spin_carve(const nsvd_model_desc& d, int B1, void* base) {
         kin = d.dims[i];
     }
     w.P = P;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t nfloats) {
-        float* q = (float*)(p + off);
-        off += nsvd_align(nfloats * sizeof(float));
-        return q;
-    };
-    w.phiT = take((size_t)2 * d.m * w.R);
-    for (int i = 0; i + 1 < d.nlayers; ++i) w.act[i] = take((size_t)d.L * d.dims[i] * w.R);
-    for (int i = 0; i < d.nlayers; ++i) w.delta[i] = take((size_t)d.L * d.dims[i] * w.R);
-    w.part = take((size_t)w.nblocks * P);
-    w.bytes = off;
+    NsvdArena a(base);
+    w.phiT = a.take((size_t)2 * d.m * w.R);
+    for (int i = 0; i + 1 < d.nlayers; ++i) w.act[i] = a.take((size_t)d.L * d.dims[i] * w.R);
+    for (int i = 0; i < d.nlayers; ++i) w.delta[i] = a.take((size_t)d.L * d.dims[i] * w.R);
+    w.part = a.take((size_t)w.nblocks * P);
+    w.bytes = a.off;
     return w;
 }
 
@@ -415,7 +400,9 @@ extern "C" int nsvd_spin_solve(const double* sigma_raw, double sigma_scale, cons
     if (L < 2) return NSVD_EINVAL;
     if (L > SP_MAXL) return NSVD_EUNSUPPORTED;
     if (!(decay >= 0.0 && decay <= 1.0)) return NSVD_EINVAL;
-    solve_set_lds_limit();
+    static NsvdLdsOptIn lds_opt_in;
+    if (const int rc = nsvd_lds_opt_in(lds_opt_in, {(const void*)spin_solve_kernel}, solve_lds_bytes(SP_MAXL)))
+        return rc;
     spin_solve_kernel<<<1, SP_THREADS, solve_lds_bytes(L), (hipStream_t)stream>>>(
         sigma_raw, sigma_scale, pi_raw, pi_scale, L, decay, gpi_scale, sigma_avg, chol, loss_eigvals, gsigma, gpi_scaled,
         status);
@@ -444,8 +431,8 @@ extern "C" int nsvd_spin_jac_step(const nsvd_model_desc* desc, const nsvd_params
     if (!params->fourier_B) return NSVD_EINVAL;
     for (int i = 0; i < d.nlayers; ++i)
         if (!params->W[i] || !params->b[i] || !grads->W[i] || !grads->b[i]) return NSVD_EINVAL;
-    if (ws_bytes < nsvd_spin_jac_workspace_bytes(desc, B1) || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
     const SpinWs w = spin_carve(d, B1, ws);
+    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int R = w.R, F = 2 * d.m, nl = d.nlayers;
 

@@ -287,15 +287,6 @@ __global__ void __launch_bounds__(SX_THREADS) spinx_solve_kernel(SpinxArgs P) {
     if (t < L) P.out64[L + 2 + t] = lam[t];
 }
 
-void sx_set_lds_limit() {
-    static const bool done = [] {
-        (void)hipFuncSetAttribute((const void*)spinx_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)sx_lds_bytes(SX_MAXL));
-        return true;
-    }();
-    (void)done;
-}
-
 }  // namespace
 
 extern "C" int nsvd_spinx_solve(const double* S_raw, double s_scale, const double* Gpp_raw, const double* Gpk_raw,
@@ -316,7 +307,8 @@ extern "C" int nsvd_spinx_solve(const double* S_raw, double s_scale, const doubl
     P.out64 = out64; P.Ts = T_s; P.Tpp = T_pp; P.Tkp = T_kp; P.Tpk = T_pk; P.Tkk = T_kk;
     P.status = status;
     P.L = L; P.update_state = update_state ? 1 : 0;
-    sx_set_lds_limit();
+    static NsvdLdsOptIn lds_opt_in;
+    if (const int rc = nsvd_lds_opt_in(lds_opt_in, {(const void*)spinx_solve_kernel}, sx_lds_bytes(SX_MAXL))) return rc;
     spinx_solve_kernel<<<1, SX_THREADS, sx_lds_bytes(L), (hipStream_t)stream>>>(P);
     NSVD_CHECK_LAUNCH();
     return 0;

@@ -462,38 +462,32 @@ struct TowerWs {
 inline TowerWs carve_tower(int B, int d0, int d1, int d2, void* base) {
     TowerWs w;
     memset(&w, 0, sizeof(w));
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t nfloats) {
-        float* q = (float*)(p + off);
-        off += nsvd_align(nfloats * sizeof(float));
-        return q;
-    };
+    NsvdArena a(base);
     int S = fwd2_slices(B, d1, d2);  // (the larger of the two modes' slice counts: one layout for both)
     if (B % 256 == 0 && fwd2_slices16(1, B, d1, d2) > S) S = fwd2_slices16(1, B, d1, d2);
-    w.Y1 = take((size_t)B * d1);
-    w.A1 = take((size_t)B * d1);
-    w.A1T = take((size_t)B * d1);
-    w.Y2p = take((size_t)S * B * d2);
-    w.Y2 = take((size_t)B * d2);
-    w.XT = take((size_t)B * d0);
-    w.W2T = take((size_t)d1 * d2);
-    w.dY2 = take((size_t)B * d2);
-    w.dY2T = take((size_t)B * d2);
-    w.dA1 = take((size_t)B * d1);
-    w.dY1T = take((size_t)B * d1);
-    w.mean1 = take(d1);
-    w.inv1 = take(d1);
-    w.mean2 = take(d2);
-    w.inv2 = take(d2);
+    w.Y1 = a.take((size_t)B * d1);
+    w.A1 = a.take((size_t)B * d1);
+    w.A1T = a.take((size_t)B * d1);
+    w.Y2p = a.take((size_t)S * B * d2);
+    w.Y2 = a.take((size_t)B * d2);
+    w.XT = a.take((size_t)B * d0);
+    w.W2T = a.take((size_t)d1 * d2);
+    w.dY2 = a.take((size_t)B * d2);
+    w.dY2T = a.take((size_t)B * d2);
+    w.dA1 = a.take((size_t)B * d1);
+    w.dY1T = a.take((size_t)B * d1);
+    w.mean1 = a.take(d1);
+    w.inv1 = a.take(d1);
+    w.mean2 = a.take(d2);
+    w.inv2 = a.take(d2);
     {   // the operands cast per call (every other one is written as bfloat16 by its producer): X (B, d0) on the A
         // side; the master weights W1 (d1, d0) and W2 (d2, d1), one after the other, on the B side. Two bytes per value.
         w.capA = (size_t)B * d0;
         w.capB = (size_t)d1 * (d0 > d2 ? d0 : d2);
-        w.hA = take((w.capA + 1) / 2);
-        w.hB = take((w.capB + 1) / 2);
+        w.hA = a.take((w.capA + 1) / 2);
+        w.hB = a.take((w.capB + 1) / 2);
     }
-    w.bytes = off;
+    w.bytes = a.off;
     return w;
 }
 
@@ -1054,7 +1048,7 @@ int nsvd_tower_forward_phase(const float* x, const nsvd_tower_params* p, int B, 
     if (!p->W1 || !p->b1 || !p->g1 || !p->be1 || !p->W2 || !p->b2 || !p->g2 || !p->be2) return NSVD_EINVAL;
     if (update_running && (!p->rm1 || !p->rv1 || !p->rm2 || !p->rv2)) return NSVD_EINVAL;
     const TowerWs w = carve_tower(B, d0, d1, d2, ws);
-    if (ws_bytes < w.bytes || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (gemm_bf16 != 0) {  // mixed precision: the section above
         const float* xs[1] = {x};
@@ -1139,14 +1133,14 @@ int nsvd_tower16_forward_pair(const float* const* x, const nsvd_tower_params* co
                               float slope, float eps, float momentum, int update_running, int flags, float* const* z,
                               void* const* ws, size_t ws_bytes, hipStream_t s) {
     if (!tower16_shape_ok(B, d0, d1, d2)) return NSVD_EUNSUPPORTED;
+    const size_t need = carve_tower(B, d0, d1, d2, nullptr).bytes;
     for (int t = 0; t < 2; ++t) {
-        if (!x[t] || !p[t] || (!z[t] && !(flags & NSVD_TOWER16_WIDE_ONLY)) || !ws[t] || ((uintptr_t)ws[t] & 255) != 0)
+        if (!x[t] || !p[t] || (!z[t] && !(flags & NSVD_TOWER16_WIDE_ONLY)) || !nsvd_ws_ok(ws[t], ws_bytes, need))
             return NSVD_EINVAL;
         if (!p[t]->W1 || !p[t]->b1 || !p[t]->g1 || !p[t]->be1 || !p[t]->W2 || !p[t]->b2 || !p[t]->g2 || !p[t]->be2)
             return NSVD_EINVAL;
         if (update_running && (!p[t]->rm1 || !p[t]->rv1 || !p[t]->rm2 || !p[t]->rv2)) return NSVD_EINVAL;
     }
-    if (ws_bytes < carve_tower(B, d0, d1, d2, nullptr).bytes) return NSVD_EINVAL;
     return tower16_forward(2, x, p, B, d0, d1, d2, slope, eps, momentum, update_running, flags, 0, z, ws, s);
 }
 
@@ -1154,11 +1148,11 @@ int nsvd_tower16_backward_pair(const float* const* x, const nsvd_tower_params* c
                                int d0, int d1, int d2, float slope, const nsvd_tower_params* const* grads,
                                void* const* ws, size_t ws_bytes, float* const* sumsq, hipStream_t s, int flags) {
     if (!tower16_shape_ok(B, d0, d1, d2)) return NSVD_EUNSUPPORTED;
+    const size_t need = carve_tower(B, d0, d1, d2, nullptr).bytes;
     for (int t = 0; t < 2; ++t)
-        if (!x[t] || !p[t] || (!dz[t] && !(flags & NSVD_TOWER16_WIDE_ONLY)) || !grads[t] || !ws[t] ||
-            ((uintptr_t)ws[t] & 255) != 0)
+        if (!x[t] || !p[t] || (!dz[t] && !(flags & NSVD_TOWER16_WIDE_ONLY)) || !grads[t] ||
+            !nsvd_ws_ok(ws[t], ws_bytes, need))
             return NSVD_EINVAL;
-    if (ws_bytes < carve_tower(B, d0, d1, d2, nullptr).bytes) return NSVD_EINVAL;
     return tower16_backward(2, x, p, dz, B, d0, d1, d2, slope, grads, ws, sumsq, s, flags);
 }
 
@@ -1185,7 +1179,7 @@ int nsvd_tower_backward_sumsq(const float* x, const nsvd_tower_params* p, const 
     if (!grads->W1 || !grads->b1 || !grads->g1 || !grads->be1 || !grads->W2 || !grads->b2 || !grads->g2 || !grads->be2)
         return NSVD_EINVAL;
     const TowerWs w = carve_tower(B, d0, d1, d2, ws);
-    if (ws_bytes < w.bytes || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (gemm_bf16 != 0) {
         const float* xs[1] = {x};

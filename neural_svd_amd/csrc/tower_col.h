@@ -475,13 +475,9 @@ inline int launch_inst_t(const Args& a, hipStream_t s) {
     constexpr int epi = 8 * 16 * NI * 128 + RED_BYTES;
     constexpr int lds_bytes = ring > epi ? ring : epi;
     static_assert(lds_bytes <= 160 * 1024, "tower_col: LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)tower_col_kernel<BWD, NI, PI, NBUF, F16>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess) return -(int)e;
-        attr_set = true;
-    }
+    static NsvdLdsOptIn lds_opt_in;
+    if (const int e = nsvd_lds_opt_in(lds_opt_in, {(const void*)tower_col_kernel<BWD, NI, PI, NBUF, F16>}, lds_bytes))
+        return e;
     hipLaunchKernelGGL((tower_col_kernel<BWD, NI, PI, NBUF, F16>), dim3((unsigned)a.nwg), dim3(512), lds_bytes, s, a);
     return 0;
 }

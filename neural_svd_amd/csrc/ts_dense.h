@@ -107,7 +107,7 @@ static inline int ts_gram(const float* X, long ldx, const float* Y, long ldy, in
     if (!X || !ws || n <= 0 || m <= 0 || ldx < m) return NSVD_EINVAL;
     if (XtY && (!Y || ldy < m)) return NSVD_EINVAL;
     if (m > NY_MAXM) return NSVD_EUNSUPPORTED;
-    if (ws_bytes < ts_gram_workspace_bytes(n, m, slots) || ((uintptr_t)ws & 255) != 0) return NSVD_EINVAL;
+    if (!nsvd_ws_ok(ws, ws_bytes, ts_gram_workspace_bytes(n, m, slots))) return NSVD_EINVAL;
     const int S = ts_slices(n);
     hipStream_t s = (hipStream_t)stream;
     double* part = (double*)ws;

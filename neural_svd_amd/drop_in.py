@@ -13,6 +13,7 @@ Plotting and the local-energy monitor are left out (they are not part of the hot
 from __future__ import annotations
 
 import contextlib
+import gc
 import os
 import time
 
@@ -315,6 +316,12 @@ class CapturedPlainStep:
                     side = torch.cuda.Stream()
                     side.wait_stream(torch.cuda.current_stream())
                     graph = torch.cuda.CUDAGraph()
+                    # No cyclic collection inside the capture (torch.cuda.graph itself no longer collects before one):
+                    # the body allocates in the autograd thread too, and a collection there that frees a dead cycle
+                    # owning an EARLIER graph destroys that graph under a global-mode capture - the process aborts.
+                    gc.collect()
+                    gc_was_on = gc.isenabled()
+                    gc.disable()
                     try:
                         with torch.cuda.stream(side):
                             with torch.cuda.graph(graph, stream=side):
@@ -325,6 +332,9 @@ class CapturedPlainStep:
                         # captured launches never ran, so the state is that of the last eager step
                         torch.cuda.current_stream().wait_stream(side)
                         raise CaptureUnavailable(f"HIP-graph capture of the plain loop body failed: {e!r}") from e
+                    finally:
+                        if gc_was_on:
+                            gc.enable()
                     torch.cuda.current_stream().wait_stream(side)
                     self.graph = graph
                 self.graph.replay()
