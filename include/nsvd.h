@@ -558,6 +558,44 @@ int nsvd_spectrum_accumulate_const_f64(const float* f, const float* Tf, const fl
                                        float sigma, int use_importance, float lim, double* cov, double* quad,
                                        void* stream);
 
+/* ---- eigenFUNCTION accuracy against the analytic ground truths (2-D problems) ----------------------------------
+ * Replaces, on the device and per chunk of the validation grid, the host evaluation of the reference's
+ * examples/operator/pde/schrodinger/ground_truths.py - Hydrogen2D.eigfunc (:134-149), HarmonicOscillator._eigfunc_1d /
+ * _eigfunc_2d (:96-107), InfiniteWell2D.eigfunc (:61-63) - and the (n, L) products that examples/linalg.py's
+ * subspace_distance (:5-8), rotate (:11-16) and procrustes (:19-28) take: three small float64 matrices are left, from
+ * which neural_svd_amd/eigfuncs.py computes those metrics. NEW SYMBOLS ONLY: NSVD_ABI_VERSION stays 6.
+ *
+ * kind / param: NSVD_GT_HYDROGEN2D with the charge Z (psi_Z(x) = Z psi_1(Z x)), NSVD_GT_HARMONIC2D with k of
+ * V = k |x|^2 (b = sqrt(k) in the reference's formula), NSVD_GT_WELL2D with the half-width lim of the box [-lim, lim]^2
+ * (psi = (1 / lim) sin(nx pi (x + lim) / (2 lim)) sin(ny pi (y + lim) / (2 lim)), 0 outside).
+ * qnums: HOST pointer to (Lg, 2) ints - (n, l), (nx, ny), (nx, ny) - 1 <= Lg <= 80 (NSVD_EUNSUPPORTED above). Lg may
+ * exceed L: a metric over a degenerate level needs the whole level. Admitted: hydrogen 0 <= n <= 16, |l| <= n (l < 0
+ * keeps the reference's sin(l th), negative l inside); oscillator 0 <= nx, ny <= 16; well 1 <= nx, ny <= 32. The
+ * library computes each function's float64 normalisation on the host (lgamma) and hands the table to the kernel BY
+ * VALUE in the launch arguments: no allocation, no copy, no synchronisation; legal on any stream and under capture.
+ * The float32 coordinates are widened to float64 and everything after that is float64: Laguerre and Hermite by their
+ * three-term recurrences, cos(l th) and sin(l th) from x / r and y / r by the Chebyshev recurrence. At r = 0 hydrogen
+ * returns the limit (the reference's formula gives NaN for l = 0: 0 * log 0): the finite value for l = 0, 0 otherwise.
+ * The far tail underflows to 0, never to NaN.
+ * NSVD_EINVAL: a null pointer, B, L or Lg <= 0, an unknown kind, param not positive and finite, a quantum number the
+ * kind does not admit. A refused call launches nothing and writes nothing. */
+#define NSVD_GT_HYDROGEN2D 0
+#define NSVD_GT_HARMONIC2D 1
+#define NSVD_GT_WELL2D 2
+/* psi (B, Lg) float64 row-major: psi[b][i] = function i at x[b] (x: (B, 2) float32). */
+int nsvd_eigfunc_eval(int kind, double param, const int* qnums, int Lg, const float* x, int B, double* psi,
+                      void* stream);
+/* One pass over a chunk. With w and phi = nan_to_num(w f) exactly as nsvd_spectrum_accumulate forms them
+ * (w = sqrt(p_train(x)) / sqrt(p_val), D = 2) and psi_w = psi / sqrt(p_val):
+ *   gram (Lg, Lg) += psi_w^T psi_w,  cross (Lg, L) += psi_w^T phi,  cov (L, L) += phi^T phi   (cov may be NULL)
+ * float64 products, sums and accumulators; the sum across workgroups is a float64 atomic +=, as
+ * nsvd_spectrum_accumulate_f64's (the order is not fixed). f: (B, L) float32, L <= 64 (NSVD_EUNSUPPORTED above).
+ * use_importance: the three-way rule of nsvd_spectrum_accumulate (NONE and GAUSSIAN in the kernel, UNIFORM
+ * NSVD_EUNSUPPORTED, anything else NSVD_EINVAL). */
+int nsvd_eigfunc_accumulate_f64(int kind, double param, const int* qnums, int Lg, const float* f, int L,
+                                const float* x, int B, float sigma, int use_importance, float lim, double* gram,
+                                double* cross, double* cov, void* stream);
+
 /* ---- next row: dense kernel operator on a minibatch (kernel-operator configuration) ---------------------------
  * Kf[i][l] = scale * sum_k K[rows[i]][cols[k]] f[k][l]: the (Kf, f) producer that
  * NestedLoRA.compute_loss_kernel's `get_approx_kernel_op(x)(model, x, importance)` contract consumes

@@ -1,6 +1,7 @@
 // Shared host/device helpers for libnsvd_hip (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <math.h>
 #include <stdint.h>
 #include <atomic>
@@ -249,6 +250,13 @@ __device__ __forceinline__ float nsvd_sqrt_gauss_pdf(const float* xr, int D, flo
         M = fmaf(t, t, M);
     }
     return sqrtf(expf(-0.5f * M + log_norm));
+}
+
+// torch.nan_to_num with float32 semantics (methods/spectrum.py:71-72): NaN -> 0, +-inf -> +-FLT_MAX
+__device__ __forceinline__ float nsvd_nan_to_num(float v) {
+    if (isnan(v)) return 0.f;
+    if (isinf(v)) return v > 0 ? FLT_MAX : -FLT_MAX;
+    return v;
 }
 
 // host: -0.5 D log(2 pi) - D log(sigma)

@@ -8,18 +8,11 @@
 // float32 running sum over 500 workgroups then carries it to 1e-4 only (measured at configs[1]: 1.7e-4 on the n = 4
 // shell with float32 accumulators, 1e-6 with these - scripts/dev/parity_diag.py).
 #include "nsvd_kernels.h"
-#include <float.h>
 
 namespace {
 
 constexpr int SR = 128;     // rows per workgroup
 constexpr int SMAXL = 64;
-
-__device__ __forceinline__ float nan_to_num(float v) {
-    if (isnan(v)) return 0.f;
-    if (isinf(v)) return v > 0 ? FLT_MAX : -FLT_MAX;
-    return v;
-}
 
 template <typename Acc>
 __global__ void __launch_bounds__(256) spectrum_kernel(const float* __restrict__ f, const float* __restrict__ Tf,
@@ -44,8 +37,8 @@ __global__ void __launch_bounds__(256) spectrum_kernel(const float* __restrict__
         for (int d = 0; d < D; ++d) zero = zero && (fabsf(xr[d]) <= 1e-8f);  // torch.isclose(x, 0)
         const bool one = pad && c == 0;
         const size_t src = (size_t)(r0 + r) * Lin + (c - pad);
-        ph[i] = one ? 1.f : nan_to_num(w * f[src]);
-        const float t = one ? 1.f : nan_to_num(w * Tf[src]);
+        ph[i] = one ? 1.f : nsvd_nan_to_num(w * f[src]);
+        const float t = one ? 1.f : nsvd_nan_to_num(w * Tf[src]);
         tp[i] = zero ? 0.f : t;
     }
     __syncthreads();

@@ -490,6 +490,12 @@ def train_operator(args, method, operator, make_batch_ftn_train, val_data, batch
     if comm is not None and not fused.hp:
         torch.manual_seed((torch.initial_seed() * 1000003 + 7919 * comm.rank + 1) % (1 << 62))
     all_eigvals, all_norms = [], []
+    # args.eigfunc_metrics (this package's switch, default off: the evaluation call and the log rows are then unchanged):
+    # the evaluation also measures the learned functions against the analytic ones (eigfuncs.eigenfunction_metrics)
+    eigfunc_kw, eigfunc_row = {}, {}
+    if getattr(args, "eigfunc_metrics", False):
+        from .operators import ground_truth_of
+        eigfunc_kw = dict(ground_truth=ground_truth_of(args))
     start = time.time()
     # the reference adds loss.item() to a host total on EVERY step (operator/__init__.py:74,99: a device sync per
     # step); here the running total lives on the device and is read at print time only. The fused loop's backward
@@ -565,6 +571,7 @@ def train_operator(args, method, operator, make_batch_ftn_train, val_data, batch
             assert n_loss > 0
             row = {"iter": it + 1, "train_loss": float(loss), "avg_train_loss": float(total_loss) / n_loss,
                    "time": time.time() - start}
+            row.update(eigfunc_row)  # (empty unless args.eigfunc_metrics: the last evaluation's per-level distances)
             if rank0:
                 print(dict(row, avg_train_loss_over=f"every {loss_stride}-th step") if sampled_mean else row)
             if log_writer is not None and rank0:
@@ -585,10 +592,16 @@ def train_operator(args, method, operator, make_batch_ftn_train, val_data, batch
                     normalize = getattr(method, "name", None) in ["nestedlora", "neuralsvd"]
                     outputs = compute_spectrum_evd(method, dataloader=batch_ftn_val(), operator=operator,
                                                    importance_train=importance_train, importance_val=importance_val,
-                                                   normalize=normalize, set_first_mode_const=False, device=device)
+                                                   normalize=normalize, set_first_mode_const=False, device=device,
+                                                   **eigfunc_kw)
                     if rank0:
                         print(f"it{it + 1} eigvals: {outputs['eigvals']}")
                         print(f"it{it + 1} norms: {outputs['norms']}")
+                    if eigfunc_kw:
+                        dist = outputs["eigfunc_metrics"]["subspace_distance"]
+                        eigfunc_row = {f"eigfunc_dist_level{i}": float(d) for i, d in enumerate(dist)}
+                        if rank0:
+                            print(f"it{it + 1} eigenfunction subspace distances per level: {dist}")
                     all_eigvals.append(outputs["eigvals"])
                     all_norms.append(outputs["norms"])
             if getattr(args, "log_dir", None) and rank0:

@@ -12,8 +12,9 @@ OperatorWrapper, get_problem, the Gaussian sampler / importance and the analytic
     get_problem                                         examples/operator/pde/problems.py:23-130 (ndim 5 / 10 and
                                                         quantum_chemistry under args.high_dim_stencil)
     get_dataloader                                      examples/operator/pde/main_pde.py:89-130 (gaussian sampler)
-    Hydrogen2D / HarmonicOscillator .get_eigvals        examples/operator/pde/schrodinger/ground_truths.py:78-90,120-132
-    InfiniteWell2D.get_eigvals                          examples/operator/pde/schrodinger/ground_truths.py:40-58
+    Hydrogen2D / HarmonicOscillator / InfiniteWell2D    examples/operator/pde/schrodinger/ground_truths.py:40-149
+      .get_qnums / .get_eigvals / .get_degeneracy / .eigfunc  (numpy float64 host mirror; the device evaluation is
+                                                        nsvd_eigfunc_eval, csrc/eig_math.h)
     Hydrogen3D.get_eigvals                              examples/operator/pde/schrodinger/ground_truths.py (3-D hydrogen)
 
 These objects are DESCRIPTORS on the scripts' configuration (Gaussian or uniform sampler / importance, or none): calling
@@ -439,9 +440,53 @@ def fused_problem_of(operator, importance, model) -> H.Problem:
 
 
 # ----------------------------------------------------------------------------------- ground truths
+def _degeneracy(keys):
+    """ToyProblem._get_degeneracy (ground_truths.py:22-37): cumulative level boundaries starting at 0, a level being a
+    run of equal keys. Like the reference, a LAST level of a single state is not closed ([0, 1, 4] for 5 hydrogen
+    states): a boundary is appended at the end only when the last run is longer than one."""
+    cnt, prev, deg = 1, keys[0], [0]
+    for k in keys[1:]:
+        if k == prev:
+            cnt += 1
+        else:
+            deg.append(cnt)
+            prev, cnt = k, 1
+    if cnt > 1:
+        deg.append(cnt)
+    return np.array(deg).cumsum()
+
+
+def _laguerre(k, alpha, z):
+    """generalised Laguerre L_k^(alpha)(z) by (j + 1) L_{j+1} = (2j + 1 + alpha - z) L_j - (j + alpha) L_{j-1}"""
+    z = np.asarray(z, dtype=np.float64)
+    lm, lc = np.zeros_like(z), np.ones_like(z)
+    for j in range(k):
+        lm, lc = lc, ((2 * j + 1 + alpha - z) * lc - (j + alpha) * lm) / (j + 1)
+    return lc
+
+
+def _hermite(n, u):
+    """physicists' Hermite H_n(u) by H_{j+1} = 2 u H_j - 2 j H_{j-1}"""
+    u = np.asarray(u, dtype=np.float64)
+    hm, hc = np.zeros_like(u), np.ones_like(u)
+    for j in range(n):
+        hm, hc = hc, 2 * u * hc - 2 * j * hm
+    return hc
+
+
 class Hydrogen2D:
+    """ground_truths.py:110-149. Differences from the reference, all deliberate: ``eigfunc`` returns the LIMIT at
+    r = 0 (the finite value for l = 0, 0 otherwise) where the reference's formula is 0 * log 0 = NaN; the charge enters
+    the functions, psi_Z(x) = Z psi_1(Z x) (the reference's eigfunc ignores it); hyp1f1 is the Laguerre recurrence
+    (hyp1f1(-k, 2a + 1, z) = k! (2a)! / (k + 2a)! L_k^(2a)(z)), not scipy.special."""
+
     def __init__(self, charge=1.0):
         self.charge = charge
+
+    def get_qnums(self, neigs):
+        """(n, l), l = -n .. n, shell after shell (ground_truths.py:115-118)"""
+        nmax = int(np.ceil(np.sqrt(neigs)))
+        return [(n, l) for n in range(0, nmax + 1) for l in range(-n, n + 1)][:neigs]
 
     def get_eigvals(self, neigs):
         """E_n = -Z^2 / (4 (n + 1/2)^2), degeneracy 2n + 1, first ``neigs`` states."""
@@ -451,6 +496,22 @@ class Hydrogen2D:
             n += 1
         q = np.array(shells[:neigs], dtype=np.float64)
         return -self.charge ** 2 / (4 * (q + 0.5) ** 2)
+
+    def get_degeneracy(self, neigs):
+        return _degeneracy([n for n, _ in self.get_qnums(neigs)])
+
+    def eigfunc(self, n, l, r, th):
+        """psi_{n,l}(r, th), numpy float64; for l < 0 the reference's sin(l th), negative l inside (:145)."""
+        r, th = np.asarray(r, dtype=np.float64), np.asarray(th, dtype=np.float64)
+        Z, a = float(self.charge), abs(int(l))
+        z = Z * r / (n + 0.5)
+        norm = Z / (n + 0.5) * math.exp(0.5 * (math.lgamma(n - a + 1) - math.lgamma(n + a + 1) - math.log(2 * n + 1)))
+        radial = norm * z ** a * np.exp(-z / 2) * _laguerre(n - a, 2 * a, z)  # (0 ** 0 = 1: the l = 0 limit at r = 0)
+        if l > 0:
+            return radial * np.cos(l * th) / math.sqrt(math.pi)
+        if l < 0:
+            return radial * np.sin(l * th) / math.sqrt(math.pi)
+        return radial / math.sqrt(2 * math.pi)
 
 
 class Hydrogen3D:
@@ -467,9 +528,20 @@ class Hydrogen3D:
 
 
 class HarmonicOscillator:
+    """ground_truths.py:66-107. Difference from the reference, deliberate: ``eigfunc`` carries k, b = sqrt(k) in the
+    reference's own formula (whose callers leave b = 1); Hermite by its recurrence, not np.polynomial."""
+
     def __init__(self, k=1.0, ndim=2):
         assert ndim == 2, f"dim={ndim} not implemented"
         self.k, self.ndim = k, ndim
+
+    def get_qnums(self, neigs):
+        """(i, n - i), i = 0 .. n, shell after shell (ground_truths.py:73-76)"""
+        q, n = [], 0
+        while len(q) < neigs:
+            q += [(i, n - i) for i in range(n + 1)]
+            n += 1
+        return np.array(q[:neigs])
 
     def get_eigvals(self, neigs):
         """sqrt(k) (2n + D) with degeneracy n + 1.  Like the reference, whole shells are emitted up
@@ -483,10 +555,39 @@ class HarmonicOscillator:
         vals = [2 * n + self.ndim for n in range(nend + 1) for _ in range(n + 1)]
         return math.sqrt(self.k) * np.array(vals, dtype=np.float64)
 
+    def get_degeneracy(self, neigs):
+        """over get_eigvals' WHOLE shells, as the reference (its boundaries run past ``neigs``)"""
+        return _degeneracy(list(self.get_eigvals(neigs)))
+
+    def eigfunc(self, nx, ny, x, y):
+        b = math.sqrt(self.k)
+
+        def one(n, t):
+            t = np.asarray(t, dtype=np.float64)
+            return (math.exp(-0.5 * (n * math.log(2.0) + math.lgamma(n + 1))) * (b / math.pi) ** 0.25 *
+                    np.exp(-b * t ** 2 / 2) * _hermite(n, math.sqrt(b) * t))
+        return one(int(nx), x) * one(int(ny), y)
+
 
 class InfiniteWell2D:
+    """ground_truths.py:40-63. Differences from the reference, deliberate: ``get_qnums`` is ENERGY-ordered (the
+    reference's list is not from the ninth state on: (3, 3), E ~ 18, precedes (4, 1), E ~ 17) - by nx^2 + ny^2, stable in
+    the reference's generation order, equal to the reference's list for neigs <= 8; levels are grouped by integer
+    equality of nx^2 + ny^2, which catches accidental degeneracies (50 = 5^2 + 5^2 = 7^2 + 1^2). ``eigfunc`` is the
+    reference's, on [0, L]; ``eigfunc_box`` is the same function in this package's coordinates, the box [-lim, lim]^2
+    with L = 2 lim as get_problem builds it, and 0 outside."""
+
     def __init__(self, L=1.0):
         self.L = L
+
+    def get_qnums(self, neigs):
+        neigs = int(neigs)
+        gen = []
+        for n in range(1, neigs + 2):  # nx, ny <= neigs covers the neigs lowest states (each (n, 1) is one)
+            for i in range(1, n):
+                gen += [(n, i), (i, n)]
+            gen.append((n, n))
+        return sorted(gen, key=lambda q: q[0] ** 2 + q[1] ** 2)[:neigs]  # (sorted is stable)
 
     def get_eigvals(self, neigs):
         """(n_x^2 + n_y^2) pi^2 / L^2 over n_x, n_y >= 1, ascending, first ``neigs`` values (ground_truths.py:40-58)."""
@@ -494,6 +595,34 @@ class InfiniteWell2D:
         n = np.arange(1, int(neigs) + 1, dtype=np.float64)
         vals = np.sort((n[:, None] ** 2 + n[None, :] ** 2).reshape(-1))[:int(neigs)]
         return vals * np.pi ** 2 / float(self.L) ** 2
+
+    def get_degeneracy(self, neigs):
+        return _degeneracy([nx * nx + ny * ny for nx, ny in self.get_qnums(neigs)])
+
+    def eigfunc(self, nx, ny, x, y):
+        L = float(self.L)
+        x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+        return 2 / L * np.sin(nx * np.pi * x / L) * np.sin(ny * np.pi * y / L)
+
+    def eigfunc_box(self, nx, ny, x, y):
+        lim = 0.5 * float(self.L)
+        x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+        inside = (np.abs(x) <= lim) & (np.abs(y) <= lim)
+        return np.where(inside, self.eigfunc(nx, ny, x + lim, y + lim), 0.0)
+
+
+def ground_truth_of(args):
+    """The ground truth with eigenfunction formulae that get_problem's configuration has (ndim 2: hydrogen, the
+    oscillator with get_problem's k = 1, the well with its side 2 lim); ProblemConfigError for any other."""
+    _require(getattr(args, "problem", "sch") == "sch" and args.ndim == 2,
+             "eigenfunction formulae: the 2-D Schroedinger problems only")
+    if args.potential_type == "hydrogen":
+        return Hydrogen2D(charge=args.charge)
+    if args.potential_type == "harmonic_oscillator":
+        return HarmonicOscillator(k=1.0, ndim=2)
+    if args.potential_type == "infinite_well":
+        return InfiniteWell2D(L=2 * args.lim)
+    raise ProblemConfigError(f"potential_type {args.potential_type}: no eigenfunction formulae")
 
 
 # cs and -eigenvalues of the periodic benchmark pair (Han, Lu and Zhou 2020), as problems.py:49-61 tabulates them

@@ -15,7 +15,11 @@ from .operators import GaussianImportance, UniformBoxImportance
 @torch.no_grad()
 def compute_spectrum_evd(model, dataloader, operator, importance_train=None, importance_val=None,
                          set_first_mode_const=False, post_align=False, normalize=False, sort=False, gpu=None,
-                         device=None):
+                         device=None, ground_truth=None):
+    """ground_truth (keyword of this package, default None: nothing changes): a 2-D ground truth of operators.py, or an
+    eigfuncs.GroundTruthTable. The eigenfunction accumulators are then filled in the same loop (nsvd_eigfunc_accumulate_f64)
+    and out["eigfunc_metrics"] holds eigfuncs.eigenfunction_metrics of them, its `order` the sort=True order when
+    sort is set. Not with set_first_mode_const."""
     if (gpu is None) == (device is None):
         raise ValueError("exactly one of gpu / device")
     if not isinstance(importance_val, UniformBoxImportance):
@@ -31,6 +35,12 @@ def compute_spectrum_evd(model, dataloader, operator, importance_train=None, imp
     cov = torch.zeros((L, L), dtype=torch.float64, device=dev)
     quad = torch.zeros_like(cov)
     eigfuncs, n = [], 0
+    acc = None
+    if ground_truth is not None:
+        if set_first_mode_const:
+            raise NsvdError("compute_spectrum_evd(ground_truth=...): not with set_first_mode_const")
+        from .eigfuncs import Accumulator
+        acc = Accumulator(ground_truth, L, dev)
     sigma = importance_train.sigma if (importance_train is not None and in_kernel) else 1.0
     for (x, _) in dataloader:
         if isinstance(x, list):
@@ -44,6 +54,8 @@ def compute_spectrum_evd(model, dataloader, operator, importance_train=None, imp
         H.spectrum_accumulate(phi.float().contiguous(), Tphi.float().contiguous(), x, sigma,
                               importance_train is not None and in_kernel, importance_val.lim, cov, quad,
                               first_mode_const=bool(set_first_mode_const))
+        if acc is not None:
+            acc.add(phi.float().contiguous(), x, sigma, importance_train is not None and in_kernel, importance_val.lim)
         n += len(x)
     out = dict()
     cov64 = (cov / n).cpu().numpy()
@@ -64,6 +76,8 @@ def compute_spectrum_evd(model, dataloader, operator, importance_train=None, imp
         out["cov"] = out["cov"][:, idx][idx, :]
         out["quad"] = out["quad"][:, idx][idx, :]
         out["norms"] = out["norms"][idx]
+    if acc is not None:
+        out["eigfunc_metrics"] = acc.metrics(np.argsort(eigvals)[::-1] if sort else None)
     if post_align:
         out["eigfuncs_aligned"], out["eigvals_aligned"], out["cov_aligned"] = post_alignment(
             out["eigfuncs"], out["cov"], out["quad"])

@@ -802,6 +802,9 @@ class FusedTrainer:
     def spectrum(self, lim: float, val_eps: float, use_ema: bool = True, chunk: int = 8192):
         """Rayleigh-quotient spectrum on the uniform grid arange(-lim, lim, val_eps)^D (main_pde.py:121-130), over ALL
         heads of the model (heads sharded: a collective - call on every rank)."""
+        return self._spectrum(lim, val_eps, use_ema, chunk, None)
+
+    def _spectrum(self, lim, val_eps, use_ema, chunk, ground_truth):
         if use_ema and self._state_sharded:
             raise RuntimeError("spectrum(use_ema=True): the EMA shadow is sharded over the ranks (dp_exchange rs_ag / "
                                "a2a); call gather_optimizer_state() on every rank first")
@@ -812,17 +815,40 @@ class FusedTrainer:
             full = FlatParams(self.full_shape, self.device, with_state=False)
             full.load_state_dict(sd)
             return _spectrum_of(self.full_shape, full.pack(full.flat, True), self.problem, self.device, self.path, lim,
-                                val_eps, chunk)
+                                val_eps, chunk, ground_truth)
         return _spectrum_of(self.shape, self._ema_params if use_ema else self._params, self.problem, self.device,
-                            self.path, lim, val_eps, chunk)
+                            self.path, lim, val_eps, chunk, ground_truth)
+
+    @torch.no_grad()
+    def eigenfunction_accuracy(self, ground_truth, lim: float, val_eps: float, use_ema: bool = True,
+                               chunk: int = 8192, order=None):
+        """How well the learned functions span the analytic eigenspaces (eigfuncs.eigenfunction_metrics: per-level
+        subspace distance, per-function angle, Procrustes rotation and residual, the levels' Gram defect) on spectrum()'s
+        grid, in spectrum()'s chunk loop: the ground truths (operators.Hydrogen2D / HarmonicOscillator / InfiniteWell2D,
+        or an eigfuncs.GroundTruthTable) are evaluated and contracted on the device, chunk by chunk
+        (nsvd_eigfunc_accumulate_f64). order: a permutation of the learned columns (compute_spectrum_evd's sort=True
+        order, for one); learned column order[i] is matched with state i. The pass's spectrum rides along under
+        "eigvals". Heads sharded: a collective, as spectrum()."""
+        res = self._spectrum(lim, val_eps, use_ema, chunk, ground_truth)
+        out = res["_eig"].metrics(order)
+        out["eigvals"] = res["eigvals"].numpy()
+        return out
 
 
 @torch.no_grad()
-def _spectrum_of(shape, params, problem, device, path, lim, val_eps, chunk):
+def _spectrum_of(shape, params, problem, device, path, lim, val_eps, chunk, ground_truth=None):
     """compute_spectrum_evd's accumulation (methods/spectrum.py:56-86) for one parameter set on the uniform grid
-    arange(-lim, lim, val_eps)^D (main_pde.py:121-130)."""
+    arange(-lim, lim, val_eps)^D (main_pde.py:121-130). With a ground truth (D = 2) the eigenfunction accumulators of
+    eigfuncs.Accumulator are filled in the same loop, from the same f and the same row weighting, and returned as
+    "_eig"."""
     import numpy as np
     D, L = shape.D, shape.L
+    eig = None
+    if ground_truth is not None:
+        if D != 2:
+            raise H.NsvdError("eigenfunction accuracy: two-dimensional problems only")
+        from .eigfuncs import Accumulator
+        eig = Accumulator(ground_truth, L, device)
     with torch.cuda.device(device):
         ax = torch.from_numpy(np.arange(-lim, lim, val_eps))  # numpy's arange values (start + i * step)
         # np.meshgrid's default 'xy' indexing, flattened row-major: the reference's point order
@@ -841,12 +867,20 @@ def _spectrum_of(shape, params, problem, device, path, lim, val_eps, chunk):
                 # the accumulation kernel evaluates the Gaussian density only: the constant sqrt p_train = (2 sigma)^(-D/2)
                 # of the uniform one weights the rows here (spectrum.compute_spectrum_evd does the same)
                 sw = (2.0 * problem.sigma) ** (-0.5 * D)
-                H.spectrum_accumulate(f * sw, Tf * sw, xb, 1.0, False, lim, cov, quad)
+                f, Tf = f * sw, Tf * sw
+                H.spectrum_accumulate(f, Tf, xb, 1.0, False, lim, cov, quad)
+                if eig is not None:
+                    eig.add(f, xb, 1.0, False, lim)
                 continue
             H.spectrum_accumulate(f, Tf, xb, problem.sigma, bool(problem.use_importance), lim, cov, quad)
+            if eig is not None:
+                eig.add(f, xb, problem.sigma, bool(problem.use_importance), lim)
     n = grid.shape[0]
     cov, quad = cov.cpu() / n, quad.cpu() / n
-    return dict(cov=cov, quad=quad, eigvals=torch.diag(quad) / torch.diag(cov), norms=torch.diag(cov))
+    out = dict(cov=cov, quad=quad, eigvals=torch.diag(quad) / torch.diag(cov), norms=torch.diag(cov))
+    if eig is not None:
+        out["_eig"] = eig
+    return out
 
 
 class GraphedSteps:
