@@ -596,6 +596,37 @@ int nsvd_eigfunc_accumulate_f64(int kind, double param, const int* qnums, int Lg
                                 const float* x, int B, float sigma, int use_importance, float lim, double* gram,
                                 double* cross, double* cov, void* stream);
 
+/* ---- the same for the 3-D hydrogen atom: three quantum numbers, x (B, 3) ---------------------------------------
+ * Replaces the host evaluation of ground_truths.py's Hydrogen3D.eigfunc (:177-193) with its real spherical harmonics
+ * (real_sph_harm / sph_harm, :218-270; cartesian_to_spherical :204-209), which the reference defines and never
+ * evaluates (its validation grid stops at ndim 2), and the same (n, L) products of examples/linalg.py as above.
+ * NEW SYMBOLS ONLY: NSVD_ABI_VERSION stays 6. Entry points of their own, and a kind that is not 3: the two above keep
+ * their (Lg, 2) table and keep refusing every kind but their three with NSVD_EINVAL; these two refuse the 2-D kinds.
+ *
+ * kind: NSVD_GT_HYDROGEN3D; param: the charge Z of -lap - Z / r. qnums: HOST pointer to (Lg, 3) ints (n, l, m),
+ * 1 <= n <= 16, 0 <= l < n, |m| <= l, 1 <= Lg <= 80 (NSVD_EUNSUPPORTED above). With rho = Z r / n, a = |m|:
+ *   psi = norm rho^l exp(-rho / 2) L_{n-l-1}^(2l+1)(rho) P_l^a(z / r) ang
+ *   norm = sqrt((Z/n)^3 / (2n)) sqrt((n-l-1)! / (n+l)!) sqrt((2l+1) / (4 pi) (l-a)! / (l+a)!)
+ *   ang = 1 (m = 0), sqrt(2) cos(a phi) (m < 0), -sqrt(2) sin(a phi) (m > 0): the reference's pairing
+ * P_l^a without the Condon-Shortley phase, by its recurrence in l from P_a^a = (2a-1)!! sin^a(theta); Laguerre by its
+ * recurrence; cos / sin of a phi by the Chebyshev recurrence on x / s, y / s, s = sqrt(x^2 + y^2) (no atan2). Float32
+ * coordinates widened to float64, float64 throughout; the normalisations are computed on the host (lgamma) and travel
+ * BY VALUE in the launch arguments (80 x 24 bytes): no allocation, no copy, no synchronisation; legal on any stream
+ * and under capture. Limits, the reference's own values: at r = 0 the finite value for l = 0 and exactly 0 otherwise;
+ * on the z axis phi = 0; past rho = 1500 the value is 0, never NaN.
+ * NSVD_EINVAL: a null pointer, B, L or Lg <= 0, any other kind, param not positive and finite, a quantum number
+ * outside the ranges above. A refused call launches nothing and writes nothing. */
+#define NSVD_GT_HYDROGEN3D 8
+/* psi (B, Lg) float64 row-major: psi[b][i] = function i at x[b] (x: (B, 3) float32). */
+int nsvd_eigfunc3_eval(int kind, double param, const int* qnums, int Lg, const float* x, int B, double* psi,
+                       void* stream);
+/* nsvd_eigfunc_accumulate_f64 with x (B, 3): p_val = (2 lim)^-3 and the Gaussian density over three coordinates
+ * (w and phi exactly as nsvd_spectrum_accumulate forms them at D = 3). Everything else as there: float64 products and
+ * atomics, L <= 64, cov may be NULL, the three-way rule for use_importance. */
+int nsvd_eigfunc3_accumulate_f64(int kind, double param, const int* qnums, int Lg, const float* f, int L,
+                                 const float* x, int B, float sigma, int use_importance, float lim, double* gram,
+                                 double* cross, double* cov, void* stream);
+
 /* ---- next row: dense kernel operator on a minibatch (kernel-operator configuration) ---------------------------
  * Kf[i][l] = scale * sum_k K[rows[i]][cols[k]] f[k][l]: the (Kf, f) producer that
  * NestedLoRA.compute_loss_kernel's `get_approx_kernel_op(x)(model, x, importance)` contract consumes

@@ -26,6 +26,7 @@ PATH_GENERIC_EXACT = 4  # opt-in: the exact Laplacian (eps <= 0) on the generic 
 NORMALIZE_L2_BALL, NORMALIZE_L2_SPHERE = 0, 1
 OPT_RMSPROP, OPT_SGD, OPT_ADAM = 0, 1, 2
 GT_HYDROGEN2D, GT_HARMONIC2D, GT_WELL2D = 0, 1, 2
+GT_HYDROGEN3D = 8  # three quantum numbers, x (B, 3): nsvd_eigfunc3_* only (the 2-D entry points refuse it, and 3)
 FEATURES_READY = 0x100
 W_PLANES_READY = 0x200
 
@@ -205,6 +206,8 @@ SIGNATURES = {
     "nsvd_spectrum_accumulate_const_f64": (_I, [_P, _P, _P, _I, _I, _I, _F, _I, _F, _P, _P, _P]),
     "nsvd_eigfunc_eval": (_I, [_I, _Dbl, C.POINTER(C.c_int), _I, _P, _I, _P, _P]),
     "nsvd_eigfunc_accumulate_f64": (_I, [_I, _Dbl, C.POINTER(C.c_int), _I, _P, _I, _P, _I, _F, _I, _F, _P, _P, _P, _P]),
+    "nsvd_eigfunc3_eval": (_I, [_I, _Dbl, C.POINTER(C.c_int), _I, _P, _I, _P, _P]),
+    "nsvd_eigfunc3_accumulate_f64": (_I, [_I, _Dbl, C.POINTER(C.c_int), _I, _P, _I, _P, _I, _F, _I, _F, _P, _P, _P, _P]),
     "nsvd_step_emits_planes":(_I, [C.POINTER(ModelDesc), _I, _I]),
     "nsvd_gemm_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, C.c_long, C.c_long, C.c_long, _I, _I, _I, _I, C.c_long, _P, _P]),
     "nsvd_to_bf16": (_I, [_P, _P, _Z, _P]),

@@ -8,6 +8,7 @@
 //   cos(l th), sin(l th) from x / r, y / r by the Chebyshev recurrence (no atan2).
 // One function = its two quantum numbers and `norm`, everything in its value that does not depend on the point (the
 // host computes it with lgamma, once per call). Loop bounds are quantum numbers: no arrays, nothing indexed at run time.
+// Below them, with three quantum numbers and a table of its own: the 3-D hydrogen atom (Hydrogen3D.eigfunc :177-193).
 #pragma once
 #include <math.h>
 
@@ -135,4 +136,104 @@ NSVD_EIG_HD double nsvd_eig_eval(int kind, double param, int a, int b, double no
     if (kind == NSVD_GT_HYDROGEN2D) return nsvd_eig_hydrogen2d(param, a, b, norm, x, y);
     if (kind == NSVD_GT_HARMONIC2D) return nsvd_eig_harmonic2d(param, a, b, norm, x, y);
     return nsvd_eig_well2d(param, a, b, norm, x, y);
+}
+
+// ---- three quantum numbers: the 3-D hydrogen atom (ground_truths.py: Hydrogen3D.eigfunc :177-193, real_sph_harm /
+// sph_harm :218-270, which the reference defines and never evaluates - its validation grid stops at ndim 2). A table
+// and a fill of their own: the 2-D ones above keep their layout and keep refusing every other kind.
+struct NsvdEigFn3 {
+    int n, l, m;
+    double norm;
+};
+struct NsvdEigTable3 {
+    NsvdEigFn3 fn[NSVD_EIG_MAX_FN];
+};
+
+// Host: check (kind, param, qnums) and fill fn[0 .. Lg). kind: NSVD_GT_HYDROGEN3D only (the 2-D kinds are
+// NSVD_EINVAL here), param the charge Z, qnums (n, l, m) with 1 <= n <= NSVD_EIG_MAX_Q, 0 <= l < n, |m| <= l.
+// With a = |m|:  norm = sqrt((Z/n)^3 / (2n)) sqrt((n-l-1)! / (n+l)!) sqrt((2l+1) / (4 pi) (l-a)! / (l+a)!) (2a-1)!!
+// times the reference's pairing of the real harmonics: 1 (m = 0), sqrt(2) (m < 0, with cos(a phi)), -sqrt(2) (m > 0,
+// with sin(a phi)). (2a-1)!! is P_a^a's leading factor, (2a)! / (2^a a!).
+static inline int nsvd_eig3_table_fill(int kind, double param, const int* qnums, int Lg, NsvdEigTable3* t) {
+    if (!qnums || !t || Lg < 1 || Lg > NSVD_EIG_MAX_FN) return NSVD_EINVAL;
+    if (!(param > 0.0) || !(param < HUGE_VAL)) return NSVD_EINVAL;
+    if (kind != NSVD_GT_HYDROGEN3D) return NSVD_EINVAL;
+    const double pi = 3.14159265358979323846, ln2 = 0.69314718055994530942;
+    for (int i = 0; i < Lg; ++i) {
+        const int n = qnums[3 * i], l = qnums[3 * i + 1], m = qnums[3 * i + 2];
+        if (n < 1 || n > NSVD_EIG_MAX_Q || l < 0 || l >= n) return NSVD_EINVAL;
+        const int a = m < 0 ? -m : m;
+        if (a > l) return NSVD_EINVAL;
+        const double zn = param / n;
+        double norm = sqrt(zn * zn * zn / (2.0 * n) * (2.0 * l + 1.0) / (4.0 * pi)) *
+                      exp(0.5 * (nsvd_eig_lfact(n - l - 1) - nsvd_eig_lfact(n + l) + nsvd_eig_lfact(l - a) -
+                                 nsvd_eig_lfact(l + a)) +
+                          nsvd_eig_lfact(2 * a) - a * ln2 - nsvd_eig_lfact(a));
+        if (m) norm *= m < 0 ? 1.41421356237309504880 : -1.41421356237309504880;
+        t->fn[i].n = n;
+        t->fn[i].l = l;
+        t->fn[i].m = m;
+        t->fn[i].norm = norm;
+    }
+    return 0;
+}
+
+// psi_{n,l,m}(x, y, z) of -lap - Z / r, rho = Z r / n, a = |m|:
+//   norm rho^l exp(-rho / 2) L_{n-l-1}^(2l+1)(rho) P_l^a(z / r) {1, cos(a phi), sin(a phi)}
+// P_l^a WITHOUT the Condon-Shortley phase (the reference's lpmv carries it and real_sph_harm's sign takes it out again):
+// P_a^a = (2a-1)!! st^a, the double factorial in norm, then (j - a + 1) P_{j+1} = (2j + 1) ct P_j - (j + a) P_{j-1}.
+// cos / sin of a phi by the Chebyshev recurrence on x / s, y / s, s = sqrt(x^2 + y^2); on the z axis phi = 0
+// (arctan2(0, 0)). At r = 0 (theta = arctan2(0, 0) = 0): the finite value for l = 0, exactly 0 otherwise.
+NSVD_EIG_HD double nsvd_eig_hydrogen3d(double Z, int n, int l, int m, double norm, double x, double y, double z) {
+    const int a = m < 0 ? -m : m;
+    const double s = sqrt(x * x + y * y);
+    const double r = sqrt(x * x + y * y + z * z);
+    const double rho = Z * r / n;
+    if (rho > NSVD_EIG_HYD_TAIL) return 0.0;
+    if (l > 0 && r == 0.0) return 0.0;
+    double ct = 1.0, st = 0.0, c = 1.0, sn = 0.0;
+    if (r > 0.0) {
+        ct = z / r;
+        st = s / r;
+    }
+    if (s > 0.0) {
+        c = x / s;
+        sn = y / s;
+    }
+    double rl = 1.0;  // rho^l
+    for (int i = 0; i < l; ++i) rl *= rho;
+    // (j + 1) L_{j+1} = (2j + 1 + alpha - rho) L_j - (j + alpha) L_{j-1}, alpha = 2l + 1
+    const double alpha = 2.0 * l + 1.0;
+    double lm = 0.0, lc = 1.0;
+    for (int j = 0; j < n - l - 1; ++j) {
+        const double ln = ((2.0 * j + 1.0 + alpha - rho) * lc - (j + alpha) * lm) / (j + 1.0);
+        lm = lc;
+        lc = ln;
+    }
+    double pm = 0.0, pc = 1.0;  // P_{j-1}^a, P_j^a from j = a
+    for (int i = 0; i < a; ++i) pc *= st;
+    for (int j = a; j < l; ++j) {
+        const double pn = ((2.0 * j + 1.0) * ct * pc - (double)(j + a) * pm) / (double)(j - a + 1);
+        pm = pc;
+        pc = pn;
+    }
+    double ang = 1.0;
+    if (a > 0) {
+        double cm = 1.0, cc = c, sm = 0.0, sc = sn;  // cos / sin of (j - 1) phi and j phi
+        for (int j = 1; j < a; ++j) {
+            const double cn = 2.0 * c * cc - cm, sq = 2.0 * c * sc - sm;
+            cm = cc;
+            cc = cn;
+            sm = sc;
+            sc = sq;
+        }
+        ang = m < 0 ? cc : sc;  // (the signs and sqrt(2) are in norm)
+    }
+    return norm * rl * exp(-0.5 * rho) * lc * pc * ang;
+}
+
+NSVD_EIG_HD double nsvd_eig3_eval(int kind, double param, int n, int l, int m, double norm, double x, double y,
+                                  double z) {
+    (void)kind;  // NSVD_GT_HYDROGEN3D: the only kind nsvd_eig3_table_fill admits
+    return nsvd_eig_hydrogen3d(param, n, l, m, norm, x, y, z);
 }

@@ -11,6 +11,10 @@ the device, chunk by chunk, nothing of size n is stored or copied):
 and every metric below is host numpy float64 on those, as compute_spectrum_evd post-processes cov and quad. Lg >= L:
 the ground-truth table always ends on a level boundary, because a metric over a degenerate level needs the whole level.
 No formula assumes gram = I: the box and the grid lose part of the outer shells (``gram_defect`` says how much).
+
+Two families of ground truths: the three 2-D ones (GroundTruthTable, pairs of quantum numbers, nsvd_eigfunc_*) and the
+3-D hydrogen atom (GroundTruthTable3D, triples (n, l, m), nsvd_eigfunc3_*: Hydrogen3D.eigfunc :177-193 with the real
+spherical harmonics :218-270). Accumulator takes either; the metrics do not know the dimension.
 """
 from __future__ import annotations
 
@@ -36,9 +40,20 @@ class GroundTruthTable:
     qnums: Tuple[Tuple[int, int], ...]
     degeneracy: Tuple[int, ...]
 
+    ndim = 2  # columns of x; the entry points are nsvd_eigfunc_eval / nsvd_eigfunc_accumulate_f64
+
     @property
     def Lg(self) -> int:
         return len(self.qnums)
+
+
+@dataclass(frozen=True)
+class GroundTruthTable3D(GroundTruthTable):
+    """The same for a ground truth on R^3: ``qnums`` are triples (n, l, m), the kind is GT_HYDROGEN3D and the entry
+    points are nsvd_eigfunc3_eval / nsvd_eigfunc3_accumulate_f64. A type and a builder of its own
+    (ground_truth_table_3d): ground_truth_table and the 2-D entry points keep refusing what they refused."""
+    qnums: Tuple[Tuple[int, int, int], ...]
+    ndim = 3
 
 
 def _level_keys(gt, neigs) -> Tuple[int, float, list, list]:
@@ -51,13 +66,14 @@ def _level_keys(gt, neigs) -> Tuple[int, float, list, list]:
     if isinstance(gt, O.InfiniteWell2D):
         q = gt.get_qnums(neigs)
         return _lib.GT_WELL2D, 0.5 * float(gt.L), q, [a * a + b * b for a, b in q]
-    raise NsvdError(f"no eigenfunction formulae for {type(gt).__name__}: Hydrogen2D, HarmonicOscillator (ndim 2) and "
-                    f"InfiniteWell2D have them")
+    raise NsvdError(f"no two-dimensional eigenfunction formulae for {type(gt).__name__}: Hydrogen2D, "
+                    f"HarmonicOscillator (ndim 2) and InfiniteWell2D have them (Hydrogen3D: ground_truth_table_3d)")
 
 
 def ground_truth_table(ground_truth, L: int) -> GroundTruthTable:
     """The first Lg states of ``ground_truth``, Lg the end of the level that holds state L - 1 (hydrogen L = 16 -> 16,
-    oscillator L = 32 -> 36, L = 64 -> 66)."""
+    oscillator L = 32 -> 36, L = 64 -> 66). The three 2-D ground truths only: Hydrogen3D goes through
+    ground_truth_table_3d, and is refused here as it always was."""
     L = int(L)
     if L < 1:
         raise ValueError("L >= 1")
@@ -71,11 +87,46 @@ def ground_truth_table(ground_truth, L: int) -> GroundTruthTable:
     return GroundTruthTable(kind, param, tuple((int(a), int(b)) for a, b in q[:e]), tuple(bounds))
 
 
+def ground_truth_table_3d(ground_truth, L: int) -> GroundTruthTable3D:
+    """The first Lg states of operators.Hydrogen3D, Lg the end of the shell that holds state L - 1: the shells end at
+    1, 5, 14, 30, 55 (L = 4 -> 5, L = 16 -> 30, L = 55 -> 55); L >= 56 is refused, the n = 6 shell ends at 91 > 80."""
+    L = int(L)
+    if L < 1:
+        raise ValueError("L >= 1")
+    if not isinstance(ground_truth, O.Hydrogen3D):
+        raise NsvdError(f"no three-dimensional eigenfunction formulae for {type(ground_truth).__name__}: Hydrogen3D "
+                        f"has them")
+    bounds = [0]
+    while bounds[-1] < L:
+        bounds.append(bounds[-1] + len(bounds) ** 2)
+    if bounds[-1] > MAX_FUNCTIONS:
+        raise NsvdError(f"the level of state {L} ends past {MAX_FUNCTIONS} functions")
+    q = ground_truth.get_qnums(bounds[-1])
+    assert [n for n, _, _ in q] == [n for n in range(1, len(bounds)) for _ in range(n * n)]
+    return GroundTruthTable3D(_lib.GT_HYDROGEN3D, float(ground_truth.charge),
+                              tuple((int(n), int(l), int(m)) for n, l, m in q), tuple(bounds))
+
+
+def table_of(ground_truth, L: int) -> GroundTruthTable:
+    """a table as it is, Hydrogen3D through ground_truth_table_3d, every other ground truth through ground_truth_table"""
+    if isinstance(ground_truth, GroundTruthTable):
+        return ground_truth
+    if isinstance(ground_truth, O.Hydrogen3D):
+        return ground_truth_table_3d(ground_truth, L)
+    return ground_truth_table(ground_truth, L)
+
+
 def evaluate_host(ground_truth, qnums, x) -> np.ndarray:
     """psi (n, len(qnums)) float64 on the HOST, through the ground truth's own eigfunc (numpy): x (n, 2) in this
-    package's coordinates (the well's box is [-lim, lim]^2). The route the device evaluation replaces; kept for
-    comparison (scripts/eval_eigfuncs.py --timing) and for callers without a GPU."""
+    package's coordinates (the well's box is [-lim, lim]^2), (n, 3) for Hydrogen3D. The route the device evaluation
+    replaces; kept for comparison (scripts/eval_eigfuncs.py --timing) and for callers without a GPU."""
     x = np.asarray(x, dtype=np.float64)
+    if isinstance(ground_truth, O.Hydrogen3D):
+        if x.ndim != 2 or x.shape[1] != 3:
+            raise NsvdError("evaluate_host: Hydrogen3D takes x (n, 3)")
+        s2 = x[:, 0] ** 2 + x[:, 1] ** 2
+        r, th, ph = np.sqrt(s2 + x[:, 2] ** 2), np.arctan2(np.sqrt(s2), x[:, 2]), np.arctan2(x[:, 1], x[:, 0])
+        return np.stack([ground_truth.eigfunc(n, l, m, r, th, ph) for n, l, m in qnums], 1)
     if isinstance(ground_truth, O.Hydrogen2D):
         r, th = np.sqrt(x[:, 0] ** 2 + x[:, 1] ** 2), np.arctan2(x[:, 1], x[:, 0])
         return np.stack([ground_truth.eigfunc(n, l, r, th) for n, l in qnums], 1)
@@ -155,7 +206,7 @@ class Accumulator:
 
     def __init__(self, ground_truth, L: int, device):
         import torch
-        self.table = ground_truth if isinstance(ground_truth, GroundTruthTable) else ground_truth_table(ground_truth, L)
+        self.table = table_of(ground_truth, L)  # (2-D or 3-D: the table's type picks the entry point in add)
         Lg = self.table.Lg
         self.gram = torch.zeros((Lg, Lg), dtype=torch.float64, device=device)
         self.cross = torch.zeros((Lg, L), dtype=torch.float64, device=device)
@@ -165,7 +216,11 @@ class Accumulator:
     def add(self, f, x, sigma: float, use_importance: bool, lim: float) -> None:
         from . import hip_ops as H
         t = self.table
-        H.eigfunc_accumulate(t.kind, t.param, t.qnums, f, x, sigma, use_importance, lim, self.gram, self.cross, self.cov)
+        if x.dim() != 2 or x.shape[1] != t.ndim:
+            raise NsvdError(f"eigenfunction accuracy: a {t.ndim}-D ground truth table on points of shape "
+                            f"{tuple(x.shape)}")
+        accumulate = H.eigfunc3_accumulate if t.ndim == 3 else H.eigfunc_accumulate
+        accumulate(t.kind, t.param, t.qnums, f, x, sigma, use_importance, lim, self.gram, self.cross, self.cov)
         self.n += int(f.shape[0])
 
     def matrices(self):

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import (MASK_CUSTOM, MASK_JOINT, MASK_SEQUENTIAL, PATH_AUTO, PATH_FUSED, PATH_FUSED_BF16X3,  # noqa: F401
-                   PATH_GENERIC, PATH_GENERIC_EXACT, GT_HYDROGEN2D, GT_HARMONIC2D, GT_WELL2D,
+                   PATH_GENERIC, PATH_GENERIC_EXACT, GT_HYDROGEN2D, GT_HARMONIC2D, GT_WELL2D, GT_HYDROGEN3D,
                    BOX_EXP, BOX_NONE, BOX_SQRT, IMP_GAUSSIAN, IMP_NONE, IMP_UNIFORM, POT_HARMONIC, POT_HYDROGEN, POT_ZERO, POT_COSINE, POT_H2_ION, POT_SIN_OF_COS, POT_MOLECULE, OP_SCHROEDINGER, OP_FOKKER_PLANCK,
                    ModelDesc, NsvdError, Params, Problem, check)
 
@@ -1468,25 +1468,47 @@ def spectrum_accumulate(f: torch.Tensor, Tf: torch.Tensor, x: torch.Tensor, sigm
     check(rc, "nsvd_spectrum_accumulate")
 
 
-def _qnums_arg(qnums):
-    """(Lg, 2) quantum numbers as the HOST int array the two eigfunc entry points read during the call"""
-    q = [(int(a), int(b)) for a, b in qnums]
-    return (C.c_int * (2 * len(q)))(*[v for ab in q for v in ab]), len(q)
+def _qnums_arg(qnums, width: int = 2):
+    """(Lg, width) quantum numbers as the HOST int array the eigfunc entry points read during the call"""
+    q = [tuple(int(v) for v in row) for row in qnums]
+    if any(len(row) != width for row in q):
+        raise NsvdError(f"quantum numbers: {width} per function")
+    return (C.c_int * (width * len(q)))(*[v for row in q for v in row]), len(q)
+
+
+def _eigfunc_eval(D, kind, param, qnums, x, out):
+    name = "eigfunc_eval" if D == 2 else "eigfunc3_eval"
+    arr, Lg = _qnums_arg(qnums, D)
+    if x.dim() != 2 or x.shape[1] != D:
+        raise NsvdError(f"{name}: x must be (B, {D})")
+    if out is not None and tuple(out.shape) != (x.shape[0], Lg):
+        raise NsvdError(f"{name}: out must be ({x.shape[0]}, {Lg})")
+    psi = torch.empty((x.shape[0], Lg), dtype=torch.float64, device=x.device) if out is None else out
+    check(getattr(_lib.load(), "nsvd_" + name)(int(kind), float(param), arr, Lg, _ptr(x, "x"), x.shape[0],
+                                               _ptr(psi, "psi", torch.float64), _stream()), "nsvd_" + name)
+    return psi
+
+
+def _eigfunc_accumulate(D, kind, param, qnums, f, x, sigma, use_importance, lim, gram, cross, cov):
+    name = "eigfunc_accumulate" if D == 2 else "eigfunc3_accumulate"
+    arr, Lg = _qnums_arg(qnums, D)
+    B, L = f.shape
+    if x.dim() != 2 or tuple(x.shape) != (B, D):
+        raise NsvdError(f"{name}: x must be (B, {D}) with f's B")
+    if tuple(gram.shape) != (Lg, Lg) or tuple(cross.shape) != (Lg, L) or (cov is not None and tuple(cov.shape) != (L, L)):
+        raise NsvdError(f"{name}: gram ({Lg}, {Lg}), cross ({Lg}, {L}), cov ({L}, {L}) or None")
+    fn = "nsvd_" + name + "_f64"
+    rc = getattr(_lib.load(), fn)(int(kind), float(param), arr, Lg, _ptr(f, "f"), L, _ptr(x, "x"), B, float(sigma),
+                                  int(bool(use_importance)), float(lim), _ptr(gram, "gram", torch.float64),
+                                  _ptr(cross, "cross", torch.float64), _ptr(cov, "cov", torch.float64), _stream())
+    check(rc, fn)
 
 
 @_on_tensor_device
 def eigfunc_eval(kind: int, param: float, qnums, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """psi (B, Lg) float64: the analytic eigenfunctions `qnums` of ground truth `kind` (GT_*) at x (B, 2) float32
     (nsvd_eigfunc_eval)."""
-    arr, Lg = _qnums_arg(qnums)
-    if x.dim() != 2 or x.shape[1] != 2:
-        raise NsvdError("eigfunc_eval: x must be (B, 2)")
-    if out is not None and tuple(out.shape) != (x.shape[0], Lg):
-        raise NsvdError(f"eigfunc_eval: out must be ({x.shape[0]}, {Lg})")
-    psi = torch.empty((x.shape[0], Lg), dtype=torch.float64, device=x.device) if out is None else out
-    check(_lib.load().nsvd_eigfunc_eval(int(kind), float(param), arr, Lg, _ptr(x, "x"), x.shape[0],
-                                        _ptr(psi, "psi", torch.float64), _stream()), "nsvd_eigfunc_eval")
-    return psi
+    return _eigfunc_eval(2, kind, param, qnums, x, out)
 
 
 @_on_tensor_device
@@ -1495,17 +1517,23 @@ def eigfunc_accumulate(kind: int, param: float, qnums, f: torch.Tensor, x: torch
                        cov: Optional[torch.Tensor] = None) -> None:
     """gram (Lg, Lg) += psi_w^T psi_w, cross (Lg, L) += psi_w^T phi, cov (L, L) += phi^T phi (or None), float64, with phi
     weighted as spectrum_accumulate weights it (nsvd_eigfunc_accumulate_f64)."""
-    arr, Lg = _qnums_arg(qnums)
-    B, L = f.shape
-    if x.dim() != 2 or tuple(x.shape) != (B, 2):
-        raise NsvdError("eigfunc_accumulate: x must be (B, 2) with f's B")
-    if tuple(gram.shape) != (Lg, Lg) or tuple(cross.shape) != (Lg, L) or (cov is not None and tuple(cov.shape) != (L, L)):
-        raise NsvdError(f"eigfunc_accumulate: gram ({Lg}, {Lg}), cross ({Lg}, {L}), cov ({L}, {L}) or None")
-    rc = _lib.load().nsvd_eigfunc_accumulate_f64(int(kind), float(param), arr, Lg, _ptr(f, "f"), L, _ptr(x, "x"), B,
-                                                 float(sigma), int(bool(use_importance)), float(lim),
-                                                 _ptr(gram, "gram", torch.float64), _ptr(cross, "cross", torch.float64),
-                                                 _ptr(cov, "cov", torch.float64), _stream())
-    check(rc, "nsvd_eigfunc_accumulate_f64")
+    _eigfunc_accumulate(2, kind, param, qnums, f, x, sigma, use_importance, lim, gram, cross, cov)
+
+
+@_on_tensor_device
+def eigfunc3_eval(kind: int, param: float, qnums, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """psi (B, Lg) float64: the states `qnums` = (n, l, m) of GT_HYDROGEN3D with charge `param` at x (B, 3) float32
+    (nsvd_eigfunc3_eval)."""
+    return _eigfunc_eval(3, kind, param, qnums, x, out)
+
+
+@_on_tensor_device
+def eigfunc3_accumulate(kind: int, param: float, qnums, f: torch.Tensor, x: torch.Tensor, sigma: float,
+                        use_importance: bool, lim: float, gram: torch.Tensor, cross: torch.Tensor,
+                        cov: Optional[torch.Tensor] = None) -> None:
+    """eigfunc_accumulate for x (B, 3): p_val = (2 lim)^-3, the Gaussian weight over three coordinates
+    (nsvd_eigfunc3_accumulate_f64)."""
+    _eigfunc_accumulate(3, kind, param, qnums, f, x, sigma, use_importance, lim, gram, cross, cov)
 
 
 def profile_next_forward(ev_start: "torch.cuda.Event", ev_stop: "torch.cuda.Event") -> None:

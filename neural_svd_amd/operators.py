@@ -15,7 +15,8 @@ OperatorWrapper, get_problem, the Gaussian sampler / importance and the analytic
     Hydrogen2D / HarmonicOscillator / InfiniteWell2D    examples/operator/pde/schrodinger/ground_truths.py:40-149
       .get_qnums / .get_eigvals / .get_degeneracy / .eigfunc  (numpy float64 host mirror; the device evaluation is
                                                         nsvd_eigfunc_eval, csrc/eig_math.h)
-    Hydrogen3D.get_eigvals                              examples/operator/pde/schrodinger/ground_truths.py (3-D hydrogen)
+    Hydrogen3D                                          examples/operator/pde/schrodinger/ground_truths.py:152-193, 204-270
+      .get_qnums / .get_eigvals / .get_degeneracy / .eigfunc  (host mirror; on the device nsvd_eigfunc3_eval)
 
 These objects are DESCRIPTORS on the scripts' configuration (Gaussian or uniform sampler / importance, or none): calling
 ``operator(method, x, importance)`` forwards to the fused HIP kernel (nsvd_operator_forward). With the Laplace
@@ -515,8 +516,51 @@ class Hydrogen2D:
 
 
 class Hydrogen3D:
+    """ground_truths.py:152-193 with the real spherical harmonics of :218-270. The reference defines ``eigfunc`` and
+    never evaluates it (its validation grid stops at ndim 2); here it is the float64 host mirror of the device
+    evaluation (nsvd_eigfunc3_eval, csrc/eig_math.h): Laguerre and associated Legendre by their recurrences, no
+    scipy.special. The charge enters as the reference's a0 = 2 / Z does."""
+
     def __init__(self, charge=1.0):
         self.charge = charge
+
+    def get_qnums(self, neigs):
+        """(n, l, m): n = 1 .. ascending, l = 0 .. n - 1, m = -l .. l (ground_truths.py:157-160)"""
+        nmax = int(np.ceil(np.sqrt(neigs)))
+        return [(n, l, m) for n in range(0, nmax + 1) for l in range(0, n) for m in range(-l, l + 1)][:neigs]
+
+    def get_degeneracy(self, neigs):
+        """the reference's routine over ITS OWN get_eigvals, short lists included: (0, 1, 5, 14, 30) for neigs = 55,
+        whose eigenvalue list stops after the n = 4 shell"""
+        return _degeneracy(list(self.get_eigvals(neigs)))
+
+    def eigfunc(self, n, l, m, r, th, phi):
+        """psi_{n,l,m} at (r, th, phi) = cartesian_to_spherical(x, y, z): th = arctan2(sqrt(x^2 + y^2), z) the polar
+        angle, phi = arctan2(y, x). With rho = Z r / n, a = |m|:
+            sqrt((Z/n)^3 / (2n) (n-l-1)! / (n+l)!) rho^l exp(-rho / 2) L_{n-l-1}^(2l+1)(rho)
+            * sqrt((2l+1) / (4 pi) (l-a)! / (l+a)!) P_l^a(cos th) * {1, sqrt(2) cos(a phi) (m < 0), -sqrt(2) sin(a phi) (m > 0)}
+        P_l^a without the Condon-Shortley phase: the reference's lpmv carries it and real_sph_harm's sign removes it.
+        The pairing of negative m with the cosine is the reference's. At r = 0: 0 ** 0 = 1 for l = 0, exactly 0 otherwise."""
+        r, th, phi = (np.asarray(v, dtype=np.float64) for v in (r, th, phi))
+        n, l, m = int(n), int(l), int(m)
+        a = abs(m)
+        if not (n >= 1 and 0 <= l < n and a <= l):
+            raise ValueError("n >= 1, 0 <= l < n, |m| <= l")
+        Z, lf = float(self.charge), math.lgamma
+        rho = Z * r / n
+        radial = (math.sqrt((Z / n) ** 3 / (2 * n)) * math.exp(0.5 * (lf(n - l) - lf(n + l + 1))) * rho ** l *
+                  np.exp(-rho / 2) * _laguerre(n - l - 1, 2 * l + 1, rho))
+        ct, st = np.cos(th), np.sin(th)
+        # P_a^a = (2a-1)!! sin^a, then (j - a + 1) P_{j+1} = (2j + 1) cos P_j - (j + a) P_{j-1}
+        pm, pc = np.zeros_like(ct), math.exp(lf(2 * a + 1) - a * math.log(2.0) - lf(a + 1)) * st ** a
+        for j in range(a, l):
+            pm, pc = pc, ((2 * j + 1) * ct * pc - (j + a) * pm) / (j - a + 1)
+        ang = math.sqrt((2 * l + 1) / (4 * math.pi)) * math.exp(0.5 * (lf(l - a + 1) - lf(l + a + 1))) * pc
+        if m < 0:
+            ang = ang * math.sqrt(2.0) * np.cos(a * phi)
+        elif m > 0:
+            ang = ang * (-math.sqrt(2.0)) * np.sin(a * phi)
+        return radial * ang
 
     def get_eigvals(self, neigs):
         """E_n = -Z^2 / (4 n^2), degeneracy n^2. Like the reference the shells run over n < ceil(neigs^(1/3)) + 1 - its
@@ -613,9 +657,12 @@ class InfiniteWell2D:
 
 def ground_truth_of(args):
     """The ground truth with eigenfunction formulae that get_problem's configuration has (ndim 2: hydrogen, the
-    oscillator with get_problem's k = 1, the well with its side 2 lim); ProblemConfigError for any other."""
-    _require(getattr(args, "problem", "sch") == "sch" and args.ndim == 2,
-             "eigenfunction formulae: the 2-D Schroedinger problems only")
+    oscillator with get_problem's k = 1, the well with its side 2 lim; ndim 3: hydrogen); ProblemConfigError for any
+    other."""
+    sch = getattr(args, "problem", "sch") == "sch"
+    if sch and args.ndim == 3 and args.potential_type == "hydrogen":
+        return Hydrogen3D(charge=args.charge)
+    _require(sch and args.ndim == 2, "eigenfunction formulae: the 2-D Schroedinger problems and 3-D hydrogen only")
     if args.potential_type == "hydrogen":
         return Hydrogen2D(charge=args.charge)
     if args.potential_type == "harmonic_oscillator":

@@ -16,8 +16,9 @@ from .operators import GaussianImportance, UniformBoxImportance
 def compute_spectrum_evd(model, dataloader, operator, importance_train=None, importance_val=None,
                          set_first_mode_const=False, post_align=False, normalize=False, sort=False, gpu=None,
                          device=None, ground_truth=None):
-    """ground_truth (keyword of this package, default None: nothing changes): a 2-D ground truth of operators.py, or an
-    eigfuncs.GroundTruthTable. The eigenfunction accumulators are then filled in the same loop (nsvd_eigfunc_accumulate_f64)
+    """ground_truth (keyword of this package, default None: nothing changes): a 2-D ground truth of operators.py, or
+    Hydrogen3D with a 3-D dataloader and UniformBoxImportance(lim, 3), or an eigfuncs.GroundTruthTable(3D). The
+    eigenfunction accumulators are then filled in the same loop (nsvd_eigfunc_accumulate_f64, nsvd_eigfunc3_accumulate_f64)
     and out["eigfunc_metrics"] holds eigfuncs.eigenfunction_metrics of them, its `order` the sort=True order when
     sort is set. Not with set_first_mode_const."""
     if (gpu is None) == (device is None):

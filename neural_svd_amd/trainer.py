@@ -825,9 +825,9 @@ class FusedTrainer:
         """How well the learned functions span the analytic eigenspaces (eigfuncs.eigenfunction_metrics: per-level
         subspace distance, per-function angle, Procrustes rotation and residual, the levels' Gram defect) on spectrum()'s
         grid, in spectrum()'s chunk loop: the ground truths (operators.Hydrogen2D / HarmonicOscillator / InfiniteWell2D,
-        or an eigfuncs.GroundTruthTable) are evaluated and contracted on the device, chunk by chunk
-        (nsvd_eigfunc_accumulate_f64). order: a permutation of the learned columns (compute_spectrum_evd's sort=True
-        order, for one); learned column order[i] is matched with state i. The pass's spectrum rides along under
+        Hydrogen3D for a 3-D model, or an eigfuncs.GroundTruthTable / GroundTruthTable3D) are evaluated and contracted on
+        the device, chunk by chunk (nsvd_eigfunc_accumulate_f64, nsvd_eigfunc3_accumulate_f64). order: a permutation of
+        the learned columns (compute_spectrum_evd's sort=True order, for one); learned column order[i] is matched with state i. The pass's spectrum rides along under
         "eigvals". Heads sharded: a collective, as spectrum()."""
         res = self._spectrum(lim, val_eps, use_ema, chunk, ground_truth)
         out = res["_eig"].metrics(order)
@@ -838,17 +838,20 @@ class FusedTrainer:
 @torch.no_grad()
 def _spectrum_of(shape, params, problem, device, path, lim, val_eps, chunk, ground_truth=None):
     """compute_spectrum_evd's accumulation (methods/spectrum.py:56-86) for one parameter set on the uniform grid
-    arange(-lim, lim, val_eps)^D (main_pde.py:121-130). With a ground truth (D = 2) the eigenfunction accumulators of
+    arange(-lim, lim, val_eps)^D (main_pde.py:121-130). With a ground truth (D = 2, or Hydrogen3D at D = 3; a ground
+    truth of the other dimension is refused by name) the eigenfunction accumulators of
     eigfuncs.Accumulator are filled in the same loop, from the same f and the same row weighting, and returned as
     "_eig"."""
     import numpy as np
     D, L = shape.D, shape.L
     eig = None
     if ground_truth is not None:
-        if D != 2:
-            raise H.NsvdError("eigenfunction accuracy: two-dimensional problems only")
-        from .eigfuncs import Accumulator
-        eig = Accumulator(ground_truth, L, device)
+        from .eigfuncs import Accumulator, table_of
+        table = table_of(ground_truth, L)
+        if table.ndim != D:
+            raise H.NsvdError(f"eigenfunction accuracy: {type(ground_truth).__name__} is a {table.ndim}-D ground truth, "
+                              f"the model takes {D}-D points")
+        eig = Accumulator(table, L, device)
     with torch.cuda.device(device):
         ax = torch.from_numpy(np.arange(-lim, lim, val_eps))  # numpy's arange values (start + i * step)
         # np.meshgrid's default 'xy' indexing, flattened row-major: the reference's point order
