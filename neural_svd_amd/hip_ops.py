@@ -6,6 +6,8 @@ requires contiguous float32 tensors on a GPU and raises otherwise - there is no 
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
@@ -28,7 +30,6 @@ def torch_binding():
     HIP stream taken in C++, the same C ABI underneath) when NSVD_BINDING=torch, else None. Like the ctypes binding it
     fails loudly when its shared object is missing."""
     global _TB
-    import os
     if os.environ.get("NSVD_BINDING", "ctypes") != "torch":
         return None
     if _TB is None:
@@ -92,17 +93,47 @@ def _ptr(t: Optional[torch.Tensor], name: str = "tensor", dtype: torch.dtype = t
     return t.data_ptr()
 
 
+def _ws(t: Optional[torch.Tensor], name: str = "ws", optional: bool = False) -> Tuple[Optional[int], int]:
+    """(address, bytes) of a workspace or scratch tensor of any dtype: on the GPU and contiguous, as `_ptr` asks of
+    every other tensor; (None, 0) for an absent optional one. Size and alignment are the library's to judge."""
+    if t is None and optional:
+        return None, 0
+    if not t.is_cuda:
+        raise NsvdError(f"{name} must live on the GPU (got {t.device}); neural_svd_amd has no CPU path")
+    if not t.is_contiguous():
+        raise NsvdError(f"{name} must be contiguous")
+    return t.data_ptr(), t.nbytes
+
+
+def _u64(v) -> int:
+    """a seed or counter as the uint64 the entry points take"""
+    return int(v) & (2 ** 64 - 1)
+
+
 def _stream() -> int:
-    """The current HIP stream of the CURRENT device; every launching wrapper below runs under `_on_tensor_device`,
-    which makes the tensors' device the current one first (the C library never calls hipSetDevice)."""
+    """The current HIP stream of the CURRENT device. Read by `_call` alone; every wrapper that reaches `_call` carries
+    `@_on_tensor_device` on its def (tests/test_hip_ops_surface.py), which makes the tensors' device the current one
+    first (the C library never calls hipSetDevice)."""
     return torch.cuda.current_stream().cuda_stream
+
+
+_ENTRY: dict = {}
+
+
+def _call(name: str, *args) -> None:
+    """The one way into a launching entry point: nsvd_<name>(*args, current stream), its return code checked. (The
+    typed function is kept by name and `check` entered on failure only: this frame is on the path of every step.)"""
+    fn = _ENTRY.get(name)
+    if fn is None:
+        fn = _ENTRY[name] = getattr(_lib.load(), "nsvd_" + name)
+    rc = fn(*args, _stream())
+    if rc != 0:
+        check(rc, "nsvd_" + name)
 
 
 def _on_tensor_device(fn):
     """Run ``fn`` with the device of its GPU tensor arguments as the current device (so that `_stream()` is a stream
     of THAT device and the kernels launch where the pointers live); tensors of one call must share a device."""
-    import functools
-
     @functools.wraps(fn)
     def guarded(*args, **kwargs):
         dev = None
@@ -138,6 +169,9 @@ class ModelShape:
     box_mask: int = 0
     box_lim: float = 0.0
 
+    def __post_init__(self):
+        object.__setattr__(self, "hidden", tuple(self.hidden))  # a list would leave the shape unhashable (_desc)
+
     @property
     def dims(self) -> Tuple[int, ...]:
         return tuple(self.hidden) + (1,)
@@ -167,6 +201,17 @@ class ModelShape:
         if self.has_exp_mask:
             shapes.append((self.L,))
         return shapes
+
+
+_DESCS: dict = {}
+
+
+def _desc(shape: ModelShape):
+    """byref of shape's nsvd_model_desc, built once per shape (frozen here, const in every entry point)"""
+    ref = _DESCS.get(shape)
+    if ref is None:
+        ref = _DESCS[shape] = C.byref(shape.desc())
+    return ref
 
 
 def make_problem(potential: int, charge_or_k: float, eps: float, op_scale: float, op_shift: float, sigma: float,
@@ -242,8 +287,7 @@ def pack_params(shape: ModelShape, ws: Sequence[torch.Tensor], bs: Sequence[torc
 
 
 def workspace_bytes(shape: ModelShape, B: int) -> int:
-    d = shape.desc()
-    n = _lib.load().nsvd_workspace_bytes(C.byref(d), int(B))
+    n = _lib.load().nsvd_workspace_bytes(_desc(shape), int(B))
     if n == 0:
         raise NsvdError("nsvd_workspace_bytes: invalid model description")
     return int(n)
@@ -252,31 +296,28 @@ def workspace_bytes(shape: ModelShape, B: int) -> int:
 def path_name(shape: ModelShape, B: int, path: int = PATH_AUTO, prob: Optional[Problem] = None) -> str:
     """"fused_mfma" / "generic" / "generic_exact" (PATH_GENERIC_EXACT with eps <= 0) (/ "unsupported": e.g. the
     exact-Laplacian mode on a shape the MFMA path does not take, under any path value but PATH_GENERIC_EXACT)."""
-    d = shape.desc()
     if prob is not None:
-        return _lib.load().nsvd_path_name_for(C.byref(d), C.byref(prob), int(B), int(path)).decode()
-    return _lib.load().nsvd_path_name(C.byref(d), int(B), int(path)).decode()
+        return _lib.load().nsvd_path_name_for(_desc(shape), C.byref(prob), int(B), int(path)).decode()
+    return _lib.load().nsvd_path_name(_desc(shape), int(B), int(path)).decode()
 
 
 def step_emits_planes(shape: ModelShape, B: int, path: int) -> bool:
     """Does a fused training step on this shape and path leave the bf16 planes of the updated weights for the next
     forward (operator_forward(planes_ready=True))? PATH_FUSED_BF16X3, MFMA shapes, no batch slices."""
-    d = shape.desc()
-    return bool(_lib.load().nsvd_step_emits_planes(C.byref(d), int(B), int(path)))
+    return bool(_lib.load().nsvd_step_emits_planes(_desc(shape), int(B), int(path)))
 
 
 def new_workspace(shape: ModelShape, B: int, device) -> torch.Tensor:
     return torch.empty(workspace_bytes(shape, B), dtype=torch.uint8, device=device)
 
 
+@_on_tensor_device
 def fourier_features(x: torch.Tensor, fourier_B: torch.Tensor, eps: float, nstencil: int) -> torch.Tensor:
     B, D = x.shape
     m = fourier_B.shape[1]
     R = nstencil * B
     out = torch.empty((2 * m, R), dtype=torch.float32, device=x.device)
-    rc = _lib.load().nsvd_fourier_features(_ptr(x, "x"), _ptr(fourier_B, "fourier_B"), _ptr(out), B, D, m, float(eps),
-                                           int(nstencil), R, _stream())
-    check(rc, "nsvd_fourier_features")
+    _call("fourier_features", _ptr(x, "x"), _ptr(fourier_B, "fourier_B"), _ptr(out), B, D, m, float(eps), int(nstencil), R)
     return out
 
 
@@ -290,9 +331,7 @@ def fourier_features_jets(x: torch.Tensor, fourier_B: torch.Tensor) -> torch.Ten
         raise NsvdError(f"fourier_B must be ({D}, m), got {tuple(fourier_B.shape)}")
     R = (D + 2) * B
     out = torch.empty((2 * m, R), dtype=torch.float32, device=x.device)
-    rc = _lib.load().nsvd_fourier_features_jets(_ptr(x, "x"), _ptr(fourier_B, "fourier_B"), _ptr(out), B, D, m, R,
-                                                _stream())
-    check(rc, "nsvd_fourier_features_jets")
+    _call("fourier_features_jets", _ptr(x, "x"), _ptr(fourier_B, "fourier_B"), _ptr(out), B, D, m, R)
     return out
 
 
@@ -302,11 +341,11 @@ def softplus_jets_inplace(z: torch.Tensor, B: int, D: int) -> torch.Tensor:
     (nsvd_softplus_jets_inplace); returns z."""
     if z.dim() != 2 or z.shape[1] != (D + 2) * B:
         raise NsvdError(f"z must be (rows, {(D + 2) * B}), got {tuple(z.shape)}")
-    rc = _lib.load().nsvd_softplus_jets_inplace(_ptr(z, "z"), z.shape[0], int(B), int(D), _stream())
-    check(rc, "nsvd_softplus_jets_inplace")
+    _call("softplus_jets_inplace", _ptr(z, "z"), z.shape[0], int(B), int(D))
     return z
 
 
+@_on_tensor_device
 def operator_forward(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor, ws: torch.Tensor,
                      save_for_backward: bool = True, path: int = PATH_AUTO,
                      out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
@@ -351,96 +390,83 @@ def operator_forward(shape: ModelShape, params: Params, prob: Problem, x: torch.
         f, Tf = out
     flags = int(save_for_backward) | (_lib.FEATURES_READY if features_ready else 0) | \
         (_lib.W_PLANES_READY if planes_ready else 0)
-    if torch_binding() is not None:
-        _TB.operator_forward(_tb_shape(shape), _tb_params(shape, params), _tb_problem(prob), x, f, Tf, ws, flags,
-                             int(path))
+    tb = torch_binding()
+    if tb is not None:
+        tb.operator_forward(_tb_shape(shape), _tb_params(shape, params), _tb_problem(prob), x, f, Tf, ws, flags, int(path))
         return f, Tf
-    d = shape.desc()
-    rc = _lib.load().nsvd_operator_forward(C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(f, "f"),
-                                           _ptr(Tf, "Tf"), ws.data_ptr(), ws.numel(), flags, int(path), _stream())
-    check(rc, "nsvd_operator_forward")
+    _call("operator_forward", _desc(shape), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(f, "f"),
+          _ptr(Tf, "Tf"), *_ws(ws), flags, int(path))
     return f, Tf
 
 
+@_on_tensor_device
 def operator_features(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor, ws: torch.Tensor,
                       save_for_backward: bool = True, path: int = PATH_AUTO) -> None:
     """Weight-independent prologue of operator_forward (Fourier features of x into ws)."""
-    d = shape.desc()
-    rc = _lib.load().nsvd_operator_features(C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), x.shape[0],
-                                            ws.data_ptr(), ws.numel(), int(save_for_backward), int(path), _stream())
-    check(rc, "nsvd_operator_features")
+    _call("operator_features", _desc(shape), C.byref(params), C.byref(prob), _ptr(x, "x"), x.shape[0], *_ws(ws),
+          int(save_for_backward), int(path))
 
 
+def _sample_features(shape, params, prob, seed, offset, state, x, ws, save_for_backward, path) -> None:
+    """operator_sample_features (state None) / _dev: one entry point of the tensor binding, two of the C ABI"""
+    tb = torch_binding()
+    if tb is not None:
+        tb.operator_sample_features(_tb_shape(shape), _tb_params(shape, params), _tb_problem(prob), _u64(seed),
+                                    _u64(offset), state.buf if state is not None else None, x, ws,
+                                    bool(save_for_backward), int(path))
+        return
+    _call("operator_sample_features" if state is None else "operator_sample_features_dev", _desc(shape),
+          C.byref(params), C.byref(prob), _u64(seed), _u64(offset), *(() if state is None else (state.ptr,)),
+          _ptr(x, "x"), x.shape[0], *_ws(ws), int(bool(save_for_backward)), int(path))
+
+
+@_on_tensor_device
 def operator_sample_features(shape: ModelShape, params: Params, prob: Problem, seed: int, offset: int,
                              x: torch.Tensor, ws: torch.Tensor, save_for_backward: bool = True,
                              path: int = PATH_AUTO) -> None:
     """x <- sigma * N(0, 1) (counter-based, keyed by seed / offset) and its features into ws, one launch."""
-    B = x.shape[0]
-    if torch_binding() is not None:
-        _TB.operator_sample_features(_tb_shape(shape), _tb_params(shape, params), _tb_problem(prob),
-                                     int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), None, x, ws,
-                                     bool(save_for_backward), int(path))
-        return
-    d = shape.desc()
-    rc = _lib.load().nsvd_operator_sample_features(C.byref(d), C.byref(params), C.byref(prob),
-                                                   int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
-                                                   _ptr(x, "x"), B, ws.data_ptr(), ws.numel(),
-                                                   int(bool(save_for_backward)), int(path), _stream())
-    check(rc, "nsvd_operator_sample_features")
+    _sample_features(shape, params, prob, seed, offset, None, x, ws, save_for_backward, path)
 
 
+@_on_tensor_device
 def operator_sample_features_dev(shape: ModelShape, params: Params, prob: Problem, seed: int, offset_base: int,
                                  state: "StepState", x: torch.Tensor, ws: torch.Tensor,
                                  save_for_backward: bool = True, path: int = PATH_AUTO) -> None:
     """operator_sample_features whose batch counter is offset_base + state.step, read on the device."""
-    B = x.shape[0]
-    if torch_binding() is not None:
-        _TB.operator_sample_features(_tb_shape(shape), _tb_params(shape, params), _tb_problem(prob),
-                                     int(seed) & (2 ** 64 - 1), int(offset_base) & (2 ** 64 - 1), state.buf, x, ws,
-                                     bool(save_for_backward), int(path))
-        return
-    d = shape.desc()
-    rc = _lib.load().nsvd_operator_sample_features_dev(C.byref(d), C.byref(params), C.byref(prob),
-                                                       int(seed) & (2 ** 64 - 1), int(offset_base) & (2 ** 64 - 1),
-                                                       state.ptr, _ptr(x, "x"), B, ws.data_ptr(), ws.numel(),
-                                                       int(bool(save_for_backward)), int(path), _stream())
-    check(rc, "nsvd_operator_sample_features_dev")
+    _sample_features(shape, params, prob, seed, offset_base, state, x, ws, save_for_backward, path)
 
 
+@_on_tensor_device
 def operator_backward(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor, df: torch.Tensor,
                       grads: Params, ws: torch.Tensor, path: int = PATH_AUTO) -> None:
     B = x.shape[0]
     if tuple(df.shape) != (B, shape.L):
         raise NsvdError(f"df must be {(B, shape.L)}")
-    if torch_binding() is not None:
-        _TB.operator_backward(_tb_shape(shape), _tb_params(shape, params), _tb_problem(prob), x, df,
-                              _tb_params(shape, grads), ws, int(path))
+    tb = torch_binding()
+    if tb is not None:
+        tb.operator_backward(_tb_shape(shape), _tb_params(shape, params), _tb_problem(prob), x, df,
+                             _tb_params(shape, grads), ws, int(path))
         return
-    d = shape.desc()
-    rc = _lib.load().nsvd_operator_backward(C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B,
-                                            _ptr(df, "df"), C.byref(grads), ws.data_ptr(), ws.numel(), int(path),
-                                            _stream())
-    check(rc, "nsvd_operator_backward")
+    _call("operator_backward", _desc(shape), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(df, "df"),
+          C.byref(grads), *_ws(ws), int(path))
 
 
+@_on_tensor_device
 def model_forward(shape: ModelShape, params: Params, x: torch.Tensor, hard_mul_const: float,
                   ws: torch.Tensor, save_for_backward: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     B = x.shape[0]
     if out is None:
         out = torch.empty((B, shape.L), dtype=torch.float32, device=x.device)
-    d = shape.desc()
-    rc = _lib.load().nsvd_model_forward(C.byref(d), C.byref(params), _ptr(x, "x"), B, float(hard_mul_const),
-                                        _ptr(out), ws.data_ptr(), ws.numel(), int(save_for_backward), _stream())
-    check(rc, "nsvd_model_forward")
+    _call("model_forward", _desc(shape), C.byref(params), _ptr(x, "x"), B, float(hard_mul_const), _ptr(out), *_ws(ws),
+          int(save_for_backward))
     return out
 
 
+@_on_tensor_device
 def model_backward(shape: ModelShape, params: Params, x: torch.Tensor, dout: torch.Tensor, grads: Params,
                    ws: torch.Tensor) -> None:
-    d = shape.desc()
-    rc = _lib.load().nsvd_model_backward(C.byref(d), C.byref(params), _ptr(x, "x"), x.shape[0], _ptr(dout, "dout"),
-                                         C.byref(grads), ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_model_backward")
+    _call("model_backward", _desc(shape), C.byref(params), _ptr(x, "x"), x.shape[0], _ptr(dout, "dout"),
+          C.byref(grads), *_ws(ws))
 
 
 def evd_scratch(B: int, L: int, device) -> torch.Tensor:
@@ -448,6 +474,7 @@ def evd_scratch(B: int, L: int, device) -> torch.Tensor:
     return torch.empty(max(n, 256), dtype=torch.uint8, device=device)
 
 
+@_on_tensor_device
 def evd_moments(f: torch.Tensor, Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor],
                 moments: Optional[torch.Tensor] = None, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
     """moments = [lam_f1 (L*L) | lam_f2 (L*L) | mean_b sum_l v_l f Tf]  with f1, f2 = chunk(f, 2)."""
@@ -456,15 +483,16 @@ def evd_moments(f: torch.Tensor, Tf: torch.Tensor, mask_kind: int, v: Optional[t
         moments = torch.empty(2 * L * L + 1, dtype=torch.float32, device=f.device)
     if scratch is None:
         scratch = evd_scratch(B, L, f.device)
-    if torch_binding() is not None:
-        _TB.evd_moments(f, Tf, int(mask_kind), v, moments, scratch)
+    tb = torch_binding()
+    if tb is not None:
+        tb.evd_moments(f, Tf, int(mask_kind), v, moments, scratch)
         return moments
-    rc = _lib.load().nsvd_evd_moments(_ptr(f, "f"), _ptr(Tf, "Tf"), B, L, int(mask_kind), _ptr(v, "v"),
-                                      _ptr(moments, "moments"), scratch.data_ptr(), _stream())
-    check(rc, "nsvd_evd_moments")
+    _call("evd_moments", _ptr(f, "f"), _ptr(Tf, "Tf"), B, L, int(mask_kind), _ptr(v, "v"), _ptr(moments, "moments"),
+          _ws(scratch, "scratch")[0])
     return moments
 
 
+@_on_tensor_device
 def evd_loss_grad(f: torch.Tensor, Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor],
                   M: Optional[torch.Tensor], moments: torch.Tensor, grad_scale: float = 1.0, want_grad: bool = True,
                   loss: Optional[torch.Tensor] = None,
@@ -474,35 +502,33 @@ def evd_loss_grad(f: torch.Tensor, Tf: torch.Tensor, mask_kind: int, v: Optional
         loss = torch.empty(3, dtype=torch.float32, device=f.device)
     if want_grad and df is None:
         df = torch.empty_like(f)
-    if torch_binding() is not None:
-        _TB.evd_loss_grad(f, Tf, int(mask_kind), v, M, moments, float(grad_scale), loss, df if want_grad else None)
+    tb = torch_binding()
+    if tb is not None:
+        tb.evd_loss_grad(f, Tf, int(mask_kind), v, M, moments, float(grad_scale), loss, df if want_grad else None)
         return loss, (df if want_grad else None)
-    rc = _lib.load().nsvd_evd_loss_grad(_ptr(f, "f"), _ptr(Tf, "Tf"), B, L, int(mask_kind), _ptr(v, "v"),
-                                        _ptr(M, "M"), _ptr(moments, "moments"), float(grad_scale),
-                                        _ptr(loss, "loss"), _ptr(df, "df") if want_grad else None, _stream())
-    check(rc, "nsvd_evd_loss_grad")
+    _call("evd_loss_grad", _ptr(f, "f"), _ptr(Tf, "Tf"), B, L, int(mask_kind), _ptr(v, "v"), _ptr(M, "M"),
+          _ptr(moments, "moments"), float(grad_scale), _ptr(loss, "loss"), _ptr(df, "df") if want_grad else None)
     return loss, (df if want_grad else None)
 
 
+@_on_tensor_device
 def evd_loss_fused(f: torch.Tensor, Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor],
                    M: Optional[torch.Tensor], moments: torch.Tensor, loss: torch.Tensor, df: Optional[torch.Tensor],
                    scratch: torch.Tensor, grad_scale: float = 1.0) -> None:
     """moments + loss + d loss / d f in one call (single GPU: nothing is exchanged in between)."""
     B, L = f.shape
-    rc = _lib.load().nsvd_evd_loss_fused(_ptr(f, "f"), _ptr(Tf, "Tf"), B, L, int(mask_kind), _ptr(v, "v"),
-                                         _ptr(M, "M"), float(grad_scale), _ptr(moments, "moments"),
-                                         _ptr(loss, "loss"), _ptr(df, "df"), scratch.data_ptr(), _stream())
-    check(rc, "nsvd_evd_loss_fused")
+    _call("evd_loss_fused", _ptr(f, "f"), _ptr(Tf, "Tf"), B, L, int(mask_kind), _ptr(v, "v"), _ptr(M, "M"),
+          float(grad_scale), _ptr(moments, "moments"), _ptr(loss, "loss"), _ptr(df, "df"), _ws(scratch, "scratch")[0])
 
 
+@_on_tensor_device
 def evd_partial(f: torch.Tensor, Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor],
                 scratch: torch.Tensor) -> None:
     B, L = f.shape
-    rc = _lib.load().nsvd_evd_partial(_ptr(f, "f"), _ptr(Tf, "Tf"), B, L, int(mask_kind), _ptr(v, "v"),
-                                      scratch.data_ptr(), _stream())
-    check(rc, "nsvd_evd_partial")
+    _call("evd_partial", _ptr(f, "f"), _ptr(Tf, "Tf"), B, L, int(mask_kind), _ptr(v, "v"), _ws(scratch, "scratch")[0])
 
 
+@_on_tensor_device
 def evd_gather_heads(gathered: torch.Tensor, f: torch.Tensor, Tf: torch.Tensor, mask_kind: int,
                      v: Optional[torch.Tensor], scratch: Optional[torch.Tensor] = None) -> None:
     """gathered (world, 2, B, L_local) packed [f | Tf] blocks of the ranks -> f, Tf (B, world * L_local); with
@@ -510,12 +536,11 @@ def evd_gather_heads(gathered: torch.Tensor, f: torch.Tensor, Tf: torch.Tensor, 
     W, two, B, Ll = gathered.shape
     if two != 2 or tuple(f.shape) != (B, W * Ll) or tuple(Tf.shape) != (B, W * Ll):
         raise NsvdError("evd_gather_heads: gathered (world, 2, B, L_local), f / Tf (B, world * L_local)")
-    rc = _lib.load().nsvd_evd_gather_heads(_ptr(gathered, "gathered"), int(W), int(B), int(Ll), int(mask_kind),
-                                           _ptr(v, "v"), _ptr(f, "f"), _ptr(Tf, "Tf"),
-                                           scratch.data_ptr() if scratch is not None else None, _stream())
-    check(rc, "nsvd_evd_gather_heads")
+    _call("evd_gather_heads", _ptr(gathered, "gathered"), int(W), int(B), int(Ll), int(mask_kind), _ptr(v, "v"),
+          _ptr(f, "f"), _ptr(Tf, "Tf"), _ws(scratch, "scratch", True)[0])
 
 
+@_on_tensor_device
 def evd_gather_head_blocks(gathered: torch.Tensor, L: int, f: torch.Tensor, Tf: torch.Tensor, mask_kind: int,
                            v: Optional[torch.Tensor], scratch: Optional[torch.Tensor] = None) -> None:
     """gathered (world, 2 * B * ceil(L / world)): rank w's block begins with its packed f (B, n_w) | Tf (B, n_w),
@@ -525,10 +550,8 @@ def evd_gather_head_blocks(gathered: torch.Tensor, L: int, f: torch.Tensor, Tf: 
     Lb = -(-int(L) // W)
     if gathered.dim() != 2 or gathered.shape[1] != 2 * B * Lb or tuple(f.shape) != (B, L) or tuple(Tf.shape) != (B, L):
         raise NsvdError("evd_gather_head_blocks: gathered (world, 2 B ceil(L / world)), f / Tf (B, L)")
-    rc = _lib.load().nsvd_evd_gather_head_blocks(_ptr(gathered, "gathered"), int(W), int(B), int(L), int(mask_kind),
-                                                 _ptr(v, "v"), _ptr(f, "f"), _ptr(Tf, "Tf"),
-                                                 scratch.data_ptr() if scratch is not None else None, _stream())
-    check(rc, "nsvd_evd_gather_head_blocks")
+    _call("evd_gather_head_blocks", _ptr(gathered, "gathered"), int(W), int(B), int(L), int(mask_kind), _ptr(v, "v"),
+          _ptr(f, "f"), _ptr(Tf, "Tf"), _ws(scratch, "scratch", True)[0])
 
 
 def _evd_check(complaint: str, shape: ModelShape, x: torch.Tensor, f: torch.Tensor, Tf: torch.Tensor,
@@ -545,20 +568,19 @@ def _evd_args(shape: ModelShape, params: Params, prob: Optional[Problem], x, f, 
               moments_reduced, evd_scratch, l_offset, grad_scale, loss, grads: Optional[Params]) -> tuple:
     """The arguments every EVD-backward entry point begins with (include/nsvd.h): desc, params, prob (the model's own
     entry point, prob None, has none), x .. loss, grads."""
-    d = shape.desc()
-    return (C.byref(d), C.byref(params)) + ((C.byref(prob),) if prob is not None else ()) + (
+    return (_desc(shape), C.byref(params)) + ((C.byref(prob),) if prob is not None else ()) + (
         _ptr(x, "x"), x.shape[0], _ptr(f, "f"), _ptr(Tf, "Tf"), int(mask_kind), _ptr(v, "v"), _ptr(M, "M"),
-        _ptr(moments, "moments"), int(bool(moments_reduced)),
-        evd_scratch.data_ptr() if evd_scratch is not None else None, int(f.shape[1]), int(l_offset), float(grad_scale),
-        _ptr(loss, "loss"), C.byref(grads) if grads is not None else None)
+        _ptr(moments, "moments"), int(bool(moments_reduced)), _ws(evd_scratch, "evd_scratch", True)[0],
+        int(f.shape[1]), int(l_offset), float(grad_scale), _ptr(loss, "loss"),
+        C.byref(grads) if grads is not None else None)
 
 
 def _next_args(next_seed: int, next_offset: int, x_next: Optional[torch.Tensor], ws_next: Optional[torch.Tensor]) -> tuple:
     """next_seed, next_offset, x_next, ws_next, ws_next_bytes of the entry points a next batch can ride in"""
-    return (int(next_seed) & (2 ** 64 - 1), int(next_offset) & (2 ** 64 - 1), _ptr(x_next, "x_next"),
-            ws_next.data_ptr() if ws_next is not None else None, ws_next.numel() if ws_next is not None else 0)
+    return (_u64(next_seed), _u64(next_offset), _ptr(x_next, "x_next"), *_ws(ws_next, "ws_next", True))
 
 
+@_on_tensor_device
 def operator_backward_evd(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor, f: torch.Tensor,
                           Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor], M: Optional[torch.Tensor],
                           moments: torch.Tensor, moments_reduced: bool, evd_scratch: Optional[torch.Tensor],
@@ -567,17 +589,16 @@ def operator_backward_evd(shape: ModelShape, params: Params, prob: Problem, x: t
     """loss gradient + operator backward in one call (d loss / d f is never materialised).
     f, Tf: (B, L_total) with L_total >= shape.L; this model owns heads [l_offset, l_offset + shape.L)."""
     _evd_check("operator_backward_evd: f/Tf must be (B, L_total), moments 2*L_total^2+1", shape, x, f, Tf, moments)
-    rc = _lib.load().nsvd_operator_backward_evd(
-        *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
-                   grad_scale, loss, grads), ws.data_ptr(), ws.numel(), int(path), _stream())
-    check(rc, "nsvd_operator_backward_evd")
+    _call("operator_backward_evd",
+          *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                     grad_scale, loss, grads), *_ws(ws), int(path))
 
 
 def backward_head_window_ok(shape: ModelShape, prob: Problem, B: int, path: int, l_count: int) -> bool:
-    d = shape.desc()
-    return bool(_lib.load().nsvd_backward_head_window_ok(C.byref(d), C.byref(prob), int(B), int(path), int(l_count)))
+    return bool(_lib.load().nsvd_backward_head_window_ok(_desc(shape), C.byref(prob), int(B), int(path), int(l_count)))
 
 
+@_on_tensor_device
 def operator_backward_evd_heads(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor, f: torch.Tensor,
                                 Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor],
                                 M: Optional[torch.Tensor], moments: torch.Tensor, moments_reduced: bool,
@@ -586,15 +607,14 @@ def operator_backward_evd_heads(shape: ModelShape, params: Params, prob: Problem
                                 path: int = PATH_AUTO, l_offset: int = 0) -> None:
     """operator_backward_evd for the heads [l_begin, l_begin + l_count) only (the other gradients are untouched)."""
     _evd_check("operator_backward_evd_heads: f/Tf must be (B, L_total), moments 2*L_total^2+1", shape, x, f, Tf, moments)
-    rc = _lib.load().nsvd_operator_backward_evd_heads(
-        *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
-                   grad_scale, loss, grads), ws.data_ptr(), ws.numel(), int(path), int(l_begin), int(l_count), _stream())
-    check(rc, "nsvd_operator_backward_evd_heads")
+    _call("operator_backward_evd_heads",
+          *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                     grad_scale, loss, grads), *_ws(ws), int(path), int(l_begin), int(l_count))
 
 
 class _DeviceSchedule:
     """What StepState and OptState share: the device buffer of the library's struct (host mirror `_mirror`), and the
-    library's `_entry`_init (through the subclass' `_init`) / `_entry`_begin on it."""
+    library's nsvd_`_entry`_init (with the subclass' `_init_args`) / nsvd_`_entry`_begin on it."""
     _mirror: type = None
     _entry: str = ""
 
@@ -608,12 +628,12 @@ class _DeviceSchedule:
 
     def reset(self, step: int) -> None:
         with torch.cuda.device(self.buf.device):
-            check(self._init(_lib.load(), int(step)), self._entry + "_init")
+            _call(self._entry + "_init", self.ptr, *self._init_args(int(step)))
 
     def begin(self) -> None:
         """cur <- the scheduled values of step `step` (loop bodies whose first backward kernel does not do it)"""
         with torch.cuda.device(self.buf.device):
-            check(getattr(_lib.load(), self._entry + "_begin")(self.ptr, _stream()), self._entry + "_begin")
+            _call(self._entry + "_begin", self.ptr)
 
     def read(self):
         """host copy, as the `_lib` mirror of the struct (synchronises)"""
@@ -624,16 +644,15 @@ class StepState(_DeviceSchedule):
     """The device-resident schedule state (include/nsvd.h: nsvd_step_state): step counter, CosineAnnealingLR /
     RMSprop / torch_ema constants and the scheduled values of the step being taken, in DEVICE memory - what lets a
     captured training step replay along the schedule (examples/operator/__init__.py:69-73)."""
-    _mirror, _entry = _lib.StepState, "nsvd_step_state"
+    _mirror, _entry = _lib.StepState, "step_state"
 
     def __init__(self, device, lr0: float, T_max: int, alpha: float, eps: float, ema_decay: float, eta_min: float = 0.0,
                  step: int = 0):
         self.args = (float(lr0), float(eta_min), int(T_max), float(alpha), float(eps), float(ema_decay))
         super().__init__(device, step)
 
-    def _init(self, lib, step: int) -> int:
-        lr0, eta_min, T_max, alpha, eps, ema_decay = self.args
-        return lib.nsvd_step_state_init(self.ptr, lr0, eta_min, T_max, alpha, eps, ema_decay, step, _stream())
+    def _init_args(self, step: int) -> tuple:
+        return self.args + (step,)
 
 
 def rmsprop_state(sq: Params, ema: Optional[Params], lr: float, alpha: float, eps: float,
@@ -664,9 +683,10 @@ def _tb_evd_step(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moment
                                    int(mask_kind), v, M, moments, bool(moments_reduced), evd_scratch, int(l_offset),
                                    float(grad_scale), loss, _tb_params(shape, grads) if grads is not None else None,
                                    _tb_rmsprop(shape, opt), ws, int(path), x_next, ws_next,
-                                   int(next_seed) & (2 ** 64 - 1), int(next_offset) & (2 ** 64 - 1))
+                                   _u64(next_seed), _u64(next_offset))
 
 
+@_on_tensor_device
 def operator_backward_evd_step(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor, f: torch.Tensor,
                                Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor],
                                M: Optional[torch.Tensor], moments: torch.Tensor, moments_reduced: bool,
@@ -679,12 +699,12 @@ def operator_backward_evd_step(shape: ModelShape, params: Params, prob: Problem,
         _tb_evd_step(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
                      grad_scale, loss, grads, opt, ws, path, None, None, 0, 0)
         return
-    rc = _lib.load().nsvd_operator_backward_evd_step(
-        *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
-                   grad_scale, loss, grads), C.byref(opt), ws.data_ptr(), ws.numel(), int(path), _stream())
-    check(rc, "nsvd_operator_backward_evd_step")
+    _call("operator_backward_evd_step",
+          *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                     grad_scale, loss, grads), C.byref(opt), *_ws(ws), int(path))
 
 
+@_on_tensor_device
 def operator_backward_evd_step_window(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor,
                                       f: torch.Tensor, Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor],
                                       M: Optional[torch.Tensor], moments: Optional[torch.Tensor], moments_reduced: bool,
@@ -702,13 +722,13 @@ def operator_backward_evd_step_window(shape: ModelShape, params: Params, prob: P
         if ev_after_chain.cuda_event == 0:  # torch creates the hipEvent lazily, at the first record
             ev_after_chain.record()
         ev = ev_after_chain.cuda_event
-    rc = _lib.load().nsvd_operator_backward_evd_step_window(
-        *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
-                   grad_scale, loss, None), C.byref(opt), ws.data_ptr(), ws.numel(), int(path), int(l_begin),
-        int(l_count), int(bool(last_window)), ev, *_next_args(next_seed, next_offset, x_next, ws_next), _stream())
-    check(rc, "nsvd_operator_backward_evd_step_window")
+    _call("operator_backward_evd_step_window",
+          *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                     grad_scale, loss, None), C.byref(opt), *_ws(ws), int(path), int(l_begin), int(l_count),
+          int(bool(last_window)), ev, *_next_args(next_seed, next_offset, x_next, ws_next))
 
 
+@_on_tensor_device
 def operator_backward_evd_step_next(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor,
                                     f: torch.Tensor, Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor],
                                     M: Optional[torch.Tensor], moments: torch.Tensor, moments_reduced: bool,
@@ -725,11 +745,10 @@ def operator_backward_evd_step_next(shape: ModelShape, params: Params, prob: Pro
         _tb_evd_step(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
                      grad_scale, loss, grads, opt, ws, path, x_next, ws_next, next_seed, next_offset)
         return
-    rc = _lib.load().nsvd_operator_backward_evd_step_next(
-        *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
-                   grad_scale, loss, grads), C.byref(opt), ws.data_ptr(), ws.numel(), int(path),
-        *_next_args(next_seed, next_offset, x_next, ws_next), _stream())
-    check(rc, "nsvd_operator_backward_evd_step_next")
+    _call("operator_backward_evd_step_next",
+          *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                     grad_scale, loss, grads), C.byref(opt), *_ws(ws), int(path),
+          *_next_args(next_seed, next_offset, x_next, ws_next))
 
 
 def optimizer_state(cfg: "_lib.OptConfig", sq: Optional[Params], mom: Optional[Params], ema: Optional[Params],
@@ -757,6 +776,7 @@ def optimizer_state(cfg: "_lib.OptConfig", sq: Optional[Params], mom: Optional[P
     return o
 
 
+@_on_tensor_device
 def operator_backward_evd_opt_step(shape: ModelShape, params: Params, prob: Problem, x: torch.Tensor,
                                    f: torch.Tensor, Tf: torch.Tensor, mask_kind: int, v: Optional[torch.Tensor],
                                    M: Optional[torch.Tensor], moments: Optional[torch.Tensor], moments_reduced: bool,
@@ -770,13 +790,13 @@ def operator_backward_evd_opt_step(shape: ModelShape, params: Params, prob: Prob
     _evd_check(complaint, shape, x, f, Tf, moments)
     if x_next is not None and (ws_next is None or tuple(x_next.shape) != tuple(x.shape)):
         raise NsvdError(complaint)
-    rc = _lib.load().nsvd_operator_backward_evd_opt_step(
-        *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
-                   grad_scale, loss, grads), C.byref(opt), ws.data_ptr(), ws.numel(), int(path),
-        *_next_args(next_seed, next_offset, x_next, ws_next), _stream())
-    check(rc, "nsvd_operator_backward_evd_opt_step")
+    _call("operator_backward_evd_opt_step",
+          *_evd_args(shape, params, prob, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                     grad_scale, loss, grads), C.byref(opt), *_ws(ws), int(path),
+          *_next_args(next_seed, next_offset, x_next, ws_next))
 
 
+@_on_tensor_device
 def model_backward_evd_step(shape: ModelShape, params: Params, x: torch.Tensor, f: torch.Tensor, Tf: torch.Tensor,
                             mask_kind: int, v: Optional[torch.Tensor], M: Optional[torch.Tensor],
                             moments: torch.Tensor, moments_reduced: bool, evd_scratch: Optional[torch.Tensor],
@@ -788,22 +808,20 @@ def model_backward_evd_step(shape: ModelShape, params: Params, x: torch.Tensor, 
     B, L = f.shape
     if tuple(Tf.shape) != (B, L) or L < l_offset + shape.L or x.shape[0] != B or moments.numel() != 2 * L * L + 1:
         raise NsvdError("model_backward_evd_step: f, Tf (B, L_total); moments 2 L_total^2 + 1")
-    rc = _lib.load().nsvd_model_backward_evd_step(
-        *_evd_args(shape, params, None, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
-                   grad_scale, loss, grads), C.byref(opt) if opt is not None else None, ws.data_ptr(), ws.numel(),
-        _stream())
-    check(rc, "nsvd_model_backward_evd_step")
+    _call("model_backward_evd_step",
+          *_evd_args(shape, params, None, x, f, Tf, mask_kind, v, M, moments, moments_reduced, evd_scratch, l_offset,
+                     grad_scale, loss, grads), C.byref(opt) if opt is not None else None, *_ws(ws))
 
 
 def model_workspace(shape: ModelShape, B: int, device) -> torch.Tensor:
     """workspace of model_forward / model_backward alone (no stencil rows; input dimension up to 64)."""
-    d = shape.desc()
-    n = _lib.load().nsvd_model_workspace_bytes(C.byref(d), int(B))
+    n = _lib.load().nsvd_model_workspace_bytes(_desc(shape), int(B))
     if n == 0:
         raise NsvdError("nsvd_model_workspace_bytes: invalid model description")
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
+@_on_tensor_device
 def kernel_apply(K: torch.Tensor, N: int, rows: torch.Tensor, cols: torch.Tensor, f: torch.Tensor, scale: float,
                  ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Kf = scale * K[rows][:, cols] @ f on the MFMA. K: (N_rows >= N, ldk) float32 with ldk >= N rounded up to 64;
@@ -817,14 +835,12 @@ def kernel_apply(K: torch.Tensor, N: int, rows: torch.Tensor, cols: torch.Tensor
     if f.dim() != 2 or f.shape[0] != B2:
         raise NsvdError("kernel_apply: f must be (len(cols), L)")
     L = f.shape[1]
-    lib = _lib.load()
     if ws is None:
-        ws = torch.empty(lib.nsvd_kernel_apply_workspace_bytes(int(N), B1, L), dtype=torch.uint8, device=f.device)
+        ws = torch.empty(_lib.load().nsvd_kernel_apply_workspace_bytes(int(N), B1, L), dtype=torch.uint8, device=f.device)
     if out is None:
         out = torch.empty((B1, L), dtype=torch.float32, device=f.device)
-    rc = lib.nsvd_kernel_apply(K.data_ptr(), K.stride(0), int(N), rows.data_ptr(), B1, cols.data_ptr(), B2,
-                               _ptr(f, "f"), L, float(scale), _ptr(out, "out"), ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_kernel_apply")
+    _call("kernel_apply", K.data_ptr(), K.stride(0), int(N), rows.data_ptr(), B1, cols.data_ptr(), B2, _ptr(f, "f"), L,
+          float(scale), _ptr(out, "out"), *_ws(ws))
     return out
 
 
@@ -848,9 +864,9 @@ def _apply_pair_partition(name: str, B1: int, B2: int, D: int, L: int) -> Tuple[
     return rg.value, cs.value
 
 
-def _apply_ws(lib, name: str, B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
+def _apply_ws(name: str, B1: int, B2: int, D: int, L: int, device) -> torch.Tensor:
     # (an unsupported shape has no workspace: the entry point itself refuses it, with its own code)
-    n = getattr(lib, f"nsvd_{name}_workspace_bytes")(B1, B2, D, L)
+    n = getattr(_lib.load(), f"nsvd_{name}_workspace_bytes")(B1, B2, D, L)
     return torch.empty(max(n, 256), dtype=torch.uint8, device=device)
 
 
@@ -867,21 +883,19 @@ def _apply(name: str, x, y, f, kind: int, params: tuple, ptypes: tuple, scale: f
     if tuple(y.shape) != (B2, D):
         raise NsvdError(f"{name}: y must be (len(f), D) with x's D")
     xp, yp, fp = _ptr(x, "x"), _ptr(y, "y"), _ptr(f, "f")
-    lib = _lib.load()
     if out is None:
         out = torch.empty((B1, L), dtype=torch.float32, device=f.device)
     elif tuple(out.shape) != (B1, L):
         raise NsvdError(f"{name}: out must be (len(x), L)")
     op = _ptr(out, "out")
     if ws is None:
-        ws = _apply_ws(lib, name, B1, B2, D, L, f.device)
+        ws = _apply_ws(name, B1, B2, D, L, f.device)
     params = tuple(t(v) for t, v in zip(ptypes, params))
-    if torch_binding() is not None:
-        getattr(_TB, name)(x, y, f, int(kind), *params, float(scale), out, ws)
+    tb = torch_binding()
+    if tb is not None:
+        getattr(tb, name)(x, y, f, int(kind), *params, float(scale), out, ws)
         return out
-    rc = getattr(lib, f"nsvd_{name}")(xp, B1, yp, B2, D, fp, L, int(kind), *params, float(scale), op, ws.data_ptr(),
-                                      ws.numel(), _stream())
-    check(rc, f"nsvd_{name}")
+    _call(name, xp, B1, yp, B2, D, fp, L, int(kind), *params, float(scale), op, *_ws(ws))
     return out
 
 
@@ -898,7 +912,6 @@ def _apply_pair(name: str, x, y, g, f, kind: int, params: tuple, ptypes: tuple, 
     if tuple(f.shape) != (B1, L):
         raise NsvdError(f"{name}: f must be (len(x), L) with g's L")
     xp, yp, gp, fp = _ptr(x, "x"), _ptr(y, "y"), _ptr(g, "g"), _ptr(f, "f")
-    lib = _lib.load()
     if out_x is None:
         out_x = torch.empty((B1, L), dtype=torch.float32, device=g.device)
     elif tuple(out_x.shape) != (B1, L):
@@ -909,14 +922,13 @@ def _apply_pair(name: str, x, y, g, f, kind: int, params: tuple, ptypes: tuple, 
         raise NsvdError(f"{name}: out_y must be (len(y), L)")
     ox, oy = _ptr(out_x, "out_x"), _ptr(out_y, "out_y")
     if ws is None:
-        ws = _apply_ws(lib, name, B1, B2, D, L, g.device)
+        ws = _apply_ws(name, B1, B2, D, L, g.device)
     params = tuple(t(v) for t, v in zip(ptypes, params))
-    if torch_binding() is not None:
-        getattr(_TB, name)(x, y, g, f, int(kind), *params, float(scale_g), float(scale_f), out_x, out_y, ws)
+    tb = torch_binding()
+    if tb is not None:
+        getattr(tb, name)(x, y, g, f, int(kind), *params, float(scale_g), float(scale_f), out_x, out_y, ws)
         return out_x, out_y
-    rc = getattr(lib, f"nsvd_{name}")(xp, B1, yp, B2, D, gp, fp, L, int(kind), *params, float(scale_g), float(scale_f),
-                                      ox, oy, ws.data_ptr(), ws.numel(), _stream())
-    check(rc, f"nsvd_{name}")
+    _call(name, xp, B1, yp, B2, D, gp, fp, L, int(kind), *params, float(scale_g), float(scale_f), ox, oy, *_ws(ws))
     return out_x, out_y
 
 
@@ -924,6 +936,7 @@ def rbf_apply_workspace(B1: int, B2: int, D: int, L: int, device) -> torch.Tenso
     return _apply_workspace("rbf_apply", B1, B2, D, L, device)
 
 
+@_on_tensor_device
 def rbf_apply(x: torch.Tensor, y: torch.Tensor, f: torch.Tensor, kind: int, ell: float, scale: float,
               ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[i] = scale * sum_j k(|x_i - y_j|) f[j] without the (B1, B2) kernel matrix (nsvd_rbf_apply). kind:
@@ -942,6 +955,7 @@ def rbf_apply_pair_partition(B1: int, B2: int, D: int, L: int) -> Tuple[int, int
     return _apply_pair_partition("rbf_apply_pair", B1, B2, D, L)
 
 
+@_on_tensor_device
 def rbf_apply_pair(x: torch.Tensor, y: torch.Tensor, g: torch.Tensor, f: torch.Tensor, kind: int, ell: float,
                    scale_g: float, scale_f: float, ws: Optional[torch.Tensor] = None,
                    out_x: Optional[torch.Tensor] = None, out_y: Optional[torch.Tensor] = None):
@@ -960,6 +974,7 @@ def dot_apply_workspace(B1: int, B2: int, D: int, L: int, device) -> torch.Tenso
     return _apply_workspace("dot_apply", B1, B2, D, L, device)
 
 
+@_on_tensor_device
 def dot_apply(x: torch.Tensor, y: torch.Tensor, f: torch.Tensor, kind: int, gamma: float, coef0: float, degree: int,
               scale: float, ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[i] = scale * sum_j k(x_i, y_j) f[j] without the (B1, B2) kernel matrix (nsvd_dot_apply). kind:
@@ -982,6 +997,7 @@ def dot_apply_pair_partition(B1: int, B2: int, D: int, L: int) -> Tuple[int, int
     return _apply_pair_partition("dot_apply_pair", B1, B2, D, L)
 
 
+@_on_tensor_device
 def dot_apply_pair(x: torch.Tensor, y: torch.Tensor, g: torch.Tensor, f: torch.Tensor, kind: int, gamma: float,
                    coef0: float, degree: int, scale_g: float, scale_f: float, ws: Optional[torch.Tensor] = None,
                    out_x: Optional[torch.Tensor] = None, out_y: Optional[torch.Tensor] = None):
@@ -1030,7 +1046,6 @@ def _gram(fn: str, X: torch.Tensor, Y: Optional[torch.Tensor], outs, use, ws: Op
         yp, ldy = _rows_ptr(Y, "Y")
     elif not use[0]:
         raise NsvdError(f"{name}: nothing to compute")
-    lib = _lib.load()
     names = ("out_xtx", "out_xty", "out_yty")
     outs = [torch.empty((m, m), dtype=f64, device=X.device) if o is None and u and (i == 0 or Y is not None) else o
             for i, (o, u) in enumerate(zip(outs, use))]
@@ -1038,11 +1053,10 @@ def _gram(fn: str, X: torch.Tensor, Y: Optional[torch.Tensor], outs, use, ws: Op
         if o is not None and tuple(o.shape) != (m, m):
             raise NsvdError(f"{name}: {nm} must be (m, m)")
     if ws is None:
-        ws = torch.empty(max(getattr(lib, fn + "_workspace_bytes")(n, m), 256), dtype=torch.uint8, device=X.device)
+        ws = torch.empty(max(getattr(_lib.load(), fn + "_workspace_bytes")(n, m), 256), dtype=torch.uint8,
+                         device=X.device)
     outs = [o if u else None for o, u in zip(outs, use)]
-    rc = getattr(lib, fn)(xp, ldx, yp, ldy, n, m, *(_ptr(o, nm, f64) for o, nm in zip(outs, names)), ws.data_ptr(),
-                          ws.numel(), _stream())
-    check(rc, fn)
+    _call(name, xp, ldx, yp, ldy, n, m, *(_ptr(o, nm, f64) for o, nm in zip(outs, names)), *_ws(ws))
     return outs
 
 
@@ -1050,6 +1064,7 @@ def tsgram_workspace(n: int, m: int, device) -> torch.Tensor:
     return _gram_workspace("nsvd_tsgram_f64", n, m, device)
 
 
+@_on_tensor_device
 def tsgram_f64(X: torch.Tensor, Y: Optional[torch.Tensor] = None, xtx: bool = True, ws: Optional[torch.Tensor] = None,
                out_xtx: Optional[torch.Tensor] = None, out_xty: Optional[torch.Tensor] = None):
     """(X^T X, X^T Y) as (m, m) float64 from (n, m) float32 blocks (nsvd_tsgram_f64): products and sums in float64, no
@@ -1057,6 +1072,7 @@ def tsgram_f64(X: torch.Tensor, Y: Optional[torch.Tensor] = None, xtx: bool = Tr
     return tuple(_gram("nsvd_tsgram_f64", X, Y, (out_xtx, out_xty), (xtx, True), ws))
 
 
+@_on_tensor_device
 def ritz_step_f64(S: torch.Tensor, A: Optional[torch.Tensor], status: torch.Tensor,
                   theta: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
                   Q: Optional[torch.Tensor] = None, T: Optional[torch.Tensor] = None,
@@ -1081,14 +1097,12 @@ def ritz_step_f64(S: torch.Tensor, A: Optional[torch.Tensor], status: torch.Tens
     if status.numel() < 1:
         raise NsvdError("ritz_step_f64: status must hold one int32")
     f64 = torch.float64
-    rc = _lib.load().nsvd_ritz_step_f64(_ptr(S, "S", f64), _ptr(A, "A", f64), _ptr(C, "C", f64), m,
-                                        _ptr(theta, "theta", f64),
-                                        _ptr(resid, "resid", f64), _ptr(Q, "Q", f64), _ptr(T, "T", f64),
-                                        _ptr(status, "status", torch.int32), _stream())
-    check(rc, "nsvd_ritz_step_f64")
+    _call("ritz_step_f64", _ptr(S, "S", f64), _ptr(A, "A", f64), _ptr(C, "C", f64), m, _ptr(theta, "theta", f64),
+          _ptr(resid, "resid", f64), _ptr(Q, "Q", f64), _ptr(T, "T", f64), _ptr(status, "status", torch.int32))
     return theta, resid, Q, T
 
 
+@_on_tensor_device
 def ts_rotate(X: torch.Tensor, T: torch.Tensor, k: Optional[int] = None,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out (n, k) = X (n, m) @ T[:, :k] with T (m, m) float64, accumulated in float64 and rounded once to float32
@@ -1107,8 +1121,7 @@ def ts_rotate(X: torch.Tensor, T: torch.Tensor, k: Optional[int] = None,
         raise NsvdError("ts_rotate: out must not alias X")
     if T.dtype != torch.float64 or not T.is_cuda:
         raise NsvdError("ts_rotate: T must be a float64 GPU tensor")
-    rc = _lib.load().nsvd_ts_rotate(xp, ldx, n, m, T.data_ptr(), T.stride(0), k, op, ldo, _stream())
-    check(rc, "nsvd_ts_rotate")
+    _call("ts_rotate", xp, ldx, n, m, T.data_ptr(), T.stride(0), k, op, ldo)
     return out
 
 
@@ -1117,6 +1130,7 @@ def tsgram3_workspace(n: int, m: int, device) -> torch.Tensor:
     return _gram_workspace("nsvd_tsgram3_f64", n, m, device)
 
 
+@_on_tensor_device
 def tsgram3_f64(X: torch.Tensor, Y: torch.Tensor, ws: Optional[torch.Tensor] = None,
                 out_xtx: Optional[torch.Tensor] = None, out_xty: Optional[torch.Tensor] = None,
                 out_yty: Optional[torch.Tensor] = None):
@@ -1125,6 +1139,7 @@ def tsgram3_f64(X: torch.Tensor, Y: torch.Tensor, ws: Optional[torch.Tensor] = N
     return tuple(_gram("nsvd_tsgram3_f64", X, Y, (out_xtx, out_xty, out_yty), (True, True, True), ws))
 
 
+@_on_tensor_device
 def svd_ritz_step_f64(PtU: torch.Tensor, RtV: torch.Tensor, Sp: torch.Tensor, Sr: torch.Tensor, status: torch.Tensor,
                       Cu: Optional[torch.Tensor] = None, Cv: Optional[torch.Tensor] = None,
                       sigma: Optional[torch.Tensor] = None, resid_l: Optional[torch.Tensor] = None,
@@ -1152,13 +1167,10 @@ def svd_ritz_step_f64(PtU: torch.Tensor, RtV: torch.Tensor, Sp: torch.Tensor, Sr
         raise NsvdError("svd_ritz_step_f64: sigma, resid_l, resid_r (m); A, B, Tu, Tv (m, m)")
     if status.numel() < 1:
         raise NsvdError("svd_ritz_step_f64: status must hold one int32")
-    rc = _lib.load().nsvd_svd_ritz_step_f64(_ptr(PtU, "PtU", f64), _ptr(RtV, "RtV", f64), _ptr(Sp, "Sp", f64),
-                                            _ptr(Sr, "Sr", f64), _ptr(Cu, "Cu", f64), _ptr(Cv, "Cv", f64), m,
-                                            _ptr(sigma, "sigma", f64), _ptr(resid_l, "resid_l", f64),
-                                            _ptr(resid_r, "resid_r", f64), _ptr(A, "A", f64), _ptr(B, "B", f64),
-                                            _ptr(Tu, "Tu", f64), _ptr(Tv, "Tv", f64),
-                                            _ptr(status, "status", torch.int32), _stream())
-    check(rc, "nsvd_svd_ritz_step_f64")
+    _call("svd_ritz_step_f64", _ptr(PtU, "PtU", f64), _ptr(RtV, "RtV", f64), _ptr(Sp, "Sp", f64), _ptr(Sr, "Sr", f64),
+          _ptr(Cu, "Cu", f64), _ptr(Cv, "Cv", f64), m, _ptr(sigma, "sigma", f64), _ptr(resid_l, "resid_l", f64),
+          _ptr(resid_r, "resid_r", f64), _ptr(A, "A", f64), _ptr(B, "B", f64), _ptr(Tu, "Tu", f64), _ptr(Tv, "Tv", f64),
+          _ptr(status, "status", torch.int32))
     return sigma, resid_l, resid_r, A, B, Tu, Tv
 
 
@@ -1182,12 +1194,10 @@ def spin_solve(sigma_raw: torch.Tensor, sigma_scale: float, pi_raw: torch.Tensor
             raise NsvdError(f"spin_solve: {name} must be ({L}, {L})")
     if loss_eigvals.numel() != L + 1 or status.numel() < 1:
         raise NsvdError("spin_solve: loss_eigvals must hold 1 + L float64 values and status one int32")
-    rc = _lib.load().nsvd_spin_solve(_ptr(sigma_raw, "sigma_raw", f64), float(sigma_scale), _ptr(pi_raw, "pi_raw", f64),
-                                     float(pi_scale), L, float(decay), float(gpi_scale), _ptr(sigma_avg, "sigma_avg"),
-                                     _ptr(chol, "chol"), _ptr(loss_eigvals, "loss_eigvals", f64),
-                                     _ptr(gsigma, "gsigma", f64), _ptr(gpi_scaled, "gpi_scaled", f64),
-                                     _ptr(status, "status", torch.int32), _stream())
-    check(rc, "nsvd_spin_solve")
+    _call("spin_solve", _ptr(sigma_raw, "sigma_raw", f64), float(sigma_scale), _ptr(pi_raw, "pi_raw", f64),
+          float(pi_scale), L, float(decay), float(gpi_scale), _ptr(sigma_avg, "sigma_avg"), _ptr(chol, "chol"),
+          _ptr(loss_eigvals, "loss_eigvals", f64), _ptr(gsigma, "gsigma", f64), _ptr(gpi_scaled, "gpi_scaled", f64),
+          _ptr(status, "status", torch.int32))
 
 
 @_on_tensor_device
@@ -1219,16 +1229,12 @@ def spinx_solve(S_raw: torch.Tensor, s_scale: float, Gpp_raw: torch.Tensor, Gpk_
         raise NsvdError("spinx_solve: w must hold L + 1 and trace_w L float64 values")
     if out64.numel() != 2 * L + 2 or status.numel() < 1:
         raise NsvdError("spinx_solve: out64 must hold 2 L + 2 float64 values and status one int32")
-    rc = _lib.load().nsvd_spinx_solve(_ptr(S_raw, "S_raw", f64), float(s_scale), _ptr(Gpp_raw, "Gpp_raw", f64),
-                                      _ptr(Gpk_raw, "Gpk_raw", f64), _ptr(Gkk_raw, "Gkk_raw", f64), float(g_scale), L,
-                                      _ptr(w, "w", f64), _ptr(trace_w, "trace_w", f64), float(decay),
-                                      1 if update_state else 0,
-                                      _ptr(sigma_avg, "sigma_avg") if update_state else None,
-                                      _ptr(chol, "chol") if update_state else None, _ptr(out64, "out64", f64),
-                                      _ptr(T_s, "T_s", f64), _ptr(T_pp, "T_pp", f64), _ptr(T_kp, "T_kp", f64),
-                                      _ptr(T_pk, "T_pk", f64), _ptr(T_kk, "T_kk", f64),
-                                      _ptr(status, "status", torch.int32), _stream())
-    check(rc, "nsvd_spinx_solve")
+    _call("spinx_solve", _ptr(S_raw, "S_raw", f64), float(s_scale), _ptr(Gpp_raw, "Gpp_raw", f64),
+          _ptr(Gpk_raw, "Gpk_raw", f64), _ptr(Gkk_raw, "Gkk_raw", f64), float(g_scale), L, _ptr(w, "w", f64),
+          _ptr(trace_w, "trace_w", f64), float(decay), 1 if update_state else 0,
+          _ptr(sigma_avg, "sigma_avg") if update_state else None, _ptr(chol, "chol") if update_state else None,
+          _ptr(out64, "out64", f64), _ptr(T_s, "T_s", f64), _ptr(T_pp, "T_pp", f64), _ptr(T_kp, "T_kp", f64),
+          _ptr(T_pk, "T_pk", f64), _ptr(T_kk, "T_kk", f64), _ptr(status, "status", torch.int32))
 
 
 @_on_tensor_device
@@ -1252,24 +1258,20 @@ def ts_rotate2(X: torch.Tensor, T1: torch.Tensor, Y: torch.Tensor, T2: torch.Ten
     op, ldo = _rows_ptr(out, "out")
     if op in (xp, yp):
         raise NsvdError("ts_rotate2: out must not alias X or Y")
-    rc = _lib.load().nsvd_ts_rotate2(xp, ldx, yp, ldy, n, m, T1.data_ptr(), T1.stride(0), T2.data_ptr(), T2.stride(0), k,
-                                     op, ldo, _stream())
-    check(rc, "nsvd_ts_rotate2")
+    _call("ts_rotate2", xp, ldx, yp, ldy, n, m, T1.data_ptr(), T1.stride(0), T2.data_ptr(), T2.stride(0), k, op, ldo)
     return out
 
 
 def spin_state_floats(shape: ModelShape) -> int:
     """floats of ONE parameter set of SpIN's compact Jacobian state ([W_0 | .. | b_0 | ..], no padding); J is (L, this)"""
-    d = shape.desc()
-    n = int(_lib.load().nsvd_spin_state_floats(C.byref(d)))
+    n = int(_lib.load().nsvd_spin_state_floats(_desc(shape)))
     if n == 0:
         raise NsvdError("nsvd_spin_state_floats: unsupported model (no exponential / box mask, D <= 64, L <= 64)")
     return n
 
 
 def spin_jac_workspace(shape: ModelShape, B1: int, device) -> torch.Tensor:
-    d = shape.desc()
-    n = int(_lib.load().nsvd_spin_jac_workspace_bytes(C.byref(d), int(B1)))
+    n = int(_lib.load().nsvd_spin_jac_workspace_bytes(_desc(shape), int(B1)))
     if n == 0:
         raise NsvdError("nsvd_spin_jac_workspace_bytes: unsupported model or batch (no exponential / box mask, D <= 64, "
                         "L <= 64, B1 >= 2)")
@@ -1291,11 +1293,8 @@ def spin_jac_step(shape: ModelShape, params: Params, x: torch.Tensor, phi: torch
         raise NsvdError("spin_jac_step: J must hold L * spin_state_floats(shape) floats")
     if ws is None:
         ws = spin_jac_workspace(shape, B1, x.device)
-    d = shape.desc()
-    rc = _lib.load().nsvd_spin_jac_step(C.byref(d), C.byref(params), _ptr(x, "x"), B1, _ptr(phi, "phi"),
-                                        float(hard_mul_const), _ptr(gsigma, "gsigma", torch.float64), float(decay),
-                                        _ptr(J, "J"), C.byref(grads), ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_spin_jac_step")
+    _call("spin_jac_step", _desc(shape), C.byref(params), _ptr(x, "x"), B1, _ptr(phi, "phi"), float(hard_mul_const),
+          _ptr(gsigma, "gsigma", torch.float64), float(decay), _ptr(J, "J"), C.byref(grads), *_ws(ws))
 
 
 def cdk_workspace(B: int, L: int, set_first_mode_const: bool, device) -> torch.Tensor:
@@ -1303,6 +1302,7 @@ def cdk_workspace(B: int, L: int, set_first_mode_const: bool, device) -> torch.T
     return torch.empty(max(n, 256), dtype=torch.uint8, device=device)
 
 
+@_on_tensor_device
 def cdk_loss_forward(f: torch.Tensor, g: torch.Tensor, batch_weights: Optional[torch.Tensor], v: torch.Tensor,
                      M: torch.Tensor, set_first_mode_const: bool, loss: torch.Tensor,
                      rs_joint: Optional[torch.Tensor], rs_indep: Optional[torch.Tensor], ws: torch.Tensor) -> None:
@@ -1315,48 +1315,41 @@ def cdk_loss_forward(f: torch.Tensor, g: torch.Tensor, batch_weights: Optional[t
         raise NsvdError("cdk_loss_forward: batch_weights must hold one weight per row")
     if (rs_joint is not None and rs_joint.numel() != B) or (rs_indep is not None and rs_indep.numel() != B * (B - 1)):
         raise NsvdError("cdk_loss_forward: rs_joint (B), rs_indep (B (B-1))")
-    rc = _lib.load().nsvd_cdk_loss_forward(_ptr(f, "f"), _ptr(g, "g"), _ptr(batch_weights, "batch_weights"),
-                                           _ptr(v, "v"), _ptr(M, "M"), B, L, int(bool(set_first_mode_const)),
-                                           _ptr(loss, "loss"), _ptr(rs_joint, "rs_joint"),
-                                           _ptr(rs_indep, "rs_indep"), ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_cdk_loss_forward")
+    _call("cdk_loss_forward", _ptr(f, "f"), _ptr(g, "g"), _ptr(batch_weights, "batch_weights"), _ptr(v, "v"),
+          _ptr(M, "M"), B, L, int(bool(set_first_mode_const)), _ptr(loss, "loss"), _ptr(rs_joint, "rs_joint"),
+          _ptr(rs_indep, "rs_indep"), *_ws(ws))
 
 
+@_on_tensor_device
 def cdk_loss_backward(v: torch.Tensor, B: int, L: int, set_first_mode_const: bool, grad_out: Optional[torch.Tensor],
                       grad_f: Optional[torch.Tensor], grad_g: Optional[torch.Tensor], ws: torch.Tensor) -> None:
     for t, n in ((grad_f, "grad_f"), (grad_g, "grad_g")):
         if t is not None and tuple(t.shape) != (B, L):
             raise NsvdError(f"cdk_loss_backward: {n} must be (B, L)")
-    rc = _lib.load().nsvd_cdk_loss_backward(_ptr(v, "v"), int(B), int(L), int(bool(set_first_mode_const)),
-                                            _ptr(grad_out, "grad_out"), _ptr(grad_f, "grad_f"),
-                                            _ptr(grad_g, "grad_g"), ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_cdk_loss_backward")
+    _call("cdk_loss_backward", _ptr(v, "v"), int(B), int(L), int(bool(set_first_mode_const)),
+          _ptr(grad_out, "grad_out"), _ptr(grad_f, "grad_f"), _ptr(grad_g, "grad_g"), *_ws(ws))
 
 
+@_on_tensor_device
 def rmsprop_ema_step(p: torch.Tensor, grad: torch.Tensor, sq: torch.Tensor, ema: Optional[torch.Tensor], lr: float,
                      alpha: float, eps: float, ema_decay: float, grad_scale: float = 1.0) -> None:
-    n = p.numel()
-    if grad.numel() != n or sq.numel() != n or (ema is not None and ema.numel() != n):
-        raise NsvdError("rmsprop_ema_step: size mismatch")
-    if torch_binding() is not None:
-        _TB.rmsprop_ema_step(p, grad, sq, ema, float(lr), float(alpha), float(eps), float(ema_decay), float(grad_scale))
+    n = _opt_sizes("rmsprop_ema_step", p, grad, sq, None, ema)
+    tb = torch_binding()
+    if tb is not None:
+        tb.rmsprop_ema_step(p, grad, sq, ema, float(lr), float(alpha), float(eps), float(ema_decay), float(grad_scale))
         return
-    rc = _lib.load().nsvd_rmsprop_ema_step(_ptr(p, "p"), _ptr(grad, "grad"), _ptr(sq, "sq"), _ptr(ema, "ema"), n,
-                                           float(lr), float(alpha), float(eps), float(ema_decay), float(grad_scale),
-                                           _stream())
-    check(rc, "nsvd_rmsprop_ema_step")
+    _call("rmsprop_ema_step", _ptr(p, "p"), _ptr(grad, "grad"), _ptr(sq, "sq"), _ptr(ema, "ema"), n, float(lr),
+          float(alpha), float(eps), float(ema_decay), float(grad_scale))
 
 
+@_on_tensor_device
 def rmsprop_ema_step_dev(p: torch.Tensor, grad: torch.Tensor, sq: torch.Tensor, ema: Optional[torch.Tensor],
                          state: "StepState", grad_scale: float = 1.0, advance: bool = True) -> None:
     """rmsprop_ema_step with lr / EMA decay read from the device-resident schedule; advance: last optimiser launch of
     the step (state.step += 1 on the device)."""
-    n = p.numel()
-    if grad.numel() != n or sq.numel() != n or (ema is not None and ema.numel() != n):
-        raise NsvdError("rmsprop_ema_step_dev: size mismatch")
-    rc = _lib.load().nsvd_rmsprop_ema_step_dev(_ptr(p, "p"), _ptr(grad, "grad"), _ptr(sq, "sq"), _ptr(ema, "ema"), n,
-                                               state.ptr, float(grad_scale), int(bool(advance)), _stream())
-    check(rc, "nsvd_rmsprop_ema_step_dev")
+    n = _opt_sizes("rmsprop_ema_step_dev", p, grad, sq, None, ema)
+    _call("rmsprop_ema_step_dev", _ptr(p, "p"), _ptr(grad, "grad"), _ptr(sq, "sq"), _ptr(ema, "ema"), n, state.ptr,
+          float(grad_scale), int(bool(advance)))
 
 
 OPTIMIZER_KINDS = {"rmsprop": _lib.OPT_RMSPROP, "sgd": _lib.OPT_SGD, "adam": _lib.OPT_ADAM}
@@ -1393,6 +1386,7 @@ def _opt_sizes(what, p, grad, sq, mom, ema):
     return n
 
 
+@_on_tensor_device
 def opt_step(cfg: _lib.OptConfig, p: torch.Tensor, grad: torch.Tensor, sq: Optional[torch.Tensor],
              mom: Optional[torch.Tensor], ema: Optional[torch.Tensor], steps_taken: int, lr: Optional[float] = None,
              ema_decay: Optional[float] = None, grad_scale: float = 1.0) -> None:
@@ -1404,39 +1398,39 @@ def opt_step(cfg: _lib.OptConfig, p: torch.Tensor, grad: torch.Tensor, sq: Optio
         c = _lib.OptConfig.from_buffer_copy(cfg)
         c.lr = cfg.lr if lr is None else float(lr)
         c.ema_decay = cfg.ema_decay if ema_decay is None else float(ema_decay)
-    if torch_binding() is not None:
-        _TB.opt_step(int(c.kind), p, grad, sq, mom, ema, c.lr, c.alpha, c.eps, c.momentum, c.beta1, c.beta2, c.ema_decay,
-                     int(steps_taken), float(grad_scale))
+    tb = torch_binding()
+    if tb is not None:
+        tb.opt_step(int(c.kind), p, grad, sq, mom, ema, c.lr, c.alpha, c.eps, c.momentum, c.beta1, c.beta2, c.ema_decay,
+                    int(steps_taken), float(grad_scale))
         return
-    rc = _lib.load().nsvd_opt_step(_ptr(p, "p"), _ptr(grad, "grad"), _ptr(sq, "sq"), _ptr(mom, "mom"), _ptr(ema, "ema"),
-                                   n, C.byref(c), int(steps_taken), float(grad_scale), _stream())
-    check(rc, "nsvd_opt_step")
+    _call("opt_step", _ptr(p, "p"), _ptr(grad, "grad"), _ptr(sq, "sq"), _ptr(mom, "mom"), _ptr(ema, "ema"), n,
+          C.byref(c), int(steps_taken), float(grad_scale))
 
 
 class OptState(_DeviceSchedule):
     """The device-resident schedule of any optimiser rule (include/nsvd.h: nsvd_opt_state): what StepState is for
     RMSprop without momentum, plus Adam's bias corrections and SGD's first-step flag."""
-    _mirror, _entry = _lib.OptState, "nsvd_opt_state"
+    _mirror, _entry = _lib.OptState, "opt_state"
 
     def __init__(self, device, cfg: _lib.OptConfig, T_max: int, eta_min: float = 0.0, step: int = 0):
         self.cfg, self.T_max, self.eta_min = cfg, int(T_max), float(eta_min)
         super().__init__(device, step)
 
-    def _init(self, lib, step: int) -> int:
-        return lib.nsvd_opt_state_init(self.ptr, C.byref(self.cfg), self.eta_min, self.T_max, step, _stream())
+    def _init_args(self, step: int) -> tuple:
+        return C.byref(self.cfg), self.eta_min, self.T_max, step
 
 
+@_on_tensor_device
 def opt_step_dev(p: torch.Tensor, grad: torch.Tensor, sq: Optional[torch.Tensor], mom: Optional[torch.Tensor],
                  ema: Optional[torch.Tensor], state: OptState, grad_scale: float = 1.0, advance: bool = True) -> None:
     """opt_step with the step's scalars read from the device-resident schedule; advance: last optimiser launch of the
     step (state.step += 1 on the device)."""
     n = _opt_sizes("opt_step_dev", p, grad, sq, mom, ema)
-    rc = _lib.load().nsvd_opt_step_dev(_ptr(p, "p"), _ptr(grad, "grad"), _ptr(sq, "sq"), _ptr(mom, "mom"),
-                                       _ptr(ema, "ema"), n, C.byref(state.cfg), state.ptr, float(grad_scale),
-                                       int(bool(advance)), _stream())
-    check(rc, "nsvd_opt_step_dev")
+    _call("opt_step_dev", _ptr(p, "p"), _ptr(grad, "grad"), _ptr(sq, "sq"), _ptr(mom, "mom"), _ptr(ema, "ema"), n,
+          C.byref(state.cfg), state.ptr, float(grad_scale), int(bool(advance)))
 
 
+@_on_tensor_device
 def spectrum_accumulate(f: torch.Tensor, Tf: torch.Tensor, x: torch.Tensor, sigma: float, use_importance: bool,
                         lim: float, cov: torch.Tensor, quad: torch.Tensor, first_mode_const: bool = False) -> None:
     """cov += phi^T phi, quad += phi^T Tphi. float32 accumulators: the reference's (methods/spectrum.py:60-75);
@@ -1453,19 +1447,16 @@ def spectrum_accumulate(f: torch.Tensor, Tf: torch.Tensor, x: torch.Tensor, sigm
     if first_mode_const and cov.dtype != torch.float64:
         raise NsvdError("spectrum_accumulate(first_mode_const=True) takes float64 accumulators")
     if cov.dtype == torch.float64:
-        fn = "nsvd_spectrum_accumulate_const_f64" if first_mode_const else "nsvd_spectrum_accumulate_f64"
-        rc = getattr(_lib.load(), fn)(_ptr(f, "f"), _ptr(Tf, "Tf"), _ptr(x, "x"), B, L, D, float(sigma),
-                                      int(bool(use_importance)), float(lim),
-                                      _ptr(cov, "cov", torch.float64), _ptr(quad, "quad", torch.float64), _stream())
-        check(rc, fn)
+        _call("spectrum_accumulate_const_f64" if first_mode_const else "spectrum_accumulate_f64", _ptr(f, "f"),
+              _ptr(Tf, "Tf"), _ptr(x, "x"), B, L, D, float(sigma), int(bool(use_importance)), float(lim),
+              _ptr(cov, "cov", torch.float64), _ptr(quad, "quad", torch.float64))
         return
-    if torch_binding() is not None:
-        _TB.spectrum_accumulate(f, Tf, x, float(sigma), bool(use_importance), float(lim), cov, quad)
+    tb = torch_binding()
+    if tb is not None:
+        tb.spectrum_accumulate(f, Tf, x, float(sigma), bool(use_importance), float(lim), cov, quad)
         return
-    rc = _lib.load().nsvd_spectrum_accumulate(_ptr(f, "f"), _ptr(Tf, "Tf"), _ptr(x, "x"), B, L, D, float(sigma),
-                                              int(bool(use_importance)), float(lim), _ptr(cov, "cov"),
-                                              _ptr(quad, "quad"), _stream())
-    check(rc, "nsvd_spectrum_accumulate")
+    _call("spectrum_accumulate", _ptr(f, "f"), _ptr(Tf, "Tf"), _ptr(x, "x"), B, L, D, float(sigma),
+          int(bool(use_importance)), float(lim), _ptr(cov, "cov"), _ptr(quad, "quad"))
 
 
 def _qnums_arg(qnums, width: int = 2):
@@ -1484,8 +1475,7 @@ def _eigfunc_eval(D, kind, param, qnums, x, out):
     if out is not None and tuple(out.shape) != (x.shape[0], Lg):
         raise NsvdError(f"{name}: out must be ({x.shape[0]}, {Lg})")
     psi = torch.empty((x.shape[0], Lg), dtype=torch.float64, device=x.device) if out is None else out
-    check(getattr(_lib.load(), "nsvd_" + name)(int(kind), float(param), arr, Lg, _ptr(x, "x"), x.shape[0],
-                                               _ptr(psi, "psi", torch.float64), _stream()), "nsvd_" + name)
+    _call(name, int(kind), float(param), arr, Lg, _ptr(x, "x"), x.shape[0], _ptr(psi, "psi", torch.float64))
     return psi
 
 
@@ -1497,11 +1487,9 @@ def _eigfunc_accumulate(D, kind, param, qnums, f, x, sigma, use_importance, lim,
         raise NsvdError(f"{name}: x must be (B, {D}) with f's B")
     if tuple(gram.shape) != (Lg, Lg) or tuple(cross.shape) != (Lg, L) or (cov is not None and tuple(cov.shape) != (L, L)):
         raise NsvdError(f"{name}: gram ({Lg}, {Lg}), cross ({Lg}, {L}), cov ({L}, {L}) or None")
-    fn = "nsvd_" + name + "_f64"
-    rc = getattr(_lib.load(), fn)(int(kind), float(param), arr, Lg, _ptr(f, "f"), L, _ptr(x, "x"), B, float(sigma),
-                                  int(bool(use_importance)), float(lim), _ptr(gram, "gram", torch.float64),
-                                  _ptr(cross, "cross", torch.float64), _ptr(cov, "cov", torch.float64), _stream())
-    check(rc, fn)
+    _call(name + "_f64", int(kind), float(param), arr, Lg, _ptr(f, "f"), L, _ptr(x, "x"), B, float(sigma),
+          int(bool(use_importance)), float(lim), _ptr(gram, "gram", torch.float64), _ptr(cross, "cross", torch.float64),
+          _ptr(cov, "cov", torch.float64))
 
 
 @_on_tensor_device
@@ -1552,21 +1540,22 @@ def dominant_kernel_name(shape: ModelShape, B: int, path: int = PATH_AUTO) -> st
 
 
 # ------------------------------------------------------------------------------ row normalisation (CDK towers)
+@_on_tensor_device
 def row_normalize(z: torch.Tensor, r_up: float, mode: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """normalize(z, r_up, 'l2_ball' | 'l2_sphere') of examples/models/siam.py:170-183 on (B, L) float32 rows."""
     if z.dim() != 2 or z.dtype != torch.float32 or not z.is_contiguous():
         raise NsvdError("row_normalize: z must be a contiguous (B, L) float32 tensor")
     if out is None:
         out = torch.empty_like(z)
-    check(_lib.load().nsvd_row_normalize_forward(_ptr(z, "z"), z.shape[0], z.shape[1], float(r_up), int(mode),
-                                                 _ptr(out, "out"), _stream()), "nsvd_row_normalize_forward")
+    _call("row_normalize_forward", _ptr(z, "z"), z.shape[0], z.shape[1], float(r_up), int(mode), _ptr(out, "out"))
     return out
 
 
+@_on_tensor_device
 def row_normalize_backward(z: torch.Tensor, dout: torch.Tensor, r_up: float, mode: int) -> torch.Tensor:
     dz = torch.empty_like(z)
-    check(_lib.load().nsvd_row_normalize_backward(_ptr(z, "z"), _ptr(dout, "dout"), z.shape[0], z.shape[1], float(r_up),
-                                                  int(mode), _ptr(dz, "dz"), _stream()), "nsvd_row_normalize_backward")
+    _call("row_normalize_backward", _ptr(z, "z"), _ptr(dout, "dout"), z.shape[0], z.shape[1], float(r_up), int(mode),
+          _ptr(dz, "dz"))
     return dz
 
 
@@ -1617,6 +1606,7 @@ def tower_y2(ws: torch.Tensor, B: int, d0: int, d1: int, d2: int) -> torch.Tenso
     return ws[off:off + 4 * B * d2].view(torch.float32).view(B, d2)
 
 
+@_on_tensor_device
 def tower_forward(x: torch.Tensor, params: dict, slope: float, eps: float, momentum: float, update_running: bool,
                   ws: torch.Tensor, gemm_bf16: bool = False, phase: int = 0) -> Optional[torch.Tensor]:
     """z = BN2(Linear2(lrelu(BN1(Linear1(x))))) in training mode; params: dict over TOWER_KEYS (torch layouts).
@@ -1633,13 +1623,12 @@ def tower_forward(x: torch.Tensor, params: dict, slope: float, eps: float, momen
             raise NsvdError(f"tower_forward: {k} must have {n} elements")
     z = torch.empty((B, d2), dtype=torch.float32, device=x.device) if phase != 1 else None
     p = _tower_struct(params, bool(update_running))
-    rc = _lib.load().nsvd_tower_forward_phase(_ptr(x, "x"), C.byref(p), B, d0, d1, d2, float(slope), float(eps),
-                                              float(momentum), int(bool(update_running)), int(gemm_bf16),
-                                              int(phase), _ptr(z, "z"), ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_tower_forward")
+    _call("tower_forward_phase", _ptr(x, "x"), C.byref(p), B, d0, d1, d2, float(slope), float(eps), float(momentum),
+          int(bool(update_running)), int(gemm_bf16), int(phase), _ptr(z, "z"), *_ws(ws))
     return z
 
 
+@_on_tensor_device
 def tower_backward(x: torch.Tensor, params: dict, dz: torch.Tensor, slope: float, ws: torch.Tensor,
                    gemm_bf16: bool = False) -> dict:
     """gradients of sum(dz * z) w.r.t. W1, b1, g1, be1, W2, b2, g2, be2 (same workspace as the forward call)."""
@@ -1649,21 +1638,22 @@ def tower_backward(x: torch.Tensor, params: dict, dz: torch.Tensor, slope: float
         raise NsvdError("tower_backward: dz must be (B, d2)")
     grads = {k: torch.empty_like(params[k]) for k in TOWER_KEYS if not k.startswith("r")}
     p, g = _tower_struct(params, False), _tower_struct(grads, False)
-    rc = _lib.load().nsvd_tower_backward(_ptr(x, "x"), C.byref(p), _ptr(dz, "dz"), B, d0, d1, d2, float(slope),
-                                         int(gemm_bf16), C.byref(g), ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_tower_backward")
+    _call("tower_backward", _ptr(x, "x"), C.byref(p), _ptr(dz, "dz"), B, d0, d1, d2, float(slope), int(gemm_bf16),
+          C.byref(g), *_ws(ws))
     return grads
 
 
+@_on_tensor_device
 def to_bf16(x: torch.Tensor) -> torch.Tensor:
     """bfloat16(x), round to nearest even (nsvd_to_bf16) - the cast the mixed-precision towers' operands go through"""
     if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() % 8:
         raise NsvdError("to_bf16: contiguous float32 tensor with a multiple of 8 elements")
     out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
-    check(_lib.load().nsvd_to_bf16(_ptr(x, "x"), out.data_ptr(), x.numel(), _stream()), "nsvd_to_bf16")
+    _call("to_bf16", _ptr(x, "x"), out.data_ptr(), x.numel())
     return out
 
 
+@_on_tensor_device
 def gemm_bf16(A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor] = None, a_kstrided: bool = False,
               b_kstrided: bool = False, out_bf16: bool = False, slices: int = 1, want_sumsq: bool = False):
     """C = A B^T on the bf16 MFMA with float32 accumulation (nsvd_gemm_bf16). A, B: bfloat16, 2-D, contiguous.
@@ -1681,11 +1671,9 @@ def gemm_bf16(A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor] = N
     ss = torch.zeros((M // 256) * (N // 128) * slices, dtype=torch.float32, device=A.device) if want_sumsq else None
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N or not bias.is_cuda):
         raise NsvdError("gemm_bf16: bias must be N float32 values on the GPU")
-    rc = _lib.load().nsvd_gemm_bf16(A.data_ptr(), B.data_ptr(), Cm.data_ptr(),
-                                    bias.data_ptr() if bias is not None else None, M, N, K, A.shape[1], B.shape[1], N,
-                                    int(bool(a_kstrided)), int(bool(b_kstrided)), int(bool(out_bf16)), int(slices),
-                                    M * N, ss.data_ptr() if ss is not None else None, _stream())
-    check(rc, "nsvd_gemm_bf16")
+    _call("gemm_bf16", A.data_ptr(), B.data_ptr(), Cm.data_ptr(), bias.data_ptr() if bias is not None else None, M, N, K,
+          A.shape[1], B.shape[1], N, int(bool(a_kstrided)), int(bool(b_kstrided)), int(bool(out_bf16)), int(slices),
+          M * N, ss.data_ptr() if ss is not None else None)
     return (Cm, ss) if want_sumsq else Cm
 
 
@@ -1701,9 +1689,8 @@ class GradScaler:
                  growth_interval: int = 2000):
         self.buf = torch.zeros(C.sizeof(_lib.GradScalerState) // 4, dtype=torch.int32, device=device)
         with torch.cuda.device(self.buf.device):
-            check(_lib.load().nsvd_grad_scaler_init(self.buf.data_ptr(), float(init_scale), float(growth_factor),
-                                                    float(backoff_factor), int(growth_interval), _stream()),
-                  "nsvd_grad_scaler_init")
+            _call("grad_scaler_init", self.buf.data_ptr(), float(init_scale), float(growth_factor),
+                  float(backoff_factor), int(growth_interval))
 
     @property
     def ptr(self) -> int:
@@ -1738,6 +1725,7 @@ def cdk_step_workspace(desc: "_lib.CdkStepDesc", device) -> torch.Tensor:
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
+@_on_tensor_device
 def cdk_step(desc: "_lib.CdkStepDesc", x: torch.Tensor, y: torch.Tensor, towers: Sequence[dict],
              momentum_bufs: Sequence[dict], v: torch.Tensor, M: torch.Tensor, loss: torch.Tensor, ws: torch.Tensor,
              rs_joint: Optional[torch.Tensor] = None, rs_indep: Optional[torch.Tensor] = None) -> None:
@@ -1750,21 +1738,8 @@ def cdk_step(desc: "_lib.CdkStepDesc", x: torch.Tensor, y: torch.Tensor, towers:
         raise NsvdError(f"cdk_step: v ({Lp}), M ({Lp}, {Lp})")
     tw = (_lib.TowerParams * 2)(_tower_struct(towers[0], True), _tower_struct(towers[1], True))
     mb = (_lib.TowerParams * 2)(_tower_struct(momentum_bufs[0], False), _tower_struct(momentum_bufs[1], False))
-    rc = _lib.load().nsvd_cdk_step(C.byref(desc), _ptr(x, "x"), _ptr(y, "y"), tw, mb, _ptr(v, "v"), _ptr(M, "M"),
-                                   _ptr(loss, "loss"), _ptr(rs_joint, "rs_joint"), _ptr(rs_indep, "rs_indep"),
-                                   ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_cdk_step")
-
-
-# every wrapper that launches kernels runs on the device of its tensors (see _on_tensor_device)
-for _name in ("fourier_features", "operator_forward", "operator_features", "operator_sample_features",
-              "operator_sample_features_dev", "rmsprop_ema_step_dev", "opt_step_dev",
-              "operator_backward", "model_forward", "model_backward", "evd_moments", "evd_loss_grad", "evd_loss_fused",
-              "evd_partial", "operator_backward_evd", "operator_backward_evd_heads", "operator_backward_evd_step", "operator_backward_evd_step_next", "operator_backward_evd_opt_step", "operator_backward_evd_step_window", "model_backward_evd_step", "kernel_apply", "rbf_apply", "dot_apply", "dot_apply_pair", "tsgram_f64", "ritz_step_f64", "ts_rotate", "tsgram3_f64", "svd_ritz_step_f64", "cdk_loss_forward",
-              "cdk_loss_backward", "rmsprop_ema_step", "opt_step", "spectrum_accumulate", "row_normalize",
-              "row_normalize_backward", "tower_forward", "tower_backward", "cdk_step", "to_bf16", "gemm_bf16"):
-    globals()[_name] = _on_tensor_device(globals()[_name])
-del _name
+    _call("cdk_step", C.byref(desc), _ptr(x, "x"), _ptr(y, "y"), tw, mb, _ptr(v, "v"), _ptr(M, "M"), _ptr(loss, "loss"),
+          _ptr(rs_joint, "rs_joint"), _ptr(rs_indep, "rs_indep"), *_ws(ws))
 
 
 # ------------------------------------------------------------------------------------- NeuralEF (include/nsvd.h)
@@ -1783,13 +1758,9 @@ def nef_operator_forward(shape: ModelShape, params: Params, prob: Problem, x: to
     phi = torch.empty((B, shape.L), dtype=torch.float32, device=dev)
     Tphi, h, r = torch.empty_like(phi), torch.empty_like(phi), torch.empty_like(phi)
     stats = torch.empty((1 + 2 * shape.D, shape.L), dtype=torch.float32, device=dev)
-    d = shape.desc()
-    rc = _lib.load().nsvd_nef_operator_forward(C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(phi),
-                                               _ptr(Tphi), _ptr(h), _ptr(r), _ptr(stats),
-                                               _ptr(norm_biased, "norm_biased"), _ptr(norm_unbiased, "norm_unbiased"),
-                                               _ptr(initialized, "initialized", torch.int32), float(momentum),
-                                               ws.data_ptr(), ws.numel(), int(path), _stream())
-    check(rc, "nsvd_nef_operator_forward")
+    _call("nef_operator_forward", _desc(shape), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(phi), _ptr(Tphi),
+          _ptr(h), _ptr(r), _ptr(stats), _ptr(norm_biased, "norm_biased"), _ptr(norm_unbiased, "norm_unbiased"),
+          _ptr(initialized, "initialized", torch.int32), float(momentum), *_ws(ws), int(path))
     return phi, Tphi, (h, r, stats)
 
 
@@ -1801,11 +1772,8 @@ def nef_operator_backward(shape: ModelShape, params: Params, prob: Problem, x: t
     if tuple(dphi.shape) != (B, shape.L):
         raise NsvdError(f"dphi must be {(B, shape.L)}")
     du0 = torch.empty_like(h)
-    d = shape.desc()
-    rc = _lib.load().nsvd_nef_operator_backward(C.byref(d), C.byref(params), C.byref(prob), _ptr(x, "x"), B,
-                                                _ptr(dphi, "dphi"), _ptr(h), _ptr(r), _ptr(stats), _ptr(du0),
-                                                C.byref(grads), ws.data_ptr(), ws.numel(), int(path), _stream())
-    check(rc, "nsvd_nef_operator_backward")
+    _call("nef_operator_backward", _desc(shape), C.byref(params), C.byref(prob), _ptr(x, "x"), B, _ptr(dphi, "dphi"),
+          _ptr(h), _ptr(r), _ptr(stats), _ptr(du0), C.byref(grads), *_ws(ws), int(path))
 
 
 @_on_tensor_device
@@ -1823,8 +1791,7 @@ def nef_loss(phi: torch.Tensor, Tphi: torch.Tensor, phi1: torch.Tensor, Tphi1: t
     dev = phi.device
     chunked = (phi1.data_ptr() == phi.data_ptr() and Tphi1.data_ptr() == Tphi.data_ptr() and B1 + B2 == B and
                phi2.data_ptr() == phi.data_ptr() + 4 * B1 * L and Tphi2.data_ptr() == Tphi.data_ptr() + 4 * B1 * L)
-    lib = _lib.load()
-    nbytes = lib.nsvd_nef_loss_workspace_bytes(B, B1, B2, L)
+    nbytes = _lib.load().nsvd_nef_loss_workspace_bytes(B, B1, B2, L)
     if nbytes == 0:
         raise NsvdError(f"nsvd_nef_loss: unsupported shape B={B}, B1={B1}, B2={B2}, L={L} (L <= 64)")
     if scratch is None:
@@ -1843,10 +1810,9 @@ def nef_loss(phi: torch.Tensor, Tphi: torch.Tensor, phi1: torch.Tensor, Tphi1: t
             raise NsvdError("nsvd_nef_loss: out must be (loss (1,), dphi (B, L), dphi1 (B1, L), dphi2 (B2, L))")
         if chunked:
             d1 = d2 = None
-    rc = lib.nsvd_nef_loss(_ptr(phi, "phi"), _ptr(Tphi, "Tphi"), B, _ptr(phi1, "phi1"), _ptr(Tphi1, "Tphi1"), B1,
-                           _ptr(phi2, "phi2"), _ptr(Tphi2, "Tphi2"), B2, L, int(bool(unbiased)), int(diagonal),
-                           _ptr(loss), _ptr(dphi), _ptr(d1), _ptr(d2), scratch.data_ptr(), nbytes, _stream())
-    check(rc, "nsvd_nef_loss")
+    _call("nef_loss", _ptr(phi, "phi"), _ptr(Tphi, "Tphi"), B, _ptr(phi1, "phi1"), _ptr(Tphi1, "Tphi1"), B1,
+          _ptr(phi2, "phi2"), _ptr(Tphi2, "Tphi2"), B2, L, int(bool(unbiased)), int(diagonal), _ptr(loss), _ptr(dphi),
+          _ptr(d1), _ptr(d2), _ws(scratch, "scratch")[0], nbytes)
     return loss, dphi, d1, d2
 
 
@@ -1907,12 +1873,10 @@ def nef_rows_forward(u: torch.Tensor, B1: Optional[int], norm_biased: Optional[t
         raise NsvdError("nsvd_nef_rows_forward: stats must hold 2 L values")
     if ws is None:
         ws = nef_rows_workspace(B, L, u.device)
-    rc = _lib.load().nsvd_nef_rows_forward(_ptr(u, "u"), B, B1, L, _ptr(out, "out"), _ptr(stats, "stats"),
-                                           _ptr(norm_biased, "norm_biased"), _ptr(norm_unbiased, "norm_unbiased"),
-                                           _ptr(initialized, "initialized", torch.int32), float(momentum),
-                                           (C.c_int * 4)(*(order + (0,) * (4 - len(order)))), len(order),
-                                           ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_nef_rows_forward")
+    _call("nef_rows_forward", _ptr(u, "u"), B, B1, L, _ptr(out, "out"), _ptr(stats, "stats"),
+          _ptr(norm_biased, "norm_biased"), _ptr(norm_unbiased, "norm_unbiased"),
+          _ptr(initialized, "initialized", torch.int32), float(momentum),
+          (C.c_int * 4)(*(order + (0,) * (4 - len(order)))), len(order), *_ws(ws))
     return out, stats
 
 
@@ -1934,10 +1898,8 @@ def nef_rows_backward(phi: Optional[torch.Tensor], stats: Optional[torch.Tensor]
         out = torch.empty_like(dphi)
     if ws is None:
         ws = nef_rows_workspace(B, L, dphi.device)
-    rc = _lib.load().nsvd_nef_rows_backward(_ptr(phi, "phi"), _ptr(stats, "stats"), B, B1, L, _ptr(dphi, "dphi"),
-                                            _ptr(dphi1, "dphi1"), _ptr(dphi2, "dphi2"), _ptr(out, "out"),
-                                            ws.data_ptr(), ws.numel(), _stream())
-    check(rc, "nsvd_nef_rows_backward")
+    _call("nef_rows_backward", _ptr(phi, "phi"), _ptr(stats, "stats"), B, B1, L, _ptr(dphi, "dphi"),
+          _ptr(dphi1, "dphi1"), _ptr(dphi2, "dphi2"), _ptr(out, "out"), *_ws(ws))
     return out
 
 
@@ -1945,8 +1907,7 @@ def nef_rows_backward(phi: Optional[torch.Tensor], stats: Optional[torch.Tensor]
 def nef_scale_heads(f: torch.Tensor, Tf: torch.Tensor, norm: torch.Tensor) -> None:
     """f /= norm, Tf /= norm per head, in place (BatchL2NormalizedFunctions in evaluation mode)."""
     B, L = f.shape
-    rc = _lib.load().nsvd_nef_scale_heads(_ptr(f, "f"), _ptr(Tf, "Tf"), _ptr(norm.reshape(-1), "norm"), B, L, _stream())
-    check(rc, "nsvd_nef_scale_heads")
+    _call("nef_scale_heads", _ptr(f, "f"), _ptr(Tf, "Tf"), _ptr(norm.reshape(-1), "norm"), B, L)
 
 
 # ------------------------------------------------------------------------ retrieval metrics (include/nsvd.h)
@@ -2029,15 +1990,12 @@ def retrieval_eval(zq: torch.Tensor, zg: torch.Tensor, q_cls: torch.Tensor, g_cl
         out["topk_rel"] = torch.empty((Nq, K), dtype=torch.uint8, device=dev)
     if want_ap:
         out["avg_prec"] = torch.empty((3, Nq), dtype=torch.float64, device=dev)
-    rc = lib.nsvd_retrieval_eval(pq, ldq, pg, ldg, Nq, Ng, d, _ptr(q_cls, "q_cls", torch.int32),
-                                 _ptr(g_cls, "g_cls", torch.int32),
-                                 _ptr(n_relevant_items if want_ap else None, "n_relevant_items", torch.int32),
-                                 int(metric), K, _ptr(out.get("topk_idx"), "topk_idx", torch.int32),
-                                 _ptr(out.get("topk_rel"), "topk_rel", torch.uint8), _ptr(out["prec_at_k"]),
-                                 _ptr(out["hits_at_k"], "hits_at_k", torch.int32),
-                                 _ptr(out.get("avg_prec"), "avg_prec", torch.float64), _ptr(out["n_relevant_found"], "n", torch.int32),
-                                 ws.data_ptr(), ws.numel() * ws.element_size(), _stream())
-    check(rc, "nsvd_retrieval_eval")
+    _call("retrieval_eval", pq, ldq, pg, ldg, Nq, Ng, d, _ptr(q_cls, "q_cls", torch.int32),
+          _ptr(g_cls, "g_cls", torch.int32),
+          _ptr(n_relevant_items if want_ap else None, "n_relevant_items", torch.int32), int(metric), K,
+          _ptr(out.get("topk_idx"), "topk_idx", torch.int32), _ptr(out.get("topk_rel"), "topk_rel", torch.uint8),
+          _ptr(out["prec_at_k"]), _ptr(out["hits_at_k"], "hits_at_k", torch.int32),
+          _ptr(out.get("avg_prec"), "avg_prec", torch.float64), _ptr(out["n_relevant_found"], "n", torch.int32), *_ws(ws))
     if want_topk:
         out["topk_rel"] = out["topk_rel"].view(torch.bool)
     return out

@@ -20,6 +20,29 @@ def test_header_declares_what_binding_binds():
     assert _declared() == sorted(_lib.SIGNATURES.keys())
 
 
+def _declared_arg_counts():
+    """name -> number of parameters of its declaration in include/nsvd.h (`void` counts as none)"""
+    src = open(os.path.join(ROOT, "include", "nsvd.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    counts = {}
+    for name, params in re.findall(r"\b(nsvd_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in counts, name + " is declared twice"
+        params = params.strip()
+        counts[name] = 0 if params in ("", "void") else len(params.split(","))
+    return counts
+
+
+def test_binding_argument_counts_match_the_header():
+    """an argument added to a declaration and forgotten in _lib.SIGNATURES (or the reverse) is caught here, not on the
+    GPU: ctypes would pass the call through with a shifted or missing argument"""
+    from neural_svd_amd import _lib
+    counts = _declared_arg_counts()
+    assert sorted(counts) == _declared() and len(counts) == 102
+    wrong = {n: (len(args), counts[n]) for n, (_, args) in _lib.SIGNATURES.items() if len(args) != counts[n]}
+    assert not wrong, f"(bound, declared) argument counts differ: {wrong}"
+
+
 def _exported(path):
     """the nsvd_* symbols the library defines in its dynamic symbol table"""
     import subprocess
@@ -61,7 +84,10 @@ def test_struct_layout_matches_header():
     #include <stdio.h>
     #include "nsvd.h"
     #include <stddef.h>
-    int main(){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(nsvd_model_desc), sizeof(nsvd_params),
+    int main(){ printf("%zu %zu %zu %zu %zu %zu ", sizeof(nsvd_opt_config), sizeof(nsvd_opt_state), sizeof(nsvd_optimizer),
+                       offsetof(nsvd_optimizer, steps_taken), offsetof(nsvd_optimizer, state),
+                       offsetof(nsvd_opt_state, cur));
+                printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(nsvd_model_desc), sizeof(nsvd_params),
                        sizeof(nsvd_problem), sizeof(nsvd_tower_params), sizeof(nsvd_rmsprop), sizeof(nsvd_cdk_step_desc),
                        offsetof(nsvd_cdk_step_desc, lr), offsetof(nsvd_cdk_step_desc, gemm_bf16),
                        offsetof(nsvd_rmsprop, state), sizeof(nsvd_step_state), offsetof(nsvd_step_state, cur),
@@ -74,6 +100,12 @@ def test_struct_layout_matches_header():
         exe = os.path.join(td, "t")
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
         out = subprocess.check_output([exe]).decode().split()
+    # the optimiser structs (OptState mirrors a device-resident struct: a wrong size is a short device buffer)
+    opt = [ctypes.sizeof(_lib.OptConfig), ctypes.sizeof(_lib.OptState), ctypes.sizeof(_lib.Optimizer),
+           _lib.Optimizer.steps_taken.offset, _lib.Optimizer.state.offset, _lib.OptState.cur.offset]
+    assert [int(v) for v in out[:6]] == opt == [64, 144, 520, 504, 512, 88]
+    assert ctypes.sizeof(_lib.OptStateCur) == 144 - 88
+    out = out[6:]
     assert [int(v) for v in out] == [ctypes.sizeof(_lib.ModelDesc), ctypes.sizeof(_lib.Params),
                                      ctypes.sizeof(_lib.Problem), ctypes.sizeof(_lib.TowerParams),
                                      ctypes.sizeof(_lib.Rmsprop), ctypes.sizeof(_lib.CdkStepDesc),

@@ -11,7 +11,10 @@ each of three families runs on cuda:0 and then on cuda:1 in this process, on the
   69 920 bytes (L = 45: 65 520).
 
 The kernels use no atomics and the launches do not depend on the device: the results of cuda:1 equal those of cuda:0
-bit for bit. Skipped where fewer than two devices are visible."""
+bit for bit. Skipped where fewer than two devices are visible.
+
+A second test calls three wrappers with their tensors on cuda:1 while cuda:0 is the current device (the device guard
+of neural_svd_amd/hip_ops.py), at the smallest shapes that reach their kernels."""
 import pytest
 import torch
 
@@ -61,6 +64,35 @@ def _spin(dev):
     return [state, chol, le, gs, gp, status]
 
 
+def _rbf_pair(dev):
+    from neural_svd_amd import hip_ops as H
+    g = torch.Generator().manual_seed(4)
+    x, y, gg, f = (torch.randn(s, generator=g).to(dev) for s in ((64, 3), (64, 3), (64, 4), (64, 4)))
+    return list(H.rbf_apply_pair(x, y, gg, f, H.RBF_GAUSSIAN, 1.5, 1.0 / 64, 1.0 / 64))
+
+
+def _gather_heads(dev):
+    from neural_svd_amd import hip_ops as H
+    W, B, Ll = 2, 32, 2
+    gath = torch.randn(W, 2, B, Ll, generator=torch.Generator().manual_seed(5)).to(dev)
+    f, Tf = torch.empty(B, W * Ll, device=dev), torch.empty(B, W * Ll, device=dev)
+    scratch = H.evd_scratch(B, W * Ll, dev).zero_()
+    H.evd_gather_heads(gath, f, Tf, H.MASK_SEQUENTIAL, None, scratch)
+    return [f, Tf, scratch]
+
+
+def _gather_head_blocks(dev):
+    from neural_svd_amd import hip_ops as H
+    W, B, L = 2, 32, 3  # rank 0 holds two heads, rank 1 one: its block's tail is never read
+    gath = torch.randn(W, 2 * B * 2, generator=torch.Generator().manual_seed(6))
+    gath[1, 2 * B:] = float("nan")
+    gath = gath.to(dev)
+    f, Tf = torch.empty(B, L, device=dev), torch.empty(B, L, device=dev)
+    scratch = H.evd_scratch(B, L, dev).zero_()
+    H.evd_gather_head_blocks(gath, L, f, Tf, H.MASK_SEQUENTIAL, None, scratch)
+    return [f, Tf, scratch]
+
+
 def test_lds_byte_counts():
     assert DOT_LDS_BYTES == 76288 and CDK_LDS_BYTES == 69632
     assert _spin_lds_bytes(SPIN_L - 1) == 65520 <= 64 * 1024 < _spin_lds_bytes(SPIN_L) == 69920
@@ -80,4 +112,24 @@ def test_second_device_matches_first(family):
         outs.append([t.cpu() for t in res])
     for a, b in zip(*outs):
         assert bool(torch.isfinite(a.double()).all())
+        assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two visible devices")
+@pytest.mark.parametrize("wrapper", ["rbf_apply_pair", "evd_gather_heads", "evd_gather_head_blocks"])
+def test_tensors_off_the_current_device_launch_where_they_live(wrapper):
+    """The device guard (hip_ops._on_tensor_device) on the three wrappers that lacked it: with the tensors on cuda:1
+    while cuda:0 is current, the call takes a stream of cuda:1 and gives, bit for bit, what the same call gives with
+    cuda:1 current (before, it handed the library a stream of cuda:0)."""
+    run = dict(rbf_apply_pair=_rbf_pair, evd_gather_heads=_gather_heads, evd_gather_head_blocks=_gather_head_blocks)[wrapper]
+    dev, outs = torch.device("cuda", 1), []
+    for current in (1, 0):
+        with torch.cuda.device(current):
+            res = run(dev)
+            assert torch.cuda.current_device() == current
+        torch.cuda.synchronize(dev)
+        outs.append([t.cpu() for t in res])
+    for a, b in zip(*outs):
+        assert a.dtype == torch.uint8 or bool(torch.isfinite(a).all())
         assert torch.equal(a, b)
