@@ -167,8 +167,16 @@ __global__ void cdk_scaler_init_kernel(nsvd_grad_scaler* gs, float scale, float 
     gs->growth_tracker = 0; gs->steps_ok = 0; gs->steps_skipped = 0; gs->last_found_inf = 0;
 }
 
+static_assert(sizeof(NSVD_TOWER_FIELDS) / sizeof(NSVD_TOWER_FIELDS[0]) == NT, "TensorTable: NT tensors per tower");
+
 struct StepWs {
+    // The three forms of a step, decided once (carve_step) and read by every stage: float32 (each tower by itself through
+    // nsvd_tower_forward / nsvd_tower_backward_sumsq); mixed precision (both towers through every launch together,
+    // tower.hip); mixed precision with fused_end - the narrow end (split-K sum, second BatchNorm, normalisation and
+    // their backward) as launches for both towers, cdk_narrow.hip, which also leave the small tensors' squares
+    bool mixed, fused_end;
     void* tower[2];
+    NsvdTower16Views tv[2];  // mixed precision: what the step itself addresses inside tower[t] (else zero)
     void* cdk;
     float *z[2], *e[2], *ge[2], *dz[2];
     float* grad[2];  // per tower: [W1 | b1 | g1 | be1 | W2 | b2 | g2 | be2], each padded to 64 floats
@@ -184,9 +192,14 @@ StepWs carve_step(const nsvd_cdk_step_desc& d, void* base) {
     StepWs w;
     memset(&w, 0, sizeof(w));
     NsvdArena a(base);
+    w.mixed = d.gemm_bf16 != 0;
+    w.fused_end = w.mixed && nsvd_narrow_supported(2, d.B, d.d2);
     w.tower_bytes = nsvd_tower_workspace_bytes(d.B, d.d0, d.d1, d.d2);
     w.cdk_bytes = nsvd_cdk_workspace_bytes(d.B, d.d2, d.set_first_mode_const);
-    for (int s = 0; s < 2; ++s) w.tower[s] = a.take_bytes(w.tower_bytes);
+    for (int s = 0; s < 2; ++s) {
+        w.tower[s] = a.take_bytes(w.tower_bytes);
+        if (w.mixed) w.tv[s] = nsvd_tower16_views(2, d.B, d.d0, d.d1, d.d2, w.tower[s]);
+    }
     w.cdk = a.take_bytes(w.cdk_bytes);
     const size_t bl = (size_t)d.B * d.d2;
     for (int s = 0; s < 2; ++s) {
@@ -206,7 +219,7 @@ StepWs carve_step(const nsvd_cdk_step_desc& d, void* base) {
     for (int s = 0; s < 2; ++s) w.grad[s] = a.take(g);
     // mixed precision with the fused narrow end: the small tensors' squares come from the kernels that write those
     // gradients (one float per strip of columns: d1 / 64 + nsvd_narrow_sumsq_count(d2) per tower)
-    w.nsmall = (d.gemm_bf16 != 0 && nsvd_narrow_supported(2, d.B, d.d2)) ? (d.d1 / 64 + nsvd_narrow_sumsq_count(d.d2)) : 0;
+    w.nsmall = w.fused_end ? (d.d1 / 64 + nsvd_narrow_sumsq_count(d.d2)) : 0;
     w.npartial = SUMSQ_BLOCKS + 2 * (nsvd_tower_sumsq_count(d.d0, d.d1, d.d2, d.gemm_bf16 != 0) + w.nsmall);
     w.partial = a.take((size_t)w.npartial);
     w.scal = a.take(64);
@@ -226,10 +239,144 @@ bool desc_ok(const nsvd_cdk_step_desc* d) {
     return true;
 }
 
-float* const* tower_fields(const nsvd_tower_params& t, float* out[NT]) {
-    out[0] = t.W1; out[1] = t.b1; out[2] = t.g1; out[3] = t.be1;
-    out[4] = t.W2; out[5] = t.b2; out[6] = t.g2; out[7] = t.be2;
-    return out;
+// One step: what its stages share, and the stages (in the order of this file's opening comment; the float32 mode goes
+// tower by tower, so a tower's forward and its normalisation are one stage, and likewise their backward).
+// Tower t = 0 embeds x, t = 1 embeds y.
+struct Step {
+    const nsvd_cdk_step_desc* d;
+    StepWs w;
+    hipStream_t s;
+    float r_up;
+    const float* in[2];
+    const nsvd_tower_params* par[2];     // parameters (updated in place)
+    const nsvd_tower_params* mom[2];     // momentum buffers
+    nsvd_tower_params grad[2];           // gradient targets: views of w.grad
+    const nsvd_tower_params* gradp[2];
+    float* sq[2];        // per tower: the partial sums of squares its gradient kernels leave (inside w.partial) ...
+    int nsq;             // ... the first nsq of them by the weight-gradient contractions, w.nsmall more behind them
+    NsvdCdkLossParts lparts;
+
+    int forward_towers_and_normalize();
+    int loss_and_its_backward(const float* v, const float* M, float* rs_joint, float* rs_indep);
+    int normalize_and_towers_backward();
+    int clip_and_step(float* loss);
+};
+
+// towers forward (BatchNorm running statistics updated, as a training-mode module does), normalize: w.z, w.e
+int Step::forward_towers_and_normalize() {
+    const int B = d->B, L = d->d2;
+    int rc = 0;
+    if (w.mixed) {
+        rc = nsvd_tower16_forward_pair(in, par, B, d->d0, d->d1, d->d2, d->slope, d->bn_eps, d->bn_momentum, 1,
+                                       d->gemm_bf16 | (w.fused_end ? NSVD_TOWER16_WIDE_ONLY : 0), w.z,
+                                       w.tower, w.tower_bytes, s);
+        if (rc) return rc;
+    }
+    if (w.fused_end) {
+        NsvdNarrowFwd f;
+        memset(&f, 0, sizeof(f));
+        for (int t = 0; t < 2; ++t) {
+            const NsvdTower16Views& tv = w.tv[t];
+            f.Y2p[t] = tv.Y2p; f.bias[t] = par[t]->b2; f.gamma[t] = par[t]->g2; f.beta[t] = par[t]->be2;
+            f.running_mean[t] = par[t]->rm2; f.running_var[t] = par[t]->rv2;
+            f.mean[t] = tv.mean2; f.invstd[t] = tv.inv2; f.Y2[t] = tv.Y2; f.z[t] = w.z[t]; f.e[t] = w.e[t];
+        }
+        f.nt = 2; f.B = B; f.N = L; f.S = w.tv[0].S; f.slice_stride = w.tv[0].slice_stride; f.part = w.narrow;
+        f.eps = d->bn_eps; f.momentum = d->bn_momentum; f.r_up = r_up;
+        f.sphere = d->normalize_mode == NSVD_NORMALIZE_L2_SPHERE;
+        return nsvd_narrow_forward(f, s);
+    }
+    for (int t = 0; t < 2; ++t) {
+        if (!w.mixed) {
+            rc = nsvd_tower_forward(in[t], par[t], B, d->d0, d->d1, d->d2, d->slope, d->bn_eps, d->bn_momentum, 1, 0,
+                                    w.z[t], w.tower[t], w.tower_bytes, s);
+            if (rc) return rc;
+        }
+        rc = nsvd_row_normalize_forward(w.z[t], B, L, r_up, d->normalize_mode, w.e[t], s);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// the loss (per-block partials: the optimiser kernel adds them) and its gradient w.r.t. the two embeddings: w.ge
+int Step::loss_and_its_backward(const float* v, const float* M, float* rs_joint, float* rs_indep) {
+    const int rc = nsvd_cdk_loss_forward_parts(w.e[0], w.e[1], nullptr, v, M, d->B, d->d2, d->set_first_mode_const,
+                                               rs_joint, rs_indep, w.cdk, w.cdk_bytes, &lparts, s);
+    if (rc) return rc;
+    return nsvd_cdk_loss_backward(v, d->B, d->d2, d->set_first_mode_const, nullptr, w.ge[0], w.ge[1], w.cdk,
+                                  w.cdk_bytes, s);
+}
+
+// normalize backward, towers backward: the gradients (grad) and the partial sums of their squares (sq)
+int Step::normalize_and_towers_backward() {
+    const int B = d->B, L = d->d2;
+    int rc = 0;
+    if (w.fused_end) {  // both, and the second BatchNorm's: 16-bit dY2 into the towers' workspaces
+        NsvdNarrowBwd b;
+        memset(&b, 0, sizeof(b));
+        for (int t = 0; t < 2; ++t) {
+            const NsvdTower16Views& tv = w.tv[t];
+            b.z[t] = w.z[t]; b.ge[t] = w.ge[t]; b.Y2[t] = tv.Y2; b.mean[t] = tv.mean2; b.invstd[t] = tv.inv2;
+            b.gamma[t] = par[t]->g2; b.dz[t] = w.dz[t]; b.dY[t] = tv.dY2h;
+            b.dgamma[t] = grad[t].g2; b.dbeta[t] = grad[t].be2; b.dbias[t] = grad[t].b2;
+            b.sumsq[t] = sq[t] + nsq + d->d1 / 64;  // (behind the contractions' and the first BatchNorm's)
+        }
+        b.nt = 2; b.B = B; b.N = L; b.dy_bf16 = (d->gemm_bf16 & NSVD_TOWER16_F16) ? 2 : 1; b.part = w.narrow;
+        b.r_up = r_up;
+        b.loss_scale = d->grad_scaler ? &((const nsvd_grad_scaler*)d->grad_scaler)->scale : nullptr;
+        b.sphere = d->normalize_mode == NSVD_NORMALIZE_L2_SPHERE;
+        rc = nsvd_narrow_backward(b, s);
+        if (rc) return rc;
+    }
+    for (int t = 0; t < 2 && !w.fused_end; ++t) {
+        rc = nsvd_row_normalize_backward(w.z[t], w.ge[t], B, L, r_up, d->normalize_mode, w.dz[t], s);
+        if (rc) return rc;
+        if (w.mixed) continue;
+        rc = nsvd_tower_backward_sumsq(in[t], par[t], w.dz[t], B, d->d0, d->d1, d->d2, d->slope, 0, &grad[t],
+                                       w.tower[t], w.tower_bytes, sq[t], s);
+        if (rc) return rc;
+    }
+    if (!w.mixed) return 0;
+    const int flags = (d->gemm_bf16 & NSVD_TOWER16_F16) |
+                      (w.fused_end ? NSVD_TOWER16_WIDE_ONLY | NSVD_TOWER16_SMALL_SUMSQ : 0);
+    return nsvd_tower16_backward_pair(in, par, w.dz, B, d->d0, d->d1, d->d2, d->slope, gradp, w.tower, w.tower_bytes,
+                                      sq, s, flags);
+}
+
+// clip_grad_norm_ + SGD momentum over all 16 tensors, the step's loss value, GradScaler.update()
+int Step::clip_and_step(float* loss) {
+    TensorTable tab;
+    memset(&tab, 0, sizeof(tab));
+    size_t q4 = 0;
+    for (int t = 0; t < 2; ++t)
+        for (int k = 0; k < NT; ++k) {
+            const int i = t * NT + k;
+            float* nsvd_tower_params::*f = NSVD_TOWER_FIELDS[k];
+            tab.p[i] = par[t]->*f; tab.buf[i] = mom[t]->*f; tab.g[i] = grad[t].*f; tab.n[i] = w.gn[k];
+            tab.h[i] = (unsigned short*)(k == 0 ? w.tv[t].W1h : (k == 4 ? w.tv[t].W2h : nullptr));
+            tab.start[i] = q4;
+            q4 += (w.gn[k] + 3) / 4;
+        }
+    tab.start[2 * NT] = q4;
+    tab.h_f16 = (d->gemm_bf16 & NSVD_TOWER16_F16) ? 1 : 0;
+    if (!w.fused_end) {
+        hipLaunchKernelGGL(cdk_sumsq_kernel, dim3(SUMSQ_BLOCKS), dim3(256), 0, s, tab, w.partial);
+        NSVD_CHECK_LAUNCH();
+    }
+    // (fused end: the SUMSQ_BLOCKS slots are unused - the partials the optimiser adds start behind them)
+    const float* part0 = w.fused_end ? w.partial + SUMSQ_BLOCKS : w.partial;
+    const int npart = w.fused_end ? w.npartial - SUMSQ_BLOCKS : w.npartial;
+    size_t blocks = (q4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;  // (each workgroup first adds the partials for itself: not too many of them)
+    hipLaunchKernelGGL(cdk_sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, tab, part0, npart,
+                       (float)d->max_grad_norm, w.scal, loss, (float)d->lr, (float)d->momentum, d->first_step, lparts,
+                       (const nsvd_grad_scaler*)d->grad_scaler);
+    NSVD_CHECK_LAUNCH();
+    if (d->grad_scaler) {
+        hipLaunchKernelGGL(cdk_scaler_update_kernel, dim3(1), dim3(1), 0, s, (nsvd_grad_scaler*)d->grad_scaler, w.scal);
+        NSVD_CHECK_LAUNCH();
+    }
+    return 0;
 }
 
 }  // namespace
@@ -255,140 +402,31 @@ extern "C" int nsvd_cdk_step(const nsvd_cdk_step_desc* d, const float* x, const 
                              const float* M, float* loss, float* rs_joint, float* rs_indep, void* ws,
                              size_t ws_bytes, void* stream) {
     if (!desc_ok(d) || !x || !y || !towers || !momentum_bufs || !v || !M || !loss || !ws) return NSVD_EINVAL;
-    const StepWs w = carve_step(*d, ws);
-    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const int B = d->B, L = d->d2;
-    const float r_up = sqrtf(d->mu);
-    const float* in[2] = {x, y};
-    int rc = 0;
-    // forward: towers (BatchNorm running statistics updated, as a training-mode module does), normalisation
-    const bool mixed = d->gemm_bf16 != 0;
-    const nsvd_tower_params* tp[2] = {&towers[0], &towers[1]};
-    // mixed precision: both towers through every launch together (tower.hip, mixed-precision section), and the narrow
-    // end - split-K sum, second BatchNorm, normalisation - as three launches for both (cdk_narrow.hip)
-    const bool narrow = mixed && nsvd_narrow_supported(2, B, L);
-    NsvdTowerNarrowViews nv[2];
-    if (mixed) {
-        rc = nsvd_tower16_forward_pair(in, tp, B, d->d0, d->d1, d->d2, d->slope, d->bn_eps, d->bn_momentum, 1,
-                                       d->gemm_bf16 | (narrow ? NSVD_TOWER16_WIDE_ONLY : 0), w.z, w.tower,
-                                       w.tower_bytes, s);
-        if (rc) return rc;
-    }
-    if (narrow) {
-        NsvdNarrowFwd f;
-        memset(&f, 0, sizeof(f));
-        for (int t = 0; t < 2; ++t) {
-            nv[t] = nsvd_tower16_narrow_views(2, B, d->d0, d->d1, d->d2, w.tower[t]);
-            f.Y2p[t] = nv[t].Y2p; f.bias[t] = towers[t].b2; f.gamma[t] = towers[t].g2; f.beta[t] = towers[t].be2;
-            f.running_mean[t] = towers[t].rm2; f.running_var[t] = towers[t].rv2;
-            f.mean[t] = nv[t].mean2; f.invstd[t] = nv[t].inv2; f.Y2[t] = nv[t].Y2; f.z[t] = w.z[t]; f.e[t] = w.e[t];
-        }
-        f.nt = 2; f.B = B; f.N = L; f.S = nv[0].S; f.slice_stride = nv[0].slice_stride; f.part = w.narrow;
-        f.eps = d->bn_eps; f.momentum = d->bn_momentum; f.r_up = r_up;
-        f.sphere = d->normalize_mode == NSVD_NORMALIZE_L2_SPHERE;
-        rc = nsvd_narrow_forward(f, s);
-        if (rc) return rc;
-    }
-    for (int t = 0; t < 2 && !narrow; ++t) {
-        if (!mixed) {
-            rc = nsvd_tower_forward(in[t], &towers[t], B, d->d0, d->d1, d->d2, d->slope, d->bn_eps, d->bn_momentum, 1,
-                                    0, w.z[t], w.tower[t], w.tower_bytes, stream);
-            if (rc) return rc;
-        }
-        rc = nsvd_row_normalize_forward(w.z[t], B, L, r_up, d->normalize_mode, w.e[t], stream);
-        if (rc) return rc;
-    }
-    // loss and its gradient w.r.t. the two embeddings
-    NsvdCdkLossParts lparts;
-    rc = nsvd_cdk_loss_forward_parts(w.e[0], w.e[1], nullptr, v, M, B, L, d->set_first_mode_const, rs_joint, rs_indep,
-                                     w.cdk, w.cdk_bytes, &lparts, s);
-    if (rc) return rc;
-    rc = nsvd_cdk_loss_backward(v, B, L, d->set_first_mode_const, nullptr, w.ge[0], w.ge[1], w.cdk, w.cdk_bytes, stream);
-    if (rc) return rc;
-    // backward: normalisation, towers (gradients into the workspace)
-    TensorTable tab;
-    memset(&tab, 0, sizeof(tab));
-    size_t q4 = 0;
-    nsvd_tower_params gr[2];
-    float* gp[2][NT];
-    const int nsq = nsvd_tower_sumsq_count(d->d0, d->d1, d->d2, mixed);
-    float* sq[2] = {w.partial + SUMSQ_BLOCKS, w.partial + SUMSQ_BLOCKS + nsq + w.nsmall};
-    const bool small_fused = narrow && w.nsmall > 0;
+    Step st;
+    memset(&st, 0, sizeof(st));
+    st.d = d;
+    st.w = carve_step(*d, ws);
+    if (!nsvd_ws_ok(ws, ws_bytes, st.w.bytes)) return NSVD_EINVAL;
+    st.s = (hipStream_t)stream;
+    st.r_up = sqrtf(d->mu);
+    st.in[0] = x; st.in[1] = y;
+    st.nsq = nsvd_tower_sumsq_count(d->d0, d->d1, d->d2, d->gemm_bf16 != 0);
     for (int t = 0; t < 2; ++t) {
-        if (!narrow) {
-            rc = nsvd_row_normalize_backward(w.z[t], w.ge[t], B, L, r_up, d->normalize_mode, w.dz[t], stream);
-            if (rc) return rc;
+        // every tensor the step reads or updates, before the first launch: there, and aligned for the optimiser's float4
+        if (!nsvd_tower_fields_ok(&towers[t], true) || !nsvd_tower_fields_ok(&momentum_bufs[t], false)) return NSVD_EINVAL;
+        st.par[t] = &towers[t];
+        st.mom[t] = &momentum_bufs[t];
+        st.gradp[t] = &st.grad[t];
+        int k = 0;
+        for (float* nsvd_tower_params::*f : NSVD_TOWER_FIELDS) {
+            if ((((uintptr_t)(towers[t].*f) | (uintptr_t)(momentum_bufs[t].*f)) & 15) != 0) return NSVD_EINVAL;
+            st.grad[t].*f = st.w.grad[t] + st.w.goff[k++];
         }
-        nsvd_tower_params& g = gr[t];
-        memset(&g, 0, sizeof(g));
-        for (int k = 0; k < NT; ++k) gp[t][k] = w.grad[t] + w.goff[k];
-        g.W1 = gp[t][0]; g.b1 = gp[t][1]; g.g1 = gp[t][2]; g.be1 = gp[t][3];
-        g.W2 = gp[t][4]; g.b2 = gp[t][5]; g.g2 = gp[t][6]; g.be2 = gp[t][7];
-        if (!mixed) {
-            rc = nsvd_tower_backward_sumsq(in[t], &towers[t], w.dz[t], B, d->d0, d->d1, d->d2, d->slope, 0, &g,
-                                           w.tower[t], w.tower_bytes, sq[t], stream);
-            if (rc) return rc;
-        }
+        st.sq[t] = st.w.partial + SUMSQ_BLOCKS + t * (st.nsq + st.w.nsmall);
     }
-    if (narrow) {  // normalisation backward, second BatchNorm backward -> bfloat16 dY2 in the towers' workspaces
-        NsvdNarrowBwd b;
-        memset(&b, 0, sizeof(b));
-        for (int t = 0; t < 2; ++t) {
-            b.z[t] = w.z[t]; b.ge[t] = w.ge[t]; b.Y2[t] = nv[t].Y2; b.mean[t] = nv[t].mean2; b.invstd[t] = nv[t].inv2;
-            b.gamma[t] = towers[t].g2; b.dz[t] = w.dz[t]; b.dY[t] = nv[t].dY2h;
-            b.dgamma[t] = gr[t].g2; b.dbeta[t] = gr[t].be2; b.dbias[t] = gr[t].b2;
-            b.sumsq[t] = small_fused ? sq[t] + nsq + d->d1 / 64 : nullptr;
-        }
-        b.nt = 2; b.B = B; b.N = L; b.dy_bf16 = (d->gemm_bf16 & NSVD_TOWER16_F16) ? 2 : 1; b.part = w.narrow; b.r_up = r_up;
-        b.loss_scale = d->grad_scaler ? &((const nsvd_grad_scaler*)d->grad_scaler)->scale : nullptr;
-        b.sphere = d->normalize_mode == NSVD_NORMALIZE_L2_SPHERE;
-        rc = nsvd_narrow_backward(b, s);
-        if (rc) return rc;
-    }
-    if (mixed) {
-        const nsvd_tower_params* gq[2] = {&gr[0], &gr[1]};
-        const float* dzs[2] = {w.dz[0], w.dz[1]};
-        rc = nsvd_tower16_backward_pair(in, tp, dzs, B, d->d0, d->d1, d->d2, d->slope, gq, w.tower, w.tower_bytes, sq, s,
-                                        (narrow ? NSVD_TOWER16_WIDE_ONLY : 0) | (small_fused ? NSVD_TOWER16_SMALL_SUMSQ : 0) |
-                                            (d->gemm_bf16 & NSVD_TOWER16_F16));
-        if (rc) return rc;
-    }
-    for (int t = 0; t < 2; ++t) {
-        float *pp[NT], *bb[NT];
-        tower_fields(towers[t], pp);
-        tower_fields(momentum_bufs[t], bb);
-        void *w1h = nullptr, *w2h = nullptr;
-        if (mixed) nsvd_tower16_weight_copies(B, d->d0, d->d1, d->d2, w.tower[t], &w1h, &w2h);
-        for (int k = 0; k < NT; ++k) {
-            const int i = t * NT + k;
-            if (!pp[k] || !bb[k]) return NSVD_EINVAL;
-            if ((((uintptr_t)pp[k] | (uintptr_t)bb[k]) & 15) != 0) return NSVD_EINVAL;
-            tab.p[i] = pp[k]; tab.buf[i] = bb[k]; tab.g[i] = gp[t][k]; tab.n[i] = w.gn[k];
-            tab.h[i] = k == 0 ? (unsigned short*)w1h : (k == 4 ? (unsigned short*)w2h : nullptr);
-            tab.start[i] = q4;
-            q4 += (w.gn[k] + 3) / 4;
-        }
-    }
-    tab.start[2 * NT] = q4;
-    tab.h_f16 = (d->gemm_bf16 & NSVD_TOWER16_F16) ? 1 : 0;
-    // clip_grad_norm_ + SGD momentum over all 16 tensors
-    if (!small_fused) {
-        hipLaunchKernelGGL(cdk_sumsq_kernel, dim3(SUMSQ_BLOCKS), dim3(256), 0, s, tab, w.partial);
-        NSVD_CHECK_LAUNCH();
-    }
-    // (small_fused: the SUMSQ_BLOCKS slots are unused - the partials the optimiser adds start behind them)
-    const float* part0 = small_fused ? w.partial + SUMSQ_BLOCKS : w.partial;
-    const int npart = small_fused ? w.npartial - SUMSQ_BLOCKS : w.npartial;
-    size_t blocks = (q4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;  // (each workgroup first adds the partials for itself: not too many of them)
-    hipLaunchKernelGGL(cdk_sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, tab, part0, npart,
-                       (float)d->max_grad_norm, w.scal, loss, (float)d->lr, (float)d->momentum, d->first_step, lparts,
-                       (const nsvd_grad_scaler*)d->grad_scaler);
-    NSVD_CHECK_LAUNCH();
-    if (d->grad_scaler) {
-        hipLaunchKernelGGL(cdk_scaler_update_kernel, dim3(1), dim3(1), 0, s, (nsvd_grad_scaler*)d->grad_scaler, w.scal);
-        NSVD_CHECK_LAUNCH();
-    }
-    return 0;
+    int rc = st.forward_towers_and_normalize();
+    if (!rc) rc = st.loss_and_its_backward(v, M, rs_joint, rs_indep);
+    if (!rc) rc = st.normalize_and_towers_backward();
+    if (!rc) rc = st.clip_and_step(loss);
+    return rc;
 }

@@ -165,6 +165,14 @@ int nsvd_rmsprop_table_launch(NsvdOptTable& t, const NsvdHyper& h, hipStream_t s
 
 // ---- CDK towers (tower.hip): the backward with per-workgroup sums of squares of the two weight-gradient contractions
 // (cdk_step.hip clips the global gradient norm without another pass over them)
+// the eight tensors of a tower that have a gradient, in the order every table over them uses (cdk_step.hip: parameters,
+// momentum buffers, gradients); the running statistics are the struct's other four
+constexpr float* nsvd_tower_params::*NSVD_TOWER_FIELDS[8] = {
+    &nsvd_tower_params::W1, &nsvd_tower_params::b1, &nsvd_tower_params::g1, &nsvd_tower_params::be1,
+    &nsvd_tower_params::W2, &nsvd_tower_params::b2, &nsvd_tower_params::g2, &nsvd_tower_params::be2};
+// is every one of them there (and, need_running, the running statistics)? The one check of every tower entry point, for
+// parameters and for gradient targets alike
+bool nsvd_tower_fields_ok(const nsvd_tower_params* t, bool need_running);
 int nsvd_tower_sumsq_count(int d0, int d1, int d2, int gemm_bf16 = 0);
 int nsvd_tower_backward_sumsq(const float* x, const nsvd_tower_params* p, const float* dz, int B, int d0, int d1,
                               int d2, float slope, int gemm_bf16, const nsvd_tower_params* grads, void* ws,
@@ -185,7 +193,16 @@ int nsvd_tower16_forward_pair(const float* const* x, const nsvd_tower_params* co
 int nsvd_tower16_backward_pair(const float* const* x, const nsvd_tower_params* const* p, const float* const* dz, int B,
                                int d0, int d1, int d2, float slope, const nsvd_tower_params* const* grads,
                                void* const* ws, size_t ws_bytes, float* const* sumsq, hipStream_t s, int flags = 0);
-void nsvd_tower16_weight_copies(int B, int d0, int d1, int d2, void* ws, void** W1h, void** W2h);
+// what the step addresses inside a mixed-precision tower's workspace: the narrow end's buffers with the split-K slice
+// count of a launch of nt towers (cdk_narrow.hip runs on them), and the 16-bit copies of W1 / W2 (the optimiser kernel
+// of the fused step refreshes them)
+struct NsvdTower16Views {
+    float *Y2p, *Y2, *mean2, *inv2;
+    void *dY2h, *W1h, *W2h;
+    int S;
+    size_t slice_stride;
+};
+NsvdTower16Views nsvd_tower16_views(int nt, int B, int d0, int d1, int d2, void* ws);
 
 // ---- the narrow end of a CDK step for both towers at once (cdk_narrow.hip): split-K sum + bias, BatchNorm2 (training),
 // normalize; and the backward of the three. Per tower t < nt.
@@ -267,11 +284,3 @@ int nsvd_narrow_sumsq_count(int N);
 bool nsvd_narrow_supported(int nt, int B, int N);
 int nsvd_narrow_forward(const NsvdNarrowFwd& a, hipStream_t s);
 int nsvd_narrow_backward(const NsvdNarrowBwd& a, hipStream_t s);
-// a mixed-precision tower's narrow-end buffers inside its workspace, and the split-K slice count of a launch of nt towers
-struct NsvdTowerNarrowViews {
-    float *Y2p, *Y2, *mean2, *inv2;
-    void* dY2h;
-    int S;
-    size_t slice_stride;
-};
-NsvdTowerNarrowViews nsvd_tower16_narrow_views(int nt, int B, int d0, int d1, int d2, void* ws);

@@ -818,31 +818,95 @@ inline bool tower16_fused(int B, int d0, int d1, int d2, float slope) {
 constexpr int MIXED_WEIGHTS_READY = 2;
 // bit 4 (NSVD_TOWER16_F16 = 16): the half type is IEEE float16 instead of bfloat16
 
-int tower16_forward(int nt, const float* const* x, const nsvd_tower_params* const* p, int B, int d0, int d1, int d2,
-                    float slope, float eps, float momentum, int update_running, int flags, int phase, float* const* z,
-                    void* const* ws, hipStream_t s) {
-    if (!tower16_shape_ok(B, d0, d1, d2)) return NSVD_EUNSUPPORTED;
+// the <true> (IEEE float16) or <false> (bfloat16) instance of a `template <bool F16>` kernel
+#define TOWER_LAUNCH_HALF(kernel, f16, grid, block, s, arg)                     \
+    do {                                                                        \
+        if (f16) hipLaunchKernelGGL(kernel<true>, grid, block, 0, s, arg);      \
+        else hipLaunchKernelGGL(kernel<false>, grid, block, 0, s, arg);         \
+        NSVD_CHECK_LAUNCH();                                                    \
+    } while (0)
+
+// tiles (= sum-of-squares partials) of the two weight-gradient contractions in mixed precision: dW2's, then dW1's
+inline int sumsq_count16(int d0, int d1, int d2) { return (d2 / 256) * (d1 / 128) + (d1 / 256) * (d0 / 128); }
+
+// One call over nt <= 2 towers of one shape, each with a workspace of its own. Every entry point builds one at its top
+// (tower_call, then tower_forward / tower_backward with that side's tensors), and the launch sequences below are its
+// members; the workspaces are carved there and nowhere else. float32 calls have nt = 1; mixed-precision calls put their
+// nt towers through every launch together.
+struct TowerCall {
+    int nt, B, d0, d1, d2;
+    float slope, eps, momentum;
+    int update_running, flags, phase;
+    bool mixed, wide_only, fused;  // fused: tower16_fused, asked once per call
+    int f16;                       // the half type is IEEE float16 (0: bfloat16)
+    int S;                         // split-K slices of the second forward contraction, in this call's mode
+    const float* x[2];
+    const nsvd_tower_params* p[2];
+    float* z[2];                        // forward
+    const float* dz[2];                 // backward
+    const nsvd_tower_params* grads[2];
+    float* sumsq[2];                    // null: no sums of squares
     TowerWs w[2];
     Tower16 v[2];
+    hipStream_t s;
+
+    BnFwd bn2_forward_desc(int t, bool bias_here) const;
+    BnBwd bn2_backward_desc(int t, int out16) const;
+    int forward_narrow_end() const;
+    int forward16() const;
+    int forward32() const;
+    int backward16() const;
+    int backward32() const;
+};
+
+// Z = BN2(Y2), from the summed Y2 in the workspace. bias_here: b2 joins in the strip kernel, which writes the biased sum
+// back for the backward (second half of a hidden-width-sharded tower: Y2 holds the all-reduced partial products)
+BnFwd TowerCall::bn2_forward_desc(int t, bool bias_here) const {
+    BnFwd f;
+    memset(&f, 0, sizeof(f));
+    f.Y = w[t].Y2; f.S = 1; f.gamma = p[t]->g2; f.beta = p[t]->be2;
+    if (bias_here) {
+        f.bias = p[t]->b2;
+        f.Ysum = w[t].Y2;
+    }
+    f.running_mean = update_running ? p[t]->rm2 : nullptr; f.running_var = update_running ? p[t]->rv2 : nullptr;
+    f.mean = w[t].mean2; f.invstd = w[t].inv2; f.out = z[t]; f.outT = nullptr; f.B = B; f.N = d2;
+    f.eps = eps; f.momentum = momentum; f.slope = 1.0f;
+    return f;
+}
+
+// dY2 = BN2'(dZ), db2 = its column sums. out16 = 0: float32 dY2 and dY2^T; 1 / 2: bfloat16 / float16 dY2 alone (the
+// Tower16 view dY2h of the same buffer)
+BnBwd TowerCall::bn2_backward_desc(int t, int out16) const {
+    BnBwd b;
+    memset(&b, 0, sizeof(b));
+    b.dout = dz[t]; b.Y = w[t].Y2; b.mean = w[t].mean2; b.invstd = w[t].inv2; b.gamma = p[t]->g2; b.beta = p[t]->be2;
+    b.dY = w[t].dY2; b.dYT = out16 ? nullptr : w[t].dY2T;
+    b.dgamma = grads[t]->g2; b.dbeta = grads[t]->be2; b.dbias = grads[t]->b2;
+    b.B = B; b.N = d2; b.slope = 1.0f; b.bf16_out = out16;
+    return b;
+}
+
+// The narrow end of either forward: Y2 = b2 + the sum of the S split-K partials, then Z = BN2(Y2). phase 1 stops behind
+// the sum (no bias: this rank's partial Y2 is in the workspace, nsvd_tower_y2_offset); phase 2 is the BatchNorm alone,
+// on the all-reduced Y2, with the bias joining there.
+int TowerCall::forward_narrow_end() const {
+    for (int t = 0; t < nt && phase != 2; ++t) {
+        const size_t n4 = (size_t)B * d2 / 4;
+        hipLaunchKernelGGL(tower_sum_slices_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, w[t].Y2p,
+                           (size_t)B * d2, S, phase == 1 ? nullptr : p[t]->b2, w[t].Y2, d2, n4);
+        NSVD_CHECK_LAUNCH();
+    }
+    if (phase == 1) return 0;
     for (int t = 0; t < nt; ++t) {
-        w[t] = carve_tower(B, d0, d1, d2, ws[t]);
-        v[t] = views16(w[t]);
+        const int rc = launch_bn_forward(bn2_forward_desc(t, phase == 2), s);
+        if (rc) return rc;
     }
+    return 0;
+}
+
+int TowerCall::forward16() const {
     int rc = 0;
-    if (phase == 2) {
-        // second half of a hidden-width-sharded tower: Y2 holds the all-reduced partial products
-        for (int t = 0; t < nt; ++t) {
-            BnFwd f;
-            memset(&f, 0, sizeof(f));
-            f.Y = w[t].Y2; f.S = 1; f.bias = p[t]->b2; f.Ysum = w[t].Y2; f.gamma = p[t]->g2; f.beta = p[t]->be2;
-            f.running_mean = update_running ? p[t]->rm2 : nullptr; f.running_var = update_running ? p[t]->rv2 : nullptr;
-            f.mean = w[t].mean2; f.invstd = w[t].inv2; f.out = z[t]; f.outT = nullptr; f.B = B; f.N = d2;
-            f.eps = eps; f.momentum = momentum; f.slope = 1.0f;
-            rc = launch_bn_forward(f, s);
-            if (rc) return rc;
-        }
-        return 0;
-    }
     {   // casts: X always; the weights unless their copies are current
         CastList c;
         memset(&c, 0, sizeof(c));
@@ -858,12 +922,10 @@ int tower16_forward(int nt, const float* const* x, const nsvd_tower_params* cons
         for (int k = 0; k < n; ++k) maxn = c.n8[k] > maxn ? c.n8[k] : maxn;
         size_t blocks = (maxn + 255) / 256;
         if (blocks > 2048) blocks = 2048;
-        if (flags & NSVD_TOWER16_F16) hipLaunchKernelGGL(tower_cast_list_kernel<true>, dim3((unsigned)blocks, n), dim3(256), 0, s, c);
-        else hipLaunchKernelGGL(tower_cast_list_kernel<false>, dim3((unsigned)blocks, n), dim3(256), 0, s, c);
-        NSVD_CHECK_LAUNCH();
+        TOWER_LAUNCH_HALF(tower_cast_list_kernel, f16, dim3((unsigned)blocks, n), dim3(256), s, c);
     }
     nsvd_g16::Args g;
-    if (tower16_fused(B, d0, d1, d2, slope)) {
+    if (fused) {
         // A1h = lrelu(BN1(Xh W1h^T + b1)) in ONE launch (whole columns per workgroup: tower_col.h)
         nsvd_tcol::Args c;
         memset(&c, 0, sizeof(c));
@@ -875,24 +937,24 @@ int tower16_forward(int nt, const float* const* x, const nsvd_tower_params* cons
             q.mean = w[t].mean1; q.invstd = w[t].inv1; q.out = v[t].A1h;
         }
         c.nt = nt; c.M = B; c.N = d1; c.K = d0; c.eps = eps; c.momentum = momentum; c.slope = slope;
-        c.f16 = (flags & NSVD_TOWER16_F16) ? 1 : 0;
+        c.f16 = f16;
         nsvd_prof_begin(s);  // bench.py --config cfg5 --amp brackets this launch (nsvd_profile_next_forward)
         rc = nsvd_tcol::launch<false>(c, s);
         nsvd_prof_end(s);
         if (rc) return rc;
     } else {
-    // Y1h = Xh W1h^T + b1
-    memset(&g, 0, sizeof(g));
-    for (int t = 0; t < nt; ++t) {
-        g.p[t].A = v[t].Xh; g.p[t].B = v[t].W1h; g.p[t].C = v[t].Y1h; g.p[t].bias = p[t]->b1;
-    }
-    g.nprob = nt; g.K = d0; g.S = 1; g.f16 = (flags & NSVD_TOWER16_F16) ? 1 : 0;
-    nsvd_g16::set_uniform(g, B, d1, d0, d0, d1);
-    nsvd_prof_begin(s);  // bench.py --config cfg5 --amp brackets this contraction (nsvd_profile_next_forward)
-    rc = nsvd_g16::launch(g, false, false, true, s);
-    nsvd_prof_end(s);
-    if (rc) return rc;
-    {   // A1h = lrelu(BN1(Y1h))
+        // Y1h = Xh W1h^T + b1
+        memset(&g, 0, sizeof(g));
+        for (int t = 0; t < nt; ++t) {
+            g.p[t].A = v[t].Xh; g.p[t].B = v[t].W1h; g.p[t].C = v[t].Y1h; g.p[t].bias = p[t]->b1;
+        }
+        g.nprob = nt; g.K = d0; g.S = 1; g.f16 = f16;
+        nsvd_g16::set_uniform(g, B, d1, d0, d0, d1);
+        nsvd_prof_begin(s);  // bench.py --config cfg5 --amp brackets this contraction (nsvd_profile_next_forward)
+        rc = nsvd_g16::launch(g, false, false, true, s);
+        nsvd_prof_end(s);
+        if (rc) return rc;
+        // A1h = lrelu(BN1(Y1h))
         Bn16Fwd f;
         memset(&f, 0, sizeof(f));
         for (int t = 0; t < nt; ++t) {
@@ -902,68 +964,63 @@ int tower16_forward(int nt, const float* const* x, const nsvd_tower_params* cons
             f.mean[t] = w[t].mean1; f.invstd[t] = w[t].inv1; f.out[t] = v[t].A1h;
         }
         f.B = B; f.N = d1; f.eps = eps; f.momentum = momentum; f.slope = slope;
-        if (flags & NSVD_TOWER16_F16) hipLaunchKernelGGL(tower_bn16_forward_kernel<true>, dim3(d1 / BN16_STRIP, nt), dim3(BN16_NT), 0, s, f);
-        else hipLaunchKernelGGL(tower_bn16_forward_kernel<false>, dim3(d1 / BN16_STRIP, nt), dim3(BN16_NT), 0, s, f);
-        NSVD_CHECK_LAUNCH();
-    }
+        TOWER_LAUNCH_HALF(tower_bn16_forward_kernel, f16, dim3(d1 / BN16_STRIP, nt), dim3(BN16_NT), s, f);
     }
     // Y2 partial products, split-K
-    const int S = fwd2_slices16(nt, B, d1, d2);
     memset(&g, 0, sizeof(g));
     for (int t = 0; t < nt; ++t) {
         g.p[t].A = v[t].A1h; g.p[t].B = v[t].W2h; g.p[t].C = w[t].Y2p;
     }
-    g.nprob = nt; g.K = d1; g.S = S; g.f16 = (flags & NSVD_TOWER16_F16) ? 1 : 0;
+    g.nprob = nt; g.K = d1; g.S = S; g.f16 = f16;
     nsvd_g16::set_uniform(g, B, d2, d1, d1, d2);
     g.slice_stride = (long)B * d2;
     rc = nsvd_g16::launch(g, false, false, false, s);
     if (rc) return rc;
-    if (flags & NSVD_TOWER16_WIDE_ONLY) return 0;  // the narrow end is the caller's (cdk_narrow.hip)
-    for (int t = 0; t < nt; ++t) {
-        const size_t n4 = (size_t)B * d2 / 4;
-        hipLaunchKernelGGL(tower_sum_slices_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, w[t].Y2p,
-                           (size_t)B * d2, S, phase == 1 ? nullptr : p[t]->b2, w[t].Y2, d2, n4);
-        NSVD_CHECK_LAUNCH();
-    }
-    if (phase == 1) return 0;
-    for (int t = 0; t < nt; ++t) {
-        BnFwd f;
-        memset(&f, 0, sizeof(f));
-        f.Y = w[t].Y2; f.S = 1; f.gamma = p[t]->g2; f.beta = p[t]->be2;
-        f.running_mean = update_running ? p[t]->rm2 : nullptr; f.running_var = update_running ? p[t]->rv2 : nullptr;
-        f.mean = w[t].mean2; f.invstd = w[t].inv2; f.out = z[t]; f.outT = nullptr; f.B = B; f.N = d2;
-        f.eps = eps; f.momentum = momentum; f.slope = 1.0f;
-        rc = launch_bn_forward(f, s);
-        if (rc) return rc;
-    }
-    return 0;
+    if (wide_only) return 0;  // the narrow end is the caller's (cdk_narrow.hip)
+    return forward_narrow_end();
 }
 
-// tiles (= sum-of-squares partials) of the two weight-gradient contractions in mixed precision: dW2's, then dW1's
-inline int sumsq_count16(int d0, int d1, int d2) { return (d2 / 256) * (d1 / 128) + (d1 / 256) * (d0 / 128); }
-
-int tower16_backward(int nt, const float* const* x, const nsvd_tower_params* const* p, const float* const* dz, int B,
-                     int d0, int d1, int d2, float slope, const nsvd_tower_params* const* grads, void* const* ws,
-                     float* const* sumsq, hipStream_t s, int flags = 0) {
-    if (!tower16_shape_ok(B, d0, d1, d2)) return NSVD_EUNSUPPORTED;
-    TowerWs w[2];
-    Tower16 v[2];
-    for (int t = 0; t < nt; ++t) {
-        w[t] = carve_tower(B, d0, d1, d2, ws[t]);
-        v[t] = views16(w[t]);
-    }
+int TowerCall::forward32() const {
     int rc = 0;
-    for (int t = 0; t < nt && !(flags & NSVD_TOWER16_WIDE_ONLY); ++t) {  // dY2h = BN2'(dZ), db2
-        BnBwd b;
-        memset(&b, 0, sizeof(b));
-        b.dout = dz[t]; b.Y = w[t].Y2; b.mean = w[t].mean2; b.invstd = w[t].inv2; b.gamma = p[t]->g2; b.beta = p[t]->be2;
-        b.dY = (float*)v[t].dY2h; b.dYT = nullptr; b.dgamma = grads[t]->g2; b.dbeta = grads[t]->be2;
-        b.dbias = grads[t]->b2; b.B = B; b.N = d2; b.slope = 1.0f; b.bf16_out = (flags & NSVD_TOWER16_F16) ? 2 : 1;
-        rc = launch_bn_backward(b, s);
+    GemmNT g;
+    BnFwd f;
+    // Y1 = X W1^T + b1
+    memset(&g, 0, sizeof(g));
+    g.A = x[0]; g.lda = d0; g.B = p[0]->W1; g.ldb = d0; g.C = w[0].Y1; g.ldc = d1; g.bias = p[0]->b1;
+    g.M = B; g.N = d1; g.K = d0; g.S = 1;
+    rc = launch_gemm(g, s, true);  // bench.py --config cfg5 brackets this contraction (nsvd_profile_next_forward)
+    if (rc) return rc;
+    // A1 = lrelu(BN1(Y1)), A1^T
+    memset(&f, 0, sizeof(f));
+    f.Y = w[0].Y1; f.S = 1; f.gamma = p[0]->g1; f.beta = p[0]->be1;
+    f.running_mean = update_running ? p[0]->rm1 : nullptr; f.running_var = update_running ? p[0]->rv1 : nullptr;
+    f.mean = w[0].mean1; f.invstd = w[0].inv1; f.out = w[0].A1; f.outT = w[0].A1T; f.B = B; f.N = d1;
+    f.eps = eps; f.momentum = momentum; f.slope = slope;
+    rc = launch_bn_forward(f, s);
+    if (rc) return rc;
+    // Y2 = A1 W2^T, split-K partials (b2 joins in the narrow end)
+    memset(&g, 0, sizeof(g));
+    g.A = w[0].A1; g.lda = d1; g.B = p[0]->W2; g.ldb = d1; g.C = w[0].Y2p; g.ldc = d2; g.slice_stride = (size_t)B * d2;
+    g.M = B; g.N = d2; g.K = d1; g.S = S;
+    rc = launch_gemm(g, s);
+    if (rc) return rc;
+    return forward_narrow_end();
+}
+
+int TowerCall::backward16() const {
+    int rc = 0;
+    for (int t = 0; t < nt && !wide_only; ++t) {  // dY2h = BN2'(dZ), db2
+        rc = launch_bn_backward(bn2_backward_desc(t, 1 + f16), s);
         if (rc) return rc;
     }
+    // the squares of the b1 / g1 / be1 gradients, behind the contractions' partials
+    float* small_sumsq[2];
+    for (int t = 0; t < nt; ++t) {
+        const bool want = sumsq[t] && (flags & NSVD_TOWER16_SMALL_SUMSQ);
+        small_sumsq[t] = want ? sumsq[t] + sumsq_count16(d0, d1, d2) : nullptr;
+    }
     nsvd_g16::Args g;
-    if (tower16_fused(B, d0, d1, d2, slope)) {
+    if (fused) {
         // dY1h = BN1'(lrelu'(dY2h W2h)), dgamma1, dbeta1, db1 in ONE launch (tower_col.h)
         nsvd_tcol::Args c;
         memset(&c, 0, sizeof(c));
@@ -971,54 +1028,149 @@ int tower16_backward(int nt, const float* const* x, const nsvd_tower_params* con
             nsvd_tcol::Prob& q = c.p[t];
             q.A = v[t].dY2h; q.W = v[t].W2h; q.gamma = p[t]->g1; q.beta = p[t]->be1; q.invstd = w[t].inv1;
             q.out = v[t].dY1h; q.A1 = v[t].A1h; q.dgamma = grads[t]->g1; q.dbeta = grads[t]->be1; q.dbias = grads[t]->b1;
-            q.sumsq = (sumsq && (flags & NSVD_TOWER16_SMALL_SUMSQ)) ? sumsq[t] + sumsq_count16(d0, d1, d2) : nullptr;
+            q.sumsq = small_sumsq[t];
         }
         c.nt = nt; c.M = B; c.N = d1; c.K = d2; c.slope = slope;
-        c.f16 = (flags & NSVD_TOWER16_F16) ? 1 : 0;
+        c.f16 = f16;
         rc = nsvd_tcol::launch<true>(c, s);
         if (rc) return rc;
     } else {
-    // dA1h = dY2h W2h
-    memset(&g, 0, sizeof(g));
-    for (int t = 0; t < nt; ++t) {
-        g.p[t].A = v[t].dY2h; g.p[t].B = v[t].W2h; g.p[t].C = v[t].dA1h;
-    }
-    g.nprob = nt; g.K = d2; g.S = 1; g.f16 = (flags & NSVD_TOWER16_F16) ? 1 : 0;
-    nsvd_g16::set_uniform(g, B, d1, d2, d1, d1);
-    rc = nsvd_g16::launch(g, false, true, true, s);
-    if (rc) return rc;
-    {   // dY1h = BN1'(lrelu'(dA1h)), db1
+        // dA1h = dY2h W2h
+        memset(&g, 0, sizeof(g));
+        for (int t = 0; t < nt; ++t) {
+            g.p[t].A = v[t].dY2h; g.p[t].B = v[t].W2h; g.p[t].C = v[t].dA1h;
+        }
+        g.nprob = nt; g.K = d2; g.S = 1; g.f16 = f16;
+        nsvd_g16::set_uniform(g, B, d1, d2, d1, d1);
+        rc = nsvd_g16::launch(g, false, true, true, s);
+        if (rc) return rc;
+        // dY1h = BN1'(lrelu'(dA1h)), db1
         Bn16Bwd b;
         memset(&b, 0, sizeof(b));
         for (int t = 0; t < nt; ++t) {
             b.dout[t] = v[t].dA1h; b.Y[t] = v[t].Y1h; b.mean[t] = w[t].mean1; b.invstd[t] = w[t].inv1;
             b.gamma[t] = p[t]->g1; b.beta[t] = p[t]->be1; b.dY[t] = v[t].dY1h; b.dgamma[t] = grads[t]->g1;
             b.dbeta[t] = grads[t]->be1; b.dbias[t] = grads[t]->b1;
-            b.sumsq[t] = (sumsq && (flags & NSVD_TOWER16_SMALL_SUMSQ)) ? sumsq[t] + sumsq_count16(d0, d1, d2) : nullptr;
+            b.sumsq[t] = small_sumsq[t];
         }
         b.B = B; b.N = d1; b.slope = slope;
-        if (flags & NSVD_TOWER16_F16) hipLaunchKernelGGL(tower_bn16_backward_kernel<true>, dim3(d1 / BN16_STRIP, nt), dim3(BN16_NT), 0, s, b);
-        else hipLaunchKernelGGL(tower_bn16_backward_kernel<false>, dim3(d1 / BN16_STRIP, nt), dim3(BN16_NT), 0, s, b);
-        NSVD_CHECK_LAUNCH();
-    }
+        TOWER_LAUNCH_HALF(tower_bn16_backward_kernel, f16, dim3(d1 / BN16_STRIP, nt), dim3(BN16_NT), s, b);
     }
     // dW2 = dY2h^T A1h and dW1 = dY1h^T Xh of every tower in ONE launch (same operand forms, same contraction length B,
     // different output shapes): a kernel boundary of these launches costs as much as a third of their MFMA work
     memset(&g, 0, sizeof(g));
     for (int t = 0; t < nt; ++t) {
         nsvd_g16::Prob& q2 = g.p[t];
-        q2.A = v[t].dY2h; q2.B = v[t].A1h; q2.C = grads[t]->W2; q2.sumsq = sumsq ? sumsq[t] : nullptr;
+        q2.A = v[t].dY2h; q2.B = v[t].A1h; q2.C = grads[t]->W2; q2.sumsq = sumsq[t];
         q2.M = d2; q2.N = d1; q2.lda = d2; q2.ldb = d1; q2.ldc = d1;
         nsvd_g16::Prob& q1 = g.p[nt + t];
         q1.A = v[t].dY1h; q1.B = v[t].Xh; q1.C = grads[t]->W1;
-        q1.sumsq = sumsq ? sumsq[t] + (d2 / 256) * (d1 / 128) : nullptr;
+        q1.sumsq = sumsq[t] ? sumsq[t] + (d2 / 256) * (d1 / 128) : nullptr;
         q1.M = d1; q1.N = d0; q1.lda = d1; q1.ldb = d0; q1.ldc = d0;
     }
-    g.nprob = 2 * nt; g.K = B; g.S = 1; g.f16 = (flags & NSVD_TOWER16_F16) ? 1 : 0;
+    g.nprob = 2 * nt; g.K = B; g.S = 1; g.f16 = f16;
     return nsvd_g16::launch(g, true, true, false, s);
 }
 
+int TowerCall::backward32() const {
+    // dY2 = BN2'(dZ), dY2^T, db2 = column sums of dY2
+    int rc = launch_bn_backward(bn2_backward_desc(0, 0), s);
+    if (rc) return rc;
+    // dW2 = dY2^T A1  (A = dY2^T (d2, B), B = A1^T (d1, B), K = B)
+    GemmNT g;
+    memset(&g, 0, sizeof(g));
+    g.A = w[0].dY2T; g.lda = B; g.B = w[0].A1T; g.ldb = B; g.C = grads[0]->W2; g.ldc = d1;
+    g.M = d2; g.N = d1; g.K = B; g.S = 1;
+    g.sumsq = sumsq[0];
+    rc = launch_gemm(g, s);
+    if (rc) return rc;
+    // W2^T (d1, d2), then dA1 = dY2 W2  (A = dY2 (B, d2), B = W2^T (d1, d2), K = d2)
+    hipLaunchKernelGGL(tower_transpose_kernel, dim3((d2 / 32) * (d1 / 32)), dim3(256), 0, s, p[0]->W2, w[0].W2T, d2, d1);
+    NSVD_CHECK_LAUNCH();
+    memset(&g, 0, sizeof(g));
+    g.A = w[0].dY2; g.lda = d2; g.B = w[0].W2T; g.ldb = d2; g.C = w[0].dA1; g.ldc = d1;
+    g.M = B; g.N = d1; g.K = d2; g.S = 1;
+    rc = launch_gemm(g, s);
+    if (rc) return rc;
+    // dY1^T = (BN1'(lrelu'(dA1)))^T, db1
+    BnBwd b;
+    memset(&b, 0, sizeof(b));
+    b.dout = w[0].dA1; b.Y = w[0].Y1; b.mean = w[0].mean1; b.invstd = w[0].inv1; b.gamma = p[0]->g1; b.beta = p[0]->be1;
+    b.dY = nullptr; b.dYT = w[0].dY1T; b.dgamma = grads[0]->g1; b.dbeta = grads[0]->be1; b.dbias = grads[0]->b1;
+    b.B = B; b.N = d1; b.slope = slope;
+    rc = launch_bn_backward(b, s);
+    if (rc) return rc;
+    // X^T (d0, B), then dW1 = dY1^T X  (A = dY1^T (d1, B), B = X^T (d0, B), K = B)
+    hipLaunchKernelGGL(tower_transpose_kernel, dim3((B / 32) * (d0 / 32)), dim3(256), 0, s, x[0], w[0].XT, B, d0);
+    NSVD_CHECK_LAUNCH();
+    memset(&g, 0, sizeof(g));
+    g.A = w[0].dY1T; g.lda = B; g.B = w[0].XT; g.ldb = B; g.C = grads[0]->W1; g.ldc = d0;
+    g.M = d1; g.N = d0; g.K = B; g.S = 1;
+    g.sumsq = sumsq[0] ? sumsq[0] + (d2 / 128) * (d1 / 128) : nullptr;
+    return launch_gemm(g, s);
+}
+
+// What every entry point checks, and the carving. flags: the gemm_bf16 bits of a mixed-precision call.
+int tower_call(TowerCall& c, int nt, const float* const* x, const nsvd_tower_params* const* p, int B, int d0, int d1,
+               int d2, float slope, int update_running, bool mixed, int flags, void* const* ws, size_t ws_bytes,
+               void* stream) {
+    memset(&c, 0, sizeof(c));
+    if (!tower_shape_ok(B, d0, d1, d2)) return NSVD_EINVAL;
+    for (int t = 0; t < nt; ++t) {
+        if (!x[t] || !ws[t] || !nsvd_tower_fields_ok(p[t], update_running != 0)) return NSVD_EINVAL;
+        c.x[t] = x[t];
+        c.p[t] = p[t];
+        c.w[t] = carve_tower(B, d0, d1, d2, ws[t]);
+        c.v[t] = views16(c.w[t]);
+        if (!nsvd_ws_ok(ws[t], ws_bytes, c.w[t].bytes)) return NSVD_EINVAL;
+    }
+    if (mixed && !tower16_shape_ok(B, d0, d1, d2)) return NSVD_EUNSUPPORTED;
+    c.nt = nt; c.B = B; c.d0 = d0; c.d1 = d1; c.d2 = d2;
+    c.slope = slope; c.update_running = update_running; c.flags = flags;
+    c.mixed = mixed;
+    c.wide_only = mixed && (flags & NSVD_TOWER16_WIDE_ONLY);
+    c.fused = mixed && tower16_fused(B, d0, d1, d2, slope);
+    c.f16 = (flags & NSVD_TOWER16_F16) ? 1 : 0;
+    c.S = mixed ? fwd2_slices16(nt, B, d1, d2) : fwd2_slices(B, d1, d2);
+    c.s = (hipStream_t)stream;
+    return 0;
+}
+
+// z[t]: where tower t's output goes (unused in phase 1 and behind NSVD_TOWER16_WIDE_ONLY)
+int tower_forward(TowerCall& c, float eps, float momentum, int phase, float* const* z) {
+    if (phase < 0 || phase > 2) return NSVD_EINVAL;
+    const bool need_z = phase == 2 || (phase == 0 && !c.wide_only);
+    for (int t = 0; t < c.nt; ++t) {
+        if (!z[t] && need_z) return NSVD_EINVAL;
+        c.z[t] = z[t];
+    }
+    c.eps = eps; c.momentum = momentum; c.phase = phase;
+    if (phase == 2) return c.forward_narrow_end();
+    return c.mixed ? c.forward16() : c.forward32();
+}
+
+// dz[t]: unused behind NSVD_TOWER16_WIDE_ONLY (the caller has written dY2h); sumsq: null, or per tower
+// nsvd_tower_sumsq_count partials (dW2's tiles, then dW1's)
+int tower_backward(TowerCall& c, const float* const* dz, const nsvd_tower_params* const* grads, float* const* sumsq) {
+    for (int t = 0; t < c.nt; ++t) {
+        if ((!dz[t] && !c.wide_only) || !nsvd_tower_fields_ok(grads[t], false)) return NSVD_EINVAL;
+        c.dz[t] = dz[t];
+        c.grads[t] = grads[t];
+        c.sumsq[t] = sumsq ? sumsq[t] : nullptr;
+    }
+    return c.mixed ? c.backward16() : c.backward32();
+}
+
 }  // namespace
+
+// Are these tower parameters (or gradient targets: need_running = false) usable - every tensor a kernel addresses
+// through the struct there, and the running statistics when they are to be updated?
+bool nsvd_tower_fields_ok(const nsvd_tower_params* t, bool need_running) {
+    if (!t) return false;
+    for (float* nsvd_tower_params::*f : NSVD_TOWER_FIELDS)
+        if (!(t->*f)) return false;
+    return !need_running || (t->rm1 && t->rv1 && t->rm2 && t->rv2);
+}
 
 extern "C" {
 
@@ -1043,74 +1195,22 @@ int nsvd_tower_forward(const float* x, const nsvd_tower_params* p, int B, int d0
 int nsvd_tower_forward_phase(const float* x, const nsvd_tower_params* p, int B, int d0, int d1, int d2, float slope,
                              float eps, float momentum, int update_running, int gemm_bf16, int phase, float* z,
                              void* ws, size_t ws_bytes, void* stream) {
-    if (phase < 0 || phase > 2) return NSVD_EINVAL;
-    if (!x || !p || (!z && phase != 1) || !ws || !tower_shape_ok(B, d0, d1, d2)) return NSVD_EINVAL;
-    if (!p->W1 || !p->b1 || !p->g1 || !p->be1 || !p->W2 || !p->b2 || !p->g2 || !p->be2) return NSVD_EINVAL;
-    if (update_running && (!p->rm1 || !p->rv1 || !p->rm2 || !p->rv2)) return NSVD_EINVAL;
-    const TowerWs w = carve_tower(B, d0, d1, d2, ws);
-    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    if (gemm_bf16 != 0) {  // mixed precision: the section above
-        const float* xs[1] = {x};
-        const nsvd_tower_params* ps[1] = {p};
-        float* zs[1] = {z};
-        void* wss[1] = {ws};
-        return tower16_forward(1, xs, ps, B, d0, d1, d2, slope, eps, momentum, update_running, gemm_bf16, phase, zs, wss, s);
-    }
-    int rc = 0;
-    GemmNT g;
-    BnFwd f;
-    if (phase == 2) {
-        // second half of a hidden-width-sharded tower: w.Y2 holds the SUM over the ranks of the partial products (the
-        // caller all-reduced it in place); the bias joins here and the biased sum is written back for the backward
-        memset(&f, 0, sizeof(f));
-        f.Y = w.Y2; f.S = 1; f.bias = p->b2; f.Ysum = w.Y2; f.gamma = p->g2; f.beta = p->be2;
-        f.running_mean = update_running ? p->rm2 : nullptr; f.running_var = update_running ? p->rv2 : nullptr;
-        f.mean = w.mean2; f.invstd = w.inv2; f.out = z; f.outT = nullptr; f.B = B; f.N = d2;
-        f.eps = eps; f.momentum = momentum; f.slope = 1.0f;
-        return launch_bn_forward(f, s);
-    }
-    // Y1 = X W1^T + b1
-    memset(&g, 0, sizeof(g));
-    g.A = x; g.lda = d0; g.B = p->W1; g.ldb = d0; g.C = w.Y1; g.ldc = d1; g.bias = p->b1;
-    g.M = B; g.N = d1; g.K = d0; g.S = 1;
-    rc = launch_gemm(g, s, true);  // bench.py --config cfg5 brackets this contraction (nsvd_profile_next_forward)
-    if (rc) return rc;
-    // A1 = lrelu(BN1(Y1)), A1^T
-    memset(&f, 0, sizeof(f));
-    f.Y = w.Y1; f.S = 1; f.gamma = p->g1; f.beta = p->be1;
-    f.running_mean = update_running ? p->rm1 : nullptr; f.running_var = update_running ? p->rv1 : nullptr;
-    f.mean = w.mean1; f.invstd = w.inv1; f.out = w.A1; f.outT = w.A1T; f.B = B; f.N = d1;
-    f.eps = eps; f.momentum = momentum; f.slope = slope;
-    rc = launch_bn_forward(f, s);
-    if (rc) return rc;
-    // Y2 = A1 W2^T (+ b2 in the strip kernel), split-K partials
-    const int S = fwd2_slices(B, d1, d2);
-    memset(&g, 0, sizeof(g));
-    g.A = w.A1; g.lda = d1; g.B = p->W2; g.ldb = d1; g.C = w.Y2p; g.ldc = d2; g.slice_stride = (size_t)B * d2;
-    g.M = B; g.N = d2; g.K = d1; g.S = S;
-    rc = launch_gemm(g, s);
-    if (rc) return rc;
-    // Y2 = b2 + sum of the partials, then Z = BN2(Y2)
-    {
-        const size_t n4 = (size_t)B * d2 / 4;
-        hipLaunchKernelGGL(tower_sum_slices_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, w.Y2p,
-                           (size_t)B * d2, S, phase == 1 ? nullptr : p->b2, w.Y2, d2, n4);
-        NSVD_CHECK_LAUNCH();
-    }
-    if (phase == 1) return 0;  // this rank's partial Y2 (no bias) is in the workspace: nsvd_tower_y2_offset
-    memset(&f, 0, sizeof(f));
-    f.Y = w.Y2; f.S = 1; f.gamma = p->g2; f.beta = p->be2;
-    f.running_mean = update_running ? p->rm2 : nullptr; f.running_var = update_running ? p->rv2 : nullptr;
-    f.mean = w.mean2; f.invstd = w.inv2; f.out = z; f.outT = nullptr; f.B = B; f.N = d2;
-    f.eps = eps; f.momentum = momentum; f.slope = 1.0f;
-    return launch_bn_forward(f, s);
+    TowerCall c;
+    const int rc = tower_call(c, 1, &x, &p, B, d0, d1, d2, slope, update_running, gemm_bf16 != 0, gemm_bf16, &ws,
+                              ws_bytes, stream);
+    return rc ? rc : tower_forward(c, eps, momentum, phase, &z);
 }
 
 int nsvd_tower_backward(const float* x, const nsvd_tower_params* p, const float* dz, int B, int d0, int d1, int d2,
                         float slope, int gemm_bf16, const nsvd_tower_params* grads, void* ws, size_t ws_bytes,
                         void* stream) {
     return nsvd_tower_backward_sumsq(x, p, dz, B, d0, d1, d2, slope, gemm_bf16, grads, ws, ws_bytes, nullptr, stream);
+}
+
+int nsvd_tower_mixed_supported(int B, int d0, int d1, int d2) { return tower16_shape_ok(B, d0, d1, d2) ? 1 : 0; }
+
+int nsvd_tower_mixed_fused(int B, int d0, int d1, int d2, float slope) {
+    return tower16_shape_ok(B, d0, d1, d2) && tower16_fused(B, d0, d1, d2, slope) ? 1 : 0;
 }
 
 }  // extern "C"
@@ -1122,113 +1222,39 @@ int nsvd_tower_sumsq_count(int d0, int d1, int d2, int gemm_bf16) {
     return (d2 / 128) * (d1 / 128) + (d1 / 128) * (d0 / 128);
 }
 
-extern "C" int nsvd_tower_mixed_supported(int B, int d0, int d1, int d2) { return tower16_shape_ok(B, d0, d1, d2) ? 1 : 0; }
-
-extern "C" int nsvd_tower_mixed_fused(int B, int d0, int d1, int d2, float slope) {
-    return tower16_shape_ok(B, d0, d1, d2) && tower16_fused(B, d0, d1, d2, slope) ? 1 : 0;
+int nsvd_tower_backward_sumsq(const float* x, const nsvd_tower_params* p, const float* dz, int B, int d0, int d1,
+                              int d2, float slope, int gemm_bf16, const nsvd_tower_params* grads, void* ws,
+                              size_t ws_bytes, float* sumsq, void* stream) {
+    TowerCall c;  // (of the flag bits the single-tower backward takes the half type alone)
+    const int rc = tower_call(c, 1, &x, &p, B, d0, d1, d2, slope, 0, gemm_bf16 != 0, gemm_bf16 & NSVD_TOWER16_F16, &ws,
+                              ws_bytes, stream);
+    return rc ? rc : tower_backward(c, &dz, &grads, sumsq ? &sumsq : nullptr);
 }
 
 // both towers of a mixed-precision CDK step through every launch together (cdk_step.hip); flags: the gemm_bf16 bits
 int nsvd_tower16_forward_pair(const float* const* x, const nsvd_tower_params* const* p, int B, int d0, int d1, int d2,
                               float slope, float eps, float momentum, int update_running, int flags, float* const* z,
                               void* const* ws, size_t ws_bytes, hipStream_t s) {
-    if (!tower16_shape_ok(B, d0, d1, d2)) return NSVD_EUNSUPPORTED;
-    const size_t need = carve_tower(B, d0, d1, d2, nullptr).bytes;
-    for (int t = 0; t < 2; ++t) {
-        if (!x[t] || !p[t] || (!z[t] && !(flags & NSVD_TOWER16_WIDE_ONLY)) || !nsvd_ws_ok(ws[t], ws_bytes, need))
-            return NSVD_EINVAL;
-        if (!p[t]->W1 || !p[t]->b1 || !p[t]->g1 || !p[t]->be1 || !p[t]->W2 || !p[t]->b2 || !p[t]->g2 || !p[t]->be2)
-            return NSVD_EINVAL;
-        if (update_running && (!p[t]->rm1 || !p[t]->rv1 || !p[t]->rm2 || !p[t]->rv2)) return NSVD_EINVAL;
-    }
-    return tower16_forward(2, x, p, B, d0, d1, d2, slope, eps, momentum, update_running, flags, 0, z, ws, s);
+    TowerCall c;
+    const int rc = tower_call(c, 2, x, p, B, d0, d1, d2, slope, update_running, true, flags, ws, ws_bytes, s);
+    return rc ? rc : tower_forward(c, eps, momentum, 0, z);
 }
 
 int nsvd_tower16_backward_pair(const float* const* x, const nsvd_tower_params* const* p, const float* const* dz, int B,
                                int d0, int d1, int d2, float slope, const nsvd_tower_params* const* grads,
                                void* const* ws, size_t ws_bytes, float* const* sumsq, hipStream_t s, int flags) {
-    if (!tower16_shape_ok(B, d0, d1, d2)) return NSVD_EUNSUPPORTED;
-    const size_t need = carve_tower(B, d0, d1, d2, nullptr).bytes;
-    for (int t = 0; t < 2; ++t)
-        if (!x[t] || !p[t] || (!dz[t] && !(flags & NSVD_TOWER16_WIDE_ONLY)) || !grads[t] ||
-            !nsvd_ws_ok(ws[t], ws_bytes, need))
-            return NSVD_EINVAL;
-    return tower16_backward(2, x, p, dz, B, d0, d1, d2, slope, grads, ws, sumsq, s, flags);
+    TowerCall c;
+    const int rc = tower_call(c, 2, x, p, B, d0, d1, d2, slope, 0, true, flags, ws, ws_bytes, s);
+    return rc ? rc : tower_backward(c, dz, grads, sumsq);
 }
 
-NsvdTowerNarrowViews nsvd_tower16_narrow_views(int nt, int B, int d0, int d1, int d2, void* ws) {
+// what cdk_step.hip addresses inside a mixed-precision tower's workspace (it asks once per tower, when it carves its own)
+NsvdTower16Views nsvd_tower16_views(int nt, int B, int d0, int d1, int d2, void* ws) {
     const TowerWs w = carve_tower(B, d0, d1, d2, ws);
-    NsvdTowerNarrowViews v;
-    v.Y2p = w.Y2p; v.Y2 = w.Y2; v.mean2 = w.mean2; v.inv2 = w.inv2; v.dY2h = views16(w).dY2h;
+    const Tower16 h = views16(w);
+    NsvdTower16Views v;
+    v.Y2p = w.Y2p; v.Y2 = w.Y2; v.mean2 = w.mean2; v.inv2 = w.inv2; v.dY2h = h.dY2h; v.W1h = h.W1h; v.W2h = h.W2h;
     v.S = fwd2_slices16(nt, B, d1, d2);
     v.slice_stride = (size_t)B * d2;
     return v;
-}
-
-// where the bfloat16 copies of W1 / W2 live inside a tower workspace (the optimiser kernel of the fused step refreshes them)
-void nsvd_tower16_weight_copies(int B, int d0, int d1, int d2, void* ws, void** W1h, void** W2h) {
-    const Tower16 v = views16(carve_tower(B, d0, d1, d2, ws));
-    *W1h = v.W1h;
-    *W2h = v.W2h;
-}
-
-int nsvd_tower_backward_sumsq(const float* x, const nsvd_tower_params* p, const float* dz, int B, int d0, int d1,
-                              int d2, float slope, int gemm_bf16, const nsvd_tower_params* grads, void* ws,
-                              size_t ws_bytes, float* sumsq, void* stream) {
-    if (!x || !p || !dz || !grads || !ws || !tower_shape_ok(B, d0, d1, d2)) return NSVD_EINVAL;
-    if (!grads->W1 || !grads->b1 || !grads->g1 || !grads->be1 || !grads->W2 || !grads->b2 || !grads->g2 || !grads->be2)
-        return NSVD_EINVAL;
-    const TowerWs w = carve_tower(B, d0, d1, d2, ws);
-    if (!nsvd_ws_ok(ws, ws_bytes, w.bytes)) return NSVD_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    if (gemm_bf16 != 0) {
-        const float* xs[1] = {x};
-        const nsvd_tower_params* ps[1] = {p};
-        const float* dzs[1] = {dz};
-        const nsvd_tower_params* gs[1] = {grads};
-        void* wss[1] = {ws};
-        float* sq[1] = {sumsq};
-        return tower16_backward(1, xs, ps, dzs, B, d0, d1, d2, slope, gs, wss, sumsq ? sq : nullptr, s,
-                                gemm_bf16 & NSVD_TOWER16_F16);
-    }
-    int rc = 0;
-    // dY2 = BN2'(dZ), dY2^T, db2 = column sums of dY2
-    BnBwd b;
-    memset(&b, 0, sizeof(b));
-    b.dout = dz; b.Y = w.Y2; b.mean = w.mean2; b.invstd = w.inv2; b.gamma = p->g2; b.beta = p->be2;
-    b.dY = w.dY2; b.dYT = w.dY2T; b.dgamma = grads->g2; b.dbeta = grads->be2; b.dbias = grads->b2;
-    b.B = B; b.N = d2; b.slope = 1.0f;
-    rc = launch_bn_backward(b, s);
-    if (rc) return rc;
-    // dW2 = dY2^T A1  (A = dY2^T (d2, B), B = A1^T (d1, B), K = B)
-    GemmNT g;
-    memset(&g, 0, sizeof(g));
-    g.A = w.dY2T; g.lda = B; g.B = w.A1T; g.ldb = B; g.C = grads->W2; g.ldc = d1;
-    g.M = d2; g.N = d1; g.K = B; g.S = 1;
-    g.sumsq = sumsq;
-    rc = launch_gemm(g, s);
-    if (rc) return rc;
-    // W2^T (d1, d2), then dA1 = dY2 W2  (A = dY2 (B, d2), B = W2^T (d1, d2), K = d2)
-    hipLaunchKernelGGL(tower_transpose_kernel, dim3((d2 / 32) * (d1 / 32)), dim3(256), 0, s, p->W2, w.W2T, d2, d1);
-    NSVD_CHECK_LAUNCH();
-    memset(&g, 0, sizeof(g));
-    g.A = w.dY2; g.lda = d2; g.B = w.W2T; g.ldb = d2; g.C = w.dA1; g.ldc = d1;
-    g.M = B; g.N = d1; g.K = d2; g.S = 1;
-    rc = launch_gemm(g, s);
-    if (rc) return rc;
-    // dY1^T = (BN1'(lrelu'(dA1)))^T, db1
-    memset(&b, 0, sizeof(b));
-    b.dout = w.dA1; b.Y = w.Y1; b.mean = w.mean1; b.invstd = w.inv1; b.gamma = p->g1; b.beta = p->be1;
-    b.dY = nullptr; b.dYT = w.dY1T; b.dgamma = grads->g1; b.dbeta = grads->be1; b.dbias = grads->b1;
-    b.B = B; b.N = d1; b.slope = slope;
-    rc = launch_bn_backward(b, s);
-    if (rc) return rc;
-    // X^T (d0, B), then dW1 = dY1^T X  (A = dY1^T (d1, B), B = X^T (d0, B), K = B)
-    hipLaunchKernelGGL(tower_transpose_kernel, dim3((B / 32) * (d0 / 32)), dim3(256), 0, s, x, w.XT, B, d0);
-    NSVD_CHECK_LAUNCH();
-    memset(&g, 0, sizeof(g));
-    g.A = w.dY1T; g.lda = B; g.B = w.XT; g.ldb = B; g.C = grads->W1; g.ldc = d0;
-    g.M = d1; g.N = d0; g.K = B; g.S = 1;
-    g.sumsq = sumsq ? sumsq + (d2 / 128) * (d1 / 128) : nullptr;
-    return launch_gemm(g, s);
 }

@@ -286,3 +286,63 @@ def test_tower_mixed_precision_shapes_and_fallback():
     with torch.autocast("cuda", dtype=torch.float16):
         out = m(x)
     assert torch.equal(out, want)
+
+
+# (B, d0, d1, d2, half): the smallest shape of each narrow-end strip instance with more than one split-K slice - the
+# <8, 256> strip (B not a multiple of 256), the <4, 256> strip, and the mixed-precision contraction in both half types
+PHASE_CASES = [(128, 128, 128, 128, None), (256, 128, 256, 256, None), (256, 128, 256, 256, "bf16"),
+               (256, 128, 256, 256, "f16")]
+
+
+@pytest.mark.parametrize("B,d0,d1,d2,half", PHASE_CASES)
+@pytest.mark.parametrize("bias", ["zero", "nonzero"])
+def test_tower_forward_phases_on_one_process(B, d0, d1, d2, half, bias):
+    """nsvd_tower_forward_phase as a hidden-width-sharded tower calls it (phase 1: up to the summed partial product in
+    tower_y2, no bias; phase 2: bias + second BatchNorm from it), with ONE rank: nothing to all-reduce, so it is the whole
+    tower and must be phase 0's, on a second workspace with the same inputs and equal clones of the running statistics.
+    b2 = 0: both routes add the same slices in the same order onto +0 and the strip kernel's `+ b2` changes no bit:
+    z, the four running statistics and all eight gradients of a following backward are IDENTICAL.
+    b2 != 0: phase 2 adds the bias with one rounded add and writes the sum back for the backward - tower_y2 afterwards
+    is torch's float32 `y2 + b2` bit for bit - where phase 0 starts the slice sum ON the bias: z agrees to the relative
+    norm the multi-rank test uses for this comparison (test_multirank_gpu.py: 2e-5 float32, 2e-3 mixed)."""
+    from neural_svd_amd import hip_ops as H
+    flag = 0 if half is None else 1 | (H.TOWER16_F16 if half == "f16" else 0)
+    g = torch.Generator().manual_seed(7 * B + d1 + (0 if half is None else 1))
+    P = dict(W1=torch.randn(d1, d0, generator=g) / d0 ** 0.5, b1=0.1 * torch.randn(d1, generator=g),
+             g1=1.0 + 0.3 * torch.randn(d1, generator=g), be1=0.2 * torch.randn(d1, generator=g),
+             W2=torch.randn(d2, d1, generator=g) / d1 ** 0.5, b2=0.1 * torch.randn(d2, generator=g),
+             g2=1.0 + 0.3 * torch.randn(d2, generator=g), be2=0.2 * torch.randn(d2, generator=g))
+    if bias == "zero":
+        P["b2"] = torch.zeros(d2)
+    x = torch.randn(B, d0, generator=g).to(DEV)
+    dz = torch.randn(B, d2, generator=g).to(DEV)
+    shared = {k: v.to(DEV).contiguous() for k, v in P.items()}
+
+    def with_running():
+        q = dict(shared)
+        for k, n in (("rm1", d1), ("rv1", d1), ("rm2", d2), ("rv2", d2)):
+            q[k] = torch.full((n,), 0.25 if k.startswith("rm") else 1.5, device=DEV)
+        return q
+
+    Pa, Pb = with_running(), with_running()
+    ws_a, ws_b = H.tower_workspace(B, d0, d1, d2, DEV), H.tower_workspace(B, d0, d1, d2, DEV)
+    assert H.tower_forward(x, Pa, 0.2, 1e-5, 0.1, True, ws_a, gemm_bf16=flag, phase=1) is None
+    y2 = H.tower_y2(ws_a, B, d0, d1, d2).clone()
+    za = H.tower_forward(x, Pa, 0.2, 1e-5, 0.1, True, ws_a, gemm_bf16=flag, phase=2)
+    zb = H.tower_forward(x, Pb, 0.2, 1e-5, 0.1, True, ws_b, gemm_bf16=flag, phase=0)
+    torch.cuda.synchronize()
+    assert float(y2.abs().max()) > 0 and bool(torch.isfinite(za).all())
+    print(f"phases {B, d0, d1, d2, half} b2 {bias}: rel(z) = {rel(za, zb):.3e}")
+    if bias == "zero":
+        assert torch.equal(za, zb)
+        for k in ("rm1", "rv1", "rm2", "rv2"):
+            assert torch.equal(Pa[k], Pb[k]), k
+            assert not torch.equal(Pa[k], with_running()[k]), k  # (and they were updated)
+        ga = H.tower_backward(x, Pa, dz, 0.2, ws_a, gemm_bf16=flag)
+        gb = H.tower_backward(x, Pb, dz, 0.2, ws_b, gemm_bf16=flag)
+        assert sorted(ga) == sorted(NAMES)
+        for k in NAMES:
+            assert torch.equal(ga[k], gb[k]), k
+    else:
+        assert torch.equal(H.tower_y2(ws_a, B, d0, d1, d2), y2 + shared["b2"])
+        assert rel(za, zb) < (2e-5 if half is None else 2e-3), rel(za, zb)

@@ -239,6 +239,46 @@ def test_next_batch_workspace():
         assert fn(*_evd(_AUTO, 1, 0, _A[7], ws_next, n_next, None, opt=opt)(WS, n)) == EINVAL
 
 
+# ---- the towers' tensors: the backward and the step refuse a null one, as the forward does ----------------------------
+TOWER_TENSORS = ("W1", "b1", "g1", "be1", "W2", "b2", "g2", "be2")  # what has a gradient
+TOWER_RUNNING = ("rm1", "rv1", "rm2", "rv2")
+
+
+def _tower_without(base, field):
+    t = _tower(base)
+    setattr(t, field, None)
+    return t
+
+
+@pytest.mark.parametrize("which", ["params", "grads"])
+@pytest.mark.parametrize("field", TOWER_TENSORS)
+def test_tower_backward_refuses_a_null_tensor(which, field):
+    """(before the towers' one validator the backward checked `grads` alone: a null g2 in `params` went into a kernel
+    argument). Everything else about the call is in order: the workspace is large enough and aligned."""
+    lib = _lib.load()
+    n = lib.nsvd_tower_workspace_bytes(TB, TD, TD, TD)
+    p = _tower_without(100, field) if which == "params" else _tower(100)
+    g = _tower_without(140, field) if which == "grads" else _tower(140)
+    assert lib.nsvd_tower_backward(_A[0], _R(p), _A[1], TB, TD, TD, TD, 0.2, 0, _R(g), WS, n, None) == EINVAL
+    if which == "params":  # what the forward already refused
+        assert lib.nsvd_tower_forward(_A[0], _R(p), TB, TD, TD, TD, 0.2, 1e-5, 0.1, 0, 0, _A[1], WS, n, None) == EINVAL
+
+
+@pytest.mark.parametrize("which,field", [("towers", f) for f in TOWER_TENSORS + TOWER_RUNNING] +
+                         [("momentum_bufs", f) for f in TOWER_TENSORS])
+def test_cdk_step_refuses_a_null_tensor_of_the_second_tower(which, field):
+    """the refusal comes before the first launch (the momentum buffers used to be looked at after the towers' backward):
+    tower 0 is complete, so a launch on the made-up addresses would return HIP's error, not NSVD_EINVAL. The step updates
+    the running statistics, so `towers` needs all twelve tensors."""
+    lib = _lib.load()
+    n = lib.nsvd_cdk_step_workspace_bytes(_R(_STEP))
+    towers = (_lib.TowerParams * 2)(_tower(100), _tower_without(120, field) if which == "towers" else _tower(120))
+    momenta = (_lib.TowerParams * 2)(_tower(140),
+                                     _tower_without(160, field) if which == "momentum_bufs" else _tower(160))
+    assert lib.nsvd_cdk_step(_R(_STEP), _A[0], _A[1], towers, momenta, _A[2], _A[3], _A[4], None, None, WS, n,
+                             None) == EINVAL
+
+
 # ---- the size queries ------------------------------------------------------------------------------------------------
 _BIG = _desc(l=64, d=3)  # with B = 8192
 _GENERIC = _desc(hidden=(128, 7))
