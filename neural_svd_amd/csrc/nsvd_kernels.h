@@ -89,16 +89,19 @@ int nsvd_evd_reduce_partials(const void* scratch, int B, int L, float* moments, 
 bool nsvd_fused_model_supported(const nsvd_model_desc& d, int B);
 int nsvd_fused_model_forward(const nsvd_model_desc& d, const nsvd_params& p, const float* x, int B, float c,
                              float* out, void* ws, int save, hipStream_t s);
-bool nsvd_fused_supported(const nsvd_model_desc& d, int B, bool exact = false);
+bool nsvd_fused_supported(const nsvd_model_desc& d, int B);  // stencil mode and exact mode alike: 1 <= D <= 3
 bool nsvd_fused_split_nd_supported(const nsvd_model_desc& d, int B);  // 5 <= D <= 12, stencil mode, explicit request
 size_t nsvd_fused_workspace_bytes(const nsvd_model_desc& d, int B);
-// Fourier features of x into the fused path's workspace (phi, and phiT_c when save != 0)
+// Fourier features of x into the fused path's workspace (phi, and phiT_c when save != 0); sampler / xout: null, or the
+// coordinates are drawn inside the kernel and stored to xout (nsvd_fourier_stencil)
 int nsvd_fused_features(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
-                        int B, void* ws, int save, hipStream_t s, const NsvdSampler* sampler = nullptr,
-                        float* xout = nullptr);
-// save: bit 0 = keep what the backward needs, bit 1 = features already prepared by nsvd_fused_features
+                        int B, void* ws, int save, hipStream_t s, const NsvdSampler* sampler, float* xout);
+// `save` of nsvd_fused_forward: keep what the backward needs; the features are already in the workspace
+// (nsvd_fused_features); bf16x3: the weight planes in the workspace are current (include/nsvd.h: NSVD_W_PLANES_READY)
+enum NsvdFwdSave : int { NSVD_FWD_SAVE = 1, NSVD_FWD_FEATURES_READY = 2, NSVD_FWD_PLANES_READY = 4 };
+// bf3: layer 0 on the bf16 MFMA with three-way split operands; raw: stop at the raw head outputs (NsvdRawOut below)
 int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
-                       int B, float* f, float* Tf, void* ws, int save, hipStream_t s, int bf3 = 0, int raw = 0);
+                       int B, float* f, float* Tf, void* ws, int save, hipStream_t s, int bf3, int raw);
 // NeuralEF: operator forward that stops at the raw head outputs (operator_api.hip: nsvd_operator_forward_raw)
 struct NsvdRawOut {
     const float* raw;  // (L, ldr): rows e B + b, e = centre, even_0, odd_0, even_1, ...
@@ -117,8 +120,8 @@ int nsvd_operator_forward_raw(const nsvd_model_desc& d, const nsvd_params& p, co
 // batch slices of the weight-gradient kernel (1: every tile contracts the whole batch)
 int nsvd_fused_wgrad_slices(const nsvd_model_desc& d, int B);
 int nsvd_fused_stream_bwd_slices(const nsvd_model_desc& d, int B);  // > 0: the streaming backward may take the step
-int nsvd_fused_backward(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
-                        int B, const float* df, const nsvd_params& g, void* ws, hipStream_t s);
+int nsvd_fused_backward(const nsvd_model_desc& d, const nsvd_params& p, int B, const float* df, const nsvd_params& g,
+                        void* ws, hipStream_t s);
 struct NsvdEvdIn;  // evd_math.h
 // backward with d loss / d f derived from the EVD moments inside the chain kernel (no df round trip)
 // g: where to store the gradients (null: not stored); opt: RMSprop + EMA applied in the weight-gradient kernel's
@@ -134,12 +137,24 @@ struct NsvdNextBatch {
     void* ws;     // the other workspace set (same size as the step's)
     float eps;    // the problem's finite-difference eps (<= 0: exact-Laplacian constants)
 };
-// window_of_step: this call is one of several head windows of ONE fused step; not_last: it neither advances the device-
-// resident schedule nor adds up the step's loss; ev_after_chain (hipEvent_t or null): recorded between its two launches
+// What a call asks of nsvd_fused_backward_evd beyond the backward of the whole model (all zero: nothing).
+// Head window [l_begin, l_begin + l_count) of the model's heads (l_count = 0: all of them): the heads of ParallelMLP share
+// nothing but the input, so the backward of a window is the same launches on pointers that start at head l_begin
+// (sample-sharded runs cut the backward into windows to start exchanging the first window's gradients while the next one
+// is computed).
+// window_of_step: this call is one of SEVERAL head windows of ONE fused step (nsvd_operator_backward_evd_step_window);
+// not_last: it neither advances the device-resident schedule nor adds up the step's loss; ev_after_chain (hipEvent_t or
+// null): recorded between its two launches (the next window's chain, on another stream, waits for it: two chains side by
+// side only slow each other). The last two are read only with window_of_step set.
+struct NsvdFusedBwdReq {
+    int l_begin, l_count;
+    const NsvdNextBatch* next;
+    int window_of_step, not_last;
+    void* ev_after_chain;
+};
 int nsvd_fused_backward_evd(const nsvd_model_desc& d, const nsvd_params& p, int B, const NsvdEvdIn& evd,
-                            const nsvd_params* g, const NsvdOptStep* opt, void* ws, hipStream_t s, int l_begin = 0,
-                            int l_count = 0, const NsvdNextBatch* next = nullptr, int window_of_step = 0,
-                            int not_last = 0, void* ev_after_chain = nullptr);
+                            const nsvd_params* g, const NsvdOptStep* opt, void* ws, hipStream_t s,
+                            const NsvdFusedBwdReq& req);
 bool nsvd_fused_backward_window_ok(const nsvd_model_desc& d, int B, int l_count);
 // stand-alone optimiser launch over n contiguous floats (optimizer.hip)
 int nsvd_rmsprop_launch(float* p, const float* grad, float* sq, float* ema, size_t n, const NsvdHyper& h,

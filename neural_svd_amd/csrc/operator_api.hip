@@ -113,7 +113,7 @@ bool want_fused(const nsvd_model_desc& d, int B, int path, bool exact = false) {
     // above the small stencil: the split form on explicit request only - NSVD_PATH_AUTO stays on the generic kernels
     // until the two are measured against each other
     if (d.D > NSVD_SMALL_D) return path == NSVD_PATH_FUSED && !exact && nsvd_fused_split_nd_supported(d, B);
-    return nsvd_fused_supported(d, B, exact);
+    return nsvd_fused_supported(d, B);
 }
 
 bool fused_requested(int path) { return path == NSVD_PATH_FUSED || path == NSVD_PATH_FUSED_BF16X3; }
@@ -175,18 +175,20 @@ int generic_mlp(const nsvd_model_desc& d, const nsvd_params& p, const float* x, 
 }
 
 int generic_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x, int B,
-                    float* f, float* Tf, void* ws, hipStream_t s, bool features_ready = false, bool exact = false) {
-    const GenericWs w = carve(d, B, ws, exact ? d.D + 2 : 0);
-    const int E = exact ? d.D + 2 : 1 + 2 * d.D, R = E * B;
+                    float* f, float* Tf, void* ws, hipStream_t s, bool features_ready, int path) {
+    const bool exact = generic_exact(path);
+    const GenericWs w = carve(d, B, ws, generic_erows(d, path));
+    const int R = w.R, E = R / B;
     // (bench.py's event bracket: the WHOLE forward - features, every layer, the finite-difference epilogue - as the fused
-    // forward kernel is one launch doing all of it)
+    // forward kernel is one launch doing all of it; closed on the error path too, or the stop event would stay armed for
+    // the next forward)
     nsvd_prof_begin(s);
     int rc = generic_mlp(d, p, x, B, prob.eps, E, w, s, features_ready, exact);
-    if (rc) return rc;
-    rc = exact ? nsvd_fd_epilogue_exact(w.z[d.nlayers - 1], R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L,
-                                        f, Tf, w.jac, w.dsc, s, nsvd_box_of(d))
-               : nsvd_fd_epilogue(w.z[d.nlayers - 1], R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L, f, Tf,
-                                  w.jac, w.dsc, s, 1, nsvd_box_of(d));
+    if (!rc)
+        rc = exact ? nsvd_fd_epilogue_exact(w.z[d.nlayers - 1], R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D,
+                                            d.L, f, Tf, w.jac, w.dsc, s, nsvd_box_of(d))
+                   : nsvd_fd_epilogue(w.z[d.nlayers - 1], R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L, f,
+                                      Tf, w.jac, w.dsc, s, 1, nsvd_box_of(d));
     nsvd_prof_end(s);
     return rc;
 }
@@ -237,6 +239,60 @@ int generic_backward(const nsvd_model_desc& d, const nsvd_params& p, const float
     return 0;
 }
 
+// What one call of the forward family asks for - nsvd_operator_forward, _features, _sample_features(_dev), _backward -
+// and which of the shared checks its entry point takes: the subsets differ, and the differences are part of the
+// interface (a call one entry point refuses, another accepts). op_call fills what the entry points share, everything
+// else off; op_prologue runs the checks in the one order all of them keep and says which kernels run.
+struct OpCall {
+    const nsvd_model_desc* desc;
+    const nsvd_params* params;
+    const nsvd_problem* prob;
+    const float* x;
+    int B;
+    void* ws;
+    size_t ws_bytes;
+    int path;
+    hipStream_t s;
+    bool others_ok;           // the entry point's own device pointers (f, Tf; df) are there
+    bool judge_problem;       // validate_problem
+    bool exact_status_first;  // NSVD_PATH_GENERIC_EXACT is judged before the parameters and the workspace
+    bool whole_params;        // check_params on the whole set (otherwise: fourier_B alone)
+    const nsvd_params* grads;
+    bool need_grads;          // check_params on grads
+    bool fused;               // (out) the MFMA kernels run
+};
+
+OpCall op_call(const nsvd_model_desc* desc, const nsvd_params* params, const nsvd_problem* prob, const float* x, int B,
+               void* ws, size_t ws_bytes, int path, void* stream) {
+    OpCall c = OpCall();
+    c.desc = desc; c.params = params; c.prob = prob;
+    c.x = x; c.B = B;
+    c.ws = ws; c.ws_bytes = ws_bytes; c.path = path; c.s = (hipStream_t)stream;
+    c.others_ok = true;
+    return c;
+}
+
+int op_prologue(OpCall& c) {
+    int rc = validate(c.desc);
+    if (rc) return rc;
+    if (!c.prob || !c.x || !c.ws || !c.others_ok || c.B <= 0) return NSVD_EINVAL;
+    if (!c.whole_params && (!c.params || !c.params->fourier_B)) return NSVD_EINVAL;
+    if (c.judge_problem && (rc = validate_problem(c.desc, c.prob, c.path)) != 0) return rc;
+    if (c.exact_status_first && generic_exact(c.path) && (rc = generic_exact_status(*c.prob)) != 0) return rc;
+    if (c.whole_params && (rc = check_params(*c.desc, c.params, true)) != 0) return rc;
+    if (c.need_grads && (rc = check_params(*c.desc, c.grads, false)) != 0) return rc;
+    return resolve_path(*c.desc, *c.prob, c.B, c.ws, c.ws_bytes, c.path, &c.fused);
+}
+
+// the features of the generic layout for c.path: the jets generic_forward reads in the exact mode, the even / odd stencil
+// rows otherwise (w.R = erows * B columns)
+int generic_features(const OpCall& c) {
+    const nsvd_model_desc& d = *c.desc;
+    const GenericWs w = carve(d, c.B, c.ws, generic_erows(d, c.path));
+    if (generic_exact(c.path)) return nsvd_fourier_features_jets(c.x, c.params->fourier_B, w.phiT, c.B, d.D, d.m, w.R, c.s);
+    return nsvd_fourier_features_evenodd(c.x, c.params->fourier_B, w.phiT, c.B, d.D, d.m, c.prob->eps, w.R, c.s);
+}
+
 }  // namespace
 
 extern "C" int nsvd_abi_version(void) { return NSVD_ABI_VERSION; }
@@ -250,7 +306,7 @@ extern "C" const char* nsvd_path_name(const nsvd_model_desc* desc, int B, int pa
 extern "C" int nsvd_step_emits_planes(const nsvd_model_desc* desc, int B, int path) {
     if (validate(desc) != 0 || B <= 0 || path != NSVD_PATH_FUSED_BF16X3) return 0;
     // (the streaming backward never runs the kernel that writes the planes)
-    return nsvd_fused_supported(*desc, B, false) && nsvd_fused_wgrad_slices(*desc, B) == 1 &&
+    return nsvd_fused_supported(*desc, B) && nsvd_fused_wgrad_slices(*desc, B) == 1 &&
                    nsvd_fused_stream_bwd_slices(*desc, B) == 0 ? 1 : 0;
 }
 
@@ -277,7 +333,7 @@ extern "C" size_t nsvd_model_workspace_bytes(const nsvd_model_desc* desc, int B)
 extern "C" size_t nsvd_workspace_bytes(const nsvd_model_desc* desc, int B) {
     if (validate(desc) != 0 || B <= 0) return 0;
     const size_t gen = carve(*desc, B, nullptr).bytes;
-    const size_t fus = (nsvd_fused_supported(*desc, B, true) || nsvd_fused_split_nd_supported(*desc, B))
+    const size_t fus = (nsvd_fused_supported(*desc, B) ||nsvd_fused_split_nd_supported(*desc, B))
                            ? nsvd_fused_workspace_bytes(*desc, B) : 0;
     return gen > fus ? gen : fus;
 }
@@ -285,28 +341,22 @@ extern "C" size_t nsvd_workspace_bytes(const nsvd_model_desc* desc, int B) {
 extern "C" int nsvd_operator_forward(const nsvd_model_desc* desc, const nsvd_params* params,
                                      const nsvd_problem* prob, const float* x, int B, float* f, float* Tf, void* ws,
                                      size_t ws_bytes, int save_for_backward, int path, void* stream) {
-    int rc = validate(desc);
-    if (rc) return rc;
-    if (!prob || !x || !f || !Tf || !ws || B <= 0) return NSVD_EINVAL;
-    rc = validate_problem(desc, prob, path);
-    if (rc) return rc;
-    const bool gexact = generic_exact(path);
-    if (gexact && (rc = generic_exact_status(*prob)) != 0) return rc;
-    rc = check_params(*desc, params, true);
-    if (rc) return rc;
-    bool fused;
-    rc = resolve_path(*desc, *prob, B, ws, ws_bytes, path, &fused);
-    if (rc) return rc;
+    OpCall c = op_call(desc, params, prob, x, B, ws, ws_bytes, path, stream);
+    c.others_ok = f && Tf;
+    c.judge_problem = c.exact_status_first = c.whole_params = true;
+    if (const int rc = op_prologue(c)) return rc;
     // eps <= 0 selects the exact Laplacian (reference diff_ops.py:7): forward-mode jets, on the MFMA path or - on
     // explicit request only - on the generic kernels
-    if (!(prob->eps > 0.f) && !fused && !gexact) return NSVD_EUNSUPPORTED;
+    if (!(prob->eps > 0.f) && !c.fused && !generic_exact(path)) return NSVD_EUNSUPPORTED;
     const bool ready = (save_for_backward & NSVD_FEATURES_READY) != 0;
-    const bool planes = (save_for_backward & NSVD_W_PLANES_READY) != 0 && path == NSVD_PATH_FUSED_BF16X3;
-    if (fused)
+    const bool bf3 = path == NSVD_PATH_FUSED_BF16X3;
+    const bool planes = (save_for_backward & NSVD_W_PLANES_READY) != 0 && bf3;
+    if (c.fused)
         return nsvd_fused_forward(*desc, *params, *prob, x, B, f, Tf, ws,
-                                  (save_for_backward & 1) | (ready ? 2 : 0) | (planes ? 4 : 0), (hipStream_t)stream,
-                                  path == NSVD_PATH_FUSED_BF16X3);
-    return generic_forward(*desc, *params, *prob, x, B, f, Tf, ws, (hipStream_t)stream, ready, gexact);
+                                  (save_for_backward & 1 ? NSVD_FWD_SAVE : 0) | (ready ? NSVD_FWD_FEATURES_READY : 0) |
+                                      (planes ? NSVD_FWD_PLANES_READY : 0),
+                                  c.s, bf3, 0);
+    return generic_forward(*desc, *params, *prob, x, B, f, Tf, ws, c.s, ready, path);
 }
 
 // NeuralEF (neuralef.hip): the operator forward up to the raw head outputs - (L, ldr) rows e B + b in the even / odd
@@ -326,7 +376,7 @@ int nsvd_operator_forward_raw(const nsvd_model_desc& d, const nsvd_params& p, co
         out->ldr = R;
         out->jac = v.jac;
         out->dsc = d.has_exp_mask ? v.dsc : nullptr;
-        return nsvd_fused_forward(d, p, prob, x, B, nullptr, nullptr, ws, 1, s, 0, 1);
+        return nsvd_fused_forward(d, p, prob, x, B, nullptr, nullptr, ws, NSVD_FWD_SAVE, s, 0, 1);
     }
     const GenericWs w = carve(d, B, ws);
     out->raw = w.z[d.nlayers - 1];
@@ -342,54 +392,31 @@ int nsvd_operator_forward_raw(const nsvd_model_desc& d, const nsvd_params& p, co
 extern "C" int nsvd_operator_features(const nsvd_model_desc* desc, const nsvd_params* params,
                                       const nsvd_problem* prob, const float* x, int B, void* ws, size_t ws_bytes,
                                       int save_for_backward, int path, void* stream) {
-    int rc = validate(desc);
-    if (rc) return rc;
-    if (!prob || !x || !ws || !params || !params->fourier_B || B <= 0) return NSVD_EINVAL;
-    bool fused;
-    rc = resolve_path(*desc, *prob, B, ws, ws_bytes, path, &fused);
-    if (rc) return rc;
-    if (fused) return nsvd_fused_features(*desc, *params, *prob, x, B, ws, save_for_backward & 1, (hipStream_t)stream);
-    if (generic_exact(path)) {  // the jet features, in the layout generic_forward(exact) reads
+    // (neither the problem nor the rest of the parameter set is judged here: the features read fourier_B and eps alone)
+    OpCall c = op_call(desc, params, prob, x, B, ws, ws_bytes, path, stream);
+    if (const int rc = op_prologue(c)) return rc;
+    if (c.fused) return nsvd_fused_features(*desc, *params, *prob, x, B, ws, save_for_backward & 1, c.s, nullptr, nullptr);
+    if (generic_exact(path)) {
         if (const int st = generic_exact_status(*prob)) return st;
-        const GenericWs w = carve(*desc, B, ws, desc->D + 2);
-        return nsvd_fourier_features_jets(x, params->fourier_B, w.phiT, B, desc->D, desc->m, w.R, stream);
+    } else if (!(prob->eps > 0.f)) {
+        return NSVD_EUNSUPPORTED;
     }
-    if (!(prob->eps > 0.f)) return NSVD_EUNSUPPORTED;
-    const GenericWs w = carve(*desc, B, ws);
-    const int E = 1 + 2 * desc->D;
-    return nsvd_fourier_features_evenodd(x, params->fourier_B, w.phiT, B, desc->D, desc->m, prob->eps, E * B,
-                                         (hipStream_t)stream);
+    return generic_features(c);
 }
 
 namespace {
 int sample_features_impl(const nsvd_model_desc* desc, const nsvd_params* params, const nsvd_problem* prob,
                          unsigned long long seed, unsigned long long offset, const nsvd_step_state* state, float* x,
                          int B, void* ws, size_t ws_bytes, int save_for_backward, int path, void* stream) {
-    int rc = validate(desc);
-    if (rc) return rc;
-    if (!prob || !x || !ws || !params || !params->fourier_B || B <= 0) return NSVD_EINVAL;
-    rc = validate_problem(desc, prob, path);
-    if (rc) return rc;
-    const bool gexact = generic_exact(path);
-    if (gexact && (rc = generic_exact_status(*prob)) != 0) return rc;
-    bool fused;
-    rc = resolve_path(*desc, *prob, B, ws, ws_bytes, path, &fused);
-    if (rc) return rc;
+    OpCall c = op_call(desc, params, prob, x, B, ws, ws_bytes, path, stream);
+    c.judge_problem = c.exact_status_first = true;
+    if (const int rc = op_prologue(c)) return rc;
     NsvdSampler smp = make_sampler(*prob, seed, offset);
     smp.offset_add = state ? (const unsigned long long*)&state->step : nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    if (fused) return nsvd_fused_features(*desc, *params, *prob, x, B, ws, save_for_backward & 1, s, &smp, x);
-    if (!(prob->eps > 0.f) && !gexact) return NSVD_EUNSUPPORTED;
-    rc = nsvd_sample_launch(smp, x, B, desc->D, s);
-    if (rc) return rc;
-    if (gexact) {
-        const GenericWs w = carve(*desc, B, ws, desc->D + 2);
-        return nsvd_fourier_features_jets(x, params->fourier_B, w.phiT, B, desc->D, desc->m, w.R, stream);
-    }
-    const GenericWs w = carve(*desc, B, ws);
-    const int E = 1 + 2 * desc->D;
-    return nsvd_fourier_features_evenodd(x, params->fourier_B, w.phiT, B, desc->D, desc->m, prob->eps, E * B,
-                                         (hipStream_t)stream);
+    if (c.fused) return nsvd_fused_features(*desc, *params, *prob, x, B, ws, save_for_backward & 1, c.s, &smp, x);
+    if (!(prob->eps > 0.f) && !generic_exact(path)) return NSVD_EUNSUPPORTED;
+    if (const int rc = nsvd_sample_launch(smp, x, B, desc->D, c.s)) return rc;
+    return generic_features(c);
 }
 }  // namespace
 
@@ -445,30 +472,24 @@ extern "C" int nsvd_model_backward(const nsvd_model_desc* desc, const nsvd_param
     rc = check_params(*desc, grads, false);
     if (rc) return rc;
     if (!nsvd_ws_ok(ws, ws_bytes, nsvd_model_workspace_bytes(desc, B))) return NSVD_EINVAL;
-    if (nsvd_fused_model_supported(*desc, B)) {
-        nsvd_problem unused;
-        memset(&unused, 0, sizeof(unused));
-        return nsvd_fused_backward(*desc, *params, unused, x, B, dout, *grads, ws, (hipStream_t)stream);
-    }
+    if (nsvd_fused_model_supported(*desc, B))
+        return nsvd_fused_backward(*desc, *params, B, dout, *grads, ws, (hipStream_t)stream);
     return generic_backward(*desc, *params, x, B, dout, *grads, ws, (hipStream_t)stream, 1);
 }
 
 extern "C" int nsvd_operator_backward(const nsvd_model_desc* desc, const nsvd_params* params,
                                       const nsvd_problem* prob, const float* x, int B, const float* df,
                                       const nsvd_params* grads, void* ws, size_t ws_bytes, int path, void* stream) {
-    int rc = validate(desc);
-    if (rc) return rc;
-    if (!prob || !x || !df || !ws || B <= 0) return NSVD_EINVAL;
-    rc = check_params(*desc, params, true);
-    if (rc) return rc;
-    rc = check_params(*desc, grads, false);
-    if (rc) return rc;
-    bool fused;
-    rc = resolve_path(*desc, *prob, B, ws, ws_bytes, path, &fused);
-    if (rc) return rc;
-    if (fused) return nsvd_fused_backward(*desc, *params, *prob, x, B, df, *grads, ws, (hipStream_t)stream);
+    // (the problem is not judged here: the backward reads what the forward saved)
+    OpCall c = op_call(desc, params, prob, x, B, ws, ws_bytes, path, stream);
+    c.others_ok = df != nullptr;
+    c.whole_params = true;
+    c.grads = grads;
+    c.need_grads = true;
+    if (const int rc = op_prologue(c)) return rc;
+    if (c.fused) return nsvd_fused_backward(*desc, *params, B, df, *grads, ws, c.s);
     if (generic_exact(path) && generic_exact_status(*prob)) return NSVD_EUNSUPPORTED;
-    return generic_backward(*desc, *params, x, B, df, *grads, ws, (hipStream_t)stream, generic_erows(*desc, path));
+    return generic_backward(*desc, *params, x, B, df, *grads, ws, c.s, generic_erows(*desc, path));
 }
 
 namespace {
@@ -703,9 +724,11 @@ int backward_evd(EvdCall& c) {
             rc = nsvd_opt_state_begin(c.opt.ostate, c.stream);
             if (rc) return rc;
         }
-        return nsvd_fused_backward_evd(*desc, *c.params, B, in, c.grads, c.take_step ? &c.opt : nullptr, c.ws, s,
-                                       c.l_begin, c.l_count, c.next.x ? &c.next : nullptr, c.window_of_step,
-                                       c.not_last, c.ev_after_chain);
+        NsvdFusedBwdReq req = NsvdFusedBwdReq();
+        req.l_begin = c.l_begin; req.l_count = c.l_count;
+        req.next = c.next.x ? &c.next : nullptr;
+        req.window_of_step = c.window_of_step; req.not_last = c.not_last; req.ev_after_chain = c.ev_after_chain;
+        return nsvd_fused_backward_evd(*desc, *c.params, B, in, c.grads, c.take_step ? &c.opt : nullptr, c.ws, s, req);
     }
     if (c.window_of_step) return NSVD_EUNSUPPORTED;  // windows of a fused step exist on the fused kernels only
     if (c.next.x) return NSVD_EUNSUPPORTED;  // guest feature workgroups exist on the fused kernels only

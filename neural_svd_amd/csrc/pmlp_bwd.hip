@@ -1,6 +1,7 @@
 // Fused MFMA path, backward half: the data-gradient chain kernel, the weight-gradient kernel with the optimiser in
 // its epilogue, and the split-K reduction (forward half and the overall design: pmlp_fwd.hip).
 #include <stdlib.h>
+#include <type_traits>
 #include "pmlp_common.h"
 #include "evd_math.h"
 #include "opt_math.h"
@@ -1086,9 +1087,9 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(ReduceArgs a) {
     }
 }
 
-// the weight-gradient / second-pass launches of one rule
+// the weight-gradient launch of one rule: tile width and plane emission pick the instance
 template <int RULE>
-void launch_wgrad(const WgradArgs& wa, bool emit, dim3 wgrid, hipStream_t s) {
+void launch_wgrad_rule(const WgradArgs& wa, bool emit, dim3 wgrid, hipStream_t s) {
     if (wa.tw == 64) {
         if (emit) hipLaunchKernelGGL((pmlp_fused_wgrad_kernel<1, true, RULE>), wgrid, dim3(256), 0, s, wa);
         else hipLaunchKernelGGL((pmlp_fused_wgrad_kernel<1, false, RULE>), wgrid, dim3(256), 0, s, wa);
@@ -1103,110 +1104,202 @@ void launch_wgrad(const WgradArgs& wa, bool emit, dim3 wgrid, hipStream_t s) {
 }  // namespace
 
 
-// Head window [l0, l0 + Lc) of the model's d.L heads: the heads of ParallelMLP share nothing but the input, so the
-// backward of a window is the same two launches on pointers that start at head l0 (sample-sharded runs cut the
-// backward into windows to start exchanging the first window's gradients while the next one is computed).
-// win: one of SEVERAL head windows of ONE fused step (nsvd_operator_backward_evd_step_window). not_last: this window
-// neither advances the device-resident schedule nor adds up the loss; ev_after_chain: recorded between the two launches
-// (the next window's chain, on another stream, waits for it: two chains side by side only slow each other).
-struct NsvdStepWindow {
-    int not_last;
-    hipEvent_t ev_after_chain;
-};
-static int fused_backward_impl(const nsvd_model_desc& dfull, const nsvd_params& p, int B, const float* df,
-                               const NsvdEvdIn* evd, const nsvd_params* gp, const NsvdOptStep* opt, void* ws,
-                               hipStream_t s, int l0 = 0, int Lc = 0, const NsvdNextBatch* next = nullptr,
-                               const NsvdStepWindow* win = nullptr) {
-    if (Lc <= 0) Lc = dfull.L;
-    if (l0 < 0 || l0 + Lc > dfull.L) return NSVD_EINVAL;
-    nsvd_params g;
-    memset(&g, 0, sizeof(g));
-    if (gp) g = *gp;
-    const FusedWs w = carve_fused(dfull, B, ws);
-    nsvd_model_desc d = dfull;
-    d.L = Lc;
-    const int F = 2 * d.m, nh = d.nlayers - 1;
-    if (Lc != dfull.L && wgrad_slices(d, B) != 1) return NSVD_EUNSUPPORTED;  // split-K partials are laid out per model
-    // element offsets of head l0 inside the per-head arrays
-    auto offW = [&](int i) { return (size_t)l0 * d.dims[i] * (i == 0 ? (size_t)F : (size_t)d.dims[i - 1]); };
-    auto offb = [&](int i) { return (size_t)l0 * d.dims[i]; };
-    const size_t offz = (size_t)l0 * HID * B, offv = (size_t)l0 * B;
+namespace {
+// f(std::integral_constant<int, RULE>()) for an optimiser rule of opt_math.h (in range: fused_bwd_plan has checked it)
+template <class F>
+void with_rule(int rule, F f) {
+    switch (rule) {
+        case NSVD_RULE_RMSPROP: f(std::integral_constant<int, NSVD_RULE_RMSPROP>()); break;
+        case NSVD_RULE_RMSPROP_MOM: f(std::integral_constant<int, NSVD_RULE_RMSPROP_MOM>()); break;
+        case NSVD_RULE_SGD: f(std::integral_constant<int, NSVD_RULE_SGD>()); break;
+        case NSVD_RULE_SGD_MOM: f(std::integral_constant<int, NSVD_RULE_SGD_MOM>()); break;
+        default: f(std::integral_constant<int, NSVD_RULE_ADAM>()); break;
+    }
+}
 
+// where the partial gradients of a slice go, in the fields every kernel that writes them has (StreamArgs, WgradArgs)
+template <class Args>
+void set_part_layout(Args& a, const PartLayout& pl, float* part, int nlayers) {
+    a.part = part;
+    a.part_stride = pl.stride;
+    for (int i = 0; i < nlayers; ++i) {
+        a.poW[i] = pl.oW[i];
+        a.pob[i] = pl.ob[i];
+    }
+    a.poscales = pl.oscales;
+}
+
+// One call of the fused backward: what it was asked for, the head window it works on, and every decision of the launch
+// sequence, each taken once by fused_bwd_plan - which also holds every refusal, so a refused call launches nothing.
+// The stages below fill one argument struct or make one launch each; run() is the sequence.
+struct FusedBwd {
+    // the call
+    const nsvd_model_desc* full;  // the model, every head
+    const nsvd_params* p;
+    int B;
+    const float* df;              // d loss / d f, or null: derived from evd inside the chain kernel
+    const NsvdEvdIn* evd;
+    nsvd_params g;                // where the gradients go (null members: not stored)
+    const NsvdOptStep* opt;       // the optimiser step in the weight-gradient epilogue, or null
+    const NsvdNextBatch* next;    // the next batch's features as guests of the chain launch, or null
+    hipEvent_t ev_after_chain;    // recorded between the chain and the weight gradients, or null
+    hipStream_t s;
+    void* ws;
+    // the head window [l0, l0 + Lc): the launches run on pointers that start at head l0
+    FusedWs w;
+    nsvd_model_desc d;            // the model with L = Lc
+    int l0, Lc, F, nh;
+    size_t offz, offv;            // element offsets of head l0 in the (L, 128, B) and (L, B) arrays ...
+    size_t offW(int i) const { return (size_t)l0 * d.dims[i] * (i == 0 ? (size_t)F : (size_t)d.dims[i - 1]); }  // ... W_i
+    size_t offb(int i) const { return (size_t)l0 * d.dims[i]; }                                                  // ... b_i
+    PartLayout pl;
+    // the decisions
+    int chain_blocks;             // (B / 32) Lc
+    bool pre_chain;               // the chain form that fetches every weight at kernel start (PRE)
+    int SS;                       // > 0: the streaming form (pmlp_stream_bwd.h) with SS batch slices instead of chain + wgrad
+    int S, Bs;                    // slices of partial gradients (split-K, or SS), rows per split-K slice
+    bool reduce;                  // the second pass adds the slices (S > 1, or the streaming form at any SS)
+    int tw, nA;                   // features per dW_0 tile (64 / 128) and how many tiles that makes
+    nsvd_step_state* state;       // RMSprop's device-resident schedule, or null
+    bool step_loss;               // direct mode: the chain leaves partial sums of the step's loss
+    bool last_window;             // this call ends the step: it advances the schedule and adds up the loss
+    bool emit;                    // bf16x3 steps: the weight-gradient kernel writes the planes of the updated weights
+    int rule;
+
+    NsvdEvdIn evd_in() const;
+    ChainArgs chain_args() const;
+    StreamArgs stream_args() const;
+    int launch_chain() const;
+    WgradArgs wgrad_args() const;
+    int launch_wgrad(const WgradArgs& wa) const;
+    int launch_reduce(const WgradArgs& wa) const;
+    int run() const;
+};
+
+int fused_bwd_plan(FusedBwd& c, const nsvd_model_desc& dfull, const nsvd_params& p, int B, const float* df,
+                   const NsvdEvdIn* evd, const nsvd_params* gp, const NsvdOptStep* opt, void* ws, hipStream_t s,
+                   const NsvdFusedBwdReq& req) {
+    memset(&c, 0, sizeof(c));
+    const bool win = req.window_of_step != 0;
+    c.full = &dfull; c.p = &p; c.B = B; c.df = df; c.evd = evd; c.opt = opt; c.next = req.next; c.s = s; c.ws = ws;
+    if (gp) c.g = *gp;
+    c.ev_after_chain = win ? (hipEvent_t)req.ev_after_chain : nullptr;
+    c.l0 = req.l_begin;
+    c.Lc = req.l_count <= 0 ? dfull.L : req.l_count;
+    if (c.l0 < 0 || c.l0 + c.Lc > dfull.L) return NSVD_EINVAL;
+    const bool whole = c.Lc == dfull.L;  // (then l0 = 0)
+    c.d = dfull;
+    c.d.L = c.Lc;
+    const int S0 = wgrad_slices(c.d, B);
+    if (!whole && S0 != 1) return NSVD_EUNSUPPORTED;  // split-K partials are laid out per model
+    c.rule = opt ? opt->rule : NSVD_RULE_RMSPROP;
+    if (c.rule < 0 || c.rule >= NSVD_RULE_COUNT) return NSVD_EINVAL;
+
+    c.w = carve_fused(dfull, B, ws);
+    c.F = 2 * c.d.m;
+    c.nh = c.d.nlayers - 1;
+    c.offz = (size_t)c.l0 * HID * B;
+    c.offv = (size_t)c.l0 * B;
+    c.pl = part_layout(c.d);
+    c.chain_blocks = (B / BS) * c.Lc;
+    c.pre_chain = (c.nh == 2 || c.nh == 3) && c.chain_blocks <= 128;
+    c.state = opt ? opt->state : nullptr;
+    c.last_window = !(win && req.not_last);
+    // the loss of the step in direct mode (no moment kernel): only when this launch sees every head of the loss
+    const bool direct = evd && !evd->moments && !evd->part;
+    c.step_loss = direct && evd->loss && B / BS <= 32 && (whole || win) && evd->l_off == 0 && evd->Lg == dfull.L && !df;
+    // the streaming form where the shape allows: no dz_i through HBM, the slices' partial gradients through the second pass
+    if (c.nh == 2 && c.F == HID && !c.next && !win && !c.state && whole && c.l0 == 0 && c.w.gpart &&
+        (df || (evd && (evd->moments || evd->part) && evd->Lg % 4 == 0 && evd->Lg <= 128)))
+        c.SS = stream_bwd_slices(c.d, B);
+    c.S = c.SS ? c.SS : S0;
+    c.Bs = B / S0;
+    c.reduce = c.SS || c.S > 1;
+    // 128 x 64 dW_0 tiles: twice as many, half as long (pmlp_common.h)
+    const int nA128 = (c.F / HID) * c.Lc;
+    c.tw = wgrad_tile_width(nA128, c.S);
+    c.nA = c.tw == 64 ? 2 * nA128 : nA128;
+    // whole model, fused optimiser, no split-K only (never with the streaming form: it skips the kernel that writes them)
+    c.emit = opt && opt->emit_planes && !c.SS && c.S == 1 && whole && c.l0 == 0;
+    return 0;
+}
+
+NsvdEvdIn FusedBwd::evd_in() const {
+    NsvdEvdIn e;
+    memset(&e, 0, sizeof(e));
+    if (evd) e = *evd;
+    e.l_off += l0;
+    return e;
+}
+
+ChainArgs FusedBwd::chain_args() const {
     ChainArgs a;
     memset(&a, 0, sizeof(a));
     a.df = df;
-    if (evd) a.evd = *evd;
-    a.evd.l_off += l0;
+    a.evd = evd_in();
     a.jac = w.jac;
     a.dsc = d.has_exp_mask ? w.dsc : nullptr;
     a.dbase = w.dbase + offv;
     a.dfsc = d.has_exp_mask ? w.dfsc + offv : nullptr;
     for (int i = 0; i < d.nlayers; ++i) {
-        a.W[i] = p.W[i] + offW(i);
+        a.W[i] = p->W[i] + offW(i);
         a.zsave[i] = (i < nh) ? w.zsave[i] + offz : nullptr;
         a.dz[i] = (i < nh) ? w.dz[i] + offz : nullptr;
     }
-    a.nlayers = d.nlayers; a.B = B; a.L = d.L;
-    a.ldl = dfull.L; a.l0 = l0;
-    const int chain_only = (B / BS) * d.L;
-    a.chain_blocks = chain_only;
-    int chain_grid = chain_only;
-    nsvd_step_state* state = opt ? opt->state : nullptr;
+    a.nlayers = d.nlayers; a.B = B; a.L = Lc;
+    a.ldl = full->L; a.l0 = l0;
+    a.chain_blocks = chain_blocks;
     a.state = state;
-    // the loss of the step in direct mode (no moment kernel): only when this launch sees every head of the loss
-    const bool direct = evd && !evd->moments && !evd->part;
-    const bool step_loss = direct && evd->loss && B / BS <= 32 && (Lc == dfull.L || win) && evd->l_off == 0 &&
-                           evd->Lg == dfull.L && !df;
     a.loss_part = step_loss ? w.loss_part : nullptr;
-    a.loss_L = dfull.L;
+    a.loss_L = full->L;
     if (next) {  // the next batch's sampling + features as guest workgroups (same arguments as nsvd_fused_features)
-        const FusedWs wn = carve_fused(dfull, B, next->ws);
-        memset(&a.feat, 0, sizeof(a.feat));
+        const FusedWs wn = carve_fused(*full, B, next->ws);
         a.feat.smp = next->smp;
         a.feat.x = next->x; a.feat.xout = next->x;
-        a.feat.fB = p.fourier_B; a.feat.phi = wn.phi; a.feat.phiTc = wn.phiTc; a.feat.sctab = wn.sctab;
+        a.feat.fB = p->fourier_B; a.feat.phi = wn.phi; a.feat.phiTc = wn.phiTc; a.feat.sctab = wn.sctab;
         a.feat.B = B; a.feat.m = d.m; a.feat.D = d.D; a.feat.eps = next->eps;
         if (opt && opt->state) a.feat.smp.offset_add = (const unsigned long long*)&opt->state->step;
         else if (opt && opt->ostate) a.feat.smp.offset_add = (const unsigned long long*)&opt->ostate->step;
         a.feat_nx = (d.m + nsvd_feat::FJ - 1) / nsvd_feat::FJ;
         a.feat_blocks = a.feat_nx * ((B + nsvd_feat::FB - 1) / nsvd_feat::FB);
-        chain_grid += a.feat_blocks;
     }
-    if (state) chain_grid += 1;  // the schedule block
-    // the streaming form (pmlp_stream_bwd.h) where the shape allows: no dz_i through HBM, the slices' partial gradients
-    // through the split-K second pass below
-    int SS = 0;
-    if (nh == 2 && F == HID && !next && !win && !state && Lc == dfull.L && l0 == 0 && w.gpart &&
-        (df || (evd && (evd->moments || evd->part) && evd->Lg % 4 == 0 && evd->Lg <= 128))) {
-        SS = stream_bwd_slices(d, B);
-    }
-    const PartLayout pl = part_layout(d);
+    return a;
+}
+
+StreamArgs FusedBwd::stream_args() const {
+    StreamArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.df = df;
+    sa.jac = w.jac;
+    sa.dsc = d.has_exp_mask ? w.dsc : nullptr;
+    sa.W1 = p->W[1] + offW(1); sa.Wl = p->W[2] + offW(2);
+    sa.a0 = w.zsave[0] + offz; sa.a1 = w.zsave[1] + offz;
+    sa.phiTc = w.phiTc;
+    sa.B = B; sa.L = Lc; sa.ldl = full->L; sa.l0 = l0; sa.S = SS; sa.Bs = B / SS;
+    sa.evd = evd_in();
+    set_part_layout(sa, pl, w.gpart, 3);
+    return sa;
+}
+
+// the chain: streaming form, or the chain kernel (PRE or not) with its guests - the next batch's feature workgroups and
+// the schedule block - behind the chain blocks
+int FusedBwd::launch_chain() const {
     if (SS) {
-        StreamArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.df = df; sa.jac = a.jac; sa.dsc = a.dsc;
-        sa.W1 = a.W[1]; sa.Wl = a.W[2]; sa.a0 = a.zsave[0]; sa.a1 = a.zsave[1]; sa.phiTc = w.phiTc;
-        sa.B = B; sa.L = d.L; sa.ldl = a.ldl; sa.l0 = a.l0; sa.S = SS; sa.Bs = B / SS;
-        sa.evd = a.evd;
-        sa.part = w.gpart; sa.part_stride = pl.stride;
-        for (int i = 0; i < 3; ++i) {
-            sa.poW[i] = pl.oW[i];
-            sa.pob[i] = pl.ob[i];
-        }
-        sa.poscales = pl.oscales;
+        const StreamArgs sa = stream_args();
         static NsvdLdsOptIn lds_opt_in;
         if (const int e = nsvd_lds_opt_in(lds_opt_in, {(const void*)pmlp_stream_bwd2_kernel}, SB2_LDS_BYTES)) return e;
-        hipLaunchKernelGGL(pmlp_stream_bwd2_kernel, dim3(d.L * SS), dim3(512), SB2_LDS_BYTES, s, sa);
-    } else if ((nh == 2 || nh == 3) && chain_only <= 128)
-        hipLaunchKernelGGL(pmlp_fused_bwd_chain_kernel<true>, dim3(chain_grid), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(pmlp_fused_bwd_chain_kernel<false>, dim3(chain_grid), dim3(256), 0, s, a);
-    NSVD_CHECK_LAUNCH();
-    if (win && win->ev_after_chain) {
-        hipError_t e = hipEventRecord(win->ev_after_chain, s);
-        if (e != hipSuccess) return -(int)e;
+        hipLaunchKernelGGL(pmlp_stream_bwd2_kernel, dim3(Lc * SS), dim3(512), SB2_LDS_BYTES, s, sa);
+    } else {
+        const ChainArgs a = chain_args();
+        const dim3 grid(a.chain_blocks + a.feat_blocks + (a.state ? 1 : 0));
+        if (pre_chain) hipLaunchKernelGGL(pmlp_fused_bwd_chain_kernel<true>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(pmlp_fused_bwd_chain_kernel<false>, grid, dim3(256), 0, s, a);
     }
+    NSVD_CHECK_LAUNCH();
+    return 0;
+}
 
+WgradArgs FusedBwd::wgrad_args() const {
     WgradArgs wa;
     memset(&wa, 0, sizeof(wa));
     for (int i = 0; i < d.nlayers; ++i) {
@@ -1219,85 +1312,66 @@ static int fused_backward_impl(const nsvd_model_desc& dfull, const nsvd_params& 
     wa.dbase = w.dbase + offv;
     wa.dfsc = d.has_exp_mask ? w.dfsc + offv : nullptr;
     wa.gscales = (d.has_exp_mask && g.scales) ? g.scales + l0 : nullptr;
-    wa.nlayers = d.nlayers; wa.B = B; wa.L = d.L; wa.F = F;
-    const int rule = opt ? opt->rule : NSVD_RULE_RMSPROP;
-    if (rule < 0 || rule >= NSVD_RULE_COUNT) return NSVD_EINVAL;
+    wa.nlayers = d.nlayers; wa.B = B; wa.L = Lc; wa.F = F;
     if (opt) {
         wa.opt = 1;
         wa.h = opt->h;
         wa.oh = opt->oh;
         auto at = [](float* q, size_t o) { return q ? q + o : nullptr; };  // (slots a rule has none of stay null)
         for (int i = 0; i < d.nlayers; ++i) {
-            wa.oW[i] = NsvdOptPtrs{p.W[i] + offW(i), at(opt->sq.W[i], offW(i)), opt->ema ? opt->ema->W[i] + offW(i) : nullptr};
-            wa.ob[i] = NsvdOptPtrs{p.b[i] + offb(i), at(opt->sq.b[i], offb(i)), opt->ema ? opt->ema->b[i] + offb(i) : nullptr};
+            wa.oW[i] = NsvdOptPtrs{p->W[i] + offW(i), at(opt->sq.W[i], offW(i)), opt->ema ? opt->ema->W[i] + offW(i) : nullptr};
+            wa.ob[i] = NsvdOptPtrs{p->b[i] + offb(i), at(opt->sq.b[i], offb(i)), opt->ema ? opt->ema->b[i] + offb(i) : nullptr};
             wa.mW[i] = opt->mom ? at(opt->mom->W[i], offW(i)) : nullptr;
             wa.mb[i] = opt->mom ? at(opt->mom->b[i], offb(i)) : nullptr;
         }
         if (d.has_exp_mask) {
-            wa.oscales = NsvdOptPtrs{p.scales + l0, at(opt->sq.scales, l0), opt->ema ? opt->ema->scales + l0 : nullptr};
+            wa.oscales = NsvdOptPtrs{p->scales + l0, at(opt->sq.scales, l0), opt->ema ? opt->ema->scales + l0 : nullptr};
             wa.mscales = opt->mom ? at(opt->mom->scales, l0) : nullptr;
         }
         wa.ostate = opt->ostate;
-        wa.ostate_adv = (win && win->not_last) ? nullptr : opt->ostate;
+        wa.ostate_adv = last_window ? opt->ostate : nullptr;
     }
-    wa.state = (win && win->not_last) ? nullptr : state;  // (the optimiser reads the schedule through wa.hstate)
+    wa.state = last_window ? state : nullptr;  // (the optimiser reads the schedule through wa.hstate)
     wa.hstate = state;
-    if (step_loss && !(win && win->not_last)) {
+    if (step_loss && last_window) {
         wa.loss_part = w.loss_part;
         wa.loss = evd->loss;
-        wa.loss_L = dfull.L;
+        wa.loss_L = full->L;
     }
-    wa.nA = (F / HID) * d.L;
-    wa.S = wgrad_slices(d, B);
-    wa.Bs = B / wa.S;
-    wa.nB = 4 * (nh - 1) * d.L;
-    if (SS) wa.S = SS;
-    if (wa.S > 1) {
-        wa.part = w.gpart;
-        wa.part_stride = pl.stride;
-        for (int i = 0; i < d.nlayers; ++i) {
-            wa.poW[i] = pl.oW[i];
-            wa.pob[i] = pl.ob[i];
-        }
-        wa.poscales = pl.oscales;
-    }
-    wa.tw = 128;
-    if (wgrad_tile_width(wa.nA, wa.S) == 64) {  // 128 x 64 tiles: twice as many, half as long (pmlp_common.h)
-        wa.tw = 64;
-        wa.nA *= 2;
-    }
-    wa.hx = pick_xcd_remap_wgrad(d.L, wa.nA / d.L, wa.tw);
-    // One launch: the dW_0 tiles go one per CU first, the small dW_i / db / last-layer workgroups
-    // then co-reside with them (measured: 55 us together vs 42 + 23 us as two launches).
+    wa.nA = nA;
+    wa.nB = 4 * (nh - 1) * Lc;
+    wa.S = S;
+    wa.Bs = Bs;
+    if (S > 1) set_part_layout(wa, pl, w.gpart, d.nlayers);
+    wa.tw = tw;
+    wa.hx = pick_xcd_remap_wgrad(Lc, nA / Lc, tw);
     wa.bid0 = 0;
     // bf16x3 steps: the planes of the updated weights go where the NEXT forward reads them (the other workspace set
-    // when the next batch's features ride along, this one otherwise); whole model, fused optimiser, no split-K only
-    // (never with the streaming form: it skips the kernel that writes the planes)
-    const bool emit = opt && opt->emit_planes && !SS && wa.S == 1 && Lc == dfull.L && l0 == 0;
+    // when the next batch's features ride along, this one otherwise)
     if (emit) {
-        const FusedWs wp = carve_fused(dfull, B, next ? next->ws : ws);
+        const FusedWs wp = carve_fused(*full, B, next ? next->ws : ws);
         wa.w0p = reinterpret_cast<unsigned short*>(wp.w0p);
         wa.whp = reinterpret_cast<unsigned short*>(wp.whp);
     }
-    const dim3 wgrid(wa.S * (wa.nA + wa.nB + 4 * d.L));
-    if (SS) {
-        // (the streaming kernel has written every slice)
-    } else {
-        switch (rule) {
-            case NSVD_RULE_RMSPROP: launch_wgrad<NSVD_RULE_RMSPROP>(wa, emit, wgrid, s); break;
-            case NSVD_RULE_RMSPROP_MOM: launch_wgrad<NSVD_RULE_RMSPROP_MOM>(wa, emit, wgrid, s); break;
-            case NSVD_RULE_SGD: launch_wgrad<NSVD_RULE_SGD>(wa, emit, wgrid, s); break;
-            case NSVD_RULE_SGD_MOM: launch_wgrad<NSVD_RULE_SGD_MOM>(wa, emit, wgrid, s); break;
-            default: launch_wgrad<NSVD_RULE_ADAM>(wa, emit, wgrid, s); break;
-        }
-    }
+    return wa;
+}
+
+// One launch: the dW_0 tiles go one per CU first, the small dW_i / db / last-layer workgroups then co-reside with them
+// (measured: 55 us together vs 42 + 23 us as two launches).
+int FusedBwd::launch_wgrad(const WgradArgs& wa) const {
+    const dim3 wgrid(wa.S * (wa.nA + wa.nB + 4 * wa.L));
+    with_rule(rule, [&](auto r) { launch_wgrad_rule<decltype(r)::value>(wa, emit, wgrid, s); });
     NSVD_CHECK_LAUNCH();
-    if (wa.S == 1 && !SS) return 0;
+    return 0;
+}
+
+// the second pass over the slices' partial gradients: stores the gradients and / or takes the step, as wa's epilogue does
+int FusedBwd::launch_reduce(const WgradArgs& wa) const {
     ReduceArgs ra;
     memset(&ra, 0, sizeof(ra));
     ra.part = w.gpart;
     ra.part_stride = pl.stride;
-    ra.S = wa.S;
+    ra.S = S;
     ra.opt = wa.opt;
     ra.h = wa.h;
     ra.state = state;
@@ -1319,35 +1393,41 @@ static int fused_backward_impl(const nsvd_model_desc& dfull, const nsvd_params& 
     size_t blocks = (ra.total4 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     const dim3 rgrid((unsigned)blocks);
-    switch (rule) {
-        case NSVD_RULE_RMSPROP: hipLaunchKernelGGL(wgrad_reduce_kernel<NSVD_RULE_RMSPROP>, rgrid, dim3(256), 0, s, ra); break;
-        case NSVD_RULE_RMSPROP_MOM: hipLaunchKernelGGL(wgrad_reduce_kernel<NSVD_RULE_RMSPROP_MOM>, rgrid, dim3(256), 0, s, ra); break;
-        case NSVD_RULE_SGD: hipLaunchKernelGGL(wgrad_reduce_kernel<NSVD_RULE_SGD>, rgrid, dim3(256), 0, s, ra); break;
-        case NSVD_RULE_SGD_MOM: hipLaunchKernelGGL(wgrad_reduce_kernel<NSVD_RULE_SGD_MOM>, rgrid, dim3(256), 0, s, ra); break;
-        default: hipLaunchKernelGGL(wgrad_reduce_kernel<NSVD_RULE_ADAM>, rgrid, dim3(256), 0, s, ra); break;
-    }
+    with_rule(rule, [&](auto r) {
+        hipLaunchKernelGGL(wgrad_reduce_kernel<decltype(r)::value>, rgrid, dim3(256), 0, s, ra);
+    });
     NSVD_CHECK_LAUNCH();
     return 0;
 }
 
-int nsvd_fused_backward(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
-                        int B, const float* df, const nsvd_params& g, void* ws, hipStream_t s) {
-    (void)prob;
-    (void)x;
-    return fused_backward_impl(d, p, B, df, nullptr, &g, nullptr, ws, s);
+int FusedBwd::run() const {
+    int rc = launch_chain();
+    if (rc) return rc;
+    if (ev_after_chain) {  // (the next window's chain, on another stream, waits for it)
+        const hipError_t e = hipEventRecord(ev_after_chain, s);
+        if (e != hipSuccess) return -(int)e;
+    }
+    const WgradArgs wa = wgrad_args();
+    if (!SS && (rc = launch_wgrad(wa)) != 0) return rc;  // (the streaming kernel has written every slice)
+    return reduce ? launch_reduce(wa) : 0;
+}
+}  // namespace
+
+int nsvd_fused_backward(const nsvd_model_desc& d, const nsvd_params& p, int B, const float* df, const nsvd_params& g,
+                        void* ws, hipStream_t s) {
+    FusedBwd c;
+    if (const int rc = fused_bwd_plan(c, d, p, B, df, nullptr, &g, nullptr, ws, s, NsvdFusedBwdReq())) return rc;
+    return c.run();
 }
 
 int nsvd_fused_backward_evd(const nsvd_model_desc& d, const nsvd_params& p, int B, const NsvdEvdIn& evd,
-                            const nsvd_params* g, const NsvdOptStep* opt, void* ws, hipStream_t s, int l_begin,
-                            int l_count, const NsvdNextBatch* next, int window_of_step, int not_last,
-                            void* ev_after_chain) {
+                            const nsvd_params* g, const NsvdOptStep* opt, void* ws, hipStream_t s,
+                            const NsvdFusedBwdReq& req) {
     if (!g && !opt) return NSVD_EINVAL;
-    if (next && (d.D < 1 || d.D > 3 || !p.fourier_B || !next->ws || !next->x)) return NSVD_EINVAL;
-    NsvdStepWindow win;
-    win.not_last = not_last;
-    win.ev_after_chain = (hipEvent_t)ev_after_chain;
-    return fused_backward_impl(d, p, B, nullptr, &evd, g, opt, ws, s, l_begin, l_count, next,
-                               window_of_step ? &win : nullptr);
+    if (req.next && (d.D < 1 || d.D > 3 || !p.fourier_B || !req.next->ws || !req.next->x)) return NSVD_EINVAL;
+    FusedBwd c;
+    if (const int rc = fused_bwd_plan(c, d, p, B, nullptr, &evd, g, opt, ws, s, req)) return rc;
+    return c.run();
 }
 
 int nsvd_fused_wgrad_slices(const nsvd_model_desc& d, int B) { return wgrad_slices(d, B); }

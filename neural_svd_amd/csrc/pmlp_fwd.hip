@@ -896,6 +896,23 @@ int launch_fwd(const FwdArgs& a, hipStream_t s, int prof = 3) {  // prof: bit 0 
     NSVD_CHECK_LAUNCH();
     return 0;
 }
+// Every instance of the forward kernel this file launches, in the order their code is emitted: instantiated here, so
+// that the object code does not depend on the order in which the host functions below come to mention them.
+template int launch_fwd<3, 1, 1>(const FwdArgs&, hipStream_t, int);  // bf16x3: jets D = 1, 2, 3 ...
+template int launch_fwd<4, 1, 1>(const FwdArgs&, hipStream_t, int);
+template int launch_fwd<5, 1, 1>(const FwdArgs&, hipStream_t, int);
+template int launch_fwd<3, 0, 1>(const FwdArgs&, hipStream_t, int);  // ... stencil D = 1, 2
+template int launch_fwd<5, 0, 1>(const FwdArgs&, hipStream_t, int);
+template int launch_fwd<3, 1, 0>(const FwdArgs&, hipStream_t, int);  // float32: jets ...
+template int launch_fwd<4, 1, 0>(const FwdArgs&, hipStream_t, int);
+template int launch_fwd<5, 1, 0>(const FwdArgs&, hipStream_t, int);
+template int launch_fwd<5, 0, 0, 0, 1>(const FwdArgs&, hipStream_t, int);  // ... K-split: layer 0 of the plain form, ...
+template int launch_fwd<3, 0, 0, 0, 2>(const FwdArgs&, hipStream_t, int);  // ... the rest of the network, ...
+template int launch_fwd<3, 0, 0, 0, 1>(const FwdArgs&, hipStream_t, int);  // ... layer 0 of the split form
+template int launch_fwd<3, 0, 0, 0, 0>(const FwdArgs&, hipStream_t, int);  // ... stencil D = 1 and the split form, ...
+template int launch_fwd<5, 0, 0, 0, 0>(const FwdArgs&, hipStream_t, int);  // ... stencil D = 2
+template int launch_fwd<4, 0, 0, 1>(const FwdArgs&, hipStream_t, int);  // plain model: four sample tiles, one
+template int launch_fwd<1, 0, 0, 1>(const FwdArgs&, hipStream_t, int);
 }  // namespace
 
 // shape conditions shared by the operator path and the plain-model path (both end in the same fused backward)
@@ -911,11 +928,10 @@ static bool fused_shape_ok(const nsvd_model_desc& d, int B) {
     return true;
 }
 
-bool nsvd_fused_supported(const nsvd_model_desc& d, int B, bool exact) {
+bool nsvd_fused_supported(const nsvd_model_desc& d, int B) {
     // E <= 5 columns per sample: the forward's LDS image (155 KB at E = 5). Stencil: E = 1 + 2D columns for D <= 2,
     // and the split form (one direction's two points + the centre per workgroup, FwdArgs::split) for D = 3; the
     // exact-Laplacian jets have E = D + 2, so D <= 3.
-    (void)exact;
     if (d.D < 1 || d.D > 3) return false;
     return fused_shape_ok(d, B);
 }
@@ -950,27 +966,14 @@ int nsvd_fused_features(const nsvd_model_desc& d, const nsvd_params& p, const ns
                                 sampler, xout, s);
 }
 
-int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
-                       int B, float* f, float* Tf, void* ws, int save, hipStream_t s, int bf3, int raw) {
-    // raw (NeuralEF): leave the raw head outputs in w.base_raw, f / Tf not written (float32 stencil forms only)
-    if (raw && (bf3 || prob.eps <= 0.f)) return NSVD_EUNSUPPORTED;
-    // above three dimensions: the float32 split form of the finite-difference mode only (nsvd_fused_split_nd_supported)
-    if (d.D > 3 && (bf3 || raw || !(prob.eps > 0.f) || !nsvd_fused_split_nd_supported(d, B))) return NSVD_EUNSUPPORTED;
-    const FusedWs w = carve_fused(d, B, ws);
-    const int E = 1 + 2 * d.D, R = E * B, F = 2 * d.m;
-    int rc = 0;
-    if (!(save & 2)) {  // bit 1 of `save`: the features are already in the workspace (nsvd_fused_features)
-        rc = nsvd_fused_features(d, p, prob, x, B, ws, save & 1, s);
-        if (rc) return rc;
-    }
-    const bool planes_ready = (save & 4) != 0;  // bf16x3: the weight planes in this workspace are current (nsvd.h)
-    save &= 1;
+namespace {
+// What the operator forward and the plain-model forward share of the kernel's arguments; each adds only its own fields
+// (outputs, block mapping, the problem or the plain-model constant, the form's split / K-split fields).
+FwdArgs fwd_args(const nsvd_model_desc& d, const nsvd_params& p, const FusedWs& w, const float* x, int B, bool save) {
     FwdArgs a;
     memset(&a, 0, sizeof(a));
     a.phiT = w.phi;
-    a.sctab = w.sctab;
     a.m = d.m;
-    a.ldr = R;
     a.nlayers = d.nlayers;
     for (int i = 0; i < d.nlayers; ++i) {
         a.W[i] = p.W[i];
@@ -979,17 +982,49 @@ int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsv
     }
     a.x = x;
     a.scales = d.has_exp_mask ? p.scales : nullptr;
-    a.prob = prob;
-    a.log_norm = nsvd_importance_log_norm(d.D, prob);
     a.box = nsvd_box_of(d);
-    a.B = B; a.D = d.D; a.L = d.L; a.F = F;
-    a.f = f; a.Tf = Tf;
+    a.B = B; a.D = d.D; a.L = d.L; a.F = 2 * d.m;
     a.jac = save ? w.jac : nullptr;
     a.dsc = (save && d.has_exp_mask) ? w.dsc : nullptr;
-    // XCD-aware block mapping: split heads into HX groups and sample blocks into 8/HX groups, minimising the
-    // bytes each XCD pulls through its L2: (L/HX) * |W_0 slab| + (nsb/SX) * |phi slab|
-    a.xcd_remap = pick_xcd_remap(d.L, B / BS, F);
-    if (bf3) {  // opt-in: layer 0 on the bf16 MFMA with three-way split operands
+    return a;
+}
+
+// the finite-difference epilogue launch behind the split forms: f, Tf (jac, dsc) from the raw head outputs in base_raw
+int fd_epilogue_of(const FwdArgs& a, hipStream_t s) {
+    return nsvd_fd_epilogue(a.base_raw, a.ldr, a.x, a.scales, a.prob, a.B, a.D, a.L, a.f, a.Tf, a.jac, a.dsc, s, 1, a.box);
+}
+
+// NSVD_KSPLIT_FOLD=0: the K-split forms leave f, Tf to the separate epilogue launch instead of their last-arriving
+// direction group (A/B measurements, tests). Read on every call: the tests switch it inside one process.
+bool ksplit_fold() {
+    const char* e = getenv("NSVD_KSPLIT_FOLD");
+    return !(e && e[0] == '0');
+}
+
+// The one-launch forms: the D + 2 jet streams of the exact Laplacian (eps <= 0), or all 1 + 2 D stencil columns in one
+// workgroup (D <= 2)
+template <int BF3>
+int launch_fwd_whole(const FwdArgs& a, hipStream_t s) {
+    if (a.prob.eps <= 0.f) {
+        switch (a.D) {
+            case 1: return launch_fwd<3, 1, BF3>(a, s);
+            case 2: return launch_fwd<4, 1, BF3>(a, s);
+            case 3: return launch_fwd<5, 1, BF3>(a, s);
+        }
+        return NSVD_EUNSUPPORTED;
+    }
+    switch (1 + 2 * a.D) {
+        case 3: return launch_fwd<3, 0, BF3>(a, s);
+        case 5: return launch_fwd<5, 0, BF3>(a, s);
+    }
+    return NSVD_EUNSUPPORTED;
+}
+
+// opt-in: layer 0 on the bf16 MFMA with three-way split operands - the weight planes first, unless they are current (a
+// fused bf16x3 step leaves the planes of the weights it has just updated)
+int forward_bf16x3(FwdArgs a, const nsvd_model_desc& d, const nsvd_params& p, const FusedWs& w, bool planes_ready,
+                   hipStream_t s) {
+    if (!planes_ready) {
         W0SplitArgs sa;
         memset(&sa, 0, sizeof(sa));
         sa.W = reinterpret_cast<const float4*>(p.W[0]);
@@ -998,84 +1033,87 @@ int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsv
         for (int i = 0; i < sa.nhid; ++i) sa.Wh[i] = reinterpret_cast<const float4*>(p.W[i + 1]);
         sa.Ph = reinterpret_cast<uint4*>(w.whp);
         sa.L = d.L; sa.m = d.m;
-        if (!planes_ready) {  // (a fused bf16x3 step leaves the planes of the weights it has just updated)
-            hipLaunchKernelGGL(w0_split_kernel, dim3(2048), dim3(256), 0, s, sa);
-            NSVD_CHECK_LAUNCH();
-        }
-        a.w0p = w.w0p;
-        a.whp = w.whp;
-        if (prob.eps <= 0.f) {
-            switch (d.D) {
-                case 1: return launch_fwd<3, 1, 1>(a, s);
-                case 2: return launch_fwd<4, 1, 1>(a, s);
-                case 3: return launch_fwd<5, 1, 1>(a, s);
-            }
-            return NSVD_EUNSUPPORTED;
-        }
-        switch (E) {
-            case 3: return launch_fwd<3, 0, 1>(a, s);
-            case 5: return launch_fwd<5, 0, 1>(a, s);
-        }
-        return NSVD_EUNSUPPORTED;
+        hipLaunchKernelGGL(w0_split_kernel, dim3(2048), dim3(256), 0, s, sa);
+        NSVD_CHECK_LAUNCH();
     }
-    if (prob.eps <= 0.f) {  // exact Laplacian: D + 2 jet streams
-        switch (d.D) {
-            case 1: return launch_fwd<3, 1>(a, s);
-            case 2: return launch_fwd<4, 1>(a, s);
-            case 3: return launch_fwd<5, 1>(a, s);
-        }
-        return NSVD_EUNSUPPORTED;
-    }
-    if (d.D == 2 && fwd_kslices(d, B) == 4) {  // configs[0]: 4 x 64 workgroups for layer 0, then 64 for the rest
-        a.ks = 4;
-        a.kpart = w.kpart;
-        {
-            const char* e = getenv("NSVD_KSPLIT_FOLD");  // "0": the separate epilogue launch (A/B measurements, tests)
-            a.tickets = (e && e[0] == '0') || raw ? nullptr : w.tickets;
-        }
-        rc = launch_fwd<5, 0, 0, 0, 1>(a, s, 1);  // (the in-run bracket of bench.py spans both launches)
-        if (rc) return rc;
-        // the rest of the network in SPLIT form - 2 x 64 workgroups of three tiles read the plain-form partials - then
-        // the finite-difference epilogue kernel: 128 CUs busy for the latency-bound hidden layers instead of 64
-        a.split = d.D;
-        a.base_raw = w.base_raw;
-        a.kplain = 1;
-        rc = launch_fwd<3, 0, 0, 0, 2>(a, s, 2);
-        if (rc || a.tickets || raw) return rc;  // (tickets: the last direction group of every tile has formed f, Tf)
-        return nsvd_fd_epilogue(w.base_raw, R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L, f, Tf,
-                                save ? w.jac : nullptr, (save && d.has_exp_mask) ? w.dsc : nullptr, s, 1, a.box);
-    }
-    // split-stencil form: D = 3 (7 stencil columns do not fit one workgroup's LDS image), and D = 2 when the plain grid
-    // would leave at least half of the CUs without a workgroup (cfg1: 64 -> 128 workgroups of three column tiles)
-    // (5 <= D <= 12: the same instance, D direction groups, ks = 1 and no tickets: the centre tile is recomputed D times,
-    // 3 D tiles against the 2 D + 1 needed, and nsvd_fd_epilogue takes its direction-loop kernel)
-    if (d.D >= 3 || (d.D == 2 && (B / BS) * d.L <= 128)) {
-        a.split = d.D;
-        a.base_raw = w.base_raw;
-        a.ks = d.D == 2 ? fwd_kslices(d, B) : 1;
-        if (a.ks == 2) {  // 2 x 128 workgroups for layer 0, then 128 for the rest of the network
-            a.kpart = w.kpart;
-            {
-                const char* e = getenv("NSVD_KSPLIT_FOLD");
-                a.tickets = (e && e[0] == '0') || raw ? nullptr : w.tickets;
-            }
-            rc = launch_fwd<3, 0, 0, 0, 1>(a, s, 1);  // (the in-run bracket of bench.py spans both launches)
-            if (rc) return rc;
-            rc = launch_fwd<3, 0, 0, 0, 2>(a, s, 2);
-            if (rc || a.tickets) return rc;
-        } else {
-            rc = launch_fwd<3>(a, s);
-        }
-        if (rc || raw) return rc;
-        return nsvd_fd_epilogue(w.base_raw, R, x, d.has_exp_mask ? p.scales : nullptr, prob, B, d.D, d.L, f, Tf,
-                                save ? w.jac : nullptr, (save && d.has_exp_mask) ? w.dsc : nullptr, s, 1, a.box);
-    }
+    a.w0p = w.w0p;
+    a.whp = w.whp;
+    return launch_fwd_whole<1>(a, s);
+}
+
+// exact Laplacian, or a stencil that fits one workgroup and fills the CUs; raw: the head outputs instead of f, Tf
+int forward_plain(FwdArgs a, const FusedWs& w, int raw, hipStream_t s) {
     if (raw) a.raw = w.base_raw;
-    switch (E) {
-        case 3: return launch_fwd<3>(a, s);
-        case 5: return launch_fwd<5>(a, s);
+    return launch_fwd_whole<0>(a, s);
+}
+
+// configs[0] (D = 2, fwd_kslices = 4): 4 x 64 workgroups for layer 0, then the rest of the network in SPLIT form - 2 x 64
+// workgroups of three tiles read the plain-form partials - and the finite-difference epilogue, by the last-arriving
+// direction group of every tile (tickets) or as a launch: 128 CUs busy for the latency-bound hidden layers instead of 64
+int forward_ksplit4(FwdArgs a, const FusedWs& w, int raw, hipStream_t s) {
+    a.ks = 4;
+    a.kpart = w.kpart;
+    a.tickets = ksplit_fold() && !raw ? w.tickets : nullptr;
+    int rc = launch_fwd<5, 0, 0, 0, 1>(a, s, 1);  // (the in-run bracket of bench.py spans both launches)
+    if (rc) return rc;
+    a.split = a.D;
+    a.base_raw = w.base_raw;
+    a.kplain = 1;
+    rc = launch_fwd<3, 0, 0, 0, 2>(a, s, 2);
+    if (rc || a.tickets || raw) return rc;  // (tickets: the last direction group of every tile has formed f, Tf)
+    return fd_epilogue_of(a, s);
+}
+
+// split-stencil form: D = 3 (7 stencil columns do not fit one workgroup's LDS image), and D = 2 when the plain grid
+// would leave at least half of the CUs without a workgroup (cfg1: 64 -> 128 workgroups of three column tiles)
+// (5 <= D <= 12: the same instance, D direction groups, ks = 1 and no tickets: the centre tile is recomputed D times,
+// 3 D tiles against the 2 D + 1 needed, and nsvd_fd_epilogue takes its direction-loop kernel)
+// ks = 2 (D = 2 only): 2 x 128 workgroups for layer 0, then 128 for the rest of the network
+int forward_split(FwdArgs a, const FusedWs& w, int ks, int raw, hipStream_t s) {
+    a.split = a.D;
+    a.base_raw = w.base_raw;
+    a.ks = ks;
+    int rc;
+    if (ks == 2) {
+        a.kpart = w.kpart;
+        a.tickets = ksplit_fold() && !raw ? w.tickets : nullptr;
+        rc = launch_fwd<3, 0, 0, 0, 1>(a, s, 1);  // (the in-run bracket of bench.py spans both launches)
+        if (rc) return rc;
+        rc = launch_fwd<3, 0, 0, 0, 2>(a, s, 2);
+        if (rc || a.tickets) return rc;
+    } else {
+        rc = launch_fwd<3>(a, s);
     }
-    return NSVD_EUNSUPPORTED;
+    if (rc || raw) return rc;
+    return fd_epilogue_of(a, s);
+}
+}  // namespace
+
+int nsvd_fused_forward(const nsvd_model_desc& d, const nsvd_params& p, const nsvd_problem& prob, const float* x,
+                       int B, float* f, float* Tf, void* ws, int save, hipStream_t s, int bf3, int raw) {
+    // raw (NeuralEF): leave the raw head outputs in w.base_raw, f / Tf not written (float32 stencil forms only)
+    if (raw && (bf3 || prob.eps <= 0.f)) return NSVD_EUNSUPPORTED;
+    // above three dimensions: the float32 split form of the finite-difference mode only (nsvd_fused_split_nd_supported)
+    if (d.D > 3 && (bf3 || raw || !(prob.eps > 0.f) || !nsvd_fused_split_nd_supported(d, B))) return NSVD_EUNSUPPORTED;
+    const bool keep = (save & NSVD_FWD_SAVE) != 0;
+    if (!(save & NSVD_FWD_FEATURES_READY))
+        if (const int rc = nsvd_fused_features(d, p, prob, x, B, ws, keep, s, nullptr, nullptr)) return rc;
+    const FusedWs w = carve_fused(d, B, ws);
+    FwdArgs a = fwd_args(d, p, w, x, B, keep);
+    a.sctab = w.sctab;
+    a.ldr = (1 + 2 * d.D) * B;
+    a.prob = prob;
+    a.log_norm = nsvd_importance_log_norm(d.D, prob);
+    a.f = f; a.Tf = Tf;
+    // XCD-aware block mapping: split heads into HX groups and sample blocks into 8/HX groups, minimising the
+    // bytes each XCD pulls through its L2: (L/HX) * |W_0 slab| + (nsb/SX) * |phi slab|
+    a.xcd_remap = pick_xcd_remap(d.L, B / BS, a.F);
+    if (bf3) return forward_bf16x3(a, d, p, w, (save & NSVD_FWD_PLANES_READY) != 0, s);
+    if (prob.eps <= 0.f) return forward_plain(a, w, 0, s);  // exact Laplacian: D + 2 jet streams
+    const int ks = d.D == 2 ? fwd_kslices(d, B) : 1;
+    if (ks == 4) return forward_ksplit4(a, w, raw, s);
+    if (d.D >= 3 || (d.D == 2 && (B / BS) * d.L <= 128)) return forward_split(a, w, ks, raw, s);
+    return forward_plain(a, w, raw, s);
 }
 
 // ---- plain model evaluation on the fused kernels (E = 1): out = c * model(x), any input dimension --------------
@@ -1084,61 +1122,42 @@ bool nsvd_fused_model_supported(const nsvd_model_desc& d, int B) {
     return fused_shape_ok(d, B);
 }
 
+// the model shape of the kernel-operator row on enough tiles: the streaming form (pmlp_plain_fwd.h) - weights in
+// registers, two workgroups per CU, tpw sample tiles per workgroup
+static int launch_plain_stream(const FwdArgs& a, int tpw, hipStream_t s) {
+    PlainFwdArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.phi = a.phiT;
+    pa.W0 = a.W[0]; pa.b0 = a.b[0]; pa.W1 = a.W[1]; pa.b1 = a.b[1]; pa.Wl = a.W[2]; pa.bl = a.b[2];
+    pa.x = a.x; pa.scales = a.scales; pa.D = a.D; pa.c = a.prob.hard_mul_const; pa.box = a.box;
+    pa.out = a.f; pa.jac = a.jac; pa.dsc = a.dsc;
+    pa.z0 = a.zsave[0]; pa.z1 = a.zsave[1];
+    pa.B = a.B; pa.L = a.L; pa.tpw = tpw;
+    static NsvdLdsOptIn lds_opt_in;
+    if (const int er = nsvd_lds_opt_in(lds_opt_in, {(const void*)pmlp_plain_stream_fwd_kernel}, PF_LDS_BYTES)) return er;
+    nsvd_prof_begin(s);
+    hipLaunchKernelGGL(pmlp_plain_stream_fwd_kernel, dim3((a.B / BS / tpw) * a.L), dim3(256), PF_LDS_BYTES, s, pa);
+    nsvd_prof_end(s);
+    NSVD_CHECK_LAUNCH();
+    return 0;
+}
+
 int nsvd_fused_model_forward(const nsvd_model_desc& d, const nsvd_params& p, const float* x, int B, float c,
                              float* out, void* ws, int save, hipStream_t s) {
     const FusedWs w = carve_fused(d, B, ws);
-    const int F = 2 * d.m;
-    int rc = nsvd_fourier_plain(x, p.fourier_B, w.phi, save ? w.phiTc : nullptr, B, d.D, d.m, s);
-    if (rc) return rc;
-    FwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.phiT = w.phi;
-    a.m = d.m;
-    a.nlayers = d.nlayers;
-    for (int i = 0; i < d.nlayers; ++i) {
-        a.W[i] = p.W[i];
-        a.b[i] = p.b[i];
-        a.zsave[i] = (save && i < d.nlayers - 1) ? w.zsave[i] : nullptr;
-    }
-    a.x = x;
-    a.scales = d.has_exp_mask ? p.scales : nullptr;
+    if (const int rc = nsvd_fourier_plain(x, p.fourier_B, w.phi, save ? w.phiTc : nullptr, B, d.D, d.m, s)) return rc;
+    FwdArgs a = fwd_args(d, p, w, x, B, save != 0);
     a.prob.hard_mul_const = c;
-    a.box = nsvd_box_of(d);
     a.plain = 1;
-    a.B = B; a.D = d.D; a.L = d.L; a.F = F;
     a.f = out;
-    a.jac = save ? w.jac : nullptr;
-    a.dsc = (save && d.has_exp_mask) ? w.dsc : nullptr;
-    // the model shape of the kernel-operator row on enough tiles: the streaming form (pmlp_plain_fwd.h) - weights in
-    // registers, two workgroups per CU
-    {
-        const int tpw = plain_stream_tpw(d, B);
-        if (tpw > 0) {
-            PlainFwdArgs pa;
-            memset(&pa, 0, sizeof(pa));
-            pa.phi = w.phi;
-            pa.W0 = p.W[0]; pa.b0 = p.b[0]; pa.W1 = p.W[1]; pa.b1 = p.b[1]; pa.Wl = p.W[2]; pa.bl = p.b[2];
-            pa.x = x; pa.scales = a.scales; pa.D = d.D; pa.c = c; pa.box = a.box;
-            pa.out = out; pa.jac = a.jac; pa.dsc = a.dsc;
-            pa.z0 = a.zsave[0]; pa.z1 = a.zsave[1];
-            pa.B = B; pa.L = d.L; pa.tpw = tpw;
-            static NsvdLdsOptIn lds_opt_in;
-            if (const int er = nsvd_lds_opt_in(lds_opt_in, {(const void*)pmlp_plain_stream_fwd_kernel}, PF_LDS_BYTES))
-                return er;
-            nsvd_prof_begin(s);
-            hipLaunchKernelGGL(pmlp_plain_stream_fwd_kernel, dim3((B / BS / tpw) * d.L), dim3(256), PF_LDS_BYTES, s, pa);
-            nsvd_prof_end(s);
-            NSVD_CHECK_LAUNCH();
-            return 0;
-        }
-    }
+    if (const int tpw = plain_stream_tpw(d, B)) return launch_plain_stream(a, tpw, s);
     // four sample tiles per workgroup (a head's W_0 / W_i tiles fetched once per 128 samples, the fixed costs of a
     // workgroup - first-chunk latency, weight DMA, epilogue - paid once per 128) whenever that still leaves every CU
     // two workgroups; one tile otherwise
     if (B % (4 * BS) == 0 && (B / (4 * BS)) * d.L >= 512) {
-        a.xcd_remap = pick_xcd_remap(d.L, B / (4 * BS), F);
+        a.xcd_remap = pick_xcd_remap(d.L, B / (4 * BS), a.F);
         return launch_fwd<4, 0, 0, 1>(a, s);
     }
-    a.xcd_remap = pick_xcd_remap(d.L, B / BS, F);
+    a.xcd_remap = pick_xcd_remap(d.L, B / BS, a.F);
     return launch_fwd<1, 0, 0, 1>(a, s);
 }
