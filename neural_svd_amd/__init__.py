@@ -7,7 +7,7 @@ from . import _lib  # noqa: F401
 
 __all__ = ["_lib", "SketchyRetrieval", "evaluate_truncations", "Nystrom", "run_nystrom", "NystromSVD", "DotKernelOperator",
            "SpIN", "SpinKernelTrainer", "SpINx", "SpinxKernelTrainer", "NefKernelTrainer", "PairedFunctions", "KernelSvdTrainer", "gaussian_cross_singular_values",
-           "gaussian_cross_modes", "kernel_singular_values"]
+           "gaussian_cross_modes", "kernel_singular_values", "DenseCrossOperator", "DenseSvdTrainer"]
 
 
 def __getattr__(name):
@@ -34,10 +34,11 @@ def __getattr__(name):
     if name == "NefKernelTrainer":  # NeuralEF on the kernel-operator path (neuralef.py), the same way
         from . import neuralef
         return neuralef.NefKernelTrainer
-    if name in ("PairedFunctions", "KernelSvdTrainer"):  # the kernel SVD path (kernel_svd.py), the same way
+    if name in ("PairedFunctions", "KernelSvdTrainer", "DenseSvdTrainer"):  # the kernel SVD path (kernel_svd.py), the same way
         from . import kernel_svd
         return getattr(kernel_svd, name)
-    if name in ("gaussian_cross_singular_values", "gaussian_cross_modes", "kernel_singular_values"):
+    if name in ("gaussian_cross_singular_values", "gaussian_cross_modes", "kernel_singular_values",
+                "DenseCrossOperator"):
         from . import kernel_ops
         return getattr(kernel_ops, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

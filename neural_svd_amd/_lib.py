@@ -243,11 +243,38 @@ SIGNATURES = {
                                  _Z, _P]),
 }
 
+# libnsvd_dense.so (include/nsvd_dense.h): the two-sided dense product, a library of its own beside libnsvd_hip.so
+DENSE_LIB_PATH = os.path.join(_PKG_DIR, "libnsvd_dense.so")
+DENSE_SIGNATURES = {
+    "nsvd_kernel_apply_pair_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "nsvd_kernel_apply_pair_partition": (_I, [_I, _I, _I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "nsvd_kernel_apply_pair": (_I, [_P, _Z, _I, _I, _P, _I, _P, _I, _P, _P, _I, _F, _F, _P, _P, _P, _Z, _P]),
+}
+
 _lib: Optional[C.CDLL] = None
+_dense: Optional[C.CDLL] = None
 
 
 class NsvdError(RuntimeError):
     pass
+
+
+def _typed(path: str, signatures: dict) -> C.CDLL:
+    """the shared library at `path` with every entry point of `signatures` typed"""
+    if not os.path.exists(path):
+        raise NsvdError(
+            f"{path} not found: the HIP extension has not been built. Run "
+            f"`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C neural_svd_amd/csrc`). "
+            f"neural_svd_amd has no CPU / eager fallback by design.")
+    lib = C.CDLL(path)
+    for name, (res, args) in signatures.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise NsvdError(f"{path} does not export {name}; rebuild the extension") from e
+        fn.restype = res
+        fn.argtypes = args
+    return lib
 
 
 def load() -> C.CDLL:
@@ -260,24 +287,21 @@ def load() -> C.CDLL:
     # /opt/rocm's runtime in, torch brings its own, and kernels launched through one cannot see memory allocated
     # through the other (HIP error 100 at the first launch: found by build() + smoke() in one process)
     import torch  # noqa: F401
-    if not os.path.exists(LIB_PATH):
-        raise NsvdError(
-            f"{LIB_PATH} not found: the HIP extension has not been built. Run "
-            f"`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C neural_svd_amd/csrc`). "
-            f"neural_svd_amd has no CPU / eager fallback by design.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise NsvdError(f"{LIB_PATH} does not export {name}; rebuild the extension") from e
-        fn.restype = res
-        fn.argtypes = args
+    lib = _typed(LIB_PATH, SIGNATURES)
     v = lib.nsvd_abi_version()
     if v != ABI_VERSION:
         raise NsvdError(f"ABI version mismatch: library {v}, binding {ABI_VERSION}; rebuild the extension")
     _lib = lib
     return lib
+
+
+def load_dense() -> C.CDLL:
+    """Load (once) and type libnsvd_dense.so, behind libnsvd_hip.so (torch's HIP runtime first, the ABI check)."""
+    global _dense
+    if _dense is None:
+        load()
+        _dense = _typed(DENSE_LIB_PATH, DENSE_SIGNATURES)
+    return _dense
 
 
 def check(rc: int, what: str) -> None:

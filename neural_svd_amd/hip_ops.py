@@ -125,7 +125,8 @@ def _call(name: str, *args) -> None:
     typed function is kept by name and `check` entered on failure only: this frame is on the path of every step.)"""
     fn = _ENTRY.get(name)
     if fn is None:
-        fn = _ENTRY[name] = getattr(_lib.load(), "nsvd_" + name)
+        full = "nsvd_" + name  # (the dense pair's entry points are libnsvd_dense.so's: include/nsvd_dense.h)
+        fn = _ENTRY[name] = getattr(_lib.load_dense() if full in _lib.DENSE_SIGNATURES else _lib.load(), full)
     rc = fn(*args, _stream())
     if rc != 0:
         check(rc, "nsvd_" + name)
@@ -842,6 +843,66 @@ def kernel_apply(K: torch.Tensor, N: int, rows: torch.Tensor, cols: torch.Tensor
     _call("kernel_apply", K.data_ptr(), K.stride(0), int(N), rows.data_ptr(), B1, cols.data_ptr(), B2, _ptr(f, "f"), L,
           float(scale), _ptr(out, "out"), *_ws(ws))
     return out
+
+
+def kernel_apply_pair_workspace(N1: int, N2: int, B1: int, B2: int, L: int, device) -> torch.Tensor:
+    """workspace of kernel_apply_pair: with B1p, N2p, Lp = B1, N2, L rounded up to 64 and (RG, CG) =
+    kernel_apply_pair_partition(...), 4 * (Lp N2p + Lp B1p + CG B1p Lp + RG N2p Lp) bytes, each term rounded up to 256"""
+    n = _lib.load_dense().nsvd_kernel_apply_pair_workspace_bytes(int(N1), int(N2), int(B1), int(B2), int(L))
+    if n == 0:
+        raise NsvdError(f"nsvd_kernel_apply_pair_workspace_bytes: every size must be positive "
+                        f"(N1={N1} N2={N2} B1={B1} B2={B2} L={L})")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def kernel_apply_pair_partition(N1: int, N2: int, B1: int, B2: int, L: int) -> Tuple[int, int]:
+    """(row groups, column groups) of an nsvd_kernel_apply_pair call of that shape: the runs of 64-row tiles of the
+    batch and of columns of A that workgroups own = the partial copies of A[rows, :]^T f and of out_x. Host only."""
+    rg, cg = C.c_int(0), C.c_int(0)
+    check(_lib.load_dense().nsvd_kernel_apply_pair_partition(int(N1), int(N2), int(B1), int(B2), int(L), C.byref(rg),
+                                                       C.byref(cg)), "nsvd_kernel_apply_pair_partition")
+    return rg.value, cg.value
+
+
+@_on_tensor_device
+def kernel_apply_pair(A: torch.Tensor, N1: int, N2: int, rows: torch.Tensor, cols: torch.Tensor, g: torch.Tensor,
+                      f: torch.Tensor, scale_g: float, scale_f: float, ws: Optional[torch.Tensor] = None,
+                      out_x: Optional[torch.Tensor] = None, out_y: Optional[torch.Tensor] = None):
+    """Both halves of an SVD step on a stored matrix in one pass (nsvd_kernel_apply_pair), no transposed copy:
+    out_x = scale_g * A[rows][:, cols] @ g ("A g", (B1, L)) and out_y = scale_f * A[rows][:, cols]^T @ f ("A^T f",
+    (B2, L)). A: (>= N1, lda) float32 on the GPU with unit column stride, lda >= N2 rounded up to 64; rows (B1),
+    cols (B2): int64; g: (B2, L), f: (B1, L). Returns (out_x, out_y)."""
+    name = "kernel_apply_pair"
+    if A.dim() != 2 or not A.is_cuda or A.dtype != torch.float32 or A.stride(1) != 1:
+        raise NsvdError(f"{name}: A must be a 2-D float32 GPU tensor with unit column stride")
+    N1, N2 = int(N1), int(N2)
+    if not (0 < N1 <= A.shape[0]) or not (0 < N2 <= A.shape[1]):
+        raise NsvdError(f"{name}: (N1, N2) = ({N1}, {N2}) must be positive and within A {tuple(A.shape)}")
+    for t, n in ((rows, "rows"), (cols, "cols")):
+        if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+            raise NsvdError(f"{name}: {n} must be a contiguous 1-D int64 GPU tensor")
+    B1, B2 = rows.numel(), cols.numel()
+    if g.dim() != 2 or g.shape[0] != B2:
+        raise NsvdError(f"{name}: g must be (len(cols), L)")
+    L = g.shape[1]
+    if tuple(f.shape) != (B1, L):
+        raise NsvdError(f"{name}: f must be (len(rows), L) with g's L")
+    gp, fp = _ptr(g, "g"), _ptr(f, "f")
+    if out_x is None:
+        out_x = torch.empty((B1, L), dtype=torch.float32, device=g.device)
+    elif tuple(out_x.shape) != (B1, L):
+        raise NsvdError(f"{name}: out_x must be (len(rows), L)")
+    if out_y is None:
+        out_y = torch.empty((B2, L), dtype=torch.float32, device=g.device)
+    elif tuple(out_y.shape) != (B2, L):
+        raise NsvdError(f"{name}: out_y must be (len(cols), L)")
+    ox, oy = _ptr(out_x, "out_x"), _ptr(out_y, "out_y")
+    if ws is None:
+        ws = torch.empty(max(_lib.load_dense().nsvd_kernel_apply_pair_workspace_bytes(N1, N2, B1, B2, L), 256),
+                         dtype=torch.uint8, device=g.device)
+    _call(name, A.data_ptr(), A.stride(0), N1, N2, rows.data_ptr(), B1, cols.data_ptr(), B2, gp, fp, L, float(scale_g),
+          float(scale_f), ox, oy, *_ws(ws))
+    return out_x, out_y
 
 
 RBF_GAUSSIAN, RBF_EXPONENTIAL = 0, 1  # NSVD_RBF_* (include/nsvd.h)

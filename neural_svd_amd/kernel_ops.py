@@ -84,6 +84,115 @@ class DenseKernelOperator:
         return torch.randint(self.N, (batch_size,), device=self.K.device, generator=generator)
 
 
+class IndexColumnModel(nn.Module):
+    """model(idx) = net(points[idx]) for an index batch (B,) or (B, 1): the column form is how index batches travel
+    through ``NestedLoRA.compute_loss_kernel_svd``, which insists on 2-D batches."""
+
+    def __init__(self, net: nn.Module, points: torch.Tensor):
+        super().__init__()
+        self.net = net
+        self.register_buffer("points", points, persistent=False)
+
+    def forward(self, idx):
+        return self.net(self.points.index_select(0, _flat_indices(idx, "IndexColumnModel")))
+
+
+def _flat_indices(idx: torch.Tensor, who: str) -> torch.Tensor:
+    """an index batch (B,) or (B, 1) as contiguous 1-D int64 on the GPU; anything else raises"""
+    if not idx.is_cuda:
+        raise H.NsvdError(f"{who}: index batches must live on the GPU (no CPU path)")
+    if idx.dim() == 2 and idx.shape[1] == 1:
+        idx = idx[:, 0]
+    if idx.dim() != 1 or idx.dtype not in (torch.int64, torch.int32):
+        raise H.NsvdError(f"{who}: an index batch is (B,) or (B, 1) of integers (got {tuple(idx.shape)} {idx.dtype})")
+    return idx.to(torch.int64).contiguous()
+
+
+class DenseCrossOperator:
+    """A: (N1, N2) float32, any values (rectangular, not symmetric): a stored matrix between N1 row points
+    ``points_x`` (N1, Dx) and N2 column points ``points_y`` (N2, Dy), as an operator from functions of the column points
+    to functions of the row points under the UNIFORM measures on both,
+
+        (A g)(i) = (1 / N2) sum_j A[i][j] g(j),
+
+    whose singular values are ``svdvals(A) / sqrt(N1 N2)``. Minibatches are point INDICES drawn with replacement, rows
+    and columns apart; the two-sided product of an SVD step is one ``nsvd_kernel_apply_pair`` call on the zero-padded
+    copy kept here (lda = ceil64(N2)) - no transposed copy exists. ``kernel_svd.DenseSvdTrainer`` trains on it; the
+    class path is ``NestedLoRA.compute_loss_kernel_svd(op.get_approx_kernel_svd_op(), idx_x[:, None], idx_y[:, None])``
+    on ``op.index_models(f_net, g_net)``."""
+
+    def __init__(self, A: torch.Tensor, points_x: torch.Tensor, points_y: torch.Tensor):
+        if A.dim() != 2 or points_x.dim() != 2 or points_y.dim() != 2 or points_x.shape[0] != A.shape[0] or \
+                points_y.shape[0] != A.shape[1]:
+            raise ValueError("DenseCrossOperator: A must be (N1, N2), points_x (N1, Dx) and points_y (N2, Dy)")
+        if not A.is_cuda:
+            raise H.NsvdError("DenseCrossOperator: A must live on the GPU (no CPU path)")
+        self.N1, self.N2 = int(A.shape[0]), int(A.shape[1])
+        self.device = A.device
+        ld = (self.N2 + 63) // 64 * 64
+        # rows are read in whole 64-float chunks: a zero-padded copy with a leading dimension of ceil64(N2)
+        self.A = torch.zeros((self.N1, ld), dtype=torch.float32, device=A.device)
+        self.A[:, :self.N2] = A.float()
+        self.points_x = points_x.to(A.device).float().contiguous()
+        self.points_y = points_y.to(A.device).float().contiguous()
+        self.dim_x, self.dim_y = int(points_x.shape[1]), int(points_y.shape[1])
+
+    def sample_indices(self, batch_size: int, generator=None):
+        """(idx_x, idx_y): `batch_size` row indices and as many column indices, drawn with replacement"""
+        return (torch.randint(self.N1, (batch_size,), device=self.device, generator=generator),
+                torch.randint(self.N2, (batch_size,), device=self.device, generator=generator))
+
+    def workspace_pair(self, B1: int, B2: int, L: int, device=None) -> torch.Tensor:
+        return H.kernel_apply_pair_workspace(self.N1, self.N2, B1, B2, L, self.device if device is None else device)
+
+    def apply_pair_raw(self, rows, cols, g, f, scale_g, scale_f, ws=None, out_x=None, out_y=None):
+        """(out_x, out_y) = (scale_g * A[rows][:, cols] @ g, scale_f * A[rows][:, cols]^T @ f): one
+        nsvd_kernel_apply_pair call, no gradient. rows (B1,), cols (B2,) int64; g: (B2, L), f: (B1, L)."""
+        return H.kernel_apply_pair(self.A, self.N1, self.N2, rows, cols, g, f, scale_g, scale_f, ws=ws, out_x=out_x,
+                                   out_y=out_y)
+
+    def index_models(self, f_net: nn.Module, g_net: nn.Module):
+        """the PairedFunctions of index wrappers: .f takes row indices, .g column indices, (B,) or (B, 1)"""
+        from .kernel_svd import PairedFunctions
+        return PairedFunctions(IndexColumnModel(f_net, self.points_x), IndexColumnModel(g_net, self.points_y))
+
+    def get_approx_kernel_svd_op(self):
+        """-> svd_op(model_f, model_g, x, y, importance=None) -> (Tg, f, Tadjf, g), the arguments of
+        NestedLoRALossFunctionSVD: x, y index batches ((B,) or (B, 1)), f = model_f(x) and g = model_g(y) differentiable
+        (index models: ``index_models``), Tg = A[x][:, y] g / B2 and Tadjf = A[x][:, y]^T f / B1 without gradient."""
+        def svd_op(model_f, model_g, x, y, importance=None):
+            if importance is not None:
+                raise NotImplementedError("DenseCrossOperator: importance weights are not defined for an index batch")
+            rows, cols = _flat_indices(x, "DenseCrossOperator: x"), _flat_indices(y, "DenseCrossOperator: y")
+            f, g = model_f(x), model_g(y)
+            with torch.no_grad():
+                Tg, Tadjf = self.apply_pair_raw(rows, cols, g.detach().float().contiguous(),
+                                                f.detach().float().contiguous(), 1.0 / cols.numel(), 1.0 / rows.numel())
+            return Tg, f, Tadjf, g
+        return svd_op
+
+    @torch.no_grad()
+    def quotients(self, model_f, model_g):
+        """Singular-value estimates of the column pairs of F = model_f(points_x) (N1, L) and G = model_g(points_y)
+        (N2, L), coordinate models evaluated on ALL points:
+        s_l = (F_l^T A G_l / (N1 N2)) / sqrt((|F_l|^2 / N1) (|G_l|^2 / N2)), with A G from one nsvd_kernel_apply_pair
+        call at rows = arange(N1), cols = arange(N2) and the column sums in float64. Returns dict(svals, norms_f,
+        norms_g) of float64 numpy arrays - the counterpart of ``kernel_singular_values``; compare with
+        ``svdvals(A) / sqrt(N1 N2)``."""
+        F = model_f(self.points_x).float().contiguous()
+        G = model_g(self.points_y).float().contiguous()
+        if F.dim() != 2 or G.dim() != 2 or F.shape[0] != self.N1 or G.shape[0] != self.N2 or F.shape[1] != G.shape[1]:
+            raise H.NsvdError("DenseCrossOperator.quotients: the models must return (N1, L) and (N2, L)")
+        rows = torch.arange(self.N1, device=self.device)
+        cols = torch.arange(self.N2, device=self.device)
+        AG, _ = self.apply_pair_raw(rows, cols, G, F, 1.0 / self.N2, 1.0 / self.N1)
+        F64 = F.double()
+        cross = (F64 * AG.double()).sum(0) / self.N1
+        nf, ng = (F64 * F64).sum(0) / self.N1, (G.double() ** 2).sum(0) / self.N2
+        return dict(svals=(cross / torch.sqrt(nf * ng)).cpu().numpy(), norms_f=nf.cpu().numpy(),
+                    norms_g=ng.cpu().numpy())
+
+
 def synthetic_psd_kernel(N: int = 10000, rank: int = 256, dim: int = 16, seed: int = 0, device="cuda:0"):
     """cfg4's operator: z_j ~ N(0, I_dim), K = A A^T / rank + 1e-3 I with A ~ randn(N, rank); seeded on the host."""
     g = torch.Generator().manual_seed(seed)
