@@ -1,7 +1,8 @@
 // What the matrix-free kernel products share (rbf_apply.hip, dot_apply.hip, rbf_apply_pair.hip, dot_apply_pair.hip;
-// the slice rule and the tile store also serve kernel_apply.hip): the padding rule,
-// the prep kernel (pad coordinates, row norms, transposes), the reduce kernels, the maps of the kernel kinds and the
-// pieces of tile_nt.h's layout that every main kernel repeats. Everything has internal linkage: each file gets its own.
+// the slice rule and the tile store also serve kernel_apply.hip, the barrier kernel_apply_pair.hip): the padding rule,
+// the prep kernel (pad coordinates, row norms, transposes), the reduce of partial copies, the maps of the kernel kinds
+// and the pieces of tile_nt.h's layout that every main kernel repeats. What only the two-sided products share is
+// pair_common.h, on top of this header. Everything has internal linkage: each file gets its own.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -41,17 +42,6 @@ static inline bool apply_args_ok(std::initializer_list<const void*> ptrs, int B1
 static inline bool apply_overlap(const float* a, size_t na, const float* b, size_t nb) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return pa < pb + nb * sizeof(float) && pb < pa + na * sizeof(float);
-}
-
-// nsvd_*_apply_pair_partition: carve is the file's own
-template <class Carve>
-static inline int apply_pair_partition(Carve carve, int B1, int B2, int D, int L, int* row_groups, int* col_slices) {
-    if (!apply_args_ok({row_groups, col_slices}, B1, B2, D, L)) return NSVD_EINVAL;
-    if (D > APPLY_MAX_D) return NSVD_EUNSUPPORTED;
-    const auto w = carve(nullptr, B1, B2, D, L);
-    *row_groups = w.RG;
-    *col_slices = w.CG;
-    return 0;
 }
 
 // the exponent's constant of the radial kinds, log2 e / (2 ell^2) (Gaussian) or log2 e / ell (exponential), in double
@@ -159,20 +149,6 @@ static __global__ void __launch_bounds__(256) apply_reduce_kernel(const float* _
                                                                   int B1, int L, float scale, float* __restrict__ out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < (size_t)B1 * L) apply_reduce_one(part, S, B1p, Lp, L, i, scale, out);
-}
-
-// both outputs of a two-sided product in one launch: out_x from the CG copies partX, then out_y from the RG copies partY
-template <int = 0>
-static __global__ void __launch_bounds__(256)
-apply_pair_reduce_kernel(const float* __restrict__ partX, int CG, int B1p, const float* __restrict__ partY, int RG, int B2p,
-                         int Lp, int B1, int B2, int L, float scale_g, float scale_f, float* __restrict__ out_x,
-                         float* __restrict__ out_y) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t nx = (size_t)B1 * L, ny = (size_t)B2 * L;
-    if (i < nx)
-        apply_reduce_one(partX, CG, B1p, Lp, L, i, scale_g, out_x);
-    else if (i - nx < ny)
-        apply_reduce_one(partY, RG, B2p, Lp, L, i - nx, scale_f, out_y);
 }
 
 // ---- device: the pieces of a main kernel -----------------------------------------------------------------------------

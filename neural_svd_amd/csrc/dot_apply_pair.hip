@@ -6,10 +6,10 @@
 // Two nsvd_dot_apply calls with swapped arguments form every x_i . y_j twice on the matrix pipe and run the map twice;
 // here each kernel value is formed ONCE per 64-head tile and feeds both contractions.
 //
-// The workgroup, its runs and the partial copies are rbf_apply_pair.hip's (prep and reduce kernels: apply_common.h): a workgroup (row group,
-// head tile, column group) owns a run of 64-row x tiles and a run of slices of at most four 64-row y chunks; per slice
-// it walks its x tiles, the K^T f accumulators of the slice's chunks (4 x 16 registers) staying in registers over the
-// run. The kernel values are dot_apply.hip's: per (x tile, chunk) a step
+// The workgroup, its runs, the partial copies, the reduce and the two-sided contraction are pair_common.h's (the prep
+// kernel: apply_common.h): a workgroup (row group, head tile, column group) owns a run of 64-row x tiles and a run of
+// slices of at most four 64-row y chunks; per slice it walks its x tiles, the K^T f accumulators of the slice's chunks
+// (4 x 16 registers) staying in registers over the run. The kernel values are dot_apply.hip's: per (x tile, chunk) a step
 //   1. forms S^T = Y_chunk X_tile^T (64 x 64 x Dp) on v_mfma_f32_32x32x2_f32 from the x tile and the y chunk in LDS
 //      (rows of Dp + 4 floats, b128 reads; the x operand is not loop invariant here, so it cannot live in registers);
 //   2. applies the map in registers - a lane owns ONE x row (|x_i| read from the tile's norms) and 4 runs of 4
@@ -19,47 +19,44 @@
 //      due, the f^T tile (first chunk of an x tile) and the next x tile (last chunk), between the step's two LDS-only
 //      barriers;
 //   4. contracts the copy with the g^T chunk into the K g accumulators (b128 reads) and reads the SAME copy column-wise
-//      (32-bit reads) against the f^T tile into the K^T f accumulators, as rbf_apply_pair.hip does.
+//      (32-bit reads) against the f^T tile into the K^T f accumulators (pair_contract).
 // g^T runs one chunk ahead in registers; the next y chunk is requested after the map and staged under the barriers, the
 // f^T tile and the x tile are requested between them (once per tile). Every buffer is single: LDS is 3 tiles + x tile +
-// y chunk = 57.5 KB at D <= 8, 77.5 KB at D = 48 (two workgroups per CU), 85.5 KB at D = 64 (one). 174 / 191 VGPRs, no
+// y chunk = 57.5 KB at D <= 8, 77.5 KB at D = 48 (two workgroups per CU), 85.5 KB at D = 64 (one). 174 / 190 VGPRs, no
 // scratch - by three rules the source keeps: staging loads are unconditional, lane offsets of global
-// addresses are opaque to the compiler (dpair_opaque), and a chain's first MFMA takes an inline zero.
-#include "apply_common.h"
-#include "pair_split.h"
+// addresses are opaque to the compiler (dpair_opaque), and a chain's first MFMA takes an inline zero. They bind what
+// this kernel takes from pair_common.h, and they are why three pieces stay here: the walk (one K g chain that FIRST
+// starts), the flush (wave-uniform addresses, one lane offset) and the registers of a coordinate block (named float4s;
+// kept in a struct they cost the polynomial kernel two registers).
+#include "pair_common.h"
 
 namespace {
 
 constexpr int T = NSVD_TNT_T, KC = NSVD_TNT_KC, LDT = NSVD_TNT_LDT;
-constexpr int DPAIR_TILE = T * LDT;   // one 64 x 64 LDS tile with padded rows
 
-struct DPairWs {
-    float* xP;     // (B1p, Dp) x coordinates, zero padded
-    float* xN;     // (B1p) |x_i| (the deep ReLU kinds: |x_i|^2), 0 for padded rows
-    float* yP;     // (B2p, Dp) y coordinates, zero padded
-    float* yN;     // (B2p) |y_j| (the deep ReLU kinds: |y_j|^2), 0 for padded rows
-    float* gT;     // (Lp, B2p) g transposed, zero padded
-    float* fT;     // (Lp, B1p) f transposed, zero padded
-    float* partX;  // (CG, B1p, Lp) partial K g
-    float* partY;  // (RG, B2p, Lp) partial K^T f
-    int B1p, B2p, Dp, Lp, RG, CG;
+struct DPairWs : PairParts {
+    float* xP;  // (B1p, Dp) x coordinates, zero padded
+    float* xN;  // (B1p) |x_i| (the deep ReLU kinds: |x_i|^2), 0 for padded rows
+    float* yP;  // (B2p, Dp) y coordinates, zero padded
+    float* yN;  // (B2p) |y_j| (the deep ReLU kinds: |y_j|^2), 0 for padded rows
+    float* gT;  // (Lp, B2p) g transposed, zero padded
+    float* fT;  // (Lp, B1p) f transposed, zero padded
+    int Dp;
     size_t bytes;
 };
 
 DPairWs carve(void* base, int B1, int B2, int D, int L) {
     const ApplyPad pd = apply_pad(B1, B2, D, L, 8);
     DPairWs w;
-    w.B1p = pd.B1p, w.B2p = pd.B2p, w.Dp = pd.Dp, w.Lp = pd.Lp;
-    pair_split(w.B1p / T, nsvd_cdiv(w.B2p / KC, PAIR_SLICE), w.Lp / T, &w.RG, &w.CG);
+    w.Dp = pd.Dp;
     NsvdArena a(base);
-    w.xP = a.take((size_t)w.B1p * w.Dp);
-    w.xN = a.take((size_t)w.B1p);
-    w.yP = a.take((size_t)w.B2p * w.Dp);
-    w.yN = a.take((size_t)w.B2p);
-    w.gT = a.take((size_t)w.Lp * w.B2p);
-    w.fT = a.take((size_t)w.Lp * w.B1p);
-    w.partX = a.take((size_t)w.CG * w.B1p * w.Lp);
-    w.partY = a.take((size_t)w.RG * w.B2p * w.Lp);
+    w.xP = a.take((size_t)pd.B1p * pd.Dp);
+    w.xN = a.take((size_t)pd.B1p);
+    w.yP = a.take((size_t)pd.B2p * pd.Dp);
+    w.yN = a.take((size_t)pd.B2p);
+    w.gT = a.take((size_t)pd.Lp * pd.B2p);
+    w.fT = a.take((size_t)pd.Lp * pd.B1p);
+    static_cast<PairParts&>(w) = pair_parts(a, pd.B1p, pd.B2p, pd.Lp);
     w.bytes = a.off;
     return w;
 }
@@ -83,29 +80,33 @@ __device__ __forceinline__ size_t dpair_opaque(size_t v) {
     return v;
 }
 
-struct DPairLane {
-    int t, lane, wv, ra, rb, kq, lr0, lc, nq, xld, nv;
+struct DPairLane : PairLane {
+    int t, nq, xld, nv;
     int so0, so1, so2, so3;  // LDS offsets of this thread's float4s of a staged (64, Dp) block
     unsigned bo0, bo1, bo2, bo3, bon;  // byte offsets of the same float4s in the workspace block, and of a norm
     size_t go, fo;  // byte offset of this thread's first float4 in a g^T chunk / an f^T tile
     size_t gr, fr;  // floats between the 4 rows it stages
 };
 
-// a (64, Dp) block of padded coordinates (contiguous in the workspace, wave-uniform address) and its 64 norms: thread t
-// moves the float4s t + 256 i < 16 Dp (named registers: hipcc demotes a float4 array rewritten inside the loop to scratch)
+// a (64, Dp) block of padded coordinates and its 64 norms, contiguous in the workspace (wave-uniform addresses)
+struct DPairBlock {
+    const float *c, *n;
+};
+
+// ... into a thread's registers: thread t moves the float4s t + 256 i < 16 Dp (named registers: hipcc demotes a float4
+// array rewritten inside the loop to scratch, and a struct of them written through a reference likewise)
 template <int KIND>
-__device__ __forceinline__ void dpair_load(const DPairLane& p, const float* __restrict__ blk,
-                                           const float* __restrict__ nrm, float4& b0, float4& b1, float4& b2,
-                                           float4& b3, float& nb) {
+__device__ __forceinline__ void dpair_load(const DPairLane& p, const DPairBlock& blk, float4& b0, float4& b1,
+                                           float4& b2, float4& b3, float& nb) {
     // Unconditional: a float4 past the block's end re-reads its last one and is not stored (a load under a condition
     // makes every staging register a value the compiler carries, and spills, between the steps).
     // Addresses are the wave-uniform base plus this lane's byte offset, opaque (dpair_opaque's note).
-    const char* s = (const char*)blk;
+    const char* s = (const char*)blk.c;
     b0 = *(const float4*)(s + dpair_opaque(p.bo0));
     b1 = *(const float4*)(s + dpair_opaque(p.bo1));
     b2 = *(const float4*)(s + dpair_opaque(p.bo2));
     b3 = *(const float4*)(s + dpair_opaque(p.bo3));
-    if (KIND != NSVD_DOT_POLYNOMIAL) nb = *(const float*)((const char*)nrm + dpair_opaque(p.bon));
+    if (KIND != NSVD_DOT_POLYNOMIAL) nb = *(const float*)((const char*)blk.n + dpair_opaque(p.bon));
 }
 
 template <int KIND>
@@ -118,20 +119,35 @@ __device__ __forceinline__ void dpair_put(const DPairLane& p, float* __restrict_
     if (KIND != NSVD_DOT_POLYNOMIAL && p.t < 64) dst[64 * p.xld + p.t] = nb;
 }
 
-// One (x tile, chunk) step. ks: kernel chunk [x row][y row]; gs: g^T chunk [head][y row]; fs: f^T tile [head][x row];
-// xs, ys: x tile and y chunk, rows of xld floats, then their 64 norms. xvalid, yvalid: how many rows of the tile and of
-// the chunk exist (>= 64: all). gb*: the g^T chunk of THIS step in registers on entry, the one at gnext on exit.
+// this thread's four float4s of a g^T chunk / an f^T tile whose first row starts at `base` (wave-uniform): rows 16
+// apart (stride16 floats), the lane's byte offset `off` opaque and added last
+__device__ __forceinline__ PairQuad dpair_load_rows(const float* base, size_t stride16, size_t off) {
+    const size_t o = dpair_opaque(off);
+    PairQuad q;
+    q.a = *(const float4*)((const char*)base + o);
+    q.b = *(const float4*)((const char*)(base + stride16) + o);
+    q.c = *(const float4*)((const char*)(base + 2 * stride16) + o);
+    q.d = *(const float4*)((const char*)(base + 3 * stride16) + o);
+    return q;
+}
+
+// the LDS of a workgroup. ks: kernel chunk [x row][y row]; gs: g^T chunk [head][y row]; fs: f^T tile [head][x row];
+// xs, ys: x tile and y chunk, rows of xld floats, then their 64 norms
+struct DPairLds {
+    float *ks, *gs, *fs, *xs, *ys;
+};
+
+// One (x tile, chunk) step. xvalid, yvalid: how many rows of the tile and of the chunk exist (>= 64: all). gb: the g^T
+// chunk of THIS step in registers on entry, the one at gnext on exit.
 // FIRST: the first chunk of an x tile - the K g accumulator ax starts here (its value on entry is not read) and the
-// f^T tile at fc is staged. (ynext, ynnext): the y chunk of the NEXT step and its norms, staged here. stage_x (last
-// chunk of an x tile that has a successor): stage the x tile at (xnext, xnnext). Pointers are wave-uniform.
+// f^T tile at fc is staged. ynext: the y chunk of the NEXT step, staged here. stage_x (last chunk of an x tile that has
+// a successor): stage the x tile xnext. Pointers are wave-uniform.
 template <int KIND, bool FIRST>
-__device__ __forceinline__ void dpair_step(const DPairLane& p, float* __restrict__ ks, float* __restrict__ gs,
-                                           float* __restrict__ fs, float* __restrict__ xs, float* __restrict__ ys,
-                                           const DPairMap& mp, int xvalid, int yvalid, float4& gb0, float4& gb1,
-                                           float4& gb2, float4& gb3, const float* __restrict__ gnext,
-                                           const float* __restrict__ ynext, const float* __restrict__ ynnext,
-                                           const float* __restrict__ fc, bool stage_x, const float* __restrict__ xnext,
-                                           const float* __restrict__ xnnext, nsvd_f32x16& ax, nsvd_f32x16& ay) {
+__device__ __forceinline__ void pair_step(const DPairLane& p, const DPairLds& l, const DPairMap& mp, int xvalid,
+                                          int yvalid, PairQuad& gb, const float* __restrict__ gnext,
+                                          const DPairBlock& ynext, const float* __restrict__ fc, bool stage_x,
+                                          const DPairBlock& xnext, nsvd_f32x16& ax, nsvd_f32x16& ay) {
+    float *const ks = l.ks, *const gs = l.gs, *const fs = l.fs, *const xs = l.xs, *const ys = l.ys;
     // S^T: this wave forms y rows jb .. jb + 31 against x rows ib .. ib + 31; jb + (lane & 31) = ra, ib + (lane & 31) = rb
     const int jb = (p.wv & 1) * 32;
     const float* yr = ys + p.ra * p.xld + p.kq;
@@ -194,7 +210,7 @@ __device__ __forceinline__ void dpair_step(const DPairLane& p, float* __restrict
     // LDS writes
     float4 yb0, yb1, yb2, yb3;  // (no initial value: dpair_put reads exactly what dpair_load wrote)
     float ynb;
-    dpair_load<KIND>(p, ynext, ynnext, yb0, yb1, yb2, yb3, ynb);
+    dpair_load<KIND>(p, ynext, yb0, yb1, yb2, yb3, ynb);
     // every wave is done with the previous step's kernel chunk, g^T chunk and f^T tile, and with this step's x tile and
     // y chunk
     apply_lds_barrier();
@@ -202,57 +218,21 @@ __device__ __forceinline__ void dpair_step(const DPairLane& p, float* __restrict
 #pragma unroll
     for (int g = 0; g < 4; ++g)
         *(float4*)(la + 8 * g) = make_float4(kv[4 * g], kv[4 * g + 1], kv[4 * g + 2], kv[4 * g + 3]);
-    float* lb = gs + p.lr0 * LDT + p.lc;
-    *(float4*)(lb) = gb0;
-    *(float4*)(lb + 16 * LDT) = gb1;
-    *(float4*)(lb + 32 * LDT) = gb2;
-    *(float4*)(lb + 48 * LDT) = gb3;
-    const size_t go = dpair_opaque(p.go);
-    gb0 = *(const float4*)((const char*)gnext + go);
-    gb1 = *(const float4*)((const char*)(gnext + p.gr) + go);
-    gb2 = *(const float4*)((const char*)(gnext + 2 * p.gr) + go);
-    gb3 = *(const float4*)((const char*)(gnext + 3 * p.gr) + go);
+    const int so = p.lr0 * LDT + p.lc;
+    pair_put(gs + so, gb);
+    gb = dpair_load_rows(gnext, p.gr, p.go);
     dpair_put<KIND>(p, ys, yb0, yb1, yb2, yb3, ynb);
-    if (FIRST) {
-        // (requested here, once per x tile, not a step ahead)
-        const size_t fo = dpair_opaque(p.fo);
-        const float4 fb0 = *(const float4*)((const char*)fc + fo), fb1 = *(const float4*)((const char*)(fc + p.fr) + fo),
-                     fb2 = *(const float4*)((const char*)(fc + 2 * p.fr) + fo),
-                     fb3 = *(const float4*)((const char*)(fc + 3 * p.fr) + fo);
-        float* lf = fs + p.lr0 * LDT + p.lc;
-        *(float4*)(lf) = fb0;
-        *(float4*)(lf + 16 * LDT) = fb1;
-        *(float4*)(lf + 32 * LDT) = fb2;
-        *(float4*)(lf + 48 * LDT) = fb3;
-    }
+    if (FIRST) pair_put(fs + so, dpair_load_rows(fc, p.fr, p.fo));  // (requested here, once per x tile, not a step ahead)
     if (stage_x) {
         float4 x0, x1, x2, x3;
         float xn;
-        dpair_load<KIND>(p, xnext, xnnext, x0, x1, x2, x3, xn);
+        dpair_load<KIND>(p, xnext, x0, x1, x2, x3, xn);
         dpair_put<KIND>(p, xs, x0, x1, x2, x3, xn);
     }
     apply_lds_barrier();
-    // K g: rows = x rows (b128 along y), columns = heads of g^T;  K^T f: rows = y rows (b32 down the x rows of the same
-    // copy), columns = heads of f^T. MFMA e of group s contracts k = 8 s + e (lanes 0-31) and 8 s + 4 + e (lanes 32-63).
-    const float* pa = ks + p.ra * LDT + p.kq;
-    const float* pg = gs + p.rb * LDT + p.kq;
-    const float* pt = ks + p.kq * LDT + p.ra;
-    const float* pf = fs + p.rb * LDT + p.kq;
-#pragma unroll
-    for (int s = 0; s < KC / 8; ++s) {
-        const float4 av = *(const float4*)(pa + s * 8), gv = *(const float4*)(pg + s * 8);
-        const float4 fv = *(const float4*)(pf + s * 8);
-        const float t0 = pt[(s * 8 + 0) * LDT], t1 = pt[(s * 8 + 1) * LDT], t2 = pt[(s * 8 + 2) * LDT],
-                    t3 = pt[(s * 8 + 3) * LDT];
-        ax = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, gv.x, FIRST && s == 0 ? zero : ax, 0, 0, 0);
-        ay = __builtin_amdgcn_mfma_f32_32x32x2f32(t0, fv.x, ay, 0, 0, 0);
-        ax = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, gv.y, ax, 0, 0, 0);
-        ay = __builtin_amdgcn_mfma_f32_32x32x2f32(t1, fv.y, ay, 0, 0, 0);
-        ax = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, gv.z, ax, 0, 0, 0);
-        ay = __builtin_amdgcn_mfma_f32_32x32x2f32(t2, fv.z, ay, 0, 0, 0);
-        ax = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, gv.w, ax, 0, 0, 0);
-        ay = __builtin_amdgcn_mfma_f32_32x32x2f32(t3, fv.w, ay, 0, 0, 0);
-    }
+    // (one K g chain: the K^T f MFMAs run between, and the other workgroup of the CU fills the rest. ax is passed as
+    // BOTH K g accumulators on purpose: the two references name one object, which makes pair_contract's two chains one)
+    pair_contract<FIRST>(p, ks, gs, fs, ax, ax, ay);
 }
 
 // store (first == true) or add-and-store the wave's 32 x 32 tile whose first element is at `tile` (wave-uniform) in a
@@ -266,21 +246,18 @@ __device__ __forceinline__ void dpair_flush(float* __restrict__ tile, size_t Lp,
     }
 }
 
-// grid (RG, Lp / 64, CG). LDS: kernel chunk | g^T chunk | f^T tile (DPAIR_TILE floats each) | x tile | y chunk
+// grid (RG, Lp / 64, CG). LDS: kernel chunk | g^T chunk | f^T tile (PAIR_TILE floats each) | x tile | y chunk
 // ((64, Dp + 4) + 64 norms each).
+// The walk is pair_walk's, written out: here the K g chain is ONE, started by the inline zero of the tile's first step
+// (FIRST is a template argument, and a zeroed second chain would be added to the tile: 16 more registers and a sum
+// that turns -0 into +0), and the flushes go through wave-uniform addresses with one opaque lane offset.
 template <int KIND>
 __global__ void __launch_bounds__(256, 2) dot_pair_main_kernel(int B1, int B2, DPairWs w, DPairMap mp) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int Dp = w.Dp;
     DPairLane p;
     p.t = threadIdx.x;
-    p.lane = p.t & 63;
-    p.wv = __builtin_amdgcn_readfirstlane(p.t >> 6);  // (uniform by construction; tells the compiler so)
-    p.ra = (p.wv & 1) * 32 + (p.lane & 31);
-    p.rb = (p.wv >> 1) * 32 + (p.lane & 31);
-    p.kq = (p.lane >> 5) * 4;
-    p.lr0 = p.t >> 4;
-    p.lc = (p.t & 15) * 4;
+    static_cast<PairLane&>(p) = pair_lane(p.t);
     p.nq = Dp >> 3;
     p.xld = Dp + 4;
     p.nv = 16 * Dp;
@@ -290,11 +267,9 @@ __global__ void __launch_bounds__(256, 2) dot_pair_main_kernel(int B1, int B2, D
     p.so2 = ((p.t + 512) / Dq) * p.xld + ((p.t + 512) % Dq) * 4;
     p.so3 = ((p.t + 768) / Dq) * p.xld + ((p.t + 768) % Dq) * 4;
     const int cblk = 64 * p.xld + 64;  // a staged coordinate block and its norms
-    float *ks = lds, *gs = lds + DPAIR_TILE, *fs = lds + 2 * DPAIR_TILE, *xs = lds + 3 * DPAIR_TILE, *ys = xs + cblk;
+    const DPairLds l = {lds, lds + PAIR_TILE, lds + 2 * PAIR_TILE, lds + 3 * PAIR_TILE, lds + 3 * PAIR_TILE + cblk};
     const int rg = blockIdx.x, tl = blockIdx.y, cg = blockIdx.z;
-    const int xtiles = w.B1p / T, chunks = w.B2p / KC, slices = (chunks + PAIR_SLICE - 1) / PAIR_SLICE;
-    const int xt0 = (int)((long)xtiles * rg / w.RG), xt1 = (int)((long)xtiles * (rg + 1) / w.RG);
-    const int sl0 = (int)((long)slices * cg / w.CG), sl1 = (int)((long)slices * (cg + 1) / w.CG);
+    const PairRuns r = pair_runs(w.B1p, w.B2p, w.RG, w.CG);
     {
         const unsigned last = (unsigned)p.nv - 1u, u = (unsigned)p.t;
         p.bo0 = 16u * min(u, last);
@@ -315,11 +290,14 @@ __global__ void __launch_bounds__(256, 2) dot_pair_main_kernel(int B1, int B2, D
     float* px = w.partX + ((size_t)cg * w.B1p + rsub) * Lp + col0;
     float* py = w.partY + ((size_t)rg * w.B2p + rsub) * Lp + col0;
     const size_t cstep = (size_t)KC * Dp;  // floats of one padded (64, Dp) coordinate block
-    for (int sl = sl0; sl < sl1; ++sl) {
+    // x tile b: its padded coordinates and norms
+    const auto xblock = [&](int b) { return DPairBlock{w.xP + (size_t)b * cstep, w.xN + (size_t)b * T}; };
+    for (int sl = r.s0; sl < r.s1; ++sl) {
         const int cb = sl * PAIR_SLICE;
-        const int nc = min(PAIR_SLICE, chunks - cb);
-        const float* yc = w.yP + (size_t)cb * cstep;  // the slice's chunks: coordinates, norms
-        const float* ync = w.yN + (size_t)cb * KC;
+        const int nc = min(PAIR_SLICE, r.chunks - cb);
+        // chunk q of the slice: its padded coordinates and norms
+        const DPairBlock y0 = {w.yP + (size_t)cb * cstep, w.yN + (size_t)cb * KC};
+        const auto ychunk = [&](int q) { return DPairBlock{y0.c + q * cstep, y0.n + q * KC}; };
         // chunk q of the slice is followed by chunk (q + 1) % nc: the walk starts over for the next x tile
         const int q1 = 1 % nc, q2 = 2 % nc, q3 = 3 % nc, q4 = 4 % nc;
         // the first x tile of the run and the first y chunk (the steps below stage every later one between their barriers)
@@ -327,38 +305,33 @@ __global__ void __launch_bounds__(256, 2) dot_pair_main_kernel(int B1, int B2, D
         {
             float4 b0, b1, b2, b3;
             float nb;
-            dpair_load<KIND>(p, w.xP + (size_t)xt0 * cstep, w.xN + (size_t)xt0 * T, b0, b1, b2, b3, nb);
-            dpair_put<KIND>(p, xs, b0, b1, b2, b3, nb);
-            dpair_load<KIND>(p, yc, ync, b0, b1, b2, b3, nb);
-            dpair_put<KIND>(p, ys, b0, b1, b2, b3, nb);
+            dpair_load<KIND>(p, xblock(r.xt0), b0, b1, b2, b3, nb);
+            dpair_put<KIND>(p, l.xs, b0, b1, b2, b3, nb);
+            dpair_load<KIND>(p, y0, b0, b1, b2, b3, nb);
+            dpair_put<KIND>(p, l.ys, b0, b1, b2, b3, nb);
         }
         __syncthreads();
         nsvd_f32x16 ay0 = {0}, ay1 = {0}, ay2 = {0}, ay3 = {0};  // one chain each: the K g MFMAs run between
         const float* gc = gp + (size_t)cb * KC;
-        const size_t go = dpair_opaque(p.go);
-        float4 gb0 = *(const float4*)((const char*)gc + go), gb1 = *(const float4*)((const char*)(gc + p.gr) + go),
-               gb2 = *(const float4*)((const char*)(gc + 2 * p.gr) + go),
-               gb3 = *(const float4*)((const char*)(gc + 3 * p.gr) + go);
-        for (int xt = xt0; xt < xt1; ++xt) {
+        PairQuad gb = dpair_load_rows(gc, p.gr, p.go);
+        for (int xt = r.xt0; xt < r.xt1; ++xt) {
             const float* fc = fp + (size_t)xt * T;
             nsvd_f32x16 ax;  // one chain (the K^T f MFMAs run between), started by the tile's first step
-            const bool more = xt + 1 < xt1;
-            const float* xn = w.xP + (size_t)(xt + 1) * cstep;  // (read only where `more`)
-            const float* xnn = w.xN + (size_t)(xt + 1) * T;
+            const bool more = xt + 1 < r.xt1;
+            const DPairBlock xn = xblock(xt + 1);  // (read only where `more`)
             const int xv = B1 - xt * T, yv = B2 - cb * KC;
             // step q consumes chunk q (in LDS) and stages chunk (q + 1) % nc of y and of g^T
-            dpair_step<KIND, true>(p, ks, gs, fs, xs, ys, mp, xv, yv, gb0, gb1, gb2, gb3, gc + q1 * KC, yc + q1 * cstep,
-                             ync + q1 * KC, fc, more && nc == 1, xn, xnn, ax, ay0);
+            pair_step<KIND, true>(p, l, mp, xv, yv, gb, gc + q1 * KC, ychunk(q1), fc, more && nc == 1, xn, ax, ay0);
             if (nc > 1)
-                dpair_step<KIND, false>(p, ks, gs, fs, xs, ys, mp, xv, yv - KC, gb0, gb1, gb2, gb3, gc + q2 * KC,
-                                 yc + q2 * cstep, ync + q2 * KC, fc, more && nc == 2, xn, xnn, ax, ay1);
+                pair_step<KIND, false>(p, l, mp, xv, yv - KC, gb, gc + q2 * KC, ychunk(q2), fc, more && nc == 2, xn,
+                                       ax, ay1);
             if (nc > 2)
-                dpair_step<KIND, false>(p, ks, gs, fs, xs, ys, mp, xv, yv - 2 * KC, gb0, gb1, gb2, gb3, gc + q3 * KC,
-                                 yc + q3 * cstep, ync + q3 * KC, fc, more && nc == 3, xn, xnn, ax, ay2);
+                pair_step<KIND, false>(p, l, mp, xv, yv - 2 * KC, gb, gc + q3 * KC, ychunk(q3), fc, more && nc == 3,
+                                       xn, ax, ay2);
             if (nc > 3)
-                dpair_step<KIND, false>(p, ks, gs, fs, xs, ys, mp, xv, yv - 3 * KC, gb0, gb1, gb2, gb3, gc + q4 * KC,
-                                 yc + q4 * cstep, ync + q4 * KC, fc, more, xn, xnn, ax, ay3);
-            dpair_flush(px + (size_t)xt * T * Lp, Lp, po, ax, sl == sl0);
+                pair_step<KIND, false>(p, l, mp, xv, yv - 3 * KC, gb, gc + q4 * KC, ychunk(q4), fc, more, xn, ax,
+                                       ay3);
+            dpair_flush(px + (size_t)xt * T * Lp, Lp, po, ax, sl == r.s0);
         }
         float* pyc = py + (size_t)cb * KC * Lp;
         dpair_flush(pyc, Lp, po, ay0, true);
@@ -368,7 +341,7 @@ __global__ void __launch_bounds__(256, 2) dot_pair_main_kernel(int B1, int B2, D
     }
 }
 
-size_t dpair_lds_bytes(int Dp) { return (size_t)(3 * DPAIR_TILE + 2 * (64 * (Dp + 4) + 64)) * sizeof(float); }
+size_t dpair_lds_bytes(int Dp) { return (size_t)(3 * PAIR_TILE + 2 * (64 * (Dp + 4) + 64)) * sizeof(float); }
 
 }  // namespace
 
@@ -378,7 +351,8 @@ extern "C" size_t nsvd_dot_apply_pair_workspace_bytes(int B1, int B2, int D, int
 }
 
 extern "C" int nsvd_dot_apply_pair_partition(int B1, int B2, int D, int L, int* row_groups, int* col_slices) {
-    return apply_pair_partition(carve, B1, B2, D, L, row_groups, col_slices);
+    return pair_partition(apply_shape_ok(B1, B2, D, L), D <= APPLY_MAX_D, row_groups, col_slices,
+                          [&] { return carve(nullptr, B1, B2, D, L); });
 }
 
 extern "C" int nsvd_dot_apply_pair(const float* x, int B1, const float* y, int B2, int D, const float* g, const float* f,
@@ -424,9 +398,7 @@ extern "C" int nsvd_dot_apply_pair(const float* x, int B1, const float* y, int B
         dot_pair_main_kernel<NSVD_DOT_RELU_NTK><<<grid, 256, dpair_lds_bytes(w.Dp), s>>>(B1, B2, w, mp);
     nsvd_prof_end(s);
     NSVD_CHECK_LAUNCH();
-    const size_t n = (size_t)(B1 + (size_t)B2) * L;
-    apply_pair_reduce_kernel<><<<(unsigned)((n + 255) / 256), 256, 0, s>>>(
-        w.partX, w.CG, w.B1p, w.partY, w.RG, w.B2p, w.Lp, B1, B2, L, scale_g, scale_f, out_x, out_y);
+    pair_reduce_launch(w, B1, B2, L, scale_g, scale_f, out_x, out_y, s);
     NSVD_CHECK_LAUNCH();
     return 0;
 }

@@ -1,6 +1,6 @@
 // The no-atomics scatter of a batch into the index space, S^T[l][j] = sum_{k: cols_k = j} f[k][l], shared by the dense
 // products (kernel_apply.hip, kernel_apply_pair.hip). Internal linkage, a template so that a file's code object holds
-// it only when the file launches it (as the kernels of apply_common.h).
+// it only when the file launches it (as the kernels of apply_common.h and pair_common.h).
 #pragma once
 #include "nsvd_common.h"
 

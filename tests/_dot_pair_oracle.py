@@ -1,7 +1,7 @@
 """Float64 restatement of the two-sided dot-product kernel operator (nsvd_dot_apply_pair,
 kernel_ops.DotKernelOperator.apply_pair_raw): out_x = scale_g * K g and out_y = scale_f * K^T f with K from
 tests/_dot_oracle.py:dot_kernel_matrix, and the partition rule and workspace layout of csrc/dot_apply_pair.hip (the
-rule is csrc/pair_split.h's, restated by tests/_pair_oracle.py:pair_split: the slice length is unchanged)."""
+rule is csrc/pair_common.h's, restated by tests/_pair_oracle.py:pair_split: the slice length is unchanged)."""
 import torch
 
 from tests import _dot_oracle as DO

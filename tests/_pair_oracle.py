@@ -45,7 +45,7 @@ PAIR_SLICE, PAIR_MAX_GROUPS, PAIR_FILL = 4, 32, 512
 
 
 def pair_split(B1, B2, L):
-    """(row groups, column slices) - csrc/rbf_apply_pair.hip:pair_split: runs of 64-row x tiles and runs of slices of
+    """(row groups, column slices) - csrc/pair_common.h:pair_split: runs of 64-row x tiles and runs of slices of
     four 64-row y chunks; whichever side has more items per group is halved until head tiles * groups reach 512
     workgroups or both sides are at one item per group or at 32 groups"""
     xt, sl, lt = (B1 + 63) // 64, ((B2 + 63) // 64 + PAIR_SLICE - 1) // PAIR_SLICE, (L + 63) // 64

@@ -46,8 +46,7 @@ CASES = [(130, 67, 5, 400, 1), (300, 1000, 193, 70, 33), (1000, 300, 64, 64, 8),
          (130, 200, 401, 90, 5), (300, 130, 1024, 1024, 70)]
 
 
-@pytest.mark.parametrize("shape", CASES, ids=lambda s: "-".join(map(str, s)))
-def test_parity_with_float64(shape):
+def _check(shape):
     """relative L2 < 3e-5 on both outputs (tests/test_kernel_apply_gpu.py's bound for a float32 MFMA contraction over up
     to 10 000 terms), then again with rows[0] and cols[0] out of range: zero rows, no contribution"""
     from neural_svd_amd import hip_ops as H
@@ -71,6 +70,22 @@ def test_parity_with_float64(shape):
         if bad:
             assert not bool(ox[0].any()) and not bool(oy[0].any())
             assert not wx[0].any() and not wy[0].any()
+
+
+@pytest.mark.parametrize("shape", CASES, ids=lambda s: "-".join(map(str, s)))
+def test_parity_with_float64(shape):
+    _check(shape)
+
+
+@pytest.mark.parametrize("N2,tail", [(1030, 1), (1100, 2), (1160, 3), (1230, 4)])
+def test_every_length_of_the_last_slice(N2, tail):
+    """B1 = 130 (one row group requests the rows of a successor tile) and 16 + tail column chunks: five slices in four
+    column groups, so one group owns two slices (add-and-store flush), and its last slice has `tail` chunks; B2 = 200
+    column indices drawn with replacement"""
+    from neural_svd_amd import hip_ops as H
+    shape = (300, N2, 130, 200, 65)
+    assert H.kernel_apply_pair_partition(*shape) == (2, 4) and (N2 + 63) // 64 == 16 + tail
+    _check(shape)
 
 
 def test_agrees_with_two_kernel_apply_calls():

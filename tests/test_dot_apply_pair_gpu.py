@@ -110,6 +110,19 @@ def test_against_float64(B1, B2, D, L, variant):
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS))
+@pytest.mark.parametrize("B2,tail", [(1030, 1), (1100, 2), (1160, 3), (1230, 4)])
+def test_every_length_of_the_last_slice(B2, tail, variant):
+    """B1 = 130 (one row group stages a successor x tile) and 16 + tail y chunks: five slices in four column groups, so
+    one group owns two slices (add-and-store flush), and its last slice has `tail` chunks"""
+    from neural_svd_amd import hip_ops as H
+    B1, D, L = 130, 5, 65
+    assert H.dot_apply_pair_partition(B1, B2, D, L) == (2, 4) and (B2 + 63) // 64 == 16 + tail
+    kind, degree = VARIANTS[variant]
+    x, y, g, f = _inputs(B1, B2, D, L)
+    _check(x, y, g, f, kind, f32(1.0 / D), 1.0, degree, f"{variant} B1={B1} B2={B2} D={D} L={L}")
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
 def test_both_products_are_fed_the_same_kernel_value(variant):
     """B1 = B2 = 65, g = f = I, scales 1: every sum has one kernel value and exact zeros, so out_x = K and
     out_y = K^T bit for bit if both contractions were fed the same number; again with x is y."""

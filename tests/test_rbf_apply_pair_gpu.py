@@ -95,6 +95,18 @@ def test_against_float64(B1, B2, D, L, kind):
 
 
 @pytest.mark.parametrize("kind", list(KINDS))
+@pytest.mark.parametrize("B2,tail", [(1030, 1), (1100, 2), (1160, 3), (1230, 4)])
+def test_every_length_of_the_last_slice(B2, tail, kind):
+    """B1 = 130 (one row group stages a successor x tile) and 16 + tail y chunks: five slices in four column groups, so
+    one group owns two slices (add-and-store flush), and its last slice has `tail` chunks"""
+    from neural_svd_amd import hip_ops as H
+    B1, D, L = 130, 5, 65
+    assert H.rbf_apply_pair_partition(B1, B2, D, L) == (2, 4) and (B2 + 63) // 64 == 16 + tail
+    x, y, g, f = _inputs(B1, B2, D, L)
+    _check(x, y, g, f, KINDS[kind], float(D) ** 0.5, f"{kind} B1={B1} B2={B2} D={D} L={L}")
+
+
+@pytest.mark.parametrize("kind", list(KINDS))
 def test_same_tensors_on_both_sides(kind):
     """x is y and f is g (the same tensors): K is symmetric, so the two outputs are the same quantity - they agree
     within the bound of either against float64 (their sums run in different orders)."""
